@@ -20,10 +20,17 @@ What keeps the number honest:
   * every slice carries a few proofs with a flipped bit in t_x at fixed positions; after the timed region every
     verdict row must equal the expected 0/1 pattern of its slice -- a kernel that accepted (or rejected) everything
     fails the run.  No oracle is involved: the pattern follows from how the inputs were built;
-  * when K steps cannot reach steady state (K < streams, or the region lasts < 0.25 s) the K-step region is
-    repeated and the MEDIAN region time is reported (`regions` in the output); `steps` stays K.
+  * a plain run times exactly K steps in one region (`--repeat R`: R regions of K steps, the MEDIAN region time is
+    reported).  With `--full`, when K steps cannot reach steady state (K < streams, or the region lasts < 0.25 s)
+    the K-step region is repeated as many times as needed and the median is reported (`regions` in the output);
+    `steps` stays K.
 
-Prints ONE JSON line on rank 0 (fields per the driver contract, plus `roofline` and `cpu_baseline`).
+A plain run sets up, warms up, times the K steps and prints the headline line (with the `roofline` block read from
+the same timed steps).  `--full` adds everything else the bench measures: the `extra` figures (other entry points,
+configurations and call shapes, each in runs of its own) and the `cpu_baseline`.  `--dump-outputs DIR` writes what
+the timed path returned in its last step (the verdict row) as DIR/verdicts.npy (float32).
+
+Prints ONE JSON line on rank 0 (fields per the driver contract, plus `roofline`; with --full also `extra` and `cpu_baseline`).
 """
 import argparse
 import hashlib
@@ -37,8 +44,9 @@ import time
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 # The ROCm runtime maps HIP streams onto at most GPU_MAX_HW_QUEUES hardware queues (default 4); batches
-# issued on different streams only overlap on the device when they sit on different hardware queues.
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "16")
+# issued on different streams only overlap on the device when they sit on different hardware queues.  The pool refuses
+# lanes on fewer than 8, so the bench sets its own value whatever the environment it was started in says.
+os.environ["GPU_MAX_HW_QUEUES"] = "16"
 
 L_ORDER = 2 ** 252 + 27742317777372353535851937790883648493
 
@@ -70,14 +78,19 @@ def parse_args():
                     help="with --gpus N: ONE process, ONE pool over N devices (bpgpu_pool_create), host pointers in / verdicts out; N may exceed the "
                          "visible GPUs (shards then share devices: plumbing check)")
     ap.add_argument("--cfg5-only", type=int, default=0, help="run only the cfg5-shape MSM figure on this many streams and print it")
-    ap.add_argument("--repeat", type=int, default=0, help="timed regions of K steps each (0 = auto: 1 when K steps reach steady state, else enough for ~1 s); the median is reported")
+    ap.add_argument("--repeat", type=int, default=0, help="timed regions of K steps each, the median is reported (0 = 1 region; with --full, "
+                                                          "0 = auto: 1 when K steps reach steady state, else enough for ~1 s)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beyond the headline: the `extra` figures (runs of their own) and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="",
+                    help="write the verdict row of the last timed step as DIR/verdicts.npy (float32), for output-for-output comparison of two builds")
     ap.add_argument("--same-input", action="store_true", help="verify the SAME slice every step (the round-1 behaviour; for the cache A/B in DESIGN.md)")
     ap.add_argument("--rlc", action="store_true",
                     help="NOT the headline metric: time the batch-combination entry point bpgpu_rangeproof_verify_rlc_dev "
                          "(one combined identity check per batch, include/bpgpu.h) instead of the per-proof one")
     ap.add_argument("--cpu-threads", type=int, default=0, help="threads of the CPU baseline (0 = all cores)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extra", action="store_true", help="skip the informational figures (batch-combined mode, cfg3, cfg5 shape)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-extra", action="store_true", help="with --full: skip the informational figures (batch-combined mode, cfg3, cfg5 shape)")
     ap.add_argument("--no-events", action="store_true", help="no kernel start/stop events in the timed region (no roofline block): measures their perturbation")
     ap.add_argument("--events-all", action="store_true", help="attach kernel start/stop events on every stream (default: every 32nd when steps >= 8 x streams)")
     return ap.parse_args()
@@ -325,8 +338,8 @@ class RangeProofBench:
 def timed(b, K, warmup, fence, repeat, gather=None, events_all=False, no_events=False, agree=None):
     """context set-up, warmup, then R regions of K steps; returns dict(elapsed (median), regions, enqueue, kern, allv)"""
     if b.pool is not None:                                   # context set-up (not a warmup step): the first chain on a lane sizes its arena
-        b.region(max(K, 1), fence)                           # and caches the work decomposition -- one untimed region of the same shape
-        if K >= 8 * b.nstreams:
+        b.region(min(max(K, 1), 8 * b.nstreams), fence)      # and caches the work decomposition -- one untimed region of the same shape
+        if K >= 8 * b.nstreams:                              # (capped where it already reaches every lane many times over)
             b.region(b.nstreams * 8, fence)
     else:
         for k in range(min(b.nstreams, max(K, 1))):
@@ -813,13 +826,16 @@ def single_process_multi_device(a):
     for _ in range(max(1, min(a.warmup, 3))):
         pool.rangeproof_verify(fx.n, fx.m, planted, fx.proof_len, coms, fx.label, rng)
     regs = []
-    for _ in range(a.repeat or 5):
+    for _ in range(a.repeat or (5 if a.full else 1)):
         t0 = time.perf_counter()
         v = pool.rangeproof_verify(fx.n, fx.m, planted, fx.proof_len, coms, fx.label, rng)
         regs.append(time.perf_counter() - t0)
         if v != exp:
             raise SystemExit("verdicts differ from the planted pattern -- result invalid")
     dt = statistics.median(regs)
+    if a.dump_outputs and a.steps:   # the call's verdicts of the last step's proofs (batch x gpus)
+        import numpy as np
+        dump_outputs(a.dump_outputs, verdicts=np.frombuffer(v, dtype=np.uint8)[-batch * a.gpus:].reshape(1, -1))
     print(json.dumps({"metric": "64-bit rangeproof verifications/sec (batched)", "value": round(total / dt, 1), "unit": "verifications/s", "n_gpus": a.gpus,
                       "steps": a.steps, "warmup": a.warmup, "ms_per_step": round(dt / max(a.steps, 1) * 1e3, 4), "higher_is_better": True, "scaling": "weak",
                       "vs_baseline": None, "dtype": "u32 limbs, u64 accumulators", "data": "synthetic (bench_data/%s.bin), host memory in, verdicts out" % fx_name,
@@ -829,8 +845,20 @@ def single_process_multi_device(a):
     pool.close()
 
 
+def dump_outputs(d, **arrays):
+    """--dump-outputs: each array as d/<name>.npy in float32 (verdicts are small integers: exact)"""
+    import numpy as np
+    os.makedirs(d, exist_ok=True)
+    for name, x in arrays.items():
+        x = np.asarray(x).astype(np.float32)
+        assert x.nbytes <= 64 << 20
+        np.save(os.path.join(d, name + ".npy"), x)
+
+
 def main():
     a = parse_args()
+    if a.cfg5_only and a.dump_outputs:
+        raise SystemExit("--dump-outputs writes the headline path's outputs; --cfg5-only does not run it")
     if a.cfg5_only:
         print(json.dumps(bench_cfg5_shape(a, 0, 48, a.cfg5_only)))
         return
@@ -880,8 +908,13 @@ def main():
     # the final identity-check gather: one collective (RCCL; gloo on host copies when ranks share a GPU)
     gather = (lambda v: bpdist.gather_verdicts(v.cpu() if oversub else v, world)) if world > 1 else None
     agree = (lambda x: bpdist.max_over_ranks(x, world, None if oversub else dev)) if world > 1 else None
-    r = timed(b, a.steps, a.warmup, fence, a.repeat, gather, a.events_all, a.no_events, agree)
+    r = timed(b, a.steps, a.warmup, fence, a.repeat if a.full else (a.repeat or 1), gather, a.events_all, a.no_events, agree)
     elapsed = bpdist.max_over_ranks(r["elapsed"], world, None if oversub else dev)
+    if a.dump_outputs and a.steps:   # what the timed path handed back in its last step: that step's verdict row (every rank's, rank order)
+        row = b.d_verdicts[a.steps - 1]
+        last = bpdist.gather_verdicts(row.cpu() if oversub else row, world)
+        if rank == 0:
+            dump_outputs(a.dump_outputs, verdicts=last.cpu().numpy())
     if world > 1 and a.steps:     # every rank's verdict rows arrived and carry that rank's planted pattern
         allv = r["allv"]
         assert allv.shape[0] == world and bool(((allv == 0) | (allv == 1) | (allv == 5)).all().item())
@@ -913,7 +946,7 @@ def main():
     b.close()
 
     extra = {}
-    want_extra = world == 1 and not a.rlc and not a.no_extra and a.steps >= 8
+    want_extra = a.full and world == 1 and not a.rlc and not a.no_extra and a.steps >= 8
     long_run = a.steps >= 640
     if want_extra:
         # (0) the same steps WITHOUT the pool's coalescing (round-2 protocol): one launch chain per step on (context, stream) pairs
@@ -1111,7 +1144,7 @@ def main():
         }
         if extra:
             out["extra"] = extra
-        if world == 1 and not a.no_cpu_baseline:
+        if a.full and world == 1 and not a.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(b.fx, a.cpu_threads)
         print(json.dumps(out))
     if world > 1:

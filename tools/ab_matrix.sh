@@ -6,7 +6,7 @@ export GPU_MAX_HW_QUEUES=16
 mkdir -p $REPO/gpurun_out/r04
 OUT=$REPO/gpurun_out/r04/ab_matrix_${TAG:-generic}.txt
 cp bulletproofs_amd/csrc/libbpgpu.so /tmp/keep.so
-B="python $REPO/bench.py --no-cpu-baseline --no-extra"
+B="python $REPO/bench.py --full --no-cpu-baseline --no-extra"
 for r in $(seq ${ROUNDS:-3}); do
   for v in $LIBS; do
     cp ab/$v.so bulletproofs_amd/csrc/libbpgpu.so

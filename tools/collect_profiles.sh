@@ -7,7 +7,7 @@ REPO=${GRAFT_REPO_ROOT:-/root/repo}
 OUT=$REPO/gpurun_out/prof_$TAG
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-B="python $REPO/bench.py --no-cpu-baseline --no-extra"
+B="python $REPO/bench.py --full --no-cpu-baseline --no-extra"
 
 stats() {  # name, args...: kernel stats csv + the bench line measured under the profiler
   local name=$1; shift
@@ -35,8 +35,8 @@ python $REPO/tools/pool_rate.py burst steady host > $OUT/pool_rate.txt 2>&1
 bash $REPO/tools/ct_counters.sh > $OUT/prover_constant_time_counters.txt 2>&1
 $REPO/tools/microbench_gather > $OUT/microbench_gather.txt 2>&1
 # the two bench lines as the driver runs them (not under the profiler)
-python $REPO/bench.py > $OUT/bench_default.json 2> $OUT/bench_default.err
-python $REPO/bench.py --steps 20 --warmup 5 > $OUT/bench_steps20.json 2> $OUT/bench_steps20.err
+python $REPO/bench.py --full > $OUT/bench_default.json 2> $OUT/bench_default.err
+python $REPO/bench.py --full --steps 20 --warmup 5 > $OUT/bench_steps20.json 2> $OUT/bench_steps20.err
 fi
 
 # counters of the WIDE chain form (what the pool issues: >= 2048 proofs per launch chain -- one-lane Horner chain aside, window sums as

@@ -37,7 +37,7 @@ def run(name, cmd, timeout=900):
 
 def main():
     py = sys.executable
-    b = [py, os.path.join(ROOT, "bench.py"), "--no-cpu-baseline", "--no-extra", "--window-bits", "16"]
+    b = [py, os.path.join(ROOT, "bench.py"), "--full", "--no-cpu-baseline", "--no-extra", "--window-bits", "16"]
     try:
         q = open("/sys/fs/cgroup/cpu.max").read().split()
         print(json.dumps({"cgroup_cpu_max": q, "nproc": os.cpu_count()}), flush=True)
@@ -45,7 +45,7 @@ def main():
         pass
     run("N=1 plain", b + ["--steps", "20", "--warmup", "5"])
     run("N=1 torchrun", [py, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr", "127.0.0.1", "--master-port", "29711",
-                         os.path.join(ROOT, "bench.py"), "--no-cpu-baseline", "--no-extra", "--window-bits", "16", "--gpus", "1", "--steps", "20", "--warmup", "5"])
+                         os.path.join(ROOT, "bench.py"), "--full", "--no-cpu-baseline", "--no-extra", "--window-bits", "16", "--gpus", "1", "--steps", "20", "--warmup", "5"])
     run("8 ranks on device 0 (torchrun form, gloo gather)", b + ["--gpus", "8", "--steps", "20", "--warmup", "5"])
     run("8 shards on device 0 (single process, one pool, one host call per step)", b + ["--gpus", "8", "--single-process", "--steps", "8", "--streams", "8"])
     run("2 shards on device 0 (single process)", b + ["--gpus", "2", "--single-process", "--steps", "8", "--streams", "16"])

@@ -8,7 +8,7 @@ mkdir -p $OUT
 cd $REPO
 export GPU_MAX_HW_QUEUES=16
 cp bulletproofs_amd/csrc/libbpgpu.so /tmp/keep.so
-B="python $REPO/bench.py --no-cpu-baseline --no-extra"
+B="python $REPO/bench.py --full --no-cpu-baseline --no-extra"
 ALONE="$B --direct --streams 1 --batch 5120 --steps 48 --warmup 8 --opt horner_lanes=1"
 for r in 1 2 3; do
   for v in "$@"; do
