@@ -61,7 +61,7 @@ BP_HD void fe_add(fe &h, const fe &f, const fe &g) {
     for (int i = 0; i < 10; i++) h.v[i] = f.v[i] + g.v[i];
 }
 
-// weak reduction of 32-bit limbs: result is "reduced"
+// weak reduction of 32-bit limbs < 2^32 - 2^7 (a limb receives a carry < 2^7): result is "reduced"
 BP_HD void fe_carry(fe &h) {
     uint32_t c;
     c = h.v[0] >> 26; h.v[0] &= BP_M26; h.v[1] += c;

@@ -23,7 +23,8 @@
 namespace bp {
 
 // ---- radix-2^16 field arithmetic, one limb per lane ---------------------------------------------
-// "small" = every limb <= 2^16 + 2^15 (output of hw_mul / hw_norm); hw_mul accepts limbs <= 2^21.
+// "small" = every limb <= 2^16 + 38 * 2^10 (hw_norm's output bound; every hw_mul / hw_sub result passes through hw_norm);
+// hw_mul accepts limbs <= 2^21.
 
 // one carry round: limb k keeps its low 16 bits and receives the overflow of limb k-1
 // (limb 15's overflow re-enters limb 0 times 38).  In: limbs < 2^26.  Out: limbs <= 2^16 + 38 * 2^10.
@@ -204,11 +205,12 @@ WV_FN wu32 hw_invsqrt_raw(const wv_ctx &cx, const wu32 &t, const wu32 &k) {
     return hw_mul(cx, r, v3, k);
 }
 
-// one lane's 16 lazy limbs (<= 2^17) -> 10 x 25.5-bit field element (lazy, limb 0 may exceed 2^26 by 19+38*small)
+// one lane's 16 lazy limbs (<= 2^17) -> 10 x 25.5-bit field element (reduced: limb 0 < 2^26 + 19, the others canonical)
 BP_HD void hw_limbs_to_fe(fe &out, const uint32_t l[16]) {
     uint32_t t[16], carry = 0;
 #pragma unroll
     for (int i = 0; i < 16; i++) {
+        BP_ASSERT(l[i] <= 0x20000u);
         const uint32_t s = l[i] + carry;
         t[i] = s & 0xffffu;
         carry = s >> 16;
@@ -223,7 +225,8 @@ BP_HD void hw_limbs_to_fe(fe &out, const uint32_t l[16]) {
         t[i] = u & 0xffffu;
         carry = u >> 16;
     }
-    // (a second overflow is impossible: the value is now < 2^256)
+    // a second overflow (carry = 1) leaves t < 2 * 38: its 38 fits limb 0 without a further carry, and the value is now < 2^256
+    t[0] += 38u * carry;
     uint32_t w[8];
 #pragma unroll
     for (int i = 0; i < 8; i++) w[i] = t[2 * i] | (t[2 * i + 1] << 16);

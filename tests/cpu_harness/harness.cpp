@@ -19,6 +19,7 @@
 #include "../../bulletproofs_amd/csrc/ipp_prover.h"
 #include "../../bulletproofs_amd/csrc/rp_prover.h"
 #include "../../bulletproofs_amd/csrc/linear_prover.h"
+#include "limb_ops.h"
 #include <algorithm>
 #include <cstdio>
 #include <cstring>
@@ -1401,6 +1402,71 @@ int h_rp_prove(uint32_t W, uint32_t gens_capacity, uint32_t party_capacity, cons
             ts_out[(size_t)p * 208 + 200] = meta & 0xff; ts_out[(size_t)p * 208 + 201] = (meta >> 8) & 0xff; ts_out[(size_t)p * 208 + 202] = (meta >> 16) & 0xff;
         }
     for (uint32_t p = 0; p < nbatch; p++) if (status[p]) return -10;
+    return 0;
+}
+
+// ---- raw-limb entry points (limb_ops.h; tests/test_limb_bounds_on_cpu.py): n cases each, ok[i] = whether case i's output met the
+// bound its source states.  tests/gpu_prims/prims.hip exports the same calls as g_* for the device build.
+int h_fe_raw(int op, uint32_t n, const uint32_t *a, const uint32_t *b, uint32_t *out, uint8_t *ok) {
+    for (uint32_t i = 0; i < n; i++) ok[i] = lo::fe_raw(op, a + 10 * i, b + 10 * i, out + 10 * i);
+    return 0;
+}
+int h_fe_cols_raw(uint32_t n, const uint64_t *c, uint32_t *out, uint8_t *ok) {
+    for (uint32_t i = 0; i < n; i++) ok[i] = lo::fe_cols_raw(c + 10 * i, out + 10 * i);
+    return 0;
+}
+int h_limbs_to_fe_raw(uint32_t n, const uint32_t *l16, uint32_t *out, uint8_t *ok) {
+    for (uint32_t i = 0; i < n; i++) ok[i] = lo::limbs_to_fe_raw(l16 + 16 * i, out + 10 * i);
+    return 0;
+}
+int h_sc_raw(int op, uint32_t n, const uint32_t *a, const uint32_t *b, uint32_t *out, uint8_t *ok) {
+    for (uint32_t i = 0; i < n; i++) ok[i] = lo::sc_raw(op, a + 10 * i, b + 10 * i, out + 10 * i);
+    return 0;
+}
+int h_sc_cols_raw(uint32_t n, const uint64_t *c, uint32_t *out, uint8_t *ok) {
+    for (uint32_t i = 0; i < n; i++) ok[i] = lo::sc_cols_raw(c + 20 * i, out + 10 * i);
+    return 0;
+}
+int h_ge_raw(int op, uint32_t n, const uint32_t *p, const uint32_t *q, uint32_t *out, uint8_t *ok) {
+    for (uint32_t i = 0; i < n; i++) ok[i] = lo::ge_raw(op, p + 40 * i, q + 40 * i, out + 40 * i);
+    return 0;
+}
+// one lockstep wavefront per case: a, b, out = 64 lanes each; ok[i] = every output limb <= LO_HW_SMALL
+int h_hw_raw(int op, uint32_t n, const uint32_t *a, const uint32_t *b, int nsq, uint32_t *out, uint8_t *ok) {
+    wv_ctx cx{0};
+    for (uint32_t i = 0; i < n; i++) {
+        wu32 x, y;
+        for (int l = 0; l < 64; l++) { x.l[l] = a[64 * i + l]; y.l[l] = b[64 * i + l]; }
+        const wu32 r = lo::hw_raw(cx, op, x, y, nsq);
+        bool good = true;
+        for (int l = 0; l < 64; l++) { out[64 * i + l] = r.l[l]; good = good && r.l[l] <= LO_HW_SMALL; }
+        ok[i] = good;
+    }
+    return 0;
+}
+// the host copies of horner_wave.h's drivers (prims.hip runs their __device__ copies): points and results as (X, Y, Z, T), 40 limbs
+int h_drv_invsqrt(uint32_t n, const uint32_t *t8, uint32_t *out10) {
+    for (uint32_t i = 0; i < n; i++) hw_invsqrt_raw_fe((const uint16_t *)(t8 + 8 * i), nullptr, (fe *)(out10 + 10 * i));
+    return 0;
+}
+int h_drv_decode(uint32_t n, const uint32_t *w8, uint32_t *out40) {
+    for (uint32_t i = 0; i < n; i++) hw_ristretto_decode(*(ge_ext *)(out40 + 40 * i), w8 + 8 * i);
+    return 0;
+}
+int h_drv_point_shift(uint32_t n, const uint32_t *p40, int shift, uint32_t *out40) {
+    for (uint32_t i = 0; i < n; i++) hw_point_shift(*(const ge_ext *)(p40 + 40 * i), shift, (ge_ext *)(out40 + 40 * i));
+    return 0;
+}
+int h_drv_shift_table8(uint32_t n, const uint32_t *p40, int shift, uint32_t *out320) {
+    for (uint32_t i = 0; i < n; i++) hw_shift_table8(*(const ge_ext *)(p40 + 40 * i), shift, (ge_cached *)(out320 + 320 * i));
+    return 0;
+}
+int h_drv_horner(uint32_t n, const uint16_t *colq16, uint32_t *out40) {
+    for (uint32_t i = 0; i < n; i++) hw_horner_msm(colq16 + 4096 * (size_t)i, (ge_ext *)(out40 + 40 * i));
+    return 0;
+}
+int h_drv_horner8(uint32_t n, const uint16_t *colq8, uint32_t *out40) {
+    for (uint32_t i = 0; i < n; i++) hw_horner8_msm(colq8 + 2048 * (size_t)i, nullptr, (ge_ext *)(out40 + 40 * i));
     return 0;
 }
 }

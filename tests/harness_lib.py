@@ -11,7 +11,7 @@ _CSRC = os.path.join(os.path.dirname(_HERE), "bulletproofs_amd", "csrc")
 
 
 def build():
-    srcs = [os.path.join(_DIR, "harness.cpp")] + [os.path.join(_CSRC, f) for f in os.listdir(_CSRC) if f.endswith(".h")]
+    srcs = [os.path.join(_DIR, "harness.cpp"), os.path.join(_DIR, "limb_ops.h")] + [os.path.join(_CSRC, f) for f in os.listdir(_CSRC) if f.endswith(".h")]
     if (not os.path.exists(_SO)) or any(os.path.getmtime(s) > os.path.getmtime(_SO) for s in srcs):
         subprocess.check_call(["g++", "-O2", "-std=c++17", "-shared", "-fPIC", "-o", _SO,
                                os.path.join(_DIR, "harness.cpp")])
