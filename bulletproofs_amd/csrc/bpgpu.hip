@@ -3707,3 +3707,296 @@ extern "C" int bpgpu_rangeproof_prove_batch(bpgpu_ctx *c, size_t n, size_t m, si
     if (transcripts_out) memcpy(transcripts_out, h_out + sz_pr + sz_cm, nbatch * TS);
     return BPGPU_OK;
 }
+
+// ============================================================================
+// R1CS constraint-system proofs (r1cs.h): the circuit is a host object; its per-variable lists are uploaded to a device on
+// first use and kept there until bpgpu_r1cs_circuit_destroy
+// ============================================================================
+struct bpgpu_r1cs_circuit {
+    uint32_t m = 0, n1 = 0, n = 0, pn = 1, k = 0, two_phase = 0, nch = 0, Q = 0;
+    std::vector<uint32_t> col_ptr;   // 3n + m + 2 entries: columns L_i, R_i, O_i (3i, 3i+1, 3i+2), V_j (3n + j), ONE (3n + m)
+    std::vector<r1cs_ent> ents;
+    std::vector<uint32_t> lbl_off;   // nch + 1
+    std::vector<uint8_t> lbl;
+    size_t off_ents = 0, off_lbl_off = 0, off_lbl = 0, dev_bytes = 0;
+    std::mutex mu;
+    std::map<int, char *> dev;       // device ordinal -> [col_ptr][ents][lbl_off][lbl]
+};
+
+extern "C" int bpgpu_r1cs_circuit_create(size_t m, size_t n1, size_t n2, int two_phase, size_t n_challenges, const uint8_t *labels,
+                                         const uint32_t *label_lens, size_t n_constraints, const uint32_t *row_ptr, size_t n_terms,
+                                         const uint8_t *term_kind, const uint32_t *term_index, const uint32_t *term_challenge,
+                                         const uint32_t *term_power, const uint8_t *term_coeff, bpgpu_r1cs_circuit **out) {
+    if (!out) return BPGPU_ERR_INVALID_ARG;
+    *out = nullptr;
+    const size_t n = n1 + n2;
+    if (m > BPGPU_R1CS_MAX_VARS || n1 > BPGPU_R1CS_MAX_VARS || n2 > BPGPU_R1CS_MAX_VARS || n > BPGPU_R1CS_MAX_VARS ||
+        n_constraints > BPGPU_R1CS_MAX_CONSTRAINTS || n_terms > BPGPU_R1CS_MAX_TERMS || n_challenges > BPGPU_R1CS_MAX_CHALLENGES)
+        return BPGPU_ERR_INVALID_ARG;
+    if (two_phase != 0 && two_phase != 1) return BPGPU_ERR_INVALID_ARG;
+    if (!two_phase && (n2 != 0 || n_challenges != 0)) return BPGPU_ERR_INVALID_ARG;   // no randomized callback: no phase 2
+    if (n_challenges && (!label_lens || !labels)) return BPGPU_ERR_INVALID_ARG;
+    if (!row_ptr || (n_terms && (!term_kind || !term_index || !term_challenge || !term_power || !term_coeff))) return BPGPU_ERR_INVALID_ARG;
+    if (row_ptr[0] != 0 || row_ptr[n_constraints] != n_terms) return BPGPU_ERR_INVALID_ARG;
+    for (size_t q = 0; q < n_constraints; q++)
+        if (row_ptr[q + 1] < row_ptr[q]) return BPGPU_ERR_INVALID_ARG;
+    auto *ci = new bpgpu_r1cs_circuit();
+    ci->m = (uint32_t)m, ci->n1 = (uint32_t)n1, ci->n = (uint32_t)n, ci->two_phase = (uint32_t)two_phase, ci->nch = (uint32_t)n_challenges;
+    ci->Q = (uint32_t)n_constraints;
+    while (ci->pn < n) ci->pn <<= 1, ci->k++;   // next_power_of_two (0 -> 1)
+    ci->lbl_off.push_back(0);
+    for (size_t j = 0; j < n_challenges; j++) {
+        if (label_lens[j] > BPGPU_R1CS_MAX_LABEL) {
+            delete ci;
+            return BPGPU_ERR_INVALID_ARG;
+        }
+        ci->lbl_off.push_back(ci->lbl_off.back() + label_lens[j]);
+    }
+    ci->lbl.assign(labels ? labels : (const uint8_t *)"", (labels ? labels : (const uint8_t *)"") + ci->lbl_off.back());
+    const size_t ncols = 3 * n + m + 1;
+    std::vector<uint32_t> cnt(ncols + 1, 0), col(n_terms);
+    for (size_t q = 0; q < n_constraints; q++)
+        for (uint32_t t = row_ptr[q]; t < row_ptr[q + 1]; t++) {
+            const uint32_t kind = term_kind[t], idx = term_index[t], ch = term_challenge[t], pw = term_power[t];
+            bool ok = true;
+            switch (kind) {
+            case BPGPU_R1CS_L: case BPGPU_R1CS_R: case BPGPU_R1CS_O: ok = idx < n; col[t] = (uint32_t)(3 * idx + kind); break;
+            case BPGPU_R1CS_V: ok = idx < m; col[t] = (uint32_t)(3 * n + idx); break;
+            case BPGPU_R1CS_ONE: ok = idx == 0; col[t] = (uint32_t)(3 * n + m); break;
+            default: ok = false;
+            }
+            if (ch == BPGPU_R1CS_NO_CHALLENGE) ok = ok && pw == 0;
+            else ok = ok && ch < n_challenges && pw >= 1 && pw <= BPGPU_R1CS_MAX_POWER;
+            sc cf;
+            memcpy(cf.v, term_coeff + (size_t)t * 32, 32);
+            ok = ok && sc_is_canonical_sc(cf);
+            if (!ok) {
+                delete ci;
+                return BPGPU_ERR_INVALID_ARG;
+            }
+            cnt[col[t] + 1]++;
+        }
+    for (size_t i = 0; i < ncols; i++) cnt[i + 1] += cnt[i];
+    ci->col_ptr = cnt;
+    ci->ents.resize(n_terms);
+    std::vector<uint32_t> fill(cnt.begin(), cnt.end() - 1);
+    for (size_t q = 0; q < n_constraints; q++)   // constraint order within each list: the reference's summation order
+        for (uint32_t t = row_ptr[q]; t < row_ptr[q + 1]; t++) {
+            r1cs_ent &e = ci->ents[fill[col[t]]++];
+            e.q = (uint32_t)q;
+            e.chal = term_challenge[t] == BPGPU_R1CS_NO_CHALLENGE ? R1_NO_CHAL : (term_challenge[t] | (term_power[t] << 16));
+            sc cf;
+            memcpy(cf.v, term_coeff + (size_t)t * 32, 32);
+            if (term_kind[t] == BPGPU_R1CS_V || term_kind[t] == BPGPU_R1CS_ONE) sc_neg(cf, cf);   // wV -= .., wc -= .. (verifier.rs:286-292)
+            sc28 cm;
+            sc_to_mont28(cm, cf);
+            memcpy(e.coeff, cm.v, 40);
+        }
+    ci->off_ents = align_up(ci->col_ptr.size() * 4);
+    ci->off_lbl_off = ci->off_ents + align_up(ci->ents.size() * sizeof(r1cs_ent));
+    ci->off_lbl = ci->off_lbl_off + align_up(ci->lbl_off.size() * 4);
+    ci->dev_bytes = ci->off_lbl + align_up(ci->lbl.size() + 1);
+    *out = ci;
+    return BPGPU_OK;
+}
+
+extern "C" void bpgpu_r1cs_circuit_destroy(bpgpu_r1cs_circuit *ci) {
+    if (!ci) return;
+    for (auto &kv : ci->dev) {
+        (void)hipSetDevice(kv.first);
+        (void)hipFree(kv.second);
+    }
+    delete ci;
+}
+
+extern "C" int bpgpu_r1cs_circuit_shape(const bpgpu_r1cs_circuit *ci, size_t *padded_n, size_t *n_unique) {
+    if (!ci) return BPGPU_ERR_INVALID_ARG;
+    if (padded_n) *padded_n = ci->pn;
+    if (n_unique) *n_unique = 11 + ci->m + 2 * ci->k;
+    return BPGPU_OK;
+}
+
+// the circuit's lists on c's device (uploaded once per device; the caller holds c->mu and has set the device)
+static int r1cs_circuit_on(bpgpu_ctx *c, const bpgpu_r1cs_circuit *cci, char **d_out) {
+    auto *ci = const_cast<bpgpu_r1cs_circuit *>(cci);
+    std::lock_guard<std::mutex> lk(ci->mu);
+    auto it = ci->dev.find(c->device);
+    if (it != ci->dev.end()) {
+        *d_out = it->second;
+        return BPGPU_OK;
+    }
+    std::vector<char> img(ci->dev_bytes, 0);
+    memcpy(img.data(), ci->col_ptr.data(), ci->col_ptr.size() * 4);
+    if (!ci->ents.empty()) memcpy(img.data() + ci->off_ents, ci->ents.data(), ci->ents.size() * sizeof(r1cs_ent));
+    memcpy(img.data() + ci->off_lbl_off, ci->lbl_off.data(), ci->lbl_off.size() * 4);
+    if (!ci->lbl.empty()) memcpy(img.data() + ci->off_lbl, ci->lbl.data(), ci->lbl.size());
+    char *d = nullptr;
+    if (hipMalloc((void **)&d, ci->dev_bytes) != hipSuccess) return fail(c, BPGPU_ERR_HIP, "out of device memory (circuit)");
+    if (hipMemcpy(d, img.data(), ci->dev_bytes, hipMemcpyHostToDevice) != hipSuccess) {
+        (void)hipFree(d);
+        return fail(c, BPGPU_ERR_HIP, "circuit upload failed");
+    }
+    ci->dev[c->device] = d;
+    *d_out = d;
+    return BPGPU_OK;
+}
+
+static int r1cs_verify_dev_locked(bpgpu_ctx *c, const bpgpu_r1cs_circuit *ci, size_t nbatch, const void *d_proofs, size_t proof_stride,
+                                  const void *d_lens, const void *d_coms, const uint8_t *shared_ts, const void *d_ts, const void *d_rng32,
+                                  void *d_verdict, void *d_msm_out, void *d_ts_out, hipStream_t s) {
+    if (shared_ts && !ts_state_ok(shared_ts)) return fail(c, BPGPU_ERR_INVALID_ARG, "malformed transcript state");
+    if (!c->d_table) return fail(c, BPGPU_ERR_NO_GENS, "generators not loaded");
+    if (proof_stride > 0xffffffu || nbatch > 0x7fffffffu / 64) return fail(c, BPGPU_ERR_INVALID_ARG, "batch too large");
+    char *dc = nullptr;
+    int rc = r1cs_circuit_on(c, ci, &dc);
+    if (rc) return rc;
+    r1cs_shape sh{};
+    sh.m = ci->m, sh.n1 = ci->n1, sh.n = ci->n, sh.pn = ci->pn, sh.k = ci->k;
+    sh.two_phase = ci->two_phase, sh.nch = ci->nch, sh.Q = ci->Q;
+    sh.nzhi = (ci->Q >> 6) + 1;
+    sh.nyhi = ((ci->pn - 1) >> 6) + 1;
+    sh.f_zlo = R1F_FIXED;
+    sh.f_zhi = sh.f_zlo + 64;
+    sh.f_ylo = sh.f_zhi + sh.nzhi;
+    sh.f_yhi = sh.f_ylo + 64;
+    sh.f_ch = sh.f_yhi + sh.nyhi;
+    sh.f_tab = sh.f_ch + sh.nch;
+    sh.nfields = sh.f_tab + 2 * sh.k;
+    sh.U = 11 + sh.m + 2 * sh.k;
+    sh.proof_stride = (uint32_t)proof_stride;
+    sh.nproofs = (uint32_t)nbatch;
+    {
+        const uint32_t n_one = ci->col_ptr[3 * ci->n + ci->m + 1] - ci->col_ptr[3 * ci->n + ci->m];
+        sh.one_chunks = n_one ? (n_one + R1_ONE_CHUNK - 1) / R1_ONE_CHUNK : 1;
+    }
+    sh.gens_short = ci->pn > c->gens_capacity ? 1u : 0u;   // verifier.rs:341-343 (a single-party proof: party 0)
+    const uint64_t ncol = (uint64_t)sh.pn + sh.m + sh.one_chunks;
+    if (ncol * nbatch > 0x7fffffffull || (uint64_t)nbatch * (2 * sh.pn + 2 + sh.U) > 0x7fffffffull / 64)
+        return fail(c, BPGPU_ERR_INVALID_ARG, "batch too large for this circuit");
+    if (!d_rng32) {
+        sh.seeded = 1;
+        if (c->test_seed_set) memcpy(sh.seed, c->test_seed, 32);
+        else if (!bp::fast_random((uint8_t *)sh.seed, 32)) return fail(c, BPGPU_ERR_HIP, "getrandom failed");
+    }
+    const size_t ngen = 2 * (size_t)sh.pn + 2;
+    const size_t sz_f = align_up((size_t)sh.nfields * nbatch * 40), sz_g = align_up(nbatch * ngen * 32), sz_u = align_up(nbatch * sh.U * 32),
+                 sz_d = align_up(((size_t)sh.pn + sh.one_chunks) * nbatch * 32), sz_st = align_up(nbatch * 4), sz_b = align_up(nbatch + 64), sz_o = align_up(nbatch * 32 + 64);
+    rc = ipp_reserve(c, sz_g + 2 * sz_u + sz_st + sz_f + sz_d + sz_b + sz_o);
+    if (rc) return rc;
+    char *d_gen = c->ipp_buf, *d_usc = d_gen + sz_g, *d_upt = d_usc + sz_u, *d_stat = d_upt + sz_u, *d_f = d_stat + sz_st, *d_dt = d_f + sz_f,
+         *d_mst = d_dt + sz_d, *d_out = d_mst + sz_b;
+    HIPCHK(c, hipMemsetAsync(d_gen, 0, sz_g + 2 * sz_u + sz_st, s));   // generator rows, per-proof rows, status
+    rp_strobe_init init;
+    memset(&init, 0, sizeof init);
+    if (shared_ts) strobe_init_from_state(init, shared_ts);
+    const uint32_t nb32 = (uint32_t)nbatch;
+    LAUNCH(c, s, "r1cs_front", k_r1cs_front, (nb32 + RP_BLOCK - 1) / RP_BLOCK, RP_BLOCK, sh, init, (const uint8_t *)d_proofs, (const uint32_t *)d_lens,
+           (const uint8_t *)d_coms, shared_ts ? (const uint32_t *)nullptr : (const uint32_t *)d_ts, (const uint8_t *)d_rng32,
+           (const uint32_t *)(dc + ci->off_lbl_off), (const uint8_t *)(dc + ci->off_lbl), (uint32_t *)d_f, (uint32_t *)d_usc, (uint32_t *)d_upt,
+           (uint32_t *)d_ts_out, (uint32_t *)d_stat);
+    if (sh.gens_short) {   // every proof stopped in launch 1 (or earlier): nothing to multiply
+        HIPCHK(c, hipMemsetAsync(d_mst, 0, sz_b + sz_o, s));
+    } else {
+        const uint32_t nt = (uint32_t)(ncol * nbatch);
+        LAUNCH(c, s, "r1cs_flatten", k_r1cs_flatten, (nt + 63) / 64, 64, nt, sh, (const uint32_t *)dc, (const r1cs_ent *)(dc + ci->off_ents),
+               (const uint32_t *)d_stat, (uint32_t *)d_f, (uint32_t *)d_gen, (uint32_t *)d_usc, (uint32_t *)d_dt);
+        LAUNCH(c, s, "r1cs_finish", k_r1cs_finish, nb32, 64, sh, (const uint32_t *)d_stat, (const uint32_t *)d_dt, (const uint32_t *)d_f, (uint32_t *)d_gen);
+        rc = msm_shared_dev_locked(c, sh.pn, 1, nbatch, sh.U, d_gen, d_usc, d_upt, d_out, d_mst, nullptr, s);
+        if (rc) return rc;
+    }
+    LAUNCH(c, s, "r1cs_verdict", k_ipp_verdict, (nb32 + 63) / 64, 64, nb32, (const uint32_t *)d_stat, (const uint8_t *)d_mst, (const uint32_t *)d_out,
+           (uint8_t *)d_verdict);
+    if (d_msm_out) HIPCHK(c, hipMemcpyAsync(d_msm_out, d_out, nbatch * 32, hipMemcpyDeviceToDevice, s));
+    HIPCHK(c, hipGetLastError());
+    return BPGPU_OK;
+}
+
+extern "C" int bpgpu_r1cs_verify_batch_ts_dev(bpgpu_ctx *c, const bpgpu_r1cs_circuit *circuit, size_t nbatch, const void *d_proofs, size_t proof_stride,
+                                              const void *d_proof_lens, const void *d_commitments, const uint8_t *shared_transcript,
+                                              const void *d_transcripts, const void *d_rng32, void *d_verdict, void *d_msm_out,
+                                              void *d_transcripts_out, void *stream) {
+    if (!c || !circuit) return BPGPU_ERR_INVALID_ARG;
+    if (nbatch == 0) return BPGPU_OK;
+    if (!d_proofs || !d_proof_lens || !d_verdict || (circuit->m && !d_commitments) || (!shared_transcript == !d_transcripts)) return BPGPU_ERR_INVALID_ARG;
+    if (((uintptr_t)d_proof_lens | (uintptr_t)d_transcripts | (uintptr_t)d_transcripts_out) & 3)
+        return fail(c, BPGPU_ERR_INVALID_ARG, "device buffers must be 4-byte aligned");
+    std::lock_guard<std::mutex> lk(c->mu);
+    HIPCHK(c, hipSetDevice(c->device));
+    hipStream_t s = stream ? (hipStream_t)stream : c->stream;
+    int rc = ctx_enter(c, s);
+    if (rc) return rc;
+    rc = r1cs_verify_dev_locked(c, circuit, nbatch, d_proofs, proof_stride, d_proof_lens, d_commitments, shared_transcript, d_transcripts, d_rng32,
+                                d_verdict, d_msm_out, d_transcripts_out, s);
+    const int rc2 = ctx_leave(c, s);
+    return rc ? rc : rc2;
+}
+
+extern "C" int bpgpu_r1cs_verify_batch_ts(bpgpu_ctx *c, const bpgpu_r1cs_circuit *circuit, size_t nbatch, const uint8_t *proofs, size_t proof_stride,
+                                          const uint32_t *proof_lens, const uint8_t *commitments, const uint8_t *transcripts, size_t transcript_stride,
+                                          const uint8_t *rng32, uint8_t *verdict, uint8_t *msm_out, uint8_t *transcripts_out) {
+    if (!c || !circuit) return BPGPU_ERR_INVALID_ARG;
+    if (nbatch == 0) return BPGPU_OK;
+    if (!proofs || !proof_lens || !verdict || !transcripts || (circuit->m && !commitments)) return BPGPU_ERR_INVALID_ARG;
+    if (transcript_stride != 0 && transcript_stride != BPGPU_TRANSCRIPT_BYTES)
+        return fail(c, BPGPU_ERR_INVALID_ARG, "transcript_stride neither 0 nor BPGPU_TRANSCRIPT_BYTES");
+    const bool per_proof = transcript_stride != 0;
+    for (size_t b = 0; b < (per_proof ? nbatch : 1); b++)
+        if (!ts_state_ok(transcripts + b * BPGPU_TRANSCRIPT_BYTES)) return fail(c, BPGPU_ERR_INVALID_ARG, "malformed transcript state %zu", b);
+    const size_t TS = BPGPU_TRANSCRIPT_BYTES, m = circuit->m;
+    std::lock_guard<std::mutex> lk(c->mu);
+    HIPCHK(c, hipSetDevice(c->device));
+    const size_t sz_pr = align_up(nbatch * proof_stride + 64), sz_l = align_up(nbatch * 4), sz_c = align_up(nbatch * m * 32 + 64),
+                 sz_t = per_proof ? align_up(nbatch * TS) : 0, sz_r = rng32 ? align_up(nbatch * 32) : 0;
+    const size_t sz_in = sz_pr + sz_l + sz_c + sz_t + sz_r, sz_v = align_up(nbatch), sz_o = align_up(nbatch * 32), sz_to = transcripts_out ? align_up(nbatch * TS) : 0;
+    hipStream_t s = c->stream;
+    int rc = ctx_enter(c, s);
+    if (rc) return rc;
+    rc = io_reserve(c, sz_in + sz_v + sz_o + sz_to);
+    if (rc) return rc;
+    char *h = nullptr;
+    rc = pin_alloc(c, s, sz_in + sz_v + sz_o + sz_to, &h);
+    if (rc) return rc;
+    char *d = c->io_dev;
+    char *d_pr = d, *d_l = d_pr + sz_pr, *d_c = d_l + sz_l, *d_t = d_c + sz_c, *d_r = d_t + sz_t, *d_v = d + sz_in, *d_o = d_v + sz_v, *d_to = d_o + sz_o;
+    memcpy(h, proofs, nbatch * proof_stride);
+    memcpy(h + sz_pr, proof_lens, nbatch * 4);
+    if (m) memcpy(h + sz_pr + sz_l, commitments, nbatch * m * 32);
+    if (per_proof) memcpy(h + sz_pr + sz_l + sz_c, transcripts, nbatch * TS);
+    if (rng32) memcpy(h + sz_pr + sz_l + sz_c + sz_t, rng32, nbatch * 32);
+    HIPCHK(c, hipMemcpyAsync(d, h, sz_in, hipMemcpyHostToDevice, s));
+    rc = r1cs_verify_dev_locked(c, circuit, nbatch, d_pr, proof_stride, d_l, d_c, per_proof ? nullptr : transcripts, per_proof ? d_t : nullptr,
+                                rng32 ? d_r : nullptr, d_v, d_o, transcripts_out ? d_to : nullptr, s);
+    char *h_out = h + sz_in;
+    if (!rc && hipMemcpyAsync(h_out, d_v, sz_v + sz_o + sz_to, hipMemcpyDeviceToHost, s) != hipSuccess) rc = fail(c, BPGPU_ERR_HIP, "D2H copy failed");
+    const int rc2 = ctx_leave(c, s), rc3 = host_wait(c, s);
+    if (rc || rc2 || rc3) return rc ? rc : (rc2 ? rc2 : rc3);
+    memcpy(verdict, h_out, nbatch);
+    if (msm_out) memcpy(msm_out, h_out + sz_v, nbatch * 32);
+    if (transcripts_out) memcpy(transcripts_out, h_out + sz_v + sz_o, nbatch * TS);
+    return BPGPU_OK;
+}
+
+// the pool form: the whole call on the next device's context (pool.hip)
+extern "C" int bpgpu_internal_pool_run_on_context(bpgpu_pool *p, size_t nbatch, uint8_t *verdict, int (*run)(bpgpu_ctx *, void *), void *arg);
+namespace {
+struct r1cs_call {
+    const bpgpu_r1cs_circuit *circuit;
+    size_t nbatch, proof_stride, transcript_stride;
+    const uint8_t *proofs, *commitments, *transcripts, *rng32;
+    const uint32_t *proof_lens;
+    uint8_t *verdict, *msm_out, *transcripts_out;
+};
+int r1cs_call_run(bpgpu_ctx *c, void *arg) {
+    const r1cs_call *a = (const r1cs_call *)arg;
+    return bpgpu_r1cs_verify_batch_ts(c, a->circuit, a->nbatch, a->proofs, a->proof_stride, a->proof_lens, a->commitments, a->transcripts,
+                                      a->transcript_stride, a->rng32, a->verdict, a->msm_out, a->transcripts_out);
+}
+}  // namespace
+
+extern "C" int bpgpu_pool_r1cs_verify_ts(bpgpu_pool *pool, const bpgpu_r1cs_circuit *circuit, size_t nbatch, const uint8_t *proofs, size_t proof_stride,
+                                         const uint32_t *proof_lens, const uint8_t *commitments, const uint8_t *transcripts, size_t transcript_stride,
+                                         const uint8_t *rng32, uint8_t *verdict, uint8_t *msm_out, uint8_t *transcripts_out) {
+    if (!pool || !circuit) return BPGPU_ERR_INVALID_ARG;
+    r1cs_call a{circuit, nbatch, proof_stride, transcript_stride, proofs, commitments, transcripts, rng32, proof_lens, verdict, msm_out, transcripts_out};
+    return bpgpu_internal_pool_run_on_context(pool, nbatch, verdict, r1cs_call_run, &a);
+}

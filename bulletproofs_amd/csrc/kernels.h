@@ -17,6 +17,7 @@
 #include "ipp_prover.h"
 #include "rp_prover.h"
 #include "linear_prover.h"
+#include "r1cs.h"
 
 #define BP_BLOCK 64   // one wavefront per workgroup: under contention a CU rarely has room for four waves of one group at once (256: -8% at 48 streams)
 #define FB_BLOCK 64
@@ -73,6 +74,9 @@ __global__ void k_ipp_vs_s(uint32_t nthreads, ipp_shape sh, const uint32_t *tab,
 __global__ void k_ipp_verdict(uint32_t n, const uint32_t *status, const uint8_t *msm_status, const uint32_t *msm_out, uint8_t *verdict);
 __global__ void k_aud_prepare(aud_shape sh, const uint32_t *party, const uint8_t *shares, const uint8_t *bit_commitments, const uint8_t *poly_commitments, const uint8_t *challenges, const uint32_t *gens, uint32_t *scalars, uint32_t *points, uint32_t *status);
 __global__ void k_aud_verdict(uint32_t n, const uint32_t *status, const uint8_t *msm_status, const uint32_t *msm_out, uint8_t *verdict);
+__global__ void k_r1cs_front(r1cs_shape sh, rp_strobe_init init, const uint8_t *proofs, const uint32_t *proof_lens, const uint8_t *commitments, const uint32_t *ts_in, const uint8_t *rng32, const uint32_t *lbl_off, const uint8_t *lbl, uint32_t *fields, uint32_t *uniq_sc, uint32_t *uniq_pt, uint32_t *ts_out, uint32_t *status);
+__global__ void k_r1cs_flatten(uint32_t nthreads, r1cs_shape sh, const uint32_t *col_ptr, const r1cs_ent *ents, const uint32_t *status, uint32_t *fields, uint32_t *gen_sc, uint32_t *uniq_sc, uint32_t *dterm);
+__global__ void k_r1cs_finish(r1cs_shape sh, const uint32_t *status, const uint32_t *dterm, const uint32_t *fields, uint32_t *gen_sc);
 __global__ void k_lin_prepare(lin_shape sh, rp_strobe_init init, const uint8_t *proofs, const uint8_t *C, const uint8_t *bvec, const uint8_t *G, const uint8_t *F, const uint8_t *B, uint32_t *scalars, uint32_t *points, uint32_t *status, uint32_t *ts_out, uint32_t *gen_sc);
 __global__ void k_from_uniform(uint32_t n, const uint32_t *uniform, uint32_t *out);
 

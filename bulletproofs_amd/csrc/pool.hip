@@ -2175,6 +2175,23 @@ int bpgpu_pool_ipp_verify(bpgpu_pool *p, size_t n, size_t nbatch, const uint8_t 
     return comb_run_placed(p, &r, base, src, in_sz, nullptr, d0, 256);
 }
 
+// a whole call on the next device's context, blocking (no combining across calls): the pool form of entry points that
+// bpgpu.hip defines on a context (bpgpu_pool_r1cs_verify_ts).  `run` gets the context; verdict bytes are marked undecided
+// until it succeeds.
+extern "C" int bpgpu_internal_pool_run_on_context(bpgpu_pool *p, size_t nbatch, uint8_t *verdict, int (*run)(bpgpu_ctx *, void *), void *arg) {
+    if (!p || p->devs.empty() || !run) return BPGPU_ERR_INVALID_ARG;
+    if (nbatch == 0) return BPGPU_OK;
+    if (!verdict) return pfail(p, BPGPU_ERR_INVALID_ARG, "null argument");
+    mark_undecided(verdict, nbatch);
+    call_guard cg(p);
+    if (!cg.ok) return pfail(p, BPGPU_ERR_INVALID_ARG, "the pool is being destroyed");
+    pool_dev *d0 = p->devs[p->rr_dev.fetch_add(1, std::memory_order_relaxed) % p->devs.size()];
+    std::lock_guard<std::mutex> lk(d0->misc_mu);
+    const int rc = run(d0->misc, arg);
+    if (rc) mark_undecided(verdict, nbatch);
+    return rc ? pfail(p, rc, "%s", bpgpu_last_error(d0->misc)) : BPGPU_OK;
+}
+
 // The queue's timeline (option "combine_trace" = ring size): one JSON object per line -- {"chain": ...} for every launch chain
 // (open -> sealed -> issue begin / end -> completion seen -> delivery begin / end -> buffer free; nanoseconds of CLOCK_MONOTONIC),
 // {"req": ...} for every eighth request per thread (submit -> slots reserved -> inputs written -> delivered -> woken).

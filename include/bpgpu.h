@@ -341,6 +341,70 @@ int bpgpu_linear_verify_batch_dev(bpgpu_ctx *ctx, size_t n, size_t nbatch, const
                                   const void *d_b, int b_shared, void *d_verdict, void *d_msm_out, void *d_transcripts_out,
                                   void *stream);
 
+/* ---- R1CS constraint-system proofs (r1cs::Verifier::verify, src/r1cs/verifier.rs:329-500) ----------------------------
+ * The reference's verifier re-runs a gadget (closures) against its constraint system.  On the verifier side only
+ * commit (verifier.rs:235-243) and challenge_scalar inside randomized callbacks (:177) touch the transcript; multiply,
+ * allocate, allocate_multiplier and constrain only append constraints and count multipliers (:67-127).  So a gadget is
+ * recorded ONCE as data -- a bpgpu_r1cs_circuit -- and verified on the device for any number of proofs.
+ *   m          : committed variables (Verifier::commit calls)
+ *   n1, n2     : multipliers before / after randomization (create_randomized_constraints, :300-321)
+ *   two_phase  : 1 when a randomized callback was registered (r1cs-2phase, even with n2 = 0), else 0 (then n2 = 0, no challenges)
+ *   labels     : the phase-2 challenge labels in draw order, concatenated; label_lens[j] bytes each
+ *   constraints: CSR rows in the order the gadget added them: row_ptr[n_constraints + 1], and per term
+ *                kind (BPGPU_R1CS_L/R/O: multiplier index < n1 + n2; _V: committed index < m; _ONE: index 0),
+ *                challenge (BPGPU_R1CS_NO_CHALLENGE, or j < n_challenges), power (0 without a challenge, else 1..BPGPU_R1CS_MAX_POWER),
+ *                coeff (32 bytes canonical): the term's coefficient is coeff * ch_j^power.  Terms are summed as
+ *                flattened_constraints does (:260-298), with the reference's signs on V and ONE.
+ * Host-only; every field is validated (BPGPU_ERR_INVALID_ARG otherwise).  The per-variable lists are uploaded to a device on
+ * first use and cached there until destroy; a circuit may be used from several threads and contexts at once. */
+typedef struct bpgpu_r1cs_circuit bpgpu_r1cs_circuit;
+#define BPGPU_R1CS_L 0
+#define BPGPU_R1CS_R 1
+#define BPGPU_R1CS_O 2
+#define BPGPU_R1CS_V 3
+#define BPGPU_R1CS_ONE 4
+#define BPGPU_R1CS_NO_CHALLENGE 0xffffffffu
+#define BPGPU_R1CS_MAX_VARS 65536            /* m, n1 + n2 (padded_n <= 2^16) */
+#define BPGPU_R1CS_MAX_CONSTRAINTS (1u << 22)
+#define BPGPU_R1CS_MAX_TERMS (1u << 24)
+#define BPGPU_R1CS_MAX_CHALLENGES 256
+#define BPGPU_R1CS_MAX_LABEL 1024
+#define BPGPU_R1CS_MAX_POWER 255
+int bpgpu_r1cs_circuit_create(size_t m, size_t n1, size_t n2, int two_phase, size_t n_challenges, const uint8_t *labels,
+                              const uint32_t *label_lens, size_t n_constraints, const uint32_t *row_ptr, size_t n_terms,
+                              const uint8_t *term_kind, const uint32_t *term_index, const uint32_t *term_challenge,
+                              const uint32_t *term_power, const uint8_t *term_coeff, bpgpu_r1cs_circuit **out);
+void bpgpu_r1cs_circuit_destroy(bpgpu_r1cs_circuit *circuit);
+/* padded_n = (n1 + n2).next_power_of_two() (0 -> 1) and the per-proof point count 11 + m + 2 lg(padded_n) of the mega-check */
+int bpgpu_r1cs_circuit_shape(const bpgpu_r1cs_circuit *circuit, size_t *padded_n, size_t *n_unique);
+/* nbatch proofs against one circuit; each as R1CSProof::from_bytes (src/r1cs/proof.rs:129-204), Verifier::new(transcript),
+ * commit(V_i) for its m commitments, the recorded gadget, and verify(proof, pc_gens, bp_gens) with the context's generators.
+ *   proofs            : nbatch x proof_stride bytes; proof_lens[b] <= proof_stride bytes of each are the proof (either
+ *                       serialization: version 0 with A_I2 = A_O2 = S2 = identity, or version 1)
+ *   commitments       : nbatch x m x 32 bytes
+ *   transcripts       : the caller's transcript(s) BEFORE Verifier::new: one 208-byte state (transcript_stride 0) or nbatch
+ *                       (stride BPGPU_TRANSCRIPT_BYTES)
+ *   rng32             : nbatch x 32 bytes -- what TranscriptRngBuilder::finalize takes from thread_rng() (verifier.rs:448) -- or
+ *                       NULL: the library's generator (ChaCha20 keyed from the OS per call)
+ *   verdict           : nbatch bytes, BPGPU_VERDICT_* (R1CSError, errors.rs:125-167: FormatError, VerificationError -- an identity
+ *                       validated point, an IPP of the wrong length, an undecodable point, a mega-check that is not the
+ *                       identity -- or InvalidGeneratorsLength when padded_n > gens_capacity)
+ *   msm_out           : optional nbatch x 32 bytes, the mega-check's encoding where the verdict came from it
+ *   transcripts_out   : optional nbatch x 208 bytes, each transcript as the reference leaves it: unchanged after a from_bytes
+ *                       failure; as of the message for an identity validated point (A_I1, A_O1, S1, T_*, L_i, R_i); after the
+ *                       phase-2 challenges for InvalidGeneratorsLength; as of `w` for an IPP whose length is not lg(padded_n);
+ *                       else after the last IPP challenge.
+ * `_dev`: device pointers (proof_lens: nbatch uint32), `shared_transcript` a HOST pointer to one state or `d_transcripts` nbatch
+ * states on the device (exactly one of the two). */
+int bpgpu_r1cs_verify_batch_ts(bpgpu_ctx *ctx, const bpgpu_r1cs_circuit *circuit, size_t nbatch, const uint8_t *proofs,
+                               size_t proof_stride, const uint32_t *proof_lens, const uint8_t *commitments,
+                               const uint8_t *transcripts, size_t transcript_stride, const uint8_t *rng32,
+                               uint8_t *verdict, uint8_t *msm_out, uint8_t *transcripts_out);
+int bpgpu_r1cs_verify_batch_ts_dev(bpgpu_ctx *ctx, const bpgpu_r1cs_circuit *circuit, size_t nbatch, const void *d_proofs,
+                                   size_t proof_stride, const void *d_proof_lens, const void *d_commitments,
+                                   const uint8_t *shared_transcript, const void *d_transcripts, const void *d_rng32,
+                                   void *d_verdict, void *d_msm_out, void *d_transcripts_out, void *stream);
+
 /* nbatch independent calls of
  *   LinearProof::create(&mut transcript, &mut rng, &C, r, a_vec, b_vec, G_vec, &F, &B).to_bytes()
  * (src/linear_proof.rs:40-173), all of one size n (a power of two) over the same G, F, B.  Per round the reference forms
@@ -607,6 +671,12 @@ int bpgpu_pool_msm_batch_shared_submit_dev(bpgpu_pool *pool, int dev_index, size
 int bpgpu_pool_ipp_verify(bpgpu_pool *pool, size_t n, size_t nbatch, const uint8_t *proofs, size_t proof_len, const uint8_t *label,
                           size_t label_len, const uint8_t *G_factors, const uint8_t *H_factors, const uint8_t *P, const uint8_t *Q,
                           const uint8_t *G, const uint8_t *H, uint8_t *verdict, uint8_t *msm_out);
+/* R1CS proofs through the pool (arguments as bpgpu_r1cs_verify_batch_ts): the whole call runs on the next device, blocking;
+ * any thread may call it, with any circuit. */
+int bpgpu_pool_r1cs_verify_ts(bpgpu_pool *pool, const bpgpu_r1cs_circuit *circuit, size_t nbatch, const uint8_t *proofs,
+                              size_t proof_stride, const uint32_t *proof_lens, const uint8_t *commitments,
+                              const uint8_t *transcripts, size_t transcript_stride, const uint8_t *rng32,
+                              uint8_t *verdict, uint8_t *msm_out, uint8_t *transcripts_out);
 /* The combining queue's timeline (set option "combine_trace" = ring size first): one JSON object per line -- every launch chain (opened,
  * sealed, issue begin / end, completion seen, delivery begin / end, buffer free; CLOCK_MONOTONIC ns) and every eighth request per thread
  * (submitted, slots reserved, inputs written, delivered, woken).  tools/combine_timeline.py turns it into "where does a request wait". */
