@@ -3976,6 +3976,323 @@ extern "C" int bpgpu_r1cs_verify_batch_ts(bpgpu_ctx *c, const bpgpu_r1cs_circuit
     return BPGPU_OK;
 }
 
+// ============================================================================
+// R1CS proof creation (r1cs_prover.h): the witness program is a host object beside the circuit, uploaded to a device on
+// first use and kept there until bpgpu_r1cs_witness_destroy
+// ============================================================================
+struct bpgpu_r1cs_witness {
+    uint32_t m = 0, n1 = 0, n = 0, nch = 0, nfree = 0, nrows = 0;
+    std::vector<uint32_t> src;       // 2n entries: src_left, then src_right
+    std::vector<uint32_t> row_ptr;   // nrows + 1
+    std::vector<r1p_term> terms;
+    size_t off_row = 0, off_terms = 0, dev_bytes = 0;
+    std::mutex mu;
+    std::map<int, char *> dev;       // device ordinal -> [src][row_ptr][terms]
+};
+
+extern "C" int bpgpu_r1cs_witness_create(const bpgpu_r1cs_circuit *ci, size_t n_free, const uint32_t *src_left, const uint32_t *src_right, size_t n_rows,
+                                         const uint32_t *row_ptr, size_t n_terms, const uint8_t *term_kind, const uint32_t *term_index,
+                                         const uint32_t *term_challenge, const uint32_t *term_power, const uint8_t *term_coeff, bpgpu_r1cs_witness **out) {
+    if (!out) return BPGPU_ERR_INVALID_ARG;
+    *out = nullptr;
+    if (!ci) return BPGPU_ERR_INVALID_ARG;
+    const size_t n = ci->n;
+    if (n_free > 2 * n || n_rows > BPGPU_R1CS_MAX_CONSTRAINTS || n_terms > BPGPU_R1CS_MAX_TERMS) return BPGPU_ERR_INVALID_ARG;
+    if ((n && (!src_left || !src_right)) || !row_ptr || (n_terms && (!term_kind || !term_index || !term_challenge || !term_power || !term_coeff)))
+        return BPGPU_ERR_INVALID_ARG;
+    if (row_ptr[0] != 0 || row_ptr[n_rows] != n_terms) return BPGPU_ERR_INVALID_ARG;
+    for (size_t r = 0; r < n_rows; r++)
+        if (row_ptr[r + 1] < row_ptr[r]) return BPGPU_ERR_INVALID_ARG;
+    // every term as bpgpu_r1cs_circuit_create checks it
+    for (size_t t = 0; t < n_terms; t++) {
+        const uint32_t kind = term_kind[t], idx = term_index[t], ch = term_challenge[t], pw = term_power[t];
+        bool ok = true;
+        switch (kind) {
+        case BPGPU_R1CS_L: case BPGPU_R1CS_R: case BPGPU_R1CS_O: ok = idx < n; break;
+        case BPGPU_R1CS_V: ok = idx < ci->m; break;
+        case BPGPU_R1CS_ONE: ok = idx == 0; break;
+        default: ok = false;
+        }
+        if (ch == BPGPU_R1CS_NO_CHALLENGE) ok = ok && pw == 0;
+        else ok = ok && ch < ci->nch && pw >= 1 && pw <= BPGPU_R1CS_MAX_POWER;
+        sc cf;
+        memcpy(cf.v, term_coeff + t * 32, 32);
+        if (!ok || !sc_is_canonical_sc(cf)) return BPGPU_ERR_INVALID_ARG;
+    }
+    // the sources of multiplier i: a free input (each used once), a row over earlier multipliers only (no challenge in phase 1), or zero
+    std::vector<uint32_t> used(n_free, 0);
+    for (size_t i = 0; i < n; i++)
+        for (int side = 0; side < 2; side++) {
+            const uint32_t s = side ? src_right[i] : src_left[i];
+            if (s == BPGPU_R1CS_SRC_ZERO) continue;
+            if (s & BPGPU_R1CS_SRC_FREE) {
+                const uint32_t j = s & ~BPGPU_R1CS_SRC_FREE;
+                if (j >= n_free || used[j]++) return BPGPU_ERR_INVALID_ARG;
+                continue;
+            }
+            if (s >= n_rows) return BPGPU_ERR_INVALID_ARG;
+            for (uint32_t t = row_ptr[s]; t < row_ptr[s + 1]; t++) {
+                if (term_kind[t] <= BPGPU_R1CS_O && term_index[t] >= i) return BPGPU_ERR_INVALID_ARG;
+                if (i < ci->n1 && term_challenge[t] != BPGPU_R1CS_NO_CHALLENGE) return BPGPU_ERR_INVALID_ARG;
+            }
+        }
+    for (size_t j = 0; j < n_free; j++)
+        if (used[j] != 1) return BPGPU_ERR_INVALID_ARG;
+    auto *w = new bpgpu_r1cs_witness();
+    w->m = ci->m, w->n1 = ci->n1, w->n = ci->n, w->nch = ci->nch, w->nfree = (uint32_t)n_free, w->nrows = (uint32_t)n_rows;
+    w->src.assign(src_left, src_left + n);
+    w->src.insert(w->src.end(), src_right, src_right + n);
+    w->row_ptr.assign(row_ptr, row_ptr + n_rows + 1);
+    w->terms.resize(n_terms);
+    for (size_t t = 0; t < n_terms; t++) {
+        r1p_term &e = w->terms[t];
+        e.kind = term_kind[t];
+        e.index = term_index[t];
+        e.chal = term_challenge[t] == BPGPU_R1CS_NO_CHALLENGE ? R1_NO_CHAL : (term_challenge[t] | (term_power[t] << 16));
+        sc cf;
+        sc28 cm;
+        memcpy(cf.v, term_coeff + t * 32, 32);
+        sc_to_mont28(cm, cf);
+        memcpy(e.coeff, cm.v, 40);
+    }
+    w->off_row = align_up(w->src.size() * 4 + 4);
+    w->off_terms = w->off_row + align_up(w->row_ptr.size() * 4);
+    w->dev_bytes = w->off_terms + align_up(w->terms.size() * sizeof(r1p_term) + 4);
+    *out = w;
+    return BPGPU_OK;
+}
+
+extern "C" void bpgpu_r1cs_witness_destroy(bpgpu_r1cs_witness *w) {
+    if (!w) return;
+    for (auto &kv : w->dev) {
+        (void)hipSetDevice(kv.first);
+        (void)hipFree(kv.second);
+    }
+    delete w;
+}
+
+// the witness program on c's device (the caller holds c->mu and has set the device)
+static int r1cs_witness_on(bpgpu_ctx *c, const bpgpu_r1cs_witness *cw, char **d_out) {
+    auto *w = const_cast<bpgpu_r1cs_witness *>(cw);
+    std::lock_guard<std::mutex> lk(w->mu);
+    auto it = w->dev.find(c->device);
+    if (it != w->dev.end()) {
+        *d_out = it->second;
+        return BPGPU_OK;
+    }
+    std::vector<char> img(w->dev_bytes, 0);
+    if (!w->src.empty()) memcpy(img.data(), w->src.data(), w->src.size() * 4);
+    memcpy(img.data() + w->off_row, w->row_ptr.data(), w->row_ptr.size() * 4);
+    if (!w->terms.empty()) memcpy(img.data() + w->off_terms, w->terms.data(), w->terms.size() * sizeof(r1p_term));
+    char *d = nullptr;
+    if (hipMalloc((void **)&d, w->dev_bytes) != hipSuccess) return fail(c, BPGPU_ERR_HIP, "out of device memory (witness program)");
+    if (hipMemcpy(d, img.data(), w->dev_bytes, hipMemcpyHostToDevice) != hipSuccess) {
+        (void)hipFree(d);
+        return fail(c, BPGPU_ERR_HIP, "witness program upload failed");
+    }
+    w->dev[c->device] = d;
+    *d_out = d;
+    return BPGPU_OK;
+}
+
+extern "C" int bpgpu_r1cs_prove_batch(bpgpu_ctx *c, const bpgpu_r1cs_circuit *ci, const bpgpu_r1cs_witness *wi, size_t nbatch, const uint8_t *v,
+                                      const uint8_t *v_blinding, const uint8_t *free_inputs, const uint8_t *transcripts, size_t transcript_stride,
+                                      const uint8_t *rng32, uint8_t *proofs_out, size_t proof_stride, uint32_t *proof_lens_out, uint8_t *commitments_out,
+                                      uint8_t *status_out, uint8_t *transcripts_out) {
+    if (!c || !ci || !wi) return BPGPU_ERR_INVALID_ARG;
+    if (wi->m != ci->m || wi->n1 != ci->n1 || wi->n != ci->n || wi->nch != ci->nch) return fail(c, BPGPU_ERR_INVALID_ARG, "witness program of another circuit");
+    if (nbatch == 0) return BPGPU_OK;
+    const size_t TS = BPGPU_TRANSCRIPT_BYTES, m = ci->m, n = ci->n, n1 = ci->n1, n2 = n - n1, pn = ci->pn, k = ci->k, nf = wi->nfree;
+    if ((m && (!v || !v_blinding || !commitments_out)) || (nf && !free_inputs) || !transcripts || !proofs_out || !proof_lens_out || !status_out)
+        return BPGPU_ERR_INVALID_ARG;
+    if (transcript_stride != 0 && transcript_stride != TS) return fail(c, BPGPU_ERR_INVALID_ARG, "transcript_stride must be 0 or %zu", TS);
+    for (size_t p = 0; p < (transcript_stride ? nbatch : 1); p++)
+        if (!ts_state_ok(transcripts + p * transcript_stride)) return fail(c, BPGPU_ERR_INVALID_ARG, "malformed transcript state");
+    const size_t ipp_len = 32 * (2 * k + 2), max_len = 1 + 32 * (n2 ? 14 : 11) + ipp_len;
+    if (proof_stride < max_len) return fail(c, BPGPU_ERR_INVALID_ARG, "proof_stride %zu < %zu", proof_stride, max_len);
+    const size_t ncol = 2 * pn + 2, nrow = std::max(std::max(n, m), (size_t)1);
+    const size_t n_gsc = std::max(std::max(3 * nbatch * ncol, 3 * nbatch * m), 15 * nbatch);
+    if ((uint64_t)n_gsc * 32 > (4ull << 30) || (uint64_t)n_gsc > 0x7fffffffull / 8 || (uint64_t)nbatch * (n + m + nf + pn) > 0x7fffffffull / 64 ||
+        (uint64_t)nbatch * 7 * nrow > 0x7fffffffull / 64)
+        return fail(c, BPGPU_ERR_INVALID_ARG, "batch too large for this circuit");
+    std::lock_guard<std::mutex> lk(c->mu);
+    HIPCHK(c, hipSetDevice(c->device));
+    if (!c->d_table) return fail(c, BPGPU_ERR_NO_GENS, "generators not loaded");
+    if (pn > c->gens_capacity) return fail(c, BPGPU_ERR_NO_GENS, "InvalidGeneratorsLength: padded_n=%zu > gens_capacity=%zu", pn, (size_t)c->gens_capacity);
+    r1p_shape sh{};
+    sh.c.m = (uint32_t)m, sh.c.n1 = (uint32_t)n1, sh.c.n = (uint32_t)n, sh.c.pn = (uint32_t)pn, sh.c.k = (uint32_t)k;
+    sh.c.two_phase = ci->two_phase, sh.c.nch = ci->nch, sh.c.Q = ci->Q;
+    sh.c.nzhi = (ci->Q >> 6) + 1;
+    sh.c.nyhi = (uint32_t)(((pn - 1) >> 6) + 1);
+    sh.c.f_zlo = R1P_FIXED;
+    sh.c.f_zhi = sh.c.f_zlo + 64;
+    sh.c.f_ylo = sh.c.f_zhi + sh.c.nzhi;
+    sh.c.f_yhi = sh.c.f_ylo + 64;
+    sh.f_yplo = sh.c.f_yhi + sh.c.nyhi;
+    sh.f_yphi = sh.f_yplo + 64;
+    sh.c.f_ch = sh.f_yphi + sh.c.nyhi;
+    sh.c.nfields = sh.c.f_ch + sh.c.nch;
+    sh.c.nproofs = (uint32_t)nbatch;
+    sh.nfree = (uint32_t)nf;
+    // the draw order of prove (prover.rs:416-418, 528-541, 583)
+    sh.o_sl1 = 3;
+    sh.o_sr1 = sh.o_sl1 + (uint32_t)n1;
+    sh.o_b2 = sh.o_sr1 + (uint32_t)n1;
+    sh.o_sl2 = sh.o_b2 + (n2 ? 3u : 0u);
+    sh.o_sr2 = sh.o_sl2 + (uint32_t)n2;
+    sh.o_tb = sh.o_sr2 + (uint32_t)n2;
+    sh.nrand = sh.o_tb + 5;
+    char *dc = nullptr, *dw = nullptr;
+    int rc = r1cs_circuit_on(c, ci, &dc);
+    if (rc) return rc;
+    rc = r1cs_witness_on(c, wi, &dw);
+    if (rc) return rc;
+    hipStream_t s = c->stream;
+    rc = ctx_enter(c, s);
+    if (rc) return rc;
+    prover_exit px{c, s};
+    // ---- inputs through pinned staging into the persistent IO buffer
+    const size_t sz_v = align_up(nbatch * m * 32 + 64), sz_f = align_up(nbatch * nf * 32 + 64), sz_rng = align_up(nbatch * 32), sz_ts = align_up(nbatch * TS);
+    const size_t sz_in = 2 * sz_v + sz_f + sz_rng + sz_ts;
+    const size_t sz_rec = align_up(nbatch * R1P_NREC * 32), sz_ipp = align_up(nbatch * ipp_len), sz_st = align_up(nbatch * 4), sz_stb = align_up(nbatch + 64);
+    const size_t sz_out = sz_rec + sz_ipp + sz_v + sz_st + sz_stb + sz_ts;
+    rc = io_reserve(c, sz_in + sz_out);
+    if (rc) return px.finish(rc);
+    char *h = nullptr;
+    rc = pin_alloc(c, s, sz_in + sz_out, &h);
+    if (rc) return px.finish(rc);
+    px.h = h;
+    px.host_secret_bytes = 2 * sz_v + sz_f + sz_rng;   // values, blindings, free inputs, the rng seeds
+    if (m) {
+        memcpy(h, v, nbatch * m * 32);
+        memcpy(h + sz_v, v_blinding, nbatch * m * 32);
+    }
+    if (nf) memcpy(h + 2 * sz_v, free_inputs, nbatch * nf * 32);
+    if (rng32) memcpy(h + 2 * sz_v + sz_f, rng32, nbatch * 32);
+    else if ((rc = os_random(c, h + 2 * sz_v + sz_f, nbatch * 32)) != 0) return px.finish(rc);   // finalize(&mut thread_rng())
+    for (size_t p = 0; p < nbatch; p++) memcpy(h + 2 * sz_v + sz_f + sz_rng + p * TS, transcripts + p * transcript_stride, TS);
+    char *d_in = c->io_dev;
+    const uint8_t *d_v = (const uint8_t *)d_in, *d_vb = (const uint8_t *)(d_in + sz_v), *d_free = (const uint8_t *)(d_in + 2 * sz_v),
+                  *d_rng = (const uint8_t *)(d_in + 2 * sz_v + sz_f);
+    uint32_t *d_ts = (uint32_t *)(d_in + 2 * sz_v + sz_f + sz_rng);
+    char *d_outb = d_in + sz_in;
+    uint32_t *d_rec = (uint32_t *)d_outb, *d_vout = (uint32_t *)(d_outb + sz_rec + sz_ipp), *d_stat = (uint32_t *)(d_outb + sz_rec + sz_ipp + sz_v);
+    uint8_t *d_ipp = (uint8_t *)(d_outb + sz_rec), *d_stb = (uint8_t *)d_stat + sz_st;
+    PX_HIPCHK(px, hipMemcpyAsync(d_in, h, sz_in, hipMemcpyHostToDevice, s));
+    PX_HIPCHK(px, hipMemsetAsync(d_outb, 0, sz_out, s));
+    // ---- working set
+    const size_t w_gs = align_up(n_gsc * 32), w_mo = align_up(5 * nbatch * 32 + 64), w_ms = align_up(std::max(nbatch * m, 5 * nbatch) + 64),
+                 w_rnd = align_up((size_t)sh.nrand * nbatch * 40), w_aw = align_up(3 * std::max(n, (size_t)1) * nbatch * 40),
+                 w_f = align_up((size_t)sh.c.nfields * nbatch * 40), w_vec = align_up(6 * std::max(n, (size_t)1) * nbatch * 40),
+                 w_t = align_up(7 * nrow * nbatch * 40), w_iv = align_up(nbatch * pn * 32), w_w = align_up(nbatch * 32);
+    const size_t need = w_gs + w_mo + w_ms + w_rnd + w_aw + w_f + w_vec + w_t + 4 * w_iv + w_w;
+    if (c->rpp_cap < need) {   // (the old block is clean: every call clears it on its way out)
+        PX_HIPCHK(px, hipDeviceSynchronize());
+        if (c->rpp_buf) PX_HIPCHK(px, hipFree(c->rpp_buf));
+        c->rpp_buf = nullptr;
+        c->rpp_cap = 0;
+        PX_HIPCHK(px, hipMalloc((void **)&c->rpp_buf, need + need / 8));
+        c->rpp_cap = need + need / 8;
+    }
+    char *wb = c->rpp_buf;
+    uint32_t *gsc = (uint32_t *)wb, *mo = (uint32_t *)(wb + w_gs);
+    uint8_t *mst = (uint8_t *)mo + w_mo;
+    uint32_t *rnd = (uint32_t *)(mst + w_ms), *aw = (uint32_t *)((char *)rnd + w_rnd), *fields = (uint32_t *)((char *)aw + w_aw),
+             *vecs = (uint32_t *)((char *)fields + w_f), *terms = (uint32_t *)((char *)vecs + w_vec), *lv = (uint32_t *)((char *)terms + w_t),
+             *rv = (uint32_t *)((char *)lv + w_iv), *gf = (uint32_t *)((char *)rv + w_iv), *hf = (uint32_t *)((char *)gf + w_iv),
+             *wv = (uint32_t *)((char *)hf + w_iv);
+    const uint32_t nb32 = (uint32_t)nbatch, n_pb = (nb32 + 63) / 64;
+    const uint32_t *src_l = (const uint32_t *)dw, *src_r = src_l + n, *row_ptr = (const uint32_t *)(dw + wi->off_row);
+    const r1p_term *wterms = (const r1p_term *)(dw + wi->off_terms);
+    const bool ct = c->prover_ct;
+    do {
+        // (1) V_j = v_j B + v~_j B~: rows (B~, B, G_0) of the generator walk, m per proof
+        if (hipMemsetAsync(gsc, 0, std::max(nbatch * m, (size_t)1) * 3 * 32, s) != hipSuccess) { rc = fail(c, BPGPU_ERR_HIP, "memset failed"); break; }
+        const uint32_t nin = (uint32_t)(nbatch * (m + nf));
+        if (nin) LAUNCH(c, s, "r1p_inputs", k_r1p_inputs, (nin + 63) / 64, 64, nin, sh, d_v, d_vb, d_free, gsc, d_stat);
+        if (m) {
+            rc = msm_shared_dev_locked(c, 1, 1, nbatch * m, 0, gsc, nullptr, nullptr, d_vout, mst, nullptr, s, true, ct);
+            if (rc) break;
+        }
+        // (2) Prover::new, the V appends, "m"; the TranscriptRng and every random scalar (32 lanes per proof)
+        LAUNCH(c, s, "r1p_rng", k_r1p_rng, (nb32 + 1) / 2, 64, sh, d_ts, (const uint32_t *)d_vout, d_vb, d_rng, rnd);
+        // (3) phase 1: witness, A_I1, A_O1, S1, the phase-2 challenges
+        for (int ph = 1; ph <= 2 && !rc; ph++) {
+            const size_t cnt = ph == 1 ? n1 : n2;
+            if (ph == 2 && !n2) {
+                LAUNCH(c, s, "r1p_chal2", k_r1p_chal2, (nb32 + RP_BLOCK - 1) / RP_BLOCK, RP_BLOCK, sh, (const uint32_t *)nullptr, d_ts, fields, d_rec);
+                break;
+            }
+            sh.i0 = ph == 1 ? 0u : (uint32_t)n1;
+            sh.i1 = ph == 1 ? (uint32_t)n1 : (uint32_t)n;
+            if (cnt) LAUNCH(c, s, "r1p_witness", k_r1p_witness, n_pb, 64, sh, src_l, src_r, row_ptr, wterms, d_v, d_free, (const uint32_t *)fields, aw);
+            if (hipMemsetAsync(gsc, 0, 3 * nbatch * ncol * 32, s) != hipSuccess) { rc = fail(c, BPGPU_ERR_HIP, "memset failed"); break; }
+            const uint32_t nr = (uint32_t)(nbatch * std::max(cnt, (size_t)1));
+            LAUNCH(c, s, "r1p_rows", k_r1p_rows, (nr + 63) / 64, 64, nr, sh, (uint32_t)cnt, ph == 1 ? 0u : sh.o_b2, (const uint32_t *)aw, (const uint32_t *)rnd, gsc);
+            rc = msm_shared_dev_locked(c, pn, 1, 3 * nbatch, 0, gsc, nullptr, nullptr, mo, mst, nullptr, s, false, ct);
+            if (rc) break;
+            if (ph == 1)
+                LAUNCH(c, s, "r1p_chal1", k_r1p_chal1, (nb32 + RP_BLOCK - 1) / RP_BLOCK, RP_BLOCK, sh, (const uint32_t *)mo, (const uint32_t *)(dc + ci->off_lbl_off),
+                       (const uint8_t *)(dc + ci->off_lbl), d_ts, fields, d_rec);
+            else
+                LAUNCH(c, s, "r1p_chal2", k_r1p_chal2, (nb32 + RP_BLOCK - 1) / RP_BLOCK, RP_BLOCK, sh, (const uint32_t *)mo, d_ts, fields, d_rec);
+        }
+        if (rc) break;
+        // (4) wL, wR, wO, wV; l, r and the t polynomial; T_1, T_3..T_6
+        const uint32_t npoly = (uint32_t)((n + m) * nbatch);
+        if (hipMemsetAsync(terms, 0, w_t, s) != hipSuccess || hipMemsetAsync(gsc, 0, 15 * nbatch * 32, s) != hipSuccess) { rc = fail(c, BPGPU_ERR_HIP, "memset failed"); break; }
+        if (npoly)
+            LAUNCH(c, s, "r1p_poly", k_r1p_poly, (npoly + 63) / 64, 64, npoly, sh, (const uint32_t *)dc, (const r1cs_ent *)(dc + ci->off_ents), (const uint32_t *)aw,
+                   (const uint32_t *)rnd, d_vb, (const uint32_t *)fields, (uint32_t)nrow, vecs, terms);
+        LAUNCH(c, s, "r1p_tsum", k_r1p_tsum, nb32, 64, sh, (uint32_t)nrow, (const uint32_t *)terms, (const uint32_t *)rnd, fields, gsc);
+        rc = msm_shared_dev_locked(c, 1, 1, 5 * nbatch, 0, gsc, nullptr, nullptr, mo, mst, nullptr, s, true, ct);
+        if (rc) break;
+        // (5) u, x, t_x, t_x_blinding, e_blinding, w; the IPP over G(padded_n), H(padded_n) with Q = w B
+        LAUNCH(c, s, "r1p_chal3", k_r1p_chal3, (nb32 + RP_BLOCK - 1) / RP_BLOCK, RP_BLOCK, sh, (const uint32_t *)mo, (const uint32_t *)rnd, d_ts, fields, d_rec, wv);
+        const uint32_t nvec = (uint32_t)(nbatch * pn);
+        LAUNCH(c, s, "r1p_vecs", k_r1p_vecs, (nvec + 63) / 64, 64, nvec, sh, (const uint32_t *)fields, (const uint32_t *)vecs, lv, rv, gf, hf);
+        if (hipGetLastError() != hipSuccess) { rc = fail(c, BPGPU_ERR_HIP, "launch failed"); break; }
+        ippc_fixed fx;
+        fx.gn = pn;
+        fx.gm = 1;
+        fx.w = wv;
+        fx.gen_scalars = gsc;
+        rc = ippc_core(c, s, pn, k, nbatch, lv, rv, gf, hf, nullptr, nullptr, nullptr, 1, d_ts, d_ipp, ipp_len, d_stb, &fx);
+    } while (0);
+    char *h_out = h + sz_in;
+    if (!rc && (hipMemcpyAsync((char *)d_stb + sz_stb, d_ts, nbatch * TS, hipMemcpyDeviceToDevice, s) != hipSuccess ||
+                hipMemcpyAsync(h_out, d_outb, sz_out, hipMemcpyDeviceToHost, s) != hipSuccess))
+        rc = fail(c, BPGPU_ERR_HIP, "D2H copy failed");
+    rc = px.finish(rc);
+    if (rc) return rc;
+    // R1CSProof::to_bytes (proof.rs:83-108): version 0 exactly when A_I2, A_O2, S2 are all the identity
+    const uint8_t *h_rec = (const uint8_t *)h_out, *h_ipp = h_rec + sz_rec, *h_v = h_ipp + sz_ipp, *h_st = h_v + sz_v, *h_stb = h_st + sz_st,
+                  *h_ts = h_stb + sz_stb;
+    for (size_t p = 0; p < nbatch; p++) {
+        const uint8_t *rec = h_rec + p * R1P_NREC * 32;
+        bool one_phase = true;
+        for (size_t b = 32 * R1P_AI2; b < 32 * (R1P_S2 + 1); b++) one_phase = one_phase && rec[b] == 0;
+        uint8_t *o = proofs_out + p * proof_stride;
+        size_t len = 0;
+        o[len++] = one_phase ? 0 : 1;
+        for (uint32_t e = 0; e < R1P_NREC; e++) {
+            if (one_phase && e >= R1P_AI2 && e <= R1P_S2) continue;
+            memcpy(o + len, rec + 32 * e, 32);
+            len += 32;
+        }
+        memcpy(o + len, h_ipp + p * ipp_len, ipp_len);
+        len += ipp_len;
+        memset(o + len, 0, proof_stride - len);
+        proof_lens_out[p] = (uint32_t)len;
+        uint32_t st;
+        memcpy(&st, h_st + 4 * p, 4);
+        status_out[p] = (uint8_t)std::max(st, (uint32_t)h_stb[p]);
+    }
+    if (m) memcpy(commitments_out, h_v, nbatch * m * 32);
+    if (transcripts_out) memcpy(transcripts_out, h_ts, nbatch * TS);
+    return BPGPU_OK;
+}
+
 // the pool form: the whole call on the next device's context (pool.hip)
 extern "C" int bpgpu_internal_pool_run_on_context(bpgpu_pool *p, size_t nbatch, uint8_t *verdict, int (*run)(bpgpu_ctx *, void *), void *arg);
 namespace {

@@ -18,6 +18,7 @@
 #include "rp_prover.h"
 #include "linear_prover.h"
 #include "r1cs.h"
+#include "r1cs_prover.h"
 
 #define BP_BLOCK 64   // one wavefront per workgroup: under contention a CU rarely has room for four waves of one group at once (256: -8% at 48 streams)
 #define FB_BLOCK 64
@@ -77,6 +78,17 @@ __global__ void k_aud_verdict(uint32_t n, const uint32_t *status, const uint8_t 
 __global__ void k_r1cs_front(r1cs_shape sh, rp_strobe_init init, const uint8_t *proofs, const uint32_t *proof_lens, const uint8_t *commitments, const uint32_t *ts_in, const uint8_t *rng32, const uint32_t *lbl_off, const uint8_t *lbl, uint32_t *fields, uint32_t *uniq_sc, uint32_t *uniq_pt, uint32_t *ts_out, uint32_t *status);
 __global__ void k_r1cs_flatten(uint32_t nthreads, r1cs_shape sh, const uint32_t *col_ptr, const r1cs_ent *ents, const uint32_t *status, uint32_t *fields, uint32_t *gen_sc, uint32_t *uniq_sc, uint32_t *dterm);
 __global__ void k_r1cs_finish(r1cs_shape sh, const uint32_t *status, const uint32_t *dterm, const uint32_t *fields, uint32_t *gen_sc);
+// k_r1cs_prove.hip
+__global__ void k_r1p_inputs(uint32_t nthreads, r1p_shape sh, const uint8_t *v, const uint8_t *vb, const uint8_t *freev, uint32_t *vrows, uint32_t *status);
+__global__ void k_r1p_rng(r1p_shape sh, uint32_t *ts, const uint32_t *vout, const uint8_t *vb, const uint8_t *rng32, uint32_t *rnd);
+__global__ void k_r1p_witness(r1p_shape sh, const uint32_t *src_l, const uint32_t *src_r, const uint32_t *row_ptr, const r1p_term *terms, const uint8_t *v, const uint8_t *freev, const uint32_t *fields, uint32_t *aw);
+__global__ void k_r1p_rows(uint32_t nthreads, r1p_shape sh, uint32_t cnt, uint32_t b0, const uint32_t *aw, const uint32_t *rnd, uint32_t *rows);
+__global__ void k_r1p_chal1(r1p_shape sh, const uint32_t *mout, const uint32_t *lbl_off, const uint8_t *lbl, uint32_t *ts, uint32_t *fields, uint32_t *recs);
+__global__ void k_r1p_chal2(r1p_shape sh, const uint32_t *mout, uint32_t *ts, uint32_t *fields, uint32_t *recs);
+__global__ void k_r1p_chal3(r1p_shape sh, const uint32_t *tout, const uint32_t *rnd, uint32_t *ts, uint32_t *fields, uint32_t *recs, uint32_t *wout);
+__global__ void k_r1p_poly(uint32_t nthreads, r1p_shape sh, const uint32_t *col_ptr, const r1cs_ent *ents, const uint32_t *aw, const uint32_t *rnd, const uint8_t *vb, const uint32_t *fields, uint32_t nrow, uint32_t *vecs, uint32_t *terms);
+__global__ void k_r1p_tsum(r1p_shape sh, uint32_t nrow, const uint32_t *terms, const uint32_t *rnd, uint32_t *fields, uint32_t *trows);
+__global__ void k_r1p_vecs(uint32_t nthreads, r1p_shape sh, const uint32_t *fields, const uint32_t *vecs, uint32_t *lv, uint32_t *rv, uint32_t *gf, uint32_t *hf);
 __global__ void k_lin_prepare(lin_shape sh, rp_strobe_init init, const uint8_t *proofs, const uint8_t *C, const uint8_t *bvec, const uint8_t *G, const uint8_t *F, const uint8_t *B, uint32_t *scalars, uint32_t *points, uint32_t *status, uint32_t *ts_out, uint32_t *gen_sc);
 __global__ void k_from_uniform(uint32_t n, const uint32_t *uniform, uint32_t *out);
 

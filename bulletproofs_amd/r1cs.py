@@ -12,6 +12,17 @@ There is no host fallback.
     verdict = cs.verify(R1CSProof.from_bytes(proof_bytes), ctx)    # ctx: Context or Pool with generators loaded
 
 ``Verifier.circuit()`` returns the recorded ``Circuit``; ``Circuit.verify_batch`` verifies many proofs of the same gadget.
+
+Proving (src/r1cs/prover.rs): ``Prover`` records the same gadget the same way and, beside the constraints, HOW each multiplier
+gets its inputs (a ``Witness``: free inputs, linear-combination rows that may hold the phase-2 challenges, or zero).  The proof
+is then made on the GPU (bpgpu_r1cs_prove_batch):
+
+    cs = Prover(transcript_state)
+    xs = [cs.commit(v, v_blinding) for v, v_blinding in values]
+    my_gadget(cs, xs)
+    proof, V = cs.prove(ctx)                   # R1CSProof, the m commitments (32 bytes each)
+
+Deviation from the reference: ``Prover.commit`` returns the ``Variable`` only; the commitments come back from proving.
 """
 import ctypes as C
 
@@ -21,6 +32,8 @@ L_ORDER = 2**252 + 27742317777372353535851937790883648493
 KIND_L, KIND_R, KIND_O, KIND_V, KIND_ONE = 0, 1, 2, 3, 4
 NO_CHALLENGE = 0xffffffff
 MAX_POWER = 255
+SRC_ZERO = 0xffffffff          # an allocate() pair left open: a_R = 0 (prover.rs:121-140)
+SRC_FREE = 0x80000000          # | j: free input j of the proof
 
 VERDICT_OK = 0
 VERDICT_VERIFICATION_ERROR = 1
@@ -232,6 +245,168 @@ class Verifier:
         return (out[0][0],) + tuple(out[1:])
 
 
+class Prover(Verifier):
+    """r1cs::Prover (src/r1cs/prover.rs) as a RECORDER: the same constraints as ``Verifier`` records for the same gadget, plus the
+    witness program.  Assignments: an int becomes the next free input of the proof; a symbolic expression of challenges (inside
+    a randomized callback) becomes an LC row evaluated on the device, as do multiply's inputs (Prover::eval, prover.rs:340-356)."""
+
+    def __init__(self, transcript):
+        super().__init__(transcript)
+        self.v, self.v_blinding, self.free = [], [], []
+        self.src_left, self.src_right, self.rows = [], [], []
+        self._witness = None
+
+    def commit(self, v, v_blinding):
+        """prover.rs:296-306; returns the Variable only (V_j is computed on the device and returned by prove)"""
+        if self._n1 is not None:
+            raise R1CSError("commit after the gadget was recorded")
+        self.v.append(v % L_ORDER)
+        self.v_blinding.append(v_blinding % L_ORDER)
+        self.V.append(None)
+        return Variable(KIND_V, len(self.V) - 1)
+
+    def _row(self, x, i):
+        lc = _as_lc(x)
+        for (kind, idx), ch, pw, _ in lc.terms:
+            if kind in (KIND_L, KIND_R, KIND_O) and idx >= i:
+                raise R1CSError("an input of multiplier %d reads multiplier %d" % (i, idx))
+            if kind in (KIND_R, KIND_O) and idx == self.pending_multiplier:
+                raise R1CSError("an input reads the right half of an allocate() pair that is still open")
+            if ch is not None and pw > MAX_POWER:
+                raise R1CSError("challenge power %d above %d" % (pw, MAX_POWER))
+        self.rows.append(list(lc.terms))
+        return len(self.rows) - 1
+
+    def _assign(self, x, i):
+        if x is None:
+            raise R1CSError("MissingAssignment: the prover needs every assignment")
+        if isinstance(x, int):
+            self.free.append(x % L_ORDER)
+            return SRC_FREE | (len(self.free) - 1)
+        return self._row(x, i)
+
+    def multiply(self, left, right):                         # prover.rs:93-119
+        i = self.num_vars
+        self.src_left.append(self._row(left, i))
+        self.src_right.append(self._row(right, i))
+        return super().multiply(left, right)
+
+    def allocate(self, assignment=None):                     # prover.rs:121-140
+        if self.pending_multiplier is None:
+            i = self.num_vars
+            self.src_left.append(self._assign(assignment, i))
+            self.src_right.append(SRC_ZERO)
+        else:
+            i = self.pending_multiplier
+            self.src_right[i] = self._assign(assignment, i)
+        return super().allocate()
+
+    def allocate_multiplier(self, input_assignments=None):  # prover.rs:142-159
+        if input_assignments is None:
+            raise R1CSError("MissingAssignment: the prover needs every assignment")
+        left, right = input_assignments
+        i = self.num_vars
+        self.src_left.append(self._assign(left, i))
+        self.src_right.append(self._assign(right, i))
+        return super().allocate_multiplier()
+
+    def structure(self):
+        """everything that must agree between the proofs of one batch: the constraints and the witness program"""
+        self._finish()
+        return (self.descriptor(), tuple(self.src_left), tuple(self.src_right), tuple(tuple(r) for r in self.rows), len(self.free))
+
+    def witness(self):
+        if self._witness is None:
+            self._finish()
+            self._witness = Witness(self.circuit(), len(self.free), self.src_left, self.src_right, self.rows)
+        return self._witness
+
+    def inputs(self):
+        """(v, v_blinding, free inputs) of this proof as 32-byte scalars"""
+        self._finish()
+        enc = lambda xs: b"".join(x.to_bytes(32, "little") for x in xs)
+        return enc(self.v), enc(self.v_blinding), enc(self.free)
+
+    def prove(self, ctx, rng32=None):
+        """Prover::prove with the generators of `ctx` (a Context): (R1CSProof, [V_j])"""
+        return prove_batch(ctx, [self], rng32)[0]
+
+
+def prove_batch(ctx, provers, rng32=None):
+    """one proof per recorded Prover, all of the same gadget (R1CSError otherwise): [(R1CSProof, [V_j])] in order.
+    rng32: len(provers) x 32 bytes (what finalize takes from thread_rng) or None (the OS generator)."""
+    if not provers:
+        return []
+    st = provers[0].structure()
+    if any(p.structure() != st for p in provers[1:]):
+        raise R1CSError("the provers of one batch must record the same gadget")
+    w = provers[0].witness()
+    ins = [p.inputs() for p in provers]
+    proofs, coms, status = w.prove_batch(ctx, provers[0].circuit(), len(provers), b"".join(i[0] for i in ins), b"".join(i[1] for i in ins),
+                                         b"".join(i[2] for i in ins), b"".join(p.transcript for p in provers), rng32)
+    if any(status):
+        raise R1CSError("non-canonical input scalar (status %s)" % list(status))
+    m = provers[0].circuit().m
+    return [(R1CSProof.from_bytes(pb), [coms[32 * (b * m + j):32 * (b * m + j + 1)] for j in range(m)]) for b, pb in enumerate(proofs)]
+
+
+class Witness:
+    """A recorded witness program as a bpgpu_r1cs_witness (host object; uploaded to each GPU on first use)."""
+
+    def __init__(self, circuit, n_free, src_left, src_right, rows):
+        L = lib()
+        self.n_free = n_free
+        row = [0]
+        kind, index, chal, power, coeff = [], [], [], [], []
+        for terms in rows:
+            for (k_, i_), ch, pw, cf in terms:
+                kind.append(k_)
+                index.append(i_)
+                chal.append(NO_CHALLENGE if ch is None else ch)
+                power.append(0 if ch is None else pw)
+                coeff.append((cf % L_ORDER).to_bytes(32, "little"))
+            row.append(len(kind))
+        u32 = C.c_uint32
+        arr = lambda xs: (u32 * max(len(xs), 1))(*xs)
+        self._h = C.c_void_p()
+        rc = L.bpgpu_r1cs_witness_create(circuit._h, n_free, arr(src_left), arr(src_right), len(rows), arr(row), len(kind), bytes(kind),
+                                         arr(index), arr(chal), arr(power), b"".join(coeff), C.byref(self._h))
+        if rc:
+            raise _lib.BpgpuError("bpgpu_r1cs_witness_create: %d" % rc)
+
+    def close(self):
+        if getattr(self, "_h", None) and self._h.value:
+            lib().bpgpu_r1cs_witness_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def prove_batch(self, ctx, circuit, nbatch, v, v_blinding, free_inputs, transcripts, rng32=None, want_transcripts=False):
+        """raw arrays: v, v_blinding nbatch x m x 32 bytes; free_inputs nbatch x n_free x 32; transcripts one 208-byte state or
+        nbatch of them.  Returns (proofs as bytes, commitments, status bytes[, transcripts])."""
+        TS = _lib.TRANSCRIPT_BYTES
+        assert len(v) == len(v_blinding) == 32 * circuit.m * nbatch and len(free_inputs) == 32 * self.n_free * nbatch
+        assert len(transcripts) in (TS, TS * nbatch) and (rng32 is None or len(rng32) == 32 * nbatch)
+        ts_stride = TS if len(transcripts) == TS * nbatch and nbatch > 1 else 0
+        stride = 1 + 32 * 14 + 32 * (2 * (circuit.padded_n.bit_length() - 1) + 2)
+        nb = max(nbatch, 1)
+        out = C.create_string_buffer(stride * nb)
+        lens = (C.c_uint32 * nb)()
+        coms = C.create_string_buffer(32 * circuit.m * nb + 1)
+        status = C.create_string_buffer(nb)
+        tso = C.create_string_buffer(TS * nb) if want_transcripts else None
+        rc = lib().bpgpu_r1cs_prove_batch(ctx.h, circuit._h, self._h, nbatch, v, v_blinding, free_inputs, transcripts, ts_stride, rng32,
+                                          out, stride, lens, coms, status, tso)
+        ctx._chk(rc)
+        proofs = [out.raw[b * stride:b * stride + lens[b]] for b in range(nbatch)]
+        res = (proofs, coms.raw[:32 * circuit.m * nbatch], status.raw[:nbatch])
+        return res + (tso.raw[:TS * nbatch],) if want_transcripts else res
+
+
 def flattened_constraints(descriptor, z, challenges):
     """flattened_constraints (verifier.rs:260-298) of a recorded descriptor for given z and challenge values:
     (wL, wR, wO, wV, wc).  Host code for checking the recording; the verifier computes this on the device."""
@@ -330,5 +505,9 @@ def lib():
         L.bpgpu_r1cs_circuit_shape.argtypes = [vp, C.POINTER(sz), C.POINTER(sz)]
         L.bpgpu_r1cs_verify_batch_ts.argtypes = [vp, vp, sz, u8p, sz, u32p, u8p, u8p, sz, u8p, u8p, u8p, u8p]
         L.bpgpu_pool_r1cs_verify_ts.argtypes = [vp, vp, sz, u8p, sz, u32p, u8p, u8p, sz, u8p, u8p, u8p, u8p]
+        L.bpgpu_r1cs_witness_create.argtypes = [vp, sz, u32p, u32p, sz, u32p, sz, u8p, u32p, u32p, u32p, u8p, C.POINTER(vp)]
+        L.bpgpu_r1cs_witness_destroy.argtypes = [vp]
+        L.bpgpu_r1cs_witness_destroy.restype = None
+        L.bpgpu_r1cs_prove_batch.argtypes = [vp, vp, vp, sz, u8p, u8p, u8p, u8p, sz, u8p, u8p, sz, u32p, u8p, u8p, u8p]
         L._r1cs_bound = True
     return L

@@ -405,6 +405,48 @@ int bpgpu_r1cs_verify_batch_ts_dev(bpgpu_ctx *ctx, const bpgpu_r1cs_circuit *cir
                                    const uint8_t *shared_transcript, const void *d_transcripts, const void *d_rng32,
                                    void *d_verdict, void *d_msm_out, void *d_transcripts_out, void *stream);
 
+/* ---- R1CS proof creation (r1cs::Prover::prove, src/r1cs/prover.rs:380-655) ------------------------------------------------
+ * The prover's gadget also computes the witness: a_L, a_R, a_O of every multiplier.  Phase-2 multipliers may take inputs from
+ * linear combinations that hold the phase-2 challenges, which exist only partway through the proof, so HOW each multiplier
+ * gets its inputs is recorded -- a bpgpu_r1cs_witness, beside the circuit -- and evaluated per proof on the device.
+ *   n_free     : free inputs per proof (the scalars the gadget assigned: allocate, allocate_multiplier)
+ *   src_left, src_right : n1 + n2 entries each, where a_L[i] / a_R[i] comes from: BPGPU_R1CS_SRC_FREE | j (free input j, each
+ *                used exactly once), an LC row index, or BPGPU_R1CS_SRC_ZERO (an allocate() pair left open: a_R = 0, so
+ *                a_O = 0, as prover.rs:121-140 leaves it).  a_O[i] = a_L[i] a_R[i].
+ *   rows       : CSR LC rows with the circuit's term encoding, evaluated as Prover::eval (prover.rs:340-356): plain sums, no
+ *                sign flip on V / ONE.  A row used by multiplier i may reference L / R / O of multipliers < i only, and no
+ *                challenge when i < n1.
+ * Host-only; validated like the circuit (BPGPU_ERR_INVALID_ARG). */
+typedef struct bpgpu_r1cs_witness bpgpu_r1cs_witness;
+#define BPGPU_R1CS_SRC_ZERO 0xffffffffu
+#define BPGPU_R1CS_SRC_FREE 0x80000000u
+int bpgpu_r1cs_witness_create(const bpgpu_r1cs_circuit *circuit, size_t n_free, const uint32_t *src_left, const uint32_t *src_right,
+                              size_t n_rows, const uint32_t *row_ptr, size_t n_terms, const uint8_t *term_kind,
+                              const uint32_t *term_index, const uint32_t *term_challenge, const uint32_t *term_power,
+                              const uint8_t *term_coeff, bpgpu_r1cs_witness **out);
+void bpgpu_r1cs_witness_destroy(bpgpu_r1cs_witness *witness);
+/* nbatch independent proofs of one recorded gadget: Prover::new(transcript), commit(v_j, v_blinding_j) for j < m, the gadget
+ * with the free inputs, prove(bp_gens) with the context's generators.
+ *   v, v_blinding     : nbatch x m x 32 bytes; free_inputs: nbatch x n_free x 32 bytes (canonical scalars)
+ *   transcripts       : the caller's transcript(s) BEFORE Prover::new: one 208-byte state (transcript_stride 0) or nbatch
+ *                       (stride BPGPU_TRANSCRIPT_BYTES)
+ *   rng32             : nbatch x 32 bytes -- what TranscriptRngBuilder::finalize takes from thread_rng() (prover.rs:411) --
+ *                       or NULL: the OS generator.  The TranscriptRng is rekeyed with every v_blinding first (merlin 2:
+ *                       meta_ad(b"v_blinding"), meta_ad(u32le(32), more), KEY(v_blinding)); the draws follow prover.rs's order.
+ *   proofs_out        : nbatch x proof_stride bytes, R1CSProof::to_bytes (proof.rs:83-108; version 0 exactly when A_I2, A_O2,
+ *                       S2 are all the identity); proof_lens_out[p] its length.  proof_stride >= 1 + 32 (14 + 2 lg(padded_n) + 2)
+ *                       (11 instead of 14 when n2 = 0).
+ *   commitments_out   : nbatch x m x 32 bytes, the V_j = v_j B + v_blinding_j B_blinding
+ *   status_out        : nbatch bytes, BPGPU_MSM_BAD_SCALAR for a non-canonical input scalar (that proof is void), else 0
+ *   transcripts_out   : optional nbatch x 208 bytes, each transcript as prove leaves it (after the last IPP challenge)
+ * BPGPU_ERR_NO_GENS when padded_n > gens_capacity (InvalidGeneratorsLength).  A witness that does not satisfy the constraints
+ * still yields a proof, as in the reference; the verifier rejects it.  With the option prover_constant_time the V_j, A_I, A_O,
+ * S and T_i commitments take the constant-time walk (byte-identical proofs).  Secrets at rest: as the other provers. */
+int bpgpu_r1cs_prove_batch(bpgpu_ctx *ctx, const bpgpu_r1cs_circuit *circuit, const bpgpu_r1cs_witness *witness, size_t nbatch,
+                           const uint8_t *v, const uint8_t *v_blinding, const uint8_t *free_inputs, const uint8_t *transcripts,
+                           size_t transcript_stride, const uint8_t *rng32, uint8_t *proofs_out, size_t proof_stride,
+                           uint32_t *proof_lens_out, uint8_t *commitments_out, uint8_t *status_out, uint8_t *transcripts_out);
+
 /* nbatch independent calls of
  *   LinearProof::create(&mut transcript, &mut rng, &C, r, a_vec, b_vec, G_vec, &F, &B).to_bytes()
  * (src/linear_proof.rs:40-173), all of one size n (a power of two) over the same G, F, B.  Per round the reference forms
@@ -493,7 +535,7 @@ int bpgpu_ipp_create_batch(bpgpu_ctx *ctx, size_t n, size_t nbatch, const uint8_
  * always adds; csrc/msm_fixed.h).  Proofs are byte-identical either way.  The inner-product rounds stay variable-time, as in the
  * reference (vartime_multiscalar_mul at ipp.rs:87-178).  Cost: ~2x the prover's time at (64, 1).
  * Secrets at rest: like the reference's parties (zeroize on Drop, party.rs:148-260), every prover entry point
- * (bpgpu_rangeproof_prove_batch, bpgpu_ipp_create_batch, bpgpu_linear_create_batch) clears what it staged before it returns,
+ * (bpgpu_rangeproof_prove_batch, bpgpu_ipp_create_batch, bpgpu_linear_create_batch, bpgpu_r1cs_prove_batch) clears what it staged before it returns,
  * on success and on every error path: the context's device IO buffer, the provers' working sets and the MSM arena (window
  * digits of secret scalars) on the stream behind the last copy, then the secret part of the pinned host staging block.
  * Not cleared: the caller's own buffers. */
