@@ -157,6 +157,9 @@ struct bpgpu_ctx {
     size_t ipp_cap = 0;
     char *rpp_buf = nullptr;                 // working set of the batched range-proof prover
     size_t rpp_cap = 0;
+    char *r1rlc_buf = nullptr;               // combined term list, accumulators and weights of the batch-combined R1CS check
+    size_t r1rlc_cap = 0;
+    uint32_t r1rlc_max_terms = 0;            // option "r1cs_rlc_max_terms": unique terms per combination (0 = R1_RLC_MAX_TERMS)
     uint32_t bucket_min = 0;                 // terms per MSM from which the bucket path is taken (0 = BK_MIN_TERMS; huge = never)
     int bucket_chain = 0;                    // option "bucket_chain": 0 = the fused chain (bucket2.h) where it applies, 1 = bucket.h's chain everywhere (A/B)
     int bucket_lanes = 0;                    // option "bucket_lanes": lanes of a (MSM, window) workgroup of the fused chain (0 = by batch width; 64, 128, 256)
@@ -456,6 +459,7 @@ void bpgpu_ctx_destroy(bpgpu_ctx *c) {
     if (c->io_dev) hipFree(c->io_dev);
     if (c->ipp_buf) hipFree(c->ipp_buf);
     if (c->rpp_buf) hipFree(c->rpp_buf);
+    if (c->r1rlc_buf) hipFree(c->r1rlc_buf);
     if (c->pin) hipHostFree(c->pin);
     for (char *q : c->pin_retired) hipHostFree(q);
     if (c->order_ev) hipEventDestroy(c->order_ev);
@@ -602,6 +606,11 @@ int bpgpu_ctx_set_option(bpgpu_ctx *c, const char *key, int64_t value) {
         c->bucket_lanes = (int)value;
         return BPGPU_OK;
     }
+    if (!strcmp(key, "r1cs_rlc_max_terms")) {
+        if (value < 0 || value > R1_RLC_MAX_TERMS) return fail(c, BPGPU_ERR_INVALID_ARG, "r1cs_rlc_max_terms must be 0 (default) .. 2^24");
+        c->r1rlc_max_terms = (uint32_t)value;
+        return BPGPU_OK;
+    }
     return fail(c, BPGPU_ERR_INVALID_ARG, "unknown option %s", key);
 }
 
@@ -628,6 +637,7 @@ int bpgpu_ctx_get_option(bpgpu_ctx *c, const char *key, int64_t *value) {
     else if (!strcmp(key, "bucket_fast_tail")) *value = c->fast_tail;
     else if (!strcmp(key, "exponent_pairs")) *value = c->exp_pairs;
     else if (!strcmp(key, "fb_walk_waves")) *value = c->walk_waves ? c->walk_waves : 2048;
+    else if (!strcmp(key, "r1cs_rlc_max_terms")) *value = c->r1rlc_max_terms ? c->r1rlc_max_terms : R1_RLC_MAX_TERMS;
     else if (!strcmp(key, "staging_residue")) {
         // test hook: non-zero bytes left in the persistent staging buffers (pinned block, device IO buffer, prover working sets,
         // arena) -- 0 after a prover entry point has returned (prover_exit)
@@ -3841,9 +3851,18 @@ static int r1cs_circuit_on(bpgpu_ctx *c, const bpgpu_r1cs_circuit *cci, char **d
     return BPGPU_OK;
 }
 
-static int r1cs_verify_dev_locked(bpgpu_ctx *c, const bpgpu_r1cs_circuit *ci, size_t nbatch, const void *d_proofs, size_t proof_stride,
-                                  const void *d_lens, const void *d_coms, const uint8_t *shared_ts, const void *d_ts, const void *d_rng32,
-                                  void *d_verdict, void *d_msm_out, void *d_ts_out, hipStream_t s) {
+// what launches 1-3 of a batch leave in c->ipp_buf for its mega-checks: generator rows (nbatch x (2 pn + 2)), per-proof scalars and
+// points (nbatch x U), status words; then room for the MSM's status bytes and outputs
+struct r1cs_staged {
+    r1cs_shape sh;
+    char *gen, *usc, *upt, *stat, *mst, *out;
+    size_t sz_mo;   // bytes of mst + out
+};
+
+// launches 1-3 of one batch against one circuit (k_r1cs_front, k_r1cs_flatten, k_r1cs_finish): everything before the mega-check
+static int r1cs_front_dev_locked(bpgpu_ctx *c, const bpgpu_r1cs_circuit *ci, size_t nbatch, const void *d_proofs, size_t proof_stride,
+                                 const void *d_lens, const void *d_coms, const uint8_t *shared_ts, const void *d_ts, const void *d_rng32,
+                                 void *d_ts_out, hipStream_t s, r1cs_staged &stg) {
     if (shared_ts && !ts_state_ok(shared_ts)) return fail(c, BPGPU_ERR_INVALID_ARG, "malformed transcript state");
     if (!c->d_table) return fail(c, BPGPU_ERR_NO_GENS, "generators not loaded");
     if (proof_stride > 0xffffffu || nbatch > 0x7fffffffu / 64) return fail(c, BPGPU_ERR_INVALID_ARG, "batch too large");
@@ -3894,21 +3913,40 @@ static int r1cs_verify_dev_locked(bpgpu_ctx *c, const bpgpu_r1cs_circuit *ci, si
            (const uint8_t *)d_coms, shared_ts ? (const uint32_t *)nullptr : (const uint32_t *)d_ts, (const uint8_t *)d_rng32,
            (const uint32_t *)(dc + ci->off_lbl_off), (const uint8_t *)(dc + ci->off_lbl), (uint32_t *)d_f, (uint32_t *)d_usc, (uint32_t *)d_upt,
            (uint32_t *)d_ts_out, (uint32_t *)d_stat);
-    if (sh.gens_short) {   // every proof stopped in launch 1 (or earlier): nothing to multiply
-        HIPCHK(c, hipMemsetAsync(d_mst, 0, sz_b + sz_o, s));
-    } else {
+    if (!sh.gens_short) {   // (gens_short: every proof stopped in launch 1 or earlier)
         const uint32_t nt = (uint32_t)(ncol * nbatch);
         LAUNCH(c, s, "r1cs_flatten", k_r1cs_flatten, (nt + 63) / 64, 64, nt, sh, (const uint32_t *)dc, (const r1cs_ent *)(dc + ci->off_ents),
                (const uint32_t *)d_stat, (uint32_t *)d_f, (uint32_t *)d_gen, (uint32_t *)d_usc, (uint32_t *)d_dt);
         LAUNCH(c, s, "r1cs_finish", k_r1cs_finish, nb32, 64, sh, (const uint32_t *)d_stat, (const uint32_t *)d_dt, (const uint32_t *)d_f, (uint32_t *)d_gen);
-        rc = msm_shared_dev_locked(c, sh.pn, 1, nbatch, sh.U, d_gen, d_usc, d_upt, d_out, d_mst, nullptr, s);
+    }
+    stg.sh = sh;
+    stg.gen = d_gen, stg.usc = d_usc, stg.upt = d_upt, stg.stat = d_stat, stg.mst = d_mst, stg.out = d_out;
+    stg.sz_mo = sz_b + sz_o;
+    return BPGPU_OK;
+}
+
+// the per-proof mega-checks of a staged batch and its verdicts
+static int r1cs_tail_dev_locked(bpgpu_ctx *c, const r1cs_staged &stg, size_t nbatch, void *d_verdict, void *d_msm_out, hipStream_t s) {
+    if (stg.sh.gens_short) {   // every proof stopped in launch 1 (or earlier): nothing to multiply
+        HIPCHK(c, hipMemsetAsync(stg.mst, 0, stg.sz_mo, s));
+    } else {
+        const int rc = msm_shared_dev_locked(c, stg.sh.pn, 1, nbatch, stg.sh.U, stg.gen, stg.usc, stg.upt, stg.out, stg.mst, nullptr, s);
         if (rc) return rc;
     }
-    LAUNCH(c, s, "r1cs_verdict", k_ipp_verdict, (nb32 + 63) / 64, 64, nb32, (const uint32_t *)d_stat, (const uint8_t *)d_mst, (const uint32_t *)d_out,
+    const uint32_t nb32 = (uint32_t)nbatch;
+    LAUNCH(c, s, "r1cs_verdict", k_ipp_verdict, (nb32 + 63) / 64, 64, nb32, (const uint32_t *)stg.stat, (const uint8_t *)stg.mst, (const uint32_t *)stg.out,
            (uint8_t *)d_verdict);
-    if (d_msm_out) HIPCHK(c, hipMemcpyAsync(d_msm_out, d_out, nbatch * 32, hipMemcpyDeviceToDevice, s));
+    if (d_msm_out) HIPCHK(c, hipMemcpyAsync(d_msm_out, stg.out, nbatch * 32, hipMemcpyDeviceToDevice, s));
     HIPCHK(c, hipGetLastError());
     return BPGPU_OK;
+}
+
+static int r1cs_verify_dev_locked(bpgpu_ctx *c, const bpgpu_r1cs_circuit *ci, size_t nbatch, const void *d_proofs, size_t proof_stride,
+                                  const void *d_lens, const void *d_coms, const uint8_t *shared_ts, const void *d_ts, const void *d_rng32,
+                                  void *d_verdict, void *d_msm_out, void *d_ts_out, hipStream_t s) {
+    r1cs_staged stg;
+    const int rc = r1cs_front_dev_locked(c, ci, nbatch, d_proofs, proof_stride, d_lens, d_coms, shared_ts, d_ts, d_rng32, d_ts_out, s, stg);
+    return rc ? rc : r1cs_tail_dev_locked(c, stg, nbatch, d_verdict, d_msm_out, s);
 }
 
 extern "C" int bpgpu_r1cs_verify_batch_ts_dev(bpgpu_ctx *c, const bpgpu_r1cs_circuit *circuit, size_t nbatch, const void *d_proofs, size_t proof_stride,
@@ -3973,6 +4011,208 @@ extern "C" int bpgpu_r1cs_verify_batch_ts(bpgpu_ctx *c, const bpgpu_r1cs_circuit
     memcpy(verdict, h_out, nbatch);
     if (msm_out) memcpy(msm_out, h_out + sz_v, nbatch * 32);
     if (transcripts_out) memcpy(transcripts_out, h_out + sz_v + sz_o, nbatch * TS);
+    return BPGPU_OK;
+}
+
+// ---- batch-combined R1CS verification (r1cs_rlc.h; an ADDITIONAL entry point, as bpgpu_rangeproof_verify_rlc) --------------
+static int r1rlc_reserve(bpgpu_ctx *c, size_t need) {
+    if (c->r1rlc_cap >= need) return BPGPU_OK;
+    HIPCHK(c, hipDeviceSynchronize());
+    if (c->r1rlc_buf) HIPCHK(c, hipFree(c->r1rlc_buf));
+    c->r1rlc_buf = nullptr;
+    c->r1rlc_cap = 0;
+    if (hipMalloc((void **)&c->r1rlc_buf, need + need / 4) != hipSuccess) return fail(c, BPGPU_ERR_HIP, "out of device memory (%zu bytes of combined list)", need + need / 4);
+    c->r1rlc_cap = need + need / 4;
+    return BPGPU_OK;
+}
+
+// one group's inputs on the device; its proof i is proof gp0 + i of the call
+struct r1cs_rlc_group {
+    const bpgpu_r1cs_circuit *ci;
+    size_t nbatch, proof_stride, gp0;
+    const char *d_proofs, *d_lens, *d_coms, *d_ts;   // d_ts: nbatch transcript states, or null with shared_ts (a host pointer)
+    const uint8_t *shared_ts;
+};
+
+// R = sum_i rho_i MegaCheck_i over every group: per slice of a group launches 1-3 (r1cs_front_dev_locked) and the weigh launch, per
+// combination of at most r1cs_rlc_max_terms unique terms the reduction and ONE shared-generator MSM over PN = max padded_n, then the sum
+// of the combinations and the verdicts (undecided where R is not the identity).  d_rng32: every proof's 32 bytes (the caller's or drawn).
+static int r1cs_rlc_dev_locked(bpgpu_ctx *c, const std::vector<r1cs_rlc_group> &gr, size_t total, const char *d_rng32, const void *d_weights64,
+                               uint8_t *d_verdict, uint8_t *d_batch, char *d_ts_out, hipStream_t s) {
+    if (!c->d_table) return fail(c, BPGPU_ERR_NO_GENS, "generators not loaded");
+    const size_t TS = BPGPU_TRANSCRIPT_BYTES;
+    const size_t cap = c->r1rlc_max_terms ? c->r1rlc_max_terms : R1_RLC_MAX_TERMS;
+    uint32_t PN = 1;   // (a group whose padded_n exceeds the generators stops in launch 1 and adds no generator term)
+    for (const auto &g : gr)
+        if (g.ci->pn <= c->gens_capacity && g.ci->pn > PN) PN = g.ci->pn;
+    // the plan: slices in call order, each inside one combination (a new combination where the next slice would pass `cap`)
+    struct slice_plan {
+        size_t grp, first, count, comb, u0;
+    };
+    std::vector<slice_plan> plan;
+    std::vector<size_t> comb_terms;
+    for (size_t gi = 0; gi < gr.size(); gi++) {
+        const size_t U = 11 + gr[gi].ci->m + 2 * (size_t)gr[gi].ci->k;
+        const size_t per = std::max<size_t>(1, std::min<size_t>(R1_RLC_SLICE, cap / U));
+        for (size_t f = 0; f < gr[gi].nbatch; f += per) {
+            const size_t cnt = std::min(per, gr[gi].nbatch - f);
+            if (comb_terms.empty() || (comb_terms.back() && comb_terms.back() + cnt * U > cap)) comb_terms.push_back(0);
+            plan.push_back({gi, f, cnt, comb_terms.size() - 1, comb_terms.back()});
+            comb_terms.back() += cnt * U;
+        }
+    }
+    size_t list_max = 1;
+    for (size_t t : comb_terms) list_max = std::max(list_max, t);
+    const size_t ncomb = comb_terms.size(), nrows = 2 * (size_t)PN + 2;
+    const size_t sz_l = align_up(list_max * 32), sz_acc = align_up(nrows * 80), sz_g = align_up(nrows * 32), sz_rho = align_up(total * 32),
+                 sz_st = align_up(total * 4), sz_parts = align_up(ncomb * 32), sz_pst = align_up(ncomb + 64), sz_res = align_up(64);
+    int rc = r1rlc_reserve(c, 2 * sz_l + sz_acc + sz_g + sz_rho + sz_st + sz_parts + sz_pst + sz_res);
+    if (rc) return rc;
+    char *d_csc = c->r1rlc_buf, *d_cpt = d_csc + sz_l, *d_acc = d_cpt + sz_l, *d_gen = d_acc + sz_acc, *d_rho = d_gen + sz_g, *d_gst = d_rho + sz_rho,
+         *d_parts = d_gst + sz_st, *d_pst = d_parts + sz_parts, *d_res = d_pst + sz_pst;
+    r1_rlc_key key;
+    memset(&key, 0, sizeof key);
+    if (!d_weights64 && !bp::fast_random((uint8_t *)key.w, 32)) return fail(c, BPGPU_ERR_HIP, "getrandom failed");   // (never the test seed: weights stay unpredictable)
+    const uint32_t n32 = (uint32_t)total;
+    LAUNCH(c, s, "r1cs_rlc_rho", k_r1cs_rlc_rho, (n32 + 63) / 64, 64, n32, (const uint8_t *)d_weights64, key, (uint32_t *)d_rho);
+    for (size_t i = 0; i < plan.size(); i++) {
+        const slice_plan &sp = plan[i];
+        const r1cs_rlc_group &g = gr[sp.grp];
+        if (i == 0 || plan[i - 1].comb != sp.comb) HIPCHK(c, hipMemsetAsync(d_acc, 0, sz_acc, s));
+        const size_t gp0 = g.gp0 + sp.first;
+        r1cs_staged stg;
+        rc = r1cs_front_dev_locked(c, g.ci, sp.count, g.d_proofs + sp.first * g.proof_stride, g.proof_stride, g.d_lens + sp.first * 4,
+                                   g.d_coms ? g.d_coms + sp.first * g.ci->m * 32 : nullptr, g.shared_ts, g.d_ts ? g.d_ts + sp.first * TS : nullptr,
+                                   d_rng32 + gp0 * 32, d_ts_out ? d_ts_out + gp0 * TS : nullptr, s, stg);
+        if (rc) return rc;
+        // a slice whose padded_n exceeds the generators stopped in launch 1 and has no generator terms (its pn may exceed PN: no row of it)
+        r1_rlc_slice sl;
+        sl.nproofs = (uint32_t)sp.count, sl.nstride = (uint32_t)((sp.count + 63) / 64 * 64), sl.U = stg.sh.U;
+        sl.ngen = stg.sh.gens_short ? 0u : 2 * stg.sh.pn + 2, sl.pn = stg.sh.pn, sl.PN = PN, sl.gp0 = (uint32_t)gp0, sl.u0 = (uint32_t)sp.u0;
+        if (sl.ngen && sl.pn > PN) return fail(c, BPGPU_ERR_INVALID_ARG, "padded_n %u above the combination's %u", sl.pn, PN);   // (PN covers every such group)
+        const uint64_t nt = (uint64_t)sl.nstride * (sl.U + sl.ngen);   // (a multiple of 64: whole wavefronts)
+        if (nt > 0x7fffffffull) return fail(c, BPGPU_ERR_INVALID_ARG, "batch too large for this circuit");
+        LAUNCH(c, s, "r1cs_rlc_weigh", k_r1cs_rlc_weigh, (uint32_t)(nt / 64), 64, sl, (const uint32_t *)stg.stat, (const uint32_t *)d_rho, (const uint32_t *)stg.gen,
+               (const uint32_t *)stg.usc, (const uint32_t *)stg.upt, (uint32_t *)d_csc, (uint32_t *)d_cpt, (uint32_t *)d_gst, (unsigned long long *)d_acc);
+        if (i + 1 == plan.size() || plan[i + 1].comb != sp.comb) {   // the combination is complete: its generator row, then its MSM
+            LAUNCH(c, s, "r1cs_rlc_reduce", k_r1cs_rlc_reduce, (uint32_t)((nrows + 63) / 64), 64, (uint32_t)nrows, (const unsigned long long *)d_acc,
+                   (uint32_t *)d_gen);
+            rc = msm_shared_dev_locked(c, PN, 1, 1, comb_terms[sp.comb], d_gen, d_csc, d_cpt, d_parts + 32 * sp.comb, d_pst + sp.comb, nullptr, s);
+            if (rc) return rc;
+        }
+    }
+    LAUNCH(c, s, "r1cs_rlc_sum", k_r1cs_rlc_sum, 1, 64, (uint32_t)ncomb, (const uint32_t *)d_parts, (const uint8_t *)d_pst, (uint32_t *)d_res);
+    LAUNCH(c, s, "r1cs_rlc_verdict", k_r1cs_rlc_verdict, (n32 + 63) / 64, 64, n32, (const uint32_t *)d_gst, (const uint32_t *)d_res, d_verdict, d_batch);
+    HIPCHK(c, hipGetLastError());
+    return BPGPU_OK;
+}
+
+extern "C" int bpgpu_r1cs_verify_rlc(bpgpu_ctx *c, size_t ngroups, const bpgpu_r1cs_circuit *const *circuits, const size_t *nbatch,
+                                     const uint8_t *const *proofs, const size_t *proof_stride, const uint32_t *const *proof_lens,
+                                     const uint8_t *const *commitments, const uint8_t *const *transcripts, const size_t *transcript_stride,
+                                     const uint8_t *rng32, const uint8_t *weights64, uint8_t *verdict, uint8_t *batch_out, uint8_t *transcripts_out) {
+    if (!c || ngroups == 0 || !circuits || !nbatch || !proofs || !proof_stride || !proof_lens || !commitments || !transcripts || !transcript_stride)
+        return BPGPU_ERR_INVALID_ARG;
+    const size_t TS = BPGPU_TRANSCRIPT_BYTES;
+    size_t total = 0;
+    for (size_t g = 0; g < ngroups; g++) {
+        if (!circuits[g]) return BPGPU_ERR_INVALID_ARG;
+        if (nbatch[g] == 0) continue;
+        if (!proofs[g] || !proof_lens[g] || !transcripts[g] || (circuits[g]->m && !commitments[g])) return BPGPU_ERR_INVALID_ARG;
+        if (transcript_stride[g] != 0 && transcript_stride[g] != TS)
+            return fail(c, BPGPU_ERR_INVALID_ARG, "transcript_stride of group %zu neither 0 nor BPGPU_TRANSCRIPT_BYTES", g);
+        if (proof_stride[g] > 0xffffffu || nbatch[g] > 0x7fffffffu / 64) return fail(c, BPGPU_ERR_INVALID_ARG, "batch too large");
+        for (size_t b = 0; b < (transcript_stride[g] ? nbatch[g] : 1); b++)
+            if (!ts_state_ok(transcripts[g] + b * TS)) return fail(c, BPGPU_ERR_INVALID_ARG, "malformed transcript state %zu of group %zu", b, g);
+        total += nbatch[g];
+    }
+    if (total == 0) {
+        if (batch_out) memset(batch_out, 0, 33);
+        return BPGPU_OK;
+    }
+    if (!verdict) return BPGPU_ERR_INVALID_ARG;
+    if (total > (1u << 24)) return fail(c, BPGPU_ERR_INVALID_ARG, "batch too large");
+    std::lock_guard<std::mutex> lk(c->mu);
+    HIPCHK(c, hipSetDevice(c->device));
+    // staging: per group proofs, lengths, commitments, per-proof transcripts; then every proof's rng bytes and weights; then the outputs
+    std::vector<size_t> off(ngroups * 4 + 1, 0);
+    size_t in = 0;
+    for (size_t g = 0; g < ngroups; g++) {
+        const size_t nb = nbatch[g];
+        off[4 * g] = in, in += nb ? align_up(nb * proof_stride[g] + 64) : 0;
+        off[4 * g + 1] = in, in += nb ? align_up(nb * 4) : 0;
+        off[4 * g + 2] = in, in += nb ? align_up(nb * circuits[g]->m * 32 + 64) : 0;
+        off[4 * g + 3] = in, in += (nb && transcript_stride[g]) ? align_up(nb * TS) : 0;
+    }
+    const size_t off_r = in, off_w = off_r + align_up(total * 32), sz_in = off_w + (weights64 ? align_up(total * 64) : 0);
+    const size_t sz_v = align_up(total), sz_b = align_up(64), sz_to = transcripts_out ? align_up(total * TS) : 0, sz_out = sz_v + sz_b + sz_to;
+    hipStream_t s = c->stream;
+    int rc = ctx_enter(c, s);
+    if (rc) return rc;
+    rc = io_reserve(c, sz_in + sz_out);
+    if (rc) return rc;
+    char *h = nullptr;
+    rc = pin_alloc(c, s, sz_in + sz_out, &h);
+    if (rc) return rc;
+    char *d = c->io_dev;
+    std::vector<r1cs_rlc_group> gr;
+    size_t gp = 0;
+    for (size_t g = 0; g < ngroups; g++) {
+        const size_t nb = nbatch[g], m = circuits[g]->m;
+        if (nb == 0) continue;
+        memcpy(h + off[4 * g], proofs[g], nb * proof_stride[g]);
+        memcpy(h + off[4 * g + 1], proof_lens[g], nb * 4);
+        if (m) memcpy(h + off[4 * g + 2], commitments[g], nb * m * 32);
+        if (transcript_stride[g]) memcpy(h + off[4 * g + 3], transcripts[g], nb * TS);
+        gr.push_back({circuits[g], nb, proof_stride[g], gp, d + off[4 * g], d + off[4 * g + 1], m ? d + off[4 * g + 2] : nullptr,
+                      transcript_stride[g] ? d + off[4 * g + 3] : nullptr, transcript_stride[g] ? nullptr : transcripts[g]});
+        gp += nb;
+    }
+    if (rng32) {
+        memcpy(h + off_r, rng32, total * 32);
+    } else {   // drawn once, as the per-proof path's seeded mode draws them (R1_RNG_DOMAIN), for the combination and any fallback alike
+        uint32_t seed[8];
+        if (c->test_seed_set) memcpy(seed, c->test_seed, 32);
+        else if (!bp::fast_random((uint8_t *)seed, 32)) return fail(c, BPGPU_ERR_HIP, "getrandom failed");
+        for (size_t p = 0; p < total; p++) {
+            uint32_t kw[16];
+            chacha20_block(seed, (uint64_t)p, R1_RNG_DOMAIN, 0u, kw);
+            memcpy(h + off_r + 32 * p, kw, 32);   // (little-endian words: the bytes k_r1cs_front takes from them)
+        }
+    }
+    if (weights64) memcpy(h + off_w, weights64, total * 64);
+    HIPCHK(c, hipMemcpyAsync(d, h, sz_in, hipMemcpyHostToDevice, s));
+    char *d_v = d + sz_in, *d_b = d_v + sz_v, *d_to = d_b + sz_b;
+    char *h_out = h + sz_in;
+    rc = r1cs_rlc_dev_locked(c, gr, total, d + off_r, weights64 ? d + off_w : nullptr, (uint8_t *)d_v, (uint8_t *)d_b, transcripts_out ? d_to : nullptr, s);
+    if (!rc && hipMemcpyAsync(h_out, d_v, sz_out, hipMemcpyDeviceToHost, s) != hipSuccess) rc = fail(c, BPGPU_ERR_HIP, "D2H copy failed");
+    int rc2 = ctx_leave(c, s), rc3 = host_wait(c, s);
+    if (rc || rc2 || rc3) return rc ? rc : (rc2 ? rc2 : rc3);
+    if ((uint8_t)h_out[sz_v] != 0) {
+        // R is not the identity, or a point did not decode: every group again through the per-proof chain, with the same rng bytes
+        // (inputs are still on the device; the transcripts it leaves are the ones already copied out)
+        uint8_t bo[33];
+        memcpy(bo, h_out + sz_v, 33);
+        rc = ctx_enter(c, s, true);
+        if (rc) return rc;
+        for (const auto &g : gr) {   // (in slices of R1_RLC_SLICE proofs, as above: the staging stays bounded)
+            for (size_t f = 0; f < g.nbatch && !rc; f += R1_RLC_SLICE) {
+                const size_t cnt = std::min<size_t>(R1_RLC_SLICE, g.nbatch - f);
+                rc = r1cs_verify_dev_locked(c, g.ci, cnt, g.d_proofs + f * g.proof_stride, g.proof_stride, g.d_lens + f * 4,
+                                            g.d_coms ? g.d_coms + f * g.ci->m * 32 : nullptr, g.shared_ts, g.d_ts ? g.d_ts + f * TS : nullptr,
+                                            d + off_r + 32 * (g.gp0 + f), d_v + g.gp0 + f, nullptr, nullptr, s);
+            }
+            if (rc) break;
+        }
+        if (!rc && hipMemcpyAsync(h_out, d_v, sz_v, hipMemcpyDeviceToHost, s) != hipSuccess) rc = fail(c, BPGPU_ERR_HIP, "D2H copy failed");
+        rc2 = ctx_leave(c, s);
+        rc3 = host_wait(c, s);
+        if (rc || rc2 || rc3) return rc ? rc : (rc2 ? rc2 : rc3);
+        memcpy(h_out + sz_v, bo, 33);
+    }
+    memcpy(verdict, h_out, total);
+    if (batch_out) memcpy(batch_out, h_out + sz_v, 33);
+    if (transcripts_out) memcpy(transcripts_out, h_out + sz_v + sz_b, total * TS);
     return BPGPU_OK;
 }
 
@@ -4308,6 +4548,21 @@ int r1cs_call_run(bpgpu_ctx *c, void *arg) {
     return bpgpu_r1cs_verify_batch_ts(c, a->circuit, a->nbatch, a->proofs, a->proof_stride, a->proof_lens, a->commitments, a->transcripts,
                                       a->transcript_stride, a->rng32, a->verdict, a->msm_out, a->transcripts_out);
 }
+struct r1cs_rlc_call {
+    size_t ngroups;
+    const bpgpu_r1cs_circuit *const *circuits;
+    const size_t *nbatch, *proof_stride, *transcript_stride;
+    const uint8_t *const *proofs;
+    const uint32_t *const *proof_lens;
+    const uint8_t *const *commitments, *const *transcripts;
+    const uint8_t *rng32, *weights64;
+    uint8_t *verdict, *batch_out, *transcripts_out;
+};
+int r1cs_rlc_call_run(bpgpu_ctx *c, void *arg) {
+    const r1cs_rlc_call *a = (const r1cs_rlc_call *)arg;
+    return bpgpu_r1cs_verify_rlc(c, a->ngroups, a->circuits, a->nbatch, a->proofs, a->proof_stride, a->proof_lens, a->commitments, a->transcripts,
+                                 a->transcript_stride, a->rng32, a->weights64, a->verdict, a->batch_out, a->transcripts_out);
+}
 }  // namespace
 
 extern "C" int bpgpu_pool_r1cs_verify_ts(bpgpu_pool *pool, const bpgpu_r1cs_circuit *circuit, size_t nbatch, const uint8_t *proofs, size_t proof_stride,
@@ -4316,4 +4571,23 @@ extern "C" int bpgpu_pool_r1cs_verify_ts(bpgpu_pool *pool, const bpgpu_r1cs_circ
     if (!pool || !circuit) return BPGPU_ERR_INVALID_ARG;
     r1cs_call a{circuit, nbatch, proof_stride, transcript_stride, proofs, commitments, transcripts, rng32, proof_lens, verdict, msm_out, transcripts_out};
     return bpgpu_internal_pool_run_on_context(pool, nbatch, verdict, r1cs_call_run, &a);
+}
+
+extern "C" int bpgpu_pool_r1cs_verify_rlc(bpgpu_pool *pool, size_t ngroups, const bpgpu_r1cs_circuit *const *circuits, const size_t *nbatch,
+                                          const uint8_t *const *proofs, const size_t *proof_stride, const uint32_t *const *proof_lens,
+                                          const uint8_t *const *commitments, const uint8_t *const *transcripts, const size_t *transcript_stride,
+                                          const uint8_t *rng32, const uint8_t *weights64, uint8_t *verdict, uint8_t *batch_out, uint8_t *transcripts_out) {
+    if (!pool || ngroups == 0 || !circuits || !nbatch || !proofs || !proof_stride || !proof_lens || !commitments || !transcripts || !transcript_stride)
+        return BPGPU_ERR_INVALID_ARG;
+    size_t total = 0;
+    for (size_t g = 0; g < ngroups; g++) total += nbatch[g];
+    if (total == 0) {   // (as the context form: nothing to combine)
+        for (size_t g = 0; g < ngroups; g++)
+            if (!circuits[g]) return BPGPU_ERR_INVALID_ARG;
+        if (batch_out) memset(batch_out, 0, 33);
+        return BPGPU_OK;
+    }
+    r1cs_rlc_call a{ngroups, circuits, nbatch, proof_stride, transcript_stride, proofs, proof_lens, commitments, transcripts, rng32, weights64,
+                    verdict, batch_out, transcripts_out};
+    return bpgpu_internal_pool_run_on_context(pool, total, verdict, r1cs_rlc_call_run, &a);
 }

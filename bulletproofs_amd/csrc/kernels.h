@@ -19,6 +19,7 @@
 #include "linear_prover.h"
 #include "r1cs.h"
 #include "r1cs_prover.h"
+#include "r1cs_rlc.h"
 
 #define BP_BLOCK 64   // one wavefront per workgroup: under contention a CU rarely has room for four waves of one group at once (256: -8% at 48 streams)
 #define FB_BLOCK 64
@@ -78,6 +79,11 @@ __global__ void k_aud_verdict(uint32_t n, const uint32_t *status, const uint8_t 
 __global__ void k_r1cs_front(r1cs_shape sh, rp_strobe_init init, const uint8_t *proofs, const uint32_t *proof_lens, const uint8_t *commitments, const uint32_t *ts_in, const uint8_t *rng32, const uint32_t *lbl_off, const uint8_t *lbl, uint32_t *fields, uint32_t *uniq_sc, uint32_t *uniq_pt, uint32_t *ts_out, uint32_t *status);
 __global__ void k_r1cs_flatten(uint32_t nthreads, r1cs_shape sh, const uint32_t *col_ptr, const r1cs_ent *ents, const uint32_t *status, uint32_t *fields, uint32_t *gen_sc, uint32_t *uniq_sc, uint32_t *dterm);
 __global__ void k_r1cs_finish(r1cs_shape sh, const uint32_t *status, const uint32_t *dterm, const uint32_t *fields, uint32_t *gen_sc);
+__global__ void k_r1cs_rlc_rho(uint32_t n, const uint8_t *weights64, r1_rlc_key key, uint32_t *rho);
+__global__ void k_r1cs_rlc_weigh(r1_rlc_slice sl, const uint32_t *status, const uint32_t *rho, const uint32_t *gen_sc, const uint32_t *uniq_sc, const uint32_t *uniq_pt, uint32_t *comb_sc, uint32_t *comb_pt, uint32_t *gstatus, unsigned long long *acc);
+__global__ void k_r1cs_rlc_reduce(uint32_t nrows, const unsigned long long *acc, uint32_t *gen_row);
+__global__ void k_r1cs_rlc_sum(uint32_t ncomb, const uint32_t *parts, const uint8_t *part_status, uint32_t *res);
+__global__ void k_r1cs_rlc_verdict(uint32_t n, const uint32_t *gstatus, const uint32_t *res, uint8_t *verdict, uint8_t *batch_out);
 // k_r1cs_prove.hip
 __global__ void k_r1p_inputs(uint32_t nthreads, r1p_shape sh, const uint8_t *v, const uint8_t *vb, const uint8_t *freev, uint32_t *vrows, uint32_t *status);
 __global__ void k_r1p_rng(r1p_shape sh, uint32_t *ts, const uint32_t *vout, const uint8_t *vb, const uint8_t *rng32, uint32_t *rnd);

@@ -12,6 +12,8 @@ There is no host fallback.
     verdict = cs.verify(R1CSProof.from_bytes(proof_bytes), ctx)    # ctx: Context or Pool with generators loaded
 
 ``Verifier.circuit()`` returns the recorded ``Circuit``; ``Circuit.verify_batch`` verifies many proofs of the same gadget.
+``verify_batch_combined`` (and ``Circuit.verify_batch_combined``) checks proofs of one or many gadgets in ONE random linear
+combination (bpgpu_r1cs_verify_rlc), with the same verdicts; ``group_verifiers`` turns [(Verifier, proof)] into its groups.
 
 Proving (src/r1cs/prover.rs): ``Prover`` records the same gadget the same way and, beside the constraints, HOW each multiplier
 gets its inputs (a ``Witness``: free inputs, linear-combination rows that may hold the phase-2 challenges, or zero).  The proof
@@ -493,6 +495,92 @@ class Circuit:
             out.append(tso.raw[:TS * nb])
         return out[0] if len(out) == 1 else tuple(out)
 
+    def verify_batch_combined(self, gens, proofs, commitments, transcripts, rng32=None, weights64=None, want_batch=False, want_transcripts=False):
+        """verify_batch's arguments through ONE combined check (bpgpu_r1cs_verify_rlc): the same verdicts; weights64: nbatch x 64 bytes
+        or None (drawn by the library).  Returns verdict bytes [, the 33 batch bytes] [, transcripts]."""
+        return verify_batch_combined(gens, [(self, proofs, commitments, transcripts)], rng32=rng32, weights64=weights64, want_batch=want_batch,
+                                     want_transcripts=want_transcripts)
+
+
+def verify_batch_combined(gens, groups, rng32=None, weights64=None, want_batch=False, want_transcripts=False):
+    """Proofs of one or many gadgets through ONE combined check (bpgpu_r1cs_verify_rlc / bpgpu_pool_r1cs_verify_rlc).
+    groups: [(circuit, proofs, commitments, transcripts)], each as Circuit.verify_batch takes them; rng32 (32 bytes per proof) and
+    weights64 (64) run over all proofs, the groups' in order, or are None.  Verdicts (VERDICT_*) are those of verify_batch.
+    Returns verdict bytes [, batch bytes: [0] = 0 when the combination was the identity, [1..33) = its encoding] [, transcripts]."""
+    groups = list(groups)
+    if not groups:
+        raise ValueError("verify_batch_combined: no groups")
+    TS = _lib.TRANSCRIPT_BYTES
+    ng = len(groups)
+    sz = C.c_size_t
+    u32p = C.POINTER(C.c_uint32)
+    circ, nbs, strides, ts_strides = (C.c_void_p * ng)(), (sz * ng)(), (sz * ng)(), (sz * ng)()
+    pr, coms, tss, lens = (C.c_char_p * ng)(), (C.c_char_p * ng)(), (C.c_char_p * ng)(), (u32p * ng)()
+    keep = []
+    total = 0
+    for g, grp in enumerate(groups):
+        if len(grp) != 4:
+            raise ValueError("group %d: (circuit, proofs, commitments, transcripts) expected" % g)
+        circuit, proofs, commitments, transcripts = grp
+        proofs = [p.to_bytes() if isinstance(p, R1CSProof) else bytes(p) for p in proofs]
+        nb = len(proofs)
+        if len(commitments) != 32 * circuit.m * nb:
+            raise ValueError("group %d: %d commitment bytes for %d proofs of m = %d" % (g, len(commitments), nb, circuit.m))
+        if len(transcripts) not in (TS, TS * nb):
+            raise ValueError("group %d: transcripts must be one state or one per proof" % g)
+        stride = (max([len(p) for p in proofs] + [1]) + 3) & ~3
+        buf = b"".join(p + bytes(stride - len(p)) for p in proofs)
+        ln = (C.c_uint32 * max(nb, 1))(*[len(p) for p in proofs])
+        cm, ts = bytes(commitments), bytes(transcripts)
+        keep += [buf, ln, cm, ts]
+        circ[g] = circuit._h.value
+        nbs[g], strides[g] = nb, stride
+        ts_strides[g] = TS if nb and len(ts) == TS * nb else 0
+        pr[g], coms[g], tss[g] = buf, cm, ts
+        lens[g] = C.cast(ln, u32p)
+        total += nb
+    if rng32 is not None and len(rng32) != 32 * total:
+        raise ValueError("rng32: 32 bytes per proof")
+    if weights64 is not None and len(weights64) != 64 * total:
+        raise ValueError("weights64: 64 bytes per proof")
+    verdict = C.create_string_buffer(max(total, 1))
+    batch = C.create_string_buffer(33)
+    tso = C.create_string_buffer(TS * max(total, 1)) if want_transcripts else None
+    L = lib()
+    fn = L.bpgpu_pool_r1cs_verify_rlc if isinstance(gens, _lib.Pool) else L.bpgpu_r1cs_verify_rlc
+    rc = fn(gens.h, ng, circ, nbs, pr, strides, lens, coms, tss, ts_strides, rng32, weights64, verdict, batch, tso)
+    gens._chk(rc)
+    out = [verdict.raw[:total]]
+    if want_batch:
+        out.append(batch.raw[:33])
+    if want_transcripts:
+        out.append(tso.raw[:TS * total])
+    return out[0] if len(out) == 1 else tuple(out)
+
+
+def group_verifiers(pairs):
+    """[(Verifier, proof)] -> (groups, index) for verify_batch_combined: verifiers that recorded an identical gadget (the same descriptor)
+    share one Circuit; each group carries one transcript per proof.  index[i] is the position of pair i's verdict in the call's verdicts."""
+    by_key, groups, members = {}, [], []
+    for i, (cs, proof) in enumerate(pairs):
+        key = repr(cs.descriptor())
+        g = by_key.get(key)
+        if g is None:
+            g = by_key[key] = len(groups)
+            groups.append((cs.circuit(), [], [], []))
+            members.append([])
+        groups[g][1].append(proof.to_bytes() if isinstance(proof, R1CSProof) else bytes(proof))
+        groups[g][2].append(b"".join(cs.V))
+        groups[g][3].append(cs.transcript)
+        members[g].append(i)
+    index = [0] * len(pairs)
+    pos = 0
+    for mem in members:
+        for i in mem:
+            index[i] = pos
+            pos += 1
+    return [(c, p, b"".join(cm), b"".join(ts)) for c, p, cm, ts in groups], index
+
 
 def lib():
     L = _lib.lib()
@@ -505,6 +593,10 @@ def lib():
         L.bpgpu_r1cs_circuit_shape.argtypes = [vp, C.POINTER(sz), C.POINTER(sz)]
         L.bpgpu_r1cs_verify_batch_ts.argtypes = [vp, vp, sz, u8p, sz, u32p, u8p, u8p, sz, u8p, u8p, u8p, u8p]
         L.bpgpu_pool_r1cs_verify_ts.argtypes = [vp, vp, sz, u8p, sz, u32p, u8p, u8p, sz, u8p, u8p, u8p, u8p]
+        szp, u8pp = C.POINTER(sz), C.POINTER(u8p)
+        rlc_args = [vp, sz, C.POINTER(vp), szp, u8pp, szp, C.POINTER(u32p), u8pp, u8pp, szp, u8p, u8p, u8p, u8p, u8p]
+        L.bpgpu_r1cs_verify_rlc.argtypes = rlc_args
+        L.bpgpu_pool_r1cs_verify_rlc.argtypes = rlc_args
         L.bpgpu_r1cs_witness_create.argtypes = [vp, sz, u32p, u32p, sz, u32p, sz, u8p, u32p, u32p, u32p, u8p, C.POINTER(vp)]
         L.bpgpu_r1cs_witness_destroy.argtypes = [vp]
         L.bpgpu_r1cs_witness_destroy.restype = None

@@ -125,6 +125,7 @@ const char *bpgpu_last_error(bpgpu_ctx *ctx);
  *   "exponent_pairs"        1 (default): the generator-exponent role handles index i together with nm-1-i (they share s_i and s_i^-1: -24 % of
  *                           the role's Montgomery products); 0: four consecutive indices per lane (for A/B)
  *   "fb_walk_waves"         wavefronts the generator half of a fused chain is cut into (0 = 2048)
+ *   "r1cs_rlc_max_terms"    proof-specific terms of one combination of bpgpu_r1cs_verify_rlc (0 = 2^24, the most); more form several MSMs
  * get_option additionally answers "fixed_table_bytes" and the effective "fixed_window_bits".
  * Returns BPGPU_ERR_INVALID_ARG for unknown keys. */
 int bpgpu_ctx_set_option(bpgpu_ctx *ctx, const char *key, int64_t value);
@@ -404,6 +405,35 @@ int bpgpu_r1cs_verify_batch_ts_dev(bpgpu_ctx *ctx, const bpgpu_r1cs_circuit *cir
                                    size_t proof_stride, const void *d_proof_lens, const void *d_commitments,
                                    const uint8_t *shared_transcript, const void *d_transcripts, const void *d_rng32,
                                    void *d_verdict, void *d_msm_out, void *d_transcripts_out, void *stream);
+/* Batch-combined R1CS verification (ADDITIONAL entry point, as bpgpu_rangeproof_verify_rlc; the reference's r1cs::Verifier has only
+ * new / commit / verify).  One call takes ngroups groups; group g is what one bpgpu_r1cs_verify_batch_ts call takes: circuits[g] (the
+ * same circuit may appear in several groups), nbatch[g] proofs (proofs[g], proof_stride[g], proof_lens[g]), commitments[g] and
+ * transcripts[g] with transcript_stride[g] (0: one shared state, BPGPU_TRANSCRIPT_BYTES: one per proof).  The per-proof arrays rng32
+ * (32 bytes), weights64 (64), verdict (1) and transcripts_out (208) run over all proofs, the groups' in order (sum(nbatch) entries).
+ *     R = sum_i rho_i * MegaCheck_i ,  rho_i = Scalar::from_bytes_mod_order_wide(weights64[i]),
+ * over the proofs that reach the mega-check.  Their generator coefficients add up in the scalar field on the generator rows of the
+ * largest padded_n, so the table walk runs once per call; their own points (11 + m + 2k per proof) form one Pippenger MSM.  R is the
+ * identity when every combined proof verifies; if one does not, R != identity except with probability ~2^-252 over the weights, which
+ * must be unpredictable to the provers (NULL = drawn by the library: uniform 512-bit strings expanded on the device from a per-call key).
+ * A zero weight leaves its proof unchecked.
+ *   rng32           : as bpgpu_r1cs_verify_batch_ts, or NULL: each proof's 32 bytes are drawn ONCE as that call's seeded mode draws them
+ *                     (ChaCha20 keyed from the OS per call) and serve both the combination and any fallback
+ *   verdict         : ALWAYS what bpgpu_r1cs_verify_batch_ts returns for the proof's group with the same rng32 bytes.  A proof that
+ *                     stops before the mega-check (FormatError, an identity validated point, InvalidGeneratorsLength, an IPP of the wrong
+ *                     length) gets that code and is left out of R.  When R is not the identity, or a point of the combined MSM does not
+ *                     decode, the call re-verifies every group through the per-proof pipeline and returns those verdicts.
+ *   batch_out       : optional 33 bytes: [0] = 0 when R is the identity and every point decoded, else 1; [1..33) = compress(R), or zeros
+ *                     when a point did not decode
+ *   transcripts_out : optional, as bpgpu_r1cs_verify_batch_ts leaves them
+ * ngroups = 0 or a NULL group array is BPGPU_ERR_INVALID_ARG; groups with nbatch[g] = 0 are skipped.  Context option
+ * "r1cs_rlc_max_terms" caps the proof-specific terms of one MSM (default 2^24): above it the call forms several combinations and adds
+ * their points before the identity test.  Memory stays bounded: groups are processed in slices of at most 1024 proofs, in the
+ * combination and in the per-proof fallback alike (the combined term list itself holds at most r1cs_rlc_max_terms terms). */
+int bpgpu_r1cs_verify_rlc(bpgpu_ctx *ctx, size_t ngroups, const bpgpu_r1cs_circuit *const *circuits, const size_t *nbatch,
+                          const uint8_t *const *proofs, const size_t *proof_stride, const uint32_t *const *proof_lens,
+                          const uint8_t *const *commitments, const uint8_t *const *transcripts, const size_t *transcript_stride,
+                          const uint8_t *rng32, const uint8_t *weights64,
+                          uint8_t *verdict, uint8_t *batch_out, uint8_t *transcripts_out);
 
 /* ---- R1CS proof creation (r1cs::Prover::prove, src/r1cs/prover.rs:380-655) ------------------------------------------------
  * The prover's gadget also computes the witness: a_L, a_R, a_O of every multiplier.  Phase-2 multipliers may take inputs from
@@ -719,6 +749,12 @@ int bpgpu_pool_r1cs_verify_ts(bpgpu_pool *pool, const bpgpu_r1cs_circuit *circui
                               size_t proof_stride, const uint32_t *proof_lens, const uint8_t *commitments,
                               const uint8_t *transcripts, size_t transcript_stride, const uint8_t *rng32,
                               uint8_t *verdict, uint8_t *msm_out, uint8_t *transcripts_out);
+/* bpgpu_r1cs_verify_rlc through the pool (same arguments): the whole call runs on the next device, blocking; any thread may call it. */
+int bpgpu_pool_r1cs_verify_rlc(bpgpu_pool *pool, size_t ngroups, const bpgpu_r1cs_circuit *const *circuits, const size_t *nbatch,
+                               const uint8_t *const *proofs, const size_t *proof_stride, const uint32_t *const *proof_lens,
+                               const uint8_t *const *commitments, const uint8_t *const *transcripts, const size_t *transcript_stride,
+                               const uint8_t *rng32, const uint8_t *weights64,
+                               uint8_t *verdict, uint8_t *batch_out, uint8_t *transcripts_out);
 /* The combining queue's timeline (set option "combine_trace" = ring size first): one JSON object per line -- every launch chain (opened,
  * sealed, issue begin / end, completion seen, delivery begin / end, buffer free; CLOCK_MONOTONIC ns) and every eighth request per thread
  * (submitted, slots reserved, inputs written, delivered, woken).  tools/combine_timeline.py turns it into "where does a request wait". */
