@@ -3763,45 +3763,26 @@ extern "C" int bpgpu_r1cs_circuit_create(size_t m, size_t n1, size_t n2, int two
         ci->lbl_off.push_back(ci->lbl_off.back() + label_lens[j]);
     }
     ci->lbl.assign(labels ? labels : (const uint8_t *)"", (labels ? labels : (const uint8_t *)"") + ci->lbl_off.back());
-    const size_t ncols = 3 * n + m + 1;
-    std::vector<uint32_t> cnt(ncols + 1, 0), col(n_terms);
-    for (size_t q = 0; q < n_constraints; q++)
-        for (uint32_t t = row_ptr[q]; t < row_ptr[q + 1]; t++) {
-            const uint32_t kind = term_kind[t], idx = term_index[t], ch = term_challenge[t], pw = term_power[t];
-            bool ok = true;
-            switch (kind) {
-            case BPGPU_R1CS_L: case BPGPU_R1CS_R: case BPGPU_R1CS_O: ok = idx < n; col[t] = (uint32_t)(3 * idx + kind); break;
-            case BPGPU_R1CS_V: ok = idx < m; col[t] = (uint32_t)(3 * n + idx); break;
-            case BPGPU_R1CS_ONE: ok = idx == 0; col[t] = (uint32_t)(3 * n + m); break;
-            default: ok = false;
-            }
-            if (ch == BPGPU_R1CS_NO_CHALLENGE) ok = ok && pw == 0;
-            else ok = ok && ch < n_challenges && pw >= 1 && pw <= BPGPU_R1CS_MAX_POWER;
-            sc cf;
-            memcpy(cf.v, term_coeff + (size_t)t * 32, 32);
-            ok = ok && sc_is_canonical_sc(cf);
-            if (!ok) {
-                delete ci;
-                return BPGPU_ERR_INVALID_ARG;
-            }
-            cnt[col[t] + 1]++;
+    for (size_t t = 0; t < n_terms; t++) {
+        const uint32_t kind = term_kind[t], idx = term_index[t], ch = term_challenge[t], pw = term_power[t];
+        bool ok = true;
+        switch (kind) {
+        case BPGPU_R1CS_L: case BPGPU_R1CS_R: case BPGPU_R1CS_O: ok = idx < n; break;
+        case BPGPU_R1CS_V: ok = idx < m; break;
+        case BPGPU_R1CS_ONE: ok = idx == 0; break;
+        default: ok = false;
         }
-    for (size_t i = 0; i < ncols; i++) cnt[i + 1] += cnt[i];
-    ci->col_ptr = cnt;
-    ci->ents.resize(n_terms);
-    std::vector<uint32_t> fill(cnt.begin(), cnt.end() - 1);
-    for (size_t q = 0; q < n_constraints; q++)   // constraint order within each list: the reference's summation order
-        for (uint32_t t = row_ptr[q]; t < row_ptr[q + 1]; t++) {
-            r1cs_ent &e = ci->ents[fill[col[t]]++];
-            e.q = (uint32_t)q;
-            e.chal = term_challenge[t] == BPGPU_R1CS_NO_CHALLENGE ? R1_NO_CHAL : (term_challenge[t] | (term_power[t] << 16));
-            sc cf;
-            memcpy(cf.v, term_coeff + (size_t)t * 32, 32);
-            if (term_kind[t] == BPGPU_R1CS_V || term_kind[t] == BPGPU_R1CS_ONE) sc_neg(cf, cf);   // wV -= .., wc -= .. (verifier.rs:286-292)
-            sc28 cm;
-            sc_to_mont28(cm, cf);
-            memcpy(e.coeff, cm.v, 40);
+        if (ch == BPGPU_R1CS_NO_CHALLENGE) ok = ok && pw == 0;
+        else ok = ok && ch < n_challenges && pw >= 1 && pw <= BPGPU_R1CS_MAX_POWER;
+        sc cf;
+        memcpy(cf.v, term_coeff + (size_t)t * 32, 32);
+        ok = ok && sc_is_canonical_sc(cf);
+        if (!ok) {
+            delete ci;
+            return BPGPU_ERR_INVALID_ARG;
         }
+    }
+    r1cs_build_lists(m, n, n_constraints, row_ptr, n_terms, term_kind, term_index, term_challenge, term_power, term_coeff, ci->col_ptr, ci->ents);
     ci->off_ents = align_up(ci->col_ptr.size() * 4);
     ci->off_lbl_off = ci->off_ents + align_up(ci->ents.size() * sizeof(r1cs_ent));
     ci->off_lbl = ci->off_lbl_off + align_up(ci->lbl_off.size() * 4);
@@ -3870,25 +3851,8 @@ static int r1cs_front_dev_locked(bpgpu_ctx *c, const bpgpu_r1cs_circuit *ci, siz
     int rc = r1cs_circuit_on(c, ci, &dc);
     if (rc) return rc;
     r1cs_shape sh{};
-    sh.m = ci->m, sh.n1 = ci->n1, sh.n = ci->n, sh.pn = ci->pn, sh.k = ci->k;
-    sh.two_phase = ci->two_phase, sh.nch = ci->nch, sh.Q = ci->Q;
-    sh.nzhi = (ci->Q >> 6) + 1;
-    sh.nyhi = ((ci->pn - 1) >> 6) + 1;
-    sh.f_zlo = R1F_FIXED;
-    sh.f_zhi = sh.f_zlo + 64;
-    sh.f_ylo = sh.f_zhi + sh.nzhi;
-    sh.f_yhi = sh.f_ylo + 64;
-    sh.f_ch = sh.f_yhi + sh.nyhi;
-    sh.f_tab = sh.f_ch + sh.nch;
-    sh.nfields = sh.f_tab + 2 * sh.k;
-    sh.U = 11 + sh.m + 2 * sh.k;
-    sh.proof_stride = (uint32_t)proof_stride;
-    sh.nproofs = (uint32_t)nbatch;
-    {
-        const uint32_t n_one = ci->col_ptr[3 * ci->n + ci->m + 1] - ci->col_ptr[3 * ci->n + ci->m];
-        sh.one_chunks = n_one ? (n_one + R1_ONE_CHUNK - 1) / R1_ONE_CHUNK : 1;
-    }
-    sh.gens_short = ci->pn > c->gens_capacity ? 1u : 0u;   // verifier.rs:341-343 (a single-party proof: party 0)
+    r1cs_shape_of(sh, ci->m, ci->n1, ci->n, ci->pn, ci->k, ci->two_phase, ci->nch, ci->Q, ci->col_ptr[3 * ci->n + ci->m + 1] - ci->col_ptr[3 * ci->n + ci->m],
+                  proof_stride, nbatch, c->gens_capacity);
     const uint64_t ncol = (uint64_t)sh.pn + sh.m + sh.one_chunks;
     if (ncol * nbatch > 0x7fffffffull || (uint64_t)nbatch * (2 * sh.pn + 2 + sh.U) > 0x7fffffffull / 64)
         return fail(c, BPGPU_ERR_INVALID_ARG, "batch too large for this circuit");

@@ -12,6 +12,8 @@
 #ifndef BPGPU_R1CS_H
 #define BPGPU_R1CS_H
 #include "rangeproof.h"
+#include <cstring>
+#include <vector>
 
 namespace bp {
 
@@ -536,6 +538,61 @@ BP_HD void r1_finish_lead(uint32_t p, const r1cs_shape &sh, const sc &delta, con
     uint32_t *row = gen_sc + (uint64_t)p * (2 * sh.pn + 2) * 8;
     store_words8(row, t2);                    // B_blinding
     store_words8(row + 8, t0);                // B
+}
+
+// ---- host side: the circuit as the launches read it (bpgpu_r1cs_circuit_create and the launch set-up of libbpgpu.so; the host harness of
+// tests/r1cs_harness runs the same two functions, so that it drives the product's data layout and not a copy of it) -------------------
+// (plain host functions: a HIP translation unit parses them in its device pass too, and emits nothing for them there)
+// the per-variable lists of VALIDATED term arrays (bpgpu_r1cs_circuit_create's arguments; kinds L, R, O, V, ONE = 0..4): col_ptr has
+// 3n + m + 2 entries over the columns L_i, R_i, O_i (3i, 3i+1, 3i+2), V_j (3n + j), ONE (3n + m)
+inline void r1cs_build_lists(size_t m, size_t n, size_t n_constraints, const uint32_t *row_ptr, size_t n_terms, const uint8_t *term_kind,
+                             const uint32_t *term_index, const uint32_t *term_challenge, const uint32_t *term_power, const uint8_t *term_coeff,
+                             std::vector<uint32_t> &col_ptr, std::vector<r1cs_ent> &ents) {
+    const size_t ncols = 3 * n + m + 1;
+    std::vector<uint32_t> cnt(ncols + 1, 0), col(n_terms);
+    for (size_t t = 0; t < n_terms; t++) {
+        const uint32_t kind = term_kind[t], idx = term_index[t];
+        col[t] = (uint32_t)(kind <= 2 ? 3 * idx + kind : kind == 3 ? 3 * n + idx : 3 * n + m);
+        cnt[col[t] + 1]++;
+    }
+    for (size_t i = 0; i < ncols; i++) cnt[i + 1] += cnt[i];
+    col_ptr = cnt;
+    ents.resize(n_terms);
+    std::vector<uint32_t> fill(cnt.begin(), cnt.end() - 1);
+    for (size_t q = 0; q < n_constraints; q++)   // constraint order within each list: the reference's summation order
+        for (uint32_t t = row_ptr[q]; t < row_ptr[q + 1]; t++) {
+            r1cs_ent &e = ents[fill[col[t]]++];
+            e.q = (uint32_t)q;
+            e.chal = term_challenge[t] == R1_NO_CHAL ? R1_NO_CHAL : (term_challenge[t] | (term_power[t] << 16));
+            sc cf;
+            memcpy(cf.v, term_coeff + (size_t)t * 32, 32);
+            if (term_kind[t] == 3 || term_kind[t] == 4) sc_neg(cf, cf);   // wV -= .., wc -= .. (verifier.rs:286-292)
+            sc28 cm;
+            sc_to_mont28(cm, cf);
+            memcpy(e.coeff, cm.v, 40);
+        }
+}
+
+// the launch shape of `nbatch` proofs of a circuit (n_one: length of its ONE list) on generators of capacity gens_capacity; the rng
+// fields (seeded, seed) are the caller's
+inline void r1cs_shape_of(r1cs_shape &sh, uint32_t m, uint32_t n1, uint32_t n, uint32_t pn, uint32_t k, uint32_t two_phase, uint32_t nch, uint32_t Q,
+                          uint32_t n_one, size_t proof_stride, size_t nbatch, size_t gens_capacity) {
+    sh.m = m, sh.n1 = n1, sh.n = n, sh.pn = pn, sh.k = k;
+    sh.two_phase = two_phase, sh.nch = nch, sh.Q = Q;
+    sh.nzhi = (Q >> 6) + 1;
+    sh.nyhi = ((pn - 1) >> 6) + 1;
+    sh.f_zlo = R1F_FIXED;
+    sh.f_zhi = sh.f_zlo + 64;
+    sh.f_ylo = sh.f_zhi + sh.nzhi;
+    sh.f_yhi = sh.f_ylo + 64;
+    sh.f_ch = sh.f_yhi + sh.nyhi;
+    sh.f_tab = sh.f_ch + sh.nch;
+    sh.nfields = sh.f_tab + 2 * sh.k;
+    sh.U = 11 + sh.m + 2 * sh.k;
+    sh.proof_stride = (uint32_t)proof_stride;
+    sh.nproofs = (uint32_t)nbatch;
+    sh.one_chunks = n_one ? (n_one + R1_ONE_CHUNK - 1) / R1_ONE_CHUNK : 1;
+    sh.gens_short = pn > gens_capacity ? 1u : 0u;   // verifier.rs:341-343 (a single-party proof: party 0)
 }
 
 }  // namespace bp

@@ -92,7 +92,17 @@ class _Arith:
                     raise R1CSError("a product of two different challenges cannot be recorded")
                 out.append((v, o.index, p + 1, k))
             return LinearCombination(out)
-        raise TypeError("a linear combination multiplies by a scalar (int) or a challenge only")
+        if isinstance(o, LinearCombination) and o._is_challenge_monomial():   # k c^e, as c * c gives it (a Scalar in the reference)
+            (_, oc, op, ok), = o.terms
+            out = []
+            for v, c, p, k in lc.terms:
+                if c is not None and c != oc:
+                    raise R1CSError("a product of two different challenges cannot be recorded")
+                out.append((v, oc, p + op, k * ok % L_ORDER))
+            return LinearCombination(out)
+        if isinstance(o, (Variable, LinearCombination)) and lc._is_challenge_monomial():
+            return _as_lc(o) * lc
+        raise TypeError("a linear combination multiplies by a scalar (int), a challenge or a product of powers of one challenge only")
 
     def __rmul__(self, o):
         return self * o
@@ -116,6 +126,10 @@ class Challenge(_Arith):
 class LinearCombination(_Arith):
     def __init__(self, terms=None):
         self.terms = list(terms or [])
+
+    def _is_challenge_monomial(self):
+        """one ONE term that carries a challenge: coefficient * c^power"""
+        return len(self.terms) == 1 and self.terms[0][0] == (KIND_ONE, 0) and self.terms[0][1] is not None
 
 
 def ONE():

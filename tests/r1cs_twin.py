@@ -542,6 +542,26 @@ def parse(b):
     return d
 
 
+def flattened_with(gadget, m, z, challenges):
+    """the twin verifier's flattened(z) for `gadget` with its challenge draws replaced by the given values: (wL, wR, wO, wV, wc).
+    As verifier.rs:300-321, an allocate() pair still open at the end of phase 1 is dropped before the deferred callbacks run."""
+    class Fixed(Verifier):
+        def __init__(self):
+            self.constraints, self.deferred, self.num_vars, self.V, self.pending_multiplier = [], [], 0, [], None
+            self.draws = list(challenges)
+
+        def challenge_scalar(self, label):
+            return self.draws.pop(0)
+
+    cs = Fixed()
+    cs.V = [bytes(32)] * m
+    gadget(cs, [Var(KIND_V, i) for i in range(m)])
+    cs.pending_multiplier = None
+    for cb in cs.deferred:
+        cb(cs)
+    return cs.flattened(z)
+
+
 # ---- the gadgets of tests/r1cs.rs, generic over the constraint system ------------------------------------------------------
 def shuffle_gadget(cs, x, y):                             # tests/r1cs.rs:22-58
     k = len(x)

@@ -7,6 +7,7 @@ import threading
 import pytest
 
 import r1cs_twin as R
+from r1cs_corpus import tamper_cases as _tamper_cases
 
 pytestmark = pytest.mark.gpu
 
@@ -115,36 +116,6 @@ def test_range_gadget(ctx, gens, n):
     proofs = [p1.to_bytes(), p2.to_bytes(), p1.to_bytes(force_two_phase=True)]
     v = _check(ctx, circuit, _range_gadget(n), gens, CAP, proofs, [V1[0], V2[0], V1[0]], [st0] * 3, _rng(b"r%d" % n, 3))
     assert list(v) == [0, 1, 0]
-
-
-def _tamper_cases(good, Vs):
-    """(proof bytes, commitments) per exit path of verifier.rs / proof.rs"""
-    one = good[0] == 0
-    nel = 11 if one else 14
-    o_T = 3 if one else 6
-    k = (len(good) - 1 - 32 * nel - 64) // 64
-    ipp = 1 + 32 * nel
-    coms = b"".join(Vs)
-    cases = []
-    for e in range(nel + 2 * k + 2):                  # a flipped byte in every element
-        b = bytearray(good)
-        b[1 + 32 * e + 7] ^= 0x10
-        cases.append((bytes(b), coms))
-    L_ = R.L.to_bytes(32, "little")
-    for off in (1 + 32 * (o_T + 5), ipp + 64 * k, ipp + 64 * k + 32):   # t_x, a, b not canonical
-        cases.append((good[:off] + L_ + good[off + 32:], coms))
-    cases.append((bytes([2]) + good[1:], coms))       # bad version byte
-    cases.append((good[:-1], coms))                   # bad length
-    cases.append((good + bytes(64), coms))            # IPP longer than lg(padded_n)
-    cases.append((good[:-128] + good[-64:], coms) if k else (good + bytes(64), coms))   # shorter
-    cases.append((good[:1] + bytes(32) + good[33:], coms))                               # identity A_I1
-    cases.append((good[:1 + 32 * (o_T + 1)] + bytes(32) + good[1 + 32 * (o_T + 2):], coms))   # identity T_3
-    if k:
-        cases.append((good[:ipp] + bytes(32) + good[ipp + 32:], coms))                   # identity L_0
-    cases.append((good, b"\xff" * 32 + coms[32:]))    # undecodable V
-    cases.append((good, coms[32:] + coms[:32]))       # swapped commitments
-    cases.append((good, coms))
-    return cases
 
 
 @pytest.mark.parametrize("form", ["one-phase", "two-phase"])

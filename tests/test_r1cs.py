@@ -81,21 +81,7 @@ def _record(gadget, m, st0=bytes(208)):
 
 def _twin_weights(gadget, m, z, challenges):
     """the twin verifier run directly, its challenge draws replaced by the given values"""
-    class Fixed(R.Verifier):
-        def __init__(self):
-            self.constraints, self.deferred, self.num_vars, self.V, self.pending_multiplier = [], [], 0, [], None
-            self.draws = list(challenges)
-
-        def challenge_scalar(self, label):
-            return self.draws.pop(0)
-
-    cs = Fixed()
-    vs = [R.Var(R.KIND_V, i) for i in range(m)]
-    cs.V = [bytes(32)] * m
-    gadget(cs, vs)
-    for cb in cs.deferred:
-        cb(cs)
-    return cs.flattened(z)
+    return R.flattened_with(gadget, m, z, challenges)
 
 
 @pytest.mark.parametrize("name,m,gadget", [
@@ -129,6 +115,37 @@ def test_recorder_refuses_products_of_two_challenges():
     cs.specify_randomized_constraints(cb)
     d = cs.descriptor()
     assert d[4] == [b"a", b"b"] and any(pw == 2 for (_, ch, pw, _) in d[5][0])
+
+
+def test_recorder_accepts_a_challenge_monomial_on_the_right():
+    """lc * (c * c): c * c is a Scalar in the reference, a pure challenge monomial (one ONE term with a challenge) here"""
+    from bulletproofs_amd import r1cs
+    cs = r1cs.Verifier(bytes(208))
+    x, y = cs.commit(bytes(32)), cs.commit(bytes(32))
+
+    def cb(cs):
+        a, b = cs.challenge_scalar(b"a"), cs.challenge_scalar(b"b")
+        lc = x * 5 - y + 7
+        assert (lc * (a * a)).terms == (lc * a * a).terms == ((a * a) * lc).terms
+        assert (lc * (a * a * 3)).terms == (lc * 3 * a * a).terms
+        assert ((lc * a) * (a * a)).terms == (lc * a * a * a).terms and all(t[2] == 3 for t in (lc * a * (a * a)).terms)
+        assert (x * (b * b)).terms == [((r1cs.KIND_V, 0), 1, 2, 1)]
+        cs.constrain(lc * (a * a) - lc * a * a)
+        with pytest.raises(r1cs.R1CSError):
+            (lc * a) * (b * b)              # two different challenges
+        with pytest.raises(TypeError):
+            lc * (a * a + 1)                # not a monomial
+        with pytest.raises(TypeError):
+            lc * (x * a)                    # a variable times a challenge is no scalar
+        with pytest.raises(TypeError):
+            lc * lc
+    cs.specify_randomized_constraints(cb)
+    d = cs.descriptor()
+    z, ch = 12345, [777, 999]
+    assert r1cs.flattened_constraints(d, z, ch) == ([], [], [], [0, 0], 0)
+    g = lambda cs_, v: cs_.specify_randomized_constraints(lambda c: c.constrain((v[0] * 5 - v[1] + 7) * (lambda a: a * a)(c.challenge_scalar(b"a"))))
+    rec = _record(g, 2)
+    assert r1cs.flattened_constraints(rec.descriptor(), z, ch[:1]) == _twin_weights(g, 2, z, ch[:1])
 
 
 def test_proof_serialization_round_trip(gens):

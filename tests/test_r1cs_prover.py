@@ -115,6 +115,25 @@ def test_recorder_refuses_missing_assignments_and_challenge_products():
         cs.multiply(a + r1cs.Variable(r1cs.KIND_R, 0), 1)
 
 
+def test_recorder_refuses_a_right_half_that_reads_a_later_multiplier():
+    """the reference allows it (assignments are values there); the witness program fills multipliers in index order"""
+    from bulletproofs_amd import r1cs
+    cs = r1cs.Prover(bytes(208))
+    x = cs.commit(3, 4)
+    cs.allocate_multiplier((1, 2))
+    a = cs.allocate(x * 1)                            # L_1: the pair stays open
+    _, _, o2 = cs.multiply(x + a, x - 2)              # multiplier 2 reads L_1: fine
+    with pytest.raises(r1cs.R1CSError, match="an input of multiplier 1 reads multiplier 2"):
+        cs.allocate(o2 + 1)                           # R_1 from O_2
+    cs = r1cs.Prover(bytes(208))
+    x = cs.commit(3, 4)
+    l0, _, o0 = cs.allocate_multiplier((1, 2))
+    a = cs.allocate(x * 1)
+    cs.multiply(x + a, x - 2)
+    cs.allocate(o0 + l0)                              # R_1 from multiplier 0, allocated before the pair was opened: recorded
+    assert cs.src_right[1] == len(cs.rows) - 1 and len(cs.src_left) == 3
+
+
 # ---- bpgpu_r1cs_witness_create through the library (host only) ---------------------------------------------------------------
 def _circuit():
     """m = 2, n1 = 1, n2 = 2, one challenge"""
