@@ -82,6 +82,48 @@ void h_compress_xyzt(const uint8_t *xyzt, uint8_t *out) {
     ge_ext p; load(p.X, xyzt); load(p.Y, xyzt + 32); load(p.Z, xyzt + 64); load(p.T, xyzt + 96);
     uint32_t w[8]; ristretto_compress(w, p); memcpy(out, w, 32);
 }
+// Each copy of the decoder by name, n encodings at a time.  which: 0 ristretto_decompress, 1 ristretto_decompress_lp (the short-register
+// copy of the fused bucket chain), 2 hw_ristretto_decode (the wavefront form of the second tables: the point only, ok[i] = 2).
+// xyzt: the coordinates the copy leaves behind, accepted or not (4 x 32 canonical bytes per encoding).
+int h_decode_copy(int which, uint32_t n, const uint8_t *enc, uint8_t *xyzt, uint8_t *ok) {
+    for (uint32_t i = 0; i < n; i++) {
+        uint32_t w[8]; memcpy(w, enc + 32 * (size_t)i, 32);
+        ge_ext p;
+        switch (which) {
+        case 0: ok[i] = ristretto_decompress(p, w) ? 1 : 0; break;
+        case 1: ok[i] = ristretto_decompress_lp(p, w) ? 1 : 0; break;
+        case 2: hw_ristretto_decode(p, w); ok[i] = 2; break;
+        default: return -1;
+        }
+        uint8_t *o = xyzt + 128 * (size_t)i;
+        store(o, p.X); store(o + 32, p.Y); store(o + 64, p.Z); store(o + 96, p.T);
+    }
+    return 0;
+}
+// Each copy of the encoder by name, n points (4 x 32 bytes, any representative, any Z).  which: 0 ristretto_compress; 1 the split form with
+// the one-lane chain (ristretto_compress_front, fe_invsqrt_raw, fe_invsqrt_fix, ristretto_compress_back); 2 the split form as the narrow and
+// bucket tails run it (bk2_tail_t4a, the wavefront chain hw_invsqrt_raw_fe, bk2_tail_t4b); 3 ristretto_compress_lp.
+int h_encode_copy(int which, uint32_t n, const uint8_t *xyzt, uint8_t *out) {
+    for (uint32_t i = 0; i < n; i++) {
+        const uint8_t *in = xyzt + 128 * (size_t)i;
+        ge_ext p; load(p.X, in); load(p.Y, in + 32); load(p.Z, in + 64); load(p.T, in + 96);
+        uint32_t w[8];
+        switch (which) {
+        case 0: ristretto_compress(w, p); break;
+        case 1: { fe tin, raw, I; ristretto_compress_front(tin, &p); fe_invsqrt_raw(raw, tin); fe_invsqrt_fix(I, raw, tin); ristretto_compress_back(w, &p, I); } break;
+        case 2: {
+            fe tin, raw; uint32_t tw[8], st[1] = {0};
+            bk2_tail_t4a(&p, &tin, tw);
+            hw_invsqrt_raw_fe((const uint16_t *)tw, nullptr, &raw);
+            bk2_tail_t4b(0, &p, &raw, &tin, st, w, nullptr, nullptr);
+        } break;
+        case 3: ristretto_compress_lp(w, &p); break;
+        default: return -1;
+        }
+        memcpy(out + 32 * (size_t)i, w, 32);
+    }
+    return 0;
+}
 // op: 0 add 1 sub 2 dbl 3 madd(+) 4 madd(-) 5 roundtrip 6 dbl x4 (3 without T) 7 neg ; inputs compressed
 int h_point_op(int op, const uint8_t *a, const uint8_t *b, uint8_t *out) {
     uint32_t wa[8], wb[8], wo[8]; memcpy(wa, a, 32); memcpy(wb, b, 32);

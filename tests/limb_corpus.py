@@ -7,6 +7,7 @@ import ctypes as C
 import random
 
 import bp_twin as T
+import point_corpus as PC
 
 P, L = T.P, T.L
 
@@ -484,9 +485,13 @@ def check_drivers(B, decode_encodings):
     out = B.drv("decode", len(enc), u32([[int.from_bytes(e[4 * i:4 * i + 4], "little") for i in range(8)] for e in enc]), 40)
     for e, o in zip(enc, out):
         d = T.decompress(e)
+        v = fe4(o)
         if d is not None:
-            v = fe4(o)
             assert v[2] == 1 and affine(v) == affine(d) and v[3] == v[0] * v[1] % P, e.hex()
+        # rejected encodings as well: the driver gives no verdict and the narrow chain doubles its output 128 times, so the
+        # coordinates must be the RFC's formulas carried to the end (what the lane decoder leaves behind)
+        failed, full = PC.decode_full(e)
+        assert (d is None) == bool(failed) and tuple(v) == full, (e.hex(), "".join(sorted(failed)))
     outs["decode"] = out
     pts = driver_points(6, b"drv")
     pts[1] = tuple(2 * c % P for c in pts[1])                   # Z != 1

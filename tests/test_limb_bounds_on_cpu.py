@@ -12,6 +12,7 @@ import pytest
 import bp_twin as T
 import harness_lib
 import limb_corpus as LC
+import point_corpus as PC
 
 
 @pytest.fixture(scope="module")
@@ -43,7 +44,8 @@ def test_wavefront_field_arithmetic_at_limb_bounds(B):
 
 
 def decode_encodings():
-    """The encodings of test_group_ops_and_ristretto_codec: 24 points, the five fixed edge strings, 200 random byte strings."""
+    """The encodings of test_group_ops_and_ristretto_codec: 24 points, the five fixed edge strings, 200 random byte strings;
+    then point_corpus.py's members: every rejection class alone, the valid ends of the range, p + k, the roots of -1."""
     pts = [T.from_uniform_bytes(hashlib.shake_256(b"p%d" % i).digest(64)) for i in range(24)]
     enc = [T.compress(p) for p in pts]
     P = T.P
@@ -51,7 +53,7 @@ def decode_encodings():
     for i in range(200):
         e = hashlib.shake_256(b"e%d" % i).digest(32)
         enc.append(bytes([e[0] & 0xfe]) + e[1:31] + bytes([e[31] & 0x7f]))
-    return enc
+    return enc + PC.ALL_ENC
 
 
 def test_wavefront_drivers_host_copies(B):
