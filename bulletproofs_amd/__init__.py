@@ -2,7 +2,7 @@
 
 Host-side mirror of the reference crate's public surface for this path
 (src/lib.rs:34-45 of dalek-cryptography/bulletproofs): RangeProof, LinearProof,
-BulletproofGens, PedersenGens, ProofError, Transcript -- all of it a thin layer
+BulletproofGens, PedersenGens, ProofError, Transcript, range_proof_mpc -- all of it a thin layer
 over the C ABI of libbpgpu.so (include/bpgpu.h).  No CPU fallback exists.
 """
 import os as _os
@@ -15,3 +15,4 @@ _os.environ.setdefault("GPU_MAX_HW_QUEUES", "16")
 from ._lib import BpgpuError, Context, Pool, lib, LIB_PATH  # noqa: F401
 from .api import (BulletproofGens, BulletproofGensShare, PedersenGens, RangeProof, LinearProof, Transcript, ProofError, VerificationError,  # noqa: F401,E402
                   FormatError, InvalidBitsize, InvalidGeneratorsLength)
+from . import range_proof_mpc  # noqa: F401,E402

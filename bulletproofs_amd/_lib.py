@@ -35,6 +35,8 @@ EXPORTS = [
     "bpgpu_gens_add_shape", "bpgpu_pool_gens_add_shape", "bpgpu_pool_gather_dev",
     "bpgpu_pool_msm_batch_shared", "bpgpu_pool_msm_batch_shared_submit", "bpgpu_pool_msm_batch", "bpgpu_pool_ipp_verify", "bpgpu_pool_trace_dump",
     "bpgpu_pool_msm_batch_shared_submit_dev",
+    "bpgpu_mpc_state1_bytes", "bpgpu_mpc_state2_bytes", "bpgpu_mpc_party_bit_commit", "bpgpu_mpc_party_poly_commit", "bpgpu_mpc_party_proof_share",
+    "bpgpu_mpc_dealer_bit_challenge", "bpgpu_mpc_dealer_poly_challenge", "bpgpu_mpc_dealer_assemble",
 ]
 
 TRANSCRIPT_BYTES = 208
@@ -100,6 +102,16 @@ def lib():
     L.bpgpu_linear_create_batch.argtypes = [vp, sz, sz, u8p, sz, u8p, u8p, u8p, u8p, u8p, u8p, i, u8p, u8p, u8p, u8p, u8p, u8p]
     L.bpgpu_linear_verify_batch_dev.argtypes = [vp, sz, sz, vp, sz, u8p, sz, u8p, vp, vp, vp, vp, vp, i, vp, vp, vp, vp]
     L.bpgpu_ipp_verification_scalars.argtypes = [vp, sz, sz, u8p, sz, u8p, sz, u8p, sz, u8p, u8p, u8p, u8p, u8p]
+    L.bpgpu_mpc_state1_bytes.argtypes = [sz]
+    L.bpgpu_mpc_state1_bytes.restype = sz
+    L.bpgpu_mpc_state2_bytes.argtypes = [sz]
+    L.bpgpu_mpc_state2_bytes.restype = sz
+    L.bpgpu_mpc_party_bit_commit.argtypes = [vp, sz, sz, C.POINTER(C.c_uint32), C.POINTER(C.c_uint64), u8p, u8p, u8p, u8p]
+    L.bpgpu_mpc_party_poly_commit.argtypes = [vp, sz, sz, u8p, u8p, i, u8p, u8p, u8p, u8p]
+    L.bpgpu_mpc_party_proof_share.argtypes = [vp, sz, sz, u8p, u8p, i, u8p, u8p]
+    L.bpgpu_mpc_dealer_bit_challenge.argtypes = [vp, sz, sz, sz, u8p, u8p, sz, u8p, sz, u8p, u8p, u8p, u8p]
+    L.bpgpu_mpc_dealer_poly_challenge.argtypes = [vp, sz, sz, u8p, u8p, u8p, u8p, u8p]
+    L.bpgpu_mpc_dealer_assemble.argtypes = [vp, sz, sz, sz, u8p, u8p, u8p, u8p, u8p, u8p, sz, u8p, sz, u8p, i, u8p, u8p, u8p]
     L.bpgpu_pool_create.argtypes = [C.POINTER(C.c_int), i, i, C.POINTER(vp)]
     L.bpgpu_pool_destroy.argtypes = [vp]
     L.bpgpu_pool_destroy.restype = None
@@ -399,6 +411,94 @@ class Context:
         self._chk(self._L.bpgpu_rangeproof_prove_batch(self.h, n, m, nb, va, blindings, label, len(label), transcript, rng, proofs, coms, tso))
         out = (proofs.raw[:pl * nb], coms.raw[:32 * m * nb])
         return out + (tso.raw[:TRANSCRIPT_BYTES * nb],) if want_transcripts else out
+
+    # ---- the multi-party aggregation protocol (bpgpu_mpc_*; the typestate classes of range_proof_mpc.py are batches of one) ----
+    def mpc_state_bytes(self, n):
+        return self._L.bpgpu_mpc_state1_bytes(n), self._L.bpgpu_mpc_state2_bytes(n)
+
+    def mpc_party_bit_commit(self, n, party_index, values, blindings, rng=None):
+        """Party::new + assign_position_with_rng for len(party_index) parties: returns (bit_commitments 96 bytes each, state1 blobs as one
+        bytearray -- secrets: zero it when done)."""
+        npar = len(party_index)
+        assert len(values) == npar and len(blindings) == 32 * npar
+        assert rng is None or len(rng) == 64 * (2 * n + 2) * npar
+        pi = (C.c_uint32 * max(npar, 1))(*party_index)
+        va = (C.c_uint64 * max(npar, 1))(*values)
+        s1 = self._L.bpgpu_mpc_state1_bytes(n)
+        bc = C.create_string_buffer(96 * max(npar, 1))
+        st = bytearray(s1 * max(npar, 1))
+        stb = (C.c_char * len(st)).from_buffer(st)
+        self._chk(self._L.bpgpu_mpc_party_bit_commit(self.h, n, npar, pi, va, blindings, rng, bc, C.cast(stb, C.c_char_p)))
+        del stb
+        return bc.raw[:96 * npar], (st if npar else bytearray())
+
+    def mpc_party_poly_commit(self, n, state1, bit_challenges, rng=None):
+        """apply_challenge_with_rng: state1 blobs, (y, z) per party (64 bytes each) or one shared pair -> (poly_commitments, state2 bytearray, status)."""
+        s1, s2 = self.mpc_state_bytes(n)
+        npar = len(state1) // s1
+        assert len(state1) == npar * s1 and len(bit_challenges) in (64, 64 * npar)
+        assert rng is None or len(rng) == 128 * npar
+        shared = 1 if (len(bit_challenges) == 64 and npar != 1) else 0
+        pc, status = C.create_string_buffer(64 * max(npar, 1)), C.create_string_buffer(max(npar, 1))
+        st = bytearray(s2 * max(npar, 1))
+        stb = (C.c_char * len(st)).from_buffer(st)
+        self._chk(self._L.bpgpu_mpc_party_poly_commit(self.h, n, npar, bytes(state1), bytes(bit_challenges), shared, rng, pc, C.cast(stb, C.c_char_p), status))
+        del stb
+        return pc.raw[:64 * npar], (st if npar else bytearray()), status.raw[:npar]
+
+    def mpc_party_proof_share(self, n, state2, poly_challenges):
+        """PartyAwaitingPolyChallenge::apply_challenge: state2 blobs, x per party (32 bytes each) or one shared -> (shares, status)."""
+        _, s2 = self.mpc_state_bytes(n)
+        npar = len(state2) // s2
+        assert len(state2) == npar * s2 and len(poly_challenges) in (32, 32 * npar)
+        shared = 1 if (len(poly_challenges) == 32 and npar != 1) else 0
+        sl = 32 * (3 + 2 * n)
+        sh, status = C.create_string_buffer(sl * max(npar, 1)), C.create_string_buffer(max(npar, 1))
+        self._chk(self._L.bpgpu_mpc_party_proof_share(self.h, n, npar, bytes(state2), bytes(poly_challenges), shared, sh, status))
+        return sh.raw[:sl * npar], status.raw[:npar]
+
+    @staticmethod
+    def _mpc_ts(nsess, label, transcripts):
+        if transcripts is None:
+            return label, len(label), None, 0
+        assert len(transcripts) in (TRANSCRIPT_BYTES, TRANSCRIPT_BYTES * nsess)
+        return None, 0, bytes(transcripts), (0 if (len(transcripts) == TRANSCRIPT_BYTES and nsess != 1) else TRANSCRIPT_BYTES)
+
+    def mpc_dealer_bit_challenge(self, n, m, bit_commitments, label=b"", transcripts=None):
+        """Dealer::new + receive_bit_commitments for len(bit_commitments) / (96 m) sessions -> (y z per session, compress(A) compress(S) per
+        session, advanced transcripts, status).  transcripts: None (Transcript::new(label)), one 208-byte state, or one per session."""
+        ns = len(bit_commitments) // (96 * m)
+        assert len(bit_commitments) == ns * 96 * m
+        lb, ll, ts, stride = self._mpc_ts(ns, label, transcripts)
+        ch, sums = C.create_string_buffer(64 * max(ns, 1)), C.create_string_buffer(64 * max(ns, 1))
+        tso, status = C.create_string_buffer(TRANSCRIPT_BYTES * max(ns, 1)), C.create_string_buffer(max(ns, 1))
+        self._chk(self._L.bpgpu_mpc_dealer_bit_challenge(self.h, n, m, ns, bytes(bit_commitments), lb, ll, ts, stride, ch, sums, tso, status))
+        return ch.raw[:64 * ns], sums.raw[:64 * ns], tso.raw[:TRANSCRIPT_BYTES * ns], status.raw[:ns]
+
+    def mpc_dealer_poly_challenge(self, m, poly_commitments, transcripts):
+        """receive_poly_commitments -> (x per session, compress(T_1) compress(T_2) per session, advanced transcripts, status)."""
+        ns = len(poly_commitments) // (64 * m)
+        assert len(poly_commitments) == ns * 64 * m and len(transcripts) == TRANSCRIPT_BYTES * ns
+        ts = C.create_string_buffer(bytes(transcripts), TRANSCRIPT_BYTES * max(ns, 1))
+        x, sums, status = C.create_string_buffer(32 * max(ns, 1)), C.create_string_buffer(64 * max(ns, 1)), C.create_string_buffer(max(ns, 1))
+        self._chk(self._L.bpgpu_mpc_dealer_poly_challenge(self.h, m, ns, bytes(poly_commitments), ts, x, sums, status))
+        return x.raw[:32 * ns], sums.raw[:64 * ns], ts.raw[:TRANSCRIPT_BYTES * ns], status.raw[:ns]
+
+    def mpc_dealer_assemble(self, n, m, shares, bit_commitments, poly_commitments, challenges, transcripts, label=b"", initial_transcripts=None,
+                            rng64=None, trusted=False):
+        """assemble_shares + receive_shares_with_rng / receive_trusted_shares -> (proofs, bad_shares (m bytes per session), status,
+        advanced transcripts).  challenges: y, z, x per session; label / initial_transcripts: what Dealer::new was given."""
+        sl = 32 * (3 + 2 * n)
+        ns = len(shares) // (sl * m)
+        assert len(shares) == ns * sl * m and len(bit_commitments) == ns * 96 * m and len(poly_commitments) == ns * 64 * m
+        assert len(challenges) == 96 * ns and len(transcripts) == TRANSCRIPT_BYTES * ns and (rng64 is None or len(rng64) == 64 * ns)
+        lb, ll, its, stride = self._mpc_ts(ns, label, initial_transcripts)
+        pl = 32 * (9 + 2 * ((n * m).bit_length() - 1))
+        ts = C.create_string_buffer(bytes(transcripts), TRANSCRIPT_BYTES * max(ns, 1))
+        pr, bad, status = C.create_string_buffer(pl * max(ns, 1)), C.create_string_buffer(m * max(ns, 1)), C.create_string_buffer(max(ns, 1))
+        self._chk(self._L.bpgpu_mpc_dealer_assemble(self.h, n, m, ns, bytes(shares), bytes(bit_commitments), bytes(poly_commitments), bytes(challenges), ts,
+                                                    lb, ll, its, stride, rng64, 1 if trusted else 0, pr, bad, status))
+        return pr.raw[:pl * ns], bad.raw[:m * ns], status.raw[:ns], ts.raw[:TRANSCRIPT_BYTES * ns]
 
     # ---- instrumentation ----
     def profile_enable(self, on=True):

@@ -3719,6 +3719,682 @@ extern "C" int bpgpu_rangeproof_prove_batch(bpgpu_ctx *c, size_t n, size_t m, si
 }
 
 // ============================================================================
+// the multi-party aggregation protocol: parties (mpc_party.h) and dealer (mpc_dealer.h)
+// ============================================================================
+// working set of the party / dealer calls: the prover's block (cleared by prover_exit on the way out)
+static int mpc_work_reserve(bpgpu_ctx *c, size_t need) {
+    if (c->rpp_cap >= need) return BPGPU_OK;
+    HIPCHK(c, hipDeviceSynchronize());
+    if (c->rpp_buf) HIPCHK(c, hipFree(c->rpp_buf));
+    c->rpp_buf = nullptr;
+    c->rpp_cap = 0;
+    HIPCHK(c, hipMalloc((void **)&c->rpp_buf, need + need / 8));
+    c->rpp_cap = need + need / 8;
+    return BPGPU_OK;
+}
+static bool mpc_bitsize_ok(size_t n) { return n == 8 || n == 16 || n == 32 || n == 64; }
+
+// the id lists of every position for bitsize n: [party_capacity][2n + 2] (mpc_fill_ids), cached like gen_ids_for's lists
+static int mpc_ids_for(bpgpu_ctx *c, size_t n, uint32_t **out) {
+    auto key = std::make_pair(n, (size_t)1 << 41);
+    auto it = c->gen_ids_cache.find(key);
+    if (it != c->gen_ids_cache.end()) {
+        *out = it->second;
+        return BPGPU_OK;
+    }
+    const size_t stride = 2 * n + 2;
+    std::vector<uint32_t> ids(c->party_capacity * stride);
+    for (size_t j = 0; j < c->party_capacity; j++) mpc_fill_ids(ids.data() + j * stride, (uint32_t)n, (uint32_t)j, (uint32_t)c->gens_capacity, (uint32_t)c->party_capacity);
+    uint32_t *d = nullptr;
+    HIPCHK(c, hipMalloc((void **)&d, ids.size() * 4));
+    HIPCHK(c, hipMemcpy(d, ids.data(), ids.size() * 4, hipMemcpyHostToDevice));
+    c->gen_ids_cache[key] = d;
+    *out = d;
+    return BPGPU_OK;
+}
+
+struct mpc_plan {
+    uint32_t nslots = 0;
+    std::vector<uint32_t> row_slot, slot_row, blk_pos, slot_pos;
+};
+static void mpc_make_plan(mpc_plan &pl, size_t nrows, const uint32_t *pos, size_t npos) {
+    const size_t cap = (size_t)mpc_plan_cap(nrows, npos);
+    pl.row_slot.assign(nrows, 0);
+    pl.slot_row.assign(cap, MPC_NO_ROW);
+    pl.blk_pos.assign(cap / MPC_WAVE, 0);
+    pl.nslots = mpc_plan_slots((uint32_t)nrows, pos, (uint32_t)npos, pl.row_slot.data(), pl.slot_row.data(), pl.blk_pos.data());
+    pl.slot_pos.assign(pl.nslots, MPC_NO_ROW);
+    for (uint32_t s = 0; s < pl.nslots; s++)
+        if (pl.slot_row[s] != MPC_NO_ROW) pl.slot_pos[s] = pos[pl.slot_row[s]];
+}
+
+// kinds * nslots multiscalar multiplications over the first n_terms generator terms of each row's POSITION (k_mpc.hip): rows
+// [kind][slot] of n_terms scalars -> d_out [kinds * nslots][8 words].  Context option prover_constant_time: the constant-time walk.
+static int mpc_walk(bpgpu_ctx *c, hipStream_t s, size_t n, uint32_t kinds, uint32_t nslots, uint32_t n_terms, const uint32_t *d_scalars, const uint32_t *d_blk_pos,
+                    const uint32_t *d_slot_pos, uint32_t *d_out) {
+    const bool ct = c->prover_ct;
+    if (ct) {
+        const int rcc = build_ct_table(c);
+        if (rcc) return rcc;
+    }
+    uint32_t *d_ids = nullptr;
+    int rc = mpc_ids_for(c, n, &d_ids);
+    if (rc) return rc;
+    const fb_params prm = ct ? c->prm_ct : c->prm;
+    const uint32_t nrows = kinds * nslots, npairs = n_terms * prm.nwin;
+    if ((uint64_t)npairs * nrows > 0x7fffffffull) return fail(c, BPGPU_ERR_INVALID_ARG, "batch too large for this shape");
+    const uint32_t nsplit = pick_splits(c, nrows, npairs);
+    arena_plan ap;
+    const size_t off_status = ap.add((size_t)nrows * 4), off_digits = ap.add((size_t)npairs * nrows * sizeof(fb_digit) + 16),
+                 off_partial = ap.add((size_t)2 * nsplit * nrows * sizeof(ge_ext) + 16);
+    rc = arena_reserve(c, ap.total);
+    if (rc) return rc;
+    uint32_t *d_status = (uint32_t *)(c->arena + off_status);
+    fb_digit *d_digits = (fb_digit *)(c->arena + off_digits);
+    ge_ext *d_partial = (ge_ext *)(c->arena + off_partial);
+    HIPCHK(c, hipMemsetAsync(d_status, 0, (size_t)nrows * 4, s));
+    const uint32_t nrec = n_terms * nrows, nblk_p = nrows / FB_BLOCK, stride = (uint32_t)(2 * n + 2);
+    if (ct) {
+        LAUNCH(c, s, "fb_recode_ct", k_fb_recode_ct, (nrec + BP_BLOCK - 1) / BP_BLOCK, BP_BLOCK, nrec, prm, nrows, n_terms, d_scalars, d_digits);
+        LAUNCH(c, s, "mpc_accum_ct", k_mpc_accum_ct, nblk_p * nsplit, FB_BLOCK, prm, nrows, nslots, nsplit, npairs, (const uint32_t *)d_ids, stride, d_blk_pos, d_slot_pos,
+               (const fb_digit *)d_digits, (const fb_entry *)c->d_table_ct, d_partial);
+    } else {
+        LAUNCH(c, s, "fb_recode", k_fb_recode, (nrec + BP_BLOCK - 1) / BP_BLOCK, BP_BLOCK, nrec, prm, nrows, n_terms, d_scalars, d_digits, d_status);
+        LAUNCH(c, s, "mpc_accum", k_mpc_accum, nblk_p * nsplit, FB_BLOCK, prm, nrows, nslots, nsplit, npairs, (const uint32_t *)d_ids, stride, d_blk_pos, d_slot_pos,
+               (const fb_digit *)d_digits, (const fb_entry *)c->d_table, d_partial);
+    }
+    ge_ext *d_red = nullptr;
+    uint32_t nred = 0;
+    enqueue_fb_reduce(c, s, nrows, nsplit, d_partial, &d_red, &nred);
+    LAUNCH(c, s, "shared_finish", k_shared_finish, (nrows + 63) / 64, 64, nrows, nred, (const ge_ext *)nullptr, 0, (const ge_ext *)d_red, (const uint32_t *)d_status, d_out,
+           (uint8_t *)nullptr, (uint8_t *)nullptr);
+    HIPCHK(c, hipGetLastError());
+    return BPGPU_OK;
+}
+
+extern "C" size_t bpgpu_mpc_state1_bytes(size_t n) { return 4 * (size_t)MPC_ST1_WORDS(n); }
+extern "C" size_t bpgpu_mpc_state2_bytes(size_t n) { return 4 * (size_t)MPC_ST2_WORDS(n); }
+
+// the state blobs that came back through the staging block are secrets too: cleared once they have been handed to the caller
+static void mpc_clear_staged_state(bpgpu_ctx *c, char *h, size_t off, size_t bytes) {
+    memset(h + off, 0, bytes);
+    if (h == c->pin) c->last_secret_bytes = off + bytes;
+}
+
+// ---- step 1: Party::new + assign_position_with_rng -------------------------------------------------------------------------
+extern "C" int bpgpu_mpc_party_bit_commit(bpgpu_ctx *c, size_t n, size_t nparties, const uint32_t *party_index, const uint64_t *values, const uint8_t *blindings,
+                                          const uint8_t *rng, uint8_t *bit_commitments, uint8_t *state1) {
+    if (!c) return BPGPU_ERR_INVALID_ARG;
+    if (nparties == 0) return BPGPU_OK;
+    if (!party_index || !values || !blindings || !bit_commitments || !state1) return BPGPU_ERR_INVALID_ARG;
+    if (!mpc_bitsize_ok(n)) return fail(c, BPGPU_ERR_INVALID_ARG, "InvalidBitsize: n must be 8, 16, 32 or 64 (party.rs:41-43)");
+    std::lock_guard<std::mutex> lk(c->mu);
+    HIPCHK(c, hipSetDevice(c->device));
+    if (!c->d_table) return fail(c, BPGPU_ERR_NO_GENS, "generators not loaded");
+    if (c->gens_capacity < n) return fail(c, BPGPU_ERR_NO_GENS, "InvalidGeneratorsLength: generators too small for n=%zu (party.rs:44-46)", n);
+    for (size_t r = 0; r < nparties; r++)
+        if (party_index[r] >= c->party_capacity)
+            return fail(c, BPGPU_ERR_NO_GENS, "InvalidGeneratorsLength: position %u of party %zu >= party_capacity %zu (party.rs:88-90)", party_index[r], r, c->party_capacity);
+    if ((uint64_t)mpc_plan_cap(nparties, c->party_capacity) * 2 * (2 * n + 2) > 0x7fffffffull / 64) return fail(c, BPGPU_ERR_INVALID_ARG, "batch too large for this shape");
+    mpc_plan pl;
+    mpc_make_plan(pl, nparties, party_index, c->party_capacity);
+    const size_t ns = pl.nslots, per_rng = 64 * (2 * n + 2), st_bytes = bpgpu_mpc_state1_bytes(n);
+    hipStream_t s = c->stream;
+    int rc = ctx_enter(c, s);
+    if (rc) return rc;
+    prover_exit px{c, s};
+    const size_t sz_sp = align_up(ns * 4), sz_bp = align_up(ns / MPC_WAVE * 4), sz_val = align_up(ns * 8), sz_bl = align_up(ns * 32), sz_rng = align_up(ns * per_rng);
+    const size_t sz_in = sz_sp + sz_bp + sz_val + sz_bl + sz_rng, sz_st = align_up(ns * st_bytes), sz_v = align_up(ns * 32), sz_as = align_up(2 * ns * 32);
+    const size_t sz_out = sz_st + sz_v + sz_as;
+    rc = io_reserve(c, sz_in + sz_out);
+    if (rc) return px.finish(rc);
+    char *h = nullptr;
+    rc = pin_alloc(c, s, sz_in + sz_out, &h);
+    if (rc) return px.finish(rc);
+    px.h = h;
+    px.host_secret_bytes = sz_in;
+    memset(h, 0, sz_in);
+    memcpy(h, pl.slot_pos.data(), ns * 4);
+    memcpy(h + sz_sp, pl.blk_pos.data(), ns / MPC_WAVE * 4);
+    char *h_val = h + sz_sp + sz_bp, *h_bl = h_val + sz_val, *h_rng = h_bl + sz_bl;
+    if (!rng) {   // Scalar::random(&mut thread_rng()): OS CSPRNG (padding slots draw too; they are never read)
+        rc = os_random(c, h_rng, ns * per_rng);
+        if (rc) return px.finish(rc);
+    }
+    for (size_t r = 0; r < nparties; r++) {
+        const size_t sl = pl.row_slot[r];
+        memcpy(h_val + sl * 8, values + r, 8);
+        memcpy(h_bl + sl * 32, blindings + r * 32, 32);
+        if (rng) memcpy(h_rng + sl * per_rng, rng + r * per_rng, per_rng);
+    }
+    char *d = c->io_dev;
+    const uint32_t *d_sp = (const uint32_t *)d, *d_bp = (const uint32_t *)(d + sz_sp);
+    const uint64_t *d_val = (const uint64_t *)(d + sz_sp + sz_bp);
+    const uint8_t *d_bl = (const uint8_t *)d_val + sz_val, *d_rng = d_bl + sz_bl;
+    uint32_t *d_st = (uint32_t *)(d + sz_in), *d_v = (uint32_t *)((char *)d_st + sz_st), *d_as = (uint32_t *)((char *)d_v + sz_v);
+    PX_HIPCHK(px, hipMemcpyAsync(d, h, sz_in, hipMemcpyHostToDevice, s));
+    const size_t row_len = 2 * n + 2, w_v = align_up(ns * 2 * 32), w_as = align_up(2 * ns * row_len * 32);
+    rc = mpc_work_reserve(c, w_v + w_as);
+    if (rc) return px.finish(rc);
+    uint32_t *gsV = (uint32_t *)c->rpp_buf, *gsAS = (uint32_t *)(c->rpp_buf + w_v);
+    do {
+        if (hipMemsetAsync(c->rpp_buf, 0, w_v + w_as, s) != hipSuccess || hipMemsetAsync(d_st, 0, sz_st, s) != hipSuccess) {
+            rc = fail(c, BPGPU_ERR_HIP, "memset failed");
+            break;
+        }
+        const uint32_t ns32 = (uint32_t)ns, nbits = (uint32_t)(ns * n), n_b = (ns32 + BP_BLOCK - 1) / BP_BLOCK;
+        LAUNCH(c, s, "mpc_commit1", k_mpc_commit1, n_b + (nbits + BP_BLOCK - 1) / BP_BLOCK, BP_BLOCK, n_b, nbits, (uint32_t)n, ns32, d_sp, d_val, d_bl, d_rng, gsV, gsAS, d_st);
+        rc = mpc_walk(c, s, n, 1, ns32, 2, gsV, d_bp, d_sp, d_v);                       // V_j = v B + v_blinding B~ (party.rs:55)
+        if (rc) break;
+        rc = mpc_walk(c, s, n, 2, ns32, (uint32_t)row_len, gsAS, d_bp, d_sp, d_as);     // A_j, S_j over B~, G_j(n), H_j(n) (party.rs:99-124)
+    } while (0);
+    char *h_out = h + sz_in;
+    if (!rc && hipMemcpyAsync(h_out, d_st, sz_out, hipMemcpyDeviceToHost, s) != hipSuccess) rc = fail(c, BPGPU_ERR_HIP, "D2H copy failed");
+    rc = px.finish(rc);
+    if (!rc)
+        for (size_t r = 0; r < nparties; r++) {
+            const size_t sl = pl.row_slot[r];
+            memcpy(state1 + r * st_bytes, h_out + sl * st_bytes, st_bytes);
+            memcpy(bit_commitments + r * 96, h_out + sz_st + sl * 32, 32);
+            memcpy(bit_commitments + r * 96 + 32, h_out + sz_st + sz_v + sl * 32, 32);
+            memcpy(bit_commitments + r * 96 + 64, h_out + sz_st + sz_v + (ns + sl) * 32, 32);
+        }
+    mpc_clear_staged_state(c, h, sz_in, sz_st);
+    return rc;
+}
+
+// validates the headers of caller-held state blobs; pos (optional): the rows' positions
+static int mpc_check_states(bpgpu_ctx *c, size_t n, size_t nrows, const uint8_t *state, size_t st_bytes, uint32_t magic, uint32_t *pos) {
+    for (size_t r = 0; r < nrows; r++) {
+        uint32_t hd[3];
+        memcpy(hd, state + r * st_bytes, 12);
+        if (hd[0] != magic || hd[1] != n || hd[2] >= c->party_capacity)
+            return fail(c, BPGPU_ERR_INVALID_ARG, "state blob %zu is not a state of this step for n=%zu on this generator set", r, n);
+        if (pos) pos[r] = hd[2];
+    }
+    return BPGPU_OK;
+}
+
+// ---- step 2: PartyAwaitingBitChallenge::apply_challenge_with_rng ------------------------------------------------------------
+extern "C" int bpgpu_mpc_party_poly_commit(bpgpu_ctx *c, size_t n, size_t nparties, const uint8_t *state1, const uint8_t *bit_challenges, int challenges_shared,
+                                           const uint8_t *rng, uint8_t *poly_commitments, uint8_t *state2, uint8_t *status) {
+    if (!c) return BPGPU_ERR_INVALID_ARG;
+    if (nparties == 0) return BPGPU_OK;
+    if (!state1 || !bit_challenges || !poly_commitments || !state2 || !status) return BPGPU_ERR_INVALID_ARG;
+    if (!mpc_bitsize_ok(n)) return fail(c, BPGPU_ERR_INVALID_ARG, "InvalidBitsize: n must be 8, 16, 32 or 64 (party.rs:41-43)");
+    std::lock_guard<std::mutex> lk(c->mu);
+    HIPCHK(c, hipSetDevice(c->device));
+    if (!c->d_table) return fail(c, BPGPU_ERR_NO_GENS, "generators not loaded");
+    if (c->gens_capacity < n) return fail(c, BPGPU_ERR_NO_GENS, "InvalidGeneratorsLength: generators too small for n=%zu", n);
+    const size_t st1_bytes = bpgpu_mpc_state1_bytes(n), st2_bytes = bpgpu_mpc_state2_bytes(n);
+    std::vector<uint32_t> pos(nparties);
+    int rc = mpc_check_states(c, n, nparties, state1, st1_bytes, MPC_MAGIC1, pos.data());
+    if (rc) return rc;
+    if ((uint64_t)mpc_plan_cap(nparties, c->party_capacity) * st2_bytes > 0x7fffffffull) return fail(c, BPGPU_ERR_INVALID_ARG, "batch too large for this shape");
+    mpc_plan pl;
+    mpc_make_plan(pl, nparties, pos.data(), c->party_capacity);
+    const size_t ns = pl.nslots, nch = challenges_shared ? 1 : ns;
+    hipStream_t s = c->stream;
+    rc = ctx_enter(c, s);
+    if (rc) return rc;
+    prover_exit px{c, s};
+    const size_t sz_sp = align_up(ns * 4), sz_bp = align_up(ns / MPC_WAVE * 4), sz_s1 = align_up(ns * st1_bytes), sz_ch = align_up(nch * 64), sz_rng = align_up(ns * 128);
+    const size_t sz_in = sz_sp + sz_bp + sz_s1 + sz_ch + sz_rng, sz_s2 = align_up(ns * st2_bytes), sz_t = align_up(2 * ns * 32), sz_stat = align_up(ns * 4);
+    const size_t sz_out = sz_s2 + sz_t + sz_stat;
+    rc = io_reserve(c, sz_in + sz_out);
+    if (rc) return px.finish(rc);
+    char *h = nullptr;
+    rc = pin_alloc(c, s, sz_in + sz_out, &h);
+    if (rc) return px.finish(rc);
+    px.h = h;
+    px.host_secret_bytes = sz_in;
+    memset(h, 0, sz_in);
+    memcpy(h, pl.slot_pos.data(), ns * 4);
+    memcpy(h + sz_sp, pl.blk_pos.data(), ns / MPC_WAVE * 4);
+    char *h_s1 = h + sz_sp + sz_bp, *h_ch = h_s1 + sz_s1, *h_rng = h_ch + sz_ch;
+    if (!rng) {
+        rc = os_random(c, h_rng, ns * 128);
+        if (rc) return px.finish(rc);
+    }
+    if (challenges_shared) memcpy(h_ch, bit_challenges, 64);
+    for (size_t r = 0; r < nparties; r++) {
+        const size_t sl = pl.row_slot[r];
+        memcpy(h_s1 + sl * st1_bytes, state1 + r * st1_bytes, st1_bytes);
+        if (!challenges_shared) memcpy(h_ch + sl * 64, bit_challenges + r * 64, 64);
+        if (rng) memcpy(h_rng + sl * 128, rng + r * 128, 128);
+    }
+    char *d = c->io_dev;
+    const uint32_t *d_sp = (const uint32_t *)d, *d_bp = (const uint32_t *)(d + sz_sp), *d_s1 = (const uint32_t *)(d + sz_sp + sz_bp);
+    const uint8_t *d_ch = (const uint8_t *)d_s1 + sz_s1, *d_rng = d_ch + sz_ch;
+    uint32_t *d_s2 = (uint32_t *)(d + sz_in), *d_t = (uint32_t *)((char *)d_s2 + sz_s2), *d_stat = (uint32_t *)((char *)d_t + sz_t);
+    PX_HIPCHK(px, hipMemcpyAsync(d, h, sz_in, hipMemcpyHostToDevice, s));
+    const size_t w_t = align_up(2 * ns * 2 * 32);
+    rc = mpc_work_reserve(c, w_t);
+    if (rc) return px.finish(rc);
+    uint32_t *gsT = (uint32_t *)c->rpp_buf;
+    do {
+        if (hipMemsetAsync(gsT, 0, w_t, s) != hipSuccess || hipMemsetAsync(d_s2, 0, sz_out, s) != hipSuccess) {
+            rc = fail(c, BPGPU_ERR_HIP, "memset failed");
+            break;
+        }
+        const uint32_t ns32 = (uint32_t)ns;
+        LAUNCH(c, s, "mpc_poly", k_mpc_poly, (ns32 + BP_BLOCK - 1) / BP_BLOCK, BP_BLOCK, (uint32_t)n, ns32, d_sp, d_s1, d_ch, challenges_shared ? 1u : 0u, d_rng, d_s2, gsT,
+               d_stat);
+        rc = mpc_walk(c, s, n, 2, ns32, 2, gsT, d_bp, d_sp, d_t);   // T_i_j = t_i B + t_i_blinding B~ (party.rs:224-227)
+    } while (0);
+    char *h_out = h + sz_in;
+    if (!rc && hipMemcpyAsync(h_out, d_s2, sz_out, hipMemcpyDeviceToHost, s) != hipSuccess) rc = fail(c, BPGPU_ERR_HIP, "D2H copy failed");
+    rc = px.finish(rc);
+    if (!rc)
+        for (size_t r = 0; r < nparties; r++) {
+            const size_t sl = pl.row_slot[r];
+            uint32_t st;
+            memcpy(&st, h_out + sz_s2 + sz_t + sl * 4, 4);
+            status[r] = (uint8_t)st;
+            memcpy(state2 + r * st2_bytes, h_out + sl * st2_bytes, st2_bytes);
+            if (st) {
+                memset(poly_commitments + r * 64, 0, 64);
+            } else {
+                memcpy(poly_commitments + r * 64, h_out + sz_s2 + sl * 32, 32);
+                memcpy(poly_commitments + r * 64 + 32, h_out + sz_s2 + (ns + sl) * 32, 32);
+            }
+        }
+    mpc_clear_staged_state(c, h, sz_in, sz_s2);
+    return rc;
+}
+
+// ---- step 3: PartyAwaitingPolyChallenge::apply_challenge -------------------------------------------------------------------
+extern "C" int bpgpu_mpc_party_proof_share(bpgpu_ctx *c, size_t n, size_t nparties, const uint8_t *state2, const uint8_t *poly_challenges, int challenges_shared,
+                                           uint8_t *shares, uint8_t *status) {
+    if (!c) return BPGPU_ERR_INVALID_ARG;
+    if (nparties == 0) return BPGPU_OK;
+    if (!state2 || !poly_challenges || !shares || !status) return BPGPU_ERR_INVALID_ARG;
+    if (!mpc_bitsize_ok(n)) return fail(c, BPGPU_ERR_INVALID_ARG, "InvalidBitsize: n must be 8, 16, 32 or 64 (party.rs:41-43)");
+    std::lock_guard<std::mutex> lk(c->mu);
+    HIPCHK(c, hipSetDevice(c->device));
+    if (!c->d_gens) return fail(c, BPGPU_ERR_NO_GENS, "generators not loaded");
+    const size_t st2_bytes = bpgpu_mpc_state2_bytes(n), share_len = 32 * (3 + 2 * n), nch = challenges_shared ? 1 : nparties;
+    int rc = mpc_check_states(c, n, nparties, state2, st2_bytes, MPC_MAGIC2, nullptr);
+    if (rc) return rc;
+    if ((uint64_t)nparties * st2_bytes > 0x7fffffffull) return fail(c, BPGPU_ERR_INVALID_ARG, "batch too large for this shape");
+    hipStream_t s = c->stream;
+    rc = ctx_enter(c, s);
+    if (rc) return rc;
+    prover_exit px{c, s};
+    const size_t sz_s2 = align_up(nparties * st2_bytes), sz_x = align_up(nch * 32), sz_in = sz_s2 + sz_x, sz_sh = align_up(nparties * share_len), sz_stat = align_up(nparties);
+    rc = io_reserve(c, sz_in + sz_sh + sz_stat);
+    if (rc) return px.finish(rc);
+    char *h = nullptr;
+    rc = pin_alloc(c, s, sz_in + sz_sh + sz_stat, &h);
+    if (rc) return px.finish(rc);
+    px.h = h;
+    px.host_secret_bytes = sz_in;
+    memcpy(h, state2, nparties * st2_bytes);
+    memcpy(h + sz_s2, poly_challenges, nch * 32);
+    char *d = c->io_dev, *d_sh = d + sz_in, *d_stat = d_sh + sz_sh;
+    PX_HIPCHK(px, hipMemcpyAsync(d, h, sz_in, hipMemcpyHostToDevice, s));
+    PX_HIPCHK(px, hipMemsetAsync(d_sh, 0, sz_sh + sz_stat, s));
+    const uint32_t np32 = (uint32_t)nparties;
+    LAUNCH(c, s, "mpc_share", k_mpc_share, (np32 + BP_BLOCK - 1) / BP_BLOCK, BP_BLOCK, np32, (uint32_t)n, (const uint32_t *)d, (const uint8_t *)(d + sz_s2),
+           challenges_shared ? 1u : 0u, (uint32_t *)d_sh, (uint8_t *)d_stat);
+    if (hipGetLastError() != hipSuccess) rc = fail(c, BPGPU_ERR_HIP, "launch failed");
+    char *h_out = h + sz_in;
+    if (!rc && hipMemcpyAsync(h_out, d_sh, sz_sh + sz_stat, hipMemcpyDeviceToHost, s) != hipSuccess) rc = fail(c, BPGPU_ERR_HIP, "D2H copy failed");
+    rc = px.finish(rc);
+    if (rc) return rc;
+    memcpy(shares, h_out, nparties * share_len);
+    memcpy(status, h_out + sz_sh, nparties);
+    return BPGPU_OK;
+}
+
+// ---- dealer ------------------------------------------------------------------------------------------------------------------
+static int mpc_dealer_shape(bpgpu_ctx *c, size_t n, size_t m, size_t *k_out) {
+    if (!mpc_bitsize_ok(n)) return fail(c, BPGPU_ERR_INVALID_ARG, "InvalidBitsize: n must be 8, 16, 32 or 64 (dealer.rs:44-46)");
+    if (m == 0 || (m & (m - 1))) return fail(c, BPGPU_ERR_INVALID_ARG, "InvalidAggregation: m must be a power of two (dealer.rs:47-49)");
+    size_t k = 0;
+    while (((size_t)1 << k) < n * m) k++;
+    if (k > BP_RP_MAX_K) return fail(c, BPGPU_ERR_INVALID_ARG, "n*m > 2^%d not supported", BP_RP_MAX_K);
+    if (!c->d_table) return fail(c, BPGPU_ERR_NO_GENS, "generators not loaded");
+    if (c->gens_capacity < n || c->party_capacity < m)
+        return fail(c, BPGPU_ERR_NO_GENS, "InvalidGeneratorsLength: generators too small for n=%zu m=%zu (dealer.rs:50-55)", n, m);
+    if (k_out) *k_out = k;
+    return BPGPU_OK;
+}
+// nsessions x ncol point sums on the device (k_mpc_ptsum): in = nsessions x m records of `rec` bytes -> out nsessions x ncol x 32, st nsessions bytes
+static int mpc_point_sums(bpgpu_ctx *c, size_t m, size_t nsessions, const uint8_t *in, uint32_t rec, uint32_t off, uint32_t ncol, uint8_t *out, uint8_t *st) {
+    if ((uint64_t)nsessions * m * rec > 0x7fffffffull) return fail(c, BPGPU_ERR_INVALID_ARG, "batch too large for this shape");
+    hipStream_t s = c->stream;
+    int rc = ctx_enter(c, s);
+    if (rc) return rc;
+    const size_t sz_in = align_up(nsessions * m * rec), sz_o = align_up(nsessions * ncol * 32), sz_st = align_up(nsessions * 4);
+    rc = io_reserve(c, sz_in + sz_o + sz_st);
+    if (rc) return rc;
+    char *h = nullptr;
+    rc = pin_alloc(c, s, sz_in + sz_o + sz_st, &h);
+    if (rc) return rc;
+    memcpy(h, in, nsessions * m * rec);
+    char *d = c->io_dev, *d_o = d + sz_in, *d_st = d_o + sz_o;
+    HIPCHK(c, hipMemcpyAsync(d, h, sz_in, hipMemcpyHostToDevice, s));
+    if (hipMemsetAsync(d_st, 0, sz_st, s) != hipSuccess) rc = fail(c, BPGPU_ERR_HIP, "memset failed");
+    const uint32_t nt = (uint32_t)(nsessions * ncol);
+    if (!rc) {
+        LAUNCH(c, s, "mpc_ptsum", k_mpc_ptsum, (nt + BP_BLOCK - 1) / BP_BLOCK, BP_BLOCK, nt, (uint32_t)m, ncol, rec, off, (const uint8_t *)d, (uint32_t *)d_o, (uint32_t *)d_st);
+        if (hipGetLastError() != hipSuccess) rc = fail(c, BPGPU_ERR_HIP, "launch failed");
+    }
+    char *h_out = h + sz_in;
+    if (!rc && hipMemcpyAsync(h_out, d_o, sz_o + sz_st, hipMemcpyDeviceToHost, s) != hipSuccess) rc = fail(c, BPGPU_ERR_HIP, "D2H copy failed");
+    const int rc2 = ctx_leave(c, s), rc3 = host_wait(c, s);
+    if (rc || rc2 || rc3) return rc ? rc : (rc2 ? rc2 : rc3);
+    memcpy(out, h_out, nsessions * ncol * 32);
+    for (size_t p = 0; p < nsessions; p++) {
+        uint32_t v;
+        memcpy(&v, h_out + sz_o + p * 4, 4);
+        st[p] = (uint8_t)v;
+    }
+    return BPGPU_OK;
+}
+
+// ---- step 4: Dealer::new + receive_bit_commitments ---------------------------------------------------------------------------
+extern "C" int bpgpu_mpc_dealer_bit_challenge(bpgpu_ctx *c, size_t n, size_t m, size_t nsessions, const uint8_t *bit_commitments, const uint8_t *label,
+                                              size_t label_len, const uint8_t *transcripts, size_t transcript_stride, uint8_t *bit_challenges,
+                                              uint8_t *sums_out, uint8_t *transcripts_out, uint8_t *status) {
+    if (!c || (label_len && !label)) return BPGPU_ERR_INVALID_ARG;
+    if (nsessions == 0) return BPGPU_OK;
+    if (!bit_commitments || !bit_challenges || !transcripts_out || !status) return BPGPU_ERR_INVALID_ARG;
+    if (transcripts && transcript_stride != 0 && transcript_stride != BPGPU_TRANSCRIPT_BYTES)
+        return fail(c, BPGPU_ERR_INVALID_ARG, "transcript_stride neither 0 nor BPGPU_TRANSCRIPT_BYTES");
+    const size_t TS = BPGPU_TRANSCRIPT_BYTES;
+    if (transcripts)
+        for (size_t p = 0; p < (transcript_stride ? nsessions : 1); p++)
+            if (!ts_state_ok(transcripts + p * TS)) return fail(c, BPGPU_ERR_INVALID_ARG, "malformed transcript state %zu", p);
+    std::vector<uint8_t> sums(nsessions * 64), st(nsessions);
+    {
+        std::lock_guard<std::mutex> lk(c->mu);
+        HIPCHK(c, hipSetDevice(c->device));
+        int rc = mpc_dealer_shape(c, n, m, nullptr);
+        if (rc) return rc;
+        rc = mpc_point_sums(c, m, nsessions, bit_commitments, 96, 32, 2, sums.data(), st.data());   // A = sum A_j, S = sum S_j (dealer.rs:117-118)
+        if (rc) return rc;
+    }
+    uint8_t st_new[BPGPU_TRANSCRIPT_BYTES];
+    if (!transcripts) bpgpu_transcript_new(label, label_len, st_new);
+    const uint8_t rp[13] = {'r', 'a', 'n', 'g', 'e', 'p', 'r', 'o', 'o', 'f', ' ', 'v', '1'}, ln[1] = {'n'}, lm[1] = {'m'}, lV[1] = {'V'}, lA[1] = {'A'}, lS[1] = {'S'},
+                  ly[1] = {'y'}, lz[1] = {'z'};
+    for (size_t p = 0; p < nsessions; p++) {
+        const uint8_t *st0 = transcripts ? transcripts + (transcript_stride ? p * TS : 0) : st_new;
+        status[p] = st[p];
+        if (st[p]) {   // an A_j or S_j that does not decode: the session fails, its transcript stays where the caller left it
+            memcpy(transcripts_out + p * TS, st0, TS);
+            memset(bit_challenges + p * 64, 0, 64);
+            if (sums_out) memset(sums_out + p * 64, 0, 64);
+            continue;
+        }
+        uint32_t w[50];
+        strobe t;
+        ts_to_strobe(t, w, st0);
+        merlin_append_message(t, DOM_SEP, 7, rp, 13);             // rangeproof_domain_sep(n, m) (dealer.rs:62)
+        merlin_append_u64(t, ln, 1, n);
+        merlin_append_u64(t, lm, 1, m);
+        for (size_t j = 0; j < m; j++) merlin_append_message(t, lV, 1, bit_commitments + (p * m + j) * 96, 32);   // as given (dealer.rs:112-114)
+        merlin_append_message(t, lA, 1, sums.data() + p * 64, 32);
+        merlin_append_message(t, lS, 1, sums.data() + p * 64 + 32, 32);
+        sc y, z;
+        rp_challenge_scalar(t, ly, 1, y);
+        rp_challenge_scalar(t, lz, 1, z);
+        memcpy(bit_challenges + p * 64, y.v, 32);
+        memcpy(bit_challenges + p * 64 + 32, z.v, 32);
+        if (sums_out) memcpy(sums_out + p * 64, sums.data() + p * 64, 64);
+        ts_from_strobe(transcripts_out + p * TS, t);
+    }
+    return BPGPU_OK;
+}
+
+// ---- step 5: receive_poly_commitments ----------------------------------------------------------------------------------------
+extern "C" int bpgpu_mpc_dealer_poly_challenge(bpgpu_ctx *c, size_t m, size_t nsessions, const uint8_t *poly_commitments, uint8_t *transcripts,
+                                               uint8_t *poly_challenges, uint8_t *sums_out, uint8_t *status) {
+    if (!c) return BPGPU_ERR_INVALID_ARG;
+    if (nsessions == 0) return BPGPU_OK;
+    if (!poly_commitments || !transcripts || !poly_challenges || !status) return BPGPU_ERR_INVALID_ARG;
+    if (m == 0 || (m & (m - 1))) return fail(c, BPGPU_ERR_INVALID_ARG, "InvalidAggregation: m must be a power of two");
+    const size_t TS = BPGPU_TRANSCRIPT_BYTES;
+    for (size_t p = 0; p < nsessions; p++)
+        if (!ts_state_ok(transcripts + p * TS)) return fail(c, BPGPU_ERR_INVALID_ARG, "malformed transcript state %zu", p);
+    std::vector<uint8_t> sums(nsessions * 64), st(nsessions);
+    {
+        std::lock_guard<std::mutex> lk(c->mu);
+        HIPCHK(c, hipSetDevice(c->device));
+        const int rc = mpc_point_sums(c, m, nsessions, poly_commitments, 64, 0, 2, sums.data(), st.data());   // T_i = sum T_i_j (dealer.rs:176-177)
+        if (rc) return rc;
+    }
+    const uint8_t lT1[3] = {'T', '_', '1'}, lT2[3] = {'T', '_', '2'}, lx[1] = {'x'};
+    for (size_t p = 0; p < nsessions; p++) {
+        status[p] = st[p];
+        if (st[p]) {
+            memset(poly_challenges + p * 32, 0, 32);
+            if (sums_out) memset(sums_out + p * 64, 0, 64);
+            continue;
+        }
+        uint32_t w[50];
+        strobe t;
+        ts_to_strobe(t, w, transcripts + p * TS);
+        merlin_append_message(t, lT1, 3, sums.data() + p * 64, 32);
+        merlin_append_message(t, lT2, 3, sums.data() + p * 64 + 32, 32);
+        sc x;
+        rp_challenge_scalar(t, lx, 1, x);
+        memcpy(poly_challenges + p * 32, x.v, 32);
+        if (sums_out) memcpy(sums_out + p * 64, sums.data() + p * 64, 64);
+        ts_from_strobe(transcripts + p * TS, t);
+    }
+    return BPGPU_OK;
+}
+
+// ---- step 6: assemble_shares, receive_shares_with_rng / receive_trusted_shares -----------------------------------------------
+// the assembling half, under the context's mutex: sums and w on the host, vectors and the inner-product argument on the device.
+// skip[p] (in/out): sessions that are void (non-canonical scalars on the way in; undecodable commitments on the way out).
+static int mpc_assemble_locked(bpgpu_ctx *c, size_t n, size_t m, size_t k, size_t nsessions, const uint8_t *shares, const uint8_t *bit_commitments,
+                               const uint8_t *poly_commitments, const uint8_t *challenges, uint8_t *transcripts, std::vector<uint8_t> &skip, uint8_t *status,
+                               uint8_t *proofs_out) {
+    const size_t nm = n * m, proof_len = 32 * (9 + 2 * k), TS = BPGPU_TRANSCRIPT_BYTES, share_len = 32 * (3 + 2 * n);
+    if ((uint64_t)nsessions * 2 * (2 * nm + 2) > 0x7fffffffull / 64 || (uint64_t)nsessions * m * share_len > 0x7fffffffull)
+        return fail(c, BPGPU_ERR_INVALID_ARG, "batch too large for this shape");
+    std::vector<uint8_t> sums(nsessions * 128), pst(2 * nsessions);
+    int rc = mpc_point_sums(c, m, nsessions, bit_commitments, 96, 32, 2, sums.data(), pst.data());
+    if (rc) return rc;
+    {
+        std::vector<uint8_t> tsum(nsessions * 64);
+        rc = mpc_point_sums(c, m, nsessions, poly_commitments, 64, 0, 2, tsum.data(), pst.data() + nsessions);
+        if (rc) return rc;
+        for (size_t p = nsessions; p-- > 0;) {   // -> A, S, T_1, T_2 per session
+            memmove(sums.data() + p * 128, sums.data() + p * 64, 64);
+            memcpy(sums.data() + p * 128 + 64, tsum.data() + p * 64, 64);
+        }
+    }
+    hipStream_t s = c->stream;
+    rc = ctx_enter(c, s);
+    if (rc) return rc;
+    prover_exit px{c, s};
+    const size_t sz_sh = align_up(nsessions * m * share_len), sz_q = align_up(nsessions * 32), sz_sk = align_up(nsessions), sz_ts = align_up(nsessions * TS);
+    const size_t sz_in = sz_sh + 2 * sz_q + sz_sk + sz_ts, sz_pr = align_up(nsessions * proof_len), sz_stb = align_up(nsessions);
+    rc = io_reserve(c, sz_in + sz_pr + sz_stb);
+    if (rc) return px.finish(rc);
+    char *h = nullptr;
+    rc = pin_alloc(c, s, sz_in + sz_pr + sz_stb, &h);
+    if (rc) return px.finish(rc);
+    px.h = h;
+    px.host_secret_bytes = sz_sh;
+    memset(h, 0, sz_in);
+    memcpy(h, shares, nsessions * m * share_len);
+    char *h_yinv = h + sz_sh, *h_w = h_yinv + sz_q, *h_sk = h_w + sz_q, *h_ts = h_sk + sz_sk;
+    std::vector<uint8_t> fixed(nsessions * 96);   // t_x, t_x_blinding, e_blinding
+    const uint8_t ltx[3] = {'t', '_', 'x'}, ltxb[12] = {'t', '_', 'x', '_', 'b', 'l', 'i', 'n', 'd', 'i', 'n', 'g'},
+                  leb[10] = {'e', '_', 'b', 'l', 'i', 'n', 'd', 'i', 'n', 'g'}, lw[1] = {'w'}, lipp[6] = {'i', 'p', 'p', ' ', 'v', '1'}, ln[1] = {'n'};
+    for (size_t p = 0; p < nsessions; p++) {
+        sc y;
+        memcpy(y.v, challenges + p * 96, 32);
+        if (pst[p] || pst[nsessions + p]) {
+            skip[p] = 1;
+            status[p] = (uint8_t)MPC_ST_BAD_POINT;
+        }
+        if (!sc_is_canonical_sc(y)) {
+            skip[p] = 1;
+            status[p] = (uint8_t)MPC_ST_BAD_SCALAR;
+        }
+        h_sk[p] = (char)skip[p];
+        if (skip[p]) {
+            memcpy(h_ts + p * TS, transcripts + p * TS, TS);
+            continue;
+        }
+        sc t_x, t_x_bl, e_bl, wch, yinv;
+        mpc_sum_shares((uint32_t)n, (uint32_t)m, shares + p * m * share_len, t_x, t_x_bl, e_bl, nullptr);
+        memcpy(fixed.data() + p * 96, t_x.v, 32);
+        memcpy(fixed.data() + p * 96 + 32, t_x_bl.v, 32);
+        memcpy(fixed.data() + p * 96 + 64, e_bl.v, 32);
+        uint32_t w[50];
+        strobe t;
+        ts_to_strobe(t, w, transcripts + p * TS);
+        merlin_append_words8(t, ltx, 3, t_x.v);                   // (dealer.rs:268-270)
+        merlin_append_words8(t, ltxb, 12, t_x_bl.v);
+        merlin_append_words8(t, leb, 10, e_bl.v);
+        rp_challenge_scalar(t, lw, 1, wch);                       // Q = w B (dealer.rs:273-274)
+        merlin_append_message(t, DOM_SEP, 7, lipp, 6);            // InnerProductProof::create: innerproduct_domain_sep(nm)
+        merlin_append_u64(t, ln, 1, nm);
+        ts_from_strobe((uint8_t *)h_ts + p * TS, t);
+        sc_invert_safegcd(yinv, y);
+        memcpy(h_yinv + p * 32, yinv.v, 32);
+        memcpy(h_w + p * 32, wch.v, 32);
+    }
+    char *d = c->io_dev, *d_yinv = d + sz_sh, *d_w = d_yinv + sz_q, *d_sk = d_w + sz_q, *d_ts = d_sk + sz_sk, *d_pr = d + sz_in, *d_stb = d_pr + sz_pr;
+    PX_HIPCHK(px, hipMemcpyAsync(d, h, sz_in, hipMemcpyHostToDevice, s));
+    PX_HIPCHK(px, hipMemsetAsync(d_pr, 0, sz_pr + sz_stb, s));
+    const size_t w_v = align_up(nsessions * nm * 32), w_gs = align_up(2 * nsessions * (2 * nm + 2) * 32);
+    rc = mpc_work_reserve(c, 4 * w_v + w_gs);
+    if (rc) return px.finish(rc);
+    uint32_t *avec = (uint32_t *)c->rpp_buf, *bvec = (uint32_t *)(c->rpp_buf + w_v), *Gf = (uint32_t *)(c->rpp_buf + 2 * w_v), *Hf = (uint32_t *)(c->rpp_buf + 3 * w_v),
+             *gsc = (uint32_t *)(c->rpp_buf + 4 * w_v);
+    do {
+        const uint32_t nt = (uint32_t)(nsessions * nm);
+        LAUNCH(c, s, "mpc_vectors", k_mpc_vectors, (nt + BP_BLOCK - 1) / BP_BLOCK, BP_BLOCK, nt, (uint32_t)n, (uint32_t)m, (const uint8_t *)d, (const uint32_t *)d_yinv,
+               (const uint8_t *)d_sk, avec, bvec, Gf, Hf);
+        ippc_fixed fx;
+        fx.gn = n;
+        fx.gm = m;
+        fx.w = (const uint32_t *)d_w;
+        fx.gen_scalars = gsc;
+        rc = ippc_core(c, s, nm, k, nsessions, avec, bvec, Gf, Hf, nullptr, nullptr, nullptr, 1, (uint32_t *)d_ts, (uint8_t *)d_pr + 224, proof_len, (uint8_t *)d_stb, &fx);
+    } while (0);
+    char *h_out = h + sz_in;
+    if (!rc && (hipMemcpyAsync(h_out, d_pr, sz_pr + sz_stb, hipMemcpyDeviceToHost, s) != hipSuccess ||
+                hipMemcpyAsync(h_ts, d_ts, nsessions * TS, hipMemcpyDeviceToHost, s) != hipSuccess))
+        rc = fail(c, BPGPU_ERR_HIP, "D2H copy failed");
+    rc = px.finish(rc);
+    if (rc) return rc;
+    for (size_t p = 0; p < nsessions; p++) {
+        uint8_t *pr = proofs_out + p * proof_len;
+        if (!skip[p] && h_out[sz_pr + p]) {   // (the inner-product rounds refused the session's vectors)
+            skip[p] = 1;
+            status[p] = (uint8_t)MPC_ST_BAD_SCALAR;
+        }
+        if (skip[p]) {
+            memset(pr, 0, proof_len);
+            continue;
+        }
+        memcpy(pr, sums.data() + p * 128, 128);
+        memcpy(pr + 128, fixed.data() + p * 96, 96);
+        memcpy(pr + 224, h_out + p * proof_len + 224, proof_len - 224);
+        memcpy(transcripts + p * TS, h_ts + p * TS, TS);
+    }
+    return BPGPU_OK;
+}
+
+extern "C" int bpgpu_mpc_dealer_assemble(bpgpu_ctx *c, size_t n, size_t m, size_t nsessions, const uint8_t *shares, const uint8_t *bit_commitments,
+                                         const uint8_t *poly_commitments, const uint8_t *challenges, uint8_t *transcripts, const uint8_t *initial_label,
+                                         size_t initial_label_len, const uint8_t *initial_transcripts, size_t initial_stride, const uint8_t *rng64, int trusted,
+                                         uint8_t *proofs_out, uint8_t *bad_shares, uint8_t *status) {
+    if (!c || (initial_label_len && !initial_label)) return BPGPU_ERR_INVALID_ARG;
+    if (nsessions == 0) return BPGPU_OK;
+    if (!shares || !bit_commitments || !poly_commitments || !challenges || !transcripts || !proofs_out || !bad_shares || !status) return BPGPU_ERR_INVALID_ARG;
+    if (initial_transcripts && initial_stride != 0 && initial_stride != BPGPU_TRANSCRIPT_BYTES)
+        return fail(c, BPGPU_ERR_INVALID_ARG, "initial_stride neither 0 nor BPGPU_TRANSCRIPT_BYTES");
+    const size_t TS = BPGPU_TRANSCRIPT_BYTES, share_len = 32 * (3 + 2 * n);
+    for (size_t p = 0; p < nsessions; p++)
+        if (!ts_state_ok(transcripts + p * TS)) return fail(c, BPGPU_ERR_INVALID_ARG, "malformed transcript state %zu", p);
+    size_t k = 0;
+    std::vector<uint8_t> skip(nsessions, 0);
+    memset(status, 0, nsessions);
+    memset(bad_shares, 0, nsessions * m);
+    {
+        std::lock_guard<std::mutex> lk(c->mu);
+        HIPCHK(c, hipSetDevice(c->device));
+        int rc = mpc_dealer_shape(c, n, m, &k);
+        if (rc) return rc;
+        for (size_t p = 0; p < nsessions; p++) {   // upstream the share fields are Scalars by type: a non-canonical one names its party
+            sc a, b, d;
+            if (!mpc_sum_shares((uint32_t)n, (uint32_t)m, shares + p * m * share_len, a, b, d, bad_shares + p * m)) {
+                skip[p] = 1;
+                status[p] = (uint8_t)MPC_ST_MALFORMED_SHARES;
+            }
+        }
+        rc = mpc_assemble_locked(c, n, m, k, nsessions, shares, bit_commitments, poly_commitments, challenges, transcripts, skip, status, proofs_out);
+        if (rc) return rc;
+    }
+    if (trusted) return BPGPU_OK;
+    // receive_shares_with_rng (dealer.rs:303-335): verify every assembled proof on the transcript Dealer::new cloned; audit the shares of the
+    // sessions that fail.  Both through the public entry points (each under the context's mutex).
+    const size_t proof_len = 32 * (9 + 2 * k);
+    std::vector<size_t> cand;
+    for (size_t p = 0; p < nsessions; p++)
+        if (!skip[p]) cand.push_back(p);
+    std::vector<size_t> blame;
+    for (size_t p = 0; p < nsessions; p++)
+        if (skip[p] && status[p] == MPC_ST_MALFORMED_SHARES) blame.push_back(p);
+    if (!cand.empty()) {
+        const size_t nc = cand.size();
+        std::vector<uint8_t> pr(nc * proof_len), cm(nc * m * 32), rg(rng64 ? nc * 64 : 0), ts(initial_transcripts && initial_stride ? nc * TS : 0), verdict(nc);
+        for (size_t q = 0; q < nc; q++) {
+            const size_t p = cand[q];
+            memcpy(pr.data() + q * proof_len, proofs_out + p * proof_len, proof_len);
+            for (size_t j = 0; j < m; j++) memcpy(cm.data() + (q * m + j) * 32, bit_commitments + (p * m + j) * 96, 32);
+            if (rng64) memcpy(rg.data() + q * 64, rng64 + p * 64, 64);
+            if (!ts.empty()) memcpy(ts.data() + q * TS, initial_transcripts + p * TS, TS);
+        }
+        int rc;
+        if (!initial_transcripts)
+            rc = bpgpu_rangeproof_verify_batch(c, n, m, nc, pr.data(), proof_len, cm.data(), initial_label, initial_label_len, rng64 ? rg.data() : nullptr, verdict.data(),
+                                               nullptr);
+        else
+            rc = bpgpu_rangeproof_verify_batch_ts(c, n, m, nc, pr.data(), proof_len, cm.data(), ts.empty() ? initial_transcripts : ts.data(), ts.empty() ? 0 : TS,
+                                                  rng64 ? rg.data() : nullptr, verdict.data(), nullptr, nullptr);
+        if (rc) return rc;
+        for (size_t q = 0; q < nc; q++)
+            if (verdict[q] != BPGPU_VERDICT_OK) blame.push_back(cand[q]);
+    }
+    if (!blame.empty()) {
+        const size_t nbl = blame.size(), nsh = nbl * m;
+        std::vector<uint32_t> pi(nsh);
+        std::vector<uint8_t> sh(nsh * share_len), bc(nsh * 96), pc(nsh * 64), ch(nsh * 96), verdict(nsh);
+        for (size_t q = 0; q < nbl; q++) {
+            const size_t p = blame[q];
+            memcpy(sh.data() + q * m * share_len, shares + p * m * share_len, m * share_len);
+            memcpy(bc.data() + q * m * 96, bit_commitments + p * m * 96, m * 96);
+            memcpy(pc.data() + q * m * 64, poly_commitments + p * m * 64, m * 64);
+            for (size_t j = 0; j < m; j++) {
+                pi[q * m + j] = (uint32_t)j;
+                memcpy(ch.data() + (q * m + j) * 96, challenges + p * 96, 96);
+            }
+        }
+        const int rc = bpgpu_rangeproof_audit_shares(c, n, nsh, pi.data(), sh.data(), bc.data(), pc.data(), ch.data(), 0, verdict.data(), nullptr);
+        if (rc) return rc;
+        for (size_t q = 0; q < nbl; q++) {
+            const size_t p = blame[q];
+            status[p] = (uint8_t)MPC_ST_MALFORMED_SHARES;   // MPCError::MalformedProofShares { bad_shares }
+            memset(proofs_out + p * proof_len, 0, proof_len);
+            for (size_t j = 0; j < m; j++) bad_shares[p * m + j] = verdict[q * m + j] != BPGPU_VERDICT_OK ? 1 : bad_shares[p * m + j];
+        }
+    }
+    return BPGPU_OK;
+}
+
+// ============================================================================
 // R1CS constraint-system proofs (r1cs.h): the circuit is a host object; its per-variable lists are uploaded to a device on
 // first use and kept there until bpgpu_r1cs_circuit_destroy
 // ============================================================================

@@ -20,6 +20,8 @@
 #include "r1cs.h"
 #include "r1cs_prover.h"
 #include "r1cs_rlc.h"
+#include "mpc_party.h"
+#include "mpc_dealer.h"
 
 #define BP_BLOCK 64   // one wavefront per workgroup: under contention a CU rarely has room for four waves of one group at once (256: -8% at 48 streams)
 #define FB_BLOCK 64
@@ -148,5 +150,14 @@ __global__ void k_linc_sterms(uint32_t n_q, uint32_t nthreads, linc_shape sh, co
 __global__ void k_linc_terms_fixed(uint32_t n_q, uint32_t nthreads, linc_shape sh, uint32_t j, const uint32_t *a, const uint32_t *b, const uint32_t *wG, const uint32_t *draws, uint32_t *gen_scalars);
 __global__ void k_linc_sterms_fixed(uint32_t n_q, uint32_t nthreads, linc_shape sh, const uint32_t *b, const uint32_t *wG, const uint32_t *draws, uint32_t *gen_scalars);
 __global__ void k_linc_final(linc_shape sh, const uint32_t *msm_out, const uint8_t *msm_status, uint32_t *ts, const uint32_t *a, const uint32_t *draws, const uint32_t *r, uint8_t *proofs, uint32_t proof_len, uint32_t *status, uint8_t *status_out);
+
+// k_mpc.hip
+__global__ void k_mpc_commit1(uint32_t n_b, uint32_t nthreads, uint32_t n, uint32_t nslots, const uint32_t *slot_pos, const uint64_t *values, const uint8_t *blindings, const uint8_t *rng, uint32_t *gsV, uint32_t *gsAS, uint32_t *st1);
+__global__ void k_mpc_poly(uint32_t n, uint32_t nslots, const uint32_t *slot_pos, const uint32_t *st1, const uint8_t *chal, uint32_t chal_shared, const uint8_t *rng, uint32_t *st2, uint32_t *gsT, uint32_t *status);
+__global__ void k_mpc_share(uint32_t nrows, uint32_t n, const uint32_t *st2, const uint8_t *xs, uint32_t x_shared, uint32_t *shares, uint8_t *status);
+__global__ void k_mpc_accum(fb_params prm, uint32_t nrows, uint32_t nslots, uint32_t nsplit, uint32_t npairs, const uint32_t *ids_tab, uint32_t ids_stride, const uint32_t *blk_pos, const uint32_t *slot_pos, const fb_digit *digits, const fb_entry *table, ge_ext *partial);
+__global__ void k_mpc_accum_ct(fb_params prm, uint32_t nrows, uint32_t nslots, uint32_t nsplit, uint32_t npairs, const uint32_t *ids_tab, uint32_t ids_stride, const uint32_t *blk_pos, const uint32_t *slot_pos, const fb_digit *digits, const fb_entry *table, ge_ext *partial);
+__global__ void k_mpc_ptsum(uint32_t nthreads, uint32_t m, uint32_t ncol, uint32_t rec, uint32_t off, const uint8_t *in, uint32_t *out, uint32_t *status);
+__global__ void k_mpc_vectors(uint32_t nthreads, uint32_t n, uint32_t m, const uint8_t *shares, const uint32_t *yinv, const uint8_t *skip, uint32_t *a_vec, uint32_t *b_vec, uint32_t *Gf, uint32_t *Hf);
 
 #endif

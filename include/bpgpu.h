@@ -574,6 +574,98 @@ int bpgpu_rangeproof_prove_batch(bpgpu_ctx *ctx, size_t n, size_t m, size_t nbat
                                  const uint8_t *shared_transcript, const uint8_t *rng,
                                  uint8_t *proofs_out, uint8_t *commitments_out, uint8_t *transcripts_out);
 
+/* ---- the multi-party aggregation protocol: parties and dealer ------------------------------------
+ * range_proof_mpc of the reference (src/range_proof/party.rs, dealer.rs, messages.rs; docs/aggregation-api.md) as six
+ * batched, STATELESS calls: host pointers in and out, nothing retained after return.  bpgpu_rangeproof_prove_batch above
+ * runs parties and dealer in-line for proofs whose secrets all sit in one process and never forms a message; these calls
+ * are the protocol itself, for a service that acts as the party for many clients, a dealer that aggregates many sessions,
+ * or values held by different owners.  What the reference keeps in its typestate structs travels as caller-held opaque
+ * blobs of bpgpu_mpc_state1_bytes(n) / bpgpu_mpc_state2_bytes(n) bytes per party; their layout is private to the library
+ * (csrc/mpc_party.h) and they hold the party's SECRETS: the caller zeroes them when done, as the reference zeroizes on
+ * Drop (party.rs:148-260).  Messages have the layouts bpgpu_rangeproof_audit_shares reads.
+ * Per-row status bytes: */
+#define BPGPU_MPC_OK 0
+#define BPGPU_MPC_MALICIOUS_DEALER 1 /* MPCError::MaliciousDealer: the poly challenge x is zero (party.rs:283-285) */
+#define BPGPU_MPC_MALFORMED_SHARES 2 /* MPCError::MalformedProofShares { bad_shares } (dealer.rs:303-335) */
+#define BPGPU_MPC_BAD_SCALAR 3       /* a challenge that is not a canonical scalar (upstream: Scalar by type) */
+#define BPGPU_MPC_BAD_POINT 4        /* an A_j, S_j, T_1_j or T_2_j that does not decode (upstream: RistrettoPoint by type) */
+/* Parameter errors are return codes: BPGPU_ERR_INVALID_ARG for InvalidBitsize (n not 8, 16, 32, 64), InvalidAggregation (m
+ * not a power of two), n m beyond the prover's limit or a blob that is no state of the step; BPGPU_ERR_NO_GENS for
+ * InvalidGeneratorsLength (n > gens_capacity, a position or m beyond party_capacity).
+ *
+ * PARTY SIDE.  Rows are independent parties of one bitsize n, each at its own position j: rows of many sessions with
+ * different m share a call.  Every commitment is a multiscalar multiplication over B~, B and PARTY j's share G_j(n), H_j(n)
+ * of the generator tables: 2n + 2 terms whatever j and party_capacity are; rows are grouped by position inside the call so
+ * that a wavefront walks one sub-table (csrc/mpc_party.h) and results come back in the caller's order.  Timing: as
+ * bpgpu_rangeproof_prove_batch -- variable time by default; with the context option "prover_constant_time" = 1 exactly
+ * V_j, A_j, S_j, T_1_j, T_2_j (party.rs:99-124, 224-227, the reference's constant-time multiscalar_mul) take the
+ * constant-time walk, byte-identical outputs.  Every call clears what it staged (prover_exit, see above).
+ *
+ * bpgpu_mpc_party_bit_commit: Party::new + PartyAwaitingPosition::assign_position_with_rng (party.rs:37-144).
+ *   party_index : nparties x uint32, the position j of each row (j >= party_capacity: BPGPU_ERR_NO_GENS)
+ *   values      : nparties x u64.  A value that does not fit n bits is ACCEPTED, as Party::new accepts it (only bits
+ *                 0..n are committed): the reference's dishonest-party scenario (mod.rs:726-799) and the dealer's check
+ *                 depend on that -- unlike bpgpu_rangeproof_prove_batch, which refuses such a value
+ *   blindings   : nparties x 32 bytes (Scalars, reduced mod l)
+ *   rng         : nparties x 64 (2n + 2) bytes in draw order a_blinding, s_blinding, s_L[0..n), s_R[0..n); NULL = OS CSPRNG
+ *   bit_commitments : nparties x 96 bytes: V_j, A_j, S_j (BitCommitment);  state1 : nparties x bpgpu_mpc_state1_bytes(n) */
+size_t bpgpu_mpc_state1_bytes(size_t n);
+size_t bpgpu_mpc_state2_bytes(size_t n);
+int bpgpu_mpc_party_bit_commit(bpgpu_ctx *ctx, size_t n, size_t nparties, const uint32_t *party_index, const uint64_t *values,
+                               const uint8_t *blindings, const uint8_t *rng, uint8_t *bit_commitments, uint8_t *state1);
+/* PartyAwaitingBitChallenge::apply_challenge_with_rng (party.rs:182-237).
+ *   bit_challenges : nparties x 64 bytes (y, z per row), or 64 bytes when challenges_shared != 0 (BitChallenge)
+ *   rng         : nparties x 128 bytes: t_1_blinding, t_2_blinding; NULL = OS CSPRNG
+ *   poly_commitments : nparties x 64 bytes: T_1_j, T_2_j (PolyCommitment);  state2 : nparties x bpgpu_mpc_state2_bytes(n)
+ *   status      : nparties bytes; a non-canonical y or z is BPGPU_MPC_BAD_SCALAR for that row (its outputs are zero) */
+int bpgpu_mpc_party_poly_commit(bpgpu_ctx *ctx, size_t n, size_t nparties, const uint8_t *state1, const uint8_t *bit_challenges,
+                                int challenges_shared, const uint8_t *rng, uint8_t *poly_commitments, uint8_t *state2,
+                                uint8_t *status);
+/* PartyAwaitingPolyChallenge::apply_challenge (party.rs:279-311).
+ *   poly_challenges : nparties x 32 bytes (x per row), or 32 bytes when challenges_shared != 0 (PolyChallenge)
+ *   shares      : nparties x 32 (3 + 2n) bytes: t_x, t_x_blinding, e_blinding, l_vec[n], r_vec[n] (ProofShare)
+ *   status      : x == 0 is BPGPU_MPC_MALICIOUS_DEALER, a non-canonical x BPGPU_MPC_BAD_SCALAR; that row's share is zero */
+int bpgpu_mpc_party_proof_share(bpgpu_ctx *ctx, size_t n, size_t nparties, const uint8_t *state2, const uint8_t *poly_challenges,
+                                int challenges_shared, uint8_t *shares, uint8_t *status);
+/* DEALER SIDE.  Rows are sessions of one shape (n, m); the messages of a session are its m parties' in position order.  The
+ * dealer's state is its transcript (one 208-byte state per session, carried by the caller) and the messages it has seen.
+ *
+ * bpgpu_mpc_dealer_bit_challenge: Dealer::new + DealerAwaitingBitCommitments::receive_bit_commitments (dealer.rs:37-137):
+ * rangeproof_domain_sep(n, m), every V_j appended AS GIVEN, A = sum A_j and S = sum S_j (decoded, added and compressed by
+ * a kernel of their own), appended; y and z drawn.
+ *   transcript  : transcripts == NULL: Transcript::new(label);  transcript_stride == 0: ONE 208-byte state shared by the
+ *                 sessions;  == BPGPU_TRANSCRIPT_BYTES: one state per session.  This is the INITIAL transcript (what
+ *                 Dealer::new clones for its final check): keep it for bpgpu_mpc_dealer_assemble
+ *   bit_challenges : nsessions x 64 bytes: y, z;  sums_out (optional) : nsessions x 64 bytes: compress(A), compress(S)
+ *   transcripts_out : nsessions x 208 bytes, the advanced transcripts
+ *   status      : an A_j or S_j that does not decode is BPGPU_MPC_BAD_POINT for that session (outputs zero, transcript
+ *                 as it came) */
+int bpgpu_mpc_dealer_bit_challenge(bpgpu_ctx *ctx, size_t n, size_t m, size_t nsessions, const uint8_t *bit_commitments,
+                                   const uint8_t *label, size_t label_len, const uint8_t *transcripts, size_t transcript_stride,
+                                   uint8_t *bit_challenges, uint8_t *sums_out, uint8_t *transcripts_out, uint8_t *status);
+/* DealerAwaitingPolyCommitments::receive_poly_commitments (dealer.rs:160-197): T_1 = sum T_1_j, T_2 = sum T_2_j appended, x drawn.
+ *   transcripts : nsessions x 208 bytes, advanced in place;  poly_challenges : nsessions x 32 bytes: x
+ *   sums_out (optional) : nsessions x 64 bytes: compress(T_1), compress(T_2) */
+int bpgpu_mpc_dealer_poly_challenge(bpgpu_ctx *ctx, size_t m, size_t nsessions, const uint8_t *poly_commitments, uint8_t *transcripts,
+                                    uint8_t *poly_challenges, uint8_t *sums_out, uint8_t *status);
+/* DealerAwaitingProofShares::assemble_shares with receive_shares_with_rng (trusted == 0) or receive_trusted_shares
+ * (trusted != 0) (dealer.rs:226-380): t_x, t_x_blinding, e_blinding summed and appended, w drawn, Q = w B, l_vec || r_vec in
+ * party order, H_factors y^-i, the inner-product argument over G(n, m), H(n, m) (bpgpu_ipp_create_batch's rounds; variable
+ * time, as upstream), the proof in RangeProof::to_bytes order.  Unless trusted, every assembled proof is verified with the
+ * batched verifier on the INITIAL transcript and rng64, and the shares of the sessions that fail go through
+ * bpgpu_rangeproof_audit_shares.
+ *   challenges  : nsessions x 96 bytes: y, z, x;  transcripts : nsessions x 208 bytes as bpgpu_mpc_dealer_poly_challenge
+ *                 left them, advanced in place to where the reference's dealer leaves its transcript
+ *   initial_*   : the transcript convention of bpgpu_mpc_dealer_bit_challenge;  rng64 : nsessions x 64 bytes or NULL
+ *   proofs_out  : nsessions x 32 (9 + 2 lg(n m)) bytes;  bad_shares : nsessions x m bytes, 1 = that party is named
+ *   status      : BPGPU_MPC_MALFORMED_SHARES: the proof did not verify, or (also when trusted) a share scalar is not
+ *                 canonical; proof bytes zero, bad_shares names the parties.  Other sessions of the call are unaffected. */
+int bpgpu_mpc_dealer_assemble(bpgpu_ctx *ctx, size_t n, size_t m, size_t nsessions, const uint8_t *shares, const uint8_t *bit_commitments,
+                              const uint8_t *poly_commitments, const uint8_t *challenges, uint8_t *transcripts,
+                              const uint8_t *initial_label, size_t initial_label_len, const uint8_t *initial_transcripts,
+                              size_t initial_stride, const uint8_t *rng64, int trusted, uint8_t *proofs_out, uint8_t *bad_shares,
+                              uint8_t *status);
+
 /* InnerProductProof::from_bytes + InnerProductProof::verification_scalars (src/inner_product_proof.rs:198-253, 373-407) for
  * nbatch proofs: what the R1CS verifier calls (src/r1cs/verifier.rs:401-404) before it builds ITS multiscalar multiplication
  * (r1cs/verifier.rs:459-491, served by bpgpu_msm_batch_shared), and what InnerProductProof::verify uses at ipp.rs:283.
