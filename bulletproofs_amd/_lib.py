@@ -21,6 +21,7 @@ EXPORTS = [
     "bpgpu_msm_batch", "bpgpu_msm_batch_dev", "bpgpu_msm_batch_shared", "bpgpu_msm_batch_shared_dev",
     "bpgpu_rangeproof_verify_batch", "bpgpu_rangeproof_verify_batch_dev", "bpgpu_ipp_verify_batch",
     "bpgpu_rangeproof_verify_rlc", "bpgpu_rangeproof_verify_rlc_dev",
+    "bpgpu_rangeproof_verify_rlc_mixed", "bpgpu_pool_rangeproof_verify_rlc_mixed",
     "bpgpu_profile_enable", "bpgpu_profile_reset", "bpgpu_profile_report",
     "bpgpu_transcript_new", "bpgpu_transcript_append_message", "bpgpu_transcript_challenge_bytes",
     "bpgpu_rangeproof_verify_batch_ts", "bpgpu_rangeproof_verify_batch_ts_dev", "bpgpu_ipp_verify_batch_dev",
@@ -86,6 +87,9 @@ def lib():
     L.bpgpu_rangeproof_verify_batch_dev.argtypes = [vp, sz, sz, sz, vp, sz, vp, u8p, sz, vp, vp, vp, vp]
     L.bpgpu_rangeproof_verify_rlc.argtypes = [vp, sz, sz, sz, u8p, sz, u8p, u8p, sz, u8p, u8p, u8p, u8p]
     L.bpgpu_rangeproof_verify_rlc_dev.argtypes = [vp, sz, sz, sz, vp, sz, vp, u8p, sz, vp, vp, vp, vp, vp]
+    szp = C.POINTER(sz)
+    L.bpgpu_rangeproof_verify_rlc_mixed.argtypes = [vp, sz, szp, szp, szp, szp, u8p, u8p, C.POINTER(u8p), szp, u8p, u8p, u8p, u8p]
+    L.bpgpu_pool_rangeproof_verify_rlc_mixed.argtypes = L.bpgpu_rangeproof_verify_rlc_mixed.argtypes
     L.bpgpu_ipp_verify_batch.argtypes = [vp, sz, sz, u8p, sz, u8p, sz, u8p, u8p, u8p, u8p, u8p, u8p, u8p, u8p]
     L.bpgpu_transcript_new.argtypes = [u8p, sz, u8p]
     L.bpgpu_transcript_append_message.argtypes = [u8p, u8p, sz, u8p, sz]
@@ -176,6 +180,28 @@ def transcript_challenge_bytes(state, label, n):
 
 
 ERR_NAMES = {0: "OK", -1: "INVALID_ARG", -2: "HIP", -3: "NO_GENS", -4: "NO_DEVICE", -5: "BAD_GENERATOR", -6: "HW_QUEUES"}
+
+
+def _rlc_mixed_call(fn, handle, groups, rng64, weights64):
+    """bpgpu_[pool_]rangeproof_verify_rlc_mixed: groups = [(n, m, proofs, proof_len, commitments, label)]"""
+    ng = len(groups)
+    sz = C.c_size_t
+    nbs = []
+    for n, m, proofs, proof_len, commitments, label in groups:
+        nb = len(proofs) // proof_len if proof_len else 0
+        assert len(proofs) == nb * proof_len and len(commitments) == 32 * m * nb
+        nbs.append(nb)
+    total = sum(nbs)
+    assert rng64 is None or len(rng64) == 64 * total
+    assert weights64 is None or len(weights64) == 64 * total
+    arr = lambda vals: (sz * max(ng, 1))(*vals)
+    labels = (C.c_char_p * max(ng, 1))(*[bytes(g[5]) for g in groups])
+    verdict = C.create_string_buffer(max(total, 1))
+    bo = C.create_string_buffer(33)
+    rc = fn(handle, ng, arr([g[0] for g in groups]), arr([g[1] for g in groups]), arr(nbs), arr([g[3] for g in groups]),
+            b"".join(bytes(g[2]) for g in groups), b"".join(bytes(g[4]) for g in groups), labels, arr([len(g[5]) for g in groups]),
+            rng64, weights64, verdict, bo)
+    return rc, verdict.raw[:total], bo.raw[0] == 0, bo.raw[1:33]
 
 
 class Context:
@@ -318,6 +344,14 @@ class Context:
         self._chk(self._L.bpgpu_rangeproof_verify_rlc(self.h, n, m, nb, proofs, proof_len, commitments, label, len(label),
                                                       rng64, weights64, verdict, bo))
         return verdict.raw[:nb], bo.raw[0] == 0, bo.raw[1:33]
+
+    def rangeproof_verify_rlc_mixed(self, groups, rng64=None, weights64=None):
+        """Batch-combined verification of proofs of mixed shapes in ONE check (bpgpu_rangeproof_verify_rlc_mixed): groups is a list of
+        (n, m, proofs, proof_len, commitments, label); rng64 / weights64: 64 bytes per proof in call order.  Returns (verdict bytes in
+        call order, batch_ok, 32-byte encoding of the combined point), as rangeproof_verify_rlc."""
+        rc, verdict, ok, enc = _rlc_mixed_call(self._L.bpgpu_rangeproof_verify_rlc_mixed, self.h, groups, rng64, weights64)
+        self._chk(rc)
+        return verdict, ok, enc
 
     # ---- stand-alone inner-product proofs ----
     def ipp_verify_batch(self, n, proofs, proof_len, label, Gf, Hf, P, Q, G, H, want_msm=False):
@@ -636,6 +670,12 @@ class Pool:
         msm = C.create_string_buffer(32 * max(nb, 1)) if want_msm else None
         self._chk(self._L.bpgpu_pool_rangeproof_verify(self.h, n, m, nb, proofs, proof_len, commitments, label, len(label), rng64, verdict, msm))
         return (verdict.raw[:nb], msm.raw[:32 * nb]) if want_msm else verdict.raw[:nb]
+
+    def rangeproof_verify_rlc_mixed(self, groups, rng64=None, weights64=None):
+        """Context.rangeproof_verify_rlc_mixed through the pool (bpgpu_pool_rangeproof_verify_rlc_mixed): the whole call on the next device"""
+        rc, verdict, ok, enc = _rlc_mixed_call(self._L.bpgpu_pool_rangeproof_verify_rlc_mixed, self.h, groups, rng64, weights64)
+        self._chk(rc)
+        return verdict, ok, enc
 
     def rangeproof_verify_ts(self, n, m, proofs, proof_len, commitments, transcripts, rng64=None, want_msm=False, want_transcripts=True):
         """The reference's call shape (bpgpu_pool_rangeproof_verify_ts): blocking, any number of threads at once; `transcripts`

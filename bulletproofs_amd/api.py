@@ -259,6 +259,40 @@ class RangeProof:
                                                     weights64)
         return [None if x == 0 else _BY_CODE[x]() for x in v]
 
+    @staticmethod
+    def verify_mixed_combined(bp_gens, pc_gens, items, rng64=None, weights64=None):
+        """Proofs of mixed shapes through ONE batch-combined check (bpgpu_rangeproof_verify_rlc_mixed; no counterpart in the crate).
+        items: [(transcript, proof, commitments, n)] in any order, every transcript a fresh Transcript(label) as for
+        verify_batch_combined; they are grouped by (n, m, proof length, label).  rng64 / weights64: 64 bytes per item, in the order
+        of `items` (each row follows its item through the regrouping).  Returns None / ProofError per item, in the caller's order."""
+        if not items:
+            return []
+        bp_gens._check_pedersen(pc_gens)
+        ni = len(items)
+        if rng64 is not None and len(rng64) != 64 * ni:
+            raise ValueError("rng64 must hold 64 bytes per item")
+        if weights64 is not None and len(weights64) != 64 * ni:
+            raise ValueError("weights64 must hold 64 bytes per item")
+        groups, order = {}, []
+        for i, (transcript, proof, commitments, n) in enumerate(items):
+            label = transcript.fresh_label
+            if label is None:
+                raise ValueError("verify_mixed_combined needs a fresh Transcript(label) per item; pre-bound transcripts go through verify_batch")
+            raw = proof.to_bytes() if isinstance(proof, RangeProof) else bytes(proof)
+            key = (n, len(commitments), len(raw), bytes(label))
+            if key not in groups:
+                groups[key] = []
+                order.append(key)
+            groups[key].append((i, raw, b"".join(commitments)))
+        index = [i for key in order for i, _, _ in groups[key]]   # call position -> item
+        call = [(key[0], key[1], b"".join(r for _, r, _ in groups[key]), key[2], b"".join(c for _, _, c in groups[key]), key[3]) for key in order]
+        rows = lambda buf: None if buf is None else b"".join(buf[64 * i:64 * i + 64] for i in index)
+        v, _, _ = bp_gens.ctx.rangeproof_verify_rlc_mixed(call, rows(rng64), rows(weights64))
+        out = [None] * ni
+        for pos, i in enumerate(index):
+            out[i] = None if v[pos] == 0 else _BY_CODE[v[pos]]()
+        return out
+
 
 class LinearProof:
     """src/linear_proof.rs (`pub use` lib.rs:36): the proof that <a, b> = c for a committed secret vector a and a public

@@ -5231,3 +5231,256 @@ extern "C" int bpgpu_pool_r1cs_verify_rlc(bpgpu_pool *pool, size_t ngroups, cons
                     verdict, batch_out, transcripts_out};
     return bpgpu_internal_pool_run_on_context(pool, total, verdict, r1cs_rlc_call_run, &a);
 }
+
+// ============================================================================
+// batch-combined range-proof verification over MIXED shapes (rlc_mix.h; an ADDITIONAL entry point, as bpgpu_rangeproof_verify_rlc)
+// ============================================================================
+namespace {
+// one group's inputs on the device; its proof i is proof gp0 + i of the call, its unique terms start at u0 of the combined list
+struct rp_mix_group {
+    size_t n, m, nbatch, proof_len, k, gp0, u0;
+    const char *d_proofs, *d_coms;
+    const uint8_t *label;
+    size_t label_len;
+    bool whole;   // rejected as a whole: every proof gets the code of the per-shape path, the group contributes nothing
+};
+}  // namespace
+
+// The checks rp_verify_dev_locked makes before its first launch -- the length-only part of from_bytes (mod.rs:505-510, ipp.rs:374-388),
+// then the parameter checks of verify_multiple_with_rng (mod.rs:358-366, ipp.rs:209): 0 = a shape the combination takes (k set),
+// 1 = the per-shape path gives every proof of the group one code
+static int rp_mix_classify(bpgpu_ctx *c, size_t n, size_t m, size_t proof_len, size_t *k_out, bool *whole) {
+    *whole = true;
+    *k_out = 0;
+    if (proof_len % 32 != 0 || proof_len < 9 * 32 || (proof_len - 9 * 32) % 64 != 0) return BPGPU_OK;
+    const size_t k = (proof_len - 9 * 32) / 64;
+    if (k >= 32) return BPGPU_OK;
+    if (!(n == 8 || n == 16 || n == 32 || n == 64) || c->gens_capacity < n || c->party_capacity < m) return BPGPU_OK;
+    if (m == 0 || n * m != ((size_t)1 << k)) return BPGPU_OK;
+    if (k > BP_RP_MAX_K) return fail(c, BPGPU_ERR_INVALID_ARG, "n*m > 2^%d not supported", BP_RP_MAX_K);
+    *k_out = k;
+    *whole = false;
+    return BPGPU_OK;
+}
+
+// R = sum_i rho_i MegaCheck_i over every group: per group launch 1 (k_rlc_mix_front) and the weigh launch, then the reduction of the
+// limb sums, ONE shared-generator MSM over (N, M) = (max n, max m) and the verdicts (undecided where R is not the identity).
+// d_rng64 / d_weights64: total x 64 bytes in call order, or null -- then drawn here, keyed by the call-global index; *d_rng_used is the
+// buffer the batching challenges came from (for the per-proof fallback).
+static int rp_mix_dev_locked(bpgpu_ctx *c, std::vector<rp_mix_group> &gr, size_t total, const char *d_rng64, const char *d_weights64, uint8_t *d_verdict,
+                             uint8_t *d_batch, hipStream_t s, const char **d_rng_used) {
+    if (!c->d_table) return fail(c, BPGPU_ERR_NO_GENS, "generators not loaded");
+    size_t N = 0, M = 0, u_total = 0;
+    for (auto &g : gr) {
+        if (g.whole || g.nbatch == 0) continue;
+        N = std::max(N, g.n), M = std::max(M, g.m);
+        g.u0 = u_total;
+        u_total += g.nbatch * (4 + 2 * g.k + g.m);
+    }
+    if (u_total > RM_MAX_TERMS) return fail(c, BPGPU_ERR_INVALID_ARG, "more than 2^24 proof-specific terms in one call");
+    const size_t nrows = N ? 2 * N * M + 2 : 0;
+    const size_t sz_l = align_up(std::max<size_t>(u_total, 1) * 32), sz_acc = align_up(nrows * 80 + 16), sz_g = align_up(nrows * 32 + 16), sz_st = align_up(total * 4),
+                 sz_res = align_up(64), sz_r = d_rng64 ? 0 : align_up(total * 64), sz_w = d_weights64 ? 0 : align_up(total * 64);
+    int rc = r1rlc_reserve(c, 2 * sz_l + sz_acc + sz_g + sz_st + sz_res + sz_r + sz_w);   // (the combined checks share their buffer)
+    if (rc) return rc;
+    char *d_csc = c->r1rlc_buf, *d_cpt = d_csc + sz_l, *d_acc = d_cpt + sz_l, *d_gen = d_acc + sz_acc, *d_gst = d_gen + sz_g, *d_res = d_gst + sz_st,
+         *d_rdraw = d_res + sz_res, *d_wdraw = d_rdraw + sz_r;
+    const uint32_t n32 = (uint32_t)total;
+    if (!d_rng64) {   // as the per-proof path's seeded mode (the tests' chain seed pins it), but per call and under this entry point's domain
+        rm_key key;
+        if (c->test_seed_set) memcpy(key.w, c->test_seed, 32);
+        else if (!bp::fast_random((uint8_t *)key.w, 32)) return fail(c, BPGPU_ERR_HIP, "getrandom failed");
+        LAUNCH(c, s, "rlc_mix_draw", k_rlc_mix_draw, (n32 + 63) / 64, 64, n32, key, (uint32_t)RM_RNG_DOMAIN, (uint32_t *)d_rdraw);
+        d_rng64 = d_rdraw;
+    }
+    if (!d_weights64) {   // (never the test seed: weights stay unpredictable)
+        rm_key key;
+        if (!bp::fast_random((uint8_t *)key.w, 32)) return fail(c, BPGPU_ERR_HIP, "getrandom failed");
+        LAUNCH(c, s, "rlc_mix_draw", k_rlc_mix_draw, (n32 + 63) / 64, 64, n32, key, (uint32_t)RM_WEIGHT_DOMAIN, (uint32_t *)d_wdraw);
+        d_weights64 = d_wdraw;
+    }
+    *d_rng_used = d_rng64;
+    // groups rejected as a whole: the per-shape path's own codes, written now; the verdict launch leaves them alone
+    for (const auto &g : gr) {
+        if (!g.whole || g.nbatch == 0) continue;
+        rp_transcripts tr;
+        tr.label = g.label;
+        tr.label_len = g.label_len;
+        rc = rp_verify_dev_locked(c, g.n, g.m, g.nbatch, g.d_proofs, g.proof_len, g.d_coms, tr, d_rng64 + 64 * g.gp0, d_verdict + g.gp0, nullptr, s);
+        if (rc) return rc;
+        HIPCHK(c, hipMemsetAsync(d_gst + 4 * g.gp0, 0xff, 4 * g.nbatch, s));
+    }
+    if (nrows) HIPCHK(c, hipMemsetAsync(d_acc, 0, nrows * 80, s));
+    for (const auto &g : gr) {
+        if (g.whole || g.nbatch == 0) continue;
+        rp_shape sh;
+        sh.n = (uint32_t)g.n, sh.m = (uint32_t)g.m, sh.nm = (uint32_t)(g.n * g.m), sh.k = (uint32_t)g.k, sh.U = (uint32_t)(4 + 2 * g.k + g.m);
+        sh.proof_len = (uint32_t)g.proof_len, sh.nproofs = (uint32_t)g.nbatch, sh.shape_verdict = 0;
+        uint32_t lg_m = 0;
+        while (((size_t)1 << lg_m) < g.m) lg_m++;
+        rm_group mg;
+        mg.nproofs = sh.nproofs, mg.nstride = (sh.nproofs + 63) / 64 * 64, mg.n = sh.n, mg.m = sh.m, mg.N = (uint32_t)N, mg.M = (uint32_t)M;
+        mg.gp0 = (uint32_t)g.gp0, mg.u0 = (uint32_t)g.u0;
+        const uint64_t nt = (uint64_t)mg.nstride * rm_terms(sh);   // (a multiple of 64: whole wavefronts)
+        if (nt > 0x7fffffffull) return fail(c, BPGPU_ERR_INVALID_ARG, "batch too large for this shape");
+        const rp_fields fl = rp_field_layout(sh.k, sh.m);
+        arena_plan ap;
+        const size_t off_fields = ap.add((size_t)fl.count * g.nbatch * BP_RP_REC * 4 + 16), off_st = ap.add(g.nbatch * 4),
+                     off_usc = ap.add(g.nbatch * sh.U * 32);
+        rc = arena_reserve(c, ap.total);
+        if (rc) return rc;
+        char *a = c->arena;
+        rp_strobe_init init;
+        make_strobe_init(init, g.label, g.label_len, g.n, g.m);
+        const rp_script_hdr *d_script = nullptr;   // (every proof of a group starts from its label's state: always the per-shape script)
+        rc = script_for(c, s, sh.n, sh.m, sh.k, init, false, &d_script);
+        if (rc) return rc;
+        HIPCHK(c, hipMemsetAsync(a + off_st, 0, g.nbatch * 4, s));
+        const uint32_t n_tr = (sh.nproofs + RP_BLOCK - 1) / RP_BLOCK, n_pt = (sh.nproofs * sh.U + RP_BLOCK - 1) / RP_BLOCK;
+        // rng64 / weights64 rows are indexed by the proof's position in the CALL: this group's slice starts at gp0.  Soundness rests on it --
+        // a slice taken at 0 would hand (group 0, proof i) and (group 1, proof i) the same weight
+        LAUNCH(c, s, "rlc_mix_front", k_rlc_mix_front, n_tr + n_pt, RP_BLOCK, sh, init, n_tr, (const uint8_t *)g.d_proofs, (const uint8_t *)g.d_coms,
+               (const uint8_t *)d_rng64 + 64 * g.gp0, (const uint8_t *)d_weights64 + 64 * g.gp0, (uint32_t *)(a + off_fields), (uint32_t *)(a + off_st), c->prm,
+               lg_m, (uint32_t *)(a + off_usc), d_script);
+        LAUNCH(c, s, "rlc_mix_weigh", k_rlc_mix_weigh, (uint32_t)(nt / 64), 64, mg, sh, c->prm, (const uint8_t *)g.d_proofs, (const uint8_t *)g.d_coms,
+               (const uint32_t *)(a + off_st), (const uint32_t *)(a + off_fields), (const uint32_t *)(a + off_usc), (uint32_t *)d_csc, (uint32_t *)d_cpt,
+               (uint32_t *)d_gst, (unsigned long long *)d_acc);
+    }
+    HIPCHK(c, hipMemsetAsync(d_res, 0, 64, s));   // (no group left: R is the identity)
+    if (u_total) {
+        LAUNCH(c, s, "rlc_mix_reduce", k_r1cs_rlc_reduce, (uint32_t)((nrows + 63) / 64), 64, (uint32_t)nrows, (const unsigned long long *)d_acc, (uint32_t *)d_gen);
+        rc = msm_shared_dev_locked(c, N, M, 1, u_total, d_gen, d_csc, d_cpt, d_res, d_res + 32, nullptr, s);
+        if (rc) return rc;
+    }
+    LAUNCH(c, s, "rlc_mix_verdict", k_rlc_mix_verdict, (n32 + 63) / 64, 64, n32, (const uint32_t *)d_gst, (const uint32_t *)d_res, (const uint8_t *)(d_res + 32),
+           d_verdict, d_batch);
+    HIPCHK(c, hipGetLastError());
+    return BPGPU_OK;
+}
+
+extern "C" int bpgpu_rangeproof_verify_rlc_mixed(bpgpu_ctx *c, size_t ngroups, const size_t *n, const size_t *m, const size_t *nbatch, const size_t *proof_len,
+                                                 const uint8_t *proofs, const uint8_t *commitments, const uint8_t *const *labels, const size_t *label_lens,
+                                                 const uint8_t *rng64, const uint8_t *weights64, uint8_t *verdict, uint8_t *batch_out) {
+    if (!c || (ngroups && (!n || !m || !nbatch || !proof_len || !labels || !label_lens))) return BPGPU_ERR_INVALID_ARG;
+    size_t total = 0, bytes_p = 0, bytes_c = 0;
+    for (size_t g = 0; g < ngroups; g++) {
+        if (label_lens[g] && !labels[g]) return BPGPU_ERR_INVALID_ARG;
+        if (nbatch[g] > RM_MAX_TERMS || proof_len[g] > 0xffffffu || m[g] > 0xffffu) return fail(c, BPGPU_ERR_INVALID_ARG, "batch too large");
+        total += nbatch[g];
+        bytes_p += nbatch[g] * proof_len[g];
+        bytes_c += nbatch[g] * m[g] * 32;
+    }
+    if (total == 0) {
+        if (batch_out) memset(batch_out, 0, 33);
+        return BPGPU_OK;
+    }
+    if (!verdict || (bytes_p && !proofs) || (bytes_c && !commitments)) return BPGPU_ERR_INVALID_ARG;
+    if (total > RM_MAX_TERMS) return fail(c, BPGPU_ERR_INVALID_ARG, "batch too large");
+    std::lock_guard<std::mutex> lk(c->mu);
+    std::vector<rp_mix_group> gr;
+    for (size_t g = 0, gp = 0; g < ngroups; g++) {   // (every refusal before the context is entered)
+        if (nbatch[g] == 0) continue;
+        rp_mix_group mg{n[g], m[g], nbatch[g], proof_len[g], 0, gp, 0, nullptr, nullptr, labels[g], label_lens[g], false};
+        const int rcc = rp_mix_classify(c, n[g], m[g], proof_len[g], &mg.k, &mg.whole);
+        if (rcc) return rcc;
+        gr.push_back(mg);
+        gp += nbatch[g];
+    }
+    HIPCHK(c, hipSetDevice(c->device));
+    // staging: per group its proofs and commitments; then every proof's rng bytes and weights; then the outputs
+    std::vector<size_t> off(2 * ngroups, 0);
+    size_t in = 0;
+    for (size_t g = 0; g < ngroups; g++) {
+        off[2 * g] = in, in += nbatch[g] ? align_up(nbatch[g] * proof_len[g] + 64) : 0;
+        off[2 * g + 1] = in, in += nbatch[g] ? align_up(nbatch[g] * m[g] * 32 + 64) : 0;
+    }
+    const size_t off_r = in, off_w = off_r + (rng64 ? align_up(total * 64) : 0), sz_in = off_w + (weights64 ? align_up(total * 64) : 0);
+    const size_t sz_v = align_up(total), sz_b = align_up(64), sz_out = sz_v + sz_b;
+    hipStream_t s = c->stream;
+    int rc = ctx_enter(c, s);
+    if (rc) return rc;
+    rc = io_reserve(c, sz_in + sz_out);
+    if (rc) return rc;
+    char *h = nullptr;
+    rc = pin_alloc(c, s, sz_in + sz_out, &h);
+    if (rc) return rc;
+    char *d = c->io_dev;
+    const uint8_t *src_p = proofs, *src_c = commitments;
+    for (size_t g = 0, gi = 0; g < ngroups; g++) {
+        const size_t nb = nbatch[g];
+        if (nb == 0) continue;
+        memcpy(h + off[2 * g], src_p, nb * proof_len[g]);
+        if (m[g]) memcpy(h + off[2 * g + 1], src_c, nb * m[g] * 32);
+        src_p += nb * proof_len[g];
+        src_c += nb * m[g] * 32;
+        gr[gi].d_proofs = d + off[2 * g];
+        gr[gi].d_coms = d + off[2 * g + 1];
+        gi++;
+    }
+    if (rng64) memcpy(h + off_r, rng64, total * 64);
+    if (weights64) memcpy(h + off_w, weights64, total * 64);
+    HIPCHK(c, hipMemcpyAsync(d, h, sz_in, hipMemcpyHostToDevice, s));
+    char *d_v = d + sz_in, *d_b = d_v + sz_v;
+    char *h_out = h + sz_in;
+    const char *d_rng_used = nullptr;
+    rc = rp_mix_dev_locked(c, gr, total, rng64 ? d + off_r : nullptr, weights64 ? d + off_w : nullptr, (uint8_t *)d_v, (uint8_t *)d_b, s, &d_rng_used);
+    if (!rc && hipMemcpyAsync(h_out, d_v, sz_out, hipMemcpyDeviceToHost, s) != hipSuccess) rc = fail(c, BPGPU_ERR_HIP, "D2H copy failed");
+    int rc2 = ctx_leave(c, s), rc3 = host_wait(c, s);
+    if (rc || rc2 || rc3) return rc ? rc : (rc2 ? rc2 : rc3);
+    if ((uint8_t)h_out[sz_v] != 0) {
+        // R is not the identity, or did not decode: every group the combination took again through the per-proof chain of its shape, with
+        // the same rng bytes (inputs, and rng bytes drawn above, are still on the device)
+        uint8_t bo[33];
+        memcpy(bo, h_out + sz_v, 33);
+        rc = ctx_enter(c, s, true);
+        if (rc) return rc;
+        for (const auto &g : gr) {
+            if (g.whole) continue;
+            rp_transcripts tr;
+            tr.label = g.label;
+            tr.label_len = g.label_len;
+            rc = rp_verify_dev_locked(c, g.n, g.m, g.nbatch, g.d_proofs, g.proof_len, g.d_coms, tr, d_rng_used + 64 * g.gp0, d_v + g.gp0, nullptr, s);
+            if (rc) break;
+        }
+        if (!rc && hipMemcpyAsync(h_out, d_v, sz_v, hipMemcpyDeviceToHost, s) != hipSuccess) rc = fail(c, BPGPU_ERR_HIP, "D2H copy failed");
+        rc2 = ctx_leave(c, s);
+        rc3 = host_wait(c, s);
+        if (rc || rc2 || rc3) return rc ? rc : (rc2 ? rc2 : rc3);
+        memcpy(h_out + sz_v, bo, 33);
+    }
+    memcpy(verdict, h_out, total);
+    if (batch_out) memcpy(batch_out, h_out + sz_v, 33);
+    return BPGPU_OK;
+}
+
+namespace {
+struct rp_mix_call {
+    size_t ngroups;
+    const size_t *n, *m, *nbatch, *proof_len;
+    const uint8_t *proofs, *commitments;
+    const uint8_t *const *labels;
+    const size_t *label_lens;
+    const uint8_t *rng64, *weights64;
+    uint8_t *verdict, *batch_out;
+};
+int rp_mix_call_run(bpgpu_ctx *c, void *arg) {
+    const rp_mix_call *a = (const rp_mix_call *)arg;
+    return bpgpu_rangeproof_verify_rlc_mixed(c, a->ngroups, a->n, a->m, a->nbatch, a->proof_len, a->proofs, a->commitments, a->labels, a->label_lens, a->rng64,
+                                             a->weights64, a->verdict, a->batch_out);
+}
+}  // namespace
+
+extern "C" int bpgpu_pool_rangeproof_verify_rlc_mixed(bpgpu_pool *pool, size_t ngroups, const size_t *n, const size_t *m, const size_t *nbatch,
+                                                      const size_t *proof_len, const uint8_t *proofs, const uint8_t *commitments, const uint8_t *const *labels,
+                                                      const size_t *label_lens, const uint8_t *rng64, const uint8_t *weights64, uint8_t *verdict,
+                                                      uint8_t *batch_out) {
+    if (!pool || (ngroups && (!n || !m || !nbatch || !proof_len || !labels || !label_lens))) return BPGPU_ERR_INVALID_ARG;
+    size_t total = 0;
+    for (size_t g = 0; g < ngroups; g++) total += nbatch[g];
+    if (total == 0) {   // (as the context form: nothing to combine)
+        if (batch_out) memset(batch_out, 0, 33);
+        return BPGPU_OK;
+    }
+    rp_mix_call a{ngroups, n, m, nbatch, proof_len, proofs, commitments, labels, label_lens, rng64, weights64, verdict, batch_out};
+    return bpgpu_internal_pool_run_on_context(pool, total, verdict, rp_mix_call_run, &a);
+}

@@ -652,6 +652,9 @@ BP_HD const uint8_t *rp_unique_point_ptr(const rp_shape &sh, const rp_inputs &in
 // An undecodable point is the Option::None of optional_multiscalar_mul -> VerificationError (mod.rs:445).
 // pts (optional, instead of tab): bucket path (bucket.h) -- store the point as one affine Niels record instead.
 // (p = t / U; `in` = rp_resolve(p, ...))
+// STORE = false (the mixed-shape combination, rlc_mix.h): only the decode's verdict -- the point goes nowhere, the call's one MSM decodes
+// the encodings of the proofs that are left
+template <bool STORE = true>
 BP_HD void rp_points_thread(uint32_t t, rp_shape sh, const rp_inputs &in, ge_cached *tab, uint32_t *status, fb_entry *pts = nullptr) {
     const uint32_t p = t / sh.U, u = t - p * sh.U;
     uint32_t w[8];
@@ -660,6 +663,7 @@ BP_HD void rp_points_thread(uint32_t t, rp_shape sh, const rp_inputs &in, ge_cac
     // (the short-register decode of bucket2.h here: 117 -> 81 spilled registers in k_rp_stage1<true>, no difference in any bench form --
     // profiles/r06/stage1_short_register_decode_ab.txt; not kept)
     if (!ristretto_decompress(pt, w)) status_raise(status + p, BP_VERDICT_VERIFICATION);
+    if (!STORE) return;
     if (pts) bk_store_point(pts + t, pt);
     else if (sh.radix5) vb_build_table16(tab + 16 * (uint64_t)t, pt, sh.a_outside && u == 0);
     else if (sh.a_outside && u == 0) ge_to_cached(tab[8 * (uint64_t)t], pt);
@@ -727,6 +731,15 @@ BP_HD void rp_emit_coeff(uint32_t *us, uint32_t u, const sc28 &vm, const sc28 *r
     }
 }
 
+// the same coefficient as a plain canonical scalar (rp_expand_a_thread<true>)
+BP_HD void rp_emit_plain(uint32_t *us, uint32_t u, const sc28 &vm, const sc28 *rho_m) {
+    sc28 t = vm;
+    if (rho_m) sc28_montmul(t, vm, *rho_m);
+    sc s;
+    sc_from_mont28(s, t);
+    store_words8(us + u * 8, s);
+}
+
 // The scalar role of a NARROW chain has 31 idle lanes beside its leader: instead of recoding its U coefficients one after the other
 // (from Montgomery form, times the weight in batch-combination mode, into signed radix-16 digits: ~1.1 us each, U = 17 at (64, 1)) the leader
 // parks them in LDS and the lanes of its group recode one each.  slot[u] = coefficient u in Montgomery form, slot[RP_DEFER_CAP] = the
@@ -757,6 +770,9 @@ BP_HD void rp_emit_deferred(uint32_t lane32, uint32_t p, const rp_shape &sh, uin
 // skip (narrow chains, option coop_split; never with weights): RP_SKIP_INV -- the inversions, u_i^2, u_i^-2 and the y^-(2^b) table were
 // written by the group's lanes (rp_split_invert_lane); RP_SKIP_ROWS -- the B_blinding / B coefficients are formed in launch 3 (rp_rows_thread).
 enum { RP_SKIP_INV = 1, RP_SKIP_ROWS = 2 };
+// PLAIN (the mixed-shape combination, rlc_mix.h; always with a weight, never bk_c / df): `recoded` is a list of canonical scalars,
+// 8 words per coefficient -- the terms go to a multiscalar multiplication of their own instead of this chain's window sums
+template <bool PLAIN = false>
 BP_HD void rp_expand_a_thread(uint32_t p, rp_shape sh, fb_params prm, uint32_t lg_m, uint32_t *fields, uint32_t *recoded,
                               fb_digit *digits, const uint32_t *status, const uint8_t *rho64 = nullptr, uint32_t bk_c = 0, const rp_defer *df = nullptr,
                               uint32_t skip = 0) {
@@ -788,7 +804,8 @@ BP_HD void rp_expand_a_thread(uint32_t p, rp_shape sh, fb_params prm, uint32_t l
     }
 #define RP_EMIT(idx, val)                                                                 \
     do {                                                                                  \
-        if (df) df->slot[(idx)] = (val);                                                  \
+        if (PLAIN) rp_emit_plain(recoded + (uint64_t)p * sh.U * 8, (idx), (val), rho);    \
+        else if (df) df->slot[(idx)] = (val);                                             \
         else rp_emit_coeff(recoded + (uint64_t)p * sh.U * (bk_c ? BK_RWORDS : 8), (idx), (val), rho, bk_c, p * sh.U, sh.radix5 != 0);        \
     } while (0)
 

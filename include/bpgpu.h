@@ -284,6 +284,31 @@ int bpgpu_rangeproof_verify_rlc_dev(bpgpu_ctx *ctx, size_t n, size_t m, size_t n
                                     const uint8_t *label, size_t label_len, const void *d_rng64,
                                     const void *d_weights64, void *d_verdict, void *d_batch_out, void *stream);
 
+/* The same combination over proofs of MIXED shapes in ONE check (ADDITIONAL entry point; not a call of the reference): a block of
+ * aggregated proofs with m = 1, 2, 4, 8, 16 outputs and more than one bit size, group after group.  BulletproofGens::new(N, M)
+ * serves every n <= N, m <= M from the same points (generators.rs:157-259), so the generator coefficients of all groups add up on the
+ * rows of the call's (N, M) = (max n, max m) and the table walk runs once per call; the 4 + 2k + m proof-specific terms of every
+ * proof form one list for one MSM.
+ *   n, m, nbatch, proof_len : ngroups values each; nbatch[g] == 0 and ngroups == 0 are valid
+ *   proofs      : group after group, nbatch[g] x proof_len[g] bytes
+ *   commitments : group after group, nbatch[g] x m[g] x 32 bytes
+ *   labels, label_lens : one Merlin label per group (Transcript::new(label), as bpgpu_rangeproof_verify_batch)
+ *   rng64, weights64 : total x 64 bytes each, in call order (total = sum nbatch[g]); rho_i = from_bytes_mod_order_wide(weights64[i])
+ *                 with i the proof's index within the CALL.  NULL = drawn by the library, expanded on the device from a per-call key,
+ *                 block = the index within the call: no two proofs of a call share a weight, whichever groups they are in
+ *   verdict     : total bytes, call order; every proof's verdict is the one bpgpu_rangeproof_verify_batch gives it in a call of its
+ *                 own shape with the same rng64 bytes.  Proofs rejected by the parser / point decoder keep their BPGPU_VERDICT_* code
+ *                 and are left out of R.  A group the per-shape call rejects as a whole (malformed proof_len, n not 8 / 16 / 32 / 64,
+ *                 n > gens_capacity or m > party_capacity, n m != 2^k) gets that call's codes, contributes nothing and does not disturb
+ *                 the others.  When R is not the identity (or does not decode) the call re-verifies group by group on the per-proof
+ *                 path with the same rng64 and returns exactly its verdicts.
+ *   batch_out   : optional 33 bytes, as bpgpu_rangeproof_verify_rlc: compress(R) as computed before any fallback
+ * One call takes at most 2^24 proofs and 2^24 proof-specific terms. */
+int bpgpu_rangeproof_verify_rlc_mixed(bpgpu_ctx *ctx, size_t ngroups, const size_t *n, const size_t *m, const size_t *nbatch,
+                                      const size_t *proof_len, const uint8_t *proofs, const uint8_t *commitments,
+                                      const uint8_t *const *labels, const size_t *label_lens, const uint8_t *rng64,
+                                      const uint8_t *weights64, uint8_t *verdict, uint8_t *batch_out);
+
 /* ---- stand-alone inner-product proofs -------------------------------------------
  * nbatch independent calls of
  *   InnerProductProof::from_bytes(proof)?.verify(n, &mut Transcript::new(label), G_factors, H_factors, &P, &Q, &G, &H)
@@ -847,6 +872,12 @@ int bpgpu_pool_r1cs_verify_rlc(bpgpu_pool *pool, size_t ngroups, const bpgpu_r1c
                                const uint8_t *const *commitments, const uint8_t *const *transcripts, const size_t *transcript_stride,
                                const uint8_t *rng32, const uint8_t *weights64,
                                uint8_t *verdict, uint8_t *batch_out, uint8_t *transcripts_out);
+/* bpgpu_rangeproof_verify_rlc_mixed through the pool (same arguments): the whole call runs on the next device, blocking; any thread
+ * may call it. */
+int bpgpu_pool_rangeproof_verify_rlc_mixed(bpgpu_pool *pool, size_t ngroups, const size_t *n, const size_t *m, const size_t *nbatch,
+                                           const size_t *proof_len, const uint8_t *proofs, const uint8_t *commitments,
+                                           const uint8_t *const *labels, const size_t *label_lens, const uint8_t *rng64,
+                                           const uint8_t *weights64, uint8_t *verdict, uint8_t *batch_out);
 /* The combining queue's timeline (set option "combine_trace" = ring size first): one JSON object per line -- every launch chain (opened,
  * sealed, issue begin / end, completion seen, delivery begin / end, buffer free; CLOCK_MONOTONIC ns) and every eighth request per thread
  * (submitted, slots reserved, inputs written, delivered, woken).  tools/combine_timeline.py turns it into "where does a request wait". */
