@@ -27,6 +27,7 @@ EXPORTS = [
     "bpgpu_rangeproof_verify_batch_ts", "bpgpu_rangeproof_verify_batch_ts_dev", "bpgpu_ipp_verify_batch_dev",
     "bpgpu_ipp_create_batch", "bpgpu_rangeproof_prove_batch", "bpgpu_rangeproof_verify_batch_submit", "bpgpu_ctx_collect",
     "bpgpu_linear_verify_batch", "bpgpu_linear_verify_batch_dev", "bpgpu_linear_create_batch",
+    "bpgpu_linear_verify_rlc", "bpgpu_linear_verify_rlc_dev",
     "bpgpu_rangeproof_audit_shares", "bpgpu_ipp_verification_scalars",
     "bpgpu_pool_create", "bpgpu_pool_destroy", "bpgpu_pool_last_error", "bpgpu_pool_set_option", "bpgpu_pool_get_option",
     "bpgpu_pool_devices", "bpgpu_pool_lanes", "bpgpu_pool_lane", "bpgpu_pool_gens_create", "bpgpu_pool_gens_load",
@@ -105,6 +106,8 @@ def lib():
     L.bpgpu_rangeproof_audit_shares.argtypes = [vp, sz, sz, C.POINTER(C.c_uint32), u8p, u8p, u8p, u8p, i, u8p, u8p]
     L.bpgpu_linear_create_batch.argtypes = [vp, sz, sz, u8p, sz, u8p, u8p, u8p, u8p, u8p, u8p, i, u8p, u8p, u8p, u8p, u8p, u8p]
     L.bpgpu_linear_verify_batch_dev.argtypes = [vp, sz, sz, vp, sz, u8p, sz, u8p, vp, vp, vp, vp, vp, i, vp, vp, vp, vp]
+    L.bpgpu_linear_verify_rlc.argtypes = [vp, sz, sz, u8p, sz, u8p, sz, u8p, u8p, u8p, u8p, u8p, u8p, i, u8p, u8p, u8p, u8p]
+    L.bpgpu_linear_verify_rlc_dev.argtypes = [vp, sz, sz, vp, sz, u8p, sz, u8p, vp, vp, vp, vp, vp, i, vp, vp, vp, vp, vp]
     L.bpgpu_ipp_verification_scalars.argtypes = [vp, sz, sz, u8p, sz, u8p, sz, u8p, sz, u8p, u8p, u8p, u8p, u8p]
     L.bpgpu_mpc_state1_bytes.argtypes = [sz]
     L.bpgpu_mpc_state1_bytes.restype = sz
@@ -404,6 +407,23 @@ class Context:
                                                     verdict, msm, tso))
         out = (verdict.raw[:nb],) + ((msm.raw[:32 * nb],) if want_msm else ()) + ((tso.raw[:TRANSCRIPT_BYTES * nb],) if want_transcripts else ())
         return out if len(out) > 1 else out[0]
+
+    def linear_verify_rlc(self, n, proofs, proof_len, Cs, G, F, B, b, label=b"", transcript=None, weights64=None, want_transcripts=False):
+        """Batch-combined LinearProof verification (bpgpu_linear_verify_rlc): arguments as linear_verify_batch, weights64: 64 bytes per
+        proof or None (drawn by the library).  Returns (verdict bytes, batch_ok, 32-byte encoding of the combined point[, transcripts]).
+        On a failing combination the verdicts come from the per-proof path (automatic fallback)."""
+        nb = len(Cs) // 32
+        assert len(proofs) == nb * proof_len and len(b) in (32 * n, 32 * n * nb)
+        assert (G is None and F is None and B is None) or (len(G) == 32 * n and len(F) == len(B) == 32)   # None: the context's generators
+        assert weights64 is None or len(weights64) == 64 * nb
+        shared = 1 if (len(b) == 32 * n and nb != 1) else 0
+        verdict = C.create_string_buffer(max(nb, 1))
+        bo = C.create_string_buffer(33)
+        tso = C.create_string_buffer(TRANSCRIPT_BYTES * max(nb, 1)) if want_transcripts else None
+        self._chk(self._L.bpgpu_linear_verify_rlc(self.h, n, nb, proofs, proof_len, label, len(label), transcript, Cs, G, F, B, b, shared,
+                                                  weights64, verdict, bo, tso))
+        out = (verdict.raw[:nb], bo.raw[0] == 0, bo.raw[1:33])
+        return out + (tso.raw[:TRANSCRIPT_BYTES * nb],) if want_transcripts else out
 
     def linear_create_batch(self, n, Cs, rs, a, b, G, F, B, label=b"", transcript=None, rng=None, want_transcripts=False):
         """LinearProof::create for len(Cs) / 32 proofs (bpgpu_linear_create_batch): returns (proofs bytes, status bytes[, transcripts])."""

@@ -370,3 +370,20 @@ class LinearProof:
         v = c.linear_verify_batch(n, b"".join(raw), ln, b"".join(bytes(x) for x in Cs), b"".join(bytes(g) for g in G), bytes(F), bytes(B), b,
                                   transcript=transcript.state)
         return [None if x == 0 else _BY_CODE[x]() for x in v]
+
+    @staticmethod
+    def verify_batch_combined(ctx, transcript, proofs, Cs, G, F, B, b_vecs, weights64=None):
+        """verify_batch's arguments and verdicts through the batch-combined check (bpgpu_linear_verify_rlc; no counterpart in the
+        crate): one identity test per batch when every proof verifies, per-proof re-verification inside the call when not.
+        weights64: 64 bytes per proof, unpredictable to the provers, or None (drawn by the library)."""
+        c = getattr(ctx, "ctx", ctx)
+        if not proofs:
+            return []
+        raw = [p.to_bytes() if isinstance(p, LinearProof) else bytes(p) for p in proofs]
+        ln, n = len(raw[0]), len(G)
+        assert all(len(r) == ln for r in raw)
+        shared = len(b_vecs) == n and isinstance(b_vecs[0], (bytes, bytearray))
+        b = b"".join(bytes(x) for x in b_vecs) if shared else b"".join(b"".join(bytes(x) for x in v) for v in b_vecs)
+        v, _, _ = c.linear_verify_rlc(n, b"".join(raw), ln, b"".join(bytes(x) for x in Cs), b"".join(bytes(g) for g in G), bytes(F), bytes(B), b,
+                                      transcript=transcript.state, weights64=weights64)
+        return [None if x == 0 else _BY_CODE[x]() for x in v]

@@ -3036,12 +3036,20 @@ extern "C" int bpgpu_ipp_verify_batch(bpgpu_ctx *c, size_t n, size_t nbatch, con
     return BPGPU_OK;
 }
 
-// LinearProof::verify for nbatch proofs (linear.h): front end (lane = proof) -> bpgpu_msm_batch's MSM -> verdicts.
-// G (n encodings), F, B are shared by the batch; b is per proof unless b_shared.
-static int lin_verify_dev_locked(bpgpu_ctx *c, size_t n, size_t nbatch, const void *d_proofs, size_t proof_len, const uint8_t *label,
-                                 size_t label_len, const uint8_t *shared_ts, const void *d_C, const void *d_G, const void *d_F,
-                                 const void *d_B, const void *d_b, int b_shared, void *d_verdict, void *d_msm_out, void *d_ts_out,
-                                 hipStream_t s) {
+// what the front end of a LinearProof batch leaves on the device (c->ipp_buf) for its multiscalar multiplication(s)
+struct lin_staged {
+    lin_shape sh;
+    bool fmt = false;     // proof_len is not a LinearProof length: nothing was launched, every proof is a FormatError
+    bool fixed = false;   // generator-table mode
+    char *d_sc = nullptr, *d_pt = nullptr, *d_stat = nullptr, *d_mst = nullptr, *d_out = nullptr, *d_gen = nullptr;
+    const void *d_G = nullptr, *d_F = nullptr, *d_B = nullptr;   // the bases in use (the context's generators in generator-table mode)
+    size_t sz_b = 0, sz_o = 0;
+};
+
+// LinearProof::from_bytes' length part, the staging and the k_lin_prepare launch (lane = proof) of nbatch proofs
+static int lin_front_dev_locked(bpgpu_ctx *c, size_t n, size_t nbatch, const void *d_proofs, size_t proof_len, const uint8_t *label,
+                                size_t label_len, const uint8_t *shared_ts, const void *d_C, const void *d_G, const void *d_F,
+                                const void *d_B, const void *d_b, int b_shared, void *d_ts_out, hipStream_t s, lin_staged &stg) {
     if (nbatch > 0x7fffffffu / 64) return fail(c, BPGPU_ERR_INVALID_ARG, "batch too large");
     if (shared_ts && !ts_state_ok(shared_ts)) return fail(c, BPGPU_ERR_INVALID_ARG, "malformed transcript state");
     // LinearProof::from_bytes, length part (linear_proof.rs:350-366)
@@ -3058,11 +3066,10 @@ static int lin_verify_dev_locked(bpgpu_ctx *c, size_t n, size_t nbatch, const vo
     }
     if (fmt) {
         if (d_ts_out) return fail(c, BPGPU_ERR_INVALID_ARG, "proof_len is not a LinearProof length: no transcripts to return");
-        HIPCHK(c, hipMemsetAsync(d_verdict, BPGPU_VERDICT_FORMAT_ERROR, nbatch, s));
-        if (d_msm_out) HIPCHK(c, hipMemsetAsync(d_msm_out, 0, nbatch * 32, s));
+        stg.fmt = true;
         return BPGPU_OK;
     }
-    lin_shape sh;
+    lin_shape &sh = stg.sh;
     sh.n = (uint32_t)n;
     sh.k = (uint32_t)k;
     sh.proof_len = (uint32_t)proof_len;
@@ -3105,7 +3112,32 @@ static int lin_verify_dev_locked(bpgpu_ctx *c, size_t n, size_t nbatch, const vo
     LAUNCH(c, s, "lin_prepare", k_lin_prepare, (nb32 + RP_BLOCK - 1) / RP_BLOCK, RP_BLOCK, sh, init, (const uint8_t *)d_proofs, (const uint8_t *)d_C,
            (const uint8_t *)d_b, (const uint8_t *)d_G, (const uint8_t *)d_F, (const uint8_t *)d_B, (uint32_t *)d_sc, (uint32_t *)d_pt,
            (uint32_t *)d_stat, (uint32_t *)d_ts_out, (uint32_t *)d_gen);
-    int rc;
+    stg.fixed = fixed;
+    stg.d_sc = d_sc, stg.d_pt = d_pt, stg.d_stat = d_stat, stg.d_mst = d_mst, stg.d_out = d_out, stg.d_gen = d_gen;
+    stg.d_G = d_G, stg.d_F = d_F, stg.d_B = d_B;
+    stg.sz_b = sz_b, stg.sz_o = sz_o;
+    return BPGPU_OK;
+}
+
+// LinearProof::verify for nbatch proofs (linear.h): front end (lane = proof) -> bpgpu_msm_batch's MSM -> verdicts.
+// G (n encodings), F, B are shared by the batch; b is per proof unless b_shared.
+static int lin_verify_dev_locked(bpgpu_ctx *c, size_t n, size_t nbatch, const void *d_proofs, size_t proof_len, const uint8_t *label,
+                                 size_t label_len, const uint8_t *shared_ts, const void *d_C, const void *d_G, const void *d_F,
+                                 const void *d_B, const void *d_b, int b_shared, void *d_verdict, void *d_msm_out, void *d_ts_out,
+                                 hipStream_t s) {
+    lin_staged stg;
+    int rc = lin_front_dev_locked(c, n, nbatch, d_proofs, proof_len, label, label_len, shared_ts, d_C, d_G, d_F, d_B, d_b, b_shared, d_ts_out, s, stg);
+    if (rc) return rc;
+    if (stg.fmt) {
+        HIPCHK(c, hipMemsetAsync(d_verdict, BPGPU_VERDICT_FORMAT_ERROR, nbatch, s));
+        if (d_msm_out) HIPCHK(c, hipMemsetAsync(d_msm_out, 0, nbatch * 32, s));
+        return BPGPU_OK;
+    }
+    const lin_shape &sh = stg.sh;
+    const bool fixed = stg.fixed;
+    const size_t N = sh.N, sz_b = stg.sz_b, sz_o = stg.sz_o;
+    const uint32_t nb32 = (uint32_t)nbatch;
+    char *d_sc = stg.d_sc, *d_pt = stg.d_pt, *d_stat = stg.d_stat, *d_mst = stg.d_mst, *d_out = stg.d_out, *d_gen = stg.d_gen;
     if (fixed && sh.shape_verdict) {      // nothing to multiply: every proof already carries its verdict
         HIPCHK(c, hipMemsetAsync(d_mst, 0, sz_b + sz_o, s));
         rc = BPGPU_OK;
@@ -4853,6 +4885,155 @@ extern "C" int bpgpu_r1cs_verify_rlc(bpgpu_ctx *c, size_t ngroups, const bpgpu_r
     memcpy(verdict, h_out, total);
     if (batch_out) memcpy(batch_out, h_out + sz_v, 33);
     if (transcripts_out) memcpy(transcripts_out, h_out + sz_v + sz_b, total * TS);
+    return BPGPU_OK;
+}
+
+// ---- batch-combined LinearProof verification (linear_rlc.h; an ADDITIONAL entry point, as bpgpu_r1cs_verify_rlc) ------------
+// R = sum_p rho_p Check_p: the front end of the per-proof path (lin_front_dev_locked), the weights, the weigh launch, the reduction of the
+// n + 2 base rows and ONE multiscalar multiplication -- the shared-generator MSM with nbatch U unique terms in generator-table mode, one
+// variable-base MSM of (n + 2) + nbatch U terms with the caller's bases -- then the verdicts (undecided where R is not the identity).
+// The combined list and the accumulators live in the combined checks' buffer (c->r1rlc_buf), beside the front end's staging.
+static int lin_rlc_dev_locked(bpgpu_ctx *c, size_t n, size_t nbatch, const void *d_proofs, size_t proof_len, const uint8_t *label,
+                              size_t label_len, const uint8_t *shared_ts, const void *d_C, const void *d_G, const void *d_F, const void *d_B,
+                              const void *d_b, int b_shared, const void *d_weights64, uint8_t *d_verdict, uint8_t *d_batch, void *d_ts_out,
+                              hipStream_t s) {
+    if (nbatch > LIN_RLC_MAX_PROOFS) return fail(c, BPGPU_ERR_INVALID_ARG, "batch too large: more than 2^24 proofs in one combination");
+    lin_staged stg;
+    int rc = lin_front_dev_locked(c, n, nbatch, d_proofs, proof_len, label, label_len, shared_ts, d_C, d_G, d_F, d_B, d_b, b_shared, d_ts_out, s, stg);
+    if (rc) return rc;
+    if (stg.fmt) {   // every proof is a FormatError: the empty sum
+        HIPCHK(c, hipMemsetAsync(d_verdict, BPGPU_VERDICT_FORMAT_ERROR, nbatch, s));
+        if (d_batch) HIPCHK(c, hipMemsetAsync(d_batch, 0, 33, s));
+        return BPGPU_OK;
+    }
+    const lin_shape &sh = stg.sh;
+    const size_t U = 2 * (size_t)sh.k + 2, nrows = (size_t)sh.n + 2, head = stg.fixed ? 0 : nrows, nterms = head + nbatch * U;
+    if (nbatch * U > LIN_RLC_MAX_TERMS) return fail(c, BPGPU_ERR_INVALID_ARG, "batch too large: more than 2^24 proof-specific terms in one combination");
+    const size_t sz_l = align_up(nterms * 32 + 64), sz_acc = align_up(nrows * 80), sz_g = align_up(nrows * 32 + 64), sz_rho = align_up(nbatch * 32),
+                 sz_bo = align_up(64);
+    rc = r1rlc_reserve(c, 2 * sz_l + sz_acc + sz_g + sz_rho + sz_bo);
+    if (rc) return rc;
+    char *d_csc = c->r1rlc_buf, *d_cpt = d_csc + sz_l, *d_acc = d_cpt + sz_l, *d_row = d_acc + sz_acc, *d_rho = d_row + sz_g, *d_bo = d_rho + sz_rho;
+    if (!d_batch) d_batch = (uint8_t *)d_bo;
+    const uint32_t nb32 = (uint32_t)nbatch;
+    if (sh.shape_verdict) {   // n != 2^k: every proof already carries its code and nothing enters R
+        HIPCHK(c, hipMemsetAsync(stg.d_mst, 0, stg.sz_b + stg.sz_o, s));
+    } else {
+        lin_rlc_key key;
+        memset(&key, 0, sizeof key);
+        if (!d_weights64 && !bp::fast_random((uint8_t *)key.w, 32)) return fail(c, BPGPU_ERR_HIP, "getrandom failed");   // (never the test seed: weights stay unpredictable)
+        LAUNCH(c, s, "lin_rlc_rho", k_lin_rlc_rho, (nb32 + 63) / 64, 64, nb32, (const uint8_t *)d_weights64, key, (uint32_t *)d_rho);
+        lin_rlc_shape ws;
+        ws.nproofs = nb32, ws.nstride = (uint32_t)((nbatch + 63) / 64 * 64), ws.n = sh.n, ws.k = sh.k, ws.U = (uint32_t)U, ws.fixed = stg.fixed ? 1u : 0u,
+        ws.u0 = (uint32_t)head;
+        const uint64_t nt = (uint64_t)ws.nstride * (U + nrows);   // (a multiple of 64: whole wavefronts)
+        if (nt > 0x7fffffffull) return fail(c, BPGPU_ERR_INVALID_ARG, "batch too large for this shape");
+        HIPCHK(c, hipMemsetAsync(d_acc, 0, sz_acc, s));
+        LAUNCH(c, s, "lin_rlc_weigh", k_lin_rlc_weigh, (uint32_t)(nt / 64), 64, ws, (const uint32_t *)stg.d_stat, (const uint32_t *)d_rho, (const uint32_t *)stg.d_gen,
+               (const uint32_t *)stg.d_sc, (const uint32_t *)stg.d_pt, (uint32_t *)d_csc, (uint32_t *)d_cpt, (unsigned long long *)d_acc);
+        // the combined coefficients of (B, F, G_0..): the generator-table row, or the head of the list with the caller's encodings
+        LAUNCH(c, s, "lin_rlc_reduce", k_lin_rlc_reduce, (uint32_t)((nrows + 63) / 64), 64, (uint32_t)nrows, (const unsigned long long *)d_acc,
+               (const uint8_t *)stg.d_B, (const uint8_t *)stg.d_F, (const uint8_t *)stg.d_G, (uint32_t *)(stg.fixed ? d_row : d_csc),
+               stg.fixed ? (uint32_t *)nullptr : (uint32_t *)d_cpt);
+        if (stg.fixed) {
+            rc = msm_shared_dev_locked(c, sh.n, 1, 1, nbatch * U, d_row, d_csc, d_cpt, stg.d_out, stg.d_mst, nullptr, s, true);
+        } else {
+            const uint32_t nt1 = (uint32_t)nterms;
+            rc = msm_batch_dev_locked(c, 1, &nt1, d_csc, d_cpt, stg.d_out, stg.d_mst, s);
+        }
+        if (rc) return rc;
+    }
+    LAUNCH(c, s, "lin_rlc_verdict", k_lin_rlc_verdict, (nb32 + 63) / 64, 64, nb32, (const uint32_t *)stg.d_stat, (const uint32_t *)stg.d_out,
+           (const uint8_t *)stg.d_mst, d_verdict, d_batch);
+    HIPCHK(c, hipGetLastError());
+    return BPGPU_OK;
+}
+
+extern "C" int bpgpu_linear_verify_rlc_dev(bpgpu_ctx *c, size_t n, size_t nbatch, const void *d_proofs, size_t proof_len, const uint8_t *label,
+                                           size_t label_len, const uint8_t *shared_transcript, const void *d_C, const void *d_G, const void *d_F,
+                                           const void *d_B, const void *d_b, int b_shared, const void *d_weights64, void *d_verdict,
+                                           void *d_batch_out, void *d_transcripts_out, void *stream) {
+    if (!c || (label_len && !label)) return BPGPU_ERR_INVALID_ARG;
+    if (nbatch == 0) return BPGPU_OK;
+    const bool from_gens = !d_G && !d_F && !d_B;
+    if (!d_proofs || !d_verdict || !d_C || (n && !d_b) || (!from_gens && (!d_F || !d_B || (n && !d_G)))) return BPGPU_ERR_INVALID_ARG;
+    if (((uintptr_t)d_proofs | (uintptr_t)d_C | (uintptr_t)d_G | (uintptr_t)d_F | (uintptr_t)d_B | (uintptr_t)d_b | (uintptr_t)d_transcripts_out) & 3)
+        return fail(c, BPGPU_ERR_INVALID_ARG, "device buffers must be 4-byte aligned");
+    std::lock_guard<std::mutex> lk(c->mu);
+    HIPCHK(c, hipSetDevice(c->device));
+    hipStream_t s = stream ? (hipStream_t)stream : c->stream;
+    int rc = ctx_enter(c, s);
+    if (rc) return rc;
+    rc = lin_rlc_dev_locked(c, n, nbatch, d_proofs, proof_len, label, label_len, shared_transcript, d_C, d_G, d_F, d_B, d_b, b_shared, d_weights64,
+                            (uint8_t *)d_verdict, (uint8_t *)d_batch_out, d_transcripts_out, s);
+    const int rc2 = ctx_leave(c, s);
+    return rc ? rc : rc2;
+}
+
+extern "C" int bpgpu_linear_verify_rlc(bpgpu_ctx *c, size_t n, size_t nbatch, const uint8_t *proofs, size_t proof_len, const uint8_t *label,
+                                       size_t label_len, const uint8_t *shared_transcript, const uint8_t *C, const uint8_t *G, const uint8_t *F,
+                                       const uint8_t *B, const uint8_t *b, int b_shared, const uint8_t *weights64, uint8_t *verdict,
+                                       uint8_t *batch_out, uint8_t *transcripts_out) {
+    if (!c || (label_len && !label)) return BPGPU_ERR_INVALID_ARG;
+    if (nbatch == 0) {
+        if (batch_out) memset(batch_out, 0, 33);
+        return BPGPU_OK;
+    }
+    const bool from_gens = !G && !F && !B;
+    if (!proofs || !verdict || !C || (n && !b) || (!from_gens && (!F || !B || (n && !G)))) return BPGPU_ERR_INVALID_ARG;
+    if (nbatch > LIN_RLC_MAX_PROOFS) return fail(c, BPGPU_ERR_INVALID_ARG, "batch too large: more than 2^24 proofs in one combination");
+    std::lock_guard<std::mutex> lk(c->mu);
+    HIPCHK(c, hipSetDevice(c->device));
+    const size_t nb_b = b_shared ? 1 : nbatch;
+    const size_t sz_pr = align_up(nbatch * proof_len + 64), sz_c = align_up(nbatch * 32 + 64), sz_g = align_up(n * 32 + 64), sz_fb = align_up(64 + 64),
+                 sz_bv = align_up(nb_b * n * 32 + 64), sz_w = weights64 ? align_up(nbatch * 64) : 0;
+    const size_t sz_in = sz_pr + sz_c + sz_g + sz_fb + sz_bv + sz_w, sz_v = align_up(nbatch), sz_bo = align_up(64);
+    const size_t sz_t = transcripts_out ? align_up(nbatch * BPGPU_TRANSCRIPT_BYTES) : 0, sz_out = sz_v + sz_bo + sz_t;
+    hipStream_t s = c->stream;
+    int rc = ctx_enter(c, s);
+    if (rc) return rc;
+    rc = io_reserve(c, sz_in + sz_out);
+    if (rc) return rc;
+    char *h = nullptr;
+    rc = pin_alloc(c, s, sz_in + sz_out, &h);
+    if (rc) return rc;
+    char *d = c->io_dev;
+    char *d_pr = d, *d_c = d_pr + sz_pr, *d_g = d_c + sz_c, *d_fb = d_g + sz_g, *d_bv = d_fb + sz_fb, *d_w = d_bv + sz_bv, *d_v = d + sz_in, *d_bo = d_v + sz_v;
+    char *d_t = transcripts_out ? d_bo + sz_bo : nullptr;
+    memcpy(h, proofs, nbatch * proof_len);
+    memcpy(h + sz_pr, C, nbatch * 32);
+    if (n) {
+        if (!from_gens) memcpy(h + sz_pr + sz_c, G, n * 32);
+        memcpy(h + sz_pr + sz_c + sz_g + sz_fb, b, nb_b * n * 32);
+    }
+    if (!from_gens) {
+        memcpy(h + sz_pr + sz_c + sz_g, F, 32);
+        memcpy(h + sz_pr + sz_c + sz_g + 32, B, 32);
+    }
+    if (weights64) memcpy(h + sz_in - sz_w, weights64, nbatch * 64);
+    HIPCHK(c, hipMemcpyAsync(d, h, sz_in, hipMemcpyHostToDevice, s));
+    const void *a_g = from_gens ? nullptr : d_g, *a_f = from_gens ? nullptr : d_fb, *a_b = from_gens ? nullptr : d_fb + 32;
+    rc = lin_rlc_dev_locked(c, n, nbatch, d_pr, proof_len, label, label_len, shared_transcript, d_c, a_g, a_f, a_b, d_bv, b_shared,
+                            weights64 ? d_w : nullptr, (uint8_t *)d_v, (uint8_t *)d_bo, d_t, s);
+    char *h_out = h + sz_in;
+    if (!rc && hipMemcpyAsync(h_out, d_v, sz_out, hipMemcpyDeviceToHost, s) != hipSuccess) rc = fail(c, BPGPU_ERR_HIP, "D2H copy failed");
+    int rc2 = ctx_leave(c, s), rc3 = host_wait(c, s);
+    if (rc || rc2 || rc3) return rc ? rc : (rc2 ? rc2 : rc3);
+    if (batch_out) memcpy(batch_out, h_out + sz_v, 33);   // (R as computed before any fallback)
+    if (transcripts_out) memcpy(transcripts_out, h_out + sz_v + sz_bo, nbatch * BPGPU_TRANSCRIPT_BYTES);
+    if ((uint8_t)h_out[sz_v] != 0) {
+        // R is not the identity, or a point of the combined MSM did not decode: the batch again through the per-proof path (inputs are
+        // still on the device; the transcripts it leaves are the ones already copied out)
+        rc = ctx_enter(c, s, true);
+        if (rc) return rc;
+        rc = lin_verify_dev_locked(c, n, nbatch, d_pr, proof_len, label, label_len, shared_transcript, d_c, a_g, a_f, a_b, d_bv, b_shared, d_v, nullptr,
+                                   nullptr, s);
+        if (!rc && hipMemcpyAsync(h_out, d_v, sz_v, hipMemcpyDeviceToHost, s) != hipSuccess) rc = fail(c, BPGPU_ERR_HIP, "D2H copy failed");
+        rc2 = ctx_leave(c, s);
+        rc3 = host_wait(c, s);
+        if (rc || rc2 || rc3) return rc ? rc : (rc2 ? rc2 : rc3);
+    }
+    memcpy(verdict, h_out, nbatch);
     return BPGPU_OK;
 }
 

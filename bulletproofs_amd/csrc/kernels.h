@@ -21,6 +21,7 @@
 #include "r1cs_prover.h"
 #include "r1cs_rlc.h"
 #include "rlc_mix.h"
+#include "linear_rlc.h"
 #include "mpc_party.h"
 #include "mpc_dealer.h"
 
@@ -87,6 +88,10 @@ __global__ void k_r1cs_rlc_weigh(r1_rlc_slice sl, const uint32_t *status, const 
 __global__ void k_r1cs_rlc_reduce(uint32_t nrows, const unsigned long long *acc, uint32_t *gen_row);
 __global__ void k_r1cs_rlc_sum(uint32_t ncomb, const uint32_t *parts, const uint8_t *part_status, uint32_t *res);
 __global__ void k_r1cs_rlc_verdict(uint32_t n, const uint32_t *gstatus, const uint32_t *res, uint8_t *verdict, uint8_t *batch_out);
+__global__ void k_lin_rlc_rho(uint32_t n, const uint8_t *weights64, lin_rlc_key key, uint32_t *rho);
+__global__ void k_lin_rlc_weigh(lin_rlc_shape sh, const uint32_t *status, const uint32_t *rho, const uint32_t *gen_sc, const uint32_t *list_sc, const uint32_t *list_pt, uint32_t *comb_sc, uint32_t *comb_pt, unsigned long long *acc);
+__global__ void k_lin_rlc_reduce(uint32_t nrows, const unsigned long long *acc, const uint8_t *B, const uint8_t *F, const uint8_t *G, uint32_t *out_sc, uint32_t *out_pt);
+__global__ void k_lin_rlc_verdict(uint32_t n, const uint32_t *status, const uint32_t *enc, const uint8_t *msm_status, uint8_t *verdict, uint8_t *batch_out);
 // k_rlc_mix.hip
 __global__ void k_rlc_mix_draw(uint32_t n, rm_key key, uint32_t dom, uint32_t *out);
 __global__ void k_rlc_mix_front(rp_shape sh, rp_strobe_init init, uint32_t n_tr, const uint8_t *proofs, const uint8_t *commitments, const uint8_t *rng64, const uint8_t *rho64, uint32_t *fields, uint32_t *status, fb_params prm, uint32_t lg_m, uint32_t *uniq_sc, const rp_script_hdr *script);

@@ -366,6 +366,45 @@ int bpgpu_linear_verify_batch_dev(bpgpu_ctx *ctx, size_t n, size_t nbatch, const
                                   const void *d_C, const void *d_G, const void *d_F, const void *d_B,
                                   const void *d_b, int b_shared, void *d_verdict, void *d_msm_out, void *d_transcripts_out,
                                   void *stream);
+/* Batch-combined LinearProof verification (ADDITIONAL entry point, as bpgpu_rangeproof_verify_rlc and bpgpu_r1cs_verify_rlc; the
+ * reference's LinearProof has only create / verify).  Arguments are those of bpgpu_linear_verify_batch, with msm_out replaced by
+ * weights64 and batch_out; one n per call.
+ *     R = sum_p rho_p * Check_p ,  rho_p = Scalar::from_bytes_mod_order_wide(weights64[p]),
+ * over the proofs that reach the final check, Check_p being the multiscalar multiplication of bpgpu_linear_verify_batch for proof p.
+ * G, F, B are shared by the batch (the caller's points or, with G = F = B = NULL, the context's generators), so their n + 2
+ * coefficients add up in the scalar field and only the 2 lg(n) + 2 points C, L_j, R_j, S of every proof cost point arithmetic: ONE
+ * multiscalar multiplication per call -- one walk of the window tables plus nbatch (2 lg(n) + 2) points in generator-table mode,
+ * (n + 2) + nbatch (2 lg(n) + 2) points with the caller's bases.  R is the identity when every combined proof verifies; if one does
+ * not, R != identity except with probability ~2^-252 over the weights, which must be unpredictable to the provers (NULL = drawn by
+ * the library: uniform 512-bit strings expanded on the device from a per-call key).  A zero weight leaves its proof unchecked.
+ *   weights64       : nbatch x 64 bytes, or NULL
+ *   verdict         : ALWAYS what bpgpu_linear_verify_batch returns for the same inputs.  A proof that stops in the front end
+ *                     (FormatError; an identity L_j / R_j; n != 2^lg_n) gets that code and is left out of R; the others get 0 when R is
+ *                     the identity and every point decoded.  Otherwise the host entry point re-verifies the batch through the per-proof
+ *                     path and returns those verdicts; the asynchronous _dev variant marks them BPGPU_VERDICT_UNDECIDED and leaves
+ *                     that to the caller.
+ *   batch_out       : optional 33 bytes: [0] = 0 when R is the identity and every point decoded, else 1; [1..33) = compress(R) as
+ *                     computed before any fallback, or zeros when a point did not decode
+ *   transcripts_out : optional, as bpgpu_linear_verify_batch leaves them
+ * Errors and shortcuts are those of bpgpu_linear_verify_batch: a proof_len that is no LinearProof length gives FormatError for every
+ * proof (and batch_out = zeros), generators missing or smaller than n an error code, nbatch = 0 BPGPU_OK.  One call takes at most 2^24
+ * proofs and 2^24 proof-specific points (nbatch (2 lg(n) + 2)); larger calls return BPGPU_ERR_INVALID_ARG.
+ * The transcript replay stays per proof (C is absorbed first and is the proof's own), so the front end costs what it costs in the
+ * per-proof call; what the combination saves is the multiscalar multiplication.  Measured on one MI355X (DESIGN 3.4,
+ * profiles/linear_rlc_rate.json): faster than bpgpu_linear_verify_batch with the caller's bases from about 1 000 proofs on (1.5x ... 2.2x
+ * at 4 096 proofs, n = 64 ... 1 024) and with the generator tables at 4 096 proofs and n >= 256 (1.2x); NOT faster (0.82x ... 1.03x) at 64
+ * proofs and with the generator tables up to 1 024 proofs: the front end (k_lin_prepare) dominates both calls there and the one combined
+ * MSM has a floor of 0.5 ... 1.5 ms.  A failing batch costs this call plus the per-proof one. */
+int bpgpu_linear_verify_rlc(bpgpu_ctx *ctx, size_t n, size_t nbatch, const uint8_t *proofs, size_t proof_len,
+                            const uint8_t *label, size_t label_len, const uint8_t *shared_transcript,
+                            const uint8_t *C, const uint8_t *G, const uint8_t *F, const uint8_t *B,
+                            const uint8_t *b, int b_shared, const uint8_t *weights64,
+                            uint8_t *verdict, uint8_t *batch_out, uint8_t *transcripts_out);
+int bpgpu_linear_verify_rlc_dev(bpgpu_ctx *ctx, size_t n, size_t nbatch, const void *d_proofs, size_t proof_len,
+                                const uint8_t *label, size_t label_len, const uint8_t *shared_transcript,
+                                const void *d_C, const void *d_G, const void *d_F, const void *d_B,
+                                const void *d_b, int b_shared, const void *d_weights64,
+                                void *d_verdict, void *d_batch_out, void *d_transcripts_out, void *stream);
 
 /* ---- R1CS constraint-system proofs (r1cs::Verifier::verify, src/r1cs/verifier.rs:329-500) ----------------------------
  * The reference's verifier re-runs a gadget (closures) against its constraint system.  On the verifier side only

@@ -418,6 +418,32 @@ class LinearProof {
         for (uint8_t v : verdict) out.push_back(v == 0 ? Status::Ok() : Status::Err(static_cast<ProofError>(v)));
         return out;
     }
+    // verify_batch's arguments and verdicts through the batch-combined check (bpgpu_linear_verify_rlc; no counterpart in the crate):
+    // one identity test per batch when every proof verifies, per-proof re-verification inside the call when not.  weights64: 64 bytes
+    // per proof, unpredictable to the provers, or nullptr (drawn by the library).
+    static std::vector<Status> verify_batch_combined(bpgpu_ctx *ctx, const Transcript &transcript, const std::vector<LinearProof> &proofs,
+                                                     const std::vector<CompressedRistretto> &Cs, const std::vector<CompressedRistretto> &G,
+                                                     const CompressedRistretto &F, const CompressedRistretto &B,
+                                                     const std::vector<std::vector<ScalarBytes>> &b_vecs, const uint8_t *weights64 = nullptr) {
+        const size_t nb = proofs.size(), n = G.size();
+        std::vector<Status> out;
+        if (nb == 0) return out;
+        if (Cs.size() != nb || b_vecs.size() != nb) throw std::invalid_argument("one commitment and one public vector per proof");
+        const size_t pl = proofs[0].bytes_.size();
+        std::vector<uint8_t> pb, cb, bb, verdict(nb);
+        for (size_t i = 0; i < nb; i++) {
+            if (proofs[i].bytes_.size() != pl || b_vecs[i].size() != n) throw std::invalid_argument("proofs of a batch must have one size");
+            pb.insert(pb.end(), proofs[i].bytes_.begin(), proofs[i].bytes_.end());
+            cb.insert(cb.end(), Cs[i].begin(), Cs[i].end());
+            for (const auto &x : b_vecs[i]) bb.insert(bb.end(), x.begin(), x.end());
+        }
+        const int rc = bpgpu_linear_verify_rlc(ctx, n, nb, pb.data(), pl, nullptr, 0, transcript.state().data(), cb.data(),
+                                               n ? G[0].data() : nullptr, F.data(), B.data(), n ? bb.data() : nullptr, 0, weights64, verdict.data(),
+                                               nullptr, nullptr);
+        if (rc != BPGPU_OK) throw GpuError(bpgpu_last_error(ctx));
+        for (uint8_t v : verdict) out.push_back(v == 0 ? Status::Ok() : Status::Err(static_cast<ProofError>(v)));
+        return out;
+    }
 
   private:
     std::vector<uint8_t> bytes_;
