@@ -22,6 +22,8 @@ EXPORTS = [
     "bpgpu_rangeproof_verify_batch", "bpgpu_rangeproof_verify_batch_dev", "bpgpu_ipp_verify_batch",
     "bpgpu_rangeproof_verify_rlc", "bpgpu_rangeproof_verify_rlc_dev",
     "bpgpu_rangeproof_verify_rlc_mixed", "bpgpu_pool_rangeproof_verify_rlc_mixed",
+    "bpgpu_rangeproof_verify_rlc_ts", "bpgpu_rangeproof_verify_rlc_ts_dev", "bpgpu_rangeproof_verify_rlc_mixed_ts",
+    "bpgpu_pool_rangeproof_verify_rlc_mixed_ts",
     "bpgpu_profile_enable", "bpgpu_profile_reset", "bpgpu_profile_report",
     "bpgpu_transcript_new", "bpgpu_transcript_append_message", "bpgpu_transcript_challenge_bytes",
     "bpgpu_rangeproof_verify_batch_ts", "bpgpu_rangeproof_verify_batch_ts_dev", "bpgpu_ipp_verify_batch_dev",
@@ -91,6 +93,10 @@ def lib():
     szp = C.POINTER(sz)
     L.bpgpu_rangeproof_verify_rlc_mixed.argtypes = [vp, sz, szp, szp, szp, szp, u8p, u8p, C.POINTER(u8p), szp, u8p, u8p, u8p, u8p]
     L.bpgpu_pool_rangeproof_verify_rlc_mixed.argtypes = L.bpgpu_rangeproof_verify_rlc_mixed.argtypes
+    L.bpgpu_rangeproof_verify_rlc_ts.argtypes = [vp, sz, sz, sz, u8p, sz, u8p, u8p, sz, u8p, u8p, u8p, u8p, u8p]
+    L.bpgpu_rangeproof_verify_rlc_ts_dev.argtypes = [vp, sz, sz, sz, vp, sz, vp, u8p, vp, vp, vp, vp, vp, vp, vp]
+    L.bpgpu_rangeproof_verify_rlc_mixed_ts.argtypes = [vp, sz, szp, szp, szp, szp, u8p, u8p, u8p, szp, u8p, u8p, u8p, u8p, u8p]
+    L.bpgpu_pool_rangeproof_verify_rlc_mixed_ts.argtypes = L.bpgpu_rangeproof_verify_rlc_mixed_ts.argtypes
     L.bpgpu_ipp_verify_batch.argtypes = [vp, sz, sz, u8p, sz, u8p, sz, u8p, u8p, u8p, u8p, u8p, u8p, u8p, u8p]
     L.bpgpu_transcript_new.argtypes = [u8p, sz, u8p]
     L.bpgpu_transcript_append_message.argtypes = [u8p, u8p, sz, u8p, sz]
@@ -205,6 +211,32 @@ def _rlc_mixed_call(fn, handle, groups, rng64, weights64):
             b"".join(bytes(g[2]) for g in groups), b"".join(bytes(g[4]) for g in groups), labels, arr([len(g[5]) for g in groups]),
             rng64, weights64, verdict, bo)
     return rc, verdict.raw[:total], bo.raw[0] == 0, bo.raw[1:33]
+
+
+def _rlc_mixed_ts_call(fn, handle, groups, rng64, weights64, want_transcripts):
+    """bpgpu_[pool_]rangeproof_verify_rlc_mixed_ts: groups = [(n, m, proofs, proof_len, commitments, states)], states = ONE 208-byte state
+    for the group or one per proof"""
+    ng = len(groups)
+    sz = C.c_size_t
+    nbs, strides = [], []
+    for n, m, proofs, proof_len, commitments, states in groups:
+        nb = len(proofs) // proof_len if proof_len else 0
+        assert len(proofs) == nb * proof_len and len(commitments) == 32 * m * nb
+        assert len(states) in (TRANSCRIPT_BYTES, TRANSCRIPT_BYTES * nb)
+        nbs.append(nb)
+        strides.append(0 if (len(states) == TRANSCRIPT_BYTES and nb != 1) else TRANSCRIPT_BYTES)
+    total = sum(nbs)
+    assert rng64 is None or len(rng64) == 64 * total
+    assert weights64 is None or len(weights64) == 64 * total
+    arr = lambda vals: (sz * max(ng, 1))(*vals)
+    verdict = C.create_string_buffer(max(total, 1))
+    bo = C.create_string_buffer(33)
+    tso = C.create_string_buffer(TRANSCRIPT_BYTES * max(total, 1)) if want_transcripts else None
+    rc = fn(handle, ng, arr([g[0] for g in groups]), arr([g[1] for g in groups]), arr(nbs), arr([g[3] for g in groups]),
+            b"".join(bytes(g[2]) for g in groups), b"".join(bytes(g[4]) for g in groups), b"".join(bytes(g[5]) for g in groups) or bytes(1), arr(strides),
+            rng64, weights64, verdict, bo, tso)
+    out = (verdict.raw[:total], bo.raw[0] == 0, bo.raw[1:33])
+    return rc, (out + (tso.raw[:TRANSCRIPT_BYTES * total],) if want_transcripts else out)
 
 
 class Context:
@@ -355,6 +387,32 @@ class Context:
         rc, verdict, ok, enc = _rlc_mixed_call(self._L.bpgpu_rangeproof_verify_rlc_mixed, self.h, groups, rng64, weights64)
         self._chk(rc)
         return verdict, ok, enc
+
+    def rangeproof_verify_rlc_ts(self, n, m, proofs, proof_len, commitments, transcripts, rng64=None, weights64=None, want_transcripts=False):
+        """rangeproof_verify_rlc on the callers' own transcripts (bpgpu_rangeproof_verify_rlc_ts): `transcripts` is ONE 208-byte state
+        shared by the batch, or nbatch of them (at any STROBE positions).  Returns (verdict bytes, batch_ok, 32-byte encoding of the
+        combined point[, advanced states])."""
+        nb = len(proofs) // proof_len if proof_len else 0
+        assert len(proofs) == nb * proof_len and len(commitments) == 32 * m * nb
+        assert len(transcripts) in (TRANSCRIPT_BYTES, TRANSCRIPT_BYTES * nb)
+        assert rng64 is None or len(rng64) == 64 * nb
+        assert weights64 is None or len(weights64) == 64 * nb
+        stride = 0 if (len(transcripts) == TRANSCRIPT_BYTES and nb != 1) else TRANSCRIPT_BYTES
+        verdict = C.create_string_buffer(max(nb, 1))
+        bo = C.create_string_buffer(33)
+        tso = C.create_string_buffer(TRANSCRIPT_BYTES * max(nb, 1)) if want_transcripts else None
+        self._chk(self._L.bpgpu_rangeproof_verify_rlc_ts(self.h, n, m, nb, proofs, proof_len, commitments, transcripts, stride, rng64, weights64,
+                                                         verdict, bo, tso))
+        out = (verdict.raw[:nb], bo.raw[0] == 0, bo.raw[1:33])
+        return out + (tso.raw[:TRANSCRIPT_BYTES * nb],) if want_transcripts else out
+
+    def rangeproof_verify_rlc_mixed_ts(self, groups, rng64=None, weights64=None, want_transcripts=False):
+        """rangeproof_verify_rlc_mixed on the callers' own transcripts (bpgpu_rangeproof_verify_rlc_mixed_ts): groups is a list of
+        (n, m, proofs, proof_len, commitments, states), states = ONE 208-byte state for the group or one per proof.  Returns (verdict
+        bytes in call order, batch_ok, 32-byte encoding of the combined point[, advanced states in call order])."""
+        rc, out = _rlc_mixed_ts_call(self._L.bpgpu_rangeproof_verify_rlc_mixed_ts, self.h, groups, rng64, weights64, want_transcripts)
+        self._chk(rc)
+        return out
 
     # ---- stand-alone inner-product proofs ----
     def ipp_verify_batch(self, n, proofs, proof_len, label, Gf, Hf, P, Q, G, H, want_msm=False):
@@ -696,6 +754,12 @@ class Pool:
         rc, verdict, ok, enc = _rlc_mixed_call(self._L.bpgpu_pool_rangeproof_verify_rlc_mixed, self.h, groups, rng64, weights64)
         self._chk(rc)
         return verdict, ok, enc
+
+    def rangeproof_verify_rlc_mixed_ts(self, groups, rng64=None, weights64=None, want_transcripts=False):
+        """Context.rangeproof_verify_rlc_mixed_ts through the pool (bpgpu_pool_rangeproof_verify_rlc_mixed_ts): the whole call on the next device"""
+        rc, out = _rlc_mixed_ts_call(self._L.bpgpu_pool_rangeproof_verify_rlc_mixed_ts, self.h, groups, rng64, weights64, want_transcripts)
+        self._chk(rc)
+        return out
 
     def rangeproof_verify_ts(self, n, m, proofs, proof_len, commitments, transcripts, rng64=None, want_msm=False, want_transcripts=True):
         """The reference's call shape (bpgpu_pool_rangeproof_verify_ts): blocking, any number of threads at once; `transcripts`

@@ -243,28 +243,37 @@ class RangeProof:
 
     @staticmethod
     def verify_batch_combined(bp_gens, pc_gens, transcript, proofs, commitments, n, rng64=None, weights64=None):
-        """The same verdicts through the batch-combined check (bpgpu_rangeproof_verify_rlc; no counterpart in the crate): one
-        identity test per batch when every proof verifies, per-proof re-verification inside the call when not.  This entry
-        point replays each proof's transcript from its label: `transcript` must be a fresh Transcript(label)."""
+        """The same verdicts through the batch-combined check (bpgpu_rangeproof_verify_rlc / _rlc_ts; no counterpart in the crate): one
+        identity test per batch when every proof verifies, per-proof re-verification inside the call when not.  `transcript`: a fresh
+        Transcript(label), replayed from its label; or a transcript the caller has already bound to its transaction or session, the
+        start state of every proof; or a list of transcripts, one per proof, at whatever positions their histories left them.  The
+        caller's transcripts are not advanced, as in verify_batch."""
         if not proofs:
             return []
         bp_gens._check_pedersen(pc_gens)
-        label = transcript.fresh_label
-        if label is None:
-            raise ValueError("verify_batch_combined needs a fresh Transcript(label); use verify_batch for pre-bound transcripts")
         raw = [p.to_bytes() if isinstance(p, RangeProof) else bytes(p) for p in proofs]
         m, ln = len(commitments[0]), len(raw[0])
         assert all(len(r) == ln for r in raw) and all(len(c) == m for c in commitments)
-        v, _, _ = bp_gens.ctx.rangeproof_verify_rlc(n, m, b"".join(raw), ln, b"".join(b"".join(c) for c in commitments), label, rng64,
-                                                    weights64)
+        flat, coms = b"".join(raw), b"".join(b"".join(c) for c in commitments)
+        if isinstance(transcript, (list, tuple)):
+            if len(transcript) != len(raw):
+                raise ValueError("verify_batch_combined: one transcript per proof")
+            v, _, _ = bp_gens.ctx.rangeproof_verify_rlc_ts(n, m, flat, ln, coms, b"".join(t.state for t in transcript), rng64, weights64)
+        elif transcript.fresh_label is None:
+            v, _, _ = bp_gens.ctx.rangeproof_verify_rlc_ts(n, m, flat, ln, coms, transcript.state, rng64, weights64)
+        else:
+            v, _, _ = bp_gens.ctx.rangeproof_verify_rlc(n, m, flat, ln, coms, transcript.fresh_label, rng64, weights64)
         return [None if x == 0 else _BY_CODE[x]() for x in v]
 
     @staticmethod
-    def verify_mixed_combined(bp_gens, pc_gens, items, rng64=None, weights64=None):
+    def verify_mixed_combined(bp_gens, pc_gens, items, rng64=None, weights64=None, bound_transcripts=False):
         """Proofs of mixed shapes through ONE batch-combined check (bpgpu_rangeproof_verify_rlc_mixed; no counterpart in the crate).
-        items: [(transcript, proof, commitments, n)] in any order, every transcript a fresh Transcript(label) as for
-        verify_batch_combined; they are grouped by (n, m, proof length, label).  rng64 / weights64: 64 bytes per item, in the order
-        of `items` (each row follows its item through the regrouping).  Returns None / ProofError per item, in the caller's order."""
+        items: [(transcript, proof, commitments, n)] in any order; fresh Transcript(label) items are grouped by (n, m, proof length,
+        label).  bound_transcripts=True also takes transcripts the caller has already bound to a transaction or session: those items
+        are grouped by (n, m, proof length), every proof starting from its own state, and combined by
+        bpgpu_rangeproof_verify_rlc_mixed_ts (a check of their own beside the fresh items'); without it a bound transcript is a
+        ValueError, as before.  rng64 / weights64: 64 bytes per item, in the order of `items` (each row follows its item through the
+        regrouping).  The caller's transcripts are not advanced.  Returns None / ProofError per item, in the caller's order."""
         if not items:
             return []
         bp_gens._check_pedersen(pc_gens)
@@ -276,21 +285,27 @@ class RangeProof:
         groups, order = {}, []
         for i, (transcript, proof, commitments, n) in enumerate(items):
             label = transcript.fresh_label
-            if label is None:
-                raise ValueError("verify_mixed_combined needs a fresh Transcript(label) per item; pre-bound transcripts go through verify_batch")
+            if label is None and not bound_transcripts:
+                raise ValueError("verify_mixed_combined needs a fresh Transcript(label) per item unless bound_transcripts=True")
             raw = proof.to_bytes() if isinstance(proof, RangeProof) else bytes(proof)
-            key = (n, len(commitments), len(raw), bytes(label))
+            key = (label is None, n, len(commitments), len(raw), b"" if label is None else bytes(label))
             if key not in groups:
                 groups[key] = []
                 order.append(key)
-            groups[key].append((i, raw, b"".join(commitments)))
-        index = [i for key in order for i, _, _ in groups[key]]   # call position -> item
-        call = [(key[0], key[1], b"".join(r for _, r, _ in groups[key]), key[2], b"".join(c for _, _, c in groups[key]), key[3]) for key in order]
-        rows = lambda buf: None if buf is None else b"".join(buf[64 * i:64 * i + 64] for i in index)
-        v, _, _ = bp_gens.ctx.rangeproof_verify_rlc_mixed(call, rows(rng64), rows(weights64))
+            groups[key].append((i, raw, b"".join(commitments), transcript.state))
         out = [None] * ni
-        for pos, i in enumerate(index):
-            out[i] = None if v[pos] == 0 else _BY_CODE[v[pos]]()
+        for bound in (False, True):
+            keys = [key for key in order if key[0] == bound]
+            if not keys:
+                continue
+            index = [g[0] for key in keys for g in groups[key]]   # call position -> item
+            call = [(key[1], key[2], b"".join(g[1] for g in groups[key]), key[3], b"".join(g[2] for g in groups[key]),
+                     b"".join(g[3] for g in groups[key]) if bound else key[4]) for key in keys]
+            rows = lambda buf: None if buf is None else b"".join(buf[64 * i:64 * i + 64] for i in index)
+            fn = bp_gens.ctx.rangeproof_verify_rlc_mixed_ts if bound else bp_gens.ctx.rangeproof_verify_rlc_mixed
+            v = fn(call, rows(rng64), rows(weights64))[0]
+            for pos, i in enumerate(index):
+                out[i] = None if v[pos] == 0 else _BY_CODE[v[pos]]()
         return out
 
 

@@ -5424,7 +5424,34 @@ struct rp_mix_group {
     const uint8_t *label;
     size_t label_len;
     bool whole;   // rejected as a whole: every proof gets the code of the per-shape path, the group contributes nothing
+    // caller-supplied transcripts (bpgpu_rangeproof_verify_rlc_mixed_ts): h_ts (host) is ONE state for the group (ts_stride == 0) or one per
+    // proof, then also staged at d_ts_in; ts_uniform: all of them at one STROBE position (u_*): the scripted replay.  d_ts_out (optional):
+    // the group's slice of the advanced states.  h_ts == nullptr: the group starts from its label.
+    const uint8_t *h_ts = nullptr;
+    size_t ts_stride = 0;
+    const char *d_ts_in = nullptr;
+    char *d_ts_out = nullptr;
+    bool ts_uniform = false;
+    uint32_t u_pos = 0, u_pos_begin = 0, u_flags = 0;
 };
+// where the per-proof path starts the group's proofs (groups rejected as a whole, and the fallback)
+static rp_transcripts rp_mix_transcripts(const rp_mix_group &g) {
+    rp_transcripts tr;
+    if (!g.h_ts) {
+        tr.label = g.label;
+        tr.label_len = g.label_len;
+        return tr;
+    }
+    if (g.ts_stride) {
+        tr.d_ts_in = g.d_ts_in;
+        tr.ts_uniform = g.ts_uniform;
+        tr.u_pos = g.u_pos, tr.u_pos_begin = g.u_pos_begin, tr.u_flags = g.u_flags;
+    } else {
+        tr.shared_ts = g.h_ts;
+    }
+    tr.d_ts_out = g.d_ts_out;
+    return tr;
+}
 }  // namespace
 
 // The checks rp_verify_dev_locked makes before its first launch -- the length-only part of from_bytes (mod.rs:505-510, ipp.rs:374-388),
@@ -5484,10 +5511,8 @@ static int rp_mix_dev_locked(bpgpu_ctx *c, std::vector<rp_mix_group> &gr, size_t
     // groups rejected as a whole: the per-shape path's own codes, written now; the verdict launch leaves them alone
     for (const auto &g : gr) {
         if (!g.whole || g.nbatch == 0) continue;
-        rp_transcripts tr;
-        tr.label = g.label;
-        tr.label_len = g.label_len;
-        rc = rp_verify_dev_locked(c, g.n, g.m, g.nbatch, g.d_proofs, g.proof_len, g.d_coms, tr, d_rng64 + 64 * g.gp0, d_verdict + g.gp0, nullptr, s);
+        rc = rp_verify_dev_locked(c, g.n, g.m, g.nbatch, g.d_proofs, g.proof_len, g.d_coms, rp_mix_transcripts(g), d_rng64 + 64 * g.gp0, d_verdict + g.gp0,
+                                  nullptr, s);
         if (rc) return rc;
         HIPCHK(c, hipMemsetAsync(d_gst + 4 * g.gp0, 0xff, 4 * g.nbatch, s));
     }
@@ -5511,18 +5536,37 @@ static int rp_mix_dev_locked(bpgpu_ctx *c, std::vector<rp_mix_group> &gr, size_t
         rc = arena_reserve(c, ap.total);
         if (rc) return rc;
         char *a = c->arena;
+        // Where the group's transcripts start, and the form of the front end's transcript role.  A label: always the per-shape script.  The
+        // caller's states: rangeproof_domain_sep(n, m) is applied on the device (part of the script then); one state for the group travels in
+        // `init` like a label's; one state per proof with all of them at one STROBE position: the script compiled for that position, the
+        // sponge words from ts_in; positions that differ (or option transcript_script = 0): the byte-wise replay.
         rp_strobe_init init;
-        make_strobe_init(init, g.label, g.label_len, g.n, g.m);
-        const rp_script_hdr *d_script = nullptr;   // (every proof of a group starts from its label's state: always the per-shape script)
-        rc = script_for(c, s, sh.n, sh.m, sh.k, init, false, &d_script);
-        if (rc) return rc;
+        const uint32_t *ts_in = nullptr;
+        if (!g.h_ts) make_strobe_init(init, g.label, g.label_len, g.n, g.m);
+        else if (!g.ts_stride) strobe_init_from_state(init, g.h_ts);
+        else {
+            memset(&init, 0, sizeof init);
+            init.pos = g.u_pos, init.pos_begin = g.u_pos_begin, init.cur_flags = g.u_flags;   // (meaningful when ts_uniform only)
+            ts_in = (const uint32_t *)g.d_ts_in;
+        }
+        const bool replay = g.h_ts && (c->no_script || (g.ts_stride && !g.ts_uniform));
+        const rp_script_hdr *d_script = nullptr;
+        if (!replay) {
+            rc = script_for(c, s, sh.n, sh.m, sh.k, init, g.h_ts != nullptr, &d_script);
+            if (rc) return rc;
+        }
         HIPCHK(c, hipMemsetAsync(a + off_st, 0, g.nbatch * 4, s));
         const uint32_t n_tr = (sh.nproofs + RP_BLOCK - 1) / RP_BLOCK, n_pt = (sh.nproofs * sh.U + RP_BLOCK - 1) / RP_BLOCK;
         // rng64 / weights64 rows are indexed by the proof's position in the CALL: this group's slice starts at gp0.  Soundness rests on it --
         // a slice taken at 0 would hand (group 0, proof i) and (group 1, proof i) the same weight
-        LAUNCH(c, s, "rlc_mix_front", k_rlc_mix_front, n_tr + n_pt, RP_BLOCK, sh, init, n_tr, (const uint8_t *)g.d_proofs, (const uint8_t *)g.d_coms,
-               (const uint8_t *)d_rng64 + 64 * g.gp0, (const uint8_t *)d_weights64 + 64 * g.gp0, (uint32_t *)(a + off_fields), (uint32_t *)(a + off_st), c->prm,
-               lg_m, (uint32_t *)(a + off_usc), d_script);
+        if (replay)
+            LAUNCH(c, s, "rlc_mix_front", k_rlc_mix_front_replay, n_tr + n_pt, RP_BLOCK, sh, init, n_tr, (const uint8_t *)g.d_proofs, (const uint8_t *)g.d_coms,
+                   (const uint8_t *)d_rng64 + 64 * g.gp0, (const uint8_t *)d_weights64 + 64 * g.gp0, (uint32_t *)(a + off_fields), (uint32_t *)(a + off_st),
+                   c->prm, lg_m, (uint32_t *)(a + off_usc), ts_in, (uint32_t *)g.d_ts_out);
+        else
+            LAUNCH(c, s, "rlc_mix_front", k_rlc_mix_front, n_tr + n_pt, RP_BLOCK, sh, init, n_tr, (const uint8_t *)g.d_proofs, (const uint8_t *)g.d_coms,
+                   (const uint8_t *)d_rng64 + 64 * g.gp0, (const uint8_t *)d_weights64 + 64 * g.gp0, (uint32_t *)(a + off_fields), (uint32_t *)(a + off_st),
+                   c->prm, lg_m, (uint32_t *)(a + off_usc), d_script, ts_in, (uint32_t *)g.d_ts_out);
         LAUNCH(c, s, "rlc_mix_weigh", k_rlc_mix_weigh, (uint32_t)(nt / 64), 64, mg, sh, c->prm, (const uint8_t *)g.d_proofs, (const uint8_t *)g.d_coms,
                (const uint32_t *)(a + off_st), (const uint32_t *)(a + off_fields), (const uint32_t *)(a + off_usc), (uint32_t *)d_csc, (uint32_t *)d_cpt,
                (uint32_t *)d_gst, (unsigned long long *)d_acc);
@@ -5539,13 +5583,18 @@ static int rp_mix_dev_locked(bpgpu_ctx *c, std::vector<rp_mix_group> &gr, size_t
     return BPGPU_OK;
 }
 
-extern "C" int bpgpu_rangeproof_verify_rlc_mixed(bpgpu_ctx *c, size_t ngroups, const size_t *n, const size_t *m, const size_t *nbatch, const size_t *proof_len,
-                                                 const uint8_t *proofs, const uint8_t *commitments, const uint8_t *const *labels, const size_t *label_lens,
-                                                 const uint8_t *rng64, const uint8_t *weights64, uint8_t *verdict, uint8_t *batch_out) {
-    if (!c || (ngroups && (!n || !m || !nbatch || !proof_len || !labels || !label_lens))) return BPGPU_ERR_INVALID_ARG;
+// The host form of the mixed-shape combination: every group from its label (labels / label_lens), or -- transcripts != nullptr -- from the
+// caller's states (bpgpu_rangeproof_verify_rlc_mixed_ts: transcripts lie group after group, one state where transcript_stride[g] == 0, else
+// nbatch[g]; transcripts_out: optional total x 208 bytes).
+static int rp_mix_host_call(bpgpu_ctx *c, size_t ngroups, const size_t *n, const size_t *m, const size_t *nbatch, const size_t *proof_len, const uint8_t *proofs,
+                            const uint8_t *commitments, const uint8_t *const *labels, const size_t *label_lens, const uint8_t *transcripts,
+                            const size_t *transcript_stride, const uint8_t *rng64, const uint8_t *weights64, uint8_t *verdict, uint8_t *batch_out,
+                            uint8_t *transcripts_out) {
+    const bool ts = transcripts != nullptr;
+    const size_t TS = BPGPU_TRANSCRIPT_BYTES;
     size_t total = 0, bytes_p = 0, bytes_c = 0;
     for (size_t g = 0; g < ngroups; g++) {
-        if (label_lens[g] && !labels[g]) return BPGPU_ERR_INVALID_ARG;
+        if (!ts && label_lens[g] && !labels[g]) return BPGPU_ERR_INVALID_ARG;
         if (nbatch[g] > RM_MAX_TERMS || proof_len[g] > 0xffffffu || m[g] > 0xffffu) return fail(c, BPGPU_ERR_INVALID_ARG, "batch too large");
         total += nbatch[g];
         bytes_p += nbatch[g] * proof_len[g];
@@ -5559,24 +5608,43 @@ extern "C" int bpgpu_rangeproof_verify_rlc_mixed(bpgpu_ctx *c, size_t ngroups, c
     if (total > RM_MAX_TERMS) return fail(c, BPGPU_ERR_INVALID_ARG, "batch too large");
     std::lock_guard<std::mutex> lk(c->mu);
     std::vector<rp_mix_group> gr;
+    const uint8_t *src_t = transcripts;
     for (size_t g = 0, gp = 0; g < ngroups; g++) {   // (every refusal before the context is entered)
-        if (nbatch[g] == 0) continue;
-        rp_mix_group mg{n[g], m[g], nbatch[g], proof_len[g], 0, gp, 0, nullptr, nullptr, labels[g], label_lens[g], false};
-        const int rcc = rp_mix_classify(c, n[g], m[g], proof_len[g], &mg.k, &mg.whole);
-        if (rcc) return rcc;
-        gr.push_back(mg);
-        gp += nbatch[g];
+        const size_t nst = ts ? (transcript_stride[g] ? nbatch[g] : 1) : 0;   // (a group without proofs still has its state(s) in the buffer)
+        if (ts && transcript_stride[g] != 0 && transcript_stride[g] != TS)
+            return fail(c, BPGPU_ERR_INVALID_ARG, "transcript_stride of group %zu neither 0 nor BPGPU_TRANSCRIPT_BYTES", g);
+        if (nbatch[g]) {
+            rp_mix_group mg{n[g], m[g], nbatch[g], proof_len[g], 0, gp, 0, nullptr, nullptr, ts ? nullptr : labels[g], ts ? 0 : label_lens[g], false};
+            if (ts) {
+                mg.h_ts = src_t;
+                mg.ts_stride = transcript_stride[g];
+                mg.u_pos = src_t[200], mg.u_pos_begin = src_t[201], mg.u_flags = src_t[202];
+                mg.ts_uniform = true;
+                for (size_t b = 0; b < nst; b++) {
+                    const uint8_t *st = src_t + b * TS;
+                    if (!ts_state_ok(st)) return fail(c, BPGPU_ERR_INVALID_ARG, "malformed transcript state %zu of group %zu", b, g);
+                    if (st[200] != src_t[200] || st[201] != src_t[201] || st[202] != src_t[202]) mg.ts_uniform = false;
+                }
+            }
+            const int rcc = rp_mix_classify(c, n[g], m[g], proof_len[g], &mg.k, &mg.whole);
+            if (rcc) return rcc;
+            gr.push_back(mg);
+            gp += nbatch[g];
+        }
+        src_t += nst * TS;
     }
     HIPCHK(c, hipSetDevice(c->device));
-    // staging: per group its proofs and commitments; then every proof's rng bytes and weights; then the outputs
-    std::vector<size_t> off(2 * ngroups, 0);
+    // staging: per group its proofs and commitments (and its states, where it has one per proof); then every proof's rng bytes and weights;
+    // then the outputs
+    std::vector<size_t> off(3 * ngroups, 0);
     size_t in = 0;
     for (size_t g = 0; g < ngroups; g++) {
-        off[2 * g] = in, in += nbatch[g] ? align_up(nbatch[g] * proof_len[g] + 64) : 0;
-        off[2 * g + 1] = in, in += nbatch[g] ? align_up(nbatch[g] * m[g] * 32 + 64) : 0;
+        off[3 * g] = in, in += nbatch[g] ? align_up(nbatch[g] * proof_len[g] + 64) : 0;
+        off[3 * g + 1] = in, in += nbatch[g] ? align_up(nbatch[g] * m[g] * 32 + 64) : 0;
+        off[3 * g + 2] = in, in += (ts && transcript_stride[g]) ? align_up(nbatch[g] * TS) : 0;
     }
     const size_t off_r = in, off_w = off_r + (rng64 ? align_up(total * 64) : 0), sz_in = off_w + (weights64 ? align_up(total * 64) : 0);
-    const size_t sz_v = align_up(total), sz_b = align_up(64), sz_out = sz_v + sz_b;
+    const size_t sz_v = align_up(total), sz_b = align_up(64), sz_to = transcripts_out ? align_up(total * TS) : 0, sz_out = sz_v + sz_b + sz_to;
     hipStream_t s = c->stream;
     int rc = ctx_enter(c, s);
     if (rc) return rc;
@@ -5590,12 +5658,17 @@ extern "C" int bpgpu_rangeproof_verify_rlc_mixed(bpgpu_ctx *c, size_t ngroups, c
     for (size_t g = 0, gi = 0; g < ngroups; g++) {
         const size_t nb = nbatch[g];
         if (nb == 0) continue;
-        memcpy(h + off[2 * g], src_p, nb * proof_len[g]);
-        if (m[g]) memcpy(h + off[2 * g + 1], src_c, nb * m[g] * 32);
+        memcpy(h + off[3 * g], src_p, nb * proof_len[g]);
+        if (m[g]) memcpy(h + off[3 * g + 1], src_c, nb * m[g] * 32);
         src_p += nb * proof_len[g];
         src_c += nb * m[g] * 32;
-        gr[gi].d_proofs = d + off[2 * g];
-        gr[gi].d_coms = d + off[2 * g + 1];
+        gr[gi].d_proofs = d + off[3 * g];
+        gr[gi].d_coms = d + off[3 * g + 1];
+        if (ts && transcript_stride[g]) {
+            memcpy(h + off[3 * g + 2], gr[gi].h_ts, nb * TS);
+            gr[gi].d_ts_in = d + off[3 * g + 2];
+        }
+        if (transcripts_out) gr[gi].d_ts_out = d + sz_in + sz_v + sz_b + gr[gi].gp0 * TS;
         gi++;
     }
     if (rng64) memcpy(h + off_r, rng64, total * 64);
@@ -5617,12 +5690,11 @@ extern "C" int bpgpu_rangeproof_verify_rlc_mixed(bpgpu_ctx *c, size_t ngroups, c
         if (rc) return rc;
         for (const auto &g : gr) {
             if (g.whole) continue;
-            rp_transcripts tr;
-            tr.label = g.label;
-            tr.label_len = g.label_len;
-            rc = rp_verify_dev_locked(c, g.n, g.m, g.nbatch, g.d_proofs, g.proof_len, g.d_coms, tr, d_rng_used + 64 * g.gp0, d_v + g.gp0, nullptr, s);
+            rc = rp_verify_dev_locked(c, g.n, g.m, g.nbatch, g.d_proofs, g.proof_len, g.d_coms, rp_mix_transcripts(g), d_rng_used + 64 * g.gp0, d_v + g.gp0,
+                                      nullptr, s);
             if (rc) break;
         }
+        // (the per-proof path wrote the same advanced states again: byte for byte those of bpgpu_rangeproof_verify_batch_ts either way)
         if (!rc && hipMemcpyAsync(h_out, d_v, sz_v, hipMemcpyDeviceToHost, s) != hipSuccess) rc = fail(c, BPGPU_ERR_HIP, "D2H copy failed");
         rc2 = ctx_leave(c, s);
         rc3 = host_wait(c, s);
@@ -5631,7 +5703,67 @@ extern "C" int bpgpu_rangeproof_verify_rlc_mixed(bpgpu_ctx *c, size_t ngroups, c
     }
     memcpy(verdict, h_out, total);
     if (batch_out) memcpy(batch_out, h_out + sz_v, 33);
+    if (transcripts_out) memcpy(transcripts_out, h_out + sz_v + sz_b, total * TS);
     return BPGPU_OK;
+}
+
+extern "C" int bpgpu_rangeproof_verify_rlc_mixed(bpgpu_ctx *c, size_t ngroups, const size_t *n, const size_t *m, const size_t *nbatch, const size_t *proof_len,
+                                                 const uint8_t *proofs, const uint8_t *commitments, const uint8_t *const *labels, const size_t *label_lens,
+                                                 const uint8_t *rng64, const uint8_t *weights64, uint8_t *verdict, uint8_t *batch_out) {
+    if (!c || (ngroups && (!n || !m || !nbatch || !proof_len || !labels || !label_lens))) return BPGPU_ERR_INVALID_ARG;
+    return rp_mix_host_call(c, ngroups, n, m, nbatch, proof_len, proofs, commitments, labels, label_lens, nullptr, nullptr, rng64, weights64, verdict, batch_out,
+                            nullptr);
+}
+
+extern "C" int bpgpu_rangeproof_verify_rlc_mixed_ts(bpgpu_ctx *c, size_t ngroups, const size_t *n, const size_t *m, const size_t *nbatch, const size_t *proof_len,
+                                                    const uint8_t *proofs, const uint8_t *commitments, const uint8_t *transcripts,
+                                                    const size_t *transcript_stride, const uint8_t *rng64, const uint8_t *weights64, uint8_t *verdict,
+                                                    uint8_t *batch_out, uint8_t *transcripts_out) {
+    if (!c || (ngroups && (!n || !m || !nbatch || !proof_len || !transcripts || !transcript_stride))) return BPGPU_ERR_INVALID_ARG;
+    if (!ngroups) {
+        if (batch_out) memset(batch_out, 0, 33);
+        return BPGPU_OK;
+    }
+    return rp_mix_host_call(c, ngroups, n, m, nbatch, proof_len, proofs, commitments, nullptr, nullptr, transcripts, transcript_stride, rng64, weights64, verdict,
+                            batch_out, transcripts_out);
+}
+
+// ---- the one-shape combination on the callers' own transcripts (rp_verify_dev_locked with rlc = true and caller states) -----------------
+extern "C" int bpgpu_rangeproof_verify_rlc_ts(bpgpu_ctx *c, size_t n, size_t m, size_t nbatch, const uint8_t *proofs, size_t proof_len, const uint8_t *commitments,
+                                              const uint8_t *transcripts, size_t transcript_stride, const uint8_t *rng64, const uint8_t *weights64,
+                                              uint8_t *verdict, uint8_t *batch_out, uint8_t *transcripts_out) {
+    if (!c) return BPGPU_ERR_INVALID_ARG;
+    if (!transcripts || (transcript_stride != 0 && transcript_stride != BPGPU_TRANSCRIPT_BYTES))
+        return fail(c, BPGPU_ERR_INVALID_ARG, "transcripts missing, or transcript_stride neither 0 nor BPGPU_TRANSCRIPT_BYTES");
+    rp_transcripts tr;
+    if (!transcript_stride) {
+        if (!ts_state_ok(transcripts)) return fail(c, BPGPU_ERR_INVALID_ARG, "malformed transcript state");
+        tr.shared_ts = transcripts;
+    } else if (nbatch) {   // the states are in host memory: all at one STROBE position -> the per-shape script, as the pool's combining queue decides it
+        tr.ts_uniform = true;
+        tr.u_pos = transcripts[200], tr.u_pos_begin = transcripts[201], tr.u_flags = transcripts[202];
+        for (size_t b = 0; b < nbatch; b++) {
+            const uint8_t *st = transcripts + b * BPGPU_TRANSCRIPT_BYTES;
+            if (!ts_state_ok(st)) return fail(c, BPGPU_ERR_INVALID_ARG, "malformed transcript state %zu", b);
+            if (st[200] != transcripts[200] || st[201] != transcripts[201] || st[202] != transcripts[202]) tr.ts_uniform = false;
+        }
+    }
+    uint8_t bo[33];
+    return rp_host_call(c, n, m, nbatch, proofs, proof_len, commitments, tr, transcript_stride ? transcripts : nullptr, rng64, verdict, nullptr, transcripts_out,
+                        true, weights64, batch_out ? batch_out : bo);
+}
+
+extern "C" int bpgpu_rangeproof_verify_rlc_ts_dev(bpgpu_ctx *c, size_t n, size_t m, size_t nbatch, const void *d_proofs, size_t proof_len,
+                                                  const void *d_commitments, const uint8_t *shared_transcript, const void *d_transcripts, const void *d_rng64,
+                                                  const void *d_weights64, void *d_verdict, void *d_batch_out, void *d_transcripts_out, void *stream) {
+    if (!c) return BPGPU_ERR_INVALID_ARG;
+    if ((shared_transcript != nullptr) == (d_transcripts != nullptr))
+        return fail(c, BPGPU_ERR_INVALID_ARG, "give exactly one of shared_transcript / d_transcripts");
+    rp_transcripts tr;
+    tr.shared_ts = shared_transcript;
+    tr.d_ts_in = d_transcripts;
+    tr.d_ts_out = d_transcripts_out;
+    return rp_dev_call(c, n, m, nbatch, d_proofs, proof_len, d_commitments, tr, d_rng64, d_verdict, nullptr, stream, true, d_weights64, d_batch_out);
 }
 
 namespace {
@@ -5643,9 +5775,15 @@ struct rp_mix_call {
     const size_t *label_lens;
     const uint8_t *rng64, *weights64;
     uint8_t *verdict, *batch_out;
+    const uint8_t *transcripts;   // != nullptr: the _ts form (labels unused)
+    const size_t *transcript_stride;
+    uint8_t *transcripts_out;
 };
 int rp_mix_call_run(bpgpu_ctx *c, void *arg) {
     const rp_mix_call *a = (const rp_mix_call *)arg;
+    if (a->transcripts)
+        return bpgpu_rangeproof_verify_rlc_mixed_ts(c, a->ngroups, a->n, a->m, a->nbatch, a->proof_len, a->proofs, a->commitments, a->transcripts,
+                                                    a->transcript_stride, a->rng64, a->weights64, a->verdict, a->batch_out, a->transcripts_out);
     return bpgpu_rangeproof_verify_rlc_mixed(c, a->ngroups, a->n, a->m, a->nbatch, a->proof_len, a->proofs, a->commitments, a->labels, a->label_lens, a->rng64,
                                              a->weights64, a->verdict, a->batch_out);
 }
@@ -5662,6 +5800,22 @@ extern "C" int bpgpu_pool_rangeproof_verify_rlc_mixed(bpgpu_pool *pool, size_t n
         if (batch_out) memset(batch_out, 0, 33);
         return BPGPU_OK;
     }
-    rp_mix_call a{ngroups, n, m, nbatch, proof_len, proofs, commitments, labels, label_lens, rng64, weights64, verdict, batch_out};
+    rp_mix_call a{ngroups, n, m, nbatch, proof_len, proofs, commitments, labels, label_lens, rng64, weights64, verdict, batch_out, nullptr, nullptr, nullptr};
+    return bpgpu_internal_pool_run_on_context(pool, total, verdict, rp_mix_call_run, &a);
+}
+
+extern "C" int bpgpu_pool_rangeproof_verify_rlc_mixed_ts(bpgpu_pool *pool, size_t ngroups, const size_t *n, const size_t *m, const size_t *nbatch,
+                                                         const size_t *proof_len, const uint8_t *proofs, const uint8_t *commitments, const uint8_t *transcripts,
+                                                         const size_t *transcript_stride, const uint8_t *rng64, const uint8_t *weights64, uint8_t *verdict,
+                                                         uint8_t *batch_out, uint8_t *transcripts_out) {
+    if (!pool || (ngroups && (!n || !m || !nbatch || !proof_len || !transcripts || !transcript_stride))) return BPGPU_ERR_INVALID_ARG;
+    size_t total = 0;
+    for (size_t g = 0; g < ngroups; g++) total += nbatch[g];
+    if (total == 0) {   // (as the context form: nothing to combine)
+        if (batch_out) memset(batch_out, 0, 33);
+        return BPGPU_OK;
+    }
+    rp_mix_call a{ngroups, n, m, nbatch, proof_len, proofs, commitments, nullptr, nullptr, rng64, weights64, verdict, batch_out, transcripts, transcript_stride,
+                  transcripts_out};
     return bpgpu_internal_pool_run_on_context(pool, total, verdict, rp_mix_call_run, &a);
 }

@@ -16,9 +16,13 @@ __global__ void __launch_bounds__(64) k_rlc_mix_draw(uint32_t n, rm_key key, uin
 // per-proof scalars times the proof's weight, the U coefficients as plain scalars into uniq_sc, lane = proof  ||  [n_tr, ..) the
 // decode of the proof's and the commitments' points, lane = point: an undecodable one stops its proof (the decoded point itself is
 // dropped: the call's one MSM decodes the encodings of the proofs that are left)
+// ts_in / ts_out (bpgpu_rangeproof_verify_rlc_mixed_ts): one caller-supplied start state per proof, all at the position the script was
+// compiled for, and where the advanced states go; both null for a group that starts from its label.  (States at differing positions:
+// k_rlc_mix_front_replay, k_rlc_mix_ts.hip.)
 __global__ void __launch_bounds__(RP_BLOCK) k_rlc_mix_front(rp_shape sh, rp_strobe_init init, uint32_t n_tr, const uint8_t *proofs, const uint8_t *commitments,
                                                             const uint8_t *rng64, const uint8_t *rho64, uint32_t *fields, uint32_t *status, fb_params prm,
-                                                            uint32_t lg_m, uint32_t *uniq_sc, const rp_script_hdr *script) {
+                                                            uint32_t lg_m, uint32_t *uniq_sc, const rp_script_hdr *script, const uint32_t *ts_in,
+                                                            uint32_t *ts_out) {
     __shared__ uint32_t lds[50 * RP_BLOCK];   // sponge states, word-major: word w of lane t at w*RP_BLOCK + t
     rp_seg_tab segs;
     segs.n = 0;
@@ -27,10 +31,9 @@ __global__ void __launch_bounds__(RP_BLOCK) k_rlc_mix_front(rp_shape sh, rp_stro
         kstate st;
         st.w = lds + threadIdx.x;
         st.stride = RP_BLOCK;
-        if (p < sh.nproofs) {
-            rp_transcript_scripted(p, sh, init, st, rp_resolve(p, sh, proofs, commitments, rng64, segs), script, fields, status);
-            rp_expand_a_thread<true>(p, sh, prm, lg_m, fields, uniq_sc, (fb_digit *)nullptr, status, rho64);
-        }
+        if (p < sh.nproofs)
+            rm_front_thread<true>(p, sh, init, st, rp_resolve(p, sh, proofs, commitments, rng64, segs), script, fields, status, prm, lg_m, uniq_sc, rho64, 0u,
+                                  ts_in, ts_out);
     } else {
         const uint32_t t = (blockIdx.x - n_tr) * RP_BLOCK + threadIdx.x;
         if (t < sh.nproofs * sh.U) rp_points_thread<false>(t, sh, rp_resolve(t / sh.U, sh, proofs, commitments, nullptr, segs), (ge_cached *)nullptr, status);

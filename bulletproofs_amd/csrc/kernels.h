@@ -94,9 +94,11 @@ __global__ void k_lin_rlc_reduce(uint32_t nrows, const unsigned long long *acc, 
 __global__ void k_lin_rlc_verdict(uint32_t n, const uint32_t *status, const uint32_t *enc, const uint8_t *msm_status, uint8_t *verdict, uint8_t *batch_out);
 // k_rlc_mix.hip
 __global__ void k_rlc_mix_draw(uint32_t n, rm_key key, uint32_t dom, uint32_t *out);
-__global__ void k_rlc_mix_front(rp_shape sh, rp_strobe_init init, uint32_t n_tr, const uint8_t *proofs, const uint8_t *commitments, const uint8_t *rng64, const uint8_t *rho64, uint32_t *fields, uint32_t *status, fb_params prm, uint32_t lg_m, uint32_t *uniq_sc, const rp_script_hdr *script);
+__global__ void k_rlc_mix_front(rp_shape sh, rp_strobe_init init, uint32_t n_tr, const uint8_t *proofs, const uint8_t *commitments, const uint8_t *rng64, const uint8_t *rho64, uint32_t *fields, uint32_t *status, fb_params prm, uint32_t lg_m, uint32_t *uniq_sc, const rp_script_hdr *script, const uint32_t *ts_in, uint32_t *ts_out);
 __global__ void k_rlc_mix_weigh(rm_group gr, rp_shape sh, fb_params prm, const uint8_t *proofs, const uint8_t *commitments, const uint32_t *status, const uint32_t *fields, const uint32_t *uniq_sc, uint32_t *comb_sc, uint32_t *comb_pt, uint32_t *gstatus, unsigned long long *acc);
 __global__ void k_rlc_mix_verdict(uint32_t n, const uint32_t *gstatus, const uint32_t *res, const uint8_t *rst, uint8_t *verdict, uint8_t *batch_out);
+// k_rlc_mix_ts.hip
+__global__ void k_rlc_mix_front_replay(rp_shape sh, rp_strobe_init init, uint32_t n_tr, const uint8_t *proofs, const uint8_t *commitments, const uint8_t *rng64, const uint8_t *rho64, uint32_t *fields, uint32_t *status, fb_params prm, uint32_t lg_m, uint32_t *uniq_sc, const uint32_t *ts_in, uint32_t *ts_out);
 // k_r1cs_prove.hip
 __global__ void k_r1p_inputs(uint32_t nthreads, r1p_shape sh, const uint8_t *v, const uint8_t *vb, const uint8_t *freev, uint32_t *vrows, uint32_t *status);
 __global__ void k_r1p_rng(r1p_shape sh, uint32_t *ts, const uint32_t *vout, const uint8_t *vb, const uint8_t *rng32, uint32_t *rnd);

@@ -59,6 +59,22 @@ BP_HD void rm_draw_thread(uint32_t gp, const rm_key &key, uint32_t dom, uint32_t
     for (int i = 0; i < 16; i++) out[16 * (uint64_t)gp + i] = w16[i];
 }
 
+// lane = proof p of one group: launch 1's transcript role, then the per-proof scalars times the proof's weight with the U coefficients as
+// plain scalars.  The two forms k_rp_stage1<SCRIPTED> has:
+//   SCRIPTED  the per-shape script from `init`'s position -- a label's state (ts_in == nullptr), or one caller-supplied state per proof
+//             (ts_in) when every state of the group sits at init's (pos, pos_begin, cur_flags) and the script was compiled for it with the
+//             domain separator: only the 50 sponge words differ per lane
+//   else      the byte-wise replay (rp_transcript_thread with ts_flags = BP_TS_DOMSEP) from ts_in[p], whatever its position
+// ts_out (optional) gets the advanced state on every path of either form (rp_ts_passthrough / rp_ts_emit).
+template <bool SCRIPTED>
+BP_HD void rm_front_thread(uint32_t p, const rp_shape &sh, const rp_strobe_init &init, kstate st, const rp_inputs &in, const rp_script_hdr *script,
+                           uint32_t *fields, uint32_t *status, const fb_params &prm, uint32_t lg_m, uint32_t *uniq_sc, const uint8_t *rho64,
+                           uint32_t ts_flags, const uint32_t *ts_in, uint32_t *ts_out) {
+    if (SCRIPTED) rp_transcript_scripted(p, sh, init, st, in, script, fields, status, ts_out, ts_in);
+    else rp_transcript_thread(p, sh, init, st, in, fields, status, ts_flags, ts_in, ts_out);
+    rp_expand_a_thread<true>(p, sh, prm, lg_m, fields, uniq_sc, (fb_digit *)nullptr, status, rho64);
+}
+
 // lane tid = term * nstride + proof.  Unique terms (term < U) go to the combined list and the lane is done (returns 0).  Term U: returns 1
 // with the weighted B_blinding / B coefficients in r0 / r1 (zero for a proof that stopped and for the padding).  Terms above: returns 2 --
 // the caller forms quad `q`'s exponents.  `p` is the lane's proof, `live` whether it contributes.

@@ -309,6 +309,56 @@ int bpgpu_rangeproof_verify_rlc_mixed(bpgpu_ctx *ctx, size_t ngroups, const size
                                       const uint8_t *const *labels, const size_t *label_lens, const uint8_t *rng64,
                                       const uint8_t *weights64, uint8_t *verdict, uint8_t *batch_out);
 
+/* Both combined checks on the CALLERS' OWN transcripts (the full `&mut Transcript` of mod.rs:345-353, as bpgpu_rangeproof_verify_batch_ts;
+ * ADDITIONAL entry points): every proof starts from a Merlin state the application has already bound to its transaction or session.
+ *   transcripts, transcript_stride : as bpgpu_rangeproof_verify_batch_ts -- stride 0: ONE 208-byte state for the batch; stride
+ *                 BPGPU_TRANSCRIPT_BYTES: nbatch states, which may sit at differing STROBE positions.  rangeproof_domain_sep(n, m) is
+ *                 applied on the device to the caller's state.  A malformed state is BPGPU_ERR_INVALID_ARG before anything runs.
+ *   transcripts_out : optional nbatch x 208 bytes, byte for byte what bpgpu_rangeproof_verify_batch_ts returns per proof (mod.rs:345-353:
+ *                 the end state; the input state back for FormatError and the parameter rejections; the state at the stopping message for
+ *                 an identity A / S / T_1 / T_2 / L_i / R_i; the state at `w` when n m != 2^k) -- whether R was the identity or the call
+ *                 fell back to the per-proof path
+ *   rng64, weights64, verdict, batch_out : as bpgpu_rangeproof_verify_rlc; the fallback re-verifies through the per-proof path with the
+ *                 same transcripts and rng bytes, so the verdicts are exactly those of bpgpu_rangeproof_verify_batch_ts
+ * With the states in host memory the call sees whether all of them sit at one (pos, pos_begin, cur_flags): then the per-shape script
+ * (compiled for that position, with the domain separator) replays them and only the 50 sponge words differ per lane; else the byte-wise
+ * replay does.  A single state equal to bpgpu_transcript_new(label) gives the R of the label entry point for the same rng64 / weights64.
+ * `_dev`: `shared_transcript` is a HOST pointer to one state (or NULL), `d_transcripts` a device pointer to nbatch states (or NULL, byte-wise
+ * replay); exactly one of the two, as bpgpu_rangeproof_verify_batch_ts_dev; undecided verdicts are BPGPU_VERDICT_UNDECIDED, as
+ * bpgpu_rangeproof_verify_rlc_dev. */
+int bpgpu_rangeproof_verify_rlc_ts(bpgpu_ctx *ctx, size_t n, size_t m, size_t nbatch,
+                                   const uint8_t *proofs, size_t proof_len, const uint8_t *commitments,
+                                   const uint8_t *transcripts, size_t transcript_stride, const uint8_t *rng64,
+                                   const uint8_t *weights64, uint8_t *verdict, uint8_t *batch_out, uint8_t *transcripts_out);
+int bpgpu_rangeproof_verify_rlc_ts_dev(bpgpu_ctx *ctx, size_t n, size_t m, size_t nbatch,
+                                       const void *d_proofs, size_t proof_len, const void *d_commitments,
+                                       const uint8_t *shared_transcript, const void *d_transcripts, const void *d_rng64,
+                                       const void *d_weights64, void *d_verdict, void *d_batch_out, void *d_transcripts_out,
+                                       void *stream);
+/* bpgpu_rangeproof_verify_rlc_mixed on the callers' own transcripts (mod.rs:345-353), group by group:
+ *   transcript_stride : ngroups values: 0 = one state for group g, BPGPU_TRANSCRIPT_BYTES = nbatch[g] states
+ *   transcripts     : group after group: 208 bytes where transcript_stride[g] == 0, else nbatch[g] x 208 (a group with nbatch[g] == 0
+ *                     still has its one state, or none, in the buffer)
+ *   transcripts_out : optional total x 208 bytes in call order, per proof what bpgpu_rangeproof_verify_batch_ts returns (above)
+ *   rng64, weights64 : rows indexed by the proof's position in the CALL, NULL = drawn by the library, exactly as the label form
+ *   verdict, batch_out : as the label form; the fallback, and the per-shape call of a group rejected as a whole, get the group's
+ *                     transcripts: every verdict is the one bpgpu_rangeproof_verify_batch_ts gives, group by group, with the same rng64
+ * The front end decides per group: one state, or states at one position -> the script for that position; positions that differ within
+ * the group -> the byte-wise replay.  A group whose single state equals bpgpu_transcript_new(label) contributes to R exactly what it
+ * does through bpgpu_rangeproof_verify_rlc_mixed.
+ * Rate (profiles/rlc_ts_rate.json: tools/rlc_mixed_rate.py --transcripts per-proof, one MI355X, the three forms interleaved, medians of
+ * 50 calls, two runs within 1.2 % on the block and 3.5 % on one shape): a block of 1 024 proofs at n = 64, m = 1 .. 16 -- the label form
+ * 3.54 ms (0.29 M/s), this call with one state per proof at differing positions 8.9 ms (0.115 M/s), bpgpu_rangeproof_verify_batch_ts group
+ * by group 9.6 ms (0.107 M/s); 4 096 proofs of (64, 1) -- 1.70 / 2.22 / 2.03 ms (2.41 / 1.84 / 2.02 M/s).  The byte-wise replay is what it
+ * costs over the label form (2.5x, 1.3x); with one state per group there is none and the call costs what the label form costs.  Against
+ * the per-proof path this call is 7 - 9 % ahead on the mixed block and 9 % behind on the one wide shape (6 % and 10 % behind with one
+ * state per group): at these two sizes there is no block size from which it is ahead throughout, and what it saves is the table walk per
+ * shape, not the transcript. */
+int bpgpu_rangeproof_verify_rlc_mixed_ts(bpgpu_ctx *ctx, size_t ngroups, const size_t *n, const size_t *m, const size_t *nbatch,
+                                         const size_t *proof_len, const uint8_t *proofs, const uint8_t *commitments,
+                                         const uint8_t *transcripts, const size_t *transcript_stride, const uint8_t *rng64,
+                                         const uint8_t *weights64, uint8_t *verdict, uint8_t *batch_out, uint8_t *transcripts_out);
+
 /* ---- stand-alone inner-product proofs -------------------------------------------
  * nbatch independent calls of
  *   InnerProductProof::from_bytes(proof)?.verify(n, &mut Transcript::new(label), G_factors, H_factors, &P, &Q, &G, &H)
@@ -917,6 +967,12 @@ int bpgpu_pool_rangeproof_verify_rlc_mixed(bpgpu_pool *pool, size_t ngroups, con
                                            const size_t *proof_len, const uint8_t *proofs, const uint8_t *commitments,
                                            const uint8_t *const *labels, const size_t *label_lens, const uint8_t *rng64,
                                            const uint8_t *weights64, uint8_t *verdict, uint8_t *batch_out);
+/* bpgpu_rangeproof_verify_rlc_mixed_ts through the pool (same arguments; the callers' transcripts of mod.rs:345-353): the whole call runs
+ * on the next device, blocking; any thread may call it. */
+int bpgpu_pool_rangeproof_verify_rlc_mixed_ts(bpgpu_pool *pool, size_t ngroups, const size_t *n, const size_t *m, const size_t *nbatch,
+                                              const size_t *proof_len, const uint8_t *proofs, const uint8_t *commitments,
+                                              const uint8_t *transcripts, const size_t *transcript_stride, const uint8_t *rng64,
+                                              const uint8_t *weights64, uint8_t *verdict, uint8_t *batch_out, uint8_t *transcripts_out);
 /* The combining queue's timeline (set option "combine_trace" = ring size first): one JSON object per line -- every launch chain (opened,
  * sealed, issue begin / end, completion seen, delivery begin / end, buffer free; CLOCK_MONOTONIC ns) and every eighth request per thread
  * (submitted, slots reserved, inputs written, delivered, woken).  tools/combine_timeline.py turns it into "where does a request wait". */

@@ -310,10 +310,12 @@ class RangeProof {
         return out;
     }
 
-    // Same verdicts through the batch-combined check (bpgpu_rangeproof_verify_rlc, no counterpart in the crate): one
+    // Same verdicts through the batch-combined check (bpgpu_rangeproof_verify_rlc / _rlc_ts, no counterpart in the crate): one
     // identity test for the whole batch when every proof verifies, per-proof re-verification inside the call when
     // not.  weights64 = nullptr draws the combination weights from the OS CSPRNG.
-    // This entry point replays every proof's transcript from its label: `transcript` must be a fresh Transcript(label).
+    // A fresh Transcript(label) is replayed from its label; a transcript the caller has already bound to its transaction or session
+    // (the `&mut Transcript` of mod.rs:345-353) goes to bpgpu_rangeproof_verify_rlc_ts as the batch's one start state.  `transcript`
+    // itself is not advanced, as in verify_batch.
     static std::vector<Status> verify_batch_combined(const BulletproofGens &bp_gens, const PedersenGens &pc_gens, const Transcript &transcript,
                                                      const std::vector<std::vector<uint8_t>> &proofs,
                                                      const std::vector<std::vector<CompressedRistretto>> &commitments, size_t n,
@@ -322,22 +324,53 @@ class RangeProof {
         std::vector<Status> out;
         if (nb == 0) return out;
         bp_gens.check_pedersen(pc_gens);
-        if (!transcript.is_fresh()) throw std::invalid_argument("verify_batch_combined needs a fresh Transcript(label); use verify_batch for pre-bound transcripts");
-        const size_t m = commitments.at(0).size(), len = proofs[0].size();
-        std::vector<uint8_t> flat(nb * len), vs(nb * m * 32), verdict(nb);
-        for (size_t i = 0; i < nb; i++) {
-            if (proofs[i].size() != len || commitments.at(i).size() != m) throw std::invalid_argument("verify_batch_combined: proofs of one call share (m, length)");
-            std::memcpy(&flat[i * len], proofs[i].data(), len);
-            for (size_t j = 0; j < m; j++) std::memcpy(&vs[(i * m + j) * 32], commitments[i][j].data(), 32);
-        }
-        const int rc = bpgpu_rangeproof_verify_rlc(bp_gens.ctx(), n, m, nb, flat.data(), len, vs.data(), transcript.label().data(),
-                                                   transcript.label().size(), rng64, weights64, verdict.data(), nullptr);
+        size_t m = 0, len = 0;
+        std::vector<uint8_t> flat, vs, verdict(nb);
+        flatten(proofs, commitments, flat, vs, m, len);
+        const int rc = transcript.is_fresh()
+                           ? bpgpu_rangeproof_verify_rlc(bp_gens.ctx(), n, m, nb, flat.data(), len, vs.data(), transcript.label().data(), transcript.label().size(),
+                                                         rng64, weights64, verdict.data(), nullptr)
+                           : bpgpu_rangeproof_verify_rlc_ts(bp_gens.ctx(), n, m, nb, flat.data(), len, vs.data(), transcript.state().data(), 0, rng64, weights64,
+                                                            verdict.data(), nullptr, nullptr);
+        if (rc != BPGPU_OK) throw GpuError(bpgpu_last_error(bp_gens.ctx()));
+        for (size_t i = 0; i < nb; i++) out.push_back(verdict[i] == 0 ? Status::Ok() : Status::Err(static_cast<ProofError>(verdict[i])));
+        return out;
+    }
+    // ... with ONE transcript per proof, each at whatever position its history left it (bpgpu_rangeproof_verify_rlc_ts, one state per
+    // proof).  The transcripts are not advanced.
+    static std::vector<Status> verify_batch_combined(const BulletproofGens &bp_gens, const PedersenGens &pc_gens, const std::vector<Transcript> &transcripts,
+                                                     const std::vector<std::vector<uint8_t>> &proofs,
+                                                     const std::vector<std::vector<CompressedRistretto>> &commitments, size_t n,
+                                                     const uint8_t *rng64 = nullptr, const uint8_t *weights64 = nullptr) {
+        const size_t nb = proofs.size();
+        std::vector<Status> out;
+        if (transcripts.size() != nb) throw std::invalid_argument("verify_batch_combined: one transcript per proof");
+        if (nb == 0) return out;
+        bp_gens.check_pedersen(pc_gens);
+        size_t m = 0, len = 0;
+        std::vector<uint8_t> flat, vs, verdict(nb), states(nb * BPGPU_TRANSCRIPT_BYTES);
+        flatten(proofs, commitments, flat, vs, m, len);
+        for (size_t i = 0; i < nb; i++) std::memcpy(&states[i * BPGPU_TRANSCRIPT_BYTES], transcripts[i].state().data(), BPGPU_TRANSCRIPT_BYTES);
+        const int rc = bpgpu_rangeproof_verify_rlc_ts(bp_gens.ctx(), n, m, nb, flat.data(), len, vs.data(), states.data(), BPGPU_TRANSCRIPT_BYTES, rng64,
+                                                      weights64, verdict.data(), nullptr, nullptr);
         if (rc != BPGPU_OK) throw GpuError(bpgpu_last_error(bp_gens.ctx()));
         for (size_t i = 0; i < nb; i++) out.push_back(verdict[i] == 0 ? Status::Ok() : Status::Err(static_cast<ProofError>(verdict[i])));
         return out;
     }
 
   private:
+    // the proofs and commitments of one combined call as flat buffers; they share (m, length)
+    static void flatten(const std::vector<std::vector<uint8_t>> &proofs, const std::vector<std::vector<CompressedRistretto>> &commitments,
+                        std::vector<uint8_t> &flat, std::vector<uint8_t> &vs, size_t &m, size_t &len) {
+        const size_t nb = proofs.size();
+        m = commitments.at(0).size(), len = proofs[0].size();
+        flat.resize(nb * len), vs.resize(nb * m * 32);
+        for (size_t i = 0; i < nb; i++) {
+            if (proofs[i].size() != len || commitments.at(i).size() != m) throw std::invalid_argument("verify_batch_combined: proofs of one call share (m, length)");
+            std::memcpy(&flat[i * len], proofs[i].data(), len);
+            for (size_t j = 0; j < m; j++) std::memcpy(&vs[(i * m + j) * 32], commitments[i][j].data(), 32);
+        }
+    }
     std::vector<uint8_t> bytes_;
 };
 
