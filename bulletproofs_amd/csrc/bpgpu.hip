@@ -157,9 +157,9 @@ struct bpgpu_ctx {
     size_t ipp_cap = 0;
     char *rpp_buf = nullptr;                 // working set of the batched range-proof prover
     size_t rpp_cap = 0;
-    char *r1rlc_buf = nullptr;               // combined term list, accumulators and weights of the batch-combined R1CS check
-    size_t r1rlc_cap = 0;
-    uint32_t r1rlc_max_terms = 0;            // option "r1cs_rlc_max_terms": unique terms per combination (0 = R1_RLC_MAX_TERMS)
+    char *comb_buf = nullptr;                // combined term list, accumulators and weights of the combined checks (R1CS, linear, mixed range proofs)
+    size_t comb_cap = 0;
+    uint32_t r1cs_rlc_max_terms = 0;         // option "r1cs_rlc_max_terms": unique terms per combination (0 = R1_RLC_MAX_TERMS)
     uint32_t bucket_min = 0;                 // terms per MSM from which the bucket path is taken (0 = BK_MIN_TERMS; huge = never)
     int bucket_chain = 0;                    // option "bucket_chain": 0 = the fused chain (bucket2.h) where it applies, 1 = bucket.h's chain everywhere (A/B)
     int bucket_lanes = 0;                    // option "bucket_lanes": lanes of a (MSM, window) workgroup of the fused chain (0 = by batch width; 64, 128, 256)
@@ -459,7 +459,7 @@ void bpgpu_ctx_destroy(bpgpu_ctx *c) {
     if (c->io_dev) hipFree(c->io_dev);
     if (c->ipp_buf) hipFree(c->ipp_buf);
     if (c->rpp_buf) hipFree(c->rpp_buf);
-    if (c->r1rlc_buf) hipFree(c->r1rlc_buf);
+    if (c->comb_buf) hipFree(c->comb_buf);
     if (c->pin) hipHostFree(c->pin);
     for (char *q : c->pin_retired) hipHostFree(q);
     if (c->order_ev) hipEventDestroy(c->order_ev);
@@ -608,7 +608,7 @@ int bpgpu_ctx_set_option(bpgpu_ctx *c, const char *key, int64_t value) {
     }
     if (!strcmp(key, "r1cs_rlc_max_terms")) {
         if (value < 0 || value > R1_RLC_MAX_TERMS) return fail(c, BPGPU_ERR_INVALID_ARG, "r1cs_rlc_max_terms must be 0 (default) .. 2^24");
-        c->r1rlc_max_terms = (uint32_t)value;
+        c->r1cs_rlc_max_terms = (uint32_t)value;
         return BPGPU_OK;
     }
     return fail(c, BPGPU_ERR_INVALID_ARG, "unknown option %s", key);
@@ -637,7 +637,7 @@ int bpgpu_ctx_get_option(bpgpu_ctx *c, const char *key, int64_t *value) {
     else if (!strcmp(key, "bucket_fast_tail")) *value = c->fast_tail;
     else if (!strcmp(key, "exponent_pairs")) *value = c->exp_pairs;
     else if (!strcmp(key, "fb_walk_waves")) *value = c->walk_waves ? c->walk_waves : 2048;
-    else if (!strcmp(key, "r1cs_rlc_max_terms")) *value = c->r1rlc_max_terms ? c->r1rlc_max_terms : R1_RLC_MAX_TERMS;
+    else if (!strcmp(key, "r1cs_rlc_max_terms")) *value = c->r1cs_rlc_max_terms ? c->r1cs_rlc_max_terms : R1_RLC_MAX_TERMS;
     else if (!strcmp(key, "staging_residue")) {
         // test hook: non-zero bytes left in the persistent staging buffers (pinned block, device IO buffer, prover working sets,
         // arena) -- 0 after a prover entry point has returned (prover_exit)
@@ -4687,14 +4687,25 @@ extern "C" int bpgpu_r1cs_verify_batch_ts(bpgpu_ctx *c, const bpgpu_r1cs_circuit
 }
 
 // ---- batch-combined R1CS verification (r1cs_rlc.h; an ADDITIONAL entry point, as bpgpu_rangeproof_verify_rlc) --------------
-static int r1rlc_reserve(bpgpu_ctx *c, size_t need) {
-    if (c->r1rlc_cap >= need) return BPGPU_OK;
+// the buffer the combined checks share (R1CS here, linear proofs and mixed range proofs below): each lays it out with an arena_plan
+static int comb_reserve(bpgpu_ctx *c, size_t need) {
+    if (c->comb_cap >= need) return BPGPU_OK;
     HIPCHK(c, hipDeviceSynchronize());
-    if (c->r1rlc_buf) HIPCHK(c, hipFree(c->r1rlc_buf));
-    c->r1rlc_buf = nullptr;
-    c->r1rlc_cap = 0;
-    if (hipMalloc((void **)&c->r1rlc_buf, need + need / 4) != hipSuccess) return fail(c, BPGPU_ERR_HIP, "out of device memory (%zu bytes of combined list)", need + need / 4);
-    c->r1rlc_cap = need + need / 4;
+    if (c->comb_buf) HIPCHK(c, hipFree(c->comb_buf));
+    c->comb_buf = nullptr;
+    c->comb_cap = 0;
+    if (hipMalloc((void **)&c->comb_buf, need + need / 4) != hipSuccess) return fail(c, BPGPU_ERR_HIP, "out of device memory (%zu bytes of combined list)", need + need / 4);
+    c->comb_cap = need + need / 4;
+    return BPGPU_OK;
+}
+
+// the weights of a combined check, lane = proof of the call: from the caller's 64 bytes each, or drawn under a per-call key and the
+// family's domain
+static int comb_rho_locked(bpgpu_ctx *c, hipStream_t s, const char *label, uint32_t n, const void *d_weights64, uint32_t dom, char *d_rho) {
+    rlc_key key;
+    memset(&key, 0, sizeof key);
+    if (!d_weights64 && !bp::fast_random((uint8_t *)key.w, 32)) return fail(c, BPGPU_ERR_HIP, "getrandom failed");   // (never the test seed: weights stay unpredictable)
+    LAUNCH(c, s, label, k_rlc_comb_rho, (n + 63) / 64, 64, n, (const uint8_t *)d_weights64, key, dom, (uint32_t *)d_rho);
     return BPGPU_OK;
 }
 
@@ -4713,7 +4724,7 @@ static int r1cs_rlc_dev_locked(bpgpu_ctx *c, const std::vector<r1cs_rlc_group> &
                                uint8_t *d_verdict, uint8_t *d_batch, char *d_ts_out, hipStream_t s) {
     if (!c->d_table) return fail(c, BPGPU_ERR_NO_GENS, "generators not loaded");
     const size_t TS = BPGPU_TRANSCRIPT_BYTES;
-    const size_t cap = c->r1rlc_max_terms ? c->r1rlc_max_terms : R1_RLC_MAX_TERMS;
+    const size_t cap = c->r1cs_rlc_max_terms ? c->r1cs_rlc_max_terms : R1_RLC_MAX_TERMS;
     uint32_t PN = 1;   // (a group whose padded_n exceeds the generators stops in launch 1 and adds no generator term)
     for (const auto &g : gr)
         if (g.ci->pn <= c->gens_capacity && g.ci->pn > PN) PN = g.ci->pn;
@@ -4736,21 +4747,21 @@ static int r1cs_rlc_dev_locked(bpgpu_ctx *c, const std::vector<r1cs_rlc_group> &
     size_t list_max = 1;
     for (size_t t : comb_terms) list_max = std::max(list_max, t);
     const size_t ncomb = comb_terms.size(), nrows = 2 * (size_t)PN + 2;
-    const size_t sz_l = align_up(list_max * 32), sz_acc = align_up(nrows * 80), sz_g = align_up(nrows * 32), sz_rho = align_up(total * 32),
-                 sz_st = align_up(total * 4), sz_parts = align_up(ncomb * 32), sz_pst = align_up(ncomb + 64), sz_res = align_up(64);
-    int rc = r1rlc_reserve(c, 2 * sz_l + sz_acc + sz_g + sz_rho + sz_st + sz_parts + sz_pst + sz_res);
+    arena_plan ap;
+    const size_t off_csc = ap.add(list_max * 32), off_cpt = ap.add(list_max * 32), off_acc = ap.add(nrows * 80), off_gen = ap.add(nrows * 32),
+                 off_rho = ap.add(total * 32), off_gst = ap.add(total * 4), off_parts = ap.add(ncomb * 32), off_pst = ap.add(ncomb + 64),
+                 off_res = ap.add(64);   // (compress(R), then its status byte at + 32)
+    int rc = comb_reserve(c, ap.total);
     if (rc) return rc;
-    char *d_csc = c->r1rlc_buf, *d_cpt = d_csc + sz_l, *d_acc = d_cpt + sz_l, *d_gen = d_acc + sz_acc, *d_rho = d_gen + sz_g, *d_gst = d_rho + sz_rho,
-         *d_parts = d_gst + sz_st, *d_pst = d_parts + sz_parts, *d_res = d_pst + sz_pst;
-    r1_rlc_key key;
-    memset(&key, 0, sizeof key);
-    if (!d_weights64 && !bp::fast_random((uint8_t *)key.w, 32)) return fail(c, BPGPU_ERR_HIP, "getrandom failed");   // (never the test seed: weights stay unpredictable)
+    char *b = c->comb_buf, *d_csc = b + off_csc, *d_cpt = b + off_cpt, *d_acc = b + off_acc, *d_gen = b + off_gen, *d_rho = b + off_rho, *d_gst = b + off_gst,
+         *d_parts = b + off_parts, *d_pst = b + off_pst, *d_res = b + off_res;
     const uint32_t n32 = (uint32_t)total;
-    LAUNCH(c, s, "r1cs_rlc_rho", k_r1cs_rlc_rho, (n32 + 63) / 64, 64, n32, (const uint8_t *)d_weights64, key, (uint32_t *)d_rho);
+    rc = comb_rho_locked(c, s, "r1cs_rlc_rho", n32, d_weights64, R1_RLC_WEIGHT_DOMAIN, d_rho);
+    if (rc) return rc;
     for (size_t i = 0; i < plan.size(); i++) {
         const slice_plan &sp = plan[i];
         const r1cs_rlc_group &g = gr[sp.grp];
-        if (i == 0 || plan[i - 1].comb != sp.comb) HIPCHK(c, hipMemsetAsync(d_acc, 0, sz_acc, s));
+        if (i == 0 || plan[i - 1].comb != sp.comb) HIPCHK(c, hipMemsetAsync(d_acc, 0, nrows * 80, s));
         const size_t gp0 = g.gp0 + sp.first;
         r1cs_staged stg;
         rc = r1cs_front_dev_locked(c, g.ci, sp.count, g.d_proofs + sp.first * g.proof_stride, g.proof_stride, g.d_lens + sp.first * 4,
@@ -4767,14 +4778,15 @@ static int r1cs_rlc_dev_locked(bpgpu_ctx *c, const std::vector<r1cs_rlc_group> &
         LAUNCH(c, s, "r1cs_rlc_weigh", k_r1cs_rlc_weigh, (uint32_t)(nt / 64), 64, sl, (const uint32_t *)stg.stat, (const uint32_t *)d_rho, (const uint32_t *)stg.gen,
                (const uint32_t *)stg.usc, (const uint32_t *)stg.upt, (uint32_t *)d_csc, (uint32_t *)d_cpt, (uint32_t *)d_gst, (unsigned long long *)d_acc);
         if (i + 1 == plan.size() || plan[i + 1].comb != sp.comb) {   // the combination is complete: its generator row, then its MSM
-            LAUNCH(c, s, "r1cs_rlc_reduce", k_r1cs_rlc_reduce, (uint32_t)((nrows + 63) / 64), 64, (uint32_t)nrows, (const unsigned long long *)d_acc,
+            LAUNCH(c, s, "r1cs_rlc_reduce", k_rlc_comb_reduce, (uint32_t)((nrows + 63) / 64), 64, (uint32_t)nrows, (const unsigned long long *)d_acc,
                    (uint32_t *)d_gen);
             rc = msm_shared_dev_locked(c, PN, 1, 1, comb_terms[sp.comb], d_gen, d_csc, d_cpt, d_parts + 32 * sp.comb, d_pst + sp.comb, nullptr, s);
             if (rc) return rc;
         }
     }
-    LAUNCH(c, s, "r1cs_rlc_sum", k_r1cs_rlc_sum, 1, 64, (uint32_t)ncomb, (const uint32_t *)d_parts, (const uint8_t *)d_pst, (uint32_t *)d_res);
-    LAUNCH(c, s, "r1cs_rlc_verdict", k_r1cs_rlc_verdict, (n32 + 63) / 64, 64, n32, (const uint32_t *)d_gst, (const uint32_t *)d_res, d_verdict, d_batch);
+    LAUNCH(c, s, "r1cs_rlc_sum", k_r1cs_rlc_sum, 1, 64, (uint32_t)ncomb, (const uint32_t *)d_parts, (const uint8_t *)d_pst, (uint32_t *)d_res, (uint8_t *)(d_res + 32));
+    LAUNCH(c, s, "r1cs_rlc_verdict", k_rlc_comb_verdict, (n32 + 63) / 64, 64, n32, (const uint32_t *)d_gst, (const uint32_t *)d_res, (const uint8_t *)(d_res + 32),
+           d_verdict, d_batch);
     HIPCHK(c, hipGetLastError());
     return BPGPU_OK;
 }
@@ -4892,7 +4904,7 @@ extern "C" int bpgpu_r1cs_verify_rlc(bpgpu_ctx *c, size_t ngroups, const bpgpu_r
 // R = sum_p rho_p Check_p: the front end of the per-proof path (lin_front_dev_locked), the weights, the weigh launch, the reduction of the
 // n + 2 base rows and ONE multiscalar multiplication -- the shared-generator MSM with nbatch U unique terms in generator-table mode, one
 // variable-base MSM of (n + 2) + nbatch U terms with the caller's bases -- then the verdicts (undecided where R is not the identity).
-// The combined list and the accumulators live in the combined checks' buffer (c->r1rlc_buf), beside the front end's staging.
+// The combined list and the accumulators live in the combined checks' buffer (c->comb_buf), beside the front end's staging.
 static int lin_rlc_dev_locked(bpgpu_ctx *c, size_t n, size_t nbatch, const void *d_proofs, size_t proof_len, const uint8_t *label,
                               size_t label_len, const uint8_t *shared_ts, const void *d_C, const void *d_G, const void *d_F, const void *d_B,
                               const void *d_b, int b_shared, const void *d_weights64, uint8_t *d_verdict, uint8_t *d_batch, void *d_ts_out,
@@ -4909,41 +4921,40 @@ static int lin_rlc_dev_locked(bpgpu_ctx *c, size_t n, size_t nbatch, const void 
     const lin_shape &sh = stg.sh;
     const size_t U = 2 * (size_t)sh.k + 2, nrows = (size_t)sh.n + 2, head = stg.fixed ? 0 : nrows, nterms = head + nbatch * U;
     if (nbatch * U > LIN_RLC_MAX_TERMS) return fail(c, BPGPU_ERR_INVALID_ARG, "batch too large: more than 2^24 proof-specific terms in one combination");
-    const size_t sz_l = align_up(nterms * 32 + 64), sz_acc = align_up(nrows * 80), sz_g = align_up(nrows * 32 + 64), sz_rho = align_up(nbatch * 32),
-                 sz_bo = align_up(64);
-    rc = r1rlc_reserve(c, 2 * sz_l + sz_acc + sz_g + sz_rho + sz_bo);
+    arena_plan ap;
+    const size_t off_csc = ap.add(nterms * 32 + 64), off_cpt = ap.add(nterms * 32 + 64), off_acc = ap.add(nrows * 80), off_row = ap.add(nrows * 32 + 64),
+                 off_rho = ap.add(nbatch * 32), off_bo = ap.add(64);
+    rc = comb_reserve(c, ap.total);
     if (rc) return rc;
-    char *d_csc = c->r1rlc_buf, *d_cpt = d_csc + sz_l, *d_acc = d_cpt + sz_l, *d_row = d_acc + sz_acc, *d_rho = d_row + sz_g, *d_bo = d_rho + sz_rho;
+    char *b = c->comb_buf, *d_csc = b + off_csc, *d_cpt = b + off_cpt, *d_acc = b + off_acc, *d_row = b + off_row, *d_rho = b + off_rho, *d_bo = b + off_bo;
     if (!d_batch) d_batch = (uint8_t *)d_bo;
     const uint32_t nb32 = (uint32_t)nbatch;
     if (sh.shape_verdict) {   // n != 2^k: every proof already carries its code and nothing enters R
         HIPCHK(c, hipMemsetAsync(stg.d_mst, 0, stg.sz_b + stg.sz_o, s));
     } else {
-        lin_rlc_key key;
-        memset(&key, 0, sizeof key);
-        if (!d_weights64 && !bp::fast_random((uint8_t *)key.w, 32)) return fail(c, BPGPU_ERR_HIP, "getrandom failed");   // (never the test seed: weights stay unpredictable)
-        LAUNCH(c, s, "lin_rlc_rho", k_lin_rlc_rho, (nb32 + 63) / 64, 64, nb32, (const uint8_t *)d_weights64, key, (uint32_t *)d_rho);
+        rc = comb_rho_locked(c, s, "lin_rlc_rho", nb32, d_weights64, LIN_RLC_WEIGHT_DOMAIN, d_rho);
+        if (rc) return rc;
         lin_rlc_shape ws;
         ws.nproofs = nb32, ws.nstride = (uint32_t)((nbatch + 63) / 64 * 64), ws.n = sh.n, ws.k = sh.k, ws.U = (uint32_t)U, ws.fixed = stg.fixed ? 1u : 0u,
         ws.u0 = (uint32_t)head;
         const uint64_t nt = (uint64_t)ws.nstride * (U + nrows);   // (a multiple of 64: whole wavefronts)
         if (nt > 0x7fffffffull) return fail(c, BPGPU_ERR_INVALID_ARG, "batch too large for this shape");
-        HIPCHK(c, hipMemsetAsync(d_acc, 0, sz_acc, s));
+        HIPCHK(c, hipMemsetAsync(d_acc, 0, nrows * 80, s));
         LAUNCH(c, s, "lin_rlc_weigh", k_lin_rlc_weigh, (uint32_t)(nt / 64), 64, ws, (const uint32_t *)stg.d_stat, (const uint32_t *)d_rho, (const uint32_t *)stg.d_gen,
                (const uint32_t *)stg.d_sc, (const uint32_t *)stg.d_pt, (uint32_t *)d_csc, (uint32_t *)d_cpt, (unsigned long long *)d_acc);
         // the combined coefficients of (B, F, G_0..): the generator-table row, or the head of the list with the caller's encodings
-        LAUNCH(c, s, "lin_rlc_reduce", k_lin_rlc_reduce, (uint32_t)((nrows + 63) / 64), 64, (uint32_t)nrows, (const unsigned long long *)d_acc,
-               (const uint8_t *)stg.d_B, (const uint8_t *)stg.d_F, (const uint8_t *)stg.d_G, (uint32_t *)(stg.fixed ? d_row : d_csc),
-               stg.fixed ? (uint32_t *)nullptr : (uint32_t *)d_cpt);
         if (stg.fixed) {
+            LAUNCH(c, s, "lin_rlc_reduce", k_rlc_comb_reduce, (uint32_t)((nrows + 63) / 64), 64, (uint32_t)nrows, (const unsigned long long *)d_acc, (uint32_t *)d_row);
             rc = msm_shared_dev_locked(c, sh.n, 1, 1, nbatch * U, d_row, d_csc, d_cpt, stg.d_out, stg.d_mst, nullptr, s, true);
         } else {
+            LAUNCH(c, s, "lin_rlc_reduce", k_lin_rlc_reduce, (uint32_t)((nrows + 63) / 64), 64, (uint32_t)nrows, (const unsigned long long *)d_acc,
+                   (const uint8_t *)stg.d_B, (const uint8_t *)stg.d_F, (const uint8_t *)stg.d_G, (uint32_t *)d_csc, (uint32_t *)d_cpt);
             const uint32_t nt1 = (uint32_t)nterms;
             rc = msm_batch_dev_locked(c, 1, &nt1, d_csc, d_cpt, stg.d_out, stg.d_mst, s);
         }
         if (rc) return rc;
     }
-    LAUNCH(c, s, "lin_rlc_verdict", k_lin_rlc_verdict, (nb32 + 63) / 64, 64, nb32, (const uint32_t *)stg.d_stat, (const uint32_t *)stg.d_out,
+    LAUNCH(c, s, "lin_rlc_verdict", k_rlc_comb_verdict, (nb32 + 63) / 64, 64, nb32, (const uint32_t *)stg.d_stat, (const uint32_t *)stg.d_out,
            (const uint8_t *)stg.d_mst, d_verdict, d_batch);
     HIPCHK(c, hipGetLastError());
     return BPGPU_OK;
@@ -5487,22 +5498,24 @@ static int rp_mix_dev_locked(bpgpu_ctx *c, std::vector<rp_mix_group> &gr, size_t
     }
     if (u_total > RM_MAX_TERMS) return fail(c, BPGPU_ERR_INVALID_ARG, "more than 2^24 proof-specific terms in one call");
     const size_t nrows = N ? 2 * N * M + 2 : 0;
-    const size_t sz_l = align_up(std::max<size_t>(u_total, 1) * 32), sz_acc = align_up(nrows * 80 + 16), sz_g = align_up(nrows * 32 + 16), sz_st = align_up(total * 4),
-                 sz_res = align_up(64), sz_r = d_rng64 ? 0 : align_up(total * 64), sz_w = d_weights64 ? 0 : align_up(total * 64);
-    int rc = r1rlc_reserve(c, 2 * sz_l + sz_acc + sz_g + sz_st + sz_res + sz_r + sz_w);   // (the combined checks share their buffer)
+    arena_plan cp;   // (the combined checks share their buffer)
+    const size_t list = std::max<size_t>(u_total, 1) * 32;
+    const size_t off_csc = cp.add(list), off_cpt = cp.add(list), off_acc = cp.add(nrows * 80 + 16), off_gen = cp.add(nrows * 32 + 16), off_gst = cp.add(total * 4),
+                 off_res = cp.add(64), off_rdraw = cp.add(d_rng64 ? 0 : total * 64), off_wdraw = cp.add(d_weights64 ? 0 : total * 64);
+    int rc = comb_reserve(c, cp.total);
     if (rc) return rc;
-    char *d_csc = c->r1rlc_buf, *d_cpt = d_csc + sz_l, *d_acc = d_cpt + sz_l, *d_gen = d_acc + sz_acc, *d_gst = d_gen + sz_g, *d_res = d_gst + sz_st,
-         *d_rdraw = d_res + sz_res, *d_wdraw = d_rdraw + sz_r;
+    char *b = c->comb_buf, *d_csc = b + off_csc, *d_cpt = b + off_cpt, *d_acc = b + off_acc, *d_gen = b + off_gen, *d_gst = b + off_gst, *d_res = b + off_res,
+         *d_rdraw = b + off_rdraw, *d_wdraw = b + off_wdraw;
     const uint32_t n32 = (uint32_t)total;
     if (!d_rng64) {   // as the per-proof path's seeded mode (the tests' chain seed pins it), but per call and under this entry point's domain
-        rm_key key;
+        rlc_key key;
         if (c->test_seed_set) memcpy(key.w, c->test_seed, 32);
         else if (!bp::fast_random((uint8_t *)key.w, 32)) return fail(c, BPGPU_ERR_HIP, "getrandom failed");
         LAUNCH(c, s, "rlc_mix_draw", k_rlc_mix_draw, (n32 + 63) / 64, 64, n32, key, (uint32_t)RM_RNG_DOMAIN, (uint32_t *)d_rdraw);
         d_rng64 = d_rdraw;
     }
     if (!d_weights64) {   // (never the test seed: weights stay unpredictable)
-        rm_key key;
+        rlc_key key;
         if (!bp::fast_random((uint8_t *)key.w, 32)) return fail(c, BPGPU_ERR_HIP, "getrandom failed");
         LAUNCH(c, s, "rlc_mix_draw", k_rlc_mix_draw, (n32 + 63) / 64, 64, n32, key, (uint32_t)RM_WEIGHT_DOMAIN, (uint32_t *)d_wdraw);
         d_weights64 = d_wdraw;
@@ -5514,7 +5527,7 @@ static int rp_mix_dev_locked(bpgpu_ctx *c, std::vector<rp_mix_group> &gr, size_t
         rc = rp_verify_dev_locked(c, g.n, g.m, g.nbatch, g.d_proofs, g.proof_len, g.d_coms, rp_mix_transcripts(g), d_rng64 + 64 * g.gp0, d_verdict + g.gp0,
                                   nullptr, s);
         if (rc) return rc;
-        HIPCHK(c, hipMemsetAsync(d_gst + 4 * g.gp0, 0xff, 4 * g.nbatch, s));
+        HIPCHK(c, hipMemsetAsync(d_gst + 4 * g.gp0, 0xff, 4 * g.nbatch, s));   // (every word RLC_GSTATUS_DONE)
     }
     if (nrows) HIPCHK(c, hipMemsetAsync(d_acc, 0, nrows * 80, s));
     for (const auto &g : gr) {
@@ -5573,11 +5586,11 @@ static int rp_mix_dev_locked(bpgpu_ctx *c, std::vector<rp_mix_group> &gr, size_t
     }
     HIPCHK(c, hipMemsetAsync(d_res, 0, 64, s));   // (no group left: R is the identity)
     if (u_total) {
-        LAUNCH(c, s, "rlc_mix_reduce", k_r1cs_rlc_reduce, (uint32_t)((nrows + 63) / 64), 64, (uint32_t)nrows, (const unsigned long long *)d_acc, (uint32_t *)d_gen);
+        LAUNCH(c, s, "rlc_mix_reduce", k_rlc_comb_reduce, (uint32_t)((nrows + 63) / 64), 64, (uint32_t)nrows, (const unsigned long long *)d_acc, (uint32_t *)d_gen);
         rc = msm_shared_dev_locked(c, N, M, 1, u_total, d_gen, d_csc, d_cpt, d_res, d_res + 32, nullptr, s);
         if (rc) return rc;
     }
-    LAUNCH(c, s, "rlc_mix_verdict", k_rlc_mix_verdict, (n32 + 63) / 64, 64, n32, (const uint32_t *)d_gst, (const uint32_t *)d_res, (const uint8_t *)(d_res + 32),
+    LAUNCH(c, s, "rlc_mix_verdict", k_rlc_comb_verdict, (n32 + 63) / 64, 64, n32, (const uint32_t *)d_gst, (const uint32_t *)d_res, (const uint8_t *)(d_res + 32),
            d_verdict, d_batch);
     HIPCHK(c, hipGetLastError());
     return BPGPU_OK;

@@ -1,15 +1,10 @@
 // k_lin_rlc.hip: HIP kernels of libbpgpu.so (gfx950) for the batch-combined LinearProof check; thin __global__ wrappers around linear_rlc.h.
+// (Its rho and verdict launches are the shared ones of k_rlc_comb.hip.)
 #include <hip/hip_runtime.h>
 #include "kernels.h"
 #include "rlc_wave.h"
 
 using namespace bp;
-
-// lane = proof: its combination weight rho (plain scalar, 8 words)
-__global__ void __launch_bounds__(64) k_lin_rlc_rho(uint32_t n, const uint8_t *weights64, lin_rlc_key key, uint32_t *rho) {
-    const uint32_t p = blockIdx.x * blockDim.x + threadIdx.x;
-    if (p < n) lin_rlc_rho_thread(p, weights64, key, rho);
-}
 
 // lane = (term, proof), proof fastest, over nstride (a multiple of 64) proofs: the 64 lanes of a wavefront share their term, so the
 // base rows take one atomic per limb per wavefront.  Launched with exactly nstride (U + n + 2) lanes: every lane reaches
@@ -24,16 +19,10 @@ __global__ void __launch_bounds__(64) k_lin_rlc_weigh(lin_rlc_shape sh, const ui
     if (tid / sh.nstride >= sh.U) rlc_accumulate(acc, row, v, base, true);   // (uniform across the wavefront)
 }
 
-// lane = row of (B, F, G_0..): the accumulated coefficient mod l (and, with explicit bases, the base's encoding beside it)
+// explicit bases, lane = row of (B, F, G_0..): the accumulated coefficient mod l and the base's encoding beside it, the head of the
+// combined list (generator-table mode reduces with k_rlc_comb_reduce)
 __global__ void __launch_bounds__(64) k_lin_rlc_reduce(uint32_t nrows, const unsigned long long *acc, const uint8_t *B, const uint8_t *F,
                                                         const uint8_t *G, uint32_t *out_sc, uint32_t *out_pt) {
     const uint32_t g = blockIdx.x * blockDim.x + threadIdx.x;
     if (g < nrows) lin_rlc_reduce_thread(g, (const uint64_t *)acc, B, F, G, out_sc, out_pt);
-}
-
-// lane = proof
-__global__ void __launch_bounds__(64) k_lin_rlc_verdict(uint32_t n, const uint32_t *status, const uint32_t *enc, const uint8_t *msm_status,
-                                                         uint8_t *verdict, uint8_t *batch_out) {
-    const uint32_t p = blockIdx.x * blockDim.x + threadIdx.x;
-    if (p < n) lin_rlc_verdict_thread(p, status, enc, msm_status, verdict, batch_out);
 }

@@ -1,15 +1,10 @@
 // k_r1cs_rlc.hip: HIP kernels of libbpgpu.so (gfx950) for the batch-combined R1CS check; thin __global__ wrappers around r1cs_rlc.h.
+// (Its rho, reduce and verdict launches are the shared ones of k_rlc_comb.hip.)
 #include <hip/hip_runtime.h>
 #include "kernels.h"
 #include "rlc_wave.h"
 
 using namespace bp;
-
-// lane = proof of the call: its combination weight rho (plain scalar, 8 words)
-__global__ void __launch_bounds__(64) k_r1cs_rlc_rho(uint32_t n, const uint8_t *weights64, r1_rlc_key key, uint32_t *rho) {
-    const uint32_t gp = blockIdx.x * blockDim.x + threadIdx.x;
-    if (gp < n) r1_rlc_rho_thread(gp, weights64, key, rho);
-}
 
 // lane = (term, proof) of one slice, proof fastest, over nstride (a multiple of 64) proofs: the 64 lanes of a wavefront share their
 // term, so generator rows take one atomic per limb per wavefront.  Launched with exactly nstride (U + ngen) lanes: every lane reaches
@@ -24,25 +19,7 @@ __global__ void __launch_bounds__(64) k_r1cs_rlc_weigh(r1_rlc_slice sl, const ui
     if (tid / sl.nstride >= sl.U) rlc_accumulate(acc, row, v, gen, true);   // (uniform across the wavefront)
 }
 
-// lane = generator row of the combination: the accumulated coefficient mod l
-__global__ void __launch_bounds__(64) k_r1cs_rlc_reduce(uint32_t nrows, const unsigned long long *acc, uint32_t *gen_row) {
-    const uint32_t g = blockIdx.x * blockDim.x + threadIdx.x;
-    if (g >= nrows) return;
-    uint64_t a[10];
-#pragma unroll
-    for (int i = 0; i < 10; i++) a[i] = acc[(uint64_t)g * 10 + i];
-    sc s;
-    rlc_acc_to_sc(s, a);
-    store_words8(gen_row + (uint64_t)g * 8, s);
-}
-
 // one lane: the combinations' points summed
-__global__ void __launch_bounds__(64) k_r1cs_rlc_sum(uint32_t ncomb, const uint32_t *parts, const uint8_t *part_status, uint32_t *res) {
-    if (blockIdx.x == 0 && threadIdx.x == 0) r1_rlc_sum_thread(ncomb, parts, part_status, res);
-}
-
-// lane = proof of the call
-__global__ void __launch_bounds__(64) k_r1cs_rlc_verdict(uint32_t n, const uint32_t *gstatus, const uint32_t *res, uint8_t *verdict, uint8_t *batch_out) {
-    const uint32_t gp = blockIdx.x * blockDim.x + threadIdx.x;
-    if (gp < n) r1_rlc_verdict_thread(gp, gstatus, res, verdict, batch_out);
+__global__ void __launch_bounds__(64) k_r1cs_rlc_sum(uint32_t ncomb, const uint32_t *parts, const uint8_t *part_status, uint32_t *res, uint8_t *rst) {
+    if (blockIdx.x == 0 && threadIdx.x == 0) r1_rlc_sum_thread(ncomb, parts, part_status, res, rst);
 }

@@ -1,5 +1,5 @@
-// k_rlc_mix.hip: HIP kernels of libbpgpu.so (gfx950) for the batch-combined check over range proofs of mixed shapes; thin __global__
-// wrappers around rlc_mix.h and the lane bodies of rangeproof.h.
+// k_rlc_mix.hip: HIP kernels of libbpgpu.so (gfx950) for the batch-combined check over range proofs of mixed shapes (its reduce and verdict
+// launches: k_rlc_comb.hip); thin __global__ wrappers around rlc_mix.h and the lane bodies of rangeproof.h.
 #include <hip/hip_runtime.h>
 #include "kernels.h"
 #include "rlc_wave.h"
@@ -7,9 +7,9 @@
 using namespace bp;
 
 // lane = proof of the call: its 64 library-drawn bytes of domain `dom`
-__global__ void __launch_bounds__(64) k_rlc_mix_draw(uint32_t n, rm_key key, uint32_t dom, uint32_t *out) {
+__global__ void __launch_bounds__(64) k_rlc_mix_draw(uint32_t n, rlc_key key, uint32_t dom, uint32_t *out) {
     const uint32_t gp = blockIdx.x * blockDim.x + threadIdx.x;
-    if (gp < n) rm_draw_thread(gp, key, dom, out);
+    if (gp < n) rlc_draw_thread(gp, key, dom, out);
 }
 
 // launch 1 of one group, the roles of k_rp_stage1<true> in batch-combination mode: [0, n_tr) the scripted transcript replay, then the
@@ -69,13 +69,4 @@ __global__ void __launch_bounds__(64) k_rlc_mix_weigh(rm_group gr, rp_shape sh, 
             rlc_accumulate(acc, row_h, h[j], live, true);
         }
     }
-}
-
-// (the reduction of the limb sums, lane = generator row of the call's MSM, is k_r1cs_rlc_reduce: rlc_acc_to_sc per row)
-
-// lane = proof of the call
-__global__ void __launch_bounds__(64) k_rlc_mix_verdict(uint32_t n, const uint32_t *gstatus, const uint32_t *res, const uint8_t *rst, uint8_t *verdict,
-                                                        uint8_t *batch_out) {
-    const uint32_t gp = blockIdx.x * blockDim.x + threadIdx.x;
-    if (gp < n) rm_verdict_thread(gp, gstatus, res, rst, verdict, batch_out);
 }

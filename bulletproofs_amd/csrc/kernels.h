@@ -83,20 +83,18 @@ __global__ void k_aud_verdict(uint32_t n, const uint32_t *status, const uint8_t 
 __global__ void k_r1cs_front(r1cs_shape sh, rp_strobe_init init, const uint8_t *proofs, const uint32_t *proof_lens, const uint8_t *commitments, const uint32_t *ts_in, const uint8_t *rng32, const uint32_t *lbl_off, const uint8_t *lbl, uint32_t *fields, uint32_t *uniq_sc, uint32_t *uniq_pt, uint32_t *ts_out, uint32_t *status);
 __global__ void k_r1cs_flatten(uint32_t nthreads, r1cs_shape sh, const uint32_t *col_ptr, const r1cs_ent *ents, const uint32_t *status, uint32_t *fields, uint32_t *gen_sc, uint32_t *uniq_sc, uint32_t *dterm);
 __global__ void k_r1cs_finish(r1cs_shape sh, const uint32_t *status, const uint32_t *dterm, const uint32_t *fields, uint32_t *gen_sc);
-__global__ void k_r1cs_rlc_rho(uint32_t n, const uint8_t *weights64, r1_rlc_key key, uint32_t *rho);
 __global__ void k_r1cs_rlc_weigh(r1_rlc_slice sl, const uint32_t *status, const uint32_t *rho, const uint32_t *gen_sc, const uint32_t *uniq_sc, const uint32_t *uniq_pt, uint32_t *comb_sc, uint32_t *comb_pt, uint32_t *gstatus, unsigned long long *acc);
-__global__ void k_r1cs_rlc_reduce(uint32_t nrows, const unsigned long long *acc, uint32_t *gen_row);
-__global__ void k_r1cs_rlc_sum(uint32_t ncomb, const uint32_t *parts, const uint8_t *part_status, uint32_t *res);
-__global__ void k_r1cs_rlc_verdict(uint32_t n, const uint32_t *gstatus, const uint32_t *res, uint8_t *verdict, uint8_t *batch_out);
-__global__ void k_lin_rlc_rho(uint32_t n, const uint8_t *weights64, lin_rlc_key key, uint32_t *rho);
+__global__ void k_r1cs_rlc_sum(uint32_t ncomb, const uint32_t *parts, const uint8_t *part_status, uint32_t *res, uint8_t *rst);
 __global__ void k_lin_rlc_weigh(lin_rlc_shape sh, const uint32_t *status, const uint32_t *rho, const uint32_t *gen_sc, const uint32_t *list_sc, const uint32_t *list_pt, uint32_t *comb_sc, uint32_t *comb_pt, unsigned long long *acc);
 __global__ void k_lin_rlc_reduce(uint32_t nrows, const unsigned long long *acc, const uint8_t *B, const uint8_t *F, const uint8_t *G, uint32_t *out_sc, uint32_t *out_pt);
-__global__ void k_lin_rlc_verdict(uint32_t n, const uint32_t *status, const uint32_t *enc, const uint8_t *msm_status, uint8_t *verdict, uint8_t *batch_out);
+// k_rlc_comb.hip
+__global__ void k_rlc_comb_rho(uint32_t n, const uint8_t *weights64, rlc_key key, uint32_t dom, uint32_t *rho);
+__global__ void k_rlc_comb_reduce(uint32_t nrows, const unsigned long long *acc, uint32_t *out_sc);
+__global__ void k_rlc_comb_verdict(uint32_t n, const uint32_t *gstatus, const uint32_t *res, const uint8_t *rst, uint8_t *verdict, uint8_t *batch_out);
 // k_rlc_mix.hip
-__global__ void k_rlc_mix_draw(uint32_t n, rm_key key, uint32_t dom, uint32_t *out);
+__global__ void k_rlc_mix_draw(uint32_t n, rlc_key key, uint32_t dom, uint32_t *out);
 __global__ void k_rlc_mix_front(rp_shape sh, rp_strobe_init init, uint32_t n_tr, const uint8_t *proofs, const uint8_t *commitments, const uint8_t *rng64, const uint8_t *rho64, uint32_t *fields, uint32_t *status, fb_params prm, uint32_t lg_m, uint32_t *uniq_sc, const rp_script_hdr *script, const uint32_t *ts_in, uint32_t *ts_out);
 __global__ void k_rlc_mix_weigh(rm_group gr, rp_shape sh, fb_params prm, const uint8_t *proofs, const uint8_t *commitments, const uint32_t *status, const uint32_t *fields, const uint32_t *uniq_sc, uint32_t *comb_sc, uint32_t *comb_pt, uint32_t *gstatus, unsigned long long *acc);
-__global__ void k_rlc_mix_verdict(uint32_t n, const uint32_t *gstatus, const uint32_t *res, const uint8_t *rst, uint8_t *verdict, uint8_t *batch_out);
 // k_rlc_mix_ts.hip
 __global__ void k_rlc_mix_front_replay(rp_shape sh, rp_strobe_init init, uint32_t n_tr, const uint8_t *proofs, const uint8_t *commitments, const uint8_t *rng64, const uint8_t *rho64, uint32_t *fields, uint32_t *status, fb_params prm, uint32_t lg_m, uint32_t *uniq_sc, const uint32_t *ts_in, uint32_t *ts_out);
 // k_r1cs_prove.hip

@@ -15,11 +15,12 @@
 //                    of the call's combined list (scalar 0 and the identity encoding for a proof that stopped), the B_blinding / B
 //                    coefficients (RPF_ROW0 / RPF_ROW1) and the 2 n m exponents, four G and four H indices per lane
 //                    (rp_expand_b4_thread), into rlc.h's limb sums at their remapped rows
-// and once per call: the reduction (rlc_acc_to_sc), ONE shared-generator MSM over (N, M) and the verdicts.
+// and once per call: the reduction (rlc_reduce_thread), ONE shared-generator MSM over (N, M) and the verdicts (rlc_verdict_thread; a group
+// rejected as a whole has its verdicts from the per-shape path and RLC_GSTATUS_DONE in gstatus).
 #ifndef BPGPU_RLC_MIX_H
 #define BPGPU_RLC_MIX_H
 #include "rangeproof.h"
-#include "rlc.h"
+#include "rlc_comb.h"
 
 namespace bp {
 
@@ -28,7 +29,6 @@ namespace bp {
 #define RM_WEIGHT_DOMAIN 0x786d6377u   // "wcmx": the combination weights
 #define RM_RNG_DOMAIN 0x786d6372u      // "rcmx": the batching challenge's rng bytes (mod.rs:396)
 #define RM_MAX_TERMS (1u << 24)        // proofs, and unique terms, of one call: rlc_acc_to_sc's 2^24 sums; 1 GiB of combined list
-#define RM_GSTATUS_DONE 0xffffffffu    // a group rejected as a whole: its verdicts were written by the per-shape path
 
 // one group: its proofs are [gp0, gp0 + nproofs) of the call, its unique terms [u0, u0 + nproofs U) of the combined list
 struct rm_group {
@@ -48,16 +48,9 @@ BP_HD uint32_t rm_gen_row(uint32_t g, uint32_t n, uint32_t m, uint32_t N, uint32
     return 2 + (is_h ? N * M : 0u) + j * N + (i - j * n);
 }
 
-// the 64 bytes of the call's proof gp in domain `dom` (16 little-endian words: what a caller's rng64 / weights64 row would hold)
-struct rm_key {
-    uint32_t w[8];
-};
-BP_HD void rm_draw_thread(uint32_t gp, const rm_key &key, uint32_t dom, uint32_t *out) {
-    uint32_t w16[16];
-    chacha20_block(key.w, (uint64_t)gp, dom, 0u, w16);
-#pragma unroll
-    for (int i = 0; i < 16; i++) out[16 * (uint64_t)gp + i] = w16[i];
-}
+// the shared key and draw body under this check's names (the host harness drives them so)
+using rm_key = rlc_key;
+BP_HD void rm_draw_thread(uint32_t gp, const rm_key &key, uint32_t dom, uint32_t *out) { rlc_draw_thread(gp, key, dom, out); }
 
 // lane = proof p of one group: launch 1's transcript role, then the per-proof scalars times the proof's weight with the U coefficients as
 // plain scalars.  The two forms k_rp_stage1<SCRIPTED> has:
@@ -128,22 +121,6 @@ BP_HD void rm_quad_rows(const rm_group &gr, uint32_t q, uint32_t j, uint32_t &ro
     const uint32_t i = 4 * q + j;
     row_g = rm_gen_row(2 + i, gr.n, gr.m, gr.N, gr.M);
     row_h = rm_gen_row(2 + gr.n * gr.m + i, gr.n, gr.m, gr.N, gr.M);
-}
-
-// verdict of the call's proof gp: nothing for a group rejected as a whole; else its front-end code; else 0 when R is the identity and
-// decoded, else undecided (the host then re-verifies group by group).  res: the MSM's 8 words, rst: its status byte.  Lane 0 also
-// writes the 33 batch bytes.
-BP_HD void rm_verdict_thread(uint32_t gp, const uint32_t *gstatus, const uint32_t *res, const uint8_t *rst, uint8_t *verdict, uint8_t *batch_out) {
-    uint32_t nz = 0;
-#pragma unroll
-    for (int i = 0; i < 8; i++) nz |= res[i];
-    const bool dec = rst[0] == 0, pass = dec && nz == 0;
-    const uint32_t st = gstatus[gp];
-    if (st != RM_GSTATUS_DONE) verdict[gp] = st ? (uint8_t)st : (pass ? (uint8_t)BP_VERDICT_OK : (uint8_t)BP_VERDICT_UNDECIDED);
-    if (gp == 0) {
-        batch_out[0] = pass ? 0 : 1;
-        for (int i = 0; i < 32; i++) batch_out[1 + i] = dec ? (uint8_t)(res[i >> 2] >> (8 * (i & 3))) : 0;
-    }
 }
 
 }  // namespace bp

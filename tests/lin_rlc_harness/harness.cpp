@@ -1,5 +1,5 @@
 // Host harness for the batch-combined LinearProof check: linear_rlc.h's per-lane bodies compiled with g++ and driven lane by lane, the
-// way k_lin_rlc_rho / k_lin_rlc_weigh / k_lin_rlc_reduce run them.  TEST-ONLY: never part of libbpgpu.so, never a fallback.
+// way k_rlc_comb_rho / k_lin_rlc_weigh / k_rlc_comb_reduce (explicit bases: k_lin_rlc_reduce) run them.  TEST-ONLY: never part of libbpgpu.so, never a fallback.
 #define BP_FE_CHECK 1
 #include "../../bulletproofs_amd/csrc/linear_rlc.h"
 #include <vector>

@@ -1,5 +1,5 @@
-// Host harness for the batch-combined R1CS check: r1cs_rlc.h's per-lane bodies compiled with g++ and driven lane by lane, the way
-// k_r1cs_rlc_weigh / k_r1cs_rlc_reduce run them.  TEST-ONLY: never part of libbpgpu.so, never a fallback.
+// Host harness for the batch-combined R1CS check: r1cs_rlc.h's per-lane bodies, and the ones of rlc_comb.h under them, compiled with g++
+// and driven lane by lane, the way k_r1cs_rlc_weigh / k_rlc_comb_reduce / k_r1cs_rlc_sum / k_rlc_comb_verdict run them.  TEST-ONLY: never part of libbpgpu.so, never a fallback.
 #define BP_FE_CHECK 1
 #include "../../bulletproofs_amd/csrc/r1cs_rlc.h"
 #include <vector>
@@ -28,11 +28,7 @@ extern "C" int r1rlc_weigh_slice(uint32_t nproofs, uint32_t U, uint32_t pn, uint
         rlc_limbs(l, v);
         for (int i = 0; i < 10; i++) acc[(size_t)row * 10 + i] += l[i];
     }
-    for (uint32_t g = 0; g < nrows; g++) {
-        sc s;
-        rlc_acc_to_sc(s, &acc[(size_t)g * 10]);
-        store_words8(gen_row_out + (size_t)g * 8, s);
-    }
+    for (uint32_t g = 0; g < nrows; g++) rlc_reduce_thread(g, acc.data(), gen_row_out);
     return 0;
 }
 
@@ -41,4 +37,14 @@ extern "C" uint32_t r1rlc_gen_row(uint32_t g, uint32_t pn, uint32_t PN) { return
 extern "C" void r1rlc_rho(const uint8_t *weights64, uint32_t gp, uint32_t *rho) {
     r1_rlc_key key{};
     r1_rlc_rho_thread(gp, weights64, key, rho);
+}
+
+// the one lane of the sum launch: the combinations' encodings and status bytes -> compress(R) and its status byte
+extern "C" void r1cs_rlc_sum_lane(uint32_t ncomb, const uint32_t *parts, const uint8_t *part_status, uint32_t *res, uint8_t *rst) {
+    r1_rlc_sum_thread(ncomb, parts, part_status, res, rst);
+}
+
+// every lane of the verdict launch the combined checks share, in descending order (lane 0's batch bytes must not depend on it)
+extern "C" void rlc_comb_verdict_lanes(uint32_t n, const uint32_t *gstatus, const uint32_t *res, const uint8_t *rst, uint8_t *verdict, uint8_t *batch_out) {
+    for (uint32_t gp = n; gp-- > 0;) rlc_verdict_thread(gp, gstatus, res, rst, verdict, batch_out);
 }

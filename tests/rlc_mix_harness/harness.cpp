@@ -1,5 +1,5 @@
 // Host harness for the batch-combined check over range proofs of mixed shapes: rlc_mix.h's per-lane bodies compiled with g++ and driven
-// lane by lane, the way k_rlc_mix_weigh / k_r1cs_rlc_reduce run them.  TEST-ONLY: never part of libbpgpu.so, never a fallback.
+// lane by lane, the way k_rlc_mix_draw / k_rlc_mix_weigh / k_rlc_comb_reduce run them.  TEST-ONLY: never part of libbpgpu.so, never a fallback.
 #define BP_FE_CHECK 1
 #include "../../bulletproofs_amd/csrc/rlc_mix.h"
 #include <vector>
@@ -68,9 +68,5 @@ extern "C" int rlcmix_weigh_group(uint32_t nproofs, uint32_t n, uint32_t m, uint
 }
 
 extern "C" void rlcmix_reduce(uint32_t nrows, const uint64_t *acc, uint32_t *gen_row_out) {
-    for (uint32_t g = 0; g < nrows; g++) {
-        sc s;
-        rlc_acc_to_sc(s, acc + (size_t)g * 10);
-        store_words8(gen_row_out + (size_t)g * 8, s);
-    }
+    for (uint32_t g = 0; g < nrows; g++) rlc_reduce_thread(g, acc, gen_row_out);
 }

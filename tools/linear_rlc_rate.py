@@ -144,11 +144,11 @@ def split_of(trace_csv):
     out = {"lin_prepare_us": 0.0, "weigh_us": 0.0, "rho_reduce_verdict_us": 0.0, "msm_us": 0.0, "runtime_fill_copy_us": 0.0}
     for s, e, name in call:
         key = ("lin_prepare_us" if "k_lin_prepare" in name else "weigh_us" if "k_lin_rlc_weigh" in name else
-               "rho_reduce_verdict_us" if "k_lin_rlc_" in name else "msm_us" if re.match(r"k_\w+", name) else "runtime_fill_copy_us")
+               "rho_reduce_verdict_us" if "k_lin_rlc_" in name or "k_rlc_comb_" in name else "msm_us" if re.match(r"k_\w+", name) else "runtime_fill_copy_us")
         out[key] += (e - s) / 1e3
     out = {k: round(v, 1) for k, v in out.items()}
     out["launches"] = len(call)
-    out["other_kernels"] = sorted({name for _, _, name in call if "k_lin_" not in name})
+    out["other_kernels"] = sorted({name for _, _, name in call if "k_lin_" not in name and "k_rlc_comb_" not in name})
     out["span_us"] = round((call[-1][1] - call[0][0]) / 1e3, 1)
     return out
 
