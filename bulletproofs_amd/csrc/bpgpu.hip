@@ -636,6 +636,13 @@ int bpgpu_ctx_get_option(bpgpu_ctx *c, const char *key, int64_t *value) {
     else if (!strcmp(key, "bucket_lanes")) *value = c->bucket_lanes;
     else if (!strcmp(key, "bucket_fast_tail")) *value = c->fast_tail;
     else if (!strcmp(key, "exponent_pairs")) *value = c->exp_pairs;
+    else if (!strcmp(key, "split_stage3")) *value = c->split_stage3;
+    else if (!strcmp(key, "transcript_coop")) *value = c->transcript_coop;
+    else if (!strcmp(key, "coop_split")) *value = c->coop_split;
+    else if (!strcmp(key, "coop_defer_emit")) *value = c->coop_defer_emit;
+    else if (!strcmp(key, "narrow_hi_max")) *value = c->narrow_hi_max;
+    else if (!strcmp(key, "narrow_hi4_max")) *value = c->narrow_hi4_max;
+    else if (!strcmp(key, "narrow_fused_finish")) *value = c->narrow_fused_finish;
     else if (!strcmp(key, "fb_walk_waves")) *value = c->walk_waves ? c->walk_waves : 2048;
     else if (!strcmp(key, "r1cs_rlc_max_terms")) *value = c->r1cs_rlc_max_terms ? c->r1cs_rlc_max_terms : R1_RLC_MAX_TERMS;
     else if (!strcmp(key, "staging_residue")) {

@@ -430,6 +430,25 @@ int h_rp_transcript_shape_stop(uint32_t n, uint32_t m, const uint8_t *proof, uin
     return 0;
 }
 
+// What k_rp_stage1_coop compares with its capacities for one shape and one start position: out4 = U, the words of the proof and its
+// commitments, the script's operations and its masks.  (The script is the one the runtime compiles: rp_script_build.)
+int h_rp_script_counts(uint32_t n, uint32_t m, uint32_t pos, uint32_t pos_begin, uint32_t cur_flags, int domsep, uint32_t *out4) {
+    uint32_t k = 0; while ((1u << k) < n * m) k++;
+    if (n * m != (1u << k)) return -1;
+    const std::vector<uint32_t> img = rp_script_build(n, m, k, pos, pos_begin, cur_flags, domsep != 0);
+    const rp_script_hdr *script = (const rp_script_hdr *)img.data();
+    out4[0] = 4 + 2 * k + m;
+    out4[1] = 8 * (9 + 2 * k) + 8 * m;
+    out4[2] = script->n_ops;
+    out4[3] = script->n_masks;
+    return 0;
+}
+// ... and the capacities themselves, as compiled: 0 RP_COOP_STAGE_WORDS, 1 RP_COOP_OPS_CAP, 2 RP_COOP_MASKS_CAP, 3 RP_DEFER_CAP, 4 BP_RP_MAX_K, 5 BP_VB_CHUNK
+uint32_t h_rp_coop_cap(int which) {
+    const uint32_t caps[6] = {RP_COOP_STAGE_WORDS, RP_COOP_OPS_CAP, RP_COOP_MASKS_CAP, RP_DEFER_CAP, BP_RP_MAX_K, BP_VB_CHUNK};
+    return which >= 0 && which < 6 ? caps[which] : 0u;
+}
+
 // Keccak-f[1600] through the 25-lane phase functions (keccak.h: keccak_f1600_masked_coop's host twin) and through the serial form,
 // with an optional XOR mask on the first nmask words: out_coop / out_serial = the permuted 200-byte states
 void h_keccak_coop(const uint8_t *state200, const uint32_t *mask, uint32_t nmask, uint8_t *out_coop, uint8_t *out_serial) {
