@@ -18,6 +18,7 @@
 #include "../../include/bpgpu.h"
 #include "kernels.h"
 #include "hostrng.h"
+#include "host_io.h"
 
 using namespace bp;
 
@@ -142,17 +143,7 @@ struct bpgpu_ctx {
     hipEvent_t order_ev = nullptr;
     hipStream_t last_stream = nullptr;
     bool have_last = false;
-    // pinned host staging (ragged work decompositions, library-drawn randomness, the host-pointer entry points' IO):
-    // copies out of it are truly asynchronous; pin_ev guards its reuse by the next call
-    char *pin = nullptr;
-    size_t last_secret_bytes = 0;                      // leading bytes of the pinned block that held the last prover call's secrets
-    size_t pin_cap = 0, pin_off = 0, pin_marked = 0;   // pin_marked: bytes already guarded by a recorded pin_ev (pin_mark)
-    hipEvent_t pin_ev = nullptr;
-    bool pin_pending = false;
-    std::vector<char *> pin_retired;         // outgrown mid-call: still referenced by that call, freed at the next one
-    // persistent device-side IO buffer of the host-pointer entry points (no hipMalloc / hipFree per call)
-    char *io_dev = nullptr;
-    size_t io_cap = 0;
+    host_staging io;                         // pinned staging block + persistent device IO buffer of the host-pointer entry points (host_io.h)
     char *ipp_buf = nullptr;                 // term lists of the stand-alone inner-product verifier
     size_t ipp_cap = 0;
     char *rpp_buf = nullptr;                 // working set of the batched range-proof prover
@@ -295,7 +286,6 @@ static int arena_reserve(bpgpu_ctx *c, size_t bytes) {
     c->arena_cap = cap;
     return BPGPU_OK;
 }
-static size_t align_up(size_t x) { return (x + 255) & ~(size_t)255; }
 struct arena_plan {
     size_t total = 0;
     size_t add(size_t bytes) {
@@ -308,7 +298,6 @@ struct arena_plan {
 static uint64_t table_bytes(uint32_t n_gens, uint32_t W);
 
 static int collect_locked(bpgpu_ctx *c);
-static int host_wait(bpgpu_ctx *c, hipStream_t s);
 // ---- ordering of calls on one context (see bpgpu_ctx::order_ev) ----
 // keep_staging: the call continues an earlier one of the same entry point and still holds pointers into the pinned staging
 // buffers (the per-proof fallback of the batch-combined check): nothing retired is freed
@@ -317,14 +306,8 @@ static int ctx_enter(bpgpu_ctx *c, hipStream_t s, bool keep_staging = false) {
         int rcp = collect_locked(c);
         if (rcp) return rcp;
     }
-    c->pin_off = 0;
-    c->pin_marked = 0;
-    if (!c->pin_retired.empty() && !keep_staging) {
-        if (c->pin_pending) HIPCHK(c, hipEventSynchronize(c->pin_ev));
-        c->pin_pending = false;
-        for (char *q : c->pin_retired) hipHostFree(q);
-        c->pin_retired.clear();
-    }
+    int rc = c->io.begin(keep_staging);
+    if (rc) return rc;
     if (c->have_last && c->last_stream != s) HIPCHK(c, hipStreamWaitEvent(s, c->order_ev, 0));
     return BPGPU_OK;
 }
@@ -332,55 +315,7 @@ static int ctx_leave(bpgpu_ctx *c, hipStream_t s) {
     HIPCHK(c, hipEventRecord(c->order_ev, s));
     c->last_stream = s;
     c->have_last = true;
-    if (c->pin_off > c->pin_marked) {   // staged bytes are in flight on s: the next call waits for them before overwriting
-        HIPCHK(c, hipEventRecord(c->pin_ev, s));
-        c->pin_pending = true;
-    }
-    return BPGPU_OK;
-}
-// bump allocation from the pinned staging buffer; the first allocation of a call waits until the previous
-// call's copies out of the buffer are done
-static int pin_alloc(bpgpu_ctx *c, hipStream_t /*s*/, size_t bytes, char **out) {
-    if (c->pin_pending) {
-        HIPCHK(c, hipEventSynchronize(c->pin_ev));
-        c->pin_pending = false;
-    }
-    const size_t need = c->pin_off + align_up(bytes);
-    if (need > c->pin_cap) {
-        if (c->pin && c->pin_off) c->pin_retired.push_back(c->pin);   // earlier pieces of this call stay valid
-        else if (c->pin) HIPCHK(c, hipHostFree(c->pin));
-        c->pin = nullptr;
-        c->pin_cap = 0;
-        const size_t cap = need + need / 2 + (64 << 10);
-        HIPCHK(c, hipHostMalloc((void **)&c->pin, cap, hipHostMallocDefault));
-        c->pin_cap = cap;
-        c->pin_off = 0;
-        c->pin_marked = 0;
-    }
-    *out = c->pin + c->pin_off;
-    c->pin_off += align_up(bytes);
-    return BPGPU_OK;
-}
-// An H2D copy out of the staging buffer has just been enqueued on s and nothing else of this call will touch the bytes
-// allocated so far: record the guard event NOW rather than at the end of the call, so that the next call on this context
-// waits for the copy, not for the whole launch chain behind it (device-pointer calls that stage only their rng bytes or a
-// segment table: with many lanes in flight the host would otherwise stall on every reuse of a lane)
-static int pin_mark(bpgpu_ctx *c, hipStream_t s) {
-    HIPCHK(c, hipEventRecord(c->pin_ev, s));
-    c->pin_pending = true;
-    c->pin_marked = c->pin_off;
-    return BPGPU_OK;
-}
-static int io_reserve(bpgpu_ctx *c, size_t bytes) {
-    if (bytes <= c->io_cap) return BPGPU_OK;
-    HIPCHK(c, hipDeviceSynchronize());
-    if (c->io_dev) HIPCHK(c, hipFree(c->io_dev));
-    c->io_dev = nullptr;
-    c->io_cap = 0;
-    const size_t cap = bytes + bytes / 2 + (64 << 10);
-    HIPCHK(c, hipMalloc((void **)&c->io_dev, cap));
-    c->io_cap = cap;
-    return BPGPU_OK;
+    return c->io.left(s);
 }
 // wait for everything enqueued on s (host-pointer entry points): spin, or sleep on a blocking event
 static int host_wait(bpgpu_ctx *c, hipStream_t s) {
@@ -390,9 +325,14 @@ static int host_wait(bpgpu_ctx *c, hipStream_t s) {
     } else {
         HIPCHK(c, hipStreamSynchronize(s));
     }
-    c->pin_pending = false;
-    c->pin_off = 0;
+    c->io.waited();
     return BPGPU_OK;
+}
+// the device working sets a prover call clears on its way out, besides the IO buffer (host_call::finish)
+static void secret_spans(bpgpu_ctx *c, dev_span b[3]) {
+    b[0] = {c->rpp_buf, c->rpp_cap};
+    b[1] = {c->ipp_buf, c->ipp_cap};
+    b[2] = {c->arena, c->arena_cap};
 }
 static int os_random(bpgpu_ctx *c, char *dst, size_t bytes);
 // finish a submitted call: wait for its stream work and hand the results to the caller's buffers
@@ -420,9 +360,11 @@ int bpgpu_ctx_create(int device, bpgpu_ctx **out) {
     if (hipSetDevice(device) != hipSuccess) return BPGPU_ERR_NO_DEVICE;
     bpgpu_ctx *c = new bpgpu_ctx();
     c->device = device;
+    c->io.err = &c->err;
+    c->io.hip_err_code = BPGPU_ERR_HIP;
     if (hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess ||
         hipEventCreateWithFlags(&c->order_ev, hipEventDisableTiming) != hipSuccess ||
-        hipEventCreateWithFlags(&c->pin_ev, hipEventDisableTiming) != hipSuccess ||
+        hipEventCreateWithFlags(&c->io.pin_ev, hipEventDisableTiming) != hipSuccess ||
         hipEventCreateWithFlags(&c->done_ev, hipEventDisableTiming | hipEventBlockingSync) != hipSuccess ||
         hipStreamCreateWithFlags(&c->stream2, hipStreamNonBlocking) != hipSuccess ||
         hipEventCreateWithFlags(&c->fork_ev, hipEventDisableTiming) != hipSuccess ||
@@ -456,14 +398,11 @@ void bpgpu_ctx_destroy(bpgpu_ctx *c) {
     for (auto &kv : c->plan_cache) hipFree(kv.second.mem);
     for (char *q : c->plan_retired) hipFree(q);
     if (c->arena) hipFree(c->arena);
-    if (c->io_dev) hipFree(c->io_dev);
+    c->io.release();
     if (c->ipp_buf) hipFree(c->ipp_buf);
     if (c->rpp_buf) hipFree(c->rpp_buf);
     if (c->comb_buf) hipFree(c->comb_buf);
-    if (c->pin) hipHostFree(c->pin);
-    for (char *q : c->pin_retired) hipHostFree(q);
     if (c->order_ev) hipEventDestroy(c->order_ev);
-    if (c->pin_ev) hipEventDestroy(c->pin_ev);
     if (c->done_ev) hipEventDestroy(c->done_ev);
     if (c->fork_ev) hipEventDestroy(c->fork_ev);
     if (c->join_ev) hipEventDestroy(c->join_ev);
@@ -647,12 +586,12 @@ int bpgpu_ctx_get_option(bpgpu_ctx *c, const char *key, int64_t *value) {
     else if (!strcmp(key, "r1cs_rlc_max_terms")) *value = c->r1cs_rlc_max_terms ? c->r1cs_rlc_max_terms : R1_RLC_MAX_TERMS;
     else if (!strcmp(key, "staging_residue")) {
         // test hook: non-zero bytes left in the persistent staging buffers (pinned block, device IO buffer, prover working sets,
-        // arena) -- 0 after a prover entry point has returned (prover_exit)
+        // arena) -- 0 after a prover entry point has returned (host_call::finish)
         if (hipSetDevice(c->device) != hipSuccess || hipDeviceSynchronize() != hipSuccess) return fail(c, BPGPU_ERR_HIP, "synchronize failed");
         int64_t nz = 0;
-        for (size_t i = 0; i < c->pin_cap && i < c->last_secret_bytes; i++) nz += c->pin[i] != 0;   // (behind the secrets: public outputs)
+        for (size_t i = 0; i < c->io.pin_cap && i < c->io.last_secret_bytes; i++) nz += c->io.pin[i] != 0;   // (behind the secrets: public outputs)
         std::vector<char> tmp;
-        const std::pair<const char *, size_t> bufs[4] = {{c->io_dev, c->io_cap}, {c->rpp_buf, c->rpp_cap}, {c->ipp_buf, c->ipp_cap}, {c->arena, c->arena_cap}};
+        const std::pair<const char *, size_t> bufs[4] = {{c->io.io_dev, c->io.io_cap}, {c->rpp_buf, c->rpp_cap}, {c->ipp_buf, c->ipp_cap}, {c->arena, c->arena_cap}};
         for (const auto &b : bufs) {
             if (!b.first || !b.second) continue;
             tmp.resize(b.second);
@@ -1076,7 +1015,7 @@ static int enqueue_vb(bpgpu_ctx *c, hipStream_t s, const vb_plan &pl, size_t nba
     // the plan is a local of the caller: stage it in pinned memory, which outlives the asynchronous copies
     const size_t b0 = pl.chunks.size() * sizeof(vb_chunk), b1 = (size_t)pl.total * 4, b2 = (nbatch + 1) * 4;
     char *h = nullptr;
-    int rc = pin_alloc(c, s, align_up(b0) + align_up(b1) + align_up(b2), &h);
+    int rc = c->io.pin_alloc(align_up(b0) + align_up(b1) + align_up(b2), &h);
     if (rc) return rc;
     char *h0 = h, *h1 = h0 + align_up(b0), *h2 = h1 + align_up(b1);
     if (!pl.chunks.empty()) {
@@ -1238,7 +1177,7 @@ static void enqueue_bucket_reduce(bpgpu_ctx *c, hipStream_t s, bk_params prm, ui
 // first-term offsets of the MSMs -> device (through pinned staging)
 static int bucket_upload_first(bpgpu_ctx *c, hipStream_t s, size_t nmsm, const uint32_t *n_terms, size_t uniform_per, bk_dev &d) {
     char *h = nullptr;
-    int rc = pin_alloc(c, s, (nmsm + 1) * 4, &h);
+    int rc = c->io.pin_alloc((nmsm + 1) * 4, &h);
     if (rc) return rc;
     uint32_t *f = (uint32_t *)h;
     uint32_t t0 = 0;
@@ -1457,28 +1396,21 @@ extern "C" int bpgpu_msm_batch(bpgpu_ctx *c, size_t nbatch, const uint32_t *n_te
     if (total && (!scalars || !points)) return BPGPU_ERR_INVALID_ARG;
     if (nbatch > 0x7fffffffu / 64 || total > 0x7fffffffu / 64) return fail(c, BPGPU_ERR_INVALID_ARG, "batch too large");
     // persistent device IO buffer + pinned staging: no allocation in steady state, one wait at the end
-    const size_t sz_terms = align_up(total * 32 + 16), sz_out = align_up(nbatch * 32), sz_st = align_up(nbatch);
     hipStream_t s = c->stream;
-    int rc = ctx_enter(c, s);
+    host_call<bpgpu_ctx> io(c, s);
+    const int r_s = io.in(total * 32 + 16), r_p = io.in(total * 32 + 16), r_o = io.out(nbatch * 32), r_st = io.out(nbatch);
+    int rc = io.open();
     if (rc) return rc;
-    rc = io_reserve(c, 2 * sz_terms + sz_out + sz_st);
-    if (rc) return rc;
-    char *h = nullptr;
-    rc = pin_alloc(c, s, 2 * sz_terms + sz_out + sz_st, &h);
-    if (rc) return rc;
-    char *d_s = c->io_dev, *d_p = d_s + sz_terms, *d_o = d_p + sz_terms;
-    char *h_o = h + 2 * sz_terms;
     if (total) {
-        memcpy(h, scalars, total * 32);
-        memcpy(h + sz_terms, points, total * 32);
-        HIPCHK(c, hipMemcpyAsync(d_s, h, 2 * sz_terms, hipMemcpyHostToDevice, s));
+        io.put(r_s, scalars, total * 32);
+        io.put(r_p, points, total * 32);
+        rc = io.upload();
     }
-    rc = msm_batch_dev_locked(c, nbatch, n_terms, d_s, d_p, d_o, d_o + sz_out, s);
-    if (!rc && hipMemcpyAsync(h_o, d_o, sz_out + sz_st, hipMemcpyDeviceToHost, s) != hipSuccess) rc = fail(c, BPGPU_ERR_HIP, "D2H copy failed");
-    const int rc2 = ctx_leave(c, s), rc3 = host_wait(c, s);
-    if (rc || rc2 || rc3) return rc ? rc : (rc2 ? rc2 : rc3);
-    memcpy(out, h_o, nbatch * 32);
-    memcpy(status, h_o + sz_out, nbatch);
+    if (!rc) rc = msm_batch_dev_locked(c, nbatch, n_terms, io.d(r_s), io.d(r_p), io.d(r_o), io.d(r_st), s);
+    rc = io.finish(io.download(rc));
+    if (rc) return rc;
+    memcpy(out, io.h(r_o), nbatch * 32);
+    memcpy(status, io.h(r_st), nbatch);
     return BPGPU_OK;
 }
 
@@ -1717,29 +1649,22 @@ extern "C" int bpgpu_msm_batch_shared(bpgpu_ctx *c, size_t n, size_t m, size_t n
     std::lock_guard<std::mutex> lk(c->mu);
     HIPCHK(c, hipSetDevice(c->device));
     const size_t ng = (2 * n * m + 2) * nbatch * 32, nu = n_unique * nbatch * 32;
-    const size_t sz_g = align_up(ng + 16), sz_u = align_up(nu + 16), sz_out = align_up(nbatch * 32), sz_st = align_up(nbatch);
     hipStream_t s = c->stream;
-    int rc = ctx_enter(c, s);
+    host_call<bpgpu_ctx> io(c, s);
+    const int r_g = io.in(ng + 16), r_us = io.in(nu + 16), r_up = io.in(nu + 16), r_o = io.out(nbatch * 32), r_st = io.out(nbatch);
+    int rc = io.open();
     if (rc) return rc;
-    rc = io_reserve(c, sz_g + 2 * sz_u + sz_out + sz_st);
-    if (rc) return rc;
-    char *h = nullptr;
-    rc = pin_alloc(c, s, sz_g + 2 * sz_u + sz_out + sz_st, &h);
-    if (rc) return rc;
-    char *d_g = c->io_dev, *d_us = d_g + sz_g, *d_up = d_us + sz_u, *d_o = d_up + sz_u;
-    char *h_o = h + sz_g + 2 * sz_u;
-    memcpy(h, gen_scalars, ng);
+    io.put(r_g, gen_scalars, ng);
     if (nu) {
-        memcpy(h + sz_g, uniq_scalars, nu);
-        memcpy(h + sz_g + sz_u, uniq_points, nu);
+        io.put(r_us, uniq_scalars, nu);
+        io.put(r_up, uniq_points, nu);
     }
-    HIPCHK(c, hipMemcpyAsync(d_g, h, sz_g + 2 * sz_u, hipMemcpyHostToDevice, s));
-    rc = msm_shared_dev_locked(c, n, m, nbatch, n_unique, d_g, d_us, d_up, d_o, d_o + sz_out, nullptr, s);
-    if (!rc && hipMemcpyAsync(h_o, d_o, sz_out + sz_st, hipMemcpyDeviceToHost, s) != hipSuccess) rc = fail(c, BPGPU_ERR_HIP, "D2H copy failed");
-    const int rc2 = ctx_leave(c, s), rc3 = host_wait(c, s);
-    if (rc || rc2 || rc3) return rc ? rc : (rc2 ? rc2 : rc3);
-    memcpy(out, h_o, nbatch * 32);
-    memcpy(status, h_o + sz_out, nbatch);
+    rc = io.upload();
+    if (!rc) rc = msm_shared_dev_locked(c, n, m, nbatch, n_unique, io.d(r_g), io.d(r_us), io.d(r_up), io.d(r_o), io.d(r_st), nullptr, s);
+    rc = io.finish(io.download(rc));
+    if (rc) return rc;
+    memcpy(out, io.h(r_o), nbatch * 32);
+    memcpy(status, io.h(r_st), nbatch);
     return BPGPU_OK;
 }
 
@@ -1926,7 +1851,7 @@ static int script_for(bpgpu_ctx *c, hipStream_t s, uint32_t n, uint32_t m, uint3
             ent.cap = cap;
         }
         char *h = nullptr;
-        const int rc = pin_alloc(c, s, bytes, &h);
+        const int rc = c->io.pin_alloc(bytes, &h);
         if (rc) {
             c->script_retired.push_back(ent.mem);
             return rc;
@@ -2042,7 +1967,7 @@ static int rp_verify_dev_locked(bpgpu_ctx *c, size_t n, size_t m, size_t nbatch,
             if (tr.d_ts_in) HIPCHK(c, hipMemcpyAsync(tr.d_ts_out, tr.d_ts_in, nbatch * BPGPU_TRANSCRIPT_BYTES, hipMemcpyDeviceToDevice, s));
             else {
                 char *h = nullptr;
-                int rcp = pin_alloc(c, s, nbatch * BPGPU_TRANSCRIPT_BYTES, &h);
+                int rcp = c->io.pin_alloc(nbatch * BPGPU_TRANSCRIPT_BYTES, &h);
                 if (rcp) return rcp;
                 uint8_t st0[BPGPU_TRANSCRIPT_BYTES];
                 if (tr.shared_ts) memcpy(st0, tr.shared_ts, BPGPU_TRANSCRIPT_BYTES);
@@ -2205,7 +2130,7 @@ static int rp_verify_dev_locked(bpgpu_ctx *c, size_t n, size_t m, size_t nbatch,
     memset(&segtab, 0, sizeof segtab);
     if (own_inits) {   // Transcript::new(label) + rangeproof_domain_sep(n, m) of every distinct label: 50 sponge words each, staged ahead of the chain
         char *h = nullptr;
-        rc = pin_alloc(c, s, distinct_labels.size() * 256, &h);
+        rc = c->io.pin_alloc(distinct_labels.size() * 256, &h);
         if (rc) return rc;
         for (size_t j = 0; j < distinct_labels.size(); j++) {
             rp_strobe_init ij;
@@ -2223,7 +2148,7 @@ static int rp_verify_dev_locked(bpgpu_ctx *c, size_t n, size_t m, size_t nbatch,
         seg_fix(segtab.in);
     } else if (h_segs) {
         char *h = nullptr;
-        rc = pin_alloc(c, s, (size_t)nseg * sizeof(rp_seg), &h);
+        rc = c->io.pin_alloc((size_t)nseg * sizeof(rp_seg), &h);
         if (rc) return rc;
         memcpy(h, h_segs, (size_t)nseg * sizeof(rp_seg));
         seg_fix((rp_seg *)h);
@@ -2257,8 +2182,8 @@ static int rp_verify_dev_locked(bpgpu_ctx *c, size_t n, size_t m, size_t nbatch,
         rc = script_for(c, s, sh.n, sh.m, sh.k, init, (ts_flags & BP_TS_DOMSEP) != 0, &d_script);
         if (rc) return rc;
     }
-    if (c->pin_off > c->pin_marked && dev_call) {   // rng / weights / segment table / a new transcript script staged above, nothing else will be
-        rc = pin_mark(c, s);
+    if (c->io.pin_off > c->io.pin_marked && dev_call) {   // rng / weights / segment table / a new transcript script staged above, nothing else will be
+        rc = c->io.pin_mark(s);
         if (rc) return rc;
     }
     if (c->rp_status_dirty) {   // (a chain whose enqueue failed half way: its status words and arrival counters were not handed back clean)
@@ -2655,69 +2580,50 @@ static int rp_host_call(bpgpu_ctx *c, size_t n, size_t m, size_t nbatch, const u
     std::lock_guard<std::mutex> lk(c->mu);
     HIPCHK(c, hipSetDevice(c->device));
     const size_t TS = BPGPU_TRANSCRIPT_BYTES;
-    const size_t sz_p = align_up(nbatch * proof_len + 64), sz_c = align_up(nbatch * m * 32 + 64), sz_r = rng64 ? align_up(nbatch * 64) : 0,
-                 sz_w = weights64 ? align_up(nbatch * 64) : 0, sz_ti = ts_in_host ? align_up(nbatch * TS) : 0;
-    const size_t sz_in = sz_p + sz_c + sz_r + sz_w + sz_ti;
-    const size_t sz_v = align_up(nbatch), sz_o = msm_out ? align_up(nbatch * 32) : 0, sz_b = rlc ? align_up(64) : 0,
-                 sz_to = ts_out_host ? align_up(nbatch * TS) : 0;
-    const size_t sz_out = sz_v + sz_o + sz_b + sz_to;
     hipStream_t s = c->stream;
-    int rc = ctx_enter(c, s);
+    host_call<bpgpu_ctx> io(c, s);
+    const int r_p = io.in(nbatch * proof_len + 64), r_c = io.in(nbatch * m * 32 + 64), r_r = io.in(rng64 ? nbatch * 64 : 0),
+              r_w = io.in(weights64 ? nbatch * 64 : 0), r_ti = io.in(ts_in_host ? nbatch * TS : 0);
+    const int r_v = io.out(nbatch), r_o = io.out(msm_out ? nbatch * 32 : 0), r_b = io.out(rlc ? 64 : 0), r_to = io.out(ts_out_host ? nbatch * TS : 0);
+    int rc = io.open();
     if (rc) return rc;
-    rc = io_reserve(c, sz_in + sz_out);
-    if (rc) return rc;
-    char *h = nullptr;
-    rc = pin_alloc(c, s, sz_in + sz_out, &h);
-    if (rc) return rc;
-    char *d = c->io_dev;
-    char *d_p = d, *d_c = d_p + sz_p, *d_r = d_c + sz_c, *d_w = d_r + sz_r, *d_ti = d_w + sz_w;
-    char *d_v = d + sz_in, *d_o = d_v + sz_v, *d_b = d_o + sz_o, *d_to = d_b + sz_b;
-    memcpy(h, proofs, nbatch * proof_len);
-    if (m) memcpy(h + sz_p, commitments, nbatch * m * 32);
-    if (rng64) memcpy(h + sz_p + sz_c, rng64, nbatch * 64);
-    if (weights64) memcpy(h + sz_p + sz_c + sz_r, weights64, nbatch * 64);
-    if (ts_in_host) memcpy(h + sz_p + sz_c + sz_r + sz_w, ts_in_host, nbatch * TS);
-    HIPCHK(c, hipMemcpyAsync(d, h, sz_in, hipMemcpyHostToDevice, s));
-    tr.d_ts_in = ts_in_host ? d_ti : nullptr;
-    tr.d_ts_out = ts_out_host ? d_to : nullptr;
-    char *h_out = h + sz_in;
-    rc = rp_verify_dev_locked(c, n, m, nbatch, d_p, proof_len, d_c, tr, rng64 ? d_r : nullptr, d_v, msm_out ? d_o : nullptr, s, rlc,
-                              weights64 ? d_w : nullptr, rlc ? d_b : nullptr);
-    if (!rc && hipMemcpyAsync(h_out, d_v, sz_out, hipMemcpyDeviceToHost, s) != hipSuccess) rc = fail(c, BPGPU_ERR_HIP, "D2H copy failed");
+    io.put(r_p, proofs, nbatch * proof_len);
+    if (m) io.put(r_c, commitments, nbatch * m * 32);
+    if (rng64) io.put(r_r, rng64, nbatch * 64);
+    if (weights64) io.put(r_w, weights64, nbatch * 64);
+    if (ts_in_host) io.put(r_ti, ts_in_host, nbatch * TS);
+    tr.d_ts_in = ts_in_host ? io.d(r_ti) : nullptr;
+    tr.d_ts_out = ts_out_host ? io.d(r_to) : nullptr;
+    char *d_rng = rng64 ? io.d(r_r) : nullptr;
+    rc = io.upload();
+    if (!rc)
+        rc = rp_verify_dev_locked(c, n, m, nbatch, io.d(r_p), proof_len, io.d(r_c), tr, d_rng, io.d(r_v), msm_out ? io.d(r_o) : nullptr, s, rlc,
+                                  weights64 ? io.d(r_w) : nullptr, rlc ? io.d(r_b) : nullptr);
+    rc = io.download(rc);
     if (submit && !rc) {   // asynchronous form: leave the results in flight; bpgpu_ctx_collect (or the next call) delivers them
-        const int rcl = ctx_leave(c, s);
+        const int rcl = io.leave_in_flight();
         if (rcl) return rcl;
         c->pend.active = true;
-        c->pend.h_out = h_out;
+        c->pend.h_out = io.h(r_v);
         c->pend.nbatch = nbatch;
-        c->pend.off_msm = sz_v;
-        c->pend.off_ts = sz_v + sz_o + sz_b;
+        c->pend.off_msm = io.off[r_o] - io.off[r_v];
+        c->pend.off_ts = io.off[r_to] - io.off[r_v];
         c->pend.verdict = verdict;
         c->pend.msm_out = msm_out;
         c->pend.ts_out = ts_out_host;
         return BPGPU_OK;
     }
-    int rc2 = ctx_leave(c, s), rc3 = host_wait(c, s);
-    if (rc || rc2 || rc3) return rc ? rc : (rc2 ? rc2 : rc3);
-    if (rlc && (uint8_t)h_out[sz_v + sz_o] != 0) {
+    rc = io.finish(rc);
+    if (rc) return rc;
+    if (rlc && (uint8_t)io.h(r_b)[0] != 0) {
         // the combination is not the identity: some proof fails -- find out which, proof by proof (inputs are still on the device)
-        uint8_t bo[33];
-        memcpy(bo, h_out + sz_v + sz_o, 33);
-        // h_out may sit in a buffer that the first pass outgrew (its nested allocations for library-drawn rng / weights)
-        // and retired: it must stay alive until the verdicts below have been copied out of it
-        rc = ctx_enter(c, s, true);
+        rc = io.rerun_per_proof(r_v, r_b, [&] { return rp_verify_dev_locked(c, n, m, nbatch, io.d(r_p), proof_len, io.d(r_c), tr, d_rng, io.d(r_v), nullptr, s); });
         if (rc) return rc;
-        rc = rp_verify_dev_locked(c, n, m, nbatch, d_p, proof_len, d_c, tr, rng64 ? d_r : nullptr, d_v, nullptr, s);
-        if (!rc && hipMemcpyAsync(h_out, d_v, sz_v, hipMemcpyDeviceToHost, s) != hipSuccess) rc = fail(c, BPGPU_ERR_HIP, "D2H copy failed");
-        rc2 = ctx_leave(c, s);
-        rc3 = host_wait(c, s);
-        if (rc || rc2 || rc3) return rc ? rc : (rc2 ? rc2 : rc3);
-        memcpy(h_out + sz_v + sz_o, bo, 33);
     }
-    memcpy(verdict, h_out, nbatch);
-    if (msm_out) memcpy(msm_out, h_out + sz_v, nbatch * 32);
-    if (rlc && batch_out) memcpy(batch_out, h_out + sz_v + sz_o, 33);
-    if (ts_out_host) memcpy(ts_out_host, h_out + sz_v + sz_o + sz_b, nbatch * TS);
+    memcpy(verdict, io.h(r_v), nbatch);
+    if (msm_out) memcpy(msm_out, io.h(r_o), nbatch * 32);
+    if (rlc && batch_out) memcpy(batch_out, io.h(r_b), 33);
+    if (ts_out_host) memcpy(ts_out_host, io.h(r_to), nbatch * TS);
     return BPGPU_OK;
 }
 
@@ -2947,26 +2853,19 @@ extern "C" int bpgpu_ipp_verification_scalars(bpgpu_ctx *c, size_t n, size_t nba
     sh.shape_verdict = shape_bad ? BPGPU_VERDICT_VERIFICATION_ERROR : 0;
     sh.bases_shared = 0;
     const size_t n_eff = shape_bad ? 0 : n, TS = BPGPU_TRANSCRIPT_BYTES;
-    const size_t sz_pr = align_up(nbatch * proof_len + 64), sz_ti = per_proof ? align_up(nbatch * TS) : 0;
-    const size_t sz_in = sz_pr + sz_ti;
-    const size_t sz_u = align_up(nbatch * (k ? k : 1) * 32), sz_s = align_up(nbatch * (n_eff ? n_eff : 1) * 32), sz_to = transcripts_out ? align_up(nbatch * TS) : 0,
-                 sz_st = align_up(nbatch * 4);
-    const size_t sz_out = 2 * sz_u + sz_s + sz_to + sz_st;
-    const size_t sz_tab = align_up(nbatch * (k ? k : 1) * 2 * 40);
     hipStream_t s = c->stream;
-    int rc = ctx_enter(c, s);
-    if (rc) return rc;
-    char *h = nullptr;
+    host_call<bpgpu_ctx> io(c, s);
+    const int r_pr = io.in(nbatch * proof_len + 64), r_ti = io.in(per_proof ? nbatch * TS : 0);
+    const int r_us = io.out(nbatch * (k ? k : 1) * 32), r_ui = io.out(nbatch * (k ? k : 1) * 32), r_s = io.out(nbatch * (n_eff ? n_eff : 1) * 32),
+              r_to = io.out(transcripts_out ? nbatch * TS : 0), r_st = io.out(nbatch * 4);
+    const int r_tab = io.dev(nbatch * (k ? k : 1) * 2 * 40);
+    int rc = io.open();
     do {
-        rc = io_reserve(c, sz_in + sz_out + sz_tab);
         if (rc) break;
-        rc = pin_alloc(c, s, sz_in + sz_out, &h);
-        if (rc) break;
-        char *d = c->io_dev;
-        char *d_pr = d, *d_ti = d + sz_pr, *d_us = d + sz_in, *d_ui = d_us + sz_u, *d_s = d_ui + sz_u, *d_to = d_s + sz_s, *d_st = d_to + sz_to, *d_tab = d + sz_in + sz_out;
-        memcpy(h, proofs, nbatch * proof_len);
-        if (per_proof) memcpy(h + sz_pr, transcripts, nbatch * TS);
-        if (hipMemcpyAsync(d, h, sz_in, hipMemcpyHostToDevice, s) != hipSuccess || hipMemsetAsync(d_us, 0, sz_out, s) != hipSuccess) {
+        char *d_pr = io.d(r_pr), *d_ti = io.d(r_ti), *d_us = io.d(r_us), *d_ui = io.d(r_ui), *d_s = io.d(r_s), *d_to = io.d(r_to), *d_st = io.d(r_st), *d_tab = io.d(r_tab);
+        io.put(r_pr, proofs, nbatch * proof_len);
+        if (per_proof) io.put(r_ti, transcripts, nbatch * TS);
+        if (io.upload() || hipMemsetAsync(d_us, 0, io.out_bytes(), s) != hipSuccess) {
             rc = fail(c, BPGPU_ERR_HIP, "staging failed");
             break;
         }
@@ -2983,16 +2882,15 @@ extern "C" int bpgpu_ipp_verification_scalars(bpgpu_ctx *c, size_t n, size_t nba
             const uint32_t nt = (uint32_t)(n_eff * nbatch);
             LAUNCH(c, s, "ipp_vs_s", k_ipp_vs_s, (nt + 63) / 64, 64, nt, sh, (const uint32_t *)d_tab, (const uint32_t *)d_st, (uint32_t *)d_s);
         }
-        if (hipMemcpyAsync(h + sz_in, d_us, sz_out, hipMemcpyDeviceToHost, s) != hipSuccess) rc = fail(c, BPGPU_ERR_HIP, "D2H copy failed");
+        rc = io.download(0);
     } while (0);
-    const int rc2 = ctx_leave(c, s), rc3 = host_wait(c, s);
-    if (rc || rc2 || rc3) return rc ? rc : (rc2 ? rc2 : rc3);
-    const char *ho = h + sz_in;
-    memcpy(u_sq, ho, nbatch * k * 32);
-    memcpy(u_inv_sq, ho + sz_u, nbatch * k * 32);
-    if (n_eff) memcpy(s_out, ho + 2 * sz_u, nbatch * n_eff * 32);
-    if (transcripts_out) memcpy(transcripts_out, ho + 2 * sz_u + sz_s, nbatch * TS);
-    const uint32_t *st32 = (const uint32_t *)(ho + 2 * sz_u + sz_s + sz_to);
+    rc = io.finish(rc);
+    if (rc) return rc;
+    memcpy(u_sq, io.h(r_us), nbatch * k * 32);
+    memcpy(u_inv_sq, io.h(r_ui), nbatch * k * 32);
+    if (n_eff) memcpy(s_out, io.h(r_s), nbatch * n_eff * 32);
+    if (transcripts_out) memcpy(transcripts_out, io.h(r_to), nbatch * TS);
+    const uint32_t *st32 = (const uint32_t *)io.h(r_st);
     for (size_t b = 0; b < nbatch; b++) {
         status[b] = (uint8_t)st32[b];
         // (with one start state for the batch the device replays from the state BEHIND the domain separator: where the reference never
@@ -3010,36 +2908,30 @@ extern "C" int bpgpu_ipp_verify_batch(bpgpu_ctx *c, size_t n, size_t nbatch, con
     if (!proofs || !verdict || !P || !Q || (n && (!G_factors || !H_factors || !G || !H))) return BPGPU_ERR_INVALID_ARG;
     std::lock_guard<std::mutex> lk(c->mu);
     HIPCHK(c, hipSetDevice(c->device));
-    const size_t sz_pr = align_up(nbatch * proof_len + 64), sz_f = align_up(nbatch * n * 32 + 64), sz_pq = align_up(nbatch * 32 + 64);
-    const size_t sz_in = sz_pr + 4 * sz_f + 2 * sz_pq, sz_v = align_up(nbatch), sz_o = align_up(nbatch * 32);
     hipStream_t s = c->stream;
-    int rc = ctx_enter(c, s);
+    host_call<bpgpu_ctx> io(c, s);
+    const size_t b_f = nbatch * n * 32 + 64, b_pq = nbatch * 32 + 64;
+    const int r_pr = io.in(nbatch * proof_len + 64), r_gf = io.in(b_f), r_hf = io.in(b_f), r_g = io.in(b_f), r_h = io.in(b_f), r_p = io.in(b_pq), r_q = io.in(b_pq);
+    const int r_v = io.out(nbatch), r_o = io.out(nbatch * 32);
+    int rc = io.open();
     if (rc) return rc;
-    rc = io_reserve(c, sz_in + sz_v + sz_o);
-    if (rc) return rc;
-    char *h = nullptr;
-    rc = pin_alloc(c, s, sz_in + sz_v + sz_o, &h);
-    if (rc) return rc;
-    char *d = c->io_dev;
-    char *d_pr = d, *d_gf = d_pr + sz_pr, *d_hf = d_gf + sz_f, *d_g = d_hf + sz_f, *d_h = d_g + sz_f, *d_p = d_h + sz_f, *d_q = d_p + sz_pq;
-    char *d_v = d + sz_in, *d_o = d_v + sz_v;
-    memcpy(h, proofs, nbatch * proof_len);
+    io.put(r_pr, proofs, nbatch * proof_len);
     if (n) {
-        memcpy(h + sz_pr, G_factors, nbatch * n * 32);
-        memcpy(h + sz_pr + sz_f, H_factors, nbatch * n * 32);
-        memcpy(h + sz_pr + 2 * sz_f, G, nbatch * n * 32);
-        memcpy(h + sz_pr + 3 * sz_f, H, nbatch * n * 32);
+        io.put(r_gf, G_factors, nbatch * n * 32);
+        io.put(r_hf, H_factors, nbatch * n * 32);
+        io.put(r_g, G, nbatch * n * 32);
+        io.put(r_h, H, nbatch * n * 32);
     }
-    memcpy(h + sz_pr + 4 * sz_f, P, nbatch * 32);
-    memcpy(h + sz_pr + 4 * sz_f + sz_pq, Q, nbatch * 32);
-    HIPCHK(c, hipMemcpyAsync(d, h, sz_in, hipMemcpyHostToDevice, s));
-    rc = ipp_verify_dev_locked(c, n, nbatch, d_pr, proof_len, label, label_len, nullptr, d_gf, d_hf, d_p, d_q, d_g, d_h, 0, d_v, d_o, s);
-    char *h_out = h + sz_in;
-    if (!rc && hipMemcpyAsync(h_out, d_v, sz_v + sz_o, hipMemcpyDeviceToHost, s) != hipSuccess) rc = fail(c, BPGPU_ERR_HIP, "D2H copy failed");
-    const int rc2 = ctx_leave(c, s), rc3 = host_wait(c, s);
-    if (rc || rc2 || rc3) return rc ? rc : (rc2 ? rc2 : rc3);
-    memcpy(verdict, h_out, nbatch);
-    if (msm_out) memcpy(msm_out, h_out + sz_v, nbatch * 32);
+    io.put(r_p, P, nbatch * 32);
+    io.put(r_q, Q, nbatch * 32);
+    rc = io.upload();
+    if (!rc)
+        rc = ipp_verify_dev_locked(c, n, nbatch, io.d(r_pr), proof_len, label, label_len, nullptr, io.d(r_gf), io.d(r_hf), io.d(r_p), io.d(r_q), io.d(r_g), io.d(r_h), 0,
+                                   io.d(r_v), io.d(r_o), s);
+    rc = io.finish(io.download(rc));
+    if (rc) return rc;
+    memcpy(verdict, io.h(r_v), nbatch);
+    if (msm_out) memcpy(msm_out, io.h(r_o), nbatch * 32);
     return BPGPU_OK;
 }
 
@@ -3194,41 +3086,32 @@ extern "C" int bpgpu_linear_verify_batch(bpgpu_ctx *c, size_t n, size_t nbatch, 
     std::lock_guard<std::mutex> lk(c->mu);
     HIPCHK(c, hipSetDevice(c->device));
     const size_t nb_b = b_shared ? 1 : nbatch;
-    const size_t sz_pr = align_up(nbatch * proof_len + 64), sz_c = align_up(nbatch * 32 + 64), sz_g = align_up(n * 32 + 64), sz_fb = align_up(64 + 64),
-                 sz_bv = align_up(nb_b * n * 32 + 64);
-    const size_t sz_in = sz_pr + sz_c + sz_g + sz_fb + sz_bv, sz_v = align_up(nbatch), sz_o = align_up(nbatch * 32);
-    const size_t sz_t = transcripts_out ? align_up(nbatch * BPGPU_TRANSCRIPT_BYTES) : 0;
     hipStream_t s = c->stream;
-    int rc = ctx_enter(c, s);
+    host_call<bpgpu_ctx> io(c, s);
+    const int r_pr = io.in(nbatch * proof_len + 64), r_c = io.in(nbatch * 32 + 64), r_g = io.in(n * 32 + 64), r_fb = io.in(64 + 64), r_bv = io.in(nb_b * n * 32 + 64);
+    const int r_v = io.out(nbatch), r_o = io.out(nbatch * 32), r_t = io.out(transcripts_out ? nbatch * BPGPU_TRANSCRIPT_BYTES : 0);
+    int rc = io.open();
     if (rc) return rc;
-    rc = io_reserve(c, sz_in + sz_v + sz_o + sz_t);
-    if (rc) return rc;
-    char *h = nullptr;
-    rc = pin_alloc(c, s, sz_in + sz_v + sz_o + sz_t, &h);
-    if (rc) return rc;
-    char *d = c->io_dev;
-    char *d_pr = d, *d_c = d_pr + sz_pr, *d_g = d_c + sz_c, *d_fb = d_g + sz_g, *d_bv = d_fb + sz_fb, *d_v = d + sz_in, *d_o = d_v + sz_v;
-    char *d_t = transcripts_out ? d_o + sz_o : nullptr;
-    memcpy(h, proofs, nbatch * proof_len);
-    memcpy(h + sz_pr, C, nbatch * 32);
+    io.put(r_pr, proofs, nbatch * proof_len);
+    io.put(r_c, C, nbatch * 32);
     if (n) {
-        if (!from_gens) memcpy(h + sz_pr + sz_c, G, n * 32);
-        memcpy(h + sz_pr + sz_c + sz_g + sz_fb, b, nb_b * n * 32);
+        if (!from_gens) io.put(r_g, G, n * 32);
+        io.put(r_bv, b, nb_b * n * 32);
     }
     if (!from_gens) {
-        memcpy(h + sz_pr + sz_c + sz_g, F, 32);
-        memcpy(h + sz_pr + sz_c + sz_g + 32, B, 32);
+        memcpy(io.h(r_fb), F, 32);
+        memcpy(io.h(r_fb) + 32, B, 32);
     }
-    HIPCHK(c, hipMemcpyAsync(d, h, sz_in, hipMemcpyHostToDevice, s));
-    rc = lin_verify_dev_locked(c, n, nbatch, d_pr, proof_len, label, label_len, shared_transcript, d_c, from_gens ? nullptr : d_g,
-                               from_gens ? nullptr : d_fb, from_gens ? nullptr : d_fb + 32, d_bv, b_shared, d_v, d_o, d_t, s);
-    char *h_out = h + sz_in;
-    if (!rc && hipMemcpyAsync(h_out, d_v, sz_v + sz_o + sz_t, hipMemcpyDeviceToHost, s) != hipSuccess) rc = fail(c, BPGPU_ERR_HIP, "D2H copy failed");
-    const int rc2 = ctx_leave(c, s), rc3 = host_wait(c, s);
-    if (rc || rc2 || rc3) return rc ? rc : (rc2 ? rc2 : rc3);
-    memcpy(verdict, h_out, nbatch);
-    if (msm_out) memcpy(msm_out, h_out + sz_v, nbatch * 32);
-    if (transcripts_out) memcpy(transcripts_out, h_out + sz_v + sz_o, nbatch * BPGPU_TRANSCRIPT_BYTES);
+    rc = io.upload();
+    if (!rc)
+        rc = lin_verify_dev_locked(c, n, nbatch, io.d(r_pr), proof_len, label, label_len, shared_transcript, io.d(r_c), from_gens ? nullptr : io.d(r_g),
+                                   from_gens ? nullptr : io.d(r_fb), from_gens ? nullptr : io.d(r_fb) + 32, io.d(r_bv), b_shared, io.d(r_v), io.d(r_o),
+                                   transcripts_out ? io.d(r_t) : nullptr, s);
+    rc = io.finish(io.download(rc));
+    if (rc) return rc;
+    memcpy(verdict, io.h(r_v), nbatch);
+    if (msm_out) memcpy(msm_out, io.h(r_o), nbatch * 32);
+    if (transcripts_out) memcpy(transcripts_out, io.h(r_t), nbatch * BPGPU_TRANSCRIPT_BYTES);
     return BPGPU_OK;
 }
 
@@ -3251,26 +3134,22 @@ extern "C" int bpgpu_rangeproof_audit_shares(bpgpu_ctx *c, size_t n, size_t nsha
         return BPGPU_OK;
     }
     hipStream_t s = c->stream;
-    int rc = ctx_enter(c, s);
-    if (rc) return rc;
     const size_t share_len = 32 * (3 + 2 * n), nch = challenges_shared ? 1 : nshares;
-    const size_t sz_pi = align_up(nshares * 4 + 64), sz_sh = align_up(nshares * share_len + 64), sz_bc = align_up(nshares * 96 + 64),
-                 sz_pc = align_up(nshares * 64 + 64), sz_ch = align_up(nch * 96 + 64);
-    const size_t sz_in = sz_pi + sz_sh + sz_bc + sz_pc + sz_ch, sz_v = align_up(nshares), sz_o = align_up(nshares * 64);
-    rc = io_reserve(c, sz_in + sz_v + sz_o);
+    host_call<bpgpu_ctx> io(c, s);
+    const int r_pi = io.in(nshares * 4 + 64), r_sh = io.in(nshares * share_len + 64), r_bc = io.in(nshares * 96 + 64), r_pc = io.in(nshares * 64 + 64),
+              r_ch = io.in(nch * 96 + 64);
+    const int r_v = io.out(nshares), r_o = io.out(nshares * 64);
+    int rc = io.open();
     if (rc) return rc;
-    char *h = nullptr;
-    rc = pin_alloc(c, s, sz_in + sz_v + sz_o, &h);
-    if (rc) return rc;
-    char *d = c->io_dev;
-    char *d_pi = d, *d_sh = d_pi + sz_pi, *d_bc = d_sh + sz_sh, *d_pc = d_bc + sz_bc, *d_ch = d_pc + sz_pc, *d_v = d + sz_in, *d_o = d_v + sz_v;
-    memcpy(h, party_index, nshares * 4);
-    memcpy(h + sz_pi, shares, nshares * share_len);
-    memcpy(h + sz_pi + sz_sh, bit_commitments, nshares * 96);
-    memcpy(h + sz_pi + sz_sh + sz_bc, poly_commitments, nshares * 64);
-    memcpy(h + sz_pi + sz_sh + sz_bc + sz_pc, challenges, nch * 96);
-    HIPCHK(c, hipMemcpyAsync(d, h, sz_in, hipMemcpyHostToDevice, s));
+    char *d_pi = io.d(r_pi), *d_sh = io.d(r_sh), *d_bc = io.d(r_bc), *d_pc = io.d(r_pc), *d_ch = io.d(r_ch), *d_v = io.d(r_v), *d_o = io.d(r_o);
+    io.put(r_pi, party_index, nshares * 4);
+    io.put(r_sh, shares, nshares * share_len);
+    io.put(r_bc, bit_commitments, nshares * 96);
+    io.put(r_pc, poly_commitments, nshares * 64);
+    io.put(r_ch, challenges, nch * 96);
+    rc = io.upload();
     do {
+        if (rc) break;
         const size_t per = 2 * n + 8;
         const size_t sz_terms = align_up(nshares * per * 32 + 64), sz_st = align_up(nshares * 4), sz_b = align_up(2 * nshares + 64);
         const size_t need = 2 * sz_terms + sz_st + sz_b;
@@ -3300,12 +3179,10 @@ extern "C" int bpgpu_rangeproof_audit_shares(bpgpu_ctx *c, size_t n, size_t nsha
                (uint8_t *)d_v);
         if (hipGetLastError() != hipSuccess) rc = fail(c, BPGPU_ERR_HIP, "launch failed");
     } while (0);
-    char *h_out = h + sz_in;
-    if (!rc && hipMemcpyAsync(h_out, d_v, sz_v + sz_o, hipMemcpyDeviceToHost, s) != hipSuccess) rc = fail(c, BPGPU_ERR_HIP, "D2H copy failed");
-    const int rc2 = ctx_leave(c, s), rc3 = host_wait(c, s);
-    if (rc || rc2 || rc3) return rc ? rc : (rc2 ? rc2 : rc3);
-    memcpy(verdict, h_out, nshares);
-    if (checks_out) memcpy(checks_out, h_out + sz_v, nshares * 64);
+    rc = io.finish(io.download(rc));
+    if (rc) return rc;
+    memcpy(verdict, io.h(r_v), nshares);
+    if (checks_out) memcpy(checks_out, io.h(r_o), nshares * 64);
     return BPGPU_OK;
 }
 
@@ -3376,32 +3253,14 @@ static int ippc_core(bpgpu_ctx *c, hipStream_t s, size_t n, size_t k, size_t nba
 // The provers stage SECRETS (values, blindings, the witness vectors, every random scalar) in the context's persistent buffers:
 // the pinned staging block, the device IO buffer, their working sets and -- as window digits of secret scalars -- the arena.
 // The reference zeroizes its party state on Drop (party.rs:148-260, 308+); here every entered call, successful or not, leaves
-// through prover_exit::finish: the device buffers are cleared on the stream behind the call's last copy, the call's end is
-// recorded (ctx_leave), the stream is drained (host_wait), then the secret part of the staging block is cleared.  What is NOT
-// cleared: registers / LDS of finished kernels and the caller's own buffers.
-struct prover_exit {
-    bpgpu_ctx *c;
-    hipStream_t s;
-    char *h = nullptr;             // the call's pinned staging block (set once allocated)
-    size_t host_secret_bytes = 0;  // leading bytes of h that hold secrets
-    int finish(int rc) {
-        bool ok = true;
-        if (c->io_dev) ok = hipMemsetAsync(c->io_dev, 0, c->io_cap, s) == hipSuccess && ok;
-        if (c->rpp_buf) ok = hipMemsetAsync(c->rpp_buf, 0, c->rpp_cap, s) == hipSuccess && ok;
-        if (c->ipp_buf) ok = hipMemsetAsync(c->ipp_buf, 0, c->ipp_cap, s) == hipSuccess && ok;
-        if (c->arena) ok = hipMemsetAsync(c->arena, 0, c->arena_cap, s) == hipSuccess && ok;
-        const int rc2 = ctx_leave(c, s), rc3 = host_wait(c, s);
-        if (h && host_secret_bytes) memset(h, 0, host_secret_bytes);
-        c->last_secret_bytes = (h == c->pin) ? host_secret_bytes : 0;
-        if (!rc && !ok) rc = fail(c, BPGPU_ERR_HIP, "clearing the prover's working set failed");
-        return rc ? rc : (rc2 ? rc2 : rc3);
-    }
-};
-#define PX_HIPCHK(px, call)                                                                                          \
-    do {                                                                                                             \
-        hipError_t e_ = (call);                                                                                      \
-        if (e_ != hipSuccess) return (px).finish(fail(c, BPGPU_ERR_HIP, "%s failed: %s", #call, hipGetErrorString(e_))); \
-    } while (0)
+// through host_call::finish with secrets() declared: the device buffers are cleared on the stream behind the call's last copy, the
+// call's end is recorded (ctx_leave), the stream is drained (host_wait), then the secret part of the staging block is cleared.
+// What is NOT cleared: registers / LDS of finished kernels and the caller's own buffers.
+// HIPRC: a HIP call as a return code, for exits that must go through finish.
+static int hip_rc(bpgpu_ctx *c, hipError_t e, const char *call) {
+    return e == hipSuccess ? BPGPU_OK : fail(c, BPGPU_ERR_HIP, "%s failed: %s", call, hipGetErrorString(e));
+}
+#define HIPRC(c, call) hip_rc(c, (call), #call)
 
 extern "C" int bpgpu_ipp_create_batch(bpgpu_ctx *c, size_t n, size_t nbatch, const uint8_t *label, size_t label_len, const uint8_t *shared_transcript,
                                       const uint8_t *Q, const uint8_t *G_factors, const uint8_t *H_factors, const uint8_t *G, const uint8_t *H,
@@ -3418,45 +3277,38 @@ extern "C" int bpgpu_ipp_create_batch(bpgpu_ctx *c, size_t n, size_t nbatch, con
     std::lock_guard<std::mutex> lk(c->mu);
     HIPCHK(c, hipSetDevice(c->device));
     hipStream_t s = c->stream;
-    int rc = ctx_enter(c, s);
-    if (rc) return rc;
-    prover_exit px{c, s};
     const size_t proof_len = 32 * (2 * k + 2), TS = BPGPU_TRANSCRIPT_BYTES;
     // ---- inputs: one pinned staging block -> the persistent device IO buffer
-    const size_t sz_v = align_up(nbatch * n * 32 + 64), sz_q = align_up(nbatch * 32 + 64), sz_base = align_up((bases_shared ? 1 : nbatch) * n * 32 + 64),
-                 sz_ts = align_up(nbatch * TS);
-    const size_t sz_in = 4 * sz_v + sz_q + 2 * sz_base + sz_ts, sz_out = align_up(nbatch * proof_len) + align_up(nbatch);
-    rc = io_reserve(c, sz_in + sz_out);
-    if (rc) return px.finish(rc);
-    char *h = nullptr;
-    rc = pin_alloc(c, s, sz_in + sz_out, &h);
-    if (rc) return px.finish(rc);
-    px.h = h;
-    px.host_secret_bytes = 2 * sz_v;   // the witness a, b
-    char *d_a = c->io_dev, *d_b = d_a + sz_v, *d_gf = d_b + sz_v, *d_hf = d_gf + sz_v, *d_q = d_hf + sz_v, *d_G = d_q + sz_q, *d_H = d_G + sz_base,
-         *d_ts = d_H + sz_base, *d_proofs = c->io_dev + sz_in, *d_stb = d_proofs + align_up(nbatch * proof_len);
-    memcpy(h, a, nbatch * n * 32);
-    memcpy(h + sz_v, b, nbatch * n * 32);
-    memcpy(h + 2 * sz_v, G_factors, nbatch * n * 32);
-    memcpy(h + 3 * sz_v, H_factors, nbatch * n * 32);
-    memcpy(h + 4 * sz_v, Q, nbatch * 32);
-    memcpy(h + 4 * sz_v + sz_q, G, (bases_shared ? 1 : nbatch) * n * 32);
-    memcpy(h + 4 * sz_v + sz_q + sz_base, H, (bases_shared ? 1 : nbatch) * n * 32);
+    host_call<bpgpu_ctx> io(c, s);
+    const size_t b_v = nbatch * n * 32 + 64, b_base = (bases_shared ? 1 : nbatch) * n * 32 + 64;
+    const int r_a = io.in(b_v), r_b = io.in(b_v), r_gf = io.in(b_v), r_hf = io.in(b_v), r_q = io.in(nbatch * 32 + 64), r_G = io.in(b_base), r_H = io.in(b_base),
+              r_ts = io.in(nbatch * TS);
+    const int r_proofs = io.out(nbatch * proof_len), r_stb = io.out(nbatch);
+    io.secrets(io.off[r_gf]);   // the witness a, b
+    int rc = io.open();
+    if (rc) return io.finish(rc);
+    io.put(r_a, a, nbatch * n * 32);
+    io.put(r_b, b, nbatch * n * 32);
+    io.put(r_gf, G_factors, nbatch * n * 32);
+    io.put(r_hf, H_factors, nbatch * n * 32);
+    io.put(r_q, Q, nbatch * 32);
+    io.put(r_G, G, (bases_shared ? 1 : nbatch) * n * 32);
+    io.put(r_H, H, (bases_shared ? 1 : nbatch) * n * 32);
     {   // every proof's transcript after innerproduct_domain_sep(n) (transcript.rs:50-53)
         uint8_t st0[BPGPU_TRANSCRIPT_BYTES];
         ipp_domain_sep_state(st0, label, label_len, shared_transcript, n, nullptr);
-        for (size_t p = 0; p < nbatch; p++) memcpy(h + 4 * sz_v + sz_q + 2 * sz_base + p * TS, st0, TS);
+        for (size_t p = 0; p < nbatch; p++) memcpy(io.h(r_ts) + p * TS, st0, TS);
     }
-    PX_HIPCHK(px, hipMemcpyAsync(c->io_dev, h, sz_in, hipMemcpyHostToDevice, s));
-    PX_HIPCHK(px, hipMemsetAsync(d_proofs, 0, nbatch * proof_len, s));
+    rc = io.upload();
+    if (!rc) rc = HIPRC(c, hipMemsetAsync(io.d(r_proofs), 0, nbatch * proof_len, s));
     // ---- rounds (ippc_core: own working set, the batched MSMs claim the arena)
-    rc = ippc_core(c, s, n, k, nbatch, d_a, d_b, d_gf, d_hf, d_q, d_G, d_H, bases_shared, (uint32_t *)d_ts, (uint8_t *)d_proofs, proof_len, (uint8_t *)d_stb);
-    char *h_out = h + sz_in;
-    if (!rc && hipMemcpyAsync(h_out, d_proofs, sz_out, hipMemcpyDeviceToHost, s) != hipSuccess) rc = fail(c, BPGPU_ERR_HIP, "D2H copy failed");
-    rc = px.finish(rc);
+    if (!rc)
+        rc = ippc_core(c, s, n, k, nbatch, io.d(r_a), io.d(r_b), io.d(r_gf), io.d(r_hf), io.d(r_q), io.d(r_G), io.d(r_H), bases_shared, (uint32_t *)io.d(r_ts),
+                       (uint8_t *)io.d(r_proofs), proof_len, (uint8_t *)io.d(r_stb));
+    rc = io.finish(io.download(rc));
     if (rc) return rc;
-    memcpy(proofs_out, h_out, nbatch * proof_len);
-    memcpy(status_out, h_out + align_up(nbatch * proof_len), nbatch);
+    memcpy(proofs_out, io.h(r_proofs), nbatch * proof_len);
+    memcpy(status_out, io.h(r_stb), nbatch);
     return BPGPU_OK;
 }
 
@@ -3484,48 +3336,41 @@ extern "C" int bpgpu_linear_create_batch(bpgpu_ctx *c, size_t n, size_t nbatch, 
         if (!c->d_table) return fail(c, BPGPU_ERR_NO_GENS, "generators not loaded");
         if (n > c->gens_capacity) return fail(c, BPGPU_ERR_NO_GENS, "InvalidGeneratorsLength: generators too small for n=%zu", n);
     }
-    int rc = ctx_enter(c, s);
-    if (rc) return rc;
-    prover_exit px{c, s};
     const size_t proof_len = 32 * (2 * k + 3), TS = BPGPU_TRANSCRIPT_BYTES, nd = 2 * k + 2, nb_b = b_shared ? 1 : nbatch;
     // ---- inputs: one pinned staging block -> the persistent device IO buffer
-    const size_t sz_v = align_up(nbatch * n * 32 + 64), sz_bv = align_up(nb_b * n * 32 + 64), sz_q = align_up(nbatch * 32 + 64), sz_g = align_up(n * 32 + 64),
-                 sz_fb = align_up(64 + 64), sz_rng = align_up(nbatch * nd * 64), sz_ts = align_up(nbatch * TS);
-    const size_t sz_in = sz_v + sz_bv + 2 * sz_q + sz_g + sz_fb + sz_rng + sz_ts, sz_pr = align_up(nbatch * proof_len), sz_stb = align_up(nbatch);
-    const size_t sz_out = sz_pr + sz_stb;
-    rc = io_reserve(c, sz_in + sz_out);
-    if (rc) return px.finish(rc);
-    char *h = nullptr;
-    rc = pin_alloc(c, s, sz_in + sz_out, &h);
-    if (rc) return px.finish(rc);
-    px.h = h;
-    px.host_secret_bytes = sz_in - sz_ts;   // a, r, the random draws (and the public inputs between them); the transcript block behind is reused for the way back
-    char *d_a = c->io_dev, *d_b = d_a + sz_v, *d_C = d_b + sz_bv, *d_r = d_C + sz_q, *d_G = d_r + sz_q, *d_fb = d_G + sz_g, *d_rng = d_fb + sz_fb,
-         *d_ts = d_rng + sz_rng, *d_proofs = c->io_dev + sz_in, *d_stb = d_proofs + sz_pr;
-    memcpy(h, a, nbatch * n * 32);
-    memcpy(h + sz_v, b, nb_b * n * 32);
-    memcpy(h + sz_v + sz_bv, C, nbatch * 32);
-    memcpy(h + sz_v + sz_bv + sz_q, r, nbatch * 32);
+    host_call<bpgpu_ctx> io(c, s);
+    const int r_a = io.in(nbatch * n * 32 + 64), r_b = io.in(nb_b * n * 32 + 64), r_C = io.in(nbatch * 32 + 64), r_r = io.in(nbatch * 32 + 64), r_G = io.in(n * 32 + 64),
+              r_fb = io.in(64 + 64), r_rng = io.in(nbatch * nd * 64), r_ts = io.in(nbatch * TS);
+    const int r_proofs = io.out(nbatch * proof_len), r_stb = io.out(nbatch);
+    io.secrets(io.off[r_ts]);   // a, r, the random draws (and the public inputs between them); the transcript block behind is reused for the way back
+    int rc = io.open();
+    if (rc) return io.finish(rc);
+    char *d_a = io.d(r_a), *d_b = io.d(r_b), *d_C = io.d(r_C), *d_r = io.d(r_r), *d_G = io.d(r_G), *d_fb = io.d(r_fb), *d_rng = io.d(r_rng), *d_ts = io.d(r_ts),
+         *d_proofs = io.d(r_proofs), *d_stb = io.d(r_stb);
+    io.put(r_a, a, nbatch * n * 32);
+    io.put(r_b, b, nb_b * n * 32);
+    io.put(r_C, C, nbatch * 32);
+    io.put(r_r, r, nbatch * 32);
     if (!from_gens) {
-        memcpy(h + sz_v + sz_bv + 2 * sz_q, G, n * 32);
-        memcpy(h + sz_v + sz_bv + 2 * sz_q + sz_g, F, 32);
-        memcpy(h + sz_v + sz_bv + 2 * sz_q + sz_g + 32, B, 32);
+        io.put(r_G, G, n * 32);
+        memcpy(io.h(r_fb), F, 32);
+        memcpy(io.h(r_fb) + 32, B, 32);
     }
     const uint8_t *e_G = from_gens ? (const uint8_t *)(c->d_gens + 16) : (const uint8_t *)d_G;          // encodings the transcript absorbs
     const uint8_t *e_F = from_gens ? (const uint8_t *)(c->d_gens + 8) : (const uint8_t *)d_fb;
     const uint8_t *e_B = from_gens ? (const uint8_t *)c->d_gens : (const uint8_t *)d_fb + 32;
     {
-        char *h_rng = h + sz_v + sz_bv + 2 * sz_q + sz_g + sz_fb;
-        if (rng) memcpy(h_rng, rng, nbatch * nd * 64);
-        else if ((rc = os_random(c, h_rng, nbatch * nd * 64)) != 0) return px.finish(rc);   // Scalar::random(&mut thread_rng())
+        if (rng) io.put(r_rng, rng, nbatch * nd * 64);
+        else if ((rc = os_random(c, io.h(r_rng), nbatch * nd * 64)) != 0) return io.finish(rc);   // Scalar::random(&mut thread_rng())
         // every proof's transcript after innerproduct_domain_sep(n) (linear_proof.rs:73)
         uint8_t st0[BPGPU_TRANSCRIPT_BYTES];
         ipp_domain_sep_state(st0, label, label_len, shared_transcript, n, nullptr);
-        for (size_t p = 0; p < nbatch; p++) memcpy(h_rng + sz_rng + p * TS, st0, TS);
+        for (size_t p = 0; p < nbatch; p++) memcpy(io.h(r_ts) + p * TS, st0, TS);
     }
-    PX_HIPCHK(px, hipMemcpyAsync(c->io_dev, h, sz_in, hipMemcpyHostToDevice, s));
-    PX_HIPCHK(px, hipMemsetAsync(d_proofs, 0, nbatch * proof_len, s));
+    rc = io.upload();
+    if (!rc) rc = HIPRC(c, hipMemsetAsync(d_proofs, 0, nbatch * proof_len, s));
     do {
+        if (rc) break;
         // ---- working set (own allocation: the batched MSMs claim the arena)
         const size_t N = n / 2 + 2, NS = n + 2;
         const size_t w_v = align_up(nbatch * n * 32), w_u = align_up(nbatch * 32), w_d = align_up(nbatch * nd * 32),
@@ -3584,14 +3429,13 @@ extern "C" int bpgpu_linear_create_batch(bpgpu_ctx *c, size_t n, size_t nbatch, 
                (const uint32_t *)w_a, (const uint32_t *)w_dr, (const uint32_t *)w_r, (uint8_t *)d_proofs, (uint32_t)proof_len, d_status, (uint8_t *)d_stb);
         if (hipGetLastError() != hipSuccess) rc = fail(c, BPGPU_ERR_HIP, "launch failed");
     } while (0);
-    char *h_out = h + sz_in;
-    if (!rc && hipMemcpyAsync(h_out, d_proofs, sz_out, hipMemcpyDeviceToHost, s) != hipSuccess) rc = fail(c, BPGPU_ERR_HIP, "D2H copy failed");
-    char *h_ts = h + (d_ts - c->io_dev);   // the transcript block of the staging buffer is free again: reuse it for the way back
+    rc = io.download(rc);
+    char *h_ts = io.h(r_ts);   // the transcript block of the staging buffer is free again: reuse it for the way back
     if (!rc && transcripts_out && hipMemcpyAsync(h_ts, d_ts, nbatch * TS, hipMemcpyDeviceToHost, s) != hipSuccess) rc = fail(c, BPGPU_ERR_HIP, "D2H copy failed");
-    rc = px.finish(rc);   // (on an error too: the stream is drained before the staging buffers are reused, the secrets cleared)
+    rc = io.finish(rc);   // (on an error too: the stream is drained before the staging buffers are reused, the secrets cleared)
     if (rc) return rc;
-    memcpy(proofs_out, h_out, nbatch * proof_len);
-    memcpy(status_out, h_out + sz_pr, nbatch);
+    memcpy(proofs_out, io.h(r_proofs), nbatch * proof_len);
+    memcpy(status_out, io.h(r_stb), nbatch);
     if (transcripts_out) memcpy(transcripts_out, h_ts, nbatch * TS);
     return BPGPU_OK;
 }
@@ -3599,6 +3443,18 @@ extern "C" int bpgpu_linear_create_batch(bpgpu_ctx *c, size_t n, size_t nbatch, 
 // ============================================================================
 // batched range-proof creation (rp_prover.h)
 // ============================================================================
+// working set of the range-proof / R1CS provers and the party / dealer calls (cleared by host_call::finish on the way out, so an
+// outgrown block is clean when it is freed)
+static int rpp_reserve(bpgpu_ctx *c, size_t need) {
+    if (c->rpp_cap >= need) return BPGPU_OK;
+    HIPCHK(c, hipDeviceSynchronize());
+    if (c->rpp_buf) HIPCHK(c, hipFree(c->rpp_buf));
+    c->rpp_buf = nullptr;
+    c->rpp_cap = 0;
+    HIPCHK(c, hipMalloc((void **)&c->rpp_buf, need + need / 8));
+    c->rpp_cap = need + need / 8;
+    return BPGPU_OK;
+}
 extern "C" int bpgpu_rangeproof_prove_batch(bpgpu_ctx *c, size_t n, size_t m, size_t nbatch, const uint64_t *values, const uint8_t *blindings,
                                             const uint8_t *label, size_t label_len, const uint8_t *shared_transcript, const uint8_t *rng,
                                             uint8_t *proofs_out, uint8_t *commitments_out, uint8_t *transcripts_out) {
@@ -3634,27 +3490,19 @@ extern "C" int bpgpu_rangeproof_prove_batch(bpgpu_ctx *c, size_t n, size_t m, si
     if (gs_bytes > (4ull << 30) || (uint64_t)nmsm1 * sh.n_gen_terms > 0x7fffffffull || (uint64_t)nbatch * nm > 0x7fffffffull / 64)
         return fail(c, BPGPU_ERR_INVALID_ARG, "batch too large for this shape");
     hipStream_t s = c->stream;
-    int rc = ctx_enter(c, s);
-    if (rc) return rc;
-    prover_exit px{c, s};
     // ---- inputs through pinned staging into the persistent IO buffer
-    const size_t sz_val = align_up(nbatch * m * 8), sz_bl = align_up(nbatch * m * 32), sz_rng = align_up(nbatch * sh.rng_per_proof), sz_ts = align_up(nbatch * TS);
-    const size_t sz_in = sz_val + sz_bl + sz_rng + sz_ts;
-    const size_t sz_pr = align_up(nbatch * proof_len), sz_cm = align_up(nbatch * m * 32);
-    const size_t sz_out = sz_pr + sz_cm + sz_ts;
-    rc = io_reserve(c, sz_in + sz_out);
-    if (rc) return px.finish(rc);
-    char *h = nullptr;
-    rc = pin_alloc(c, s, sz_in + sz_out, &h);
-    if (rc) return px.finish(rc);
-    px.h = h;
-    px.host_secret_bytes = sz_val + sz_bl + sz_rng;   // values, blindings, every random scalar
-    memcpy(h, values, nbatch * m * 8);
-    memcpy(h + sz_val, blindings, nbatch * m * 32);
-    if (rng) memcpy(h + sz_val + sz_bl, rng, nbatch * sh.rng_per_proof);
+    host_call<bpgpu_ctx> io(c, s);
+    const int r_val = io.in(nbatch * m * 8), r_bl = io.in(nbatch * m * 32), r_rng = io.in(nbatch * sh.rng_per_proof), r_ts = io.in(nbatch * TS);
+    const int r_pr = io.out(nbatch * proof_len), r_cm = io.out(nbatch * m * 32), r_to = io.out(nbatch * TS);
+    io.secrets(io.off[r_ts]);   // values, blindings, every random scalar
+    int rc = io.open();
+    if (rc) return io.finish(rc);
+    io.put(r_val, values, nbatch * m * 8);
+    io.put(r_bl, blindings, nbatch * m * 32);
+    if (rng) io.put(r_rng, rng, nbatch * sh.rng_per_proof);
     else {   // thread_rng() of prove_multiple (mod.rs:291-310): OS CSPRNG
-        rc = os_random(c, h + sz_val + sz_bl, nbatch * sh.rng_per_proof);
-        if (rc) return px.finish(rc);
+        rc = os_random(c, io.h(r_rng), nbatch * sh.rng_per_proof);
+        if (rc) return io.finish(rc);
     }
     uint8_t st_start[BPGPU_TRANSCRIPT_BYTES];
     {   // every proof's transcript after rangeproof_domain_sep(n, m) (transcript.rs:44-48)
@@ -3669,26 +3517,18 @@ extern "C" int bpgpu_rangeproof_prove_batch(bpgpu_ctx *c, size_t n, size_t m, si
         merlin_append_u64(t, lm, 1, m);
         uint8_t st1[BPGPU_TRANSCRIPT_BYTES];
         ts_from_strobe(st1, t);
-        for (size_t p = 0; p < nbatch; p++) memcpy(h + sz_val + sz_bl + sz_rng + p * TS, st1, TS);
+        for (size_t p = 0; p < nbatch; p++) memcpy(io.h(r_ts) + p * TS, st1, TS);
     }
-    char *d_in = c->io_dev;
-    const uint64_t *d_values = (const uint64_t *)d_in;
-    const uint8_t *d_bl = (const uint8_t *)(d_in + sz_val), *d_rng = (const uint8_t *)(d_in + sz_val + sz_bl);
-    uint32_t *d_ts = (uint32_t *)(d_in + sz_val + sz_bl + sz_rng);
-    uint8_t *d_proofs = (uint8_t *)(d_in + sz_in), *d_coms = d_proofs + sz_pr;
-    PX_HIPCHK(px, hipMemcpyAsync(d_in, h, sz_in, hipMemcpyHostToDevice, s));
+    const uint64_t *d_values = (const uint64_t *)io.d(r_val);
+    const uint8_t *d_bl = (const uint8_t *)io.d(r_bl), *d_rng = (const uint8_t *)io.d(r_rng);
+    uint32_t *d_ts = (uint32_t *)io.d(r_ts);
+    uint8_t *d_proofs = (uint8_t *)io.d(r_pr), *d_coms = (uint8_t *)io.d(r_cm);
+    if ((rc = io.upload())) return io.finish(rc);
     // ---- working set
     const size_t w_gs = align_up(gs_bytes), w_mo = align_up(nmsm1 * 32), w_ms = align_up(nmsm1 + 64), w_f = align_up(RPP_FIXED * nbatch * 32),
                  w_p = align_up(RPP_PARTY_FIELDS * nbatch * m * 32), w_v = align_up(nbatch * nm * 32), w_q = align_up(nbatch * 32), w_gen = align_up(nm * 32);
     const size_t need = w_gs + w_mo + w_ms + w_f + w_p + 10 * w_v + w_q + 2 * w_gen;
-    if (c->rpp_cap < need) {   // (the old block is clean: every call clears it on its way out)
-        PX_HIPCHK(px, hipDeviceSynchronize());
-        if (c->rpp_buf) PX_HIPCHK(px, hipFree(c->rpp_buf));
-        c->rpp_buf = nullptr;
-        c->rpp_cap = 0;
-        PX_HIPCHK(px, hipMalloc((void **)&c->rpp_buf, need + need / 8));
-        c->rpp_cap = need + need / 8;
-    }
+    if ((rc = rpp_reserve(c, need))) return io.finish(rc);
     char *wb = c->rpp_buf;
     uint32_t *gsc = (uint32_t *)wb, *mo = (uint32_t *)(wb + w_gs);
     uint8_t *mst = (uint8_t *)mo + w_mo;
@@ -3705,7 +3545,7 @@ extern "C" int bpgpu_rangeproof_prove_batch(bpgpu_ctx *c, size_t n, size_t m, si
         if (rc) break;
         LAUNCH(c, s, "gather32", k_gather32, ((uint32_t)(2 * nm) + BP_BLOCK - 1) / BP_BLOCK, BP_BLOCK, (uint32_t)(2 * nm), (const uint32_t *)(d_ids + 2),
                (const uint32_t *)c->d_gens, Genc);   // G(n, m) then H(n, m): Henc = Genc + nm records when w_gen is exact
-        if (hipMemsetAsync(gsc, 0, gs_bytes, s) != hipSuccess || hipMemsetAsync(d_proofs, 0, sz_pr, s) != hipSuccess) {
+        if (hipMemsetAsync(gsc, 0, gs_bytes, s) != hipSuccess || hipMemsetAsync(d_proofs, 0, io.width(r_pr), s) != hipSuccess) {
             rc = fail(c, BPGPU_ERR_HIP, "memset failed");
             break;
         }
@@ -3743,34 +3583,19 @@ extern "C" int bpgpu_rangeproof_prove_batch(bpgpu_ctx *c, size_t n, size_t m, si
         fx.gen_scalars = gsc;
         rc = ippc_core(c, s, nm, k, nbatch, avec, bvec, Gf, Hf, qenc, Genc, Genc + 8 * nm, 1, d_ts, d_proofs + 224, proof_len, nullptr, &fx);
     } while (0);
-    char *h_out = h + sz_in;
-    if (!rc) {
-        if (hipMemcpyAsync(d_coms + sz_cm, d_ts, nbatch * TS, hipMemcpyDeviceToDevice, s) != hipSuccess ||
-            hipMemcpyAsync(h_out, d_proofs, sz_out, hipMemcpyDeviceToHost, s) != hipSuccess)
-            rc = fail(c, BPGPU_ERR_HIP, "D2H copy failed");
-    }
-    rc = px.finish(rc);
+    if (!rc && (hipMemcpyAsync(io.d(r_to), d_ts, nbatch * TS, hipMemcpyDeviceToDevice, s) != hipSuccess || io.download(0)))
+        rc = fail(c, BPGPU_ERR_HIP, "D2H copy failed");
+    rc = io.finish(rc);
     if (rc) return rc;
-    memcpy(proofs_out, h_out, nbatch * proof_len);
-    memcpy(commitments_out, h_out + sz_pr, nbatch * m * 32);
-    if (transcripts_out) memcpy(transcripts_out, h_out + sz_pr + sz_cm, nbatch * TS);
+    memcpy(proofs_out, io.h(r_pr), nbatch * proof_len);
+    memcpy(commitments_out, io.h(r_cm), nbatch * m * 32);
+    if (transcripts_out) memcpy(transcripts_out, io.h(r_to), nbatch * TS);
     return BPGPU_OK;
 }
 
 // ============================================================================
 // the multi-party aggregation protocol: parties (mpc_party.h) and dealer (mpc_dealer.h)
 // ============================================================================
-// working set of the party / dealer calls: the prover's block (cleared by prover_exit on the way out)
-static int mpc_work_reserve(bpgpu_ctx *c, size_t need) {
-    if (c->rpp_cap >= need) return BPGPU_OK;
-    HIPCHK(c, hipDeviceSynchronize());
-    if (c->rpp_buf) HIPCHK(c, hipFree(c->rpp_buf));
-    c->rpp_buf = nullptr;
-    c->rpp_cap = 0;
-    HIPCHK(c, hipMalloc((void **)&c->rpp_buf, need + need / 8));
-    c->rpp_cap = need + need / 8;
-    return BPGPU_OK;
-}
 static bool mpc_bitsize_ok(size_t n) { return n == 8 || n == 16 || n == 32 || n == 64; }
 
 // the id lists of every position for bitsize n: [party_capacity][2n + 2] (mpc_fill_ids), cached like gen_ids_for's lists
@@ -3855,9 +3680,9 @@ extern "C" size_t bpgpu_mpc_state1_bytes(size_t n) { return 4 * (size_t)MPC_ST1_
 extern "C" size_t bpgpu_mpc_state2_bytes(size_t n) { return 4 * (size_t)MPC_ST2_WORDS(n); }
 
 // the state blobs that came back through the staging block are secrets too: cleared once they have been handed to the caller
-static void mpc_clear_staged_state(bpgpu_ctx *c, char *h, size_t off, size_t bytes) {
-    memset(h + off, 0, bytes);
-    if (h == c->pin) c->last_secret_bytes = off + bytes;
+static void mpc_clear_staged_state(host_call<bpgpu_ctx> &io, int r) {
+    memset(io.h(r), 0, io.width(r));
+    if (io.hb == io.st.pin) io.st.last_secret_bytes = io.off[r + 1];
 }
 
 // ---- step 1: Party::new + assign_position_with_rng -------------------------------------------------------------------------
@@ -3879,26 +3704,19 @@ extern "C" int bpgpu_mpc_party_bit_commit(bpgpu_ctx *c, size_t n, size_t npartie
     mpc_make_plan(pl, nparties, party_index, c->party_capacity);
     const size_t ns = pl.nslots, per_rng = 64 * (2 * n + 2), st_bytes = bpgpu_mpc_state1_bytes(n);
     hipStream_t s = c->stream;
-    int rc = ctx_enter(c, s);
-    if (rc) return rc;
-    prover_exit px{c, s};
-    const size_t sz_sp = align_up(ns * 4), sz_bp = align_up(ns / MPC_WAVE * 4), sz_val = align_up(ns * 8), sz_bl = align_up(ns * 32), sz_rng = align_up(ns * per_rng);
-    const size_t sz_in = sz_sp + sz_bp + sz_val + sz_bl + sz_rng, sz_st = align_up(ns * st_bytes), sz_v = align_up(ns * 32), sz_as = align_up(2 * ns * 32);
-    const size_t sz_out = sz_st + sz_v + sz_as;
-    rc = io_reserve(c, sz_in + sz_out);
-    if (rc) return px.finish(rc);
-    char *h = nullptr;
-    rc = pin_alloc(c, s, sz_in + sz_out, &h);
-    if (rc) return px.finish(rc);
-    px.h = h;
-    px.host_secret_bytes = sz_in;
-    memset(h, 0, sz_in);
-    memcpy(h, pl.slot_pos.data(), ns * 4);
-    memcpy(h + sz_sp, pl.blk_pos.data(), ns / MPC_WAVE * 4);
-    char *h_val = h + sz_sp + sz_bp, *h_bl = h_val + sz_val, *h_rng = h_bl + sz_bl;
+    host_call<bpgpu_ctx> io(c, s);
+    const int r_sp = io.in(ns * 4), r_bp = io.in(ns / MPC_WAVE * 4), r_val = io.in(ns * 8), r_bl = io.in(ns * 32), r_rng = io.in(ns * per_rng);
+    const int r_st = io.out(ns * st_bytes), r_v = io.out(ns * 32), r_as = io.out(2 * ns * 32);
+    io.secrets(io.in_bytes());
+    int rc = io.open();
+    if (rc) return io.finish(rc);
+    memset(io.h(r_sp), 0, io.in_bytes());
+    io.put(r_sp, pl.slot_pos.data(), ns * 4);
+    io.put(r_bp, pl.blk_pos.data(), ns / MPC_WAVE * 4);
+    char *h_val = io.h(r_val), *h_bl = io.h(r_bl), *h_rng = io.h(r_rng);
     if (!rng) {   // Scalar::random(&mut thread_rng()): OS CSPRNG (padding slots draw too; they are never read)
         rc = os_random(c, h_rng, ns * per_rng);
-        if (rc) return px.finish(rc);
+        if (rc) return io.finish(rc);
     }
     for (size_t r = 0; r < nparties; r++) {
         const size_t sl = pl.row_slot[r];
@@ -3906,18 +3724,17 @@ extern "C" int bpgpu_mpc_party_bit_commit(bpgpu_ctx *c, size_t n, size_t npartie
         memcpy(h_bl + sl * 32, blindings + r * 32, 32);
         if (rng) memcpy(h_rng + sl * per_rng, rng + r * per_rng, per_rng);
     }
-    char *d = c->io_dev;
-    const uint32_t *d_sp = (const uint32_t *)d, *d_bp = (const uint32_t *)(d + sz_sp);
-    const uint64_t *d_val = (const uint64_t *)(d + sz_sp + sz_bp);
-    const uint8_t *d_bl = (const uint8_t *)d_val + sz_val, *d_rng = d_bl + sz_bl;
-    uint32_t *d_st = (uint32_t *)(d + sz_in), *d_v = (uint32_t *)((char *)d_st + sz_st), *d_as = (uint32_t *)((char *)d_v + sz_v);
-    PX_HIPCHK(px, hipMemcpyAsync(d, h, sz_in, hipMemcpyHostToDevice, s));
+    const uint32_t *d_sp = (const uint32_t *)io.d(r_sp), *d_bp = (const uint32_t *)io.d(r_bp);
+    const uint64_t *d_val = (const uint64_t *)io.d(r_val);
+    const uint8_t *d_bl = (const uint8_t *)io.d(r_bl), *d_rng = (const uint8_t *)io.d(r_rng);
+    uint32_t *d_st = (uint32_t *)io.d(r_st), *d_v = (uint32_t *)io.d(r_v), *d_as = (uint32_t *)io.d(r_as);
+    if ((rc = io.upload())) return io.finish(rc);
     const size_t row_len = 2 * n + 2, w_v = align_up(ns * 2 * 32), w_as = align_up(2 * ns * row_len * 32);
-    rc = mpc_work_reserve(c, w_v + w_as);
-    if (rc) return px.finish(rc);
+    rc = rpp_reserve(c, w_v + w_as);
+    if (rc) return io.finish(rc);
     uint32_t *gsV = (uint32_t *)c->rpp_buf, *gsAS = (uint32_t *)(c->rpp_buf + w_v);
     do {
-        if (hipMemsetAsync(c->rpp_buf, 0, w_v + w_as, s) != hipSuccess || hipMemsetAsync(d_st, 0, sz_st, s) != hipSuccess) {
+        if (hipMemsetAsync(c->rpp_buf, 0, w_v + w_as, s) != hipSuccess || hipMemsetAsync(d_st, 0, io.width(r_st), s) != hipSuccess) {
             rc = fail(c, BPGPU_ERR_HIP, "memset failed");
             break;
         }
@@ -3927,18 +3744,16 @@ extern "C" int bpgpu_mpc_party_bit_commit(bpgpu_ctx *c, size_t n, size_t npartie
         if (rc) break;
         rc = mpc_walk(c, s, n, 2, ns32, (uint32_t)row_len, gsAS, d_bp, d_sp, d_as);     // A_j, S_j over B~, G_j(n), H_j(n) (party.rs:99-124)
     } while (0);
-    char *h_out = h + sz_in;
-    if (!rc && hipMemcpyAsync(h_out, d_st, sz_out, hipMemcpyDeviceToHost, s) != hipSuccess) rc = fail(c, BPGPU_ERR_HIP, "D2H copy failed");
-    rc = px.finish(rc);
+    rc = io.finish(io.download(rc));
     if (!rc)
         for (size_t r = 0; r < nparties; r++) {
             const size_t sl = pl.row_slot[r];
-            memcpy(state1 + r * st_bytes, h_out + sl * st_bytes, st_bytes);
-            memcpy(bit_commitments + r * 96, h_out + sz_st + sl * 32, 32);
-            memcpy(bit_commitments + r * 96 + 32, h_out + sz_st + sz_v + sl * 32, 32);
-            memcpy(bit_commitments + r * 96 + 64, h_out + sz_st + sz_v + (ns + sl) * 32, 32);
+            memcpy(state1 + r * st_bytes, io.h(r_st) + sl * st_bytes, st_bytes);
+            memcpy(bit_commitments + r * 96, io.h(r_v) + sl * 32, 32);
+            memcpy(bit_commitments + r * 96 + 32, io.h(r_as) + sl * 32, 32);
+            memcpy(bit_commitments + r * 96 + 64, io.h(r_as) + (ns + sl) * 32, 32);
         }
-    mpc_clear_staged_state(c, h, sz_in, sz_st);
+    mpc_clear_staged_state(io, r_st);
     return rc;
 }
 
@@ -3974,26 +3789,19 @@ extern "C" int bpgpu_mpc_party_poly_commit(bpgpu_ctx *c, size_t n, size_t nparti
     mpc_make_plan(pl, nparties, pos.data(), c->party_capacity);
     const size_t ns = pl.nslots, nch = challenges_shared ? 1 : ns;
     hipStream_t s = c->stream;
-    rc = ctx_enter(c, s);
-    if (rc) return rc;
-    prover_exit px{c, s};
-    const size_t sz_sp = align_up(ns * 4), sz_bp = align_up(ns / MPC_WAVE * 4), sz_s1 = align_up(ns * st1_bytes), sz_ch = align_up(nch * 64), sz_rng = align_up(ns * 128);
-    const size_t sz_in = sz_sp + sz_bp + sz_s1 + sz_ch + sz_rng, sz_s2 = align_up(ns * st2_bytes), sz_t = align_up(2 * ns * 32), sz_stat = align_up(ns * 4);
-    const size_t sz_out = sz_s2 + sz_t + sz_stat;
-    rc = io_reserve(c, sz_in + sz_out);
-    if (rc) return px.finish(rc);
-    char *h = nullptr;
-    rc = pin_alloc(c, s, sz_in + sz_out, &h);
-    if (rc) return px.finish(rc);
-    px.h = h;
-    px.host_secret_bytes = sz_in;
-    memset(h, 0, sz_in);
-    memcpy(h, pl.slot_pos.data(), ns * 4);
-    memcpy(h + sz_sp, pl.blk_pos.data(), ns / MPC_WAVE * 4);
-    char *h_s1 = h + sz_sp + sz_bp, *h_ch = h_s1 + sz_s1, *h_rng = h_ch + sz_ch;
+    host_call<bpgpu_ctx> io(c, s);
+    const int r_sp = io.in(ns * 4), r_bp = io.in(ns / MPC_WAVE * 4), r_s1 = io.in(ns * st1_bytes), r_ch = io.in(nch * 64), r_rng = io.in(ns * 128);
+    const int r_s2 = io.out(ns * st2_bytes), r_t = io.out(2 * ns * 32), r_stat = io.out(ns * 4);
+    io.secrets(io.in_bytes());
+    rc = io.open();
+    if (rc) return io.finish(rc);
+    memset(io.h(r_sp), 0, io.in_bytes());
+    io.put(r_sp, pl.slot_pos.data(), ns * 4);
+    io.put(r_bp, pl.blk_pos.data(), ns / MPC_WAVE * 4);
+    char *h_s1 = io.h(r_s1), *h_ch = io.h(r_ch), *h_rng = io.h(r_rng);
     if (!rng) {
         rc = os_random(c, h_rng, ns * 128);
-        if (rc) return px.finish(rc);
+        if (rc) return io.finish(rc);
     }
     if (challenges_shared) memcpy(h_ch, bit_challenges, 64);
     for (size_t r = 0; r < nparties; r++) {
@@ -4002,17 +3810,16 @@ extern "C" int bpgpu_mpc_party_poly_commit(bpgpu_ctx *c, size_t n, size_t nparti
         if (!challenges_shared) memcpy(h_ch + sl * 64, bit_challenges + r * 64, 64);
         if (rng) memcpy(h_rng + sl * 128, rng + r * 128, 128);
     }
-    char *d = c->io_dev;
-    const uint32_t *d_sp = (const uint32_t *)d, *d_bp = (const uint32_t *)(d + sz_sp), *d_s1 = (const uint32_t *)(d + sz_sp + sz_bp);
-    const uint8_t *d_ch = (const uint8_t *)d_s1 + sz_s1, *d_rng = d_ch + sz_ch;
-    uint32_t *d_s2 = (uint32_t *)(d + sz_in), *d_t = (uint32_t *)((char *)d_s2 + sz_s2), *d_stat = (uint32_t *)((char *)d_t + sz_t);
-    PX_HIPCHK(px, hipMemcpyAsync(d, h, sz_in, hipMemcpyHostToDevice, s));
+    const uint32_t *d_sp = (const uint32_t *)io.d(r_sp), *d_bp = (const uint32_t *)io.d(r_bp), *d_s1 = (const uint32_t *)io.d(r_s1);
+    const uint8_t *d_ch = (const uint8_t *)io.d(r_ch), *d_rng = (const uint8_t *)io.d(r_rng);
+    uint32_t *d_s2 = (uint32_t *)io.d(r_s2), *d_t = (uint32_t *)io.d(r_t), *d_stat = (uint32_t *)io.d(r_stat);
+    if ((rc = io.upload())) return io.finish(rc);
     const size_t w_t = align_up(2 * ns * 2 * 32);
-    rc = mpc_work_reserve(c, w_t);
-    if (rc) return px.finish(rc);
+    rc = rpp_reserve(c, w_t);
+    if (rc) return io.finish(rc);
     uint32_t *gsT = (uint32_t *)c->rpp_buf;
     do {
-        if (hipMemsetAsync(gsT, 0, w_t, s) != hipSuccess || hipMemsetAsync(d_s2, 0, sz_out, s) != hipSuccess) {
+        if (hipMemsetAsync(gsT, 0, w_t, s) != hipSuccess || hipMemsetAsync(d_s2, 0, io.out_bytes(), s) != hipSuccess) {
             rc = fail(c, BPGPU_ERR_HIP, "memset failed");
             break;
         }
@@ -4021,24 +3828,22 @@ extern "C" int bpgpu_mpc_party_poly_commit(bpgpu_ctx *c, size_t n, size_t nparti
                d_stat);
         rc = mpc_walk(c, s, n, 2, ns32, 2, gsT, d_bp, d_sp, d_t);   // T_i_j = t_i B + t_i_blinding B~ (party.rs:224-227)
     } while (0);
-    char *h_out = h + sz_in;
-    if (!rc && hipMemcpyAsync(h_out, d_s2, sz_out, hipMemcpyDeviceToHost, s) != hipSuccess) rc = fail(c, BPGPU_ERR_HIP, "D2H copy failed");
-    rc = px.finish(rc);
+    rc = io.finish(io.download(rc));
     if (!rc)
         for (size_t r = 0; r < nparties; r++) {
             const size_t sl = pl.row_slot[r];
             uint32_t st;
-            memcpy(&st, h_out + sz_s2 + sz_t + sl * 4, 4);
+            memcpy(&st, io.h(r_stat) + sl * 4, 4);
             status[r] = (uint8_t)st;
-            memcpy(state2 + r * st2_bytes, h_out + sl * st2_bytes, st2_bytes);
+            memcpy(state2 + r * st2_bytes, io.h(r_s2) + sl * st2_bytes, st2_bytes);
             if (st) {
                 memset(poly_commitments + r * 64, 0, 64);
             } else {
-                memcpy(poly_commitments + r * 64, h_out + sz_s2 + sl * 32, 32);
-                memcpy(poly_commitments + r * 64 + 32, h_out + sz_s2 + (ns + sl) * 32, 32);
+                memcpy(poly_commitments + r * 64, io.h(r_t) + sl * 32, 32);
+                memcpy(poly_commitments + r * 64 + 32, io.h(r_t) + (ns + sl) * 32, 32);
             }
         }
-    mpc_clear_staged_state(c, h, sz_in, sz_s2);
+    mpc_clear_staged_state(io, r_s2);
     return rc;
 }
 
@@ -4057,32 +3862,24 @@ extern "C" int bpgpu_mpc_party_proof_share(bpgpu_ctx *c, size_t n, size_t nparti
     if (rc) return rc;
     if ((uint64_t)nparties * st2_bytes > 0x7fffffffull) return fail(c, BPGPU_ERR_INVALID_ARG, "batch too large for this shape");
     hipStream_t s = c->stream;
-    rc = ctx_enter(c, s);
-    if (rc) return rc;
-    prover_exit px{c, s};
-    const size_t sz_s2 = align_up(nparties * st2_bytes), sz_x = align_up(nch * 32), sz_in = sz_s2 + sz_x, sz_sh = align_up(nparties * share_len), sz_stat = align_up(nparties);
-    rc = io_reserve(c, sz_in + sz_sh + sz_stat);
-    if (rc) return px.finish(rc);
-    char *h = nullptr;
-    rc = pin_alloc(c, s, sz_in + sz_sh + sz_stat, &h);
-    if (rc) return px.finish(rc);
-    px.h = h;
-    px.host_secret_bytes = sz_in;
-    memcpy(h, state2, nparties * st2_bytes);
-    memcpy(h + sz_s2, poly_challenges, nch * 32);
-    char *d = c->io_dev, *d_sh = d + sz_in, *d_stat = d_sh + sz_sh;
-    PX_HIPCHK(px, hipMemcpyAsync(d, h, sz_in, hipMemcpyHostToDevice, s));
-    PX_HIPCHK(px, hipMemsetAsync(d_sh, 0, sz_sh + sz_stat, s));
+    host_call<bpgpu_ctx> io(c, s);
+    const int r_s2 = io.in(nparties * st2_bytes), r_x = io.in(nch * 32), r_sh = io.out(nparties * share_len), r_stat = io.out(nparties);
+    io.secrets(io.in_bytes());
+    rc = io.open();
+    if (rc) return io.finish(rc);
+    io.put(r_s2, state2, nparties * st2_bytes);
+    io.put(r_x, poly_challenges, nch * 32);
+    rc = io.upload();
+    if (!rc) rc = HIPRC(c, hipMemsetAsync(io.d(r_sh), 0, io.out_bytes(), s));
+    if (rc) return io.finish(rc);
     const uint32_t np32 = (uint32_t)nparties;
-    LAUNCH(c, s, "mpc_share", k_mpc_share, (np32 + BP_BLOCK - 1) / BP_BLOCK, BP_BLOCK, np32, (uint32_t)n, (const uint32_t *)d, (const uint8_t *)(d + sz_s2),
-           challenges_shared ? 1u : 0u, (uint32_t *)d_sh, (uint8_t *)d_stat);
+    LAUNCH(c, s, "mpc_share", k_mpc_share, (np32 + BP_BLOCK - 1) / BP_BLOCK, BP_BLOCK, np32, (uint32_t)n, (const uint32_t *)io.d(r_s2), (const uint8_t *)io.d(r_x),
+           challenges_shared ? 1u : 0u, (uint32_t *)io.d(r_sh), (uint8_t *)io.d(r_stat));
     if (hipGetLastError() != hipSuccess) rc = fail(c, BPGPU_ERR_HIP, "launch failed");
-    char *h_out = h + sz_in;
-    if (!rc && hipMemcpyAsync(h_out, d_sh, sz_sh + sz_stat, hipMemcpyDeviceToHost, s) != hipSuccess) rc = fail(c, BPGPU_ERR_HIP, "D2H copy failed");
-    rc = px.finish(rc);
+    rc = io.finish(io.download(rc));
     if (rc) return rc;
-    memcpy(shares, h_out, nparties * share_len);
-    memcpy(status, h_out + sz_sh, nparties);
+    memcpy(shares, io.h(r_sh), nparties * share_len);
+    memcpy(status, io.h(r_stat), nparties);
     return BPGPU_OK;
 }
 
@@ -4103,31 +3900,25 @@ static int mpc_dealer_shape(bpgpu_ctx *c, size_t n, size_t m, size_t *k_out) {
 static int mpc_point_sums(bpgpu_ctx *c, size_t m, size_t nsessions, const uint8_t *in, uint32_t rec, uint32_t off, uint32_t ncol, uint8_t *out, uint8_t *st) {
     if ((uint64_t)nsessions * m * rec > 0x7fffffffull) return fail(c, BPGPU_ERR_INVALID_ARG, "batch too large for this shape");
     hipStream_t s = c->stream;
-    int rc = ctx_enter(c, s);
+    host_call<bpgpu_ctx> io(c, s);
+    const int r_in = io.in(nsessions * m * rec), r_o = io.out(nsessions * ncol * 32), r_st = io.out(nsessions * 4);
+    int rc = io.open();
     if (rc) return rc;
-    const size_t sz_in = align_up(nsessions * m * rec), sz_o = align_up(nsessions * ncol * 32), sz_st = align_up(nsessions * 4);
-    rc = io_reserve(c, sz_in + sz_o + sz_st);
-    if (rc) return rc;
-    char *h = nullptr;
-    rc = pin_alloc(c, s, sz_in + sz_o + sz_st, &h);
-    if (rc) return rc;
-    memcpy(h, in, nsessions * m * rec);
-    char *d = c->io_dev, *d_o = d + sz_in, *d_st = d_o + sz_o;
-    HIPCHK(c, hipMemcpyAsync(d, h, sz_in, hipMemcpyHostToDevice, s));
-    if (hipMemsetAsync(d_st, 0, sz_st, s) != hipSuccess) rc = fail(c, BPGPU_ERR_HIP, "memset failed");
+    io.put(r_in, in, nsessions * m * rec);
+    rc = io.upload();
+    if (!rc && hipMemsetAsync(io.d(r_st), 0, io.width(r_st), s) != hipSuccess) rc = fail(c, BPGPU_ERR_HIP, "memset failed");
     const uint32_t nt = (uint32_t)(nsessions * ncol);
     if (!rc) {
-        LAUNCH(c, s, "mpc_ptsum", k_mpc_ptsum, (nt + BP_BLOCK - 1) / BP_BLOCK, BP_BLOCK, nt, (uint32_t)m, ncol, rec, off, (const uint8_t *)d, (uint32_t *)d_o, (uint32_t *)d_st);
+        LAUNCH(c, s, "mpc_ptsum", k_mpc_ptsum, (nt + BP_BLOCK - 1) / BP_BLOCK, BP_BLOCK, nt, (uint32_t)m, ncol, rec, off, (const uint8_t *)io.d(r_in), (uint32_t *)io.d(r_o),
+               (uint32_t *)io.d(r_st));
         if (hipGetLastError() != hipSuccess) rc = fail(c, BPGPU_ERR_HIP, "launch failed");
     }
-    char *h_out = h + sz_in;
-    if (!rc && hipMemcpyAsync(h_out, d_o, sz_o + sz_st, hipMemcpyDeviceToHost, s) != hipSuccess) rc = fail(c, BPGPU_ERR_HIP, "D2H copy failed");
-    const int rc2 = ctx_leave(c, s), rc3 = host_wait(c, s);
-    if (rc || rc2 || rc3) return rc ? rc : (rc2 ? rc2 : rc3);
-    memcpy(out, h_out, nsessions * ncol * 32);
+    rc = io.finish(io.download(rc));
+    if (rc) return rc;
+    memcpy(out, io.h(r_o), nsessions * ncol * 32);
     for (size_t p = 0; p < nsessions; p++) {
         uint32_t v;
-        memcpy(&v, h_out + sz_o + p * 4, 4);
+        memcpy(&v, io.h(r_st) + p * 4, 4);
         st[p] = (uint8_t)v;
     }
     return BPGPU_OK;
@@ -4249,21 +4040,15 @@ static int mpc_assemble_locked(bpgpu_ctx *c, size_t n, size_t m, size_t k, size_
         }
     }
     hipStream_t s = c->stream;
-    rc = ctx_enter(c, s);
-    if (rc) return rc;
-    prover_exit px{c, s};
-    const size_t sz_sh = align_up(nsessions * m * share_len), sz_q = align_up(nsessions * 32), sz_sk = align_up(nsessions), sz_ts = align_up(nsessions * TS);
-    const size_t sz_in = sz_sh + 2 * sz_q + sz_sk + sz_ts, sz_pr = align_up(nsessions * proof_len), sz_stb = align_up(nsessions);
-    rc = io_reserve(c, sz_in + sz_pr + sz_stb);
-    if (rc) return px.finish(rc);
-    char *h = nullptr;
-    rc = pin_alloc(c, s, sz_in + sz_pr + sz_stb, &h);
-    if (rc) return px.finish(rc);
-    px.h = h;
-    px.host_secret_bytes = sz_sh;
-    memset(h, 0, sz_in);
-    memcpy(h, shares, nsessions * m * share_len);
-    char *h_yinv = h + sz_sh, *h_w = h_yinv + sz_q, *h_sk = h_w + sz_q, *h_ts = h_sk + sz_sk;
+    host_call<bpgpu_ctx> io(c, s);
+    const int r_sh = io.in(nsessions * m * share_len), r_yinv = io.in(nsessions * 32), r_w = io.in(nsessions * 32), r_sk = io.in(nsessions), r_ts = io.in(nsessions * TS);
+    const int r_pr = io.out(nsessions * proof_len), r_stb = io.out(nsessions);
+    io.secrets(io.off[r_yinv]);   // the shares
+    rc = io.open();
+    if (rc) return io.finish(rc);
+    memset(io.h(r_sh), 0, io.in_bytes());
+    io.put(r_sh, shares, nsessions * m * share_len);
+    char *h_yinv = io.h(r_yinv), *h_w = io.h(r_w), *h_sk = io.h(r_sk), *h_ts = io.h(r_ts);
     std::vector<uint8_t> fixed(nsessions * 96);   // t_x, t_x_blinding, e_blinding
     const uint8_t ltx[3] = {'t', '_', 'x'}, ltxb[12] = {'t', '_', 'x', '_', 'b', 'l', 'i', 'n', 'd', 'i', 'n', 'g'},
                   leb[10] = {'e', '_', 'b', 'l', 'i', 'n', 'd', 'i', 'n', 'g'}, lw[1] = {'w'}, lipp[6] = {'i', 'p', 'p', ' ', 'v', '1'}, ln[1] = {'n'};
@@ -4302,12 +4087,13 @@ static int mpc_assemble_locked(bpgpu_ctx *c, size_t n, size_t m, size_t k, size_
         memcpy(h_yinv + p * 32, yinv.v, 32);
         memcpy(h_w + p * 32, wch.v, 32);
     }
-    char *d = c->io_dev, *d_yinv = d + sz_sh, *d_w = d_yinv + sz_q, *d_sk = d_w + sz_q, *d_ts = d_sk + sz_sk, *d_pr = d + sz_in, *d_stb = d_pr + sz_pr;
-    PX_HIPCHK(px, hipMemcpyAsync(d, h, sz_in, hipMemcpyHostToDevice, s));
-    PX_HIPCHK(px, hipMemsetAsync(d_pr, 0, sz_pr + sz_stb, s));
+    char *d = io.d(r_sh), *d_yinv = io.d(r_yinv), *d_w = io.d(r_w), *d_sk = io.d(r_sk), *d_ts = io.d(r_ts), *d_pr = io.d(r_pr), *d_stb = io.d(r_stb);
+    rc = io.upload();
+    if (!rc) rc = HIPRC(c, hipMemsetAsync(d_pr, 0, io.out_bytes(), s));
+    if (rc) return io.finish(rc);
     const size_t w_v = align_up(nsessions * nm * 32), w_gs = align_up(2 * nsessions * (2 * nm + 2) * 32);
-    rc = mpc_work_reserve(c, 4 * w_v + w_gs);
-    if (rc) return px.finish(rc);
+    rc = rpp_reserve(c, 4 * w_v + w_gs);
+    if (rc) return io.finish(rc);
     uint32_t *avec = (uint32_t *)c->rpp_buf, *bvec = (uint32_t *)(c->rpp_buf + w_v), *Gf = (uint32_t *)(c->rpp_buf + 2 * w_v), *Hf = (uint32_t *)(c->rpp_buf + 3 * w_v),
              *gsc = (uint32_t *)(c->rpp_buf + 4 * w_v);
     do {
@@ -4321,15 +4107,14 @@ static int mpc_assemble_locked(bpgpu_ctx *c, size_t n, size_t m, size_t k, size_
         fx.gen_scalars = gsc;
         rc = ippc_core(c, s, nm, k, nsessions, avec, bvec, Gf, Hf, nullptr, nullptr, nullptr, 1, (uint32_t *)d_ts, (uint8_t *)d_pr + 224, proof_len, (uint8_t *)d_stb, &fx);
     } while (0);
-    char *h_out = h + sz_in;
-    if (!rc && (hipMemcpyAsync(h_out, d_pr, sz_pr + sz_stb, hipMemcpyDeviceToHost, s) != hipSuccess ||
-                hipMemcpyAsync(h_ts, d_ts, nsessions * TS, hipMemcpyDeviceToHost, s) != hipSuccess))
+    if (!rc && (io.download(0) || hipMemcpyAsync(h_ts, d_ts, nsessions * TS, hipMemcpyDeviceToHost, s) != hipSuccess))
         rc = fail(c, BPGPU_ERR_HIP, "D2H copy failed");
-    rc = px.finish(rc);
+    rc = io.finish(rc);
     if (rc) return rc;
+    const char *h_out = io.h(r_pr);
     for (size_t p = 0; p < nsessions; p++) {
         uint8_t *pr = proofs_out + p * proof_len;
-        if (!skip[p] && h_out[sz_pr + p]) {   // (the inner-product rounds refused the session's vectors)
+        if (!skip[p] && io.h(r_stb)[p]) {   // (the inner-product rounds refused the session's vectors)
             skip[p] = 1;
             status[p] = (uint8_t)MPC_ST_BAD_SCALAR;
         }
@@ -4662,34 +4447,27 @@ extern "C" int bpgpu_r1cs_verify_batch_ts(bpgpu_ctx *c, const bpgpu_r1cs_circuit
     const size_t TS = BPGPU_TRANSCRIPT_BYTES, m = circuit->m;
     std::lock_guard<std::mutex> lk(c->mu);
     HIPCHK(c, hipSetDevice(c->device));
-    const size_t sz_pr = align_up(nbatch * proof_stride + 64), sz_l = align_up(nbatch * 4), sz_c = align_up(nbatch * m * 32 + 64),
-                 sz_t = per_proof ? align_up(nbatch * TS) : 0, sz_r = rng32 ? align_up(nbatch * 32) : 0;
-    const size_t sz_in = sz_pr + sz_l + sz_c + sz_t + sz_r, sz_v = align_up(nbatch), sz_o = align_up(nbatch * 32), sz_to = transcripts_out ? align_up(nbatch * TS) : 0;
     hipStream_t s = c->stream;
-    int rc = ctx_enter(c, s);
+    host_call<bpgpu_ctx> io(c, s);
+    const int r_pr = io.in(nbatch * proof_stride + 64), r_l = io.in(nbatch * 4), r_c = io.in(nbatch * m * 32 + 64), r_t = io.in(per_proof ? nbatch * TS : 0),
+              r_r = io.in(rng32 ? nbatch * 32 : 0);
+    const int r_v = io.out(nbatch), r_o = io.out(nbatch * 32), r_to = io.out(transcripts_out ? nbatch * TS : 0);
+    int rc = io.open();
     if (rc) return rc;
-    rc = io_reserve(c, sz_in + sz_v + sz_o + sz_to);
+    io.put(r_pr, proofs, nbatch * proof_stride);
+    io.put(r_l, proof_lens, nbatch * 4);
+    if (m) io.put(r_c, commitments, nbatch * m * 32);
+    if (per_proof) io.put(r_t, transcripts, nbatch * TS);
+    if (rng32) io.put(r_r, rng32, nbatch * 32);
+    rc = io.upload();
+    if (!rc)
+        rc = r1cs_verify_dev_locked(c, circuit, nbatch, io.d(r_pr), proof_stride, io.d(r_l), io.d(r_c), per_proof ? nullptr : transcripts, per_proof ? io.d(r_t) : nullptr,
+                                    rng32 ? io.d(r_r) : nullptr, io.d(r_v), io.d(r_o), transcripts_out ? io.d(r_to) : nullptr, s);
+    rc = io.finish(io.download(rc));
     if (rc) return rc;
-    char *h = nullptr;
-    rc = pin_alloc(c, s, sz_in + sz_v + sz_o + sz_to, &h);
-    if (rc) return rc;
-    char *d = c->io_dev;
-    char *d_pr = d, *d_l = d_pr + sz_pr, *d_c = d_l + sz_l, *d_t = d_c + sz_c, *d_r = d_t + sz_t, *d_v = d + sz_in, *d_o = d_v + sz_v, *d_to = d_o + sz_o;
-    memcpy(h, proofs, nbatch * proof_stride);
-    memcpy(h + sz_pr, proof_lens, nbatch * 4);
-    if (m) memcpy(h + sz_pr + sz_l, commitments, nbatch * m * 32);
-    if (per_proof) memcpy(h + sz_pr + sz_l + sz_c, transcripts, nbatch * TS);
-    if (rng32) memcpy(h + sz_pr + sz_l + sz_c + sz_t, rng32, nbatch * 32);
-    HIPCHK(c, hipMemcpyAsync(d, h, sz_in, hipMemcpyHostToDevice, s));
-    rc = r1cs_verify_dev_locked(c, circuit, nbatch, d_pr, proof_stride, d_l, d_c, per_proof ? nullptr : transcripts, per_proof ? d_t : nullptr,
-                                rng32 ? d_r : nullptr, d_v, d_o, transcripts_out ? d_to : nullptr, s);
-    char *h_out = h + sz_in;
-    if (!rc && hipMemcpyAsync(h_out, d_v, sz_v + sz_o + sz_to, hipMemcpyDeviceToHost, s) != hipSuccess) rc = fail(c, BPGPU_ERR_HIP, "D2H copy failed");
-    const int rc2 = ctx_leave(c, s), rc3 = host_wait(c, s);
-    if (rc || rc2 || rc3) return rc ? rc : (rc2 ? rc2 : rc3);
-    memcpy(verdict, h_out, nbatch);
-    if (msm_out) memcpy(msm_out, h_out + sz_v, nbatch * 32);
-    if (transcripts_out) memcpy(transcripts_out, h_out + sz_v + sz_o, nbatch * TS);
+    memcpy(verdict, io.h(r_v), nbatch);
+    if (msm_out) memcpy(msm_out, io.h(r_o), nbatch * 32);
+    if (transcripts_out) memcpy(transcripts_out, io.h(r_to), nbatch * TS);
     return BPGPU_OK;
 }
 
@@ -4835,17 +4613,13 @@ extern "C" int bpgpu_r1cs_verify_rlc(bpgpu_ctx *c, size_t ngroups, const bpgpu_r
         off[4 * g + 2] = in, in += nb ? align_up(nb * circuits[g]->m * 32 + 64) : 0;
         off[4 * g + 3] = in, in += (nb && transcript_stride[g]) ? align_up(nb * TS) : 0;
     }
-    const size_t off_r = in, off_w = off_r + align_up(total * 32), sz_in = off_w + (weights64 ? align_up(total * 64) : 0);
-    const size_t sz_v = align_up(total), sz_b = align_up(64), sz_to = transcripts_out ? align_up(total * TS) : 0, sz_out = sz_v + sz_b + sz_to;
     hipStream_t s = c->stream;
-    int rc = ctx_enter(c, s);
+    host_call<bpgpu_ctx> io(c, s);
+    const int r_g = io.in(in), r_r = io.in(total * 32), r_w = io.in(weights64 ? total * 64 : 0);   // (the groups' pieces: off[] inside r_g)
+    const int r_v = io.out(total), r_b = io.out(64), r_to = io.out(transcripts_out ? total * TS : 0);
+    int rc = io.open();
     if (rc) return rc;
-    rc = io_reserve(c, sz_in + sz_out);
-    if (rc) return rc;
-    char *h = nullptr;
-    rc = pin_alloc(c, s, sz_in + sz_out, &h);
-    if (rc) return rc;
-    char *d = c->io_dev;
+    char *h = io.h(r_g), *d = io.d(r_g);
     std::vector<r1cs_rlc_group> gr;
     size_t gp = 0;
     for (size_t g = 0; g < ngroups; g++) {
@@ -4860,50 +4634,43 @@ extern "C" int bpgpu_r1cs_verify_rlc(bpgpu_ctx *c, size_t ngroups, const bpgpu_r
         gp += nb;
     }
     if (rng32) {
-        memcpy(h + off_r, rng32, total * 32);
+        io.put(r_r, rng32, total * 32);
     } else {   // drawn once, as the per-proof path's seeded mode draws them (R1_RNG_DOMAIN), for the combination and any fallback alike
         uint32_t seed[8];
         if (c->test_seed_set) memcpy(seed, c->test_seed, 32);
-        else if (!bp::fast_random((uint8_t *)seed, 32)) return fail(c, BPGPU_ERR_HIP, "getrandom failed");
+        else if (!bp::fast_random((uint8_t *)seed, 32)) return io.finish(fail(c, BPGPU_ERR_HIP, "getrandom failed"));
         for (size_t p = 0; p < total; p++) {
             uint32_t kw[16];
             chacha20_block(seed, (uint64_t)p, R1_RNG_DOMAIN, 0u, kw);
-            memcpy(h + off_r + 32 * p, kw, 32);   // (little-endian words: the bytes k_r1cs_front takes from them)
+            memcpy(io.h(r_r) + 32 * p, kw, 32);   // (little-endian words: the bytes k_r1cs_front takes from them)
         }
     }
-    if (weights64) memcpy(h + off_w, weights64, total * 64);
-    HIPCHK(c, hipMemcpyAsync(d, h, sz_in, hipMemcpyHostToDevice, s));
-    char *d_v = d + sz_in, *d_b = d_v + sz_v, *d_to = d_b + sz_b;
-    char *h_out = h + sz_in;
-    rc = r1cs_rlc_dev_locked(c, gr, total, d + off_r, weights64 ? d + off_w : nullptr, (uint8_t *)d_v, (uint8_t *)d_b, transcripts_out ? d_to : nullptr, s);
-    if (!rc && hipMemcpyAsync(h_out, d_v, sz_out, hipMemcpyDeviceToHost, s) != hipSuccess) rc = fail(c, BPGPU_ERR_HIP, "D2H copy failed");
-    int rc2 = ctx_leave(c, s), rc3 = host_wait(c, s);
-    if (rc || rc2 || rc3) return rc ? rc : (rc2 ? rc2 : rc3);
-    if ((uint8_t)h_out[sz_v] != 0) {
+    if (weights64) io.put(r_w, weights64, total * 64);
+    char *d_r = io.d(r_r), *d_v = io.d(r_v);
+    rc = io.upload();
+    if (!rc)
+        rc = r1cs_rlc_dev_locked(c, gr, total, d_r, weights64 ? io.d(r_w) : nullptr, (uint8_t *)d_v, (uint8_t *)io.d(r_b), transcripts_out ? io.d(r_to) : nullptr, s);
+    rc = io.finish(io.download(rc));
+    if (rc) return rc;
+    if ((uint8_t)io.h(r_b)[0] != 0) {
         // R is not the identity, or a point did not decode: every group again through the per-proof chain, with the same rng bytes
         // (inputs are still on the device; the transcripts it leaves are the ones already copied out)
-        uint8_t bo[33];
-        memcpy(bo, h_out + sz_v, 33);
-        rc = ctx_enter(c, s, true);
+        rc = io.rerun_per_proof(r_v, r_b, [&] {
+            int rcg = BPGPU_OK;
+            for (const auto &g : gr)   // (in slices of R1_RLC_SLICE proofs, as above: the staging stays bounded)
+                for (size_t f = 0; f < g.nbatch && !rcg; f += R1_RLC_SLICE) {
+                    const size_t cnt = std::min<size_t>(R1_RLC_SLICE, g.nbatch - f);
+                    rcg = r1cs_verify_dev_locked(c, g.ci, cnt, g.d_proofs + f * g.proof_stride, g.proof_stride, g.d_lens + f * 4,
+                                                 g.d_coms ? g.d_coms + f * g.ci->m * 32 : nullptr, g.shared_ts, g.d_ts ? g.d_ts + f * TS : nullptr,
+                                                 d_r + 32 * (g.gp0 + f), d_v + g.gp0 + f, nullptr, nullptr, s);
+                }
+            return rcg;
+        });
         if (rc) return rc;
-        for (const auto &g : gr) {   // (in slices of R1_RLC_SLICE proofs, as above: the staging stays bounded)
-            for (size_t f = 0; f < g.nbatch && !rc; f += R1_RLC_SLICE) {
-                const size_t cnt = std::min<size_t>(R1_RLC_SLICE, g.nbatch - f);
-                rc = r1cs_verify_dev_locked(c, g.ci, cnt, g.d_proofs + f * g.proof_stride, g.proof_stride, g.d_lens + f * 4,
-                                            g.d_coms ? g.d_coms + f * g.ci->m * 32 : nullptr, g.shared_ts, g.d_ts ? g.d_ts + f * TS : nullptr,
-                                            d + off_r + 32 * (g.gp0 + f), d_v + g.gp0 + f, nullptr, nullptr, s);
-            }
-            if (rc) break;
-        }
-        if (!rc && hipMemcpyAsync(h_out, d_v, sz_v, hipMemcpyDeviceToHost, s) != hipSuccess) rc = fail(c, BPGPU_ERR_HIP, "D2H copy failed");
-        rc2 = ctx_leave(c, s);
-        rc3 = host_wait(c, s);
-        if (rc || rc2 || rc3) return rc ? rc : (rc2 ? rc2 : rc3);
-        memcpy(h_out + sz_v, bo, 33);
     }
-    memcpy(verdict, h_out, total);
-    if (batch_out) memcpy(batch_out, h_out + sz_v, 33);
-    if (transcripts_out) memcpy(transcripts_out, h_out + sz_v + sz_b, total * TS);
+    memcpy(verdict, io.h(r_v), total);
+    if (batch_out) memcpy(batch_out, io.h(r_b), 33);
+    if (transcripts_out) memcpy(transcripts_out, io.h(r_to), total * TS);
     return BPGPU_OK;
 }
 
@@ -5003,55 +4770,43 @@ extern "C" int bpgpu_linear_verify_rlc(bpgpu_ctx *c, size_t n, size_t nbatch, co
     std::lock_guard<std::mutex> lk(c->mu);
     HIPCHK(c, hipSetDevice(c->device));
     const size_t nb_b = b_shared ? 1 : nbatch;
-    const size_t sz_pr = align_up(nbatch * proof_len + 64), sz_c = align_up(nbatch * 32 + 64), sz_g = align_up(n * 32 + 64), sz_fb = align_up(64 + 64),
-                 sz_bv = align_up(nb_b * n * 32 + 64), sz_w = weights64 ? align_up(nbatch * 64) : 0;
-    const size_t sz_in = sz_pr + sz_c + sz_g + sz_fb + sz_bv + sz_w, sz_v = align_up(nbatch), sz_bo = align_up(64);
-    const size_t sz_t = transcripts_out ? align_up(nbatch * BPGPU_TRANSCRIPT_BYTES) : 0, sz_out = sz_v + sz_bo + sz_t;
     hipStream_t s = c->stream;
-    int rc = ctx_enter(c, s);
+    host_call<bpgpu_ctx> io(c, s);
+    const int r_pr = io.in(nbatch * proof_len + 64), r_c = io.in(nbatch * 32 + 64), r_g = io.in(n * 32 + 64), r_fb = io.in(64 + 64), r_bv = io.in(nb_b * n * 32 + 64),
+              r_w = io.in(weights64 ? nbatch * 64 : 0);
+    const int r_v = io.out(nbatch), r_bo = io.out(64), r_t = io.out(transcripts_out ? nbatch * BPGPU_TRANSCRIPT_BYTES : 0);
+    int rc = io.open();
     if (rc) return rc;
-    rc = io_reserve(c, sz_in + sz_out);
-    if (rc) return rc;
-    char *h = nullptr;
-    rc = pin_alloc(c, s, sz_in + sz_out, &h);
-    if (rc) return rc;
-    char *d = c->io_dev;
-    char *d_pr = d, *d_c = d_pr + sz_pr, *d_g = d_c + sz_c, *d_fb = d_g + sz_g, *d_bv = d_fb + sz_fb, *d_w = d_bv + sz_bv, *d_v = d + sz_in, *d_bo = d_v + sz_v;
-    char *d_t = transcripts_out ? d_bo + sz_bo : nullptr;
-    memcpy(h, proofs, nbatch * proof_len);
-    memcpy(h + sz_pr, C, nbatch * 32);
+    io.put(r_pr, proofs, nbatch * proof_len);
+    io.put(r_c, C, nbatch * 32);
     if (n) {
-        if (!from_gens) memcpy(h + sz_pr + sz_c, G, n * 32);
-        memcpy(h + sz_pr + sz_c + sz_g + sz_fb, b, nb_b * n * 32);
+        if (!from_gens) io.put(r_g, G, n * 32);
+        io.put(r_bv, b, nb_b * n * 32);
     }
     if (!from_gens) {
-        memcpy(h + sz_pr + sz_c + sz_g, F, 32);
-        memcpy(h + sz_pr + sz_c + sz_g + 32, B, 32);
+        memcpy(io.h(r_fb), F, 32);
+        memcpy(io.h(r_fb) + 32, B, 32);
     }
-    if (weights64) memcpy(h + sz_in - sz_w, weights64, nbatch * 64);
-    HIPCHK(c, hipMemcpyAsync(d, h, sz_in, hipMemcpyHostToDevice, s));
-    const void *a_g = from_gens ? nullptr : d_g, *a_f = from_gens ? nullptr : d_fb, *a_b = from_gens ? nullptr : d_fb + 32;
-    rc = lin_rlc_dev_locked(c, n, nbatch, d_pr, proof_len, label, label_len, shared_transcript, d_c, a_g, a_f, a_b, d_bv, b_shared,
-                            weights64 ? d_w : nullptr, (uint8_t *)d_v, (uint8_t *)d_bo, d_t, s);
-    char *h_out = h + sz_in;
-    if (!rc && hipMemcpyAsync(h_out, d_v, sz_out, hipMemcpyDeviceToHost, s) != hipSuccess) rc = fail(c, BPGPU_ERR_HIP, "D2H copy failed");
-    int rc2 = ctx_leave(c, s), rc3 = host_wait(c, s);
-    if (rc || rc2 || rc3) return rc ? rc : (rc2 ? rc2 : rc3);
-    if (batch_out) memcpy(batch_out, h_out + sz_v, 33);   // (R as computed before any fallback)
-    if (transcripts_out) memcpy(transcripts_out, h_out + sz_v + sz_bo, nbatch * BPGPU_TRANSCRIPT_BYTES);
-    if ((uint8_t)h_out[sz_v] != 0) {
+    if (weights64) io.put(r_w, weights64, nbatch * 64);
+    const void *a_g = from_gens ? nullptr : io.d(r_g), *a_f = from_gens ? nullptr : io.d(r_fb), *a_b = from_gens ? nullptr : io.d(r_fb) + 32;
+    rc = io.upload();
+    if (!rc)
+        rc = lin_rlc_dev_locked(c, n, nbatch, io.d(r_pr), proof_len, label, label_len, shared_transcript, io.d(r_c), a_g, a_f, a_b, io.d(r_bv), b_shared,
+                                weights64 ? io.d(r_w) : nullptr, (uint8_t *)io.d(r_v), (uint8_t *)io.d(r_bo), transcripts_out ? io.d(r_t) : nullptr, s);
+    rc = io.finish(io.download(rc));
+    if (rc) return rc;
+    if (batch_out) memcpy(batch_out, io.h(r_bo), 33);   // (R as computed before any fallback)
+    if (transcripts_out) memcpy(transcripts_out, io.h(r_t), nbatch * BPGPU_TRANSCRIPT_BYTES);
+    if ((uint8_t)io.h(r_bo)[0] != 0) {
         // R is not the identity, or a point of the combined MSM did not decode: the batch again through the per-proof path (inputs are
         // still on the device; the transcripts it leaves are the ones already copied out)
-        rc = ctx_enter(c, s, true);
+        rc = io.rerun_per_proof(r_v, r_bo, [&] {
+            return lin_verify_dev_locked(c, n, nbatch, io.d(r_pr), proof_len, label, label_len, shared_transcript, io.d(r_c), a_g, a_f, a_b, io.d(r_bv), b_shared,
+                                         io.d(r_v), nullptr, nullptr, s);
+        });
         if (rc) return rc;
-        rc = lin_verify_dev_locked(c, n, nbatch, d_pr, proof_len, label, label_len, shared_transcript, d_c, a_g, a_f, a_b, d_bv, b_shared, d_v, nullptr,
-                                   nullptr, s);
-        if (!rc && hipMemcpyAsync(h_out, d_v, sz_v, hipMemcpyDeviceToHost, s) != hipSuccess) rc = fail(c, BPGPU_ERR_HIP, "D2H copy failed");
-        rc2 = ctx_leave(c, s);
-        rc3 = host_wait(c, s);
-        if (rc || rc2 || rc3) return rc ? rc : (rc2 ? rc2 : rc3);
     }
-    memcpy(verdict, h_out, nbatch);
+    memcpy(verdict, io.h(r_v), nbatch);
     return BPGPU_OK;
 }
 
@@ -5227,52 +4982,36 @@ extern "C" int bpgpu_r1cs_prove_batch(bpgpu_ctx *c, const bpgpu_r1cs_circuit *ci
     rc = r1cs_witness_on(c, wi, &dw);
     if (rc) return rc;
     hipStream_t s = c->stream;
-    rc = ctx_enter(c, s);
-    if (rc) return rc;
-    prover_exit px{c, s};
     // ---- inputs through pinned staging into the persistent IO buffer
-    const size_t sz_v = align_up(nbatch * m * 32 + 64), sz_f = align_up(nbatch * nf * 32 + 64), sz_rng = align_up(nbatch * 32), sz_ts = align_up(nbatch * TS);
-    const size_t sz_in = 2 * sz_v + sz_f + sz_rng + sz_ts;
-    const size_t sz_rec = align_up(nbatch * R1P_NREC * 32), sz_ipp = align_up(nbatch * ipp_len), sz_st = align_up(nbatch * 4), sz_stb = align_up(nbatch + 64);
-    const size_t sz_out = sz_rec + sz_ipp + sz_v + sz_st + sz_stb + sz_ts;
-    rc = io_reserve(c, sz_in + sz_out);
-    if (rc) return px.finish(rc);
-    char *h = nullptr;
-    rc = pin_alloc(c, s, sz_in + sz_out, &h);
-    if (rc) return px.finish(rc);
-    px.h = h;
-    px.host_secret_bytes = 2 * sz_v + sz_f + sz_rng;   // values, blindings, free inputs, the rng seeds
+    host_call<bpgpu_ctx> io(c, s);
+    const int r_v = io.in(nbatch * m * 32 + 64), r_vb = io.in(nbatch * m * 32 + 64), r_free = io.in(nbatch * nf * 32 + 64), r_rng = io.in(nbatch * 32), r_ts = io.in(nbatch * TS);
+    const int r_rec = io.out(nbatch * R1P_NREC * 32), r_ipp = io.out(nbatch * ipp_len), r_vout = io.out(nbatch * m * 32 + 64), r_stat = io.out(nbatch * 4),
+              r_stb = io.out(nbatch + 64), r_to = io.out(nbatch * TS);
+    io.secrets(io.off[r_ts]);   // values, blindings, free inputs, the rng seeds
+    rc = io.open();
+    if (rc) return io.finish(rc);
     if (m) {
-        memcpy(h, v, nbatch * m * 32);
-        memcpy(h + sz_v, v_blinding, nbatch * m * 32);
+        io.put(r_v, v, nbatch * m * 32);
+        io.put(r_vb, v_blinding, nbatch * m * 32);
     }
-    if (nf) memcpy(h + 2 * sz_v, free_inputs, nbatch * nf * 32);
-    if (rng32) memcpy(h + 2 * sz_v + sz_f, rng32, nbatch * 32);
-    else if ((rc = os_random(c, h + 2 * sz_v + sz_f, nbatch * 32)) != 0) return px.finish(rc);   // finalize(&mut thread_rng())
-    for (size_t p = 0; p < nbatch; p++) memcpy(h + 2 * sz_v + sz_f + sz_rng + p * TS, transcripts + p * transcript_stride, TS);
-    char *d_in = c->io_dev;
-    const uint8_t *d_v = (const uint8_t *)d_in, *d_vb = (const uint8_t *)(d_in + sz_v), *d_free = (const uint8_t *)(d_in + 2 * sz_v),
-                  *d_rng = (const uint8_t *)(d_in + 2 * sz_v + sz_f);
-    uint32_t *d_ts = (uint32_t *)(d_in + 2 * sz_v + sz_f + sz_rng);
-    char *d_outb = d_in + sz_in;
-    uint32_t *d_rec = (uint32_t *)d_outb, *d_vout = (uint32_t *)(d_outb + sz_rec + sz_ipp), *d_stat = (uint32_t *)(d_outb + sz_rec + sz_ipp + sz_v);
-    uint8_t *d_ipp = (uint8_t *)(d_outb + sz_rec), *d_stb = (uint8_t *)d_stat + sz_st;
-    PX_HIPCHK(px, hipMemcpyAsync(d_in, h, sz_in, hipMemcpyHostToDevice, s));
-    PX_HIPCHK(px, hipMemsetAsync(d_outb, 0, sz_out, s));
+    if (nf) io.put(r_free, free_inputs, nbatch * nf * 32);
+    if (rng32) io.put(r_rng, rng32, nbatch * 32);
+    else if ((rc = os_random(c, io.h(r_rng), nbatch * 32)) != 0) return io.finish(rc);   // finalize(&mut thread_rng())
+    for (size_t p = 0; p < nbatch; p++) memcpy(io.h(r_ts) + p * TS, transcripts + p * transcript_stride, TS);
+    const uint8_t *d_v = (const uint8_t *)io.d(r_v), *d_vb = (const uint8_t *)io.d(r_vb), *d_free = (const uint8_t *)io.d(r_free), *d_rng = (const uint8_t *)io.d(r_rng);
+    uint32_t *d_ts = (uint32_t *)io.d(r_ts);
+    uint32_t *d_rec = (uint32_t *)io.d(r_rec), *d_vout = (uint32_t *)io.d(r_vout), *d_stat = (uint32_t *)io.d(r_stat);
+    uint8_t *d_ipp = (uint8_t *)io.d(r_ipp), *d_stb = (uint8_t *)io.d(r_stb);
+    rc = io.upload();
+    if (!rc) rc = HIPRC(c, hipMemsetAsync(io.d(r_rec), 0, io.out_bytes(), s));
+    if (rc) return io.finish(rc);
     // ---- working set
     const size_t w_gs = align_up(n_gsc * 32), w_mo = align_up(5 * nbatch * 32 + 64), w_ms = align_up(std::max(nbatch * m, 5 * nbatch) + 64),
                  w_rnd = align_up((size_t)sh.nrand * nbatch * 40), w_aw = align_up(3 * std::max(n, (size_t)1) * nbatch * 40),
                  w_f = align_up((size_t)sh.c.nfields * nbatch * 40), w_vec = align_up(6 * std::max(n, (size_t)1) * nbatch * 40),
                  w_t = align_up(7 * nrow * nbatch * 40), w_iv = align_up(nbatch * pn * 32), w_w = align_up(nbatch * 32);
     const size_t need = w_gs + w_mo + w_ms + w_rnd + w_aw + w_f + w_vec + w_t + 4 * w_iv + w_w;
-    if (c->rpp_cap < need) {   // (the old block is clean: every call clears it on its way out)
-        PX_HIPCHK(px, hipDeviceSynchronize());
-        if (c->rpp_buf) PX_HIPCHK(px, hipFree(c->rpp_buf));
-        c->rpp_buf = nullptr;
-        c->rpp_cap = 0;
-        PX_HIPCHK(px, hipMalloc((void **)&c->rpp_buf, need + need / 8));
-        c->rpp_cap = need + need / 8;
-    }
+    if ((rc = rpp_reserve(c, need))) return io.finish(rc);
     char *wb = c->rpp_buf;
     uint32_t *gsc = (uint32_t *)wb, *mo = (uint32_t *)(wb + w_gs);
     uint8_t *mst = (uint8_t *)mo + w_mo;
@@ -5338,15 +5077,12 @@ extern "C" int bpgpu_r1cs_prove_batch(bpgpu_ctx *c, const bpgpu_r1cs_circuit *ci
         fx.gen_scalars = gsc;
         rc = ippc_core(c, s, pn, k, nbatch, lv, rv, gf, hf, nullptr, nullptr, nullptr, 1, d_ts, d_ipp, ipp_len, d_stb, &fx);
     } while (0);
-    char *h_out = h + sz_in;
-    if (!rc && (hipMemcpyAsync((char *)d_stb + sz_stb, d_ts, nbatch * TS, hipMemcpyDeviceToDevice, s) != hipSuccess ||
-                hipMemcpyAsync(h_out, d_outb, sz_out, hipMemcpyDeviceToHost, s) != hipSuccess))
-        rc = fail(c, BPGPU_ERR_HIP, "D2H copy failed");
-    rc = px.finish(rc);
+    if (!rc && (hipMemcpyAsync(io.d(r_to), d_ts, nbatch * TS, hipMemcpyDeviceToDevice, s) != hipSuccess || io.download(0))) rc = fail(c, BPGPU_ERR_HIP, "D2H copy failed");
+    rc = io.finish(rc);
     if (rc) return rc;
     // R1CSProof::to_bytes (proof.rs:83-108): version 0 exactly when A_I2, A_O2, S2 are all the identity
-    const uint8_t *h_rec = (const uint8_t *)h_out, *h_ipp = h_rec + sz_rec, *h_v = h_ipp + sz_ipp, *h_st = h_v + sz_v, *h_stb = h_st + sz_st,
-                  *h_ts = h_stb + sz_stb;
+    const uint8_t *h_rec = (const uint8_t *)io.h(r_rec), *h_ipp = (const uint8_t *)io.h(r_ipp), *h_v = (const uint8_t *)io.h(r_vout),
+                  *h_st = (const uint8_t *)io.h(r_stat), *h_stb = (const uint8_t *)io.h(r_stb), *h_ts = (const uint8_t *)io.h(r_to);
     for (size_t p = 0; p < nbatch; p++) {
         const uint8_t *rec = h_rec + p * R1P_NREC * 32;
         bool one_phase = true;
@@ -5663,17 +5399,13 @@ static int rp_mix_host_call(bpgpu_ctx *c, size_t ngroups, const size_t *n, const
         off[3 * g + 1] = in, in += nbatch[g] ? align_up(nbatch[g] * m[g] * 32 + 64) : 0;
         off[3 * g + 2] = in, in += (ts && transcript_stride[g]) ? align_up(nbatch[g] * TS) : 0;
     }
-    const size_t off_r = in, off_w = off_r + (rng64 ? align_up(total * 64) : 0), sz_in = off_w + (weights64 ? align_up(total * 64) : 0);
-    const size_t sz_v = align_up(total), sz_b = align_up(64), sz_to = transcripts_out ? align_up(total * TS) : 0, sz_out = sz_v + sz_b + sz_to;
     hipStream_t s = c->stream;
-    int rc = ctx_enter(c, s);
+    host_call<bpgpu_ctx> io(c, s);
+    const int r_g = io.in(in), r_r = io.in(rng64 ? total * 64 : 0), r_w = io.in(weights64 ? total * 64 : 0);   // (the groups' pieces: off[] inside r_g)
+    const int r_v = io.out(total), r_b = io.out(64), r_to = io.out(transcripts_out ? total * TS : 0);
+    int rc = io.open();
     if (rc) return rc;
-    rc = io_reserve(c, sz_in + sz_out);
-    if (rc) return rc;
-    char *h = nullptr;
-    rc = pin_alloc(c, s, sz_in + sz_out, &h);
-    if (rc) return rc;
-    char *d = c->io_dev;
+    char *h = io.h(r_g), *d = io.d(r_g);
     const uint8_t *src_p = proofs, *src_c = commitments;
     for (size_t g = 0, gi = 0; g < ngroups; g++) {
         const size_t nb = nbatch[g];
@@ -5688,42 +5420,35 @@ static int rp_mix_host_call(bpgpu_ctx *c, size_t ngroups, const size_t *n, const
             memcpy(h + off[3 * g + 2], gr[gi].h_ts, nb * TS);
             gr[gi].d_ts_in = d + off[3 * g + 2];
         }
-        if (transcripts_out) gr[gi].d_ts_out = d + sz_in + sz_v + sz_b + gr[gi].gp0 * TS;
+        if (transcripts_out) gr[gi].d_ts_out = io.d(r_to) + gr[gi].gp0 * TS;
         gi++;
     }
-    if (rng64) memcpy(h + off_r, rng64, total * 64);
-    if (weights64) memcpy(h + off_w, weights64, total * 64);
-    HIPCHK(c, hipMemcpyAsync(d, h, sz_in, hipMemcpyHostToDevice, s));
-    char *d_v = d + sz_in, *d_b = d_v + sz_v;
-    char *h_out = h + sz_in;
+    if (rng64) io.put(r_r, rng64, total * 64);
+    if (weights64) io.put(r_w, weights64, total * 64);
+    char *d_v = io.d(r_v);
     const char *d_rng_used = nullptr;
-    rc = rp_mix_dev_locked(c, gr, total, rng64 ? d + off_r : nullptr, weights64 ? d + off_w : nullptr, (uint8_t *)d_v, (uint8_t *)d_b, s, &d_rng_used);
-    if (!rc && hipMemcpyAsync(h_out, d_v, sz_out, hipMemcpyDeviceToHost, s) != hipSuccess) rc = fail(c, BPGPU_ERR_HIP, "D2H copy failed");
-    int rc2 = ctx_leave(c, s), rc3 = host_wait(c, s);
-    if (rc || rc2 || rc3) return rc ? rc : (rc2 ? rc2 : rc3);
-    if ((uint8_t)h_out[sz_v] != 0) {
+    rc = io.upload();
+    if (!rc) rc = rp_mix_dev_locked(c, gr, total, rng64 ? io.d(r_r) : nullptr, weights64 ? io.d(r_w) : nullptr, (uint8_t *)d_v, (uint8_t *)io.d(r_b), s, &d_rng_used);
+    rc = io.finish(io.download(rc));
+    if (rc) return rc;
+    if ((uint8_t)io.h(r_b)[0] != 0) {
         // R is not the identity, or did not decode: every group the combination took again through the per-proof chain of its shape, with
         // the same rng bytes (inputs, and rng bytes drawn above, are still on the device)
-        uint8_t bo[33];
-        memcpy(bo, h_out + sz_v, 33);
-        rc = ctx_enter(c, s, true);
+        // (the per-proof path writes the same advanced states again: byte for byte those of bpgpu_rangeproof_verify_batch_ts either way)
+        rc = io.rerun_per_proof(r_v, r_b, [&] {
+            for (const auto &g : gr) {
+                if (g.whole) continue;
+                const int rcg = rp_verify_dev_locked(c, g.n, g.m, g.nbatch, g.d_proofs, g.proof_len, g.d_coms, rp_mix_transcripts(g), d_rng_used + 64 * g.gp0, d_v + g.gp0,
+                                                     nullptr, s);
+                if (rcg) return rcg;
+            }
+            return (int)BPGPU_OK;
+        });
         if (rc) return rc;
-        for (const auto &g : gr) {
-            if (g.whole) continue;
-            rc = rp_verify_dev_locked(c, g.n, g.m, g.nbatch, g.d_proofs, g.proof_len, g.d_coms, rp_mix_transcripts(g), d_rng_used + 64 * g.gp0, d_v + g.gp0,
-                                      nullptr, s);
-            if (rc) break;
-        }
-        // (the per-proof path wrote the same advanced states again: byte for byte those of bpgpu_rangeproof_verify_batch_ts either way)
-        if (!rc && hipMemcpyAsync(h_out, d_v, sz_v, hipMemcpyDeviceToHost, s) != hipSuccess) rc = fail(c, BPGPU_ERR_HIP, "D2H copy failed");
-        rc2 = ctx_leave(c, s);
-        rc3 = host_wait(c, s);
-        if (rc || rc2 || rc3) return rc ? rc : (rc2 ? rc2 : rc3);
-        memcpy(h_out + sz_v, bo, 33);
     }
-    memcpy(verdict, h_out, total);
-    if (batch_out) memcpy(batch_out, h_out + sz_v, 33);
-    if (transcripts_out) memcpy(transcripts_out, h_out + sz_v + sz_b, total * TS);
+    memcpy(verdict, io.h(r_v), total);
+    if (batch_out) memcpy(batch_out, io.h(r_b), 33);
+    if (transcripts_out) memcpy(transcripts_out, io.h(r_to), total * TS);
     return BPGPU_OK;
 }
 

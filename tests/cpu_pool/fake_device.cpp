@@ -80,6 +80,9 @@ struct ihipStream_t {
 struct ihipEvent_t {
     std::atomic<uint64_t> recorded{0}, done{0};   // tickets: record k completes when done >= k
 };
+// every stream the program created (hipDeviceSynchronize waits for all of them)
+static std::mutex g_streams_mu;
+static std::vector<ihipStream_t *> g_streams;
 static ihipStream_t *default_stream() {
     static ihipStream_t *s = new ihipStream_t();
     return s;
@@ -103,17 +106,33 @@ hipError_t hipGetLastError(void) { return hipSuccess; }
 const char *hipGetErrorString(hipError_t e) { return e == hipSuccess ? "no error" : "fake HIP error"; }
 hipError_t hipStreamCreateWithFlags(hipStream_t *s, unsigned) {
     *s = (hipStream_t) new ihipStream_t();
+    std::lock_guard<std::mutex> g(g_streams_mu);
+    g_streams.push_back((ihipStream_t *)*s);
     return hipSuccess;
 }
 hipError_t hipStreamDestroy(hipStream_t s) {
     if (s) {
         S(s)->sync();
+        {
+            std::lock_guard<std::mutex> g(g_streams_mu);
+            for (size_t i = 0; i < g_streams.size(); i++)
+                if (g_streams[i] == (ihipStream_t *)s) g_streams.erase(g_streams.begin() + i--);
+        }
         delete (ihipStream_t *)s;
     }
     return hipSuccess;
 }
 hipError_t hipStreamSynchronize(hipStream_t s) {
     S(s)->sync();
+    return hipSuccess;
+}
+hipError_t hipDeviceSynchronize(void) {
+    std::vector<ihipStream_t *> all;
+    {
+        std::lock_guard<std::mutex> g(g_streams_mu);
+        all = g_streams;
+    }
+    for (ihipStream_t *st : all) st->sync();
     return hipSuccess;
 }
 hipError_t hipStreamQuery(hipStream_t s) { return S(s)->idle() ? hipSuccess : hipErrorNotReady; }
@@ -194,6 +213,16 @@ hipError_t hipDeviceGetAttribute(int *v, hipDeviceAttribute_t, int) {
     return hipSuccess;
 }
 }   // extern "C"
+
+// a gate: the stream stops at it until fake_open_gates() (tests that need work to stay "in flight")
+static std::atomic<uint64_t> g_gates_pushed{0}, g_gates_open{0};
+extern "C" void fake_stream_gate(hipStream_t s) {
+    const uint64_t k = g_gates_pushed.fetch_add(1) + 1;
+    S(s)->push([k] {
+        while (g_gates_open.load(std::memory_order_acquire) < k) std::this_thread::sleep_for(std::chrono::microseconds(20));
+    });
+}
+extern "C" void fake_open_gates(void) { g_gates_open.store(g_gates_pushed.load(), std::memory_order_release); }
 
 // ---- the fake back end: what pool.hip calls of bpgpu.hip ---------------------------------------------------------------------
 static std::atomic<int> g_chains_running{0};
