@@ -29,7 +29,7 @@ EXPORTS = [
     "bpgpu_rangeproof_verify_batch_ts", "bpgpu_rangeproof_verify_batch_ts_dev", "bpgpu_ipp_verify_batch_dev",
     "bpgpu_ipp_create_batch", "bpgpu_rangeproof_prove_batch", "bpgpu_rangeproof_verify_batch_submit", "bpgpu_ctx_collect",
     "bpgpu_linear_verify_batch", "bpgpu_linear_verify_batch_dev", "bpgpu_linear_create_batch",
-    "bpgpu_linear_verify_rlc", "bpgpu_linear_verify_rlc_dev",
+    "bpgpu_linear_verify_rlc", "bpgpu_linear_verify_rlc_dev", "bpgpu_ipp_verify_rlc", "bpgpu_ipp_verify_rlc_dev",
     "bpgpu_rangeproof_audit_shares", "bpgpu_ipp_verification_scalars",
     "bpgpu_pool_create", "bpgpu_pool_destroy", "bpgpu_pool_last_error", "bpgpu_pool_set_option", "bpgpu_pool_get_option",
     "bpgpu_pool_devices", "bpgpu_pool_lanes", "bpgpu_pool_lane", "bpgpu_pool_gens_create", "bpgpu_pool_gens_load",
@@ -114,6 +114,8 @@ def lib():
     L.bpgpu_linear_verify_batch_dev.argtypes = [vp, sz, sz, vp, sz, u8p, sz, u8p, vp, vp, vp, vp, vp, i, vp, vp, vp, vp]
     L.bpgpu_linear_verify_rlc.argtypes = [vp, sz, sz, u8p, sz, u8p, sz, u8p, u8p, u8p, u8p, u8p, u8p, i, u8p, u8p, u8p, u8p]
     L.bpgpu_linear_verify_rlc_dev.argtypes = [vp, sz, sz, vp, sz, u8p, sz, u8p, vp, vp, vp, vp, vp, i, vp, vp, vp, vp, vp]
+    L.bpgpu_ipp_verify_rlc.argtypes = [vp, sz, sz, u8p, sz, u8p, sz, u8p, u8p, u8p, u8p, u8p, u8p, u8p, sz, u8p, u8p, u8p]
+    L.bpgpu_ipp_verify_rlc_dev.argtypes = [vp, sz, sz, vp, sz, u8p, sz, u8p, vp, vp, vp, vp, vp, vp, sz, vp, vp, vp, vp]
     L.bpgpu_ipp_verification_scalars.argtypes = [vp, sz, sz, u8p, sz, u8p, sz, u8p, sz, u8p, u8p, u8p, u8p, u8p]
     L.bpgpu_mpc_state1_bytes.argtypes = [sz]
     L.bpgpu_mpc_state1_bytes.restype = sz
@@ -422,6 +424,22 @@ class Context:
         msm = C.create_string_buffer(32 * max(nb, 1)) if want_msm else None
         self._chk(self._L.bpgpu_ipp_verify_batch(self.h, n, nb, proofs, proof_len, label, len(label), Gf, Hf, P, Q, G, H, verdict, msm))
         return (verdict.raw[:nb], msm.raw[:32 * nb]) if want_msm else verdict.raw[:nb]
+
+    def ipp_verify_rlc(self, n, proofs, proof_len, Gf, Hf, P, Q, G, H, label=b"", transcript=None, gens_m=1, weights64=None):
+        """Batch-combined InnerProductProof verification (bpgpu_ipp_verify_rlc) of len(P) / 32 proofs.  G, H: n points each, shared by
+        the batch, or both None: the context's G(n / gens_m, gens_m), H(n / gens_m, gens_m) through the window tables.  weights64: 64
+        bytes per proof or None (drawn by the library).  Returns (verdict bytes, batch_ok, 32-byte encoding of the combined point).  On
+        a failing combination the verdicts come from the per-proof path (automatic fallback)."""
+        nb = len(P) // 32
+        assert len(proofs) == nb * proof_len and len(Gf) == len(Hf) == 32 * n * nb and len(Q) == 32 * nb
+        assert G is None or len(G) == 32 * n
+        assert H is None or len(H) == 32 * n
+        assert weights64 is None or len(weights64) == 64 * nb
+        verdict = C.create_string_buffer(max(nb, 1))
+        bo = C.create_string_buffer(33)
+        self._chk(self._L.bpgpu_ipp_verify_rlc(self.h, n, nb, proofs, proof_len, label, len(label), transcript, Gf, Hf, P, Q, G, H, gens_m,
+                                               weights64, verdict, bo))
+        return verdict.raw[:nb], bo.raw[0] == 0, bo.raw[1:33]
 
     def ipp_verification_scalars(self, n, proofs, proof_len, label=b"", transcripts=None, want_transcripts=False):
         """InnerProductProof::verification_scalars for len(proofs) / proof_len proofs (bpgpu_ipp_verification_scalars): returns

@@ -4810,6 +4810,211 @@ extern "C" int bpgpu_linear_verify_rlc(bpgpu_ctx *c, size_t n, size_t nbatch, co
     return BPGPU_OK;
 }
 
+// ---- batch-combined InnerProductProof verification (ipp_rlc.h; an ADDITIONAL entry point, as bpgpu_linear_verify_rlc) ---------
+// generator-table mode: gens_m >= 1 divides n and the context holds G(n / gens_m, gens_m), H(n / gens_m, gens_m)
+static int ipp_rlc_gens_ok(bpgpu_ctx *c, size_t n, size_t gens_m) {
+    if (gens_m == 0 || n % gens_m != 0) return fail(c, BPGPU_ERR_INVALID_ARG, "gens_m=%zu does not divide n=%zu", gens_m, n);
+    if (!c->d_table) return fail(c, BPGPU_ERR_NO_GENS, "generators not loaded");
+    if (n / gens_m > c->gens_capacity || gens_m > c->party_capacity)
+        return fail(c, BPGPU_ERR_NO_GENS, "InvalidGeneratorsLength: generators too small for n=%zu m=%zu", n / gens_m, gens_m);
+    return BPGPU_OK;
+}
+
+// R = sum_p rho_p Check_p for bases shared by the batch: the front end of bpgpu_ipp_verification_scalars (k_ipp_vs_front: status, u_j^2,
+// u_j^-2 and the table (u_j, u_j^-1) per proof), the weights, the unique terms, the weigh launch over the 2n rows (G_0.., H_0..), their
+// reduction and ONE multiscalar multiplication -- the shared-generator MSM with nbatch U unique terms in generator-table mode
+// (d_G == d_H == NULL), one variable-base MSM of 2n + nbatch U terms with the caller's bases -- then the verdicts (undecided where R is
+// not the identity).  The staging lives in c->ipp_buf, the combined list and the accumulators in c->comb_buf; neither grows with
+// nbatch x n.
+static int ipp_rlc_dev_locked(bpgpu_ctx *c, size_t n, size_t nbatch, const void *d_proofs, size_t proof_len, const uint8_t *label,
+                              size_t label_len, const uint8_t *shared_ts, const void *d_Gf, const void *d_Hf, const void *d_P, const void *d_Q,
+                              const void *d_G, const void *d_H, size_t gens_m, const void *d_weights64, uint8_t *d_verdict, uint8_t *d_batch,
+                              hipStream_t s) {
+    if (nbatch > IPP_RLC_MAX_PROOFS) return fail(c, BPGPU_ERR_INVALID_ARG, "batch too large: more than 2^24 proofs in one combination");
+    if (shared_ts && !ts_state_ok(shared_ts)) return fail(c, BPGPU_ERR_INVALID_ARG, "malformed transcript state");
+    const bool fixed = d_G == nullptr && d_H == nullptr;
+    if (fixed) {
+        const int rcg = ipp_rlc_gens_ok(c, n, gens_m);
+        if (rcg) return rcg;
+    }
+    // InnerProductProof::from_bytes, length part (ipp.rs:374-388)
+    size_t k = 0;
+    bool fmt = proof_len % 32 != 0;
+    if (!fmt) {
+        const size_t ne = proof_len / 32;
+        if (ne < 2 || (ne - 2) % 2 != 0) fmt = true;
+        else {
+            k = (ne - 2) / 2;
+            if (k >= 32) fmt = true;
+        }
+    }
+    if (fmt) {   // every proof is a FormatError: the empty sum
+        HIPCHK(c, hipMemsetAsync(d_verdict, BPGPU_VERDICT_FORMAT_ERROR, nbatch, s));
+        if (d_batch) HIPCHK(c, hipMemsetAsync(d_batch, 0, 33, s));
+        return BPGPU_OK;
+    }
+    const bool shape_bad = n != ((size_t)1 << k);   // ipp.rs:203-211
+    if (!shape_bad && k > BP_RP_MAX_K) return fail(c, BPGPU_ERR_INVALID_ARG, "n > 2^%d not supported", BP_RP_MAX_K);
+    ipp_shape sh;
+    sh.n = shape_bad ? 0u : (uint32_t)n;
+    sh.k = (uint32_t)k;
+    sh.N = 0;
+    sh.proof_len = (uint32_t)proof_len;
+    sh.nproofs = (uint32_t)nbatch;
+    sh.shape_verdict = shape_bad ? BPGPU_VERDICT_VERIFICATION_ERROR : 0;
+    sh.bases_shared = 1;
+    const size_t U = 2 * k + 2, nrows = 2 * n + (fixed ? 2 : 0), head = fixed ? 0 : 2 * n, nterms = head + nbatch * U, kk = k ? k : 1;
+    if (nbatch * U > IPP_RLC_MAX_TERMS) return fail(c, BPGPU_ERR_INVALID_ARG, "batch too large: more than 2^24 proof-specific terms in one combination");
+    const uint32_t nb32 = (uint32_t)nbatch, nstride = (uint32_t)((nbatch + 63) / 64 * 64);
+    // rows per weigh lane (n = 2^k: a divisor of n): a Gray-code walk where the launch stays wide enough without the lanes it folds
+    const size_t wB = (uint64_t)nstride * 2 * n < IPP_RLC_BLOCK_MIN_PAIRS ? 1 : (n < IPP_RLC_BLOCK ? n : IPP_RLC_BLOCK);
+    const uint64_t nt = shape_bad ? 0 : (uint64_t)nstride * (2 * n / wB);   // (a multiple of 64: whole wavefronts)
+    if (nt > 0x7fffffffull) return fail(c, BPGPU_ERR_INVALID_ARG, "batch too large for this shape");
+    // staging: front-end status, u_j^2, u_j^-2 (zeroed: a proof that stops writes none), the tables, rho a / rho b, MSM status / result
+    const size_t sz_st = align_up(nbatch * 4), sz_u = align_up(nbatch * kk * 32), sz_tab = align_up(nbatch * kk * 80), sz_ab = align_up(nbatch * 80),
+                 sz_b = align_up(64), sz_o = align_up(64);
+    int rc = ipp_reserve(c, sz_st + 2 * sz_u + sz_tab + sz_ab + sz_b + sz_o);
+    if (rc) return rc;
+    char *d_stat = c->ipp_buf, *d_us = d_stat + sz_st, *d_ui = d_us + sz_u, *d_tab = d_ui + sz_u, *d_ab = d_tab + sz_tab, *d_mst = d_ab + sz_ab,
+         *d_out = d_mst + sz_b;
+    arena_plan ap;
+    const size_t off_csc = ap.add(nterms * 32 + 64), off_cpt = ap.add(nterms * 32 + 64), off_acc = ap.add(nrows * 80), off_row = ap.add(nrows * 32 + 64),
+                 off_rho = ap.add(nbatch * 32), off_bo = ap.add(64);
+    rc = comb_reserve(c, ap.total);
+    if (rc) return rc;
+    char *b = c->comb_buf, *d_csc = b + off_csc, *d_cpt = b + off_cpt, *d_acc = b + off_acc, *d_row = b + off_row, *d_rho = b + off_rho, *d_bo = b + off_bo;
+    if (!d_batch) d_batch = (uint8_t *)d_bo;
+    HIPCHK(c, hipMemsetAsync(d_stat, 0, sz_st + 2 * sz_u, s));
+    rp_strobe_init init;
+    {
+        uint8_t st0[BPGPU_TRANSCRIPT_BYTES];
+        ipp_domain_sep_state(st0, label, label_len, shared_ts, n, &init);
+    }
+    LAUNCH(c, s, "ipp_rlc_front", k_ipp_vs_front, (nb32 + RP_BLOCK - 1) / RP_BLOCK, RP_BLOCK, sh, init, (const uint8_t *)d_proofs, (const uint32_t *)nullptr,
+           (uint32_t *)d_us, (uint32_t *)d_ui, (uint32_t *)d_tab, (uint32_t *)nullptr, (uint32_t *)d_stat);
+    if (shape_bad) {   // n != 2^k: every proof already carries its code and nothing enters R
+        HIPCHK(c, hipMemsetAsync(d_mst, 0, sz_b + sz_o, s));
+    } else {
+        rc = comb_rho_locked(c, s, "ipp_rlc_rho", nb32, d_weights64, IPP_RLC_WEIGHT_DOMAIN, d_rho);
+        if (rc) return rc;
+        ipp_rlc_shape ws;
+        ws.nproofs = nb32, ws.nstride = nstride, ws.n = (uint32_t)n, ws.k = (uint32_t)k, ws.U = (uint32_t)U, ws.proof_len = (uint32_t)proof_len,
+        ws.row0 = fixed ? 2u : 0u, ws.u0 = (uint32_t)head, ws.B = (uint32_t)wB;
+        HIPCHK(c, hipMemsetAsync(d_acc, 0, nrows * 80, s));
+        LAUNCH(c, s, "ipp_rlc_uniq", k_ipp_rlc_uniq, (nb32 + 63) / 64, 64, ws, (const uint32_t *)d_stat, (const uint32_t *)d_rho, (const uint8_t *)d_proofs,
+               (const uint8_t *)d_P, (const uint8_t *)d_Q, (const uint32_t *)d_us, (const uint32_t *)d_ui, (uint32_t *)d_ab, (uint32_t *)d_csc, (uint32_t *)d_cpt);
+        LAUNCH(c, s, "ipp_rlc_weigh", k_ipp_rlc_weigh, (uint32_t)(nt / 64), 64, ws, (const uint32_t *)d_stat, (const uint32_t *)d_ab, (const uint32_t *)d_tab,
+               (const uint8_t *)d_Gf, (const uint8_t *)d_Hf, (unsigned long long *)d_acc);
+        // the combined coefficients of (G_0.., H_0..): the generator-table row behind B_blinding = B = 0, or the head of the list with the
+        // caller's encodings
+        if (fixed) {
+            LAUNCH(c, s, "ipp_rlc_reduce", k_rlc_comb_reduce, (uint32_t)((nrows + 63) / 64), 64, (uint32_t)nrows, (const unsigned long long *)d_acc, (uint32_t *)d_row);
+            rc = msm_shared_dev_locked(c, n / gens_m, gens_m, 1, nbatch * U, d_row, d_csc, d_cpt, d_out, d_mst, nullptr, s);
+        } else {
+            LAUNCH(c, s, "ipp_rlc_reduce", k_ipp_rlc_reduce, (uint32_t)((nrows + 63) / 64), 64, (uint32_t)nrows, (uint32_t)n, (const unsigned long long *)d_acc,
+                   (const uint8_t *)d_G, (const uint8_t *)d_H, (uint32_t *)d_csc, (uint32_t *)d_cpt);
+            const uint32_t nt1 = (uint32_t)nterms;
+            rc = msm_batch_dev_locked(c, 1, &nt1, d_csc, d_cpt, d_out, d_mst, s);
+        }
+        if (rc) return rc;
+    }
+    LAUNCH(c, s, "ipp_rlc_verdict", k_rlc_comb_verdict, (nb32 + 63) / 64, 64, nb32, (const uint32_t *)d_stat, (const uint32_t *)d_out, (const uint8_t *)d_mst,
+           d_verdict, d_batch);
+    HIPCHK(c, hipGetLastError());
+    return BPGPU_OK;
+}
+
+extern "C" int bpgpu_ipp_verify_rlc_dev(bpgpu_ctx *c, size_t n, size_t nbatch, const void *d_proofs, size_t proof_len, const uint8_t *label,
+                                        size_t label_len, const uint8_t *shared_transcript, const void *d_G_factors, const void *d_H_factors,
+                                        const void *d_P, const void *d_Q, const void *d_G, const void *d_H, size_t gens_m, const void *d_weights64,
+                                        void *d_verdict, void *d_batch_out, void *stream) {
+    if (!c || (label_len && !label)) return BPGPU_ERR_INVALID_ARG;
+    if (nbatch == 0) return BPGPU_OK;
+    if (!d_proofs || !d_verdict || !d_P || !d_Q || (n && (!d_G_factors || !d_H_factors)) || (d_G == nullptr) != (d_H == nullptr)) return BPGPU_ERR_INVALID_ARG;
+    if (((uintptr_t)d_proofs | (uintptr_t)d_G_factors | (uintptr_t)d_H_factors | (uintptr_t)d_P | (uintptr_t)d_Q | (uintptr_t)d_G | (uintptr_t)d_H) & 3)
+        return fail(c, BPGPU_ERR_INVALID_ARG, "device buffers must be 4-byte aligned");
+    std::lock_guard<std::mutex> lk(c->mu);
+    HIPCHK(c, hipSetDevice(c->device));
+    hipStream_t s = stream ? (hipStream_t)stream : c->stream;
+    int rc = ctx_enter(c, s);
+    if (rc) return rc;
+    rc = ipp_rlc_dev_locked(c, n, nbatch, d_proofs, proof_len, label, label_len, shared_transcript, d_G_factors, d_H_factors, d_P, d_Q, d_G, d_H, gens_m,
+                            d_weights64, (uint8_t *)d_verdict, (uint8_t *)d_batch_out, s);
+    const int rc2 = ctx_leave(c, s);
+    return rc ? rc : rc2;
+}
+
+extern "C" int bpgpu_ipp_verify_rlc(bpgpu_ctx *c, size_t n, size_t nbatch, const uint8_t *proofs, size_t proof_len, const uint8_t *label,
+                                    size_t label_len, const uint8_t *shared_transcript, const uint8_t *G_factors, const uint8_t *H_factors,
+                                    const uint8_t *P, const uint8_t *Q, const uint8_t *G, const uint8_t *H, size_t gens_m, const uint8_t *weights64,
+                                    uint8_t *verdict, uint8_t *batch_out) {
+    if (!c || (label_len && !label)) return BPGPU_ERR_INVALID_ARG;
+    if (nbatch == 0) {
+        if (batch_out) memset(batch_out, 0, 33);
+        return BPGPU_OK;
+    }
+    if (!proofs || !verdict || !P || !Q || (n && (!G_factors || !H_factors)) || (G == nullptr) != (H == nullptr)) return BPGPU_ERR_INVALID_ARG;
+    if (nbatch > IPP_RLC_MAX_PROOFS) return fail(c, BPGPU_ERR_INVALID_ARG, "batch too large: more than 2^24 proofs in one combination");
+    const bool from_gens = !G && !H;
+    std::lock_guard<std::mutex> lk(c->mu);
+    HIPCHK(c, hipSetDevice(c->device));
+    if (from_gens) {   // (before anything is staged: the fallback gathers 2n encodings of the context's generators)
+        const int rcg = ipp_rlc_gens_ok(c, n, gens_m);
+        if (rcg) return rcg;
+    }
+    hipStream_t s = c->stream;
+    host_call<bpgpu_ctx> io(c, s);
+    const size_t b_f = nbatch * n * 32 + 64, b_pq = nbatch * 32 + 64, b_g = n * 32 + 64;
+    const int r_pr = io.in(nbatch * proof_len + 64), r_gf = io.in(b_f), r_hf = io.in(b_f), r_p = io.in(b_pq), r_q = io.in(b_pq),
+              r_g = io.in(from_gens ? 0 : b_g), r_h = io.in(from_gens ? 0 : b_g), r_w = io.in(weights64 ? nbatch * 64 : 0);
+    const int r_v = io.out(nbatch), r_bo = io.out(64);
+    const int r_gen = io.dev(from_gens ? 2 * n * 32 + 64 : 0);   // the generators' encodings, for the per-proof fallback
+    int rc = io.open();
+    if (rc) return rc;
+    io.put(r_pr, proofs, nbatch * proof_len);
+    if (n) {
+        io.put(r_gf, G_factors, nbatch * n * 32);
+        io.put(r_hf, H_factors, nbatch * n * 32);
+        if (!from_gens) {
+            io.put(r_g, G, n * 32);
+            io.put(r_h, H, n * 32);
+        }
+    }
+    io.put(r_p, P, nbatch * 32);
+    io.put(r_q, Q, nbatch * 32);
+    if (weights64) io.put(r_w, weights64, nbatch * 64);
+    const void *a_g = from_gens ? nullptr : io.d(r_g), *a_h = from_gens ? nullptr : io.d(r_h);
+    rc = io.upload();
+    if (!rc)
+        rc = ipp_rlc_dev_locked(c, n, nbatch, io.d(r_pr), proof_len, label, label_len, shared_transcript, io.d(r_gf), io.d(r_hf), io.d(r_p), io.d(r_q), a_g, a_h,
+                                gens_m, weights64 ? io.d(r_w) : nullptr, (uint8_t *)io.d(r_v), (uint8_t *)io.d(r_bo), s);
+    rc = io.finish(io.download(rc));
+    if (rc) return rc;
+    if (batch_out) memcpy(batch_out, io.h(r_bo), 33);   // (R as computed before any fallback)
+    if ((uint8_t)io.h(r_bo)[0] != 0) {
+        // R is not the identity, or a point of the combined MSM did not decode: the batch again through the per-proof path with the
+        // bases given once (inputs are still on the device; in generator-table mode G(n / gens_m, gens_m), H(..) are gathered first)
+        rc = io.rerun_per_proof(r_v, r_bo, [&]() -> int {
+            const void *f_g = a_g, *f_h = a_h;
+            if (from_gens && n) {
+                uint32_t *d_ids = nullptr;
+                const int rci = gen_ids_for(c, n / gens_m, gens_m, &d_ids);
+                if (rci) return rci;
+                LAUNCH(c, s, "gather32", k_gather32, ((uint32_t)(2 * n) + BP_BLOCK - 1) / BP_BLOCK, BP_BLOCK, (uint32_t)(2 * n), (const uint32_t *)(d_ids + 2),
+                       (const uint32_t *)c->d_gens, (uint32_t *)io.d(r_gen));
+                f_g = io.d(r_gen), f_h = io.d(r_gen) + n * 32;
+            } else if (from_gens) {
+                f_g = f_h = io.d(r_gen);
+            }
+            return ipp_verify_dev_locked(c, n, nbatch, io.d(r_pr), proof_len, label, label_len, shared_transcript, io.d(r_gf), io.d(r_hf), io.d(r_p), io.d(r_q),
+                                         f_g, f_h, 1, io.d(r_v), nullptr, s);
+        });
+        if (rc) return rc;
+    }
+    memcpy(verdict, io.h(r_v), nbatch);
+    return BPGPU_OK;
+}
+
 // ============================================================================
 // R1CS proof creation (r1cs_prover.h): the witness program is a host object beside the circuit, uploaded to a device on
 // first use and kept there until bpgpu_r1cs_witness_destroy

@@ -22,6 +22,7 @@
 #include "r1cs_rlc.h"
 #include "rlc_mix.h"
 #include "linear_rlc.h"
+#include "ipp_rlc.h"
 #include "mpc_party.h"
 #include "mpc_dealer.h"
 
@@ -87,6 +88,10 @@ __global__ void k_r1cs_rlc_weigh(r1_rlc_slice sl, const uint32_t *status, const 
 __global__ void k_r1cs_rlc_sum(uint32_t ncomb, const uint32_t *parts, const uint8_t *part_status, uint32_t *res, uint8_t *rst);
 __global__ void k_lin_rlc_weigh(lin_rlc_shape sh, const uint32_t *status, const uint32_t *rho, const uint32_t *gen_sc, const uint32_t *list_sc, const uint32_t *list_pt, uint32_t *comb_sc, uint32_t *comb_pt, unsigned long long *acc);
 __global__ void k_lin_rlc_reduce(uint32_t nrows, const unsigned long long *acc, const uint8_t *B, const uint8_t *F, const uint8_t *G, uint32_t *out_sc, uint32_t *out_pt);
+// k_ipp_rlc.hip
+__global__ void k_ipp_rlc_uniq(ipp_rlc_shape sh, const uint32_t *status, const uint32_t *rho, const uint8_t *proofs, const uint8_t *P, const uint8_t *Q, const uint32_t *u_sq, const uint32_t *u_inv_sq, uint32_t *ab, uint32_t *comb_sc, uint32_t *comb_pt);
+__global__ void k_ipp_rlc_weigh(ipp_rlc_shape sh, const uint32_t *status, const uint32_t *ab, const uint32_t *tab, const uint8_t *Gf, const uint8_t *Hf, unsigned long long *acc);
+__global__ void k_ipp_rlc_reduce(uint32_t nrows, uint32_t n, const unsigned long long *acc, const uint8_t *G, const uint8_t *H, uint32_t *out_sc, uint32_t *out_pt);
 // k_rlc_comb.hip
 __global__ void k_rlc_comb_rho(uint32_t n, const uint8_t *weights64, rlc_key key, uint32_t dom, uint32_t *rho);
 __global__ void k_rlc_comb_reduce(uint32_t nrows, const unsigned long long *acc, uint32_t *out_sc);

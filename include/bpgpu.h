@@ -382,6 +382,56 @@ int bpgpu_ipp_verify_batch_dev(bpgpu_ctx *ctx, size_t n, size_t nbatch, const vo
                                const void *d_G_factors, const void *d_H_factors, const void *d_P, const void *d_Q,
                                const void *d_G, const void *d_H, int bases_shared,
                                void *d_verdict, void *d_msm_out, void *stream);
+/* Batch-combined InnerProductProof verification (ADDITIONAL entry point, as bpgpu_rangeproof_verify_rlc, bpgpu_r1cs_verify_rlc and
+ * bpgpu_linear_verify_rlc; the reference's InnerProductProof has only create / verify).  proofs, G_factors, H_factors, P, Q and the
+ * transcript are those of bpgpu_ipp_verify_batch_dev; G, H hold n x 32 bytes, shared by the batch (the bases_shared != 0 form, the only
+ * one this call takes); msm_out is replaced by weights64 and batch_out; one n per call.
+ *     R = sum_p rho_p * Check_p ,  rho_p = Scalar::from_bytes_mod_order_wide(weights64[p]),
+ * over the proofs that reach the final check, Check_p being the multiscalar multiplication of bpgpu_ipp_verify_batch for proof p.
+ * G and H are shared, so their 2n coefficients add up in the scalar field and only the 2 lg(n) + 2 points Q, L_j, R_j, P of every
+ * proof cost point arithmetic: ONE multiscalar multiplication per call -- one walk of the window tables plus nbatch (2 lg(n) + 2) points
+ * in generator-table mode, 2n + nbatch (2 lg(n) + 2) points with the caller's bases -- and no buffer of the call grows with nbatch x n
+ * (the per-proof call stages nbatch (2n + 2 lg(n) + 2) terms and decodes G, H once per proof).  R is the identity when every combined
+ * proof verifies; if one does not, R != identity except with probability ~2^-252 over the weights, which must be unpredictable to the
+ * provers (NULL = drawn by the library: uniform 512-bit strings expanded on the device from a per-call key).  A zero weight leaves its
+ * proof unchecked.
+ *   G, H      : n x 32 bytes each.  G = H = NULL: generator-table mode -- the bases are the context's bp_gens.G(n / gens_m, gens_m) and
+ *               bp_gens.H(n / gens_m, gens_m), chained in party order (range_proof/mod.rs:439-442), and their coefficients go through
+ *               the fixed-base window tables instead of per-call point tables.  Exactly one of them NULL: BPGPU_ERR_INVALID_ARG
+ *   gens_m    : generator-table mode only (ignored with explicit bases): >= 1 and a divisor of n, else BPGPU_ERR_INVALID_ARG;
+ *               BPGPU_ERR_NO_GENS when no generators are loaded, n / gens_m > gens_capacity or gens_m > party_capacity
+ *   weights64 : nbatch x 64 bytes, or NULL
+ *   verdict   : ALWAYS what bpgpu_ipp_verify_batch_dev(..., bases_shared = 1, ...) returns for the same inputs and points.  A proof that
+ *               stops in the front end (FormatError: non-canonical a / b; VerificationError: n != 2^lg_n, an identity L_j / R_j) gets
+ *               that code and is left out of R; the others get 0 when R is the identity and every point decoded.  Otherwise the host
+ *               entry point re-verifies the batch through the per-proof path (in generator-table mode on the generators' encodings)
+ *               and returns those verdicts; the asynchronous _dev variant marks them BPGPU_VERDICT_UNDECIDED and leaves that to the
+ *               caller.
+ *   batch_out : optional 33 bytes: [0] = 0 when R is the identity and every point decoded, else 1; [1..33) = compress(R) as computed
+ *               before any fallback, or zeros when a point (a shared G_i / H_i included) did not decode
+ * A proof_len that is no InnerProductProof length gives FormatError for every proof (and batch_out = zeros); nbatch = 0 is BPGPU_OK.
+ * One call takes at most 2^24 proofs and 2^24 proof-specific points (nbatch (2 lg(n) + 2)); larger calls return
+ * BPGPU_ERR_INVALID_ARG.  There are no per-proof transcripts and no transcripts_out: the per-proof call that defines the verdicts has
+ * neither.
+ * The transcript replay stays per proof (k_ipp_vs_front: one lane per proof, serial over lg(n) rounds and one inversion) and sets the
+ * floor of the call, 0.19 ... 0.31 ms; what the combination saves is the per-proof staging, the decodes of G, H per proof and the
+ * per-proof multiscalar multiplications.  Measured on one MI355X (profiles/ipp_rlc_rate.json, n = 64 ... 1 024 against
+ * bpgpu_ipp_verify_batch_dev with bases_shared = 1): faster at every shape measured -- 1.2x ... 1.4x at 64 proofs of n = 64, 1.6x ... 1.7x
+ * at 1 024 and 3.0x ... 3.1x at 4 096; 2.8x ... 8.8x at n = 256; 6.3x ... 16.1x at n = 1 024 -- the caller's bases and the generator tables
+ * within 1 ... 4 % of each other from 1 024 proofs on (11 % at 256 x 4 096) and the tables 11 ... 44 % slower at 64 proofs (the table
+ * walk is a fixed cost).
+ * The call never takes less than 0.74 ms (the one combined MSM alone is 0.5 ... 1.5 ms of kernels).  A failing batch costs this call
+ * plus the per-proof one: 1.06x ... 1.82x the per-proof call alone. */
+int bpgpu_ipp_verify_rlc(bpgpu_ctx *ctx, size_t n, size_t nbatch, const uint8_t *proofs, size_t proof_len,
+                         const uint8_t *label, size_t label_len, const uint8_t *shared_transcript,
+                         const uint8_t *G_factors, const uint8_t *H_factors, const uint8_t *P, const uint8_t *Q,
+                         const uint8_t *G, const uint8_t *H, size_t gens_m, const uint8_t *weights64,
+                         uint8_t *verdict, uint8_t *batch_out);
+int bpgpu_ipp_verify_rlc_dev(bpgpu_ctx *ctx, size_t n, size_t nbatch, const void *d_proofs, size_t proof_len,
+                             const uint8_t *label, size_t label_len, const uint8_t *shared_transcript,
+                             const void *d_G_factors, const void *d_H_factors, const void *d_P, const void *d_Q,
+                             const void *d_G, const void *d_H, size_t gens_m, const void *d_weights64,
+                             void *d_verdict, void *d_batch_out, void *stream);
 
 /* ---- linear proofs (LinearProof, `pub use` src/lib.rs:36) --------------------------------
  * nbatch independent calls of
