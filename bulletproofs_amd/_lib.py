@@ -28,6 +28,7 @@ EXPORTS = [
     "bpgpu_transcript_new", "bpgpu_transcript_append_message", "bpgpu_transcript_challenge_bytes",
     "bpgpu_rangeproof_verify_batch_ts", "bpgpu_rangeproof_verify_batch_ts_dev", "bpgpu_ipp_verify_batch_dev",
     "bpgpu_ipp_create_batch", "bpgpu_rangeproof_prove_batch", "bpgpu_rangeproof_verify_batch_submit", "bpgpu_ctx_collect",
+    "bpgpu_rangeproof_prove_batch_ts", "bpgpu_rangeproof_prove_batch_ts_dev",
     "bpgpu_linear_verify_batch", "bpgpu_linear_verify_batch_dev", "bpgpu_linear_create_batch",
     "bpgpu_linear_verify_rlc", "bpgpu_linear_verify_rlc_dev", "bpgpu_ipp_verify_rlc", "bpgpu_ipp_verify_rlc_dev",
     "bpgpu_rangeproof_audit_shares", "bpgpu_ipp_verification_scalars",
@@ -106,7 +107,9 @@ def lib():
     L.bpgpu_ipp_verify_batch_dev.argtypes = [vp, sz, sz, vp, sz, u8p, sz, u8p, vp, vp, vp, vp, vp, vp, i, vp, vp, vp]
     L.bpgpu_ipp_create_batch.argtypes = [vp, sz, sz, u8p, sz, u8p, u8p, u8p, u8p, u8p, u8p, i, u8p, u8p, u8p, u8p]
     L.bpgpu_rangeproof_prove_batch.argtypes = [vp, sz, sz, sz, C.POINTER(C.c_uint64), u8p, u8p, sz, u8p, u8p, u8p, u8p, u8p]
-    L.bpgpu_rangeproof_verify_batch_submit.argtypes = [vp, sz, sz, sz, u8p, sz, u8p, u8p, sz, u8p, u8p, u8p]
+    L.bpgpu_rangeproof_prove_batch_ts.argtypes = [vp, sz, sz, sz, C.POINTER(C.c_uint64), u8p, u8p, sz, u8p, u8p, u8p, u8p]
+    L.bpgpu_rangeproof_prove_batch_ts_dev.argtypes = [vp, sz, sz, sz, vp, vp, vp, sz, vp, vp, vp, vp, vp]
+    L.bpgpu_rangeproof_verify_batch_submit.argtypes =[vp, sz, sz, sz, u8p, sz, u8p, u8p, sz, u8p, u8p, u8p]
     L.bpgpu_ctx_collect.argtypes = [vp]
     L.bpgpu_linear_verify_batch.argtypes = [vp, sz, sz, u8p, sz, u8p, sz, u8p, u8p, u8p, u8p, u8p, u8p, i, u8p, u8p, u8p]
     L.bpgpu_rangeproof_audit_shares.argtypes = [vp, sz, sz, C.POINTER(C.c_uint32), u8p, u8p, u8p, u8p, i, u8p, u8p]
@@ -541,6 +544,29 @@ class Context:
         self._chk(self._L.bpgpu_rangeproof_prove_batch(self.h, n, m, nb, va, blindings, label, len(label), transcript, rng, proofs, coms, tso))
         out = (proofs.raw[:pl * nb], coms.raw[:32 * m * nb])
         return out + (tso.raw[:TRANSCRIPT_BYTES * nb],) if want_transcripts else out
+
+    def rangeproof_prove_batch_ts(self, n, m, values, blindings, transcripts, rng32=None, want_transcripts=False):
+        """The same proofs on the callers' own transcripts, the random scalars drawn on the device (bpgpu_rangeproof_prove_batch_ts).
+        transcripts: one 208-byte state (before rangeproof_domain_sep) shared by every proof, or one per proof; rng32: 32 bytes per
+        proof, the seed of its ChaChaRng (None: the library draws them).  Returns (proofs bytes, commitments bytes[, final states])."""
+        nb = len(values) // m
+        assert len(values) == nb * m and len(blindings) == 32 * nb * m
+        assert transcripts is None or len(transcripts) in (TRANSCRIPT_BYTES, TRANSCRIPT_BYTES * nb)
+        assert rng32 is None or len(rng32) == 32 * nb
+        stride = TRANSCRIPT_BYTES if (transcripts is not None and nb != 1 and len(transcripts) == TRANSCRIPT_BYTES * nb) else 0
+        pl = 32 * (9 + 2 * ((n * m).bit_length() - 1))
+        va = (C.c_uint64 * max(len(values), 1))(*values)
+        proofs, coms = C.create_string_buffer(pl * max(nb, 1)), C.create_string_buffer(32 * m * max(nb, 1))
+        tso = C.create_string_buffer(TRANSCRIPT_BYTES * max(nb, 1)) if want_transcripts else None
+        self._chk(self._L.bpgpu_rangeproof_prove_batch_ts(self.h, n, m, nb, va, blindings, transcripts, stride, rng32, proofs, coms, tso))
+        out = (proofs.raw[:pl * nb], coms.raw[:32 * m * nb])
+        return out + (tso.raw[:TRANSCRIPT_BYTES * nb],) if want_transcripts else out
+
+    def rangeproof_prove_batch_ts_dev(self, n, m, nbatch, d_values, d_blindings, d_transcripts, transcript_stride, d_rng32, d_proofs, d_commitments,
+                                      d_transcripts_out=None, stream=None):
+        """bpgpu_rangeproof_prove_batch_ts_dev: every buffer a device address (int), asynchronous on `stream`."""
+        self._chk(self._L.bpgpu_rangeproof_prove_batch_ts_dev(self.h, n, m, nbatch, d_values, d_blindings, d_transcripts, transcript_stride, d_rng32, d_proofs,
+                                                              d_commitments, d_transcripts_out, stream))
 
     # ---- the multi-party aggregation protocol (bpgpu_mpc_*; the typestate classes of range_proof_mpc.py are batches of one) ----
     def mpc_state_bytes(self, n):

@@ -178,22 +178,55 @@ class RangeProof:
         return self._raw
 
     @staticmethod
-    def prove_multiple_with_rng(bp_gens, pc_gens, transcript, values, blindings, n, rng_bytes=None):
+    def prove_multiple_with_rng(bp_gens, pc_gens, transcript, values, blindings, n, rng_bytes=None, rng_seed32=None):
         """RangeProof::prove_multiple_with_rng (mod.rs:234-288) on the GPU (variable time: see include/bpgpu.h).  values: ints,
         blindings: 32-byte scalars; rng_bytes: the bytes the rng would hand Scalar::random, in the reference's draw order
-        (None = OS CSPRNG).  Returns (RangeProof, [commitment bytes]); `transcript` is left advanced."""
+        (None = OS CSPRNG).  rng_seed32 instead: the rng is ChaChaRng::from_seed(rng_seed32), its scalars drawn on the device
+        (bpgpu_rangeproof_prove_batch_ts).  Returns (RangeProof, [commitment bytes]); `transcript` is left advanced."""
         bp_gens._check_pedersen(pc_gens)
         m = len(values)
-        proofs, coms, ts = bp_gens.ctx.rangeproof_prove_batch(n, m, list(values), b"".join(blindings), transcript=transcript.state, rng=rng_bytes,
-                                                            want_transcripts=True)
+        if rng_seed32 is not None:
+            if rng_bytes is not None or len(rng_seed32) != 32:
+                raise ValueError("rng_seed32: 32 bytes, and not together with rng_bytes")
+            proofs, coms, ts = bp_gens.ctx.rangeproof_prove_batch_ts(n, m, list(values), b"".join(blindings), transcript.state, bytes(rng_seed32),
+                                                                   want_transcripts=True)
+        else:
+            proofs, coms, ts = bp_gens.ctx.rangeproof_prove_batch(n, m, list(values), b"".join(blindings), transcript=transcript.state, rng=rng_bytes,
+                                                                want_transcripts=True)
         transcript.state = ts
         transcript.fresh_label = None
         return RangeProof(proofs), [coms[32 * j:32 * j + 32] for j in range(m)]
 
     @staticmethod
-    def prove_single_with_rng(bp_gens, pc_gens, transcript, v, v_blinding, n, rng_bytes=None):
-        proof, coms = RangeProof.prove_multiple_with_rng(bp_gens, pc_gens, transcript, [v], [v_blinding], n, rng_bytes)
+    def prove_single_with_rng(bp_gens, pc_gens, transcript, v, v_blinding, n, rng_bytes=None, rng_seed32=None):
+        proof, coms = RangeProof.prove_multiple_with_rng(bp_gens, pc_gens, transcript, [v], [v_blinding], n, rng_bytes, rng_seed32)
         return proof, coms[0]
+
+    @staticmethod
+    def prove_batch(bp_gens, pc_gens, transcript, values, blindings, n, rng32=None):
+        """len(values) proofs in ONE GPU pass (bpgpu_rangeproof_prove_batch_ts; no counterpart in the crate): values[i] / blindings[i]
+        are the m values / 32-byte blindings of proof i.  `transcript`: one bound Transcript, the start state of every proof (not
+        advanced, as in verify_batch), or a list of transcripts, one per proof, each left advanced as prove_multiple_with_rng
+        leaves it.  rng32: 32 bytes per proof, proof i's rng being ChaChaRng::from_seed(rng32[32 i:32 i + 32]) (None: the library
+        draws the seeds).  Returns [(RangeProof, [commitment bytes])]."""
+        if not values:
+            return []
+        bp_gens._check_pedersen(pc_gens)
+        nb, m = len(values), len(values[0])
+        if any(len(v) != m for v in values) or len(blindings) != nb or any(len(b) != m for b in blindings):
+            raise ValueError("prove_batch: m values and m blindings per proof")
+        per_proof = isinstance(transcript, (list, tuple))
+        if per_proof and len(transcript) != nb:
+            raise ValueError("prove_batch: one transcript per proof")
+        states = b"".join(t.state for t in transcript) if per_proof else transcript.state
+        proofs, coms, ts = bp_gens.ctx.rangeproof_prove_batch_ts(n, m, [x for v in values for x in v], b"".join(x for b in blindings for x in b), states,
+                                                               rng32, want_transcripts=True)
+        if per_proof:
+            for i, t in enumerate(transcript):
+                t.state = ts[208 * i:208 * i + 208]
+                t.fresh_label = None
+        pl = len(proofs) // nb
+        return [(RangeProof(proofs[pl * i:pl * i + pl]), [coms[32 * (m * i + j):32 * (m * i + j) + 32] for j in range(m)]) for i in range(nb)]
 
     @staticmethod
     def prove_multiple(bp_gens, pc_gens, transcript, values, blindings, n):

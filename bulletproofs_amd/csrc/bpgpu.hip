@@ -3455,28 +3455,23 @@ static int rpp_reserve(bpgpu_ctx *c, size_t need) {
     c->rpp_cap = need + need / 8;
     return BPGPU_OK;
 }
-extern "C" int bpgpu_rangeproof_prove_batch(bpgpu_ctx *c, size_t n, size_t m, size_t nbatch, const uint64_t *values, const uint8_t *blindings,
-                                            const uint8_t *label, size_t label_len, const uint8_t *shared_transcript, const uint8_t *rng,
-                                            uint8_t *proofs_out, uint8_t *commitments_out, uint8_t *transcripts_out) {
-    if (!c || (label_len && !label)) return BPGPU_ERR_INVALID_ARG;
-    if (nbatch == 0) return BPGPU_OK;
-    if (!values || !blindings || !proofs_out || !commitments_out) return BPGPU_ERR_INVALID_ARG;
-    // the parameter checks of prove_multiple_with_rng / Party::new / Dealer::new (mod.rs:244-246, party.rs:41-53, dealer.rs:34-60)
+// the parameter checks of prove_multiple_with_rng / Party::new / Dealer::new (mod.rs:244-246, party.rs:41-53, dealer.rs:34-60) ...
+static int rpp_check_nm(bpgpu_ctx *c, size_t n, size_t m) {
     if (!(n == 8 || n == 16 || n == 32 || n == 64)) return fail(c, BPGPU_ERR_INVALID_ARG, "InvalidBitsize: n must be 8, 16, 32 or 64");
     if (m == 0 || (m & (m - 1))) return fail(c, BPGPU_ERR_INVALID_ARG, "InvalidAggregation: m must be a power of two");
-    if (shared_transcript && !ts_state_ok(shared_transcript)) return fail(c, BPGPU_ERR_INVALID_ARG, "malformed transcript state");
-    std::lock_guard<std::mutex> lk(c->mu);
-    HIPCHK(c, hipSetDevice(c->device));
+    return BPGPU_OK;
+}
+// ... and, with the context locked, those against the loaded generators, the values (host memory; nullptr: not checkable) and the sizes
+static int rpp_shape_locked(bpgpu_ctx *c, size_t n, size_t m, size_t nbatch, const uint64_t *values, rpp_shape &sh) {
     if (!c->d_table) return fail(c, BPGPU_ERR_NO_GENS, "generators not loaded");
     if (c->gens_capacity < n || c->party_capacity < m) return fail(c, BPGPU_ERR_NO_GENS, "InvalidGeneratorsLength: generators too small for n=%zu m=%zu", n, m);
-    if (n < 64)
+    if (n < 64 && values)
         for (size_t i = 0; i < nbatch * m; i++)
             if (values[i] >> n) return fail(c, BPGPU_ERR_INVALID_ARG, "value %zu does not fit %zu bits", i, n);   // (the reference would prove a false statement's bits silently; refuse)
     const size_t nm = n * m;
     size_t k = 0;
     while (((size_t)1 << k) < nm) k++;
     if (k > BP_RP_MAX_K) return fail(c, BPGPU_ERR_INVALID_ARG, "n*m > 2^%d not supported", BP_RP_MAX_K);
-    rpp_shape sh;
     sh.n = (uint32_t)n;
     sh.m = (uint32_t)m;
     sh.nm = (uint32_t)nm;
@@ -3485,17 +3480,43 @@ extern "C" int bpgpu_rangeproof_prove_batch(bpgpu_ctx *c, size_t n, size_t m, si
     sh.proof_len = (uint32_t)(32 * (9 + 2 * k));
     sh.n_gen_terms = (uint32_t)(2 * nm + 2);
     sh.rng_per_proof = (uint32_t)(64 * (m * (2 * n + 2) + 2 * m));
-    const size_t nmsm1 = nbatch * (2 + m), TS = BPGPU_TRANSCRIPT_BYTES, proof_len = sh.proof_len;
+    const size_t nmsm1 = nbatch * (2 + m);
     const uint64_t gs_bytes = (uint64_t)nmsm1 * sh.n_gen_terms * 32;
     if (gs_bytes > (4ull << 30) || (uint64_t)nmsm1 * sh.n_gen_terms > 0x7fffffffull || (uint64_t)nbatch * nm > 0x7fffffffull / 64)
         return fail(c, BPGPU_ERR_INVALID_ARG, "batch too large for this shape");
+    return BPGPU_OK;
+}
+// where the chain's draws and start transcripts come from (rpp_chain)
+struct rpp_source {
+    const uint8_t *rng = nullptr;       // 64 bytes per draw, or
+    const uint8_t *seeds = nullptr;     // 32 bytes per proof
+    const uint32_t *ts_in = nullptr;    // the callers' states before rangeproof_domain_sep (nullptr: d_ts holds separated states)
+    uint32_t ts_in_stride = 0;          // words between them: 0 (one for all) or BP_TS_WORDS
+};
+static int rpp_chain(bpgpu_ctx *c, hipStream_t s, const rpp_shape &sh, const uint64_t *d_values, const uint8_t *d_bl, rpp_source src, uint32_t *d_ts,
+                     uint8_t *d_proofs, uint8_t *d_coms, const char *stage_seeds);
+
+extern "C" int bpgpu_rangeproof_prove_batch(bpgpu_ctx *c, size_t n, size_t m, size_t nbatch, const uint64_t *values, const uint8_t *blindings,
+                                            const uint8_t *label, size_t label_len, const uint8_t *shared_transcript, const uint8_t *rng,
+                                            uint8_t *proofs_out, uint8_t *commitments_out, uint8_t *transcripts_out) {
+    if (!c || (label_len && !label)) return BPGPU_ERR_INVALID_ARG;
+    if (nbatch == 0) return BPGPU_OK;
+    if (!values || !blindings || !proofs_out || !commitments_out) return BPGPU_ERR_INVALID_ARG;
+    int rc = rpp_check_nm(c, n, m);
+    if (rc) return rc;
+    if (shared_transcript && !ts_state_ok(shared_transcript)) return fail(c, BPGPU_ERR_INVALID_ARG, "malformed transcript state");
+    std::lock_guard<std::mutex> lk(c->mu);
+    HIPCHK(c, hipSetDevice(c->device));
+    rpp_shape sh;
+    if ((rc = rpp_shape_locked(c, n, m, nbatch, values, sh))) return rc;
+    const size_t TS = BPGPU_TRANSCRIPT_BYTES, proof_len = sh.proof_len;
     hipStream_t s = c->stream;
     // ---- inputs through pinned staging into the persistent IO buffer
     host_call<bpgpu_ctx> io(c, s);
     const int r_val = io.in(nbatch * m * 8), r_bl = io.in(nbatch * m * 32), r_rng = io.in(nbatch * sh.rng_per_proof), r_ts = io.in(nbatch * TS);
     const int r_pr = io.out(nbatch * proof_len), r_cm = io.out(nbatch * m * 32), r_to = io.out(nbatch * TS);
     io.secrets(io.off[r_ts]);   // values, blindings, every random scalar
-    int rc = io.open();
+    rc = io.open();
     if (rc) return io.finish(rc);
     io.put(r_val, values, nbatch * m * 8);
     io.put(r_bl, blindings, nbatch * m * 32);
@@ -3524,11 +3545,35 @@ extern "C" int bpgpu_rangeproof_prove_batch(bpgpu_ctx *c, size_t n, size_t m, si
     uint32_t *d_ts = (uint32_t *)io.d(r_ts);
     uint8_t *d_proofs = (uint8_t *)io.d(r_pr), *d_coms = (uint8_t *)io.d(r_cm);
     if ((rc = io.upload())) return io.finish(rc);
+    rpp_source src;
+    src.rng = d_rng;
+    rc = rpp_chain(c, s, sh, d_values, d_bl, src, d_ts, d_proofs, d_coms, nullptr);
+    if (!rc && (hipMemcpyAsync(io.d(r_to), d_ts, nbatch * TS, hipMemcpyDeviceToDevice, s) != hipSuccess || io.download(0)))
+        rc = fail(c, BPGPU_ERR_HIP, "D2H copy failed");
+    rc = io.finish(rc);
+    if (rc) return rc;
+    memcpy(proofs_out, io.h(r_pr), nbatch * proof_len);
+    memcpy(commitments_out, io.h(r_cm), nbatch * m * 32);
+    if (transcripts_out) memcpy(transcripts_out, io.h(r_to), nbatch * TS);
+    return BPGPU_OK;
+}
+
+// The prover's launch chain over device-resident inputs, enqueued on s.  The draws come from src.rng (64 bytes each, transcripts in
+// d_ts already separated) or from src.seeds (32 bytes per proof, every draw computed by the lane that consumes it; the transcripts
+// start at src.ts_in, before rangeproof_domain_sep).  d_ts: the working states, left as the prover leaves them (nullptr: kept in the
+// working set).  stage_seeds: seeds in pinned host memory, which the chain copies into its working set and reads from there.
+static int rpp_chain(bpgpu_ctx *c, hipStream_t s, const rpp_shape &sh, const uint64_t *d_values, const uint8_t *d_bl, rpp_source src, uint32_t *d_ts,
+                     uint8_t *d_proofs, uint8_t *d_coms, const char *stage_seeds) {
+    const size_t n = sh.n, m = sh.m, nm = sh.nm, k = sh.k, nbatch = sh.nproofs, proof_len = sh.proof_len, nmsm1 = nbatch * (2 + m);
+    const uint64_t gs_bytes = (uint64_t)nmsm1 * sh.n_gen_terms * 32;
+    const bool seeded = src.seeds || stage_seeds;
+    int rc;
     // ---- working set
     const size_t w_gs = align_up(gs_bytes), w_mo = align_up(nmsm1 * 32), w_ms = align_up(nmsm1 + 64), w_f = align_up(RPP_FIXED * nbatch * 32),
-                 w_p = align_up(RPP_PARTY_FIELDS * nbatch * m * 32), w_v = align_up(nbatch * nm * 32), w_q = align_up(nbatch * 32), w_gen = align_up(nm * 32);
-    const size_t need = w_gs + w_mo + w_ms + w_f + w_p + 10 * w_v + w_q + 2 * w_gen;
-    if ((rc = rpp_reserve(c, need))) return io.finish(rc);
+                 w_p = align_up(RPP_PARTY_FIELDS * nbatch * m * 32), w_v = align_up(nbatch * nm * 32), w_q = align_up(nbatch * 32), w_gen = align_up(nm * 32),
+                 w_seed = stage_seeds ? align_up(nbatch * 32) : 0, w_ts = d_ts ? 0 : align_up(nbatch * BPGPU_TRANSCRIPT_BYTES);
+    const size_t need = w_gs + w_mo + w_ms + w_f + w_p + 10 * w_v + w_q + 2 * w_gen + w_seed + w_ts;
+    if ((rc = rpp_reserve(c, need))) return rc;
     char *wb = c->rpp_buf;
     uint32_t *gsc = (uint32_t *)wb, *mo = (uint32_t *)(wb + w_gs);
     uint8_t *mst = (uint8_t *)mo + w_mo;
@@ -3538,22 +3583,42 @@ extern "C" int bpgpu_rangeproof_prove_batch(bpgpu_ctx *c, size_t n, size_t m, si
              *r1 = (uint32_t *)(vv + 5 * w_v), *avec = (uint32_t *)(vv + 6 * w_v), *bvec = (uint32_t *)(vv + 7 * w_v), *Gf = (uint32_t *)(vv + 8 * w_v),
              *Hf = (uint32_t *)(vv + 9 * w_v);
     uint32_t *qenc = (uint32_t *)(vv + 10 * w_v), *Genc = (uint32_t *)((char *)qenc + w_q), *Henc = (uint32_t *)((char *)Genc + w_gen);
+    char *seed_slot = (char *)Henc + w_gen;
+    if (!d_ts) d_ts = (uint32_t *)(seed_slot + w_seed);
     const uint32_t nb32 = (uint32_t)nbatch, nbits = (uint32_t)(nbatch * nm), n_b = (nb32 + BP_BLOCK - 1) / BP_BLOCK;
     do {
+        if (stage_seeds) {   // library-drawn seeds of a device-pointer call: pinned staging -> the working set (cleared with it)
+            // and wait for that one copy: the caller clears the staged seeds when this returns
+            if (hipMemcpyAsync(seed_slot, stage_seeds, nbatch * 32, hipMemcpyHostToDevice, s) != hipSuccess || c->io.pin_mark(s) ||
+                hipEventSynchronize(c->io.pin_ev) != hipSuccess) {
+                rc = fail(c, BPGPU_ERR_HIP, "staging the seeds failed");
+                break;
+            }
+            c->io.pin_pending = false;
+            src.seeds = (const uint8_t *)seed_slot;
+        }
         uint32_t *d_ids = nullptr;
         rc = gen_ids_for(c, n, m, &d_ids);
         if (rc) break;
         LAUNCH(c, s, "gather32", k_gather32, ((uint32_t)(2 * nm) + BP_BLOCK - 1) / BP_BLOCK, BP_BLOCK, (uint32_t)(2 * nm), (const uint32_t *)(d_ids + 2),
                (const uint32_t *)c->d_gens, Genc);   // G(n, m) then H(n, m): Henc = Genc + nm records when w_gen is exact
-        if (hipMemsetAsync(gsc, 0, gs_bytes, s) != hipSuccess || hipMemsetAsync(d_proofs, 0, io.width(r_pr), s) != hipSuccess) {
+        if (hipMemsetAsync(gsc, 0, gs_bytes, s) != hipSuccess || hipMemsetAsync(d_proofs, 0, nbatch * proof_len, s) != hipSuccess) {
             rc = fail(c, BPGPU_ERR_HIP, "memset failed");
             break;
         }
         // (1) V_j, A, S
-        LAUNCH(c, s, "rpp_commit1", k_rpp_commit1, n_b + (nbits + BP_BLOCK - 1) / BP_BLOCK, BP_BLOCK, n_b, nbits, sh, d_values, d_bl, d_rng, gsc, party, sL, sR);
+        if (seeded)
+            LAUNCH(c, s, "rpp_commit1_seed", k_rpp_commit1_seed, n_b + (nbits + BP_BLOCK - 1) / BP_BLOCK, BP_BLOCK, n_b, nbits, sh, d_values, d_bl, src.seeds, gsc, party,
+                   sL, sR);
+        else
+            LAUNCH(c, s, "rpp_commit1", k_rpp_commit1, n_b + (nbits + BP_BLOCK - 1) / BP_BLOCK, BP_BLOCK, n_b, nbits, sh, d_values, d_bl, src.rng, gsc, party, sL, sR);
         rc = msm_shared_dev_locked(c, n, m, nmsm1, 0, gsc, nullptr, nullptr, mo, mst, nullptr, s, false, c->prover_ct);
         if (rc) break;
-        LAUNCH(c, s, "rpp_chal1", k_rpp_chal1, (nb32 + RP_BLOCK - 1) / RP_BLOCK, RP_BLOCK, sh, (const uint32_t *)mo, d_ts, fields, d_proofs, d_coms);
+        if (src.ts_in)
+            LAUNCH(c, s, "rpp_chal1_sep", k_rpp_chal1_sep, (nb32 + RP_BLOCK - 1) / RP_BLOCK, RP_BLOCK, sh, (const uint32_t *)mo, src.ts_in, src.ts_in_stride, d_ts, fields,
+                   d_proofs, d_coms);
+        else
+            LAUNCH(c, s, "rpp_chal1", k_rpp_chal1, (nb32 + RP_BLOCK - 1) / RP_BLOCK, RP_BLOCK, sh, (const uint32_t *)mo, d_ts, fields, d_proofs, d_coms);
         // (2) polynomials, T_1, T_2
         const uint32_t npar = (uint32_t)(nbatch * m);
         LAUNCH(c, s, "rpp_poly", k_rpp_poly, (npar + BP_BLOCK - 1) / BP_BLOCK, BP_BLOCK, npar, sh, d_values, (const uint32_t *)fields, (const uint32_t *)sL,
@@ -3562,7 +3627,8 @@ extern "C" int bpgpu_rangeproof_prove_batch(bpgpu_ctx *c, size_t n, size_t m, si
             rc = fail(c, BPGPU_ERR_HIP, "memset failed");
             break;
         }
-        LAUNCH(c, s, "rpp_tcommit", k_rpp_tcommit, n_b, BP_BLOCK, sh, d_rng, gsc, party);
+        if (seeded) LAUNCH(c, s, "rpp_tcommit_seed", k_rpp_tcommit_seed, n_b, BP_BLOCK, sh, src.seeds, gsc, party);
+        else LAUNCH(c, s, "rpp_tcommit", k_rpp_tcommit, n_b, BP_BLOCK, sh, src.rng, gsc, party);
         rc = msm_shared_dev_locked(c, n, m, 2 * nbatch, 0, gsc, nullptr, nullptr, mo, mst, nullptr, s, false, c->prover_ct);
         if (rc) break;
         // (3) x, t_x ..., w; Q = w B; the inner-product argument's inputs
@@ -3583,14 +3649,105 @@ extern "C" int bpgpu_rangeproof_prove_batch(bpgpu_ctx *c, size_t n, size_t m, si
         fx.gen_scalars = gsc;
         rc = ippc_core(c, s, nm, k, nbatch, avec, bvec, Gf, Hf, qenc, Genc, Genc + 8 * nm, 1, d_ts, d_proofs + 224, proof_len, nullptr, &fx);
     } while (0);
-    if (!rc && (hipMemcpyAsync(io.d(r_to), d_ts, nbatch * TS, hipMemcpyDeviceToDevice, s) != hipSuccess || io.download(0)))
-        rc = fail(c, BPGPU_ERR_HIP, "D2H copy failed");
-    rc = io.finish(rc);
+    return rc;
+}
+
+// ---- the callers' own transcripts, one seed per proof (rp_prover.h: rpp_from_seed, rpp_chal1_lane<true>) ----
+static int rpp_ts_args(bpgpu_ctx *c, size_t n, size_t m, size_t transcript_stride) {
+    int rc = rpp_check_nm(c, n, m);
+    if (rc) return rc;
+    if (transcript_stride != 0 && transcript_stride != BPGPU_TRANSCRIPT_BYTES)
+        return fail(c, BPGPU_ERR_INVALID_ARG, "transcript_stride must be 0 or %d", BPGPU_TRANSCRIPT_BYTES);
+    return BPGPU_OK;
+}
+
+extern "C" int bpgpu_rangeproof_prove_batch_ts(bpgpu_ctx *c, size_t n, size_t m, size_t nbatch, const uint64_t *values, const uint8_t *blindings,
+                                               const uint8_t *transcripts, size_t transcript_stride, const uint8_t *rng32, uint8_t *proofs_out,
+                                               uint8_t *commitments_out, uint8_t *transcripts_out) {
+    if (!c) return BPGPU_ERR_INVALID_ARG;
+    if (nbatch == 0) return BPGPU_OK;
+    if (!values || !blindings || !proofs_out || !commitments_out) return BPGPU_ERR_INVALID_ARG;
+    if (!transcripts) return fail(c, BPGPU_ERR_INVALID_ARG, "transcripts missing");
+    int rc = rpp_ts_args(c, n, m, transcript_stride);
+    if (rc) return rc;
+    const size_t TS = BPGPU_TRANSCRIPT_BYTES, nstates = transcript_stride ? nbatch : 1;
+    for (size_t p = 0; p < nstates; p++)
+        if (!ts_state_ok(transcripts + p * TS)) return fail(c, BPGPU_ERR_INVALID_ARG, "malformed transcript state %zu", p);
+    std::lock_guard<std::mutex> lk(c->mu);
+    HIPCHK(c, hipSetDevice(c->device));
+    rpp_shape sh;
+    if ((rc = rpp_shape_locked(c, n, m, nbatch, values, sh))) return rc;
+    const size_t proof_len = sh.proof_len;
+    hipStream_t s = c->stream;
+    // ---- inputs through pinned staging into the persistent IO buffer: 32 bytes of randomness per proof, no draw buffer
+    host_call<bpgpu_ctx> io(c, s);
+    const int r_val = io.in(nbatch * m * 8), r_bl = io.in(nbatch * m * 32), r_seed = io.in(nbatch * 32), r_ts = io.in(nstates * TS);
+    const int r_pr = io.out(nbatch * proof_len), r_cm = io.out(nbatch * m * 32), r_to = io.out(nbatch * TS);
+    io.secrets(io.off[r_ts]);   // values, blindings, the seeds
+    rc = io.open();
+    if (rc) return io.finish(rc);
+    io.put(r_val, values, nbatch * m * 8);
+    io.put(r_bl, blindings, nbatch * m * 32);
+    if (rng32) io.put(r_seed, rng32, nbatch * 32);
+    else if ((rc = os_random(c, io.h(r_seed), nbatch * 32)) != 0) return io.finish(rc);
+    io.put(r_ts, transcripts, nstates * TS);
+    if ((rc = io.upload())) return io.finish(rc);
+    rpp_source src;
+    src.seeds = (const uint8_t *)io.d(r_seed);
+    src.ts_in = (const uint32_t *)io.d(r_ts);
+    src.ts_in_stride = transcript_stride ? BP_TS_WORDS : 0;
+    rc = rpp_chain(c, s, sh, (const uint64_t *)io.d(r_val), (const uint8_t *)io.d(r_bl), src, (uint32_t *)io.d(r_to), (uint8_t *)io.d(r_pr), (uint8_t *)io.d(r_cm),
+                   nullptr);
+    rc = io.finish(io.download(rc));
     if (rc) return rc;
     memcpy(proofs_out, io.h(r_pr), nbatch * proof_len);
     memcpy(commitments_out, io.h(r_cm), nbatch * m * 32);
     if (transcripts_out) memcpy(transcripts_out, io.h(r_to), nbatch * TS);
     return BPGPU_OK;
+}
+
+extern "C" int bpgpu_rangeproof_prove_batch_ts_dev(bpgpu_ctx *c, size_t n, size_t m, size_t nbatch, const void *d_values, const void *d_blindings,
+                                                   const void *d_transcripts, size_t transcript_stride, const void *d_rng32, void *d_proofs_out,
+                                                   void *d_commitments_out, void *d_transcripts_out, void *stream) {
+    if (!c) return BPGPU_ERR_INVALID_ARG;
+    if (nbatch == 0) return BPGPU_OK;
+    if (!d_values || !d_blindings || !d_proofs_out || !d_commitments_out) return BPGPU_ERR_INVALID_ARG;
+    if (!d_transcripts) return fail(c, BPGPU_ERR_INVALID_ARG, "transcripts missing");
+    int rc = rpp_ts_args(c, n, m, transcript_stride);
+    if (rc) return rc;
+    if (((uintptr_t)d_values & 7) || (((uintptr_t)d_blindings | (uintptr_t)d_transcripts | (uintptr_t)d_rng32 | (uintptr_t)d_proofs_out | (uintptr_t)d_commitments_out |
+                                       (uintptr_t)d_transcripts_out) & 3))
+        return fail(c, BPGPU_ERR_INVALID_ARG, "device buffers must be 4-byte aligned (values: 8-byte)");
+    std::lock_guard<std::mutex> lk(c->mu);
+    HIPCHK(c, hipSetDevice(c->device));
+    rpp_shape sh;
+    if ((rc = rpp_shape_locked(c, n, m, nbatch, nullptr, sh))) return rc;
+    hipStream_t s = stream ? (hipStream_t)stream : c->stream;
+    if ((rc = ctx_enter(c, s))) return rc;
+    char *h_seeds = nullptr;
+    if (!d_rng32) {   // the library's own seeds: drawn into pinned staging, copied by the chain into its working set
+        rc = c->io.pin_alloc(nbatch * 32, &h_seeds);
+        if (!rc) rc = os_random(c, h_seeds, nbatch * 32);
+    }
+    rpp_source src;
+    src.seeds = (const uint8_t *)d_rng32;
+    src.ts_in = (const uint32_t *)d_transcripts;
+    src.ts_in_stride = transcript_stride ? BP_TS_WORDS : 0;
+    if (!rc) rc = rpp_chain(c, s, sh, (const uint64_t *)d_values, (const uint8_t *)d_blindings, src, (uint32_t *)d_transcripts_out, (uint8_t *)d_proofs_out,
+                            (uint8_t *)d_commitments_out, h_seeds);
+    // the exit of a prover (host_call::finish) without its wait: working sets and arena cleared on the stream behind the last kernel
+    dev_span b[3];
+    secret_spans(c, b);
+    bool ok = true;
+    for (const dev_span &x : b)
+        if (x.p) ok = hipMemsetAsync(x.p, 0, x.bytes, s) == hipSuccess && ok;
+    const int rc2 = ctx_leave(c, s);
+    if (h_seeds) {   // (the chain has waited until the seeds had left the staging block: the one wait of this form)
+        memset(h_seeds, 0, nbatch * 32);
+        c->io.last_secret_bytes = (h_seeds == c->io.pin) ? nbatch * 32 : 0;
+    }
+    if (!rc && !ok) rc = fail(c, BPGPU_ERR_HIP, "clearing the prover's working set failed");
+    return rc ? rc : rc2;
 }
 
 // ============================================================================

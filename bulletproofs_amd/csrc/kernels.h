@@ -126,6 +126,9 @@ __global__ void k_rpp_poly(uint32_t nthreads, rpp_shape sh, const uint64_t *valu
 __global__ void k_rpp_tcommit(rpp_shape sh, const uint8_t *rng, uint32_t *gen_scalars, uint32_t *party);
 __global__ void k_rpp_chal2(rpp_shape sh, const uint32_t *msm_out, uint32_t *ts, uint32_t *fields, const uint32_t *party, uint32_t *gen_scalars, uint8_t *proofs);
 __global__ void k_rpp_vectors(uint32_t nthreads, rpp_shape sh, const uint32_t *fields, const uint32_t *l0, const uint32_t *l1, const uint32_t *r0, const uint32_t *r1, uint32_t *a_vec, uint32_t *b_vec, uint32_t *Gf, uint32_t *Hf);
+__global__ void k_rpp_commit1_seed(uint32_t n_b, uint32_t nthreads, rpp_shape sh, const uint64_t *values, const uint8_t *blindings, const uint8_t *seeds, uint32_t *gen_scalars, uint32_t *party, uint32_t *sL, uint32_t *sR);
+__global__ void k_rpp_tcommit_seed(rpp_shape sh, const uint8_t *seeds, uint32_t *gen_scalars, uint32_t *party);
+__global__ void k_rpp_chal1_sep(rpp_shape sh, const uint32_t *msm_out, const uint32_t *ts_in, uint32_t ts_in_stride, uint32_t *ts, uint32_t *fields, uint8_t *proofs, uint8_t *commitments);
 __global__ void k_gather32(uint32_t count, const uint32_t *ids, const uint32_t *src, uint32_t *dst);
 // k_ippc.hip
 __global__ void k_ippc_init(uint32_t nthreads, ippc_shape sh, const uint8_t *a_in, const uint8_t *b_in, const uint8_t *Gf, const uint8_t *Hf, uint32_t *a, uint32_t *b, uint32_t *wG, uint32_t *wH, uint32_t *status);

@@ -19,6 +19,7 @@
 // instruction stream, byte-identical results.
 #ifndef BPGPU_RP_PROVER_H
 #define BPGPU_RP_PROVER_H
+#include "chacha20.h"
 #include "ipp_prover.h"
 
 namespace bp {
@@ -41,15 +42,33 @@ BP_HD void rpp_wide(sc &r, const uint8_t *p64) {
     load_words8(w + 8, p64 + 32);
     sc_from_wide(r, w);
 }
-BP_HD const uint8_t *rpp_rng_party(const rpp_shape &sh, const uint8_t *rng, uint32_t p, uint32_t j) {
-    return rng + (uint64_t)p * sh.rng_per_proof + (uint64_t)j * 64 * (2 * sh.n + 2);
-}
 BP_HD uint32_t *rpp_row(uint32_t *gen_scalars, const rpp_shape &sh, uint32_t msm, uint32_t slot) {
     return gen_scalars + ((uint64_t)msm * sh.n_gen_terms + slot) * 8;
 }
 
+// Scalar::from_bytes_mod_order_wide of keystream block d of ChaCha20 under `seed32` (64-bit block counter d, stream id 0): what
+// rand_chacha's ChaChaRng::from_seed(seed32) hands to the d-th Scalar::random.  State and block live in registers (chacha20.h).
+BP_HD void rpp_draw(sc &r, const uint8_t *seed32, uint64_t d) {
+    uint32_t key[8], w[16];
+    load_words8(key, seed32);
+    chacha20_block(key, d, 0, 0, w);
+    sc_from_wide(r, w);
+}
+// Where a draw comes from: draw(r, sh, p, d) = the d-th random scalar of proof p, d counting in the order above -- party j's
+// a_blinding is j (2n + 2), its s_blinding the next, s_L[i] at + 2 + i, s_R[i] at + 2 + n + i; t_1_blinding_j is m (2n + 2) + 2j,
+// t_2_blinding_j the next.  Either the caller's bytes (bpgpu_rangeproof_prove_batch) or a 32-byte seed per proof (..._prove_batch_ts).
+struct rpp_from_bytes {
+    const uint8_t *rng;     // [proof][rng_per_proof]
+    BP_HD void draw(sc &r, const rpp_shape &sh, uint32_t p, uint32_t d) const { rpp_wide(r, rng + (uint64_t)p * sh.rng_per_proof + 64 * (uint64_t)d); }
+};
+struct rpp_from_seed {
+    const uint8_t *seeds;   // [proof][32]
+    BP_HD void draw(sc &r, const rpp_shape &, uint32_t p, uint32_t d) const { rpp_draw(r, seeds + 32 * (uint64_t)p, d); }
+};
+
 // lane = (proof p, party j, bit i): the bit's terms of A (MSM row 2p) and S (row 2p + 1); s_L, s_R kept for the polynomials
-BP_HD void rpp_bits_thread(uint32_t tid, rpp_shape sh, const uint64_t *values, const uint8_t *rng, uint32_t *gen_scalars, uint32_t *sL, uint32_t *sR) {
+template <class Src>
+BP_HD void rpp_bits_lane(uint32_t tid, rpp_shape sh, const uint64_t *values, const Src &src, uint32_t *gen_scalars, uint32_t *sL, uint32_t *sR) {
     const uint32_t p = tid / sh.nm, q = tid - p * sh.nm, j = q / sh.n, i = q - j * sh.n;
     const uint64_t v = values[(uint64_t)p * sh.m + j];
     const bool bit = (v >> i) & 1;
@@ -59,29 +78,33 @@ BP_HD void rpp_bits_thread(uint32_t tid, rpp_shape sh, const uint64_t *values, c
     sc_neg(m1, one);
     ippc_st(rpp_row(gen_scalars, sh, 2 * p, 2 + q), bit ? one : zero);            // a_L on G
     ippc_st(rpp_row(gen_scalars, sh, 2 * p, 2 + sh.nm + q), bit ? zero : m1);     // a_R = a_L - 1 on H
-    const uint8_t *r = rpp_rng_party(sh, rng, p, j) + 128;
-    rpp_wide(s, r + 64 * (uint64_t)i);
+    const uint32_t d = j * (2 * sh.n + 2) + 2 + i;
+    src.draw(s, sh, p, d);
     ippc_st(rpp_row(gen_scalars, sh, 2 * p + 1, 2 + q), s);
     ippc_st(sL + 8 * (uint64_t)tid, s);
-    rpp_wide(s, r + 64 * (uint64_t)(sh.n + i));
+    src.draw(s, sh, p, d + sh.n);
     ippc_st(rpp_row(gen_scalars, sh, 2 * p + 1, 2 + sh.nm + q), s);
     ippc_st(sR + 8 * (uint64_t)tid, s);
 }
+BP_HD void rpp_bits_thread(uint32_t tid, rpp_shape sh, const uint64_t *values, const uint8_t *rng, uint32_t *gen_scalars, uint32_t *sL, uint32_t *sR) {
+    rpp_bits_lane(tid, sh, values, rpp_from_bytes{rng}, gen_scalars, sL, sR);
+}
 
 // lane = proof: the blinding terms of A and S (summed over the parties) and the V_j rows (MSM 2 nproofs + p m + j)
-BP_HD void rpp_blind_thread(uint32_t p, rpp_shape sh, const uint64_t *values, const uint8_t *blindings, const uint8_t *rng, uint32_t *gen_scalars,
-                            uint32_t *party) {
+template <class Src>
+BP_HD void rpp_blind_lane(uint32_t p, rpp_shape sh, const uint64_t *values, const uint8_t *blindings, const Src &src, uint32_t *gen_scalars,
+                          uint32_t *party) {
     const uint64_t PB = (uint64_t)sh.nproofs * sh.m;
     sc sa, ss, x;
     sc_0(sa);
     sc_0(ss);
     for (uint32_t j = 0; j < sh.m; j++) {
         const uint64_t pj = (uint64_t)p * sh.m + j;
-        const uint8_t *r = rpp_rng_party(sh, rng, p, j);
-        rpp_wide(x, r);
+        const uint32_t d = j * (2 * sh.n + 2);
+        src.draw(x, sh, p, d);
         ippc_st(party + ((uint64_t)RPP_ABL * PB + pj) * 8, x);
         sc_add(sa, sa, x);
-        rpp_wide(x, r + 64);
+        src.draw(x, sh, p, d + 1);
         ippc_st(party + ((uint64_t)RPP_SBL * PB + pj) * 8, x);
         sc_add(ss, ss, x);
         uint32_t w[16];
@@ -99,6 +122,10 @@ BP_HD void rpp_blind_thread(uint32_t p, rpp_shape sh, const uint64_t *values, co
     }
     ippc_st(rpp_row(gen_scalars, sh, 2 * p, 0), sa);
     ippc_st(rpp_row(gen_scalars, sh, 2 * p + 1, 0), ss);
+}
+BP_HD void rpp_blind_thread(uint32_t p, rpp_shape sh, const uint64_t *values, const uint8_t *blindings, const uint8_t *rng, uint32_t *gen_scalars,
+                            uint32_t *party) {
+    rpp_blind_lane(p, sh, values, blindings, rpp_from_bytes{rng}, gen_scalars, party);
 }
 
 BP_HD void rpp_ts_load(strobe &t, kstate st, const uint32_t *tw) {
@@ -119,11 +146,26 @@ BP_HD void rpp_copy8(uint32_t *dst, const uint32_t *src) {
 }
 
 // lane = proof: commitments out; transcript V_j, A, S -> y, z (mod.rs:255-259, dealer.rs:103-125)
-// msm_out rows: 2p = A, 2p + 1 = S, 2 nproofs + p m + j = V_j.  The transcript state already holds rangeproof_domain_sep.
-BP_HD void rpp_chal1_thread(uint32_t p, rpp_shape sh, kstate st, const uint32_t *msm_out, uint32_t *ts, uint32_t *fields, uint8_t *proofs,
-                            uint8_t *commitments) {
+// msm_out rows: 2p = A, 2p + 1 = S, 2 nproofs + p m + j = V_j.
+// SEP = false: the state in ts already holds rangeproof_domain_sep.  SEP = true: the lane starts from the caller's own state at
+// ts_in + p ts_in_stride words (stride 0: one state for every proof) and applies rangeproof_domain_sep(n, m) (transcript.rs:44-48)
+// through the byte-wise STROBE path: a separator that crosses the rate boundary permutes in the middle.  A state whose position
+// bytes are out of range (device memory, which the host cannot check) starts at position 0: never an index past the sponge.
+template <bool SEP>
+BP_HD void rpp_chal1_lane(uint32_t p, rpp_shape sh, kstate st, const uint32_t *msm_out, const uint32_t *ts_in, uint32_t ts_in_stride, uint32_t *ts,
+                          uint32_t *fields, uint8_t *proofs, uint8_t *commitments) {
     strobe t;
-    rpp_ts_load(t, st, ts + (uint64_t)p * BP_TS_WORDS);
+    if (SEP) {
+        rpp_ts_load(t, st, ts_in + (uint64_t)p * ts_in_stride);
+        if (t.pos >= BP_STROBE_R || t.pos_begin > BP_STROBE_R) t.pos = t.pos_begin = 0;
+        const uint8_t dsep[7] = {'d', 'o', 'm', '-', 's', 'e', 'p'}, l_n[1] = {'n'}, l_m[1] = {'m'};
+        const uint8_t rpv1[13] = {'r', 'a', 'n', 'g', 'e', 'p', 'r', 'o', 'o', 'f', ' ', 'v', '1'};
+        merlin_append_message(t, dsep, 7, rpv1, 13);
+        merlin_append_u64(t, l_n, 1, sh.n);
+        merlin_append_u64(t, l_m, 1, sh.m);
+    } else {
+        rpp_ts_load(t, st, ts + (uint64_t)p * BP_TS_WORDS);
+    }
     const uint8_t lV[1] = {'V'}, lA[1] = {'A'}, lS[1] = {'S'}, ly[1] = {'y'}, lz[1] = {'z'};
     uint32_t w[8];
     for (uint32_t j = 0; j < sh.m; j++) {
@@ -144,6 +186,10 @@ BP_HD void rpp_chal1_thread(uint32_t p, rpp_shape sh, kstate st, const uint32_t 
     ippc_st(fields + ((uint64_t)RPP_Y * sh.nproofs + p) * 8, y);
     ippc_st(fields + ((uint64_t)RPP_Z * sh.nproofs + p) * 8, z);
     rpp_ts_store(ts + (uint64_t)p * BP_TS_WORDS, t);
+}
+BP_HD void rpp_chal1_thread(uint32_t p, rpp_shape sh, kstate st, const uint32_t *msm_out, uint32_t *ts, uint32_t *fields, uint8_t *proofs,
+                            uint8_t *commitments) {
+    rpp_chal1_lane<false>(p, sh, st, msm_out, nullptr, 0, ts, fields, proofs, commitments);
 }
 
 // lane = (proof, party): l(X) = l0 + l1 X, r(X) = r0 + r1 X and the coefficients of t(X) = <l, r> (party.rs:145-172)
@@ -208,20 +254,21 @@ BP_HD void rpp_poly_thread(uint32_t tid, rpp_shape sh, const uint64_t *values, c
 }
 
 // lane = proof: T_1, T_2 rows (MSM 2p, 2p + 1): (sum_j t_i,j) on B, (sum_j t_i_blinding_j) on B_blinding
-BP_HD void rpp_tcommit_thread(uint32_t p, rpp_shape sh, const uint8_t *rng, uint32_t *gen_scalars, uint32_t *party) {
+template <class Src>
+BP_HD void rpp_tcommit_lane(uint32_t p, rpp_shape sh, const Src &src, uint32_t *gen_scalars, uint32_t *party) {
     const uint64_t PB = (uint64_t)sh.nproofs * sh.m;
     sc s1, s2, b1, b2, x;
     sc_0(s1);
     sc_0(s2);
     sc_0(b1);
     sc_0(b2);
-    const uint8_t *r = rng + (uint64_t)p * sh.rng_per_proof + (uint64_t)sh.m * 64 * (2 * sh.n + 2);
+    const uint32_t d0 = sh.m * (2 * sh.n + 2);
     for (uint32_t j = 0; j < sh.m; j++) {
         const uint64_t pj = (uint64_t)p * sh.m + j;
-        rpp_wide(x, r + 128 * (uint64_t)j);
+        src.draw(x, sh, p, d0 + 2 * j);
         ippc_st(party + ((uint64_t)RPP_T1B * PB + pj) * 8, x);
         sc_add(b1, b1, x);
-        rpp_wide(x, r + 128 * (uint64_t)j + 64);
+        src.draw(x, sh, p, d0 + 2 * j + 1);
         ippc_st(party + ((uint64_t)RPP_T2B * PB + pj) * 8, x);
         sc_add(b2, b2, x);
         ippc_ld(x, party + ((uint64_t)RPP_T1 * PB + pj) * 8);
@@ -233,6 +280,9 @@ BP_HD void rpp_tcommit_thread(uint32_t p, rpp_shape sh, const uint8_t *rng, uint
     ippc_st(rpp_row(gen_scalars, sh, 2 * p, 1), s1);
     ippc_st(rpp_row(gen_scalars, sh, 2 * p + 1, 0), b2);
     ippc_st(rpp_row(gen_scalars, sh, 2 * p + 1, 1), s2);
+}
+BP_HD void rpp_tcommit_thread(uint32_t p, rpp_shape sh, const uint8_t *rng, uint32_t *gen_scalars, uint32_t *party) {
+    rpp_tcommit_lane(p, sh, rpp_from_bytes{rng}, gen_scalars, party);
 }
 
 // lane = proof: T_1, T_2 -> x; t_x, t_x_blinding, e_blinding (party.rs:217-244 summed by the dealer, dealer.rs:262-266) -> w;

@@ -738,6 +738,38 @@ int bpgpu_rangeproof_prove_batch(bpgpu_ctx *ctx, size_t n, size_t m, size_t nbat
                                  const uint8_t *shared_transcript, const uint8_t *rng,
                                  uint8_t *proofs_out, uint8_t *commitments_out, uint8_t *transcripts_out);
 
+/* The same proofs on the callers' OWN transcripts, with the random scalars drawn on the device from one 32-byte seed per proof.
+ *   transcripts : the callers' states BEFORE rangeproof_domain_sep(n, m), at any STROBE position: one 208-byte state shared by
+ *                 every proof (transcript_stride = 0) or one per proof (transcript_stride = BPGPU_TRANSCRIPT_BYTES).  The separator is
+ *                 applied per proof on the device.  transcripts_out (optional, nbatch x 208): each state as the prover leaves it --
+ *                 what bpgpu_rangeproof_verify_batch_ts leaves for the same proof.
+ *   rng32       : nbatch x 32 bytes, proof p's seed: the rng handed to prove_multiple_with_rng is rand_chacha's
+ *                 ChaChaRng::from_seed(rng32[p]).  Draw d of proof p is Scalar::from_bytes_mod_order_wide of keystream block d of
+ *                 ChaCha20 under that key (64-bit block counter d, stream id 0), d in the order of the `rng` buffer above:
+ *                 party j: a_blinding j(2n+2), s_blinding j(2n+2)+1, s_L[i] j(2n+2)+2+i, s_R[i] j(2n+2)+2+n+i;
+ *                 t_1_blinding_j m(2n+2)+2j, t_2_blinding_j m(2n+2)+2j+1.  Each draw is computed by the device lane that consumes it:
+ *                 no buffer of draws exists in the caller's memory, in staging or on the device.
+ *                 NULL = 32 bytes per proof from the OS-seeded CSPRNG of the library.
+ * CONTRACT: for every p the three outputs equal bpgpu_rangeproof_prove_batch(nbatch = 1, shared_transcript = transcripts[p],
+ * rng = keystream blocks 0 .. D-1 of rng32[p]) with D = m(2n+2) + 2m.
+ * Errors: those of bpgpu_rangeproof_prove_batch, and BPGPU_ERR_INVALID_ARG for transcripts == NULL, a stride other than 0 or 208
+ * and a malformed state (every state is checked before anything is staged).  nbatch = 0 is BPGPU_OK.  "prover_constant_time"
+ * applies as above.  The seeds are secrets: staged in the secret part of the staging block and cleared with it on every exit.
+ * The _dev form takes device pointers (4-byte aligned, values 8-byte) and enqueues on `stream` (NULL: the context's own) with the
+ * conventions of the other _dev entry points; nothing is read back, so what the host form checks in the data is the caller's
+ * to guarantee: values < 2^n (a proof of a larger value does not verify) and well-formed states (a state whose position bytes are
+ * out of range is started at position 0).  The library's working sets and the MSM arena are cleared on that stream behind the last
+ * kernel; the caller's buffers are the caller's.  With d_rng32 = NULL the library draws the seeds, uploads them through its own
+ * staging and clears that once the copy has completed (the one wait of the _dev form). */
+int bpgpu_rangeproof_prove_batch_ts(bpgpu_ctx *ctx, size_t n, size_t m, size_t nbatch, const uint64_t *values,
+                                    const uint8_t *blindings, const uint8_t *transcripts, size_t transcript_stride,
+                                    const uint8_t *rng32, uint8_t *proofs_out, uint8_t *commitments_out,
+                                    uint8_t *transcripts_out);
+int bpgpu_rangeproof_prove_batch_ts_dev(bpgpu_ctx *ctx, size_t n, size_t m, size_t nbatch, const void *d_values,
+                                        const void *d_blindings, const void *d_transcripts, size_t transcript_stride,
+                                        const void *d_rng32, void *d_proofs_out, void *d_commitments_out,
+                                        void *d_transcripts_out, void *stream);
+
 /* ---- the multi-party aggregation protocol: parties and dealer ------------------------------------
  * range_proof_mpc of the reference (src/range_proof/party.rs, dealer.rs, messages.rs; docs/aggregation-api.md) as six
  * batched, STATELESS calls: host pointers in and out, nothing retained after return.  bpgpu_rangeproof_prove_batch above

@@ -240,6 +240,45 @@ class RangeProof {
                                                                    uint64_t v, const ScalarBytes &v_blinding, size_t n) {
         return prove_single_with_rng(bp_gens, pc_gens, transcript, v, v_blinding, n, nullptr);
     }
+    // values.size() proofs in ONE GPU pass (bpgpu_rangeproof_prove_batch_ts; no counterpart in the crate): values[i] / blindings[i] are
+    // the m values / blindings of proof i; transcripts: ONE bound transcript, the start state of every proof (not advanced), or one
+    // per proof, each left advanced as prove_multiple_with_rng leaves it.  rng32: 32 bytes per proof, proof i's rng being
+    // ChaChaRng::from_seed(rng32 + 32 i), its scalars drawn on the device; nullptr: the library draws the seeds.
+    static std::vector<std::pair<RangeProof, std::vector<CompressedRistretto>>> prove_batch(const BulletproofGens &bp_gens, const PedersenGens &pc_gens,
+                                                                                            std::vector<Transcript> &transcripts,
+                                                                                            const std::vector<std::vector<uint64_t>> &values,
+                                                                                            const std::vector<std::vector<ScalarBytes>> &blindings, size_t n,
+                                                                                            const uint8_t *rng32 = nullptr) {
+        bp_gens.check_pedersen(pc_gens);
+        const size_t nb = values.size(), m = nb ? values[0].size() : 0;
+        std::vector<std::pair<RangeProof, std::vector<CompressedRistretto>>> out(nb);
+        if (!nb) return out;
+        if (blindings.size() != nb || (transcripts.size() != nb && transcripts.size() != 1)) throw std::invalid_argument("prove_batch: one row per proof");
+        const bool per_proof = transcripts.size() == nb && nb != 1;
+        size_t k = 0;
+        while ((size_t(1) << k) < n * m) k++;
+        const size_t pl = 32 * (9 + 2 * k), TS = BPGPU_TRANSCRIPT_BYTES;
+        std::vector<uint64_t> va(nb * m);
+        std::vector<uint8_t> bl(32 * nb * m), ts(per_proof ? nb * TS : TS), tso(nb * TS), pr(nb * pl), vc(32 * nb * m);
+        for (size_t i = 0; i < nb; i++) {
+            if (values[i].size() != m || blindings[i].size() != m) throw std::invalid_argument("prove_batch: WrongNumBlindingFactors");
+            for (size_t j = 0; j < m; j++) {
+                va[i * m + j] = values[i][j];
+                std::memcpy(&bl[32 * (i * m + j)], blindings[i][j].data(), 32);
+            }
+            if (per_proof || i == 0) std::memcpy(&ts[i * TS], transcripts[i].state().data(), TS);
+        }
+        const int rc = bpgpu_rangeproof_prove_batch_ts(bp_gens.ctx(), n, m, nb, va.data(), bl.data(), ts.data(), per_proof ? TS : 0, rng32, pr.data(),
+                                                       vc.data(), tso.data());
+        if (rc != BPGPU_OK) throw GpuError(bpgpu_last_error(bp_gens.ctx()));
+        for (size_t i = 0; i < nb; i++) {
+            out[i].first.bytes_.assign(pr.begin() + i * pl, pr.begin() + (i + 1) * pl);
+            out[i].second.resize(m);
+            for (size_t j = 0; j < m; j++) std::memcpy(out[i].second[j].data(), &vc[32 * (i * m + j)], 32);
+            if (transcripts.size() == nb) std::memcpy(transcripts[i].state_mut().data(), &tso[i * TS], TS);
+        }
+        return out;
+    }
     const std::vector<uint8_t> &to_bytes() const { return bytes_; }
 
     // verify_multiple_with_rng: rng64 = the 64 bytes the rng would hand Scalar::random (mod.rs:396)
