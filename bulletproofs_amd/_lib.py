@@ -31,6 +31,9 @@ EXPORTS = [
     "bpgpu_rangeproof_prove_batch_ts", "bpgpu_rangeproof_prove_batch_ts_dev",
     "bpgpu_linear_verify_batch", "bpgpu_linear_verify_batch_dev", "bpgpu_linear_create_batch",
     "bpgpu_linear_verify_rlc", "bpgpu_linear_verify_rlc_dev", "bpgpu_ipp_verify_rlc", "bpgpu_ipp_verify_rlc_dev",
+    "bpgpu_ipp_verify_batch_ts", "bpgpu_ipp_verify_batch_ts_dev", "bpgpu_ipp_verify_rlc_ts", "bpgpu_ipp_verify_rlc_ts_dev",
+    "bpgpu_linear_verify_batch_ts", "bpgpu_linear_verify_batch_ts_dev", "bpgpu_linear_verify_rlc_ts", "bpgpu_linear_verify_rlc_ts_dev",
+    "bpgpu_ipp_create_batch_ts", "bpgpu_linear_create_batch_ts",
     "bpgpu_rangeproof_audit_shares", "bpgpu_ipp_verification_scalars",
     "bpgpu_pool_create", "bpgpu_pool_destroy", "bpgpu_pool_last_error", "bpgpu_pool_set_option", "bpgpu_pool_get_option",
     "bpgpu_pool_devices", "bpgpu_pool_lanes", "bpgpu_pool_lane", "bpgpu_pool_gens_create", "bpgpu_pool_gens_load",
@@ -119,6 +122,16 @@ def lib():
     L.bpgpu_linear_verify_rlc_dev.argtypes = [vp, sz, sz, vp, sz, u8p, sz, u8p, vp, vp, vp, vp, vp, i, vp, vp, vp, vp, vp]
     L.bpgpu_ipp_verify_rlc.argtypes = [vp, sz, sz, u8p, sz, u8p, sz, u8p, u8p, u8p, u8p, u8p, u8p, u8p, sz, u8p, u8p, u8p]
     L.bpgpu_ipp_verify_rlc_dev.argtypes = [vp, sz, sz, vp, sz, u8p, sz, u8p, vp, vp, vp, vp, vp, vp, sz, vp, vp, vp, vp]
+    L.bpgpu_ipp_verify_batch_ts.argtypes = [vp, sz, sz, u8p, sz, u8p, sz, u8p, u8p, u8p, u8p, u8p, u8p, i, u8p, u8p, u8p]
+    L.bpgpu_ipp_verify_batch_ts_dev.argtypes = [vp, sz, sz, vp, sz, u8p, vp, vp, vp, vp, vp, vp, vp, i, vp, vp, vp, vp]
+    L.bpgpu_ipp_verify_rlc_ts.argtypes = [vp, sz, sz, u8p, sz, u8p, sz, u8p, u8p, u8p, u8p, u8p, u8p, sz, u8p, u8p, u8p, u8p]
+    L.bpgpu_ipp_verify_rlc_ts_dev.argtypes = [vp, sz, sz, vp, sz, u8p, vp, vp, vp, vp, vp, vp, vp, sz, vp, vp, vp, vp, vp]
+    L.bpgpu_linear_verify_batch_ts.argtypes = [vp, sz, sz, u8p, sz, u8p, sz, u8p, u8p, u8p, u8p, u8p, i, u8p, u8p, u8p]
+    L.bpgpu_linear_verify_batch_ts_dev.argtypes = [vp, sz, sz, vp, sz, u8p, vp, vp, vp, vp, vp, vp, i, vp, vp, vp, vp]
+    L.bpgpu_linear_verify_rlc_ts.argtypes = [vp, sz, sz, u8p, sz, u8p, sz, u8p, u8p, u8p, u8p, u8p, i, u8p, u8p, u8p, u8p]
+    L.bpgpu_linear_verify_rlc_ts_dev.argtypes = [vp, sz, sz, vp, sz, u8p, vp, vp, vp, vp, vp, vp, i, vp, vp, vp, vp, vp]
+    L.bpgpu_ipp_create_batch_ts.argtypes = [vp, sz, sz, u8p, sz, u8p, u8p, u8p, u8p, u8p, i, u8p, u8p, u8p, u8p, u8p]
+    L.bpgpu_linear_create_batch_ts.argtypes = [vp, sz, sz, u8p, sz, u8p, u8p, u8p, u8p, u8p, i, u8p, u8p, u8p, u8p, u8p, u8p]
     L.bpgpu_ipp_verification_scalars.argtypes = [vp, sz, sz, u8p, sz, u8p, sz, u8p, sz, u8p, u8p, u8p, u8p, u8p]
     L.bpgpu_mpc_state1_bytes.argtypes = [sz]
     L.bpgpu_mpc_state1_bytes.restype = sz
@@ -529,6 +542,104 @@ class Context:
         out, st = C.create_string_buffer(pl * max(nb, 1)), C.create_string_buffer(max(nb, 1))
         self._chk(self._L.bpgpu_ipp_create_batch(self.h, n, nb, label, len(label), transcript, Q, Gf, Hf, G, H, shared, a, b, out, st))
         return out.raw[:pl * nb], st.raw[:nb]
+
+    # ---- inner-product and linear proofs on the callers' own transcripts (bpgpu_*_ts) ----
+    @staticmethod
+    def _ts_stride(transcripts, nb):
+        """transcripts: ONE 208-byte state (before innerproduct_domain_sep) for every proof, or one per proof"""
+        assert transcripts is not None and len(transcripts) in (TRANSCRIPT_BYTES, TRANSCRIPT_BYTES * nb)
+        return TRANSCRIPT_BYTES if (nb != 1 and len(transcripts) == TRANSCRIPT_BYTES * nb) else 0
+
+    def ipp_verify_batch_ts(self, n, proofs, proof_len, transcripts, Gf, Hf, P, Q, G, H, want_msm=False, want_transcripts=False):
+        """InnerProductProof::verify of len(P) / 32 proofs, each on its caller's own transcript (bpgpu_ipp_verify_batch_ts).  G, H: n points
+        each shared by the batch, or n per proof."""
+        nb = len(P) // 32
+        assert len(proofs) == nb * proof_len and len(Gf) == len(Hf) == 32 * n * nb and len(Q) == 32 * nb
+        assert len(G) == len(H) and len(G) in (32 * n, 32 * n * nb)
+        shared = 1 if (len(G) == 32 * n and nb != 1) else 0
+        verdict = C.create_string_buffer(max(nb, 1))
+        msm = C.create_string_buffer(32 * max(nb, 1)) if want_msm else None
+        tso = C.create_string_buffer(TRANSCRIPT_BYTES * max(nb, 1)) if want_transcripts else None
+        self._chk(self._L.bpgpu_ipp_verify_batch_ts(self.h, n, nb, proofs, proof_len, transcripts, self._ts_stride(transcripts, nb), Gf, Hf, P, Q, G, H,
+                                                    shared, verdict, msm, tso))
+        out = (verdict.raw[:nb],) + ((msm.raw[:32 * nb],) if want_msm else ()) + ((tso.raw[:TRANSCRIPT_BYTES * nb],) if want_transcripts else ())
+        return out if len(out) > 1 else out[0]
+
+    def ipp_verify_rlc_ts(self, n, proofs, proof_len, transcripts, Gf, Hf, P, Q, G, H, gens_m=1, weights64=None, want_transcripts=False):
+        """ipp_verify_rlc on the callers' own transcripts (bpgpu_ipp_verify_rlc_ts).  Returns (verdict bytes, batch_ok, 32-byte encoding of
+        the combined point[, transcripts])."""
+        nb = len(P) // 32
+        assert len(proofs) == nb * proof_len and len(Gf) == len(Hf) == 32 * n * nb and len(Q) == 32 * nb
+        assert (G is None and H is None) or len(G) == len(H) == 32 * n
+        assert weights64 is None or len(weights64) == 64 * nb
+        verdict = C.create_string_buffer(max(nb, 1))
+        bo = C.create_string_buffer(33)
+        tso = C.create_string_buffer(TRANSCRIPT_BYTES * max(nb, 1)) if want_transcripts else None
+        self._chk(self._L.bpgpu_ipp_verify_rlc_ts(self.h, n, nb, proofs, proof_len, transcripts, self._ts_stride(transcripts, nb), Gf, Hf, P, Q, G, H,
+                                                  gens_m, weights64, verdict, bo, tso))
+        out = (verdict.raw[:nb], bo.raw[0] == 0, bo.raw[1:33])
+        return out + (tso.raw[:TRANSCRIPT_BYTES * nb],) if want_transcripts else out
+
+    def linear_verify_batch_ts(self, n, proofs, proof_len, transcripts, Cs, G, F, B, b, want_msm=False, want_transcripts=False):
+        """linear_verify_batch on the callers' own transcripts (bpgpu_linear_verify_batch_ts)."""
+        nb = len(Cs) // 32
+        assert len(proofs) == nb * proof_len and len(b) in (32 * n, 32 * n * nb)
+        assert (G is None and F is None and B is None) or (len(G) == 32 * n and len(F) == len(B) == 32)   # None: the context's generators
+        shared = 1 if (len(b) == 32 * n and nb != 1) else 0
+        verdict = C.create_string_buffer(max(nb, 1))
+        msm = C.create_string_buffer(32 * max(nb, 1)) if want_msm else None
+        tso = C.create_string_buffer(TRANSCRIPT_BYTES * max(nb, 1)) if want_transcripts else None
+        self._chk(self._L.bpgpu_linear_verify_batch_ts(self.h, n, nb, proofs, proof_len, transcripts, self._ts_stride(transcripts, nb), Cs, G, F, B, b,
+                                                       shared, verdict, msm, tso))
+        out = (verdict.raw[:nb],) + ((msm.raw[:32 * nb],) if want_msm else ()) + ((tso.raw[:TRANSCRIPT_BYTES * nb],) if want_transcripts else ())
+        return out if len(out) > 1 else out[0]
+
+    def linear_verify_rlc_ts(self, n, proofs, proof_len, transcripts, Cs, G, F, B, b, weights64=None, want_transcripts=False):
+        """linear_verify_rlc on the callers' own transcripts (bpgpu_linear_verify_rlc_ts).  Returns (verdict bytes, batch_ok, 32-byte encoding
+        of the combined point[, transcripts])."""
+        nb = len(Cs) // 32
+        assert len(proofs) == nb * proof_len and len(b) in (32 * n, 32 * n * nb)
+        assert (G is None and F is None and B is None) or (len(G) == 32 * n and len(F) == len(B) == 32)
+        assert weights64 is None or len(weights64) == 64 * nb
+        shared = 1 if (len(b) == 32 * n and nb != 1) else 0
+        verdict = C.create_string_buffer(max(nb, 1))
+        bo = C.create_string_buffer(33)
+        tso = C.create_string_buffer(TRANSCRIPT_BYTES * max(nb, 1)) if want_transcripts else None
+        self._chk(self._L.bpgpu_linear_verify_rlc_ts(self.h, n, nb, proofs, proof_len, transcripts, self._ts_stride(transcripts, nb), Cs, G, F, B, b,
+                                                     shared, weights64, verdict, bo, tso))
+        out = (verdict.raw[:nb], bo.raw[0] == 0, bo.raw[1:33])
+        return out + (tso.raw[:TRANSCRIPT_BYTES * nb],) if want_transcripts else out
+
+    def ipp_create_batch_ts(self, n, transcripts, Q, Gf, Hf, G, H, a, b, want_transcripts=False):
+        """ipp_create_batch on the callers' own transcripts (bpgpu_ipp_create_batch_ts): returns (proofs bytes, status bytes[, the states as
+        create() leaves them])."""
+        nb = len(Q) // 32
+        assert len(a) == len(b) == len(Gf) == len(Hf) == 32 * n * nb and len(G) == len(H) and len(G) in (32 * n, 32 * n * nb)
+        shared = 1 if (len(G) == 32 * n and nb != 1) else 0
+        pl = 32 * (2 * (n.bit_length() - 1) + 2)
+        out, st = C.create_string_buffer(pl * max(nb, 1)), C.create_string_buffer(max(nb, 1))
+        tso = C.create_string_buffer(TRANSCRIPT_BYTES * max(nb, 1)) if want_transcripts else None
+        self._chk(self._L.bpgpu_ipp_create_batch_ts(self.h, n, nb, transcripts, self._ts_stride(transcripts, nb), Q, Gf, Hf, G, H, shared, a, b, out, st,
+                                                    tso))
+        res = (out.raw[:pl * nb], st.raw[:nb])
+        return res + (tso.raw[:TRANSCRIPT_BYTES * nb],) if want_transcripts else res
+
+    def linear_create_batch_ts(self, n, transcripts, Cs, rs, a, b, G, F, B, rng32=None, want_transcripts=False):
+        """linear_create_batch on the callers' own transcripts, the random scalars drawn on the device (bpgpu_linear_create_batch_ts).
+        rng32: 32 bytes per proof, the seed of its ChaChaRng (None: the library draws them).  Returns (proofs bytes, status bytes[,
+        transcripts])."""
+        nb = len(Cs) // 32
+        assert len(rs) == 32 * nb and len(a) == 32 * n * nb and len(b) in (32 * n, 32 * n * nb)
+        assert (G is None and F is None and B is None) or (len(G) == 32 * n and len(F) == len(B) == 32)
+        assert rng32 is None or len(rng32) == 32 * nb
+        shared = 1 if (len(b) == 32 * n and nb != 1) else 0
+        pl = 32 * (2 * (n.bit_length() - 1) + 3)
+        out, st = C.create_string_buffer(pl * max(nb, 1)), C.create_string_buffer(max(nb, 1))
+        tso = C.create_string_buffer(TRANSCRIPT_BYTES * max(nb, 1)) if want_transcripts else None
+        self._chk(self._L.bpgpu_linear_create_batch_ts(self.h, n, nb, transcripts, self._ts_stride(transcripts, nb), rng32, Cs, rs, a, b, shared, G, F,
+                                                       B, out, st, tso))
+        res = (out.raw[:pl * nb], st.raw[:nb])
+        return res + (tso.raw[:TRANSCRIPT_BYTES * nb],) if want_transcripts else res
 
     def rangeproof_prove_batch(self, n, m, values, blindings, label=b"", transcript=None, rng=None, want_transcripts=False):
         """RangeProof::prove_multiple_with_rng for len(values) / m proofs (bpgpu_rangeproof_prove_batch): returns

@@ -368,19 +368,27 @@ class LinearProof:
         return len(self._raw)
 
     @staticmethod
-    def create(transcript, rng_bytes, C, r, a_vec, b_vec, G_vec, F, B, ctx):
+    def create(transcript, rng_bytes, C, r, a_vec, b_vec, G_vec, F, B, ctx, rng_seed32=None):
         """LinearProof::create(transcript, rng, &C, r, a_vec, b_vec, G_vec, &F, &B) (linear_proof.rs:40-173) on the GPU (variable
         time, like the reference's).  rng_bytes: the 64 * (2 lg n + 2) bytes the rng would yield to Scalar::random, or None for
-        the OS CSPRNG.  The transcript is left advanced.  Raises ValueError for InvalidInputLength / InvalidGeneratorsLength."""
+        the OS CSPRNG.  rng_seed32 instead: the rng is ChaChaRng::from_seed(rng_seed32), its scalars drawn on the device
+        (bpgpu_linear_create_batch_ts).  The transcript is left advanced.  Raises ValueError for InvalidInputLength /
+        InvalidGeneratorsLength."""
         c = getattr(ctx, "ctx", ctx)
         n = len(b_vec)
         if len(G_vec) != n:
             raise InvalidGeneratorsLength()
         if len(a_vec) != n or n == 0 or n & (n - 1):
             raise ValueError("InvalidInputLength")
-        proofs, status, ts = c.linear_create_batch(n, bytes(C), bytes(r), b"".join(bytes(x) for x in a_vec), b"".join(bytes(x) for x in b_vec),
-                                                   b"".join(bytes(g) for g in G_vec), bytes(F), bytes(B), transcript=transcript.state, rng=rng_bytes,
-                                                   want_transcripts=True)
+        a, b, G = b"".join(bytes(x) for x in a_vec), b"".join(bytes(x) for x in b_vec), b"".join(bytes(g) for g in G_vec)
+        if rng_seed32 is not None:
+            if rng_bytes is not None or len(rng_seed32) != 32:
+                raise ValueError("rng_seed32: 32 bytes, and not together with rng_bytes")
+            proofs, status, ts = c.linear_create_batch_ts(n, transcript.state, bytes(C), bytes(r), a, b, G, bytes(F), bytes(B), rng32=bytes(rng_seed32),
+                                                          want_transcripts=True)
+        else:
+            proofs, status, ts = c.linear_create_batch(n, bytes(C), bytes(r), a, b, G, bytes(F), bytes(B), transcript=transcript.state, rng=rng_bytes,
+                                                       want_transcripts=True)
         if status[0] != 0:
             raise ValueError("an input point does not decode or a scalar is not canonical")
         transcript.state = ts
@@ -404,34 +412,86 @@ class LinearProof:
             raise _BY_CODE[v[0]]()
 
     @staticmethod
-    def verify_batch(ctx, transcript, proofs, Cs, G, F, B, b_vecs):
-        """proofs[i].verify(&mut transcript.clone(), &Cs[i], G, F, B, b_vecs[i]) for all i in one GPU pass -> list of None /
-        ProofError.  b_vecs: one vector per proof, or a single vector (list of scalars) shared by all."""
+    def create_batch(ctx, transcripts, Cs, rs, a_vecs, b_vecs, G, F, B, rng_seed32=None):
+        """len(Cs) proofs in ONE GPU pass (bpgpu_linear_create_batch_ts; no counterpart in the crate).  `transcripts`: one bound Transcript,
+        the start state of every proof (not advanced), or a list of transcripts, one per proof, each left advanced as create() leaves
+        it.  a_vecs: one secret vector per proof; b_vecs: one public vector per proof, or a single vector shared by all.
+        rng_seed32: 32 bytes per proof, proof i's rng being ChaChaRng::from_seed(rng_seed32[32 i:32 i + 32]) (None: the library draws
+        the seeds).  Returns [LinearProof]; raises ValueError when an input of some proof does not decode or is not canonical."""
         c = getattr(ctx, "ctx", ctx)
-        if not proofs:
+        if not Cs:
             return []
+        nb, n = len(Cs), len(G)
+        per_proof = isinstance(transcripts, (list, tuple))
+        if per_proof and len(transcripts) != nb:
+            raise ValueError("create_batch: one transcript per proof")
+        if len(rs) != nb or len(a_vecs) != nb or any(len(a) != n for a in a_vecs) or n == 0 or n & (n - 1):
+            raise ValueError("InvalidInputLength")
+        shared = len(b_vecs) == n and isinstance(b_vecs[0], (bytes, bytearray))
+        b = b"".join(bytes(x) for x in b_vecs) if shared else b"".join(b"".join(bytes(x) for x in v) for v in b_vecs)
+        states = b"".join(t.state for t in transcripts) if per_proof else transcripts.state
+        proofs, status, ts = c.linear_create_batch_ts(n, states, b"".join(bytes(x) for x in Cs), b"".join(bytes(x) for x in rs),
+                                                      b"".join(b"".join(bytes(x) for x in a) for a in a_vecs), b, b"".join(bytes(g) for g in G), bytes(F),
+                                                      bytes(B), rng32=rng_seed32, want_transcripts=True)
+        if any(status):
+            raise ValueError("an input point does not decode or a scalar is not canonical (proof %d)" % next(i for i, x in enumerate(status) if x))
+        if per_proof:
+            for i, t in enumerate(transcripts):
+                t.state = ts[208 * i:208 * i + 208]
+                t.fresh_label = None
+        pl = len(proofs) // nb
+        return [LinearProof(proofs[pl * i:pl * i + pl]) for i in range(nb)]
+
+    @staticmethod
+    def _batch_args(proofs, Cs, G, b_vecs):
         raw = [p.to_bytes() if isinstance(p, LinearProof) else bytes(p) for p in proofs]
         ln, n = len(raw[0]), len(G)
         assert all(len(r) == ln for r in raw)
         shared = len(b_vecs) == n and isinstance(b_vecs[0], (bytes, bytearray))
         b = b"".join(bytes(x) for x in b_vecs) if shared else b"".join(b"".join(bytes(x) for x in v) for v in b_vecs)
-        v = c.linear_verify_batch(n, b"".join(raw), ln, b"".join(bytes(x) for x in Cs), b"".join(bytes(g) for g in G), bytes(F), bytes(B), b,
-                                  transcript=transcript.state)
+        return n, b"".join(raw), ln, b"".join(bytes(x) for x in Cs), b"".join(bytes(g) for g in G), b
+
+    @staticmethod
+    def _advance(transcripts, ts):
+        for i, t in enumerate(transcripts):
+            t.state = ts[208 * i:208 * i + 208]
+            t.fresh_label = None
+
+    @staticmethod
+    def verify_batch(ctx, transcript, proofs, Cs, G, F, B, b_vecs):
+        """proofs[i].verify(&mut transcript.clone(), &Cs[i], G, F, B, b_vecs[i]) for all i in one GPU pass -> list of None /
+        ProofError.  b_vecs: one vector per proof, or a single vector (list of scalars) shared by all.  `transcript`: one Transcript, the
+        start state of every proof (not advanced), or a list of transcripts, one per proof (bpgpu_linear_verify_batch_ts), each left as
+        verify() leaves it (after an Err: the state right after innerproduct_domain_sep(n), as in verify())."""
+        c = getattr(ctx, "ctx", ctx)
+        if not proofs:
+            return []
+        n, raw, ln, cs, g, b = LinearProof._batch_args(proofs, Cs, G, b_vecs)
+        if isinstance(transcript, (list, tuple)):
+            if len(transcript) != len(proofs):
+                raise ValueError("verify_batch: one transcript per proof")
+            v, ts = c.linear_verify_batch_ts(n, raw, ln, b"".join(t.state for t in transcript), cs, g, bytes(F), bytes(B), b, want_transcripts=True)
+            LinearProof._advance(transcript, ts)
+        else:
+            v = c.linear_verify_batch(n, raw, ln, cs, g, bytes(F), bytes(B), b, transcript=transcript.state)
         return [None if x == 0 else _BY_CODE[x]() for x in v]
 
     @staticmethod
     def verify_batch_combined(ctx, transcript, proofs, Cs, G, F, B, b_vecs, weights64=None):
-        """verify_batch's arguments and verdicts through the batch-combined check (bpgpu_linear_verify_rlc; no counterpart in the
-        crate): one identity test per batch when every proof verifies, per-proof re-verification inside the call when not.
-        weights64: 64 bytes per proof, unpredictable to the provers, or None (drawn by the library)."""
+        """verify_batch's arguments and verdicts through the batch-combined check (bpgpu_linear_verify_rlc / _rlc_ts; no counterpart in
+        the crate): one identity test per batch when every proof verifies, per-proof re-verification inside the call when not.
+        weights64: 64 bytes per proof, unpredictable to the provers, or None (drawn by the library).  A list of transcripts, one per
+        proof, is left advanced as in verify_batch."""
         c = getattr(ctx, "ctx", ctx)
         if not proofs:
             return []
-        raw = [p.to_bytes() if isinstance(p, LinearProof) else bytes(p) for p in proofs]
-        ln, n = len(raw[0]), len(G)
-        assert all(len(r) == ln for r in raw)
-        shared = len(b_vecs) == n and isinstance(b_vecs[0], (bytes, bytearray))
-        b = b"".join(bytes(x) for x in b_vecs) if shared else b"".join(b"".join(bytes(x) for x in v) for v in b_vecs)
-        v, _, _ = c.linear_verify_rlc(n, b"".join(raw), ln, b"".join(bytes(x) for x in Cs), b"".join(bytes(g) for g in G), bytes(F), bytes(B), b,
-                                      transcript=transcript.state, weights64=weights64)
+        n, raw, ln, cs, g, b = LinearProof._batch_args(proofs, Cs, G, b_vecs)
+        if isinstance(transcript, (list, tuple)):
+            if len(transcript) != len(proofs):
+                raise ValueError("verify_batch_combined: one transcript per proof")
+            v, _, _, ts = c.linear_verify_rlc_ts(n, raw, ln, b"".join(t.state for t in transcript), cs, g, bytes(F), bytes(B), b, weights64=weights64,
+                                                 want_transcripts=True)
+            LinearProof._advance(transcript, ts)
+        else:
+            v, _, _ = c.linear_verify_rlc(n, raw, ln, cs, g, bytes(F), bytes(B), b, transcript=transcript.state, weights64=weights64)
         return [None if x == 0 else _BY_CODE[x]() for x in v]

@@ -2717,12 +2717,48 @@ static void ipp_domain_sep_state(uint8_t st0[BPGPU_TRANSCRIPT_BYTES], const uint
     }
 }
 
+// The callers' own transcripts of the bpgpu_ipp_*_ts / bpgpu_linear_*_ts entry points: states BEFORE innerproduct_domain_sep(n), which the
+// lanes apply themselves (ipp.h: ipp_ts_start).  One state for every proof -- `shared` (host memory, handed to the kernels by value), or
+// d_in with stride 0 -- or one per proof (d_in, stride BP_TS_WORDS).  With an ipp_ts the label / shared_ts arguments are not looked at.
+struct ipp_ts {
+    const uint8_t *shared = nullptr;
+    const void *d_in = nullptr;
+    uint32_t stride = 0;       // words between the states at d_in
+    void *d_out = nullptr;     // nbatch states (optional; the inner-product calls only: the linear ones have had a d_ts_out all along)
+};
+static void ipp_ts_init(rp_strobe_init &init, const ipp_ts &ts) {
+    memset(&init, 0, sizeof init);
+    if (ts.shared) strobe_init_from_state(init, ts.shared);
+}
+// the argument checks of the host forms: every state is looked at before anything is staged
+static int ipp_ts_host_args(bpgpu_ctx *c, const uint8_t *transcripts, size_t transcript_stride, size_t nbatch) {
+    if (!transcripts || (transcript_stride != 0 && transcript_stride != BPGPU_TRANSCRIPT_BYTES))
+        return fail(c, BPGPU_ERR_INVALID_ARG, "transcripts missing, or transcript_stride neither 0 nor BPGPU_TRANSCRIPT_BYTES");
+    for (size_t b = 0; b < (transcript_stride ? nbatch : 1); b++)
+        if (!ts_state_ok(transcripts + b * BPGPU_TRANSCRIPT_BYTES)) return fail(c, BPGPU_ERR_INVALID_ARG, "malformed transcript state %zu", b);
+    return BPGPU_OK;
+}
+// ... and of the _dev forms: one checked host state or nbatch device states (which the lanes guard themselves)
+static int ipp_ts_dev_args(bpgpu_ctx *c, const uint8_t *shared_transcript, const void *d_transcripts, const void *d_transcripts_out, ipp_ts &ts) {
+    if ((shared_transcript != nullptr) == (d_transcripts != nullptr))
+        return fail(c, BPGPU_ERR_INVALID_ARG, "give exactly one of shared_transcript / d_transcripts");
+    if (shared_transcript && !ts_state_ok(shared_transcript)) return fail(c, BPGPU_ERR_INVALID_ARG, "malformed transcript state");
+    if (((uintptr_t)d_transcripts | (uintptr_t)d_transcripts_out) & 3) return fail(c, BPGPU_ERR_INVALID_ARG, "device buffers must be 4-byte aligned");
+    ts.shared = shared_transcript;
+    ts.d_in = d_transcripts;
+    ts.stride = BP_TS_WORDS;
+    return BPGPU_OK;
+}
+
 static int ipp_verify_dev_locked(bpgpu_ctx *c, size_t n, size_t nbatch, const void *d_proofs, size_t proof_len, const uint8_t *label,
                                  size_t label_len, const uint8_t *shared_ts, const void *d_Gf, const void *d_Hf, const void *d_P,
                                  const void *d_Q, const void *d_G, const void *d_H, int bases_shared, void *d_verdict, void *d_msm_out,
-                                 hipStream_t s) {
+                                 hipStream_t s, const ipp_ts *ts = nullptr) {
     if (nbatch > 0x7fffffffu / 64) return fail(c, BPGPU_ERR_INVALID_ARG, "batch too large");
-    if (shared_ts && !ts_state_ok(shared_ts)) return fail(c, BPGPU_ERR_INVALID_ARG, "malformed transcript state");
+    if (!ts && shared_ts && !ts_state_ok(shared_ts)) return fail(c, BPGPU_ERR_INVALID_ARG, "malformed transcript state");
+    const uint32_t nb32 = (uint32_t)nbatch;
+    rp_strobe_init init;
+    if (ts) ipp_ts_init(init, *ts);
     // InnerProductProof::from_bytes, length part (ipp.rs:374-388)
     size_t k = 0;
     bool fmt = false;
@@ -2738,6 +2774,8 @@ static int ipp_verify_dev_locked(bpgpu_ctx *c, size_t n, size_t nbatch, const vo
     if (fmt) {
         HIPCHK(c, hipMemsetAsync(d_verdict, BPGPU_VERDICT_FORMAT_ERROR, nbatch, s));
         if (d_msm_out) HIPCHK(c, hipMemsetAsync(d_msm_out, 0, nbatch * 32, s));
+        if (ts && ts->d_out)   // from_bytes rejects every proof: the callers' states go back as they came
+            LAUNCH(c, s, "ipp_ts_input", k_ipp_ts_input, (nb32 + 63) / 64, 64, nb32, init, (const uint32_t *)ts->d_in, ts->stride, (uint32_t *)ts->d_out);
         return BPGPU_OK;
     }
     ipp_shape sh;
@@ -2763,15 +2801,17 @@ static int ipp_verify_dev_locked(bpgpu_ctx *c, size_t n, size_t nbatch, const vo
     }
     char *d_sc = c->ipp_buf, *d_pt = d_sc + sz_terms, *d_stat = d_pt + sz_terms, *d_mst = d_stat + sz_st, *d_out = d_mst + sz_b;
     HIPCHK(c, hipMemsetAsync(d_sc, 0, 2 * sz_terms + sz_st, s));   // scalars, points, status
-    rp_strobe_init init;
-    {
+    if (ts) {
+        LAUNCH(c, s, "ipp_prepare_ts", k_ipp_prepare_ts, (nb32 + RP_BLOCK - 1) / RP_BLOCK, RP_BLOCK, sh, init, (const uint8_t *)d_proofs, (const uint8_t *)d_Gf,
+               (const uint8_t *)d_Hf, (const uint8_t *)d_P, (const uint8_t *)d_Q, (const uint8_t *)d_G, (const uint8_t *)d_H, (uint32_t *)d_sc,
+               (uint32_t *)d_pt, (uint32_t *)d_stat, (const uint32_t *)ts->d_in, ts->stride, (uint32_t *)ts->d_out);
+    } else {
         uint8_t st0[BPGPU_TRANSCRIPT_BYTES];
         ipp_domain_sep_state(st0, label, label_len, shared_ts, n, &init);
+        LAUNCH(c, s, "ipp_prepare", k_ipp_prepare, (nb32 + RP_BLOCK - 1) / RP_BLOCK, RP_BLOCK, sh, init, (const uint8_t *)d_proofs, (const uint8_t *)d_Gf,
+               (const uint8_t *)d_Hf, (const uint8_t *)d_P, (const uint8_t *)d_Q, (const uint8_t *)d_G, (const uint8_t *)d_H, (uint32_t *)d_sc,
+               (uint32_t *)d_pt, (uint32_t *)d_stat);
     }
-    const uint32_t nb32 = (uint32_t)nbatch;
-    LAUNCH(c, s, "ipp_prepare", k_ipp_prepare, (nb32 + RP_BLOCK - 1) / RP_BLOCK, RP_BLOCK, sh, init, (const uint8_t *)d_proofs, (const uint8_t *)d_Gf,
-           (const uint8_t *)d_Hf, (const uint8_t *)d_P, (const uint8_t *)d_Q, (const uint8_t *)d_G, (const uint8_t *)d_H, (uint32_t *)d_sc,
-           (uint32_t *)d_pt, (uint32_t *)d_stat);
     std::vector<uint32_t> nt(nbatch, (uint32_t)N);
     int rc = msm_batch_dev_locked(c, nbatch, nt.data(), d_sc, d_pt, d_out, d_mst, s);
     if (rc) return rc;
@@ -2900,39 +2940,93 @@ extern "C" int bpgpu_ipp_verification_scalars(bpgpu_ctx *c, size_t n, size_t nba
     return BPGPU_OK;
 }
 
-extern "C" int bpgpu_ipp_verify_batch(bpgpu_ctx *c, size_t n, size_t nbatch, const uint8_t *proofs, size_t proof_len, const uint8_t *label,
-                                      size_t label_len, const uint8_t *G_factors, const uint8_t *H_factors, const uint8_t *P,
-                                      const uint8_t *Q, const uint8_t *G, const uint8_t *H, uint8_t *verdict, uint8_t *msm_out) {
-    if (!c || (label_len && !label)) return BPGPU_ERR_INVALID_ARG;
+// host pointers.  ts_host (with ts_stride 0 or BPGPU_TRANSCRIPT_BYTES): the callers' own transcripts, checked by the caller, in place of the label
+static int ipp_verify_host_call(bpgpu_ctx *c, size_t n, size_t nbatch, const uint8_t *proofs, size_t proof_len, const uint8_t *label, size_t label_len,
+                                const uint8_t *ts_host, size_t ts_stride, const uint8_t *G_factors, const uint8_t *H_factors, const uint8_t *P,
+                                const uint8_t *Q, const uint8_t *G, const uint8_t *H, int bases_shared, uint8_t *verdict, uint8_t *msm_out,
+                                uint8_t *ts_out_host) {
     if (nbatch == 0) return BPGPU_OK;
     if (!proofs || !verdict || !P || !Q || (n && (!G_factors || !H_factors || !G || !H))) return BPGPU_ERR_INVALID_ARG;
     std::lock_guard<std::mutex> lk(c->mu);
     HIPCHK(c, hipSetDevice(c->device));
     hipStream_t s = c->stream;
     host_call<bpgpu_ctx> io(c, s);
-    const size_t b_f = nbatch * n * 32 + 64, b_pq = nbatch * 32 + 64;
-    const int r_pr = io.in(nbatch * proof_len + 64), r_gf = io.in(b_f), r_hf = io.in(b_f), r_g = io.in(b_f), r_h = io.in(b_f), r_p = io.in(b_pq), r_q = io.in(b_pq);
-    const int r_v = io.out(nbatch), r_o = io.out(nbatch * 32);
+    const size_t TS = BPGPU_TRANSCRIPT_BYTES, nb_g = bases_shared ? 1 : nbatch, nstates = !ts_host ? 0 : ts_stride ? nbatch : 1;
+    const size_t b_f = nbatch * n * 32 + 64, b_g = nb_g * n * 32 + 64, b_pq = nbatch * 32 + 64;
+    const int r_pr = io.in(nbatch * proof_len + 64), r_gf = io.in(b_f), r_hf = io.in(b_f), r_g = io.in(b_g), r_h = io.in(b_g), r_p = io.in(b_pq), r_q = io.in(b_pq),
+              r_ti = io.in(nstates * TS);
+    const int r_v = io.out(nbatch), r_o = io.out(nbatch * 32), r_to = io.out(ts_out_host ? nbatch * TS : 0);
     int rc = io.open();
     if (rc) return rc;
     io.put(r_pr, proofs, nbatch * proof_len);
     if (n) {
         io.put(r_gf, G_factors, nbatch * n * 32);
         io.put(r_hf, H_factors, nbatch * n * 32);
-        io.put(r_g, G, nbatch * n * 32);
-        io.put(r_h, H, nbatch * n * 32);
+        io.put(r_g, G, nb_g * n * 32);
+        io.put(r_h, H, nb_g * n * 32);
     }
     io.put(r_p, P, nbatch * 32);
     io.put(r_q, Q, nbatch * 32);
+    ipp_ts ts;
+    if (ts_host) {
+        io.put(r_ti, ts_host, nstates * TS);
+        ts.d_in = io.d(r_ti);
+        ts.stride = ts_stride ? BP_TS_WORDS : 0;
+        ts.d_out = ts_out_host ? io.d(r_to) : nullptr;
+    }
     rc = io.upload();
     if (!rc)
-        rc = ipp_verify_dev_locked(c, n, nbatch, io.d(r_pr), proof_len, label, label_len, nullptr, io.d(r_gf), io.d(r_hf), io.d(r_p), io.d(r_q), io.d(r_g), io.d(r_h), 0,
-                                   io.d(r_v), io.d(r_o), s);
+        rc = ipp_verify_dev_locked(c, n, nbatch, io.d(r_pr), proof_len, label, label_len, nullptr, io.d(r_gf), io.d(r_hf), io.d(r_p), io.d(r_q), io.d(r_g), io.d(r_h),
+                                   bases_shared, io.d(r_v), io.d(r_o), s, ts_host ? &ts : nullptr);
     rc = io.finish(io.download(rc));
     if (rc) return rc;
     memcpy(verdict, io.h(r_v), nbatch);
     if (msm_out) memcpy(msm_out, io.h(r_o), nbatch * 32);
+    if (ts_out_host) memcpy(ts_out_host, io.h(r_to), nbatch * TS);
     return BPGPU_OK;
+}
+
+extern "C" int bpgpu_ipp_verify_batch(bpgpu_ctx *c, size_t n, size_t nbatch, const uint8_t *proofs, size_t proof_len, const uint8_t *label,
+                                      size_t label_len, const uint8_t *G_factors, const uint8_t *H_factors, const uint8_t *P,
+                                      const uint8_t *Q, const uint8_t *G, const uint8_t *H, uint8_t *verdict, uint8_t *msm_out) {
+    if (!c || (label_len && !label)) return BPGPU_ERR_INVALID_ARG;
+    return ipp_verify_host_call(c, n, nbatch, proofs, proof_len, label, label_len, nullptr, 0, G_factors, H_factors, P, Q, G, H, 0, verdict, msm_out, nullptr);
+}
+
+// ---- the same verification on the callers' own transcripts (ipp.h: ipp_prepare_lane<true>) ----
+extern "C" int bpgpu_ipp_verify_batch_ts(bpgpu_ctx *c, size_t n, size_t nbatch, const uint8_t *proofs, size_t proof_len, const uint8_t *transcripts,
+                                         size_t transcript_stride, const uint8_t *G_factors, const uint8_t *H_factors, const uint8_t *P,
+                                         const uint8_t *Q, const uint8_t *G, const uint8_t *H, int bases_shared, uint8_t *verdict, uint8_t *msm_out,
+                                         uint8_t *transcripts_out) {
+    if (!c) return BPGPU_ERR_INVALID_ARG;
+    const int rca = ipp_ts_host_args(c, transcripts, transcript_stride, nbatch);
+    if (rca) return rca;
+    return ipp_verify_host_call(c, n, nbatch, proofs, proof_len, nullptr, 0, transcripts, transcript_stride, G_factors, H_factors, P, Q, G, H, bases_shared,
+                                verdict, msm_out, transcripts_out);
+}
+
+extern "C" int bpgpu_ipp_verify_batch_ts_dev(bpgpu_ctx *c, size_t n, size_t nbatch, const void *d_proofs, size_t proof_len, const uint8_t *shared_transcript,
+                                             const void *d_transcripts, const void *d_G_factors, const void *d_H_factors, const void *d_P,
+                                             const void *d_Q, const void *d_G, const void *d_H, int bases_shared, void *d_verdict, void *d_msm_out,
+                                             void *d_transcripts_out, void *stream) {
+    if (!c) return BPGPU_ERR_INVALID_ARG;
+    ipp_ts ts;
+    const int rca = ipp_ts_dev_args(c, shared_transcript, d_transcripts, d_transcripts_out, ts);
+    if (rca) return rca;
+    ts.d_out = d_transcripts_out;
+    if (nbatch == 0) return BPGPU_OK;
+    if (!d_proofs || !d_verdict || !d_P || !d_Q || (n && (!d_G_factors || !d_H_factors || !d_G || !d_H))) return BPGPU_ERR_INVALID_ARG;
+    if (((uintptr_t)d_proofs | (uintptr_t)d_G_factors | (uintptr_t)d_H_factors | (uintptr_t)d_P | (uintptr_t)d_Q | (uintptr_t)d_G | (uintptr_t)d_H) & 3)
+        return fail(c, BPGPU_ERR_INVALID_ARG, "device buffers must be 4-byte aligned");
+    std::lock_guard<std::mutex> lk(c->mu);
+    HIPCHK(c, hipSetDevice(c->device));
+    hipStream_t s = stream ? (hipStream_t)stream : c->stream;
+    int rc = ctx_enter(c, s);
+    if (rc) return rc;
+    rc = ipp_verify_dev_locked(c, n, nbatch, d_proofs, proof_len, nullptr, 0, nullptr, d_G_factors, d_H_factors, d_P, d_Q, d_G, d_H, bases_shared, d_verdict,
+                               d_msm_out, s, &ts);
+    const int rc2 = ctx_leave(c, s);
+    return rc ? rc : rc2;
 }
 
 // what the front end of a LinearProof batch leaves on the device (c->ipp_buf) for its multiscalar multiplication(s)
@@ -2948,9 +3042,10 @@ struct lin_staged {
 // LinearProof::from_bytes' length part, the staging and the k_lin_prepare launch (lane = proof) of nbatch proofs
 static int lin_front_dev_locked(bpgpu_ctx *c, size_t n, size_t nbatch, const void *d_proofs, size_t proof_len, const uint8_t *label,
                                 size_t label_len, const uint8_t *shared_ts, const void *d_C, const void *d_G, const void *d_F,
-                                const void *d_B, const void *d_b, int b_shared, void *d_ts_out, hipStream_t s, lin_staged &stg) {
+                                const void *d_B, const void *d_b, int b_shared, void *d_ts_out, hipStream_t s, lin_staged &stg,
+                                const ipp_ts *ts = nullptr) {
     if (nbatch > 0x7fffffffu / 64) return fail(c, BPGPU_ERR_INVALID_ARG, "batch too large");
-    if (shared_ts && !ts_state_ok(shared_ts)) return fail(c, BPGPU_ERR_INVALID_ARG, "malformed transcript state");
+    if (!ts && shared_ts && !ts_state_ok(shared_ts)) return fail(c, BPGPU_ERR_INVALID_ARG, "malformed transcript state");
     // LinearProof::from_bytes, length part (linear_proof.rs:350-366)
     size_t k = 0;
     bool fmt = false;
@@ -3003,14 +3098,19 @@ static int lin_front_dev_locked(bpgpu_ctx *c, size_t n, size_t nbatch, const voi
     HIPCHK(c, hipMemsetAsync(d_sc, 0, 2 * sz_terms + sz_st, s));   // scalars, points, status
     if (fixed) HIPCHK(c, hipMemsetAsync(d_gen, 0, sz_gen, s));
     rp_strobe_init init;
-    {
+    const uint32_t nb32 = (uint32_t)nbatch;
+    if (ts) {
+        ipp_ts_init(init, *ts);
+        LAUNCH(c, s, "lin_prepare_ts", k_lin_prepare_ts, (nb32 + RP_BLOCK - 1) / RP_BLOCK, RP_BLOCK, sh, init, (const uint8_t *)d_proofs, (const uint8_t *)d_C,
+               (const uint8_t *)d_b, (const uint8_t *)d_G, (const uint8_t *)d_F, (const uint8_t *)d_B, (uint32_t *)d_sc, (uint32_t *)d_pt,
+               (uint32_t *)d_stat, (uint32_t *)d_ts_out, (uint32_t *)d_gen, (const uint32_t *)ts->d_in, ts->stride, (uint32_t)n);
+    } else {
         uint8_t st0[BPGPU_TRANSCRIPT_BYTES];
         ipp_domain_sep_state(st0, label, label_len, shared_ts, n, &init);
+        LAUNCH(c, s, "lin_prepare", k_lin_prepare, (nb32 + RP_BLOCK - 1) / RP_BLOCK, RP_BLOCK, sh, init, (const uint8_t *)d_proofs, (const uint8_t *)d_C,
+               (const uint8_t *)d_b, (const uint8_t *)d_G, (const uint8_t *)d_F, (const uint8_t *)d_B, (uint32_t *)d_sc, (uint32_t *)d_pt,
+               (uint32_t *)d_stat, (uint32_t *)d_ts_out, (uint32_t *)d_gen);
     }
-    const uint32_t nb32 = (uint32_t)nbatch;
-    LAUNCH(c, s, "lin_prepare", k_lin_prepare, (nb32 + RP_BLOCK - 1) / RP_BLOCK, RP_BLOCK, sh, init, (const uint8_t *)d_proofs, (const uint8_t *)d_C,
-           (const uint8_t *)d_b, (const uint8_t *)d_G, (const uint8_t *)d_F, (const uint8_t *)d_B, (uint32_t *)d_sc, (uint32_t *)d_pt,
-           (uint32_t *)d_stat, (uint32_t *)d_ts_out, (uint32_t *)d_gen);
     stg.fixed = fixed;
     stg.d_sc = d_sc, stg.d_pt = d_pt, stg.d_stat = d_stat, stg.d_mst = d_mst, stg.d_out = d_out, stg.d_gen = d_gen;
     stg.d_G = d_G, stg.d_F = d_F, stg.d_B = d_B;
@@ -3023,9 +3123,9 @@ static int lin_front_dev_locked(bpgpu_ctx *c, size_t n, size_t nbatch, const voi
 static int lin_verify_dev_locked(bpgpu_ctx *c, size_t n, size_t nbatch, const void *d_proofs, size_t proof_len, const uint8_t *label,
                                  size_t label_len, const uint8_t *shared_ts, const void *d_C, const void *d_G, const void *d_F,
                                  const void *d_B, const void *d_b, int b_shared, void *d_verdict, void *d_msm_out, void *d_ts_out,
-                                 hipStream_t s) {
+                                 hipStream_t s, const ipp_ts *ts = nullptr) {
     lin_staged stg;
-    int rc = lin_front_dev_locked(c, n, nbatch, d_proofs, proof_len, label, label_len, shared_ts, d_C, d_G, d_F, d_B, d_b, b_shared, d_ts_out, s, stg);
+    int rc = lin_front_dev_locked(c, n, nbatch, d_proofs, proof_len, label, label_len, shared_ts, d_C, d_G, d_F, d_B, d_b, b_shared, d_ts_out, s, stg, ts);
     if (rc) return rc;
     if (stg.fmt) {
         HIPCHK(c, hipMemsetAsync(d_verdict, BPGPU_VERDICT_FORMAT_ERROR, nbatch, s));
@@ -3075,11 +3175,12 @@ extern "C" int bpgpu_linear_verify_batch_dev(bpgpu_ctx *c, size_t n, size_t nbat
     return rc ? rc : rc2;
 }
 
-extern "C" int bpgpu_linear_verify_batch(bpgpu_ctx *c, size_t n, size_t nbatch, const uint8_t *proofs, size_t proof_len, const uint8_t *label,
-                                         size_t label_len, const uint8_t *shared_transcript, const uint8_t *C, const uint8_t *G, const uint8_t *F,
-                                         const uint8_t *B, const uint8_t *b, int b_shared, uint8_t *verdict, uint8_t *msm_out,
-                                         uint8_t *transcripts_out) {
-    if (!c || (label_len && !label)) return BPGPU_ERR_INVALID_ARG;
+// host pointers.  ts_host (with ts_stride 0 or BPGPU_TRANSCRIPT_BYTES): the callers' own transcripts, checked by the caller, in place of label /
+// shared_transcript
+static int lin_verify_host_call(bpgpu_ctx *c, size_t n, size_t nbatch, const uint8_t *proofs, size_t proof_len, const uint8_t *label, size_t label_len,
+                                const uint8_t *shared_transcript, const uint8_t *ts_host, size_t ts_stride, const uint8_t *C, const uint8_t *G,
+                                const uint8_t *F, const uint8_t *B, const uint8_t *b, int b_shared, uint8_t *verdict, uint8_t *msm_out,
+                                uint8_t *transcripts_out) {
     if (nbatch == 0) return BPGPU_OK;
     const bool from_gens = !G && !F && !B;
     if (!proofs || !verdict || !C || (n && !b) || (!from_gens && (!F || !B || (n && !G)))) return BPGPU_ERR_INVALID_ARG;
@@ -3088,7 +3189,9 @@ extern "C" int bpgpu_linear_verify_batch(bpgpu_ctx *c, size_t n, size_t nbatch, 
     const size_t nb_b = b_shared ? 1 : nbatch;
     hipStream_t s = c->stream;
     host_call<bpgpu_ctx> io(c, s);
-    const int r_pr = io.in(nbatch * proof_len + 64), r_c = io.in(nbatch * 32 + 64), r_g = io.in(n * 32 + 64), r_fb = io.in(64 + 64), r_bv = io.in(nb_b * n * 32 + 64);
+    const size_t nstates = !ts_host ? 0 : ts_stride ? nbatch : 1;
+    const int r_pr = io.in(nbatch * proof_len + 64), r_c = io.in(nbatch * 32 + 64), r_g = io.in(n * 32 + 64), r_fb = io.in(64 + 64), r_bv = io.in(nb_b * n * 32 + 64),
+              r_ti = io.in(nstates * BPGPU_TRANSCRIPT_BYTES);
     const int r_v = io.out(nbatch), r_o = io.out(nbatch * 32), r_t = io.out(transcripts_out ? nbatch * BPGPU_TRANSCRIPT_BYTES : 0);
     int rc = io.open();
     if (rc) return rc;
@@ -3102,17 +3205,67 @@ extern "C" int bpgpu_linear_verify_batch(bpgpu_ctx *c, size_t n, size_t nbatch, 
         memcpy(io.h(r_fb), F, 32);
         memcpy(io.h(r_fb) + 32, B, 32);
     }
+    ipp_ts ts;
+    if (ts_host) {
+        io.put(r_ti, ts_host, nstates * BPGPU_TRANSCRIPT_BYTES);
+        ts.d_in = io.d(r_ti);
+        ts.stride = ts_stride ? BP_TS_WORDS : 0;
+    }
     rc = io.upload();
     if (!rc)
         rc = lin_verify_dev_locked(c, n, nbatch, io.d(r_pr), proof_len, label, label_len, shared_transcript, io.d(r_c), from_gens ? nullptr : io.d(r_g),
                                    from_gens ? nullptr : io.d(r_fb), from_gens ? nullptr : io.d(r_fb) + 32, io.d(r_bv), b_shared, io.d(r_v), io.d(r_o),
-                                   transcripts_out ? io.d(r_t) : nullptr, s);
+                                   transcripts_out ? io.d(r_t) : nullptr, s, ts_host ? &ts : nullptr);
     rc = io.finish(io.download(rc));
     if (rc) return rc;
     memcpy(verdict, io.h(r_v), nbatch);
     if (msm_out) memcpy(msm_out, io.h(r_o), nbatch * 32);
     if (transcripts_out) memcpy(transcripts_out, io.h(r_t), nbatch * BPGPU_TRANSCRIPT_BYTES);
     return BPGPU_OK;
+}
+
+extern "C" int bpgpu_linear_verify_batch(bpgpu_ctx *c, size_t n, size_t nbatch, const uint8_t *proofs, size_t proof_len, const uint8_t *label,
+                                         size_t label_len, const uint8_t *shared_transcript, const uint8_t *C, const uint8_t *G, const uint8_t *F,
+                                         const uint8_t *B, const uint8_t *b, int b_shared, uint8_t *verdict, uint8_t *msm_out,
+                                         uint8_t *transcripts_out) {
+    if (!c || (label_len && !label)) return BPGPU_ERR_INVALID_ARG;
+    return lin_verify_host_call(c, n, nbatch, proofs, proof_len, label, label_len, shared_transcript, nullptr, 0, C, G, F, B, b, b_shared, verdict, msm_out,
+                                transcripts_out);
+}
+
+// ---- the same verification on the callers' own transcripts (linear.h: lin_prepare_lane<true>) ----
+extern "C" int bpgpu_linear_verify_batch_ts(bpgpu_ctx *c, size_t n, size_t nbatch, const uint8_t *proofs, size_t proof_len, const uint8_t *transcripts,
+                                            size_t transcript_stride, const uint8_t *C, const uint8_t *G, const uint8_t *F, const uint8_t *B,
+                                            const uint8_t *b, int b_shared, uint8_t *verdict, uint8_t *msm_out, uint8_t *transcripts_out) {
+    if (!c) return BPGPU_ERR_INVALID_ARG;
+    const int rca = ipp_ts_host_args(c, transcripts, transcript_stride, nbatch);
+    if (rca) return rca;
+    return lin_verify_host_call(c, n, nbatch, proofs, proof_len, nullptr, 0, nullptr, transcripts, transcript_stride, C, G, F, B, b, b_shared, verdict, msm_out,
+                                transcripts_out);
+}
+
+extern "C" int bpgpu_linear_verify_batch_ts_dev(bpgpu_ctx *c, size_t n, size_t nbatch, const void *d_proofs, size_t proof_len,
+                                                const uint8_t *shared_transcript, const void *d_transcripts, const void *d_C, const void *d_G,
+                                                const void *d_F, const void *d_B, const void *d_b, int b_shared, void *d_verdict, void *d_msm_out,
+                                                void *d_transcripts_out, void *stream) {
+    if (!c) return BPGPU_ERR_INVALID_ARG;
+    ipp_ts ts;
+    const int rca = ipp_ts_dev_args(c, shared_transcript, d_transcripts, d_transcripts_out, ts);
+    if (rca) return rca;
+    if (nbatch == 0) return BPGPU_OK;
+    const bool from_gens = !d_G && !d_F && !d_B;
+    if (!d_proofs || !d_verdict || !d_C || (n && !d_b) || (!from_gens && (!d_F || !d_B || (n && !d_G)))) return BPGPU_ERR_INVALID_ARG;
+    if (((uintptr_t)d_proofs | (uintptr_t)d_C | (uintptr_t)d_G | (uintptr_t)d_F | (uintptr_t)d_B | (uintptr_t)d_b) & 3)
+        return fail(c, BPGPU_ERR_INVALID_ARG, "device buffers must be 4-byte aligned");
+    std::lock_guard<std::mutex> lk(c->mu);
+    HIPCHK(c, hipSetDevice(c->device));
+    hipStream_t s = stream ? (hipStream_t)stream : c->stream;
+    int rc = ctx_enter(c, s);
+    if (rc) return rc;
+    rc = lin_verify_dev_locked(c, n, nbatch, d_proofs, proof_len, nullptr, 0, nullptr, d_C, d_G, d_F, d_B, d_b, b_shared, d_verdict, d_msm_out, d_transcripts_out,
+                               s, &ts);
+    const int rc2 = ctx_leave(c, s);
+    return rc ? rc : rc2;
 }
 
 // ProofShare::audit_share for nshares shares of bitsize n (audit.h): front end (lane = share) -> the ragged (2n + 3, 5) pairs of
@@ -3262,10 +3415,12 @@ static int hip_rc(bpgpu_ctx *c, hipError_t e, const char *call) {
 }
 #define HIPRC(c, call) hip_rc(c, (call), #call)
 
-extern "C" int bpgpu_ipp_create_batch(bpgpu_ctx *c, size_t n, size_t nbatch, const uint8_t *label, size_t label_len, const uint8_t *shared_transcript,
-                                      const uint8_t *Q, const uint8_t *G_factors, const uint8_t *H_factors, const uint8_t *G, const uint8_t *H,
-                                      int bases_shared, const uint8_t *a, const uint8_t *b, uint8_t *proofs_out, uint8_t *status_out) {
-    if (!c || (label_len && !label)) return BPGPU_ERR_INVALID_ARG;
+// ts_host (with ts_stride 0 or BPGPU_TRANSCRIPT_BYTES): the callers' own transcripts, checked by the caller, in place of label / shared_transcript:
+// k_ipp_ts_fill turns them into the rounds' working states, which ts_out_host (optional) gets back as create() leaves them
+static int ipp_create_host_call(bpgpu_ctx *c, size_t n, size_t nbatch, const uint8_t *label, size_t label_len, const uint8_t *shared_transcript,
+                                const uint8_t *ts_host, size_t ts_stride, const uint8_t *Q, const uint8_t *G_factors, const uint8_t *H_factors,
+                                const uint8_t *G, const uint8_t *H, int bases_shared, const uint8_t *a, const uint8_t *b, uint8_t *proofs_out,
+                                uint8_t *status_out, uint8_t *ts_out_host) {
     if (nbatch == 0) return BPGPU_OK;
     if (!Q || !G_factors || !H_factors || !G || !H || !a || !b || !proofs_out || !status_out) return BPGPU_ERR_INVALID_ARG;
     if (n == 0 || (n & (n - 1))) return fail(c, BPGPU_ERR_INVALID_ARG, "n must be a power of two (ipp.rs:54-59)");
@@ -3282,8 +3437,8 @@ extern "C" int bpgpu_ipp_create_batch(bpgpu_ctx *c, size_t n, size_t nbatch, con
     host_call<bpgpu_ctx> io(c, s);
     const size_t b_v = nbatch * n * 32 + 64, b_base = (bases_shared ? 1 : nbatch) * n * 32 + 64;
     const int r_a = io.in(b_v), r_b = io.in(b_v), r_gf = io.in(b_v), r_hf = io.in(b_v), r_q = io.in(nbatch * 32 + 64), r_G = io.in(b_base), r_H = io.in(b_base),
-              r_ts = io.in(nbatch * TS);
-    const int r_proofs = io.out(nbatch * proof_len), r_stb = io.out(nbatch);
+              r_ts = io.in((!ts_host ? nbatch : ts_stride ? nbatch : 1) * TS);
+    const int r_proofs = io.out(nbatch * proof_len), r_stb = io.out(nbatch), r_to = io.out(ts_host ? nbatch * TS : 0);
     io.secrets(io.off[r_gf]);   // the witness a, b
     int rc = io.open();
     if (rc) return io.finish(rc);
@@ -3294,32 +3449,62 @@ extern "C" int bpgpu_ipp_create_batch(bpgpu_ctx *c, size_t n, size_t nbatch, con
     io.put(r_q, Q, nbatch * 32);
     io.put(r_G, G, (bases_shared ? 1 : nbatch) * n * 32);
     io.put(r_H, H, (bases_shared ? 1 : nbatch) * n * 32);
-    {   // every proof's transcript after innerproduct_domain_sep(n) (transcript.rs:50-53)
+    if (ts_host) {
+        io.put(r_ts, ts_host, (ts_stride ? nbatch : 1) * TS);
+    } else {   // every proof's transcript after innerproduct_domain_sep(n) (transcript.rs:50-53)
         uint8_t st0[BPGPU_TRANSCRIPT_BYTES];
         ipp_domain_sep_state(st0, label, label_len, shared_transcript, n, nullptr);
         for (size_t p = 0; p < nbatch; p++) memcpy(io.h(r_ts) + p * TS, st0, TS);
     }
+    uint32_t *d_ts = (uint32_t *)io.d(ts_host ? r_to : r_ts);   // the rounds' working states
     rc = io.upload();
     if (!rc) rc = HIPRC(c, hipMemsetAsync(io.d(r_proofs), 0, nbatch * proof_len, s));
+    if (!rc && ts_host) {   // the separator per proof on the device
+        const uint32_t nb32 = (uint32_t)nbatch;
+        LAUNCH(c, s, "ipp_ts_fill", k_ipp_ts_fill, (nb32 + RP_BLOCK - 1) / RP_BLOCK, RP_BLOCK, nb32, (uint32_t)n, (const uint32_t *)io.d(r_ts),
+               (uint32_t)(ts_stride ? BP_TS_WORDS : 0), d_ts);
+        rc = HIPRC(c, hipGetLastError());
+    }
     // ---- rounds (ippc_core: own working set, the batched MSMs claim the arena)
     if (!rc)
-        rc = ippc_core(c, s, n, k, nbatch, io.d(r_a), io.d(r_b), io.d(r_gf), io.d(r_hf), io.d(r_q), io.d(r_G), io.d(r_H), bases_shared, (uint32_t *)io.d(r_ts),
+        rc = ippc_core(c, s, n, k, nbatch, io.d(r_a), io.d(r_b), io.d(r_gf), io.d(r_hf), io.d(r_q), io.d(r_G), io.d(r_H), bases_shared, d_ts,
                        (uint8_t *)io.d(r_proofs), proof_len, (uint8_t *)io.d(r_stb));
     rc = io.finish(io.download(rc));
     if (rc) return rc;
     memcpy(proofs_out, io.h(r_proofs), nbatch * proof_len);
     memcpy(status_out, io.h(r_stb), nbatch);
+    if (ts_out_host) memcpy(ts_out_host, io.h(r_to), nbatch * TS);
     return BPGPU_OK;
+}
+
+extern "C" int bpgpu_ipp_create_batch(bpgpu_ctx *c, size_t n, size_t nbatch, const uint8_t *label, size_t label_len, const uint8_t *shared_transcript,
+                                      const uint8_t *Q, const uint8_t *G_factors, const uint8_t *H_factors, const uint8_t *G, const uint8_t *H,
+                                      int bases_shared, const uint8_t *a, const uint8_t *b, uint8_t *proofs_out, uint8_t *status_out) {
+    if (!c || (label_len && !label)) return BPGPU_ERR_INVALID_ARG;
+    return ipp_create_host_call(c, n, nbatch, label, label_len, shared_transcript, nullptr, 0, Q, G_factors, H_factors, G, H, bases_shared, a, b, proofs_out,
+                                status_out, nullptr);
+}
+
+extern "C" int bpgpu_ipp_create_batch_ts(bpgpu_ctx *c, size_t n, size_t nbatch, const uint8_t *transcripts, size_t transcript_stride, const uint8_t *Q,
+                                         const uint8_t *G_factors, const uint8_t *H_factors, const uint8_t *G, const uint8_t *H, int bases_shared,
+                                         const uint8_t *a, const uint8_t *b, uint8_t *proofs_out, uint8_t *status_out, uint8_t *transcripts_out) {
+    if (!c) return BPGPU_ERR_INVALID_ARG;
+    const int rca = ipp_ts_host_args(c, transcripts, transcript_stride, nbatch);
+    if (rca) return rca;
+    return ipp_create_host_call(c, n, nbatch, nullptr, 0, nullptr, transcripts, transcript_stride, Q, G_factors, H_factors, G, H, bases_shared, a, b, proofs_out,
+                                status_out, transcripts_out);
 }
 
 // ============================================================================
 // batched linear-proof creation (linear_prover.h)
 // ============================================================================
-extern "C" int bpgpu_linear_create_batch(bpgpu_ctx *c, size_t n, size_t nbatch, const uint8_t *label, size_t label_len, const uint8_t *shared_transcript,
-                                         const uint8_t *rng, const uint8_t *C, const uint8_t *r, const uint8_t *a, const uint8_t *b, int b_shared,
-                                         const uint8_t *G, const uint8_t *F, const uint8_t *B, uint8_t *proofs_out, uint8_t *status_out,
-                                         uint8_t *transcripts_out) {
-    if (!c || (label_len && !label)) return BPGPU_ERR_INVALID_ARG;
+// ts_host == NULL: `rng` holds 64 (2 lg n + 2) bytes per proof (NULL: the OS generator's) and every proof starts from the label's / the shared
+// state.  ts_host (with ts_stride 0 or BPGPU_TRANSCRIPT_BYTES): the callers' own transcripts, checked by the caller, and `rng` holds ONE 32-byte
+// seed per proof (NULL: the OS generator's), from which linc_public_lane draws on the device -- no buffer of draws anywhere on the host.
+static int lin_create_host_call(bpgpu_ctx *c, size_t n, size_t nbatch, const uint8_t *label, size_t label_len, const uint8_t *shared_transcript,
+                                const uint8_t *ts_host, size_t ts_stride, const uint8_t *rng, const uint8_t *C, const uint8_t *r, const uint8_t *a,
+                                const uint8_t *b, int b_shared, const uint8_t *G, const uint8_t *F, const uint8_t *B, uint8_t *proofs_out,
+                                uint8_t *status_out, uint8_t *transcripts_out) {
     if (nbatch == 0) return BPGPU_OK;
     const bool from_gens = !G && !F && !B;   // bases = the context's generators: every MSM through the window tables
     if (!C || !r || !a || !b || (!from_gens && (!G || !F || !B)) || !proofs_out || !status_out) return BPGPU_ERR_INVALID_ARG;
@@ -3340,13 +3525,15 @@ extern "C" int bpgpu_linear_create_batch(bpgpu_ctx *c, size_t n, size_t nbatch, 
     // ---- inputs: one pinned staging block -> the persistent device IO buffer
     host_call<bpgpu_ctx> io(c, s);
     const int r_a = io.in(nbatch * n * 32 + 64), r_b = io.in(nb_b * n * 32 + 64), r_C = io.in(nbatch * 32 + 64), r_r = io.in(nbatch * 32 + 64), r_G = io.in(n * 32 + 64),
-              r_fb = io.in(64 + 64), r_rng = io.in(nbatch * nd * 64), r_ts = io.in(nbatch * TS);
-    const int r_proofs = io.out(nbatch * proof_len), r_stb = io.out(nbatch);
-    io.secrets(io.off[r_ts]);   // a, r, the random draws (and the public inputs between them); the transcript block behind is reused for the way back
+              r_fb = io.in(64 + 64), r_rng = io.in(ts_host ? nbatch * 32 : nbatch * nd * 64), r_ts = io.in((!ts_host ? nbatch : ts_stride ? nbatch : 1) * TS);
+    const int r_proofs = io.out(nbatch * proof_len), r_stb = io.out(nbatch), r_to = io.out(ts_host ? nbatch * TS : 0);
+    // a, r, the random draws or the seeds (and the public inputs between them); without ts_host the transcript block behind is reused for the way back
+    io.secrets(io.off[r_ts]);
     int rc = io.open();
     if (rc) return io.finish(rc);
     char *d_a = io.d(r_a), *d_b = io.d(r_b), *d_C = io.d(r_C), *d_r = io.d(r_r), *d_G = io.d(r_G), *d_fb = io.d(r_fb), *d_rng = io.d(r_rng), *d_ts = io.d(r_ts),
          *d_proofs = io.d(r_proofs), *d_stb = io.d(r_stb);
+    if (ts_host) d_ts = io.d(r_to);   // the working states: filled by k_linc_public_ts from the callers' at r_ts
     io.put(r_a, a, nbatch * n * 32);
     io.put(r_b, b, nb_b * n * 32);
     io.put(r_C, C, nbatch * 32);
@@ -3359,7 +3546,11 @@ extern "C" int bpgpu_linear_create_batch(bpgpu_ctx *c, size_t n, size_t nbatch, 
     const uint8_t *e_G = from_gens ? (const uint8_t *)(c->d_gens + 16) : (const uint8_t *)d_G;          // encodings the transcript absorbs
     const uint8_t *e_F = from_gens ? (const uint8_t *)(c->d_gens + 8) : (const uint8_t *)d_fb;
     const uint8_t *e_B = from_gens ? (const uint8_t *)c->d_gens : (const uint8_t *)d_fb + 32;
-    {
+    if (ts_host) {
+        if (rng) io.put(r_rng, rng, nbatch * 32);
+        else if ((rc = os_random(c, io.h(r_rng), nbatch * 32)) != 0) return io.finish(rc);
+        io.put(r_ts, ts_host, (ts_stride ? nbatch : 1) * TS);
+    } else {
         if (rng) io.put(r_rng, rng, nbatch * nd * 64);
         else if ((rc = os_random(c, io.h(r_rng), nbatch * nd * 64)) != 0) return io.finish(rc);   // Scalar::random(&mut thread_rng())
         // every proof's transcript after innerproduct_domain_sep(n) (linear_proof.rs:73)
@@ -3395,8 +3586,13 @@ extern "C" int bpgpu_linear_create_batch(bpgpu_ctx *c, size_t n, size_t nbatch, 
         const uint32_t nb32 = (uint32_t)nbatch, nt32 = (uint32_t)(nbatch * n), n_q = (nb32 + BP_BLOCK - 1) / BP_BLOCK;
         LAUNCH(c, s, "linc_init", k_linc_init, (nt32 + BP_BLOCK - 1) / BP_BLOCK, BP_BLOCK, nt32, sh, (const uint8_t *)d_a, (const uint8_t *)d_b, w_a, w_b, w_G,
                d_status);
-        LAUNCH(c, s, "linc_public", k_linc_public, (nb32 + RP_BLOCK - 1) / RP_BLOCK, RP_BLOCK, sh, (const uint8_t *)d_C, (const uint8_t *)d_b, e_G, e_F, e_B,
-               (const uint8_t *)d_r, (const uint8_t *)d_rng, (uint32_t *)d_ts, w_r, w_dr, d_status);
+        if (ts_host)
+            LAUNCH(c, s, "linc_public_ts", k_linc_public_ts, (nb32 + RP_BLOCK - 1) / RP_BLOCK, RP_BLOCK, sh, (const uint8_t *)d_C, (const uint8_t *)d_b, e_G, e_F, e_B,
+                   (const uint8_t *)d_r, (const uint8_t *)d_rng, (const uint32_t *)io.d(r_ts), (uint32_t)(ts_stride ? BP_TS_WORDS : 0), (uint32_t *)d_ts, w_r, w_dr,
+                   d_status);
+        else
+            LAUNCH(c, s, "linc_public", k_linc_public, (nb32 + RP_BLOCK - 1) / RP_BLOCK, RP_BLOCK, sh, (const uint8_t *)d_C, (const uint8_t *)d_b, e_G, e_F, e_B,
+                   (const uint8_t *)d_r, (const uint8_t *)d_rng, (uint32_t *)d_ts, w_r, w_dr, d_status);
         std::vector<uint32_t> nterms(2 * nbatch, (uint32_t)N);
         for (uint32_t j = 0; j < k && !rc; j++) {
             if (from_gens) {   // rows of generator-table scalars (B_blinding, B, G_0..): m_sc holds [2 nbatch][n + 2] scalars
@@ -3430,14 +3626,36 @@ extern "C" int bpgpu_linear_create_batch(bpgpu_ctx *c, size_t n, size_t nbatch, 
         if (hipGetLastError() != hipSuccess) rc = fail(c, BPGPU_ERR_HIP, "launch failed");
     } while (0);
     rc = io.download(rc);
-    char *h_ts = io.h(r_ts);   // the transcript block of the staging buffer is free again: reuse it for the way back
-    if (!rc && transcripts_out && hipMemcpyAsync(h_ts, d_ts, nbatch * TS, hipMemcpyDeviceToHost, s) != hipSuccess) rc = fail(c, BPGPU_ERR_HIP, "D2H copy failed");
+    // without ts_host the transcript block of the staging buffer is free again: reuse it for the way back (with it the states are an output region)
+    char *h_ts = io.h(ts_host ? r_to : r_ts);
+    if (!rc && transcripts_out && !ts_host && hipMemcpyAsync(h_ts, d_ts, nbatch * TS, hipMemcpyDeviceToHost, s) != hipSuccess)
+        rc = fail(c, BPGPU_ERR_HIP, "D2H copy failed");
     rc = io.finish(rc);   // (on an error too: the stream is drained before the staging buffers are reused, the secrets cleared)
     if (rc) return rc;
     memcpy(proofs_out, io.h(r_proofs), nbatch * proof_len);
     memcpy(status_out, io.h(r_stb), nbatch);
     if (transcripts_out) memcpy(transcripts_out, h_ts, nbatch * TS);
     return BPGPU_OK;
+}
+
+extern "C" int bpgpu_linear_create_batch(bpgpu_ctx *c, size_t n, size_t nbatch, const uint8_t *label, size_t label_len, const uint8_t *shared_transcript,
+                                         const uint8_t *rng, const uint8_t *C, const uint8_t *r, const uint8_t *a, const uint8_t *b, int b_shared,
+                                         const uint8_t *G, const uint8_t *F, const uint8_t *B, uint8_t *proofs_out, uint8_t *status_out,
+                                         uint8_t *transcripts_out) {
+    if (!c || (label_len && !label)) return BPGPU_ERR_INVALID_ARG;
+    return lin_create_host_call(c, n, nbatch, label, label_len, shared_transcript, nullptr, 0, rng, C, r, a, b, b_shared, G, F, B, proofs_out, status_out,
+                                transcripts_out);
+}
+
+extern "C" int bpgpu_linear_create_batch_ts(bpgpu_ctx *c, size_t n, size_t nbatch, const uint8_t *transcripts, size_t transcript_stride,
+                                            const uint8_t *rng32, const uint8_t *C, const uint8_t *r, const uint8_t *a, const uint8_t *b, int b_shared,
+                                            const uint8_t *G, const uint8_t *F, const uint8_t *B, uint8_t *proofs_out, uint8_t *status_out,
+                                            uint8_t *transcripts_out) {
+    if (!c) return BPGPU_ERR_INVALID_ARG;
+    const int rca = ipp_ts_host_args(c, transcripts, transcript_stride, nbatch);
+    if (rca) return rca;
+    return lin_create_host_call(c, n, nbatch, nullptr, 0, nullptr, transcripts, transcript_stride, rng32, C, r, a, b, b_shared, G, F, B, proofs_out, status_out,
+                                transcripts_out);
 }
 
 // ============================================================================
@@ -4839,10 +5057,10 @@ extern "C" int bpgpu_r1cs_verify_rlc(bpgpu_ctx *c, size_t ngroups, const bpgpu_r
 static int lin_rlc_dev_locked(bpgpu_ctx *c, size_t n, size_t nbatch, const void *d_proofs, size_t proof_len, const uint8_t *label,
                               size_t label_len, const uint8_t *shared_ts, const void *d_C, const void *d_G, const void *d_F, const void *d_B,
                               const void *d_b, int b_shared, const void *d_weights64, uint8_t *d_verdict, uint8_t *d_batch, void *d_ts_out,
-                              hipStream_t s) {
+                              hipStream_t s, const ipp_ts *ts = nullptr) {
     if (nbatch > LIN_RLC_MAX_PROOFS) return fail(c, BPGPU_ERR_INVALID_ARG, "batch too large: more than 2^24 proofs in one combination");
     lin_staged stg;
-    int rc = lin_front_dev_locked(c, n, nbatch, d_proofs, proof_len, label, label_len, shared_ts, d_C, d_G, d_F, d_B, d_b, b_shared, d_ts_out, s, stg);
+    int rc = lin_front_dev_locked(c, n, nbatch, d_proofs, proof_len, label, label_len, shared_ts, d_C, d_G, d_F, d_B, d_b, b_shared, d_ts_out, s, stg, ts);
     if (rc) return rc;
     if (stg.fmt) {   // every proof is a FormatError: the empty sum
         HIPCHK(c, hipMemsetAsync(d_verdict, BPGPU_VERDICT_FORMAT_ERROR, nbatch, s));
@@ -4912,11 +5130,12 @@ extern "C" int bpgpu_linear_verify_rlc_dev(bpgpu_ctx *c, size_t n, size_t nbatch
     return rc ? rc : rc2;
 }
 
-extern "C" int bpgpu_linear_verify_rlc(bpgpu_ctx *c, size_t n, size_t nbatch, const uint8_t *proofs, size_t proof_len, const uint8_t *label,
-                                       size_t label_len, const uint8_t *shared_transcript, const uint8_t *C, const uint8_t *G, const uint8_t *F,
-                                       const uint8_t *B, const uint8_t *b, int b_shared, const uint8_t *weights64, uint8_t *verdict,
-                                       uint8_t *batch_out, uint8_t *transcripts_out) {
-    if (!c || (label_len && !label)) return BPGPU_ERR_INVALID_ARG;
+// host pointers.  ts_host (with ts_stride 0 or BPGPU_TRANSCRIPT_BYTES): the callers' own transcripts, checked by the caller, in place of label /
+// shared_transcript; the per-proof fallback starts again from them
+static int lin_rlc_host_call(bpgpu_ctx *c, size_t n, size_t nbatch, const uint8_t *proofs, size_t proof_len, const uint8_t *label, size_t label_len,
+                             const uint8_t *shared_transcript, const uint8_t *ts_host, size_t ts_stride, const uint8_t *C, const uint8_t *G,
+                             const uint8_t *F, const uint8_t *B, const uint8_t *b, int b_shared, const uint8_t *weights64, uint8_t *verdict,
+                             uint8_t *batch_out, uint8_t *transcripts_out) {
     if (nbatch == 0) {
         if (batch_out) memset(batch_out, 0, 33);
         return BPGPU_OK;
@@ -4930,7 +5149,7 @@ extern "C" int bpgpu_linear_verify_rlc(bpgpu_ctx *c, size_t n, size_t nbatch, co
     hipStream_t s = c->stream;
     host_call<bpgpu_ctx> io(c, s);
     const int r_pr = io.in(nbatch * proof_len + 64), r_c = io.in(nbatch * 32 + 64), r_g = io.in(n * 32 + 64), r_fb = io.in(64 + 64), r_bv = io.in(nb_b * n * 32 + 64),
-              r_w = io.in(weights64 ? nbatch * 64 : 0);
+              r_w = io.in(weights64 ? nbatch * 64 : 0), r_ti = io.in((!ts_host ? 0 : ts_stride ? nbatch : 1) * BPGPU_TRANSCRIPT_BYTES);
     const int r_v = io.out(nbatch), r_bo = io.out(64), r_t = io.out(transcripts_out ? nbatch * BPGPU_TRANSCRIPT_BYTES : 0);
     int rc = io.open();
     if (rc) return rc;
@@ -4946,10 +5165,17 @@ extern "C" int bpgpu_linear_verify_rlc(bpgpu_ctx *c, size_t n, size_t nbatch, co
     }
     if (weights64) io.put(r_w, weights64, nbatch * 64);
     const void *a_g = from_gens ? nullptr : io.d(r_g), *a_f = from_gens ? nullptr : io.d(r_fb), *a_b = from_gens ? nullptr : io.d(r_fb) + 32;
+    ipp_ts ts;
+    if (ts_host) {
+        io.put(r_ti, ts_host, (ts_stride ? nbatch : 1) * BPGPU_TRANSCRIPT_BYTES);
+        ts.d_in = io.d(r_ti);
+        ts.stride = ts_stride ? BP_TS_WORDS : 0;
+    }
+    const ipp_ts *a_ts = ts_host ? &ts : nullptr;
     rc = io.upload();
     if (!rc)
         rc = lin_rlc_dev_locked(c, n, nbatch, io.d(r_pr), proof_len, label, label_len, shared_transcript, io.d(r_c), a_g, a_f, a_b, io.d(r_bv), b_shared,
-                                weights64 ? io.d(r_w) : nullptr, (uint8_t *)io.d(r_v), (uint8_t *)io.d(r_bo), transcripts_out ? io.d(r_t) : nullptr, s);
+                                weights64 ? io.d(r_w) : nullptr, (uint8_t *)io.d(r_v), (uint8_t *)io.d(r_bo), transcripts_out ? io.d(r_t) : nullptr, s, a_ts);
     rc = io.finish(io.download(rc));
     if (rc) return rc;
     if (batch_out) memcpy(batch_out, io.h(r_bo), 33);   // (R as computed before any fallback)
@@ -4959,12 +5185,57 @@ extern "C" int bpgpu_linear_verify_rlc(bpgpu_ctx *c, size_t n, size_t nbatch, co
         // still on the device; the transcripts it leaves are the ones already copied out)
         rc = io.rerun_per_proof(r_v, r_bo, [&] {
             return lin_verify_dev_locked(c, n, nbatch, io.d(r_pr), proof_len, label, label_len, shared_transcript, io.d(r_c), a_g, a_f, a_b, io.d(r_bv), b_shared,
-                                         io.d(r_v), nullptr, nullptr, s);
+                                         io.d(r_v), nullptr, nullptr, s, a_ts);
         });
         if (rc) return rc;
     }
     memcpy(verdict, io.h(r_v), nbatch);
     return BPGPU_OK;
+}
+
+extern "C" int bpgpu_linear_verify_rlc(bpgpu_ctx *c, size_t n, size_t nbatch, const uint8_t *proofs, size_t proof_len, const uint8_t *label,
+                                       size_t label_len, const uint8_t *shared_transcript, const uint8_t *C, const uint8_t *G, const uint8_t *F,
+                                       const uint8_t *B, const uint8_t *b, int b_shared, const uint8_t *weights64, uint8_t *verdict,
+                                       uint8_t *batch_out, uint8_t *transcripts_out) {
+    if (!c || (label_len && !label)) return BPGPU_ERR_INVALID_ARG;
+    return lin_rlc_host_call(c, n, nbatch, proofs, proof_len, label, label_len, shared_transcript, nullptr, 0, C, G, F, B, b, b_shared, weights64, verdict,
+                             batch_out, transcripts_out);
+}
+
+// ---- the combined check on the callers' own transcripts ----
+extern "C" int bpgpu_linear_verify_rlc_ts(bpgpu_ctx *c, size_t n, size_t nbatch, const uint8_t *proofs, size_t proof_len, const uint8_t *transcripts,
+                                          size_t transcript_stride, const uint8_t *C, const uint8_t *G, const uint8_t *F, const uint8_t *B,
+                                          const uint8_t *b, int b_shared, const uint8_t *weights64, uint8_t *verdict, uint8_t *batch_out,
+                                          uint8_t *transcripts_out) {
+    if (!c) return BPGPU_ERR_INVALID_ARG;
+    const int rca = ipp_ts_host_args(c, transcripts, transcript_stride, nbatch);
+    if (rca) return rca;
+    return lin_rlc_host_call(c, n, nbatch, proofs, proof_len, nullptr, 0, nullptr, transcripts, transcript_stride, C, G, F, B, b, b_shared, weights64, verdict,
+                             batch_out, transcripts_out);
+}
+
+extern "C" int bpgpu_linear_verify_rlc_ts_dev(bpgpu_ctx *c, size_t n, size_t nbatch, const void *d_proofs, size_t proof_len, const uint8_t *shared_transcript,
+                                              const void *d_transcripts, const void *d_C, const void *d_G, const void *d_F, const void *d_B,
+                                              const void *d_b, int b_shared, const void *d_weights64, void *d_verdict, void *d_batch_out,
+                                              void *d_transcripts_out, void *stream) {
+    if (!c) return BPGPU_ERR_INVALID_ARG;
+    ipp_ts ts;
+    const int rca = ipp_ts_dev_args(c, shared_transcript, d_transcripts, d_transcripts_out, ts);
+    if (rca) return rca;
+    if (nbatch == 0) return BPGPU_OK;
+    const bool from_gens = !d_G && !d_F && !d_B;
+    if (!d_proofs || !d_verdict || !d_C || (n && !d_b) || (!from_gens && (!d_F || !d_B || (n && !d_G)))) return BPGPU_ERR_INVALID_ARG;
+    if (((uintptr_t)d_proofs | (uintptr_t)d_C | (uintptr_t)d_G | (uintptr_t)d_F | (uintptr_t)d_B | (uintptr_t)d_b) & 3)
+        return fail(c, BPGPU_ERR_INVALID_ARG, "device buffers must be 4-byte aligned");
+    std::lock_guard<std::mutex> lk(c->mu);
+    HIPCHK(c, hipSetDevice(c->device));
+    hipStream_t s = stream ? (hipStream_t)stream : c->stream;
+    int rc = ctx_enter(c, s);
+    if (rc) return rc;
+    rc = lin_rlc_dev_locked(c, n, nbatch, d_proofs, proof_len, nullptr, 0, nullptr, d_C, d_G, d_F, d_B, d_b, b_shared, d_weights64, (uint8_t *)d_verdict,
+                            (uint8_t *)d_batch_out, d_transcripts_out, s, &ts);
+    const int rc2 = ctx_leave(c, s);
+    return rc ? rc : rc2;
 }
 
 // ---- batch-combined InnerProductProof verification (ipp_rlc.h; an ADDITIONAL entry point, as bpgpu_linear_verify_rlc) ---------
@@ -4986,9 +5257,11 @@ static int ipp_rlc_gens_ok(bpgpu_ctx *c, size_t n, size_t gens_m) {
 static int ipp_rlc_dev_locked(bpgpu_ctx *c, size_t n, size_t nbatch, const void *d_proofs, size_t proof_len, const uint8_t *label,
                               size_t label_len, const uint8_t *shared_ts, const void *d_Gf, const void *d_Hf, const void *d_P, const void *d_Q,
                               const void *d_G, const void *d_H, size_t gens_m, const void *d_weights64, uint8_t *d_verdict, uint8_t *d_batch,
-                              hipStream_t s) {
+                              hipStream_t s, const ipp_ts *ts = nullptr) {
     if (nbatch > IPP_RLC_MAX_PROOFS) return fail(c, BPGPU_ERR_INVALID_ARG, "batch too large: more than 2^24 proofs in one combination");
-    if (shared_ts && !ts_state_ok(shared_ts)) return fail(c, BPGPU_ERR_INVALID_ARG, "malformed transcript state");
+    if (!ts && shared_ts && !ts_state_ok(shared_ts)) return fail(c, BPGPU_ERR_INVALID_ARG, "malformed transcript state");
+    rp_strobe_init init;
+    if (ts) ipp_ts_init(init, *ts);
     const bool fixed = d_G == nullptr && d_H == nullptr;
     if (fixed) {
         const int rcg = ipp_rlc_gens_ok(c, n, gens_m);
@@ -5008,6 +5281,8 @@ static int ipp_rlc_dev_locked(bpgpu_ctx *c, size_t n, size_t nbatch, const void 
     if (fmt) {   // every proof is a FormatError: the empty sum
         HIPCHK(c, hipMemsetAsync(d_verdict, BPGPU_VERDICT_FORMAT_ERROR, nbatch, s));
         if (d_batch) HIPCHK(c, hipMemsetAsync(d_batch, 0, 33, s));
+        if (ts && ts->d_out)
+            LAUNCH(c, s, "ipp_ts_input", k_ipp_ts_input, ((uint32_t)nbatch + 63) / 64, 64, (uint32_t)nbatch, init, (const uint32_t *)ts->d_in, ts->stride, (uint32_t *)ts->d_out);
         return BPGPU_OK;
     }
     const bool shape_bad = n != ((size_t)1 << k);   // ipp.rs:203-211
@@ -5042,13 +5317,15 @@ static int ipp_rlc_dev_locked(bpgpu_ctx *c, size_t n, size_t nbatch, const void 
     char *b = c->comb_buf, *d_csc = b + off_csc, *d_cpt = b + off_cpt, *d_acc = b + off_acc, *d_row = b + off_row, *d_rho = b + off_rho, *d_bo = b + off_bo;
     if (!d_batch) d_batch = (uint8_t *)d_bo;
     HIPCHK(c, hipMemsetAsync(d_stat, 0, sz_st + 2 * sz_u, s));
-    rp_strobe_init init;
-    {
+    if (ts) {
+        LAUNCH(c, s, "ipp_rlc_front_ts", k_ipp_vs_front_ts, (nb32 + RP_BLOCK - 1) / RP_BLOCK, RP_BLOCK, sh, init, (const uint8_t *)d_proofs, (const uint32_t *)ts->d_in,
+               ts->stride, (uint32_t *)d_us, (uint32_t *)d_ui, (uint32_t *)d_tab, (uint32_t *)ts->d_out, (uint32_t *)d_stat);
+    } else {
         uint8_t st0[BPGPU_TRANSCRIPT_BYTES];
         ipp_domain_sep_state(st0, label, label_len, shared_ts, n, &init);
+        LAUNCH(c, s, "ipp_rlc_front", k_ipp_vs_front, (nb32 + RP_BLOCK - 1) / RP_BLOCK, RP_BLOCK, sh, init, (const uint8_t *)d_proofs, (const uint32_t *)nullptr,
+               (uint32_t *)d_us, (uint32_t *)d_ui, (uint32_t *)d_tab, (uint32_t *)nullptr, (uint32_t *)d_stat);
     }
-    LAUNCH(c, s, "ipp_rlc_front", k_ipp_vs_front, (nb32 + RP_BLOCK - 1) / RP_BLOCK, RP_BLOCK, sh, init, (const uint8_t *)d_proofs, (const uint32_t *)nullptr,
-           (uint32_t *)d_us, (uint32_t *)d_ui, (uint32_t *)d_tab, (uint32_t *)nullptr, (uint32_t *)d_stat);
     if (shape_bad) {   // n != 2^k: every proof already carries its code and nothing enters R
         HIPCHK(c, hipMemsetAsync(d_mst, 0, sz_b + sz_o, s));
     } else {
@@ -5101,11 +5378,12 @@ extern "C" int bpgpu_ipp_verify_rlc_dev(bpgpu_ctx *c, size_t n, size_t nbatch, c
     return rc ? rc : rc2;
 }
 
-extern "C" int bpgpu_ipp_verify_rlc(bpgpu_ctx *c, size_t n, size_t nbatch, const uint8_t *proofs, size_t proof_len, const uint8_t *label,
-                                    size_t label_len, const uint8_t *shared_transcript, const uint8_t *G_factors, const uint8_t *H_factors,
-                                    const uint8_t *P, const uint8_t *Q, const uint8_t *G, const uint8_t *H, size_t gens_m, const uint8_t *weights64,
-                                    uint8_t *verdict, uint8_t *batch_out) {
-    if (!c || (label_len && !label)) return BPGPU_ERR_INVALID_ARG;
+// host pointers.  ts_host (with ts_stride 0 or BPGPU_TRANSCRIPT_BYTES): the callers' own transcripts, checked by the caller, in place of label /
+// shared_transcript, and ts_out_host (optional) what they are left as; the per-proof fallback starts again from the input states
+static int ipp_rlc_host_call(bpgpu_ctx *c, size_t n, size_t nbatch, const uint8_t *proofs, size_t proof_len, const uint8_t *label, size_t label_len,
+                             const uint8_t *shared_transcript, const uint8_t *ts_host, size_t ts_stride, const uint8_t *G_factors,
+                             const uint8_t *H_factors, const uint8_t *P, const uint8_t *Q, const uint8_t *G, const uint8_t *H, size_t gens_m,
+                             const uint8_t *weights64, uint8_t *verdict, uint8_t *batch_out, uint8_t *ts_out_host) {
     if (nbatch == 0) {
         if (batch_out) memset(batch_out, 0, 33);
         return BPGPU_OK;
@@ -5123,8 +5401,9 @@ extern "C" int bpgpu_ipp_verify_rlc(bpgpu_ctx *c, size_t n, size_t nbatch, const
     host_call<bpgpu_ctx> io(c, s);
     const size_t b_f = nbatch * n * 32 + 64, b_pq = nbatch * 32 + 64, b_g = n * 32 + 64;
     const int r_pr = io.in(nbatch * proof_len + 64), r_gf = io.in(b_f), r_hf = io.in(b_f), r_p = io.in(b_pq), r_q = io.in(b_pq),
-              r_g = io.in(from_gens ? 0 : b_g), r_h = io.in(from_gens ? 0 : b_g), r_w = io.in(weights64 ? nbatch * 64 : 0);
-    const int r_v = io.out(nbatch), r_bo = io.out(64);
+              r_g = io.in(from_gens ? 0 : b_g), r_h = io.in(from_gens ? 0 : b_g), r_w = io.in(weights64 ? nbatch * 64 : 0),
+              r_ti = io.in((!ts_host ? 0 : ts_stride ? nbatch : 1) * BPGPU_TRANSCRIPT_BYTES);
+    const int r_v = io.out(nbatch), r_bo = io.out(64), r_to = io.out(ts_out_host ? nbatch * BPGPU_TRANSCRIPT_BYTES : 0);
     const int r_gen = io.dev(from_gens ? 2 * n * 32 + 64 : 0);   // the generators' encodings, for the per-proof fallback
     int rc = io.open();
     if (rc) return rc;
@@ -5141,13 +5420,22 @@ extern "C" int bpgpu_ipp_verify_rlc(bpgpu_ctx *c, size_t n, size_t nbatch, const
     io.put(r_q, Q, nbatch * 32);
     if (weights64) io.put(r_w, weights64, nbatch * 64);
     const void *a_g = from_gens ? nullptr : io.d(r_g), *a_h = from_gens ? nullptr : io.d(r_h);
+    ipp_ts ts;
+    if (ts_host) {
+        io.put(r_ti, ts_host, (ts_stride ? nbatch : 1) * BPGPU_TRANSCRIPT_BYTES);
+        ts.d_in = io.d(r_ti);
+        ts.stride = ts_stride ? BP_TS_WORDS : 0;
+        ts.d_out = ts_out_host ? io.d(r_to) : nullptr;
+    }
     rc = io.upload();
     if (!rc)
         rc = ipp_rlc_dev_locked(c, n, nbatch, io.d(r_pr), proof_len, label, label_len, shared_transcript, io.d(r_gf), io.d(r_hf), io.d(r_p), io.d(r_q), a_g, a_h,
-                                gens_m, weights64 ? io.d(r_w) : nullptr, (uint8_t *)io.d(r_v), (uint8_t *)io.d(r_bo), s);
+                                gens_m, weights64 ? io.d(r_w) : nullptr, (uint8_t *)io.d(r_v), (uint8_t *)io.d(r_bo), s, ts_host ? &ts : nullptr);
     rc = io.finish(io.download(rc));
     if (rc) return rc;
     if (batch_out) memcpy(batch_out, io.h(r_bo), 33);   // (R as computed before any fallback)
+    if (ts_out_host) memcpy(ts_out_host, io.h(r_to), nbatch * BPGPU_TRANSCRIPT_BYTES);
+    ts.d_out = nullptr;   // (the fallback's transcripts are the ones already copied out)
     if ((uint8_t)io.h(r_bo)[0] != 0) {
         // R is not the identity, or a point of the combined MSM did not decode: the batch again through the per-proof path with the
         // bases given once (inputs are still on the device; in generator-table mode G(n / gens_m, gens_m), H(..) are gathered first)
@@ -5164,12 +5452,57 @@ extern "C" int bpgpu_ipp_verify_rlc(bpgpu_ctx *c, size_t n, size_t nbatch, const
                 f_g = f_h = io.d(r_gen);
             }
             return ipp_verify_dev_locked(c, n, nbatch, io.d(r_pr), proof_len, label, label_len, shared_transcript, io.d(r_gf), io.d(r_hf), io.d(r_p), io.d(r_q),
-                                         f_g, f_h, 1, io.d(r_v), nullptr, s);
+                                         f_g, f_h, 1, io.d(r_v), nullptr, s, ts_host ? &ts : nullptr);
         });
         if (rc) return rc;
     }
     memcpy(verdict, io.h(r_v), nbatch);
     return BPGPU_OK;
+}
+
+extern "C" int bpgpu_ipp_verify_rlc(bpgpu_ctx *c, size_t n, size_t nbatch, const uint8_t *proofs, size_t proof_len, const uint8_t *label,
+                                    size_t label_len, const uint8_t *shared_transcript, const uint8_t *G_factors, const uint8_t *H_factors,
+                                    const uint8_t *P, const uint8_t *Q, const uint8_t *G, const uint8_t *H, size_t gens_m, const uint8_t *weights64,
+                                    uint8_t *verdict, uint8_t *batch_out) {
+    if (!c || (label_len && !label)) return BPGPU_ERR_INVALID_ARG;
+    return ipp_rlc_host_call(c, n, nbatch, proofs, proof_len, label, label_len, shared_transcript, nullptr, 0, G_factors, H_factors, P, Q, G, H, gens_m, weights64,
+                             verdict, batch_out, nullptr);
+}
+
+// ---- the combined check on the callers' own transcripts (ipp.h: ipp_vs_front_lane<true>) ----
+extern "C" int bpgpu_ipp_verify_rlc_ts(bpgpu_ctx *c, size_t n, size_t nbatch, const uint8_t *proofs, size_t proof_len, const uint8_t *transcripts,
+                                       size_t transcript_stride, const uint8_t *G_factors, const uint8_t *H_factors, const uint8_t *P, const uint8_t *Q,
+                                       const uint8_t *G, const uint8_t *H, size_t gens_m, const uint8_t *weights64, uint8_t *verdict, uint8_t *batch_out,
+                                       uint8_t *transcripts_out) {
+    if (!c) return BPGPU_ERR_INVALID_ARG;
+    const int rca = ipp_ts_host_args(c, transcripts, transcript_stride, nbatch);
+    if (rca) return rca;
+    return ipp_rlc_host_call(c, n, nbatch, proofs, proof_len, nullptr, 0, nullptr, transcripts, transcript_stride, G_factors, H_factors, P, Q, G, H, gens_m,
+                             weights64, verdict, batch_out, transcripts_out);
+}
+
+extern "C" int bpgpu_ipp_verify_rlc_ts_dev(bpgpu_ctx *c, size_t n, size_t nbatch, const void *d_proofs, size_t proof_len, const uint8_t *shared_transcript,
+                                           const void *d_transcripts, const void *d_G_factors, const void *d_H_factors, const void *d_P, const void *d_Q,
+                                           const void *d_G, const void *d_H, size_t gens_m, const void *d_weights64, void *d_verdict, void *d_batch_out,
+                                           void *d_transcripts_out, void *stream) {
+    if (!c) return BPGPU_ERR_INVALID_ARG;
+    ipp_ts ts;
+    const int rca = ipp_ts_dev_args(c, shared_transcript, d_transcripts, d_transcripts_out, ts);
+    if (rca) return rca;
+    ts.d_out = d_transcripts_out;
+    if (nbatch == 0) return BPGPU_OK;
+    if (!d_proofs || !d_verdict || !d_P || !d_Q || (n && (!d_G_factors || !d_H_factors)) || (d_G == nullptr) != (d_H == nullptr)) return BPGPU_ERR_INVALID_ARG;
+    if (((uintptr_t)d_proofs | (uintptr_t)d_G_factors | (uintptr_t)d_H_factors | (uintptr_t)d_P | (uintptr_t)d_Q | (uintptr_t)d_G | (uintptr_t)d_H) & 3)
+        return fail(c, BPGPU_ERR_INVALID_ARG, "device buffers must be 4-byte aligned");
+    std::lock_guard<std::mutex> lk(c->mu);
+    HIPCHK(c, hipSetDevice(c->device));
+    hipStream_t s = stream ? (hipStream_t)stream : c->stream;
+    int rc = ctx_enter(c, s);
+    if (rc) return rc;
+    rc = ipp_rlc_dev_locked(c, n, nbatch, d_proofs, proof_len, nullptr, 0, nullptr, d_G_factors, d_H_factors, d_P, d_Q, d_G, d_H, gens_m, d_weights64,
+                            (uint8_t *)d_verdict, (uint8_t *)d_batch_out, s, &ts);
+    const int rc2 = ctx_leave(c, s);
+    return rc ? rc : rc2;
 }
 
 // ============================================================================

@@ -22,6 +22,18 @@ __global__ void __launch_bounds__(RP_BLOCK) k_linc_public(linc_shape sh, const u
     if (p < sh.nproofs) linc_public_thread(p, sh, st, C, b_in, G, F, B, r_in, rng, ts, r_out, draws, status);
 }
 
+// the same lane from the callers' own transcripts (before innerproduct_domain_sep(n)), the draws taken from one 32-byte seed per proof
+__global__ void __launch_bounds__(RP_BLOCK) k_linc_public_ts(linc_shape sh, const uint8_t *C, const uint8_t *b_in, const uint8_t *G, const uint8_t *F,
+                                                              const uint8_t *B, const uint8_t *r_in, const uint8_t *seeds, const uint32_t *ts_in,
+                                                              uint32_t ts_in_stride, uint32_t *ts, uint32_t *r_out, uint32_t *draws, uint32_t *status) {
+    __shared__ uint32_t lds[50 * RP_BLOCK];
+    const uint32_t p = blockIdx.x * RP_BLOCK + threadIdx.x;
+    kstate st;
+    st.w = lds + threadIdx.x;
+    st.stride = RP_BLOCK;
+    if (p < sh.nproofs) linc_public_lane<true>(p, sh, st, C, b_in, G, F, B, r_in, rpp_from_seed{seeds}, ts_in, ts_in_stride, ts, r_out, draws, status);
+}
+
 // blocks [0, n_q): the B and F terms (lane = proof: the two inner products)  ||  the G_t terms (lane = (proof, t))
 __global__ void __launch_bounds__(BP_BLOCK) k_linc_terms(uint32_t n_q, uint32_t nthreads, linc_shape sh, uint32_t j, const uint32_t *a, const uint32_t *b,
                                                           const uint32_t *wG, const uint32_t *draws, const uint8_t *G, const uint8_t *F, const uint8_t *B,

@@ -77,6 +77,11 @@ __global__ void k_rlc_finish(uint32_t nsplit, const ge_ext *hq, const ge_ext *pa
 __global__ void k_rp_verdict(uint32_t n, uint32_t *status, const uint8_t *msm_verdict, uint8_t *out);
 __global__ void k_ipp_prepare(ipp_shape sh, rp_strobe_init init, const uint8_t *proofs, const uint8_t *Gf, const uint8_t *Hf, const uint8_t *P, const uint8_t *Q, const uint8_t *G, const uint8_t *H, uint32_t *scalars, uint32_t *points, uint32_t *status);
 __global__ void k_ipp_vs_front(ipp_shape sh, rp_strobe_init init, const uint8_t *proofs, const uint32_t *ts_in, uint32_t *u_sq, uint32_t *u_inv_sq, uint32_t *tab, uint32_t *ts_out, uint32_t *status);
+// the callers' own transcripts (ipp.h: ipp_ts_start)
+__global__ void k_ipp_prepare_ts(ipp_shape sh, rp_strobe_init init, const uint8_t *proofs, const uint8_t *Gf, const uint8_t *Hf, const uint8_t *P, const uint8_t *Q, const uint8_t *G, const uint8_t *H, uint32_t *scalars, uint32_t *points, uint32_t *status, const uint32_t *ts_in, uint32_t ts_in_stride, uint32_t *ts_out);
+__global__ void k_ipp_vs_front_ts(ipp_shape sh, rp_strobe_init init, const uint8_t *proofs, const uint32_t *ts_in, uint32_t ts_in_stride, uint32_t *u_sq, uint32_t *u_inv_sq, uint32_t *tab, uint32_t *ts_out, uint32_t *status);
+__global__ void k_ipp_ts_input(uint32_t nproofs, rp_strobe_init init, const uint32_t *ts_in, uint32_t ts_in_stride, uint32_t *ts_out);
+__global__ void k_ipp_ts_fill(uint32_t nproofs, uint32_t n, const uint32_t *ts_in, uint32_t ts_in_stride, uint32_t *ts);
 __global__ void k_ipp_vs_s(uint32_t nthreads, ipp_shape sh, const uint32_t *tab, const uint32_t *status, uint32_t *s_out);
 __global__ void k_ipp_verdict(uint32_t n, const uint32_t *status, const uint8_t *msm_status, const uint32_t *msm_out, uint8_t *verdict);
 __global__ void k_aud_prepare(aud_shape sh, const uint32_t *party, const uint8_t *shares, const uint8_t *bit_commitments, const uint8_t *poly_commitments, const uint8_t *challenges, const uint32_t *gens, uint32_t *scalars, uint32_t *points, uint32_t *status);
@@ -114,6 +119,7 @@ __global__ void k_r1p_poly(uint32_t nthreads, r1p_shape sh, const uint32_t *col_
 __global__ void k_r1p_tsum(r1p_shape sh, uint32_t nrow, const uint32_t *terms, const uint32_t *rnd, uint32_t *fields, uint32_t *trows);
 __global__ void k_r1p_vecs(uint32_t nthreads, r1p_shape sh, const uint32_t *fields, const uint32_t *vecs, uint32_t *lv, uint32_t *rv, uint32_t *gf, uint32_t *hf);
 __global__ void k_lin_prepare(lin_shape sh, rp_strobe_init init, const uint8_t *proofs, const uint8_t *C, const uint8_t *bvec, const uint8_t *G, const uint8_t *F, const uint8_t *B, uint32_t *scalars, uint32_t *points, uint32_t *status, uint32_t *ts_out, uint32_t *gen_sc);
+__global__ void k_lin_prepare_ts(lin_shape sh, rp_strobe_init init, const uint8_t *proofs, const uint8_t *C, const uint8_t *bvec, const uint8_t *G, const uint8_t *F, const uint8_t *B, uint32_t *scalars, uint32_t *points, uint32_t *status, uint32_t *ts_out, uint32_t *gen_sc, const uint32_t *ts_in, uint32_t ts_in_stride, uint32_t ts_n);
 __global__ void k_from_uniform(uint32_t n, const uint32_t *uniform, uint32_t *out);
 
 // k_rlc.hip, bucket variant of the batch combination
@@ -162,6 +168,7 @@ __global__ void k_msm_tail(uint32_t nmsm, int have_bucket, const ge_ext *gS, con
 // k_linc.hip
 __global__ void k_linc_init(uint32_t nthreads, linc_shape sh, const uint8_t *a_in, const uint8_t *b_in, uint32_t *a, uint32_t *b, uint32_t *wG, uint32_t *status);
 __global__ void k_linc_public(linc_shape sh, const uint8_t *C, const uint8_t *b_in, const uint8_t *G, const uint8_t *F, const uint8_t *B, const uint8_t *r_in, const uint8_t *rng, uint32_t *ts, uint32_t *r_out, uint32_t *draws, uint32_t *status);
+__global__ void k_linc_public_ts(linc_shape sh, const uint8_t *C, const uint8_t *b_in, const uint8_t *G, const uint8_t *F, const uint8_t *B, const uint8_t *r_in, const uint8_t *seeds, const uint32_t *ts_in, uint32_t ts_in_stride, uint32_t *ts, uint32_t *r_out, uint32_t *draws, uint32_t *status);
 __global__ void k_linc_terms(uint32_t n_q, uint32_t nthreads, linc_shape sh, uint32_t j, const uint32_t *a, const uint32_t *b, const uint32_t *wG, const uint32_t *draws, const uint8_t *G, const uint8_t *F, const uint8_t *B, uint32_t *msm_sc, uint32_t *msm_pt);
 __global__ void k_linc_challenge(linc_shape sh, uint32_t j, const uint32_t *msm_out, const uint8_t *msm_status, uint32_t *ts, const uint32_t *draws, uint32_t *r_io, uint32_t *x, uint32_t *xinv, uint8_t *proofs, uint32_t proof_len, uint32_t *status);
 __global__ void k_linc_fold(uint32_t nthreads, linc_shape sh, uint32_t j, const uint32_t *x, const uint32_t *xinv, uint32_t *a, uint32_t *b, uint32_t *wG);

@@ -10,7 +10,7 @@
 // (one Montgomery product per s_i: times x_j or x_j^-1 for the bit that flips).
 #ifndef BPGPU_LINEAR_H
 #define BPGPU_LINEAR_H
-#include "rangeproof.h"
+#include "ipp.h"
 
 namespace bp {
 
@@ -29,9 +29,25 @@ struct lin_shape {
 // (r, a b_0, a s_0, ..) in the proof's row of gen_sc.
 // ts_out (optional): the transcript as verify() leaves it (after the x_star challenge) for proofs that reach the final
 // check; the start state for proofs rejected before that.
-BP_HD void lin_prepare_thread(uint32_t p, lin_shape sh, const rp_strobe_init &init, kstate st, const uint8_t *proofs, const uint8_t *C,
-                              const uint8_t *bvec, const uint8_t *G, const uint8_t *F, const uint8_t *B, uint32_t *scalars,
-                              uint32_t *points, uint32_t *status, uint32_t *ts_out = nullptr, uint32_t *gen_sc = nullptr) {
+// TS = false: every lane starts from `init`, the one state behind innerproduct_domain_sep(n).  TS = true: the callers' own states before
+// the separator (ipp_ts_start: ts_in + p ts_in_stride words, or `init`), which the lane applies for ts_n = the callers' n (sh.n is 0 when
+// n != 2^k); the start state a rejected proof gets back is then its own state behind the separator.
+template <bool TS>
+BP_HD void lin_ts_rejected(uint32_t p, const rp_strobe_init &init, kstate st, const uint32_t *ts_in, uint32_t ts_in_stride, uint32_t ts_n, uint32_t *ts_out) {
+    if (!ts_out) return;
+    if (TS) {
+        strobe t;
+        ipp_ts_start(t, st, p, init, ts_in, ts_in_stride, ts_n);
+        rp_ts_emit(p, st, rp_ts_meta(t.pos, t.pos_begin, t.cur_flags), ts_out);
+    } else {
+        rp_ts_passthrough(p, init, nullptr, ts_out);
+    }
+}
+template <bool TS>
+BP_HD void lin_prepare_lane(uint32_t p, lin_shape sh, const rp_strobe_init &init, kstate st, const uint8_t *proofs, const uint8_t *C,
+                            const uint8_t *bvec, const uint8_t *G, const uint8_t *F, const uint8_t *B, uint32_t *scalars,
+                            uint32_t *points, uint32_t *status, uint32_t *ts_out, uint32_t *gen_sc, const uint32_t *ts_in, uint32_t ts_in_stride,
+                            uint32_t ts_n) {
     const uint32_t n = sh.n, k = sh.k;
     const bool fx = gen_sc != nullptr;
     const uint32_t iC = fx ? 0u : 2u, iL = iC + 1, iR = iL + k, iS = fx ? 2 * k + 1 : 3 + 2 * k + n, iG = 3 + 2 * k;
@@ -43,21 +59,25 @@ BP_HD void lin_prepare_thread(uint32_t p, lin_shape sh, const rp_strobe_init &in
     load_words8(r.v, Sb + 64);
     if (!sc_is_canonical_sc(a) || !sc_is_canonical_sc(r)) {
         status[p] = BP_VERDICT_FORMAT;
-        rp_ts_passthrough(p, init, nullptr, ts_out);
+        lin_ts_rejected<TS>(p, init, st, ts_in, ts_in_stride, ts_n, ts_out);
         return;
     }
     if (sh.shape_verdict) {
         status[p] = sh.shape_verdict;
-        rp_ts_passthrough(p, init, nullptr, ts_out);
+        lin_ts_rejected<TS>(p, init, st, ts_in, ts_in_stride, ts_n, ts_out);
         return;
     }
     const uint8_t *bp_ = bvec + (sh.b_shared ? 0 : (uint64_t)p * n * 32);
     strobe t;
-    t.st = st;
-    for (uint32_t i = 0; i < 50; i++) ks_set32(st, i, init.w[i]);
-    t.pos = init.pos;
-    t.pos_begin = init.pos_begin;
-    t.cur_flags = init.cur_flags;
+    if (TS) {
+        ipp_ts_start(t, st, p, init, ts_in, ts_in_stride, ts_n);
+    } else {
+        t.st = st;
+        for (uint32_t i = 0; i < 50; i++) ks_set32(st, i, init.w[i]);
+        t.pos = init.pos;
+        t.pos_begin = init.pos_begin;
+        t.cur_flags = init.cur_flags;
+    }
     uint32_t *sc_out = scalars + (uint64_t)p * sh.N * 8, *pt_out = points + (uint64_t)p * sh.N * 8;
     const uint8_t lC[1] = {'C'}, lb[3] = {'b', '_', 'i'}, lG[3] = {'G', '_', 'i'}, lF[1] = {'F'}, lB[1] = {'B'}, lL[1] = {'L'}, lR[1] = {'R'},
                   lx[3] = {'x', '_', 'j'}, lS[1] = {'S'}, lxs[6] = {'x', '_', 's', 't', 'a', 'r'};
@@ -74,7 +94,7 @@ BP_HD void lin_prepare_thread(uint32_t p, lin_shape sh, const rp_strobe_init &in
     }
     if (fmt) {
         status[p] = BP_VERDICT_FORMAT;
-        rp_ts_passthrough(p, init, nullptr, ts_out);
+        lin_ts_rejected<TS>(p, init, st, ts_in, ts_in_stride, ts_n, ts_out);
         return;
     }
     for (uint32_t i = 0; i < n; i++) {
@@ -112,7 +132,7 @@ BP_HD void lin_prepare_thread(uint32_t p, lin_shape sh, const rp_strobe_init &in
     }
     if (verr) {
         status_raise(status + p, BP_VERDICT_VERIFICATION);
-        rp_ts_passthrough(p, init, nullptr, ts_out);
+        lin_ts_rejected<TS>(p, init, st, ts_in, ts_in_stride, ts_n, ts_out);
         return;
     }
     load_words8(w, Sb);
@@ -183,6 +203,11 @@ BP_HD void lin_prepare_thread(uint32_t p, lin_shape sh, const rp_strobe_init &in
         sc_neg(m1, one);
         store_words8(sc_out + iS * 8, m1);
     }
+}
+BP_HD void lin_prepare_thread(uint32_t p, lin_shape sh, const rp_strobe_init &init, kstate st, const uint8_t *proofs, const uint8_t *C,
+                              const uint8_t *bvec, const uint8_t *G, const uint8_t *F, const uint8_t *B, uint32_t *scalars,
+                              uint32_t *points, uint32_t *status, uint32_t *ts_out = nullptr, uint32_t *gen_sc = nullptr) {
+    lin_prepare_lane<false>(p, sh, init, st, proofs, C, bvec, G, F, B, scalars, points, status, ts_out, gen_sc, nullptr, 0, 0);
 }
 
 }  // namespace bp

@@ -16,7 +16,8 @@
 // which calls vartime_multiscalar_mul (:104, 112, 140).
 #ifndef BPGPU_LINEAR_PROVER_H
 #define BPGPU_LINEAR_PROVER_H
-#include "ipp_prover.h"
+#include "ipp.h"
+#include "rp_prover.h"
 
 namespace bp {
 
@@ -45,18 +46,24 @@ BP_HD void linc_init_thread(uint32_t tid, linc_shape sh, const uint8_t *a_in, co
 
 // lane = proof: the public inputs into the transcript (linear_proof.rs:73-83), the blinding r, and the 2k + 2 scalars the
 // reference draws with Scalar::random (s_j, t_j per round, then s_star, t_star: 64 bytes each, in that order).
-// ts[p]: the proof's transcript after innerproduct_domain_sep(n) on entry, advanced on exit.
-BP_HD void linc_public_thread(uint32_t p, linc_shape sh, kstate st, const uint8_t *C, const uint8_t *b_in, const uint8_t *G, const uint8_t *F,
-                              const uint8_t *B, const uint8_t *r_in, const uint8_t *rng, uint32_t *ts, uint32_t *r_out, uint32_t *draws,
-                              uint32_t *status) {
+// SEP = false: ts[p] holds the proof's transcript after innerproduct_domain_sep(n) on entry.  SEP = true: the lane starts from the caller's
+// own state at ts_in + p ts_in_stride words (stride 0: one state for every proof) and applies the separator (ipp_ts_start).  Either way
+// ts[p] is the advanced state on exit.
+// src: where the draws come from (rp_prover.h): the caller's 64 bytes per draw (rpp_from_bytes), or keystream block d of ChaCha20 under the
+// proof's 32-byte seed (rpp_from_seed) -- draw d = s_j (d = 2j), t_j (2j + 1), s_star (2k), t_star (2k + 1): linear_proof.rs:103-104, 146-147.
+template <bool SEP, class Src>
+BP_HD void linc_public_lane(uint32_t p, linc_shape sh, kstate st, const uint8_t *C, const uint8_t *b_in, const uint8_t *G, const uint8_t *F,
+                            const uint8_t *B, const uint8_t *r_in, const Src &src, const uint32_t *ts_in, uint32_t ts_in_stride, uint32_t *ts,
+                            uint32_t *r_out, uint32_t *draws, uint32_t *status) {
     const uint32_t n = sh.n, nd = 2 * sh.k + 2;
     uint32_t *tw = ts + (uint64_t)p * BP_TS_WORDS;
     strobe t;
-    t.st = st;
-    for (uint32_t i = 0; i < 50; i++) ks_set32(st, i, tw[i]);
-    t.pos = tw[50] & 0xffu;
-    t.pos_begin = (tw[50] >> 8) & 0xffu;
-    t.cur_flags = (tw[50] >> 16) & 0xffu;
+    if (SEP) {
+        const rp_strobe_init none{};
+        ipp_ts_start(t, st, p, none, ts_in, ts_in_stride, n);
+    } else {
+        rpp_ts_load(t, st, tw);
+    }
     const uint8_t lC[1] = {'C'}, lb[3] = {'b', '_', 'i'}, lG[3] = {'G', '_', 'i'}, lF[1] = {'F'}, lB[1] = {'B'};
     uint32_t w[8];
     load_words8(w, C + (uint64_t)p * 32);
@@ -81,15 +88,18 @@ BP_HD void linc_public_thread(uint32_t p, linc_shape sh, kstate st, const uint8_
     load_words8(r.v, r_in + (uint64_t)p * 32);
     if (!sc_is_canonical_sc(r)) status_raise(status + p, BP_STATUS_BAD_SCALAR);
     ippc_st(r_out + 8 * (uint64_t)p, r);
+    rpp_shape rs{};
+    rs.rng_per_proof = 64 * nd;
     for (uint32_t d = 0; d < nd; d++) {
-        uint32_t wide[16];
-        const uint8_t *src = rng + ((uint64_t)p * nd + d) * 64;
-        load_words8(wide, src);
-        load_words8(wide + 8, src + 32);
         sc x;
-        sc_from_wide(x, wide);
+        src.draw(x, rs, p, d);
         ippc_st(draws + 8 * ((uint64_t)p * nd + d), x);
     }
+}
+BP_HD void linc_public_thread(uint32_t p, linc_shape sh, kstate st, const uint8_t *C, const uint8_t *b_in, const uint8_t *G, const uint8_t *F,
+                              const uint8_t *B, const uint8_t *r_in, const uint8_t *rng, uint32_t *ts, uint32_t *r_out, uint32_t *draws,
+                              uint32_t *status) {
+    linc_public_lane<false>(p, sh, st, C, b_in, G, F, B, r_in, rpp_from_bytes{rng}, nullptr, 0, ts, r_out, draws, status);
 }
 
 // lane = (proof p, index t), round j: the G_t term of L (MSM 2p) or R (MSM 2p + 1); each MSM has n/2 + 2 terms:

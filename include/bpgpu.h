@@ -411,8 +411,8 @@ int bpgpu_ipp_verify_batch_dev(bpgpu_ctx *ctx, size_t n, size_t nbatch, const vo
  *               before any fallback, or zeros when a point (a shared G_i / H_i included) did not decode
  * A proof_len that is no InnerProductProof length gives FormatError for every proof (and batch_out = zeros); nbatch = 0 is BPGPU_OK.
  * One call takes at most 2^24 proofs and 2^24 proof-specific points (nbatch (2 lg(n) + 2)); larger calls return
- * BPGPU_ERR_INVALID_ARG.  There are no per-proof transcripts and no transcripts_out: the per-proof call that defines the verdicts has
- * neither.
+ * BPGPU_ERR_INVALID_ARG.  This call has no per-proof transcripts and no transcripts_out (the per-proof call that defines its verdicts
+ * has neither): bpgpu_ipp_verify_rlc_ts below has both.
  * The transcript replay stays per proof (k_ipp_vs_front: one lane per proof, serial over lg(n) rounds and one inversion) and sets the
  * floor of the call, 0.19 ... 0.31 ms; what the combination saves is the per-proof staging, the decodes of G, H per proof and the
  * per-proof multiscalar multiplications.  Measured on one MI355X (profiles/ipp_rlc_rate.json, n = 64 ... 1 024 against
@@ -505,6 +505,81 @@ int bpgpu_linear_verify_rlc_dev(bpgpu_ctx *ctx, size_t n, size_t nbatch, const v
                                 const void *d_C, const void *d_G, const void *d_F, const void *d_B,
                                 const void *d_b, int b_shared, const void *d_weights64,
                                 void *d_verdict, void *d_batch_out, void *d_transcripts_out, void *stream);
+
+/* ---- inner-product and linear proofs on the callers' OWN transcripts ---------------------------------------------------------
+ * InnerProductProof and LinearProof are sub-protocols: a protocol that embeds one has bound its own Merlin transcript (label, session
+ * id, earlier messages) before it calls create / verify, and that transcript differs from proof to proof.  The _ts entry points are
+ * the calls above with `label, label_len, shared_transcript` replaced by the convention of bpgpu_rangeproof_verify_batch_ts /
+ * bpgpu_rangeproof_prove_batch_ts; every other argument, error and shortcut is the sibling's.
+ *   transcripts       : REQUIRED.  transcript_stride = 0: ONE 208-byte state, every proof starts from it;
+ *                       transcript_stride = BPGPU_TRANSCRIPT_BYTES: nbatch states, one per proof.  The states are the callers' states
+ *                       BEFORE innerproduct_domain_sep(n) (transcript.rs:50-53), at any STROBE position: the separator is applied per
+ *                       proof on the device, byte by byte, also where it crosses the 166-byte rate boundary in its middle.
+ *                       transcripts == NULL, any other stride or a malformed state (position bytes out of range) return
+ *                       BPGPU_ERR_INVALID_ARG before anything is staged, the outputs untouched.  nbatch = 0 is BPGPU_OK.
+ *   transcripts_out   : optional nbatch x 208 bytes.
+ *       linear        : as bpgpu_linear_verify_batch documents them for shared_transcript = the proof's own state.
+ *       inner product : what verification_scalars leaves in the caller's `&mut Transcript` (ipp.rs:203-222, transcript.rs:75-87): the
+ *                       INPUT state for a proof that from_bytes or n != 2^lg_n rejects (the reference returns before the separator);
+ *                       for an identity L_j / R_j the state as of that message -- separator and earlier rounds absorbed, nothing of
+ *                       the identity point; the state after the last u challenge otherwise.
+ *   _dev forms        : as bpgpu_rangeproof_verify_batch_ts_dev -- exactly one of shared_transcript (host, one state) and
+ *                       d_transcripts (device, nbatch states, 4-byte aligned) is given; work is enqueued on `stream` (NULL: the
+ *                       context's own).  Device states cannot be checked by the host: one whose position bytes are out of range is
+ *                       started at position 0.  The _dev combined checks mark undecided verdicts BPGPU_VERDICT_UNDECIDED.
+ * Contracts (tests/test_gpu_ipp_linear_ts.py):
+ *   per proof     : every output of row p -- verdict / status, msm_out, proof bytes, transcripts_out -- equals the sibling called with
+ *                   nbatch = 1 and shared_transcript = transcripts[p];
+ *   shared state  : with transcript_stride = 0 the outputs equal the sibling's on the whole batch with that shared_transcript, byte
+ *                   for byte (batch_out of the combined checks included, for equal weights64);
+ *   combined      : verdict and transcripts_out of an _rlc_ts call ALWAYS equal those of the _verify_batch_ts call on the same inputs,
+ *                   also with a failing proof in the batch and for proofs stopped in the front end.  The host forms' per-proof
+ *                   fallback starts again from the callers' input states.
+ * bpgpu_ipp_verify_batch_ts takes bases_shared like the _dev form (bpgpu_ipp_verify_batch does not): != 0, G and H hold n x 32 bytes.
+ * The front ends do the work of their siblings plus one 208-byte load and the separator (at most two permutations) per proof.  Measured on
+ * one MI355X (profiles/ipp_linear_ts_rate.json; 4 096 proofs, generator tables, blocking calls alternating, median): one state
+ * per proof against one shared state 2.23 / 2.15 ms (n = 64) and 17.88 / 17.45 ms (n = 1 024) for bpgpu_linear_verify_batch_ts, 2.52 / 2.46
+ * and 17.35 / 17.47 ms for bpgpu_ipp_verify_rlc_ts; the _dev forms 2.03 / 1.98, 17.51 / 17.12, 1.68 / 1.68 and 2.68 / 2.64 ms -- ratios of
+ * 0.99 ... 1.04, each form's calls within 0.5 ... 4.3 % of its median (the host inner-product call at n = 1 024, which stages 268 MB: 9 ... 34 %). */
+int bpgpu_ipp_verify_batch_ts(bpgpu_ctx *ctx, size_t n, size_t nbatch, const uint8_t *proofs, size_t proof_len,
+                              const uint8_t *transcripts, size_t transcript_stride,
+                              const uint8_t *G_factors, const uint8_t *H_factors, const uint8_t *P, const uint8_t *Q,
+                              const uint8_t *G, const uint8_t *H, int bases_shared,
+                              uint8_t *verdict, uint8_t *msm_out, uint8_t *transcripts_out);
+int bpgpu_ipp_verify_batch_ts_dev(bpgpu_ctx *ctx, size_t n, size_t nbatch, const void *d_proofs, size_t proof_len,
+                                  const uint8_t *shared_transcript, const void *d_transcripts,
+                                  const void *d_G_factors, const void *d_H_factors, const void *d_P, const void *d_Q,
+                                  const void *d_G, const void *d_H, int bases_shared,
+                                  void *d_verdict, void *d_msm_out, void *d_transcripts_out, void *stream);
+int bpgpu_ipp_verify_rlc_ts(bpgpu_ctx *ctx, size_t n, size_t nbatch, const uint8_t *proofs, size_t proof_len,
+                            const uint8_t *transcripts, size_t transcript_stride,
+                            const uint8_t *G_factors, const uint8_t *H_factors, const uint8_t *P, const uint8_t *Q,
+                            const uint8_t *G, const uint8_t *H, size_t gens_m, const uint8_t *weights64,
+                            uint8_t *verdict, uint8_t *batch_out, uint8_t *transcripts_out);
+int bpgpu_ipp_verify_rlc_ts_dev(bpgpu_ctx *ctx, size_t n, size_t nbatch, const void *d_proofs, size_t proof_len,
+                                const uint8_t *shared_transcript, const void *d_transcripts,
+                                const void *d_G_factors, const void *d_H_factors, const void *d_P, const void *d_Q,
+                                const void *d_G, const void *d_H, size_t gens_m, const void *d_weights64,
+                                void *d_verdict, void *d_batch_out, void *d_transcripts_out, void *stream);
+int bpgpu_linear_verify_batch_ts(bpgpu_ctx *ctx, size_t n, size_t nbatch, const uint8_t *proofs, size_t proof_len,
+                                 const uint8_t *transcripts, size_t transcript_stride,
+                                 const uint8_t *C, const uint8_t *G, const uint8_t *F, const uint8_t *B,
+                                 const uint8_t *b, int b_shared, uint8_t *verdict, uint8_t *msm_out, uint8_t *transcripts_out);
+int bpgpu_linear_verify_batch_ts_dev(bpgpu_ctx *ctx, size_t n, size_t nbatch, const void *d_proofs, size_t proof_len,
+                                     const uint8_t *shared_transcript, const void *d_transcripts,
+                                     const void *d_C, const void *d_G, const void *d_F, const void *d_B,
+                                     const void *d_b, int b_shared, void *d_verdict, void *d_msm_out, void *d_transcripts_out,
+                                     void *stream);
+int bpgpu_linear_verify_rlc_ts(bpgpu_ctx *ctx, size_t n, size_t nbatch, const uint8_t *proofs, size_t proof_len,
+                               const uint8_t *transcripts, size_t transcript_stride,
+                               const uint8_t *C, const uint8_t *G, const uint8_t *F, const uint8_t *B,
+                               const uint8_t *b, int b_shared, const uint8_t *weights64,
+                               uint8_t *verdict, uint8_t *batch_out, uint8_t *transcripts_out);
+int bpgpu_linear_verify_rlc_ts_dev(bpgpu_ctx *ctx, size_t n, size_t nbatch, const void *d_proofs, size_t proof_len,
+                                   const uint8_t *shared_transcript, const void *d_transcripts,
+                                   const void *d_C, const void *d_G, const void *d_F, const void *d_B,
+                                   const void *d_b, int b_shared, const void *d_weights64,
+                                   void *d_verdict, void *d_batch_out, void *d_transcripts_out, void *stream);
 
 /* ---- R1CS constraint-system proofs (r1cs::Verifier::verify, src/r1cs/verifier.rs:329-500) ----------------------------
  * The reference's verifier re-runs a gadget (closures) against its constraint system.  On the verifier side only
@@ -704,6 +779,30 @@ int bpgpu_ipp_create_batch(bpgpu_ctx *ctx, size_t n, size_t nbatch, const uint8_
                            const uint8_t *shared_transcript, const uint8_t *Q, const uint8_t *G_factors,
                            const uint8_t *H_factors, const uint8_t *G, const uint8_t *H, int bases_shared,
                            const uint8_t *a, const uint8_t *b, uint8_t *proofs_out, uint8_t *status);
+
+/* ---- creation on the callers' own transcripts ------------------------------------------------------------------------------
+ * bpgpu_ipp_create_batch / bpgpu_linear_create_batch with `label, label_len, shared_transcript` replaced by `transcripts,
+ * transcript_stride` -- the convention, errors and contracts of the _ts verifiers above (bpgpu_ipp_verify_batch_ts): the callers' states
+ * before innerproduct_domain_sep(n), which the device applies per proof; every output of row p equals the sibling's with nbatch = 1
+ * and shared_transcript = transcripts[p], and with transcript_stride = 0 the sibling's on the whole batch.
+ *   transcripts_out : optional nbatch x 208 bytes: each proof's state as create() leaves it (inner product: after the last u
+ *                     challenge; linear: after x_star) -- the state the matching _ts verifier leaves for the proof.
+ * bpgpu_linear_create_batch_ts takes its randomness as ONE seed per proof:
+ *   rng32 : nbatch x 32 bytes; the rng handed to create() is ChaChaRng::from_seed(rng32[p]) (rand_chacha: ChaCha20, 64-bit block
+ *           counter, stream id 0).  Draw d is Scalar::from_bytes_mod_order_wide(keystream block d), in the reference's order
+ *           (linear_proof.rs:103-104, 146-147): s_j = draw 2j, t_j = draw 2j + 1, s_star = draw 2 lg n, t_star = draw 2 lg n + 1 --
+ *           the proof bpgpu_linear_create_batch makes from rng = keystream blocks 0 .. 2 lg n + 1 of the seed.  The draws are computed
+ *           on the device by the lane that fills the chain's working set; no buffer of draws exists in the caller's memory or in
+ *           staging.  NULL: 32 bytes per proof from the OS CSPRNG.  The seeds are secrets: they sit in the secret part of the staging
+ *           block and are cleared with the working set on every exit, error paths included. */
+int bpgpu_ipp_create_batch_ts(bpgpu_ctx *ctx, size_t n, size_t nbatch, const uint8_t *transcripts, size_t transcript_stride,
+                              const uint8_t *Q, const uint8_t *G_factors, const uint8_t *H_factors, const uint8_t *G,
+                              const uint8_t *H, int bases_shared, const uint8_t *a, const uint8_t *b, uint8_t *proofs_out,
+                              uint8_t *status, uint8_t *transcripts_out);
+int bpgpu_linear_create_batch_ts(bpgpu_ctx *ctx, size_t n, size_t nbatch, const uint8_t *transcripts, size_t transcript_stride,
+                                 const uint8_t *rng32, const uint8_t *C, const uint8_t *r, const uint8_t *a, const uint8_t *b,
+                                 int b_shared, const uint8_t *G, const uint8_t *F, const uint8_t *B, uint8_t *proofs_out,
+                                 uint8_t *status_out, uint8_t *transcripts_out);
 
 /* ---- batched range-proof creation (prover side) ------------------------------------------
  * nbatch independent calls of

@@ -517,7 +517,89 @@ class LinearProof {
         return out;
     }
 
+    // ---- one Transcript per proof (bpgpu_linear_*_ts): each proof runs on its caller's own transcript, bound to whatever session it
+    // belongs to, and every transcript is left as create() / verify() leaves it (after an Err: right after innerproduct_domain_sep(n))
+    static std::vector<Status> verify_batch(bpgpu_ctx *ctx, std::vector<Transcript> &transcripts, const std::vector<LinearProof> &proofs,
+                                            const std::vector<CompressedRistretto> &Cs, const std::vector<CompressedRistretto> &G,
+                                            const CompressedRistretto &F, const CompressedRistretto &B,
+                                            const std::vector<std::vector<ScalarBytes>> &b_vecs) {
+        return verify_ts(ctx, transcripts, proofs, Cs, G, F, B, b_vecs, false, nullptr);
+    }
+    static std::vector<Status> verify_batch_combined(bpgpu_ctx *ctx, std::vector<Transcript> &transcripts, const std::vector<LinearProof> &proofs,
+                                                     const std::vector<CompressedRistretto> &Cs, const std::vector<CompressedRistretto> &G,
+                                                     const CompressedRistretto &F, const CompressedRistretto &B,
+                                                     const std::vector<std::vector<ScalarBytes>> &b_vecs, const uint8_t *weights64 = nullptr) {
+        return verify_ts(ctx, transcripts, proofs, Cs, G, F, B, b_vecs, true, weights64);
+    }
+    // transcripts.size() proofs in one GPU pass (no counterpart in the crate).  rng_seed32: 32 bytes per proof, proof i's rng being
+    // ChaChaRng::from_seed(rng_seed32 + 32 i), its scalars drawn on the device (nullptr: the library draws the seeds).
+    static std::vector<LinearProof> create_batch(bpgpu_ctx *ctx, std::vector<Transcript> &transcripts, const std::vector<CompressedRistretto> &Cs,
+                                                 const std::vector<ScalarBytes> &rs, const std::vector<std::vector<ScalarBytes>> &a_vecs,
+                                                 const std::vector<std::vector<ScalarBytes>> &b_vecs, const std::vector<CompressedRistretto> &G,
+                                                 const CompressedRistretto &F, const CompressedRistretto &B, const uint8_t *rng_seed32 = nullptr) {
+        const size_t nb = transcripts.size(), n = G.size();
+        std::vector<LinearProof> out;
+        if (nb == 0) return out;
+        if (Cs.size() != nb || rs.size() != nb || a_vecs.size() != nb || b_vecs.size() != nb)
+            throw std::invalid_argument("one commitment, blinding, secret and public vector per proof");
+        if (n == 0 || (n & (n - 1))) throw std::invalid_argument("InvalidInputLength");
+        size_t lg = 0;
+        while ((size_t(1) << lg) < n) lg++;
+        const size_t pl = 32 * (2 * lg + 3);
+        std::vector<uint8_t> ts, cb, rb, ab, bb, pb(nb * pl), status(nb), tso(nb * BPGPU_TRANSCRIPT_BYTES);
+        for (size_t i = 0; i < nb; i++) {
+            if (a_vecs[i].size() != n || b_vecs[i].size() != n) throw std::invalid_argument("InvalidInputLength");
+            ts.insert(ts.end(), transcripts[i].state().begin(), transcripts[i].state().end());
+            cb.insert(cb.end(), Cs[i].begin(), Cs[i].end());
+            rb.insert(rb.end(), rs[i].begin(), rs[i].end());
+            for (const auto &x : a_vecs[i]) ab.insert(ab.end(), x.begin(), x.end());
+            for (const auto &x : b_vecs[i]) bb.insert(bb.end(), x.begin(), x.end());
+        }
+        const int rc = bpgpu_linear_create_batch_ts(ctx, n, nb, ts.data(), BPGPU_TRANSCRIPT_BYTES, rng_seed32, cb.data(), rb.data(), ab.data(), bb.data(), 0,
+                                                    G[0].data(), F.data(), B.data(), pb.data(), status.data(), tso.data());
+        if (rc != BPGPU_OK) throw GpuError(bpgpu_last_error(ctx));
+        for (uint8_t s : status)
+            if (s != 0) throw std::invalid_argument("an input point does not decode or a scalar is not canonical");
+        for (size_t i = 0; i < nb; i++) {
+            std::memcpy(transcripts[i].state_mut().data(), &tso[i * BPGPU_TRANSCRIPT_BYTES], BPGPU_TRANSCRIPT_BYTES);
+            LinearProof p;
+            p.bytes_.assign(pb.begin() + i * pl, pb.begin() + (i + 1) * pl);
+            out.push_back(std::move(p));
+        }
+        return out;
+    }
+
   private:
+    static std::vector<Status> verify_ts(bpgpu_ctx *ctx, std::vector<Transcript> &transcripts, const std::vector<LinearProof> &proofs,
+                                         const std::vector<CompressedRistretto> &Cs, const std::vector<CompressedRistretto> &G,
+                                         const CompressedRistretto &F, const CompressedRistretto &B,
+                                         const std::vector<std::vector<ScalarBytes>> &b_vecs, bool combined, const uint8_t *weights64) {
+        const size_t nb = proofs.size(), n = G.size();
+        std::vector<Status> out;
+        if (nb == 0) return out;
+        if (transcripts.size() != nb || Cs.size() != nb || b_vecs.size() != nb)
+            throw std::invalid_argument("one transcript, one commitment and one public vector per proof");
+        const size_t pl = proofs[0].bytes_.size();
+        std::vector<uint8_t> ts, pb, cb, bb, verdict(nb), tso(nb * BPGPU_TRANSCRIPT_BYTES);
+        for (size_t i = 0; i < nb; i++) {
+            if (proofs[i].bytes_.size() != pl || b_vecs[i].size() != n) throw std::invalid_argument("proofs of a batch must have one size");
+            ts.insert(ts.end(), transcripts[i].state().begin(), transcripts[i].state().end());
+            pb.insert(pb.end(), proofs[i].bytes_.begin(), proofs[i].bytes_.end());
+            cb.insert(cb.end(), Cs[i].begin(), Cs[i].end());
+            for (const auto &x : b_vecs[i]) bb.insert(bb.end(), x.begin(), x.end());
+        }
+        const uint8_t *g = n ? G[0].data() : nullptr, *b = n ? bb.data() : nullptr;
+        const int rc = combined ? bpgpu_linear_verify_rlc_ts(ctx, n, nb, pb.data(), pl, ts.data(), BPGPU_TRANSCRIPT_BYTES, cb.data(), g, F.data(), B.data(), b, 0,
+                                                             weights64, verdict.data(), nullptr, tso.data())
+                                : bpgpu_linear_verify_batch_ts(ctx, n, nb, pb.data(), pl, ts.data(), BPGPU_TRANSCRIPT_BYTES, cb.data(), g, F.data(), B.data(), b, 0,
+                                                               verdict.data(), nullptr, tso.data());
+        if (rc != BPGPU_OK) throw GpuError(bpgpu_last_error(ctx));
+        for (size_t i = 0; i < nb; i++) {
+            std::memcpy(transcripts[i].state_mut().data(), &tso[i * BPGPU_TRANSCRIPT_BYTES], BPGPU_TRANSCRIPT_BYTES);
+            out.push_back(verdict[i] == 0 ? Status::Ok() : Status::Err(static_cast<ProofError>(verdict[i])));
+        }
+        return out;
+    }
     std::vector<uint8_t> bytes_;
 };
 
