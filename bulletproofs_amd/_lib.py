@@ -15,6 +15,7 @@ EXPORTS = [
     "bpgpu_r1cs_circuit_create", "bpgpu_r1cs_circuit_destroy", "bpgpu_r1cs_circuit_shape", "bpgpu_r1cs_verify_batch_ts",
     "bpgpu_r1cs_verify_batch_ts_dev", "bpgpu_pool_r1cs_verify_ts", "bpgpu_r1cs_witness_create", "bpgpu_r1cs_witness_destroy",
     "bpgpu_r1cs_prove_batch", "bpgpu_r1cs_verify_rlc", "bpgpu_pool_r1cs_verify_rlc",
+    "bpgpu_r1cs_witness_check", "bpgpu_r1cs_prove_batch_checked",
     "bpgpu_version", "bpgpu_ctx_create", "bpgpu_ctx_destroy", "bpgpu_last_error", "bpgpu_ctx_set_option",
     "bpgpu_ctx_get_option",
     "bpgpu_synchronize", "bpgpu_gens_create", "bpgpu_gens_load", "bpgpu_gens_export",

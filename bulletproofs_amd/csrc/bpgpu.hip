@@ -4606,6 +4606,11 @@ struct bpgpu_r1cs_circuit {
     size_t off_ents = 0, off_lbl_off = 0, off_lbl = 0, dev_bytes = 0;
     std::mutex mu;
     std::map<int, char *> dev;       // device ordinal -> [col_ptr][ents][lbl_off][lbl]
+    // the row form of the witness check (r1cs_check.h): built at the first check, uploaded to a device at the first check there
+    bool rows_built = false;
+    r1c_rows rows;
+    size_t off_rterms = 0, off_rlongs = 0, rows_bytes = 0;
+    std::map<int, char *> dev_rows;  // device ordinal -> [units][terms][longs]
 };
 
 extern "C" int bpgpu_r1cs_circuit_create(size_t m, size_t n1, size_t n2, int two_phase, size_t n_challenges, const uint8_t *labels,
@@ -4672,6 +4677,10 @@ extern "C" void bpgpu_r1cs_circuit_destroy(bpgpu_r1cs_circuit *ci) {
         (void)hipSetDevice(kv.first);
         (void)hipFree(kv.second);
     }
+    for (auto &kv : ci->dev_rows) {
+        (void)hipSetDevice(kv.first);
+        (void)hipFree(kv.second);
+    }
     delete ci;
 }
 
@@ -4703,6 +4712,37 @@ static int r1cs_circuit_on(bpgpu_ctx *c, const bpgpu_r1cs_circuit *cci, char **d
         return fail(c, BPGPU_ERR_HIP, "circuit upload failed");
     }
     ci->dev[c->device] = d;
+    *d_out = d;
+    return BPGPU_OK;
+}
+
+// the circuit's row form on c's device (r1cs_check.h; the caller holds c->mu and has set the device)
+static int r1cs_rows_on(bpgpu_ctx *c, const bpgpu_r1cs_circuit *cci, char **d_out) {
+    auto *ci = const_cast<bpgpu_r1cs_circuit *>(cci);
+    std::lock_guard<std::mutex> lk(ci->mu);
+    if (!ci->rows_built) {
+        r1c_build_rows(ci->m, ci->n, ci->Q, ci->col_ptr, ci->ents, ci->rows);
+        ci->off_rterms = align_up(ci->rows.units.size() * sizeof(r1c_unit) + 4);
+        ci->off_rlongs = ci->off_rterms + align_up(ci->rows.terms.size() * sizeof(r1p_term) + 4);
+        ci->rows_bytes = ci->off_rlongs + align_up(ci->rows.longs.size() * sizeof(r1c_long) + 4);
+        ci->rows_built = true;
+    }
+    auto it = ci->dev_rows.find(c->device);
+    if (it != ci->dev_rows.end()) {
+        *d_out = it->second;
+        return BPGPU_OK;
+    }
+    std::vector<char> img(ci->rows_bytes, 0);
+    if (!ci->rows.units.empty()) memcpy(img.data(), ci->rows.units.data(), ci->rows.units.size() * sizeof(r1c_unit));
+    if (!ci->rows.terms.empty()) memcpy(img.data() + ci->off_rterms, ci->rows.terms.data(), ci->rows.terms.size() * sizeof(r1p_term));
+    if (!ci->rows.longs.empty()) memcpy(img.data() + ci->off_rlongs, ci->rows.longs.data(), ci->rows.longs.size() * sizeof(r1c_long));
+    char *d = nullptr;
+    if (hipMalloc((void **)&d, ci->rows_bytes) != hipSuccess) return fail(c, BPGPU_ERR_HIP, "out of device memory (circuit rows)");
+    if (hipMemcpy(d, img.data(), ci->rows_bytes, hipMemcpyHostToDevice) != hipSuccess) {
+        (void)hipFree(d);
+        return fail(c, BPGPU_ERR_HIP, "circuit row upload failed");
+    }
+    ci->dev_rows[c->device] = d;
     *d_out = d;
     return BPGPU_OK;
 }
@@ -5624,11 +5664,36 @@ static int r1cs_witness_on(bpgpu_ctx *c, const bpgpu_r1cs_witness *cw, char **d_
     return BPGPU_OK;
 }
 
-extern "C" int bpgpu_r1cs_prove_batch(bpgpu_ctx *c, const bpgpu_r1cs_circuit *ci, const bpgpu_r1cs_witness *wi, size_t nbatch, const uint8_t *v,
-                                      const uint8_t *v_blinding, const uint8_t *free_inputs, const uint8_t *transcripts, size_t transcript_stride,
-                                      const uint8_t *rng32, uint8_t *proofs_out, size_t proof_stride, uint32_t *proof_lens_out, uint8_t *commitments_out,
-                                      uint8_t *status_out, uint8_t *transcripts_out) {
-    if (!c || !ci || !wi) return BPGPU_ERR_INVALID_ARG;
+// The witness check's launches over one batch (r1cs_check.h): a_L, a_R, a_O in aw, the challenges in fields and v on the device, as the
+// prover's witness launches take and leave them.  first is pre-set to R1C_SATISFIED, count and map (optional) are zeroed; partial holds
+// rows.nslots x per x 32 bytes.  The batch goes in slices of `per` proofs (r1c_slice).
+static void r1cs_check_launch_locked(bpgpu_ctx *c, const bpgpu_r1cs_circuit *ci, const char *drows, const r1p_shape &sh, size_t nbatch, size_t per,
+                                     const uint8_t *d_v, const uint32_t *aw, const uint32_t *fields, const uint32_t *d_stat, uint32_t mapw, uint32_t *partial,
+                                     uint32_t *d_first, uint32_t *d_count, uint32_t *d_map, hipStream_t s) {
+    const r1c_rows &rw = ci->rows;
+    const r1c_unit *units = (const r1c_unit *)drows;
+    const r1p_term *rterms = (const r1p_term *)(drows + ci->off_rterms);
+    const r1c_long *longs = (const r1c_long *)(drows + ci->off_rlongs);
+    if (rw.units.empty()) return;
+    for (size_t p0 = 0; p0 < nbatch; p0 += per) {
+        const uint32_t cnt = (uint32_t)std::min(per, nbatch - p0), nt = (uint32_t)(rw.units.size() * cnt);
+        LAUNCH(c, s, "r1c_units", k_r1c_units, (nt + 63) / 64, 64, nt, sh, (uint32_t)p0, cnt, units, rterms, aw, d_v, fields, d_stat, mapw, partial, d_first,
+               d_count, d_map);
+        if (!rw.longs.empty()) {   // (circuits with rows of more than R1C_CHUNK terms only)
+            const uint32_t nl = (uint32_t)(rw.longs.size() * cnt);
+            LAUNCH(c, s, "r1c_long", k_r1c_long, (nl + 63) / 64, 64, nl, (uint32_t)p0, cnt, longs, (const uint32_t *)partial, d_stat, mapw, d_first, d_count,
+                   d_map);
+        }
+    }
+}
+
+// bpgpu_r1cs_prove_batch and bpgpu_r1cs_prove_batch_checked: one launch chain, the check (on the proof's own phase-2 challenges, between
+// the last witness launch and r1p_poly) on or off
+static int r1cs_prove_impl(bpgpu_ctx *c, const bpgpu_r1cs_circuit *ci, const bpgpu_r1cs_witness *wi, size_t nbatch, const uint8_t *v,
+                           const uint8_t *v_blinding, const uint8_t *free_inputs, const uint8_t *transcripts, size_t transcript_stride,
+                           const uint8_t *rng32, uint8_t *proofs_out, size_t proof_stride, uint32_t *proof_lens_out, uint8_t *commitments_out,
+                           uint8_t *status_out, uint8_t *transcripts_out, bool check, uint32_t *unsat_first_out) {
+    if (!c || !ci || !wi || (check && !unsat_first_out)) return BPGPU_ERR_INVALID_ARG;
     if (wi->m != ci->m || wi->n1 != ci->n1 || wi->n != ci->n || wi->nch != ci->nch) return fail(c, BPGPU_ERR_INVALID_ARG, "witness program of another circuit");
     if (nbatch == 0) return BPGPU_OK;
     const size_t TS = BPGPU_TRANSCRIPT_BYTES, m = ci->m, n = ci->n, n1 = ci->n1, n2 = n - n1, pn = ci->pn, k = ci->k, nf = wi->nfree;
@@ -5676,12 +5741,19 @@ extern "C" int bpgpu_r1cs_prove_batch(bpgpu_ctx *c, const bpgpu_r1cs_circuit *ci
     if (rc) return rc;
     rc = r1cs_witness_on(c, wi, &dw);
     if (rc) return rc;
+    char *drows = nullptr;
+    size_t chk_per = 0;
+    if (check) {
+        rc = r1cs_rows_on(c, ci, &drows);
+        if (rc) return rc;
+        chk_per = r1c_slice(ci->rows, nbatch);
+    }
     hipStream_t s = c->stream;
     // ---- inputs through pinned staging into the persistent IO buffer
     host_call<bpgpu_ctx> io(c, s);
     const int r_v = io.in(nbatch * m * 32 + 64), r_vb = io.in(nbatch * m * 32 + 64), r_free = io.in(nbatch * nf * 32 + 64), r_rng = io.in(nbatch * 32), r_ts = io.in(nbatch * TS);
     const int r_rec = io.out(nbatch * R1P_NREC * 32), r_ipp = io.out(nbatch * ipp_len), r_vout = io.out(nbatch * m * 32 + 64), r_stat = io.out(nbatch * 4),
-              r_stb = io.out(nbatch + 64), r_to = io.out(nbatch * TS);
+              r_stb = io.out(nbatch + 64), r_to = io.out(nbatch * TS), r_first = io.out(check ? nbatch * 4 : 0);
     io.secrets(io.off[r_ts]);   // values, blindings, free inputs, the rng seeds
     rc = io.open();
     if (rc) return io.finish(rc);
@@ -5699,13 +5771,15 @@ extern "C" int bpgpu_r1cs_prove_batch(bpgpu_ctx *c, const bpgpu_r1cs_circuit *ci
     uint8_t *d_ipp = (uint8_t *)io.d(r_ipp), *d_stb = (uint8_t *)io.d(r_stb);
     rc = io.upload();
     if (!rc) rc = HIPRC(c, hipMemsetAsync(io.d(r_rec), 0, io.out_bytes(), s));
+    if (!rc && check) rc = HIPRC(c, hipMemsetAsync(io.d(r_first), 0xff, nbatch * 4, s));   // R1C_SATISFIED
     if (rc) return io.finish(rc);
     // ---- working set
     const size_t w_gs = align_up(n_gsc * 32), w_mo = align_up(5 * nbatch * 32 + 64), w_ms = align_up(std::max(nbatch * m, 5 * nbatch) + 64),
                  w_rnd = align_up((size_t)sh.nrand * nbatch * 40), w_aw = align_up(3 * std::max(n, (size_t)1) * nbatch * 40),
                  w_f = align_up((size_t)sh.c.nfields * nbatch * 40), w_vec = align_up(6 * std::max(n, (size_t)1) * nbatch * 40),
-                 w_t = align_up(7 * nrow * nbatch * 40), w_iv = align_up(nbatch * pn * 32), w_w = align_up(nbatch * 32);
-    const size_t need = w_gs + w_mo + w_ms + w_rnd + w_aw + w_f + w_vec + w_t + 4 * w_iv + w_w;
+                 w_t = align_up(7 * nrow * nbatch * 40), w_iv = align_up(nbatch * pn * 32), w_w = align_up(nbatch * 32),
+                 w_part = check ? align_up((size_t)ci->rows.nslots * chk_per * 32) : 0;
+    const size_t need = w_gs + w_mo + w_ms + w_rnd + w_aw + w_f + w_vec + w_t + 4 * w_iv + w_w + w_part;
     if ((rc = rpp_reserve(c, need))) return io.finish(rc);
     char *wb = c->rpp_buf;
     uint32_t *gsc = (uint32_t *)wb, *mo = (uint32_t *)(wb + w_gs);
@@ -5713,7 +5787,7 @@ extern "C" int bpgpu_r1cs_prove_batch(bpgpu_ctx *c, const bpgpu_r1cs_circuit *ci
     uint32_t *rnd = (uint32_t *)(mst + w_ms), *aw = (uint32_t *)((char *)rnd + w_rnd), *fields = (uint32_t *)((char *)aw + w_aw),
              *vecs = (uint32_t *)((char *)fields + w_f), *terms = (uint32_t *)((char *)vecs + w_vec), *lv = (uint32_t *)((char *)terms + w_t),
              *rv = (uint32_t *)((char *)lv + w_iv), *gf = (uint32_t *)((char *)rv + w_iv), *hf = (uint32_t *)((char *)gf + w_iv),
-             *wv = (uint32_t *)((char *)hf + w_iv);
+             *wv = (uint32_t *)((char *)hf + w_iv), *part = (uint32_t *)((char *)wv + w_w);
     const uint32_t nb32 = (uint32_t)nbatch, n_pb = (nb32 + 63) / 64;
     const uint32_t *src_l = (const uint32_t *)dw, *src_r = src_l + n, *row_ptr = (const uint32_t *)(dw + wi->off_row);
     const r1p_term *wterms = (const r1p_term *)(dw + wi->off_terms);
@@ -5751,6 +5825,9 @@ extern "C" int bpgpu_r1cs_prove_batch(bpgpu_ctx *c, const bpgpu_r1cs_circuit *ci
                 LAUNCH(c, s, "r1p_chal2", k_r1p_chal2, (nb32 + RP_BLOCK - 1) / RP_BLOCK, RP_BLOCK, sh, (const uint32_t *)mo, d_ts, fields, d_rec);
         }
         if (rc) break;
+        if (check)   // every constraint row over the finished witness and the proof's own challenges
+            r1cs_check_launch_locked(c, ci, drows, sh, nbatch, chk_per, d_v, (const uint32_t *)aw, (const uint32_t *)fields, (const uint32_t *)d_stat, 0, part,
+                                     (uint32_t *)io.d(r_first), nullptr, nullptr, s);
         // (4) wL, wR, wO, wV; l, r and the t polynomial; T_1, T_3..T_6
         const uint32_t npoly = (uint32_t)((n + m) * nbatch);
         if (hipMemsetAsync(terms, 0, w_t, s) != hipSuccess || hipMemsetAsync(gsc, 0, 15 * nbatch * 32, s) != hipSuccess) { rc = fail(c, BPGPU_ERR_HIP, "memset failed"); break; }
@@ -5800,6 +5877,111 @@ extern "C" int bpgpu_r1cs_prove_batch(bpgpu_ctx *c, const bpgpu_r1cs_circuit *ci
     }
     if (m) memcpy(commitments_out, h_v, nbatch * m * 32);
     if (transcripts_out) memcpy(transcripts_out, h_ts, nbatch * TS);
+    if (check) {   // a proof whose witness fails is void: no proof bytes, its transcript as it came (a non-canonical input outranks it)
+        memcpy(unsat_first_out, io.h(r_first), nbatch * 4);
+        for (size_t p = 0; p < nbatch; p++) {
+            if (status_out[p] != 0) unsat_first_out[p] = BPGPU_R1CS_SATISFIED;
+            if (unsat_first_out[p] == BPGPU_R1CS_SATISFIED) continue;
+            status_out[p] = BPGPU_R1CS_UNSATISFIED;
+            memset(proofs_out + p * proof_stride, 0, proof_stride);
+            proof_lens_out[p] = 0;
+            if (transcripts_out) memcpy(transcripts_out + p * TS, transcripts + p * transcript_stride, TS);
+        }
+    }
+    return BPGPU_OK;
+}
+
+extern "C" int bpgpu_r1cs_prove_batch(bpgpu_ctx *c, const bpgpu_r1cs_circuit *ci, const bpgpu_r1cs_witness *wi, size_t nbatch, const uint8_t *v,
+                                      const uint8_t *v_blinding, const uint8_t *free_inputs, const uint8_t *transcripts, size_t transcript_stride,
+                                      const uint8_t *rng32, uint8_t *proofs_out, size_t proof_stride, uint32_t *proof_lens_out, uint8_t *commitments_out,
+                                      uint8_t *status_out, uint8_t *transcripts_out) {
+    return r1cs_prove_impl(c, ci, wi, nbatch, v, v_blinding, free_inputs, transcripts, transcript_stride, rng32, proofs_out, proof_stride, proof_lens_out,
+                           commitments_out, status_out, transcripts_out, false, nullptr);
+}
+
+extern "C" int bpgpu_r1cs_prove_batch_checked(bpgpu_ctx *c, const bpgpu_r1cs_circuit *ci, const bpgpu_r1cs_witness *wi, size_t nbatch, const uint8_t *v,
+                                              const uint8_t *v_blinding, const uint8_t *free_inputs, const uint8_t *transcripts, size_t transcript_stride,
+                                              const uint8_t *rng32, uint8_t *proofs_out, size_t proof_stride, uint32_t *proof_lens_out,
+                                              uint8_t *commitments_out, uint8_t *status_out, uint8_t *transcripts_out, uint32_t *unsat_first_out) {
+    return r1cs_prove_impl(c, ci, wi, nbatch, v, v_blinding, free_inputs, transcripts, transcript_stride, rng32, proofs_out, proof_stride, proof_lens_out,
+                           commitments_out, status_out, transcripts_out, true, unsat_first_out);
+}
+
+// The stand-alone check: the challenges loaded from the caller's values, then the prover's own input and witness launches (no V rows,
+// no blindings, no transcript, no generators) and the check launches.
+extern "C" int bpgpu_r1cs_witness_check(bpgpu_ctx *c, const bpgpu_r1cs_circuit *ci, const bpgpu_r1cs_witness *wi, size_t nbatch, const uint8_t *v,
+                                        const uint8_t *free_inputs, const uint8_t *challenges, uint32_t *first_out, uint32_t *count_out, uint8_t *map_out,
+                                        size_t map_stride, uint8_t *status_out) {
+    if (!ci || !wi) return BPGPU_ERR_INVALID_ARG;
+    if (wi->m != ci->m || wi->n1 != ci->n1 || wi->n != ci->n || wi->nch != ci->nch) return fail(c, BPGPU_ERR_INVALID_ARG, "witness program of another circuit");
+    const size_t m = ci->m, n = ci->n, nf = wi->nfree, nch = ci->nch, Q = ci->Q, map_bytes = (Q + 7) / 8, mapw = map_out ? (Q + 31) / 32 : 0;
+    if (nch && !challenges) return fail(c, BPGPU_ERR_INVALID_ARG, "the circuit has %zu challenges: their values are needed", nch);
+    if (map_out && map_stride < map_bytes) return fail(c, BPGPU_ERR_INVALID_ARG, "map_stride %zu < %zu", map_stride, map_bytes);
+    if (!c) return BPGPU_ERR_INVALID_ARG;
+    if (nbatch == 0) return BPGPU_OK;
+    if ((m && !v) || (nf && !free_inputs) || !first_out || !status_out) return BPGPU_ERR_INVALID_ARG;
+    if ((uint64_t)nbatch * (m + nf + nch + 1) > 0x7fffffffull / 64 || (uint64_t)nbatch * std::max(3 * n + nch, (size_t)1) * 40 > (4ull << 30) ||
+        (uint64_t)nbatch * std::max(mapw, (size_t)1) * 4 > (1ull << 30))
+        return fail(c, BPGPU_ERR_INVALID_ARG, "batch too large for this circuit");
+    std::lock_guard<std::mutex> lk(c->mu);
+    HIPCHK(c, hipSetDevice(c->device));
+    r1p_shape sh{};
+    sh.c.m = (uint32_t)m, sh.c.n1 = ci->n1, sh.c.n = (uint32_t)n, sh.c.pn = ci->pn, sh.c.k = ci->k;
+    sh.c.two_phase = ci->two_phase, sh.c.nch = ci->nch, sh.c.Q = ci->Q;
+    sh.c.f_ch = 0;                       // the only fields: the challenges
+    sh.c.nfields = (uint32_t)nch;
+    sh.c.nproofs = (uint32_t)nbatch;
+    sh.nfree = (uint32_t)nf;
+    sh.i0 = 0, sh.i1 = (uint32_t)n;      // every challenge is known: one witness launch over both phases
+    char *dw = nullptr, *drows = nullptr;
+    int rc = r1cs_witness_on(c, wi, &dw);
+    if (rc) return rc;
+    rc = r1cs_rows_on(c, ci, &drows);
+    if (rc) return rc;
+    const size_t per = r1c_slice(ci->rows, nbatch);
+    hipStream_t s = c->stream;
+    host_call<bpgpu_ctx> io(c, s);
+    const int r_v = io.in(nbatch * m * 32 + 64), r_free = io.in(nbatch * nf * 32 + 64), r_ch = io.in(nbatch * nch * 32 + 64);
+    const int r_first = io.out(nbatch * 4), r_cnt = io.out(nbatch * 4), r_stat = io.out(nbatch * 4), r_map = io.out(nbatch * mapw * 4);
+    io.secrets(io.in_bytes());   // values and free inputs (the challenges ride along)
+    rc = io.open();
+    if (rc) return io.finish(rc);
+    if (m) io.put(r_v, v, nbatch * m * 32);
+    if (nf) io.put(r_free, free_inputs, nbatch * nf * 32);
+    if (nch) io.put(r_ch, challenges, nbatch * nch * 32);
+    const uint8_t *d_v = (const uint8_t *)io.d(r_v), *d_free = (const uint8_t *)io.d(r_free), *d_ch = (const uint8_t *)io.d(r_ch);
+    uint32_t *d_first = (uint32_t *)io.d(r_first), *d_cnt = (uint32_t *)io.d(r_cnt), *d_stat = (uint32_t *)io.d(r_stat),
+             *d_map = map_out ? (uint32_t *)io.d(r_map) : nullptr;
+    rc = io.upload();
+    if (!rc) rc = HIPRC(c, hipMemsetAsync(io.d(r_first), 0, io.out_bytes(), s));
+    if (!rc) rc = HIPRC(c, hipMemsetAsync(d_first, 0xff, nbatch * 4, s));   // R1C_SATISFIED
+    if (rc) return io.finish(rc);
+    const size_t w_aw = align_up(3 * std::max(n, (size_t)1) * nbatch * 40), w_f = align_up(std::max(nch, (size_t)1) * nbatch * 40),
+                 w_part = align_up((size_t)ci->rows.nslots * per * 32);
+    if ((rc = rpp_reserve(c, w_aw + w_f + w_part))) return io.finish(rc);
+    uint32_t *aw = (uint32_t *)c->rpp_buf, *fields = (uint32_t *)(c->rpp_buf + w_aw), *part = (uint32_t *)(c->rpp_buf + w_aw + w_f);
+    const uint32_t *src_l = (const uint32_t *)dw, *src_r = src_l + n, *row_ptr = (const uint32_t *)(dw + wi->off_row);
+    const r1p_term *wterms = (const r1p_term *)(dw + wi->off_terms);
+    const uint32_t nb32 = (uint32_t)nbatch, nchal = (uint32_t)(nbatch * nch), nin = (uint32_t)(nbatch * (m + nf));
+    if (nchal) LAUNCH(c, s, "r1c_chal", k_r1c_chal, (nchal + 63) / 64, 64, nchal, sh, d_ch, fields, d_stat);
+    if (nin) LAUNCH(c, s, "r1p_inputs", k_r1p_inputs, (nin + 63) / 64, 64, nin, sh, d_v, (const uint8_t *)nullptr, d_free, (uint32_t *)nullptr, d_stat);
+    if (n) LAUNCH(c, s, "r1p_witness", k_r1p_witness, (nb32 + 63) / 64, 64, sh, src_l, src_r, row_ptr, wterms, d_v, d_free, (const uint32_t *)fields, aw);
+    r1cs_check_launch_locked(c, ci, drows, sh, nbatch, per, d_v, (const uint32_t *)aw, (const uint32_t *)fields, (const uint32_t *)d_stat, (uint32_t)mapw, part,
+                             d_first, d_cnt, d_map, s);
+    if (hipGetLastError() != hipSuccess) rc = fail(c, BPGPU_ERR_HIP, "launch failed");
+    rc = io.finish(io.download(rc));
+    if (rc) return rc;
+    memcpy(first_out, io.h(r_first), nbatch * 4);
+    if (count_out) memcpy(count_out, io.h(r_cnt), nbatch * 4);
+    for (size_t p = 0; p < nbatch; p++) {
+        uint32_t st;
+        memcpy(&st, io.h(r_stat) + 4 * p, 4);
+        status_out[p] = (uint8_t)st;
+        if (map_out) {   // (little-endian words: bit q % 8 of byte q / 8)
+            memcpy(map_out + p * map_stride, io.h(r_map) + p * mapw * 4, map_bytes);
+            memset(map_out + p * map_stride + map_bytes, 0, map_stride - map_bytes);
+        }
+    }
     return BPGPU_OK;
 }
 

@@ -19,6 +19,7 @@
 #include "linear_prover.h"
 #include "r1cs.h"
 #include "r1cs_prover.h"
+#include "r1cs_check.h"
 #include "r1cs_rlc.h"
 #include "rlc_mix.h"
 #include "linear_rlc.h"
@@ -118,6 +119,9 @@ __global__ void k_r1p_chal3(r1p_shape sh, const uint32_t *tout, const uint32_t *
 __global__ void k_r1p_poly(uint32_t nthreads, r1p_shape sh, const uint32_t *col_ptr, const r1cs_ent *ents, const uint32_t *aw, const uint32_t *rnd, const uint8_t *vb, const uint32_t *fields, uint32_t nrow, uint32_t *vecs, uint32_t *terms);
 __global__ void k_r1p_tsum(r1p_shape sh, uint32_t nrow, const uint32_t *terms, const uint32_t *rnd, uint32_t *fields, uint32_t *trows);
 __global__ void k_r1p_vecs(uint32_t nthreads, r1p_shape sh, const uint32_t *fields, const uint32_t *vecs, uint32_t *lv, uint32_t *rv, uint32_t *gf, uint32_t *hf);
+__global__ void k_r1c_chal(uint32_t nthreads, r1p_shape sh, const uint8_t *chal, uint32_t *fields, uint32_t *status);
+__global__ void k_r1c_units(uint32_t nthreads, r1p_shape sh, uint32_t p0, uint32_t cnt, const r1c_unit *units, const r1p_term *terms, const uint32_t *aw, const uint8_t *v, const uint32_t *fields, const uint32_t *status, uint32_t mapw, uint32_t *partial, uint32_t *first, uint32_t *count, uint32_t *map);
+__global__ void k_r1c_long(uint32_t nthreads, uint32_t p0, uint32_t cnt, const r1c_long *longs, const uint32_t *partial, const uint32_t *status, uint32_t mapw, uint32_t *first, uint32_t *count, uint32_t *map);
 __global__ void k_lin_prepare(lin_shape sh, rp_strobe_init init, const uint8_t *proofs, const uint8_t *C, const uint8_t *bvec, const uint8_t *G, const uint8_t *F, const uint8_t *B, uint32_t *scalars, uint32_t *points, uint32_t *status, uint32_t *ts_out, uint32_t *gen_sc);
 __global__ void k_lin_prepare_ts(lin_shape sh, rp_strobe_init init, const uint8_t *proofs, const uint8_t *C, const uint8_t *bvec, const uint8_t *G, const uint8_t *F, const uint8_t *B, uint32_t *scalars, uint32_t *points, uint32_t *status, uint32_t *ts_out, uint32_t *gen_sc, const uint32_t *ts_in, uint32_t ts_in_stride, uint32_t ts_n);
 __global__ void k_from_uniform(uint32_t n, const uint32_t *uniform, uint32_t *out);

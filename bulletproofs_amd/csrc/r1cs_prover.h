@@ -60,6 +60,10 @@ BP_HD void r1p_inputs_thread(uint32_t tid, const r1p_shape &sh, const uint8_t *v
     if (tid < nvm) {
         const uint32_t p = tid / sh.c.m;
         r1p_ld_bytes(a, v + (uint64_t)tid * 32);
+        if (!vrows) {   // the stand-alone constraint check (r1cs_check.h): no blindings, no V rows
+            if (!sc_is_canonical_sc(a)) status_raise(status + p, BP_STATUS_BAD_SCALAR);
+            return;
+        }
         r1p_ld_bytes(b, vb + (uint64_t)tid * 32);
         if (!sc_is_canonical_sc(a) || !sc_is_canonical_sc(b)) status_raise(status + p, BP_STATUS_BAD_SCALAR);
         uint32_t *row = vrows + (uint64_t)tid * 24;
@@ -242,31 +246,35 @@ BP_HD void r1p_term_value(sc &val, const r1p_shape &sh, const r1p_term &e, const
     default: sc_from_u32(val, 1);
     }
 }
+// coeff * ch_j^e * value of one term, reduced (the witness rows and the constraint check of r1cs_check.h both sum these)
+BP_HD void r1p_term_product(sc &s, const r1p_shape &sh, const r1p_term &e, const uint32_t *aw, const uint8_t *v, const uint32_t *fields, uint32_t p) {
+    sc val;
+    sc28 c, vm, prod;
+#pragma unroll
+    for (int q = 0; q < 10; q++) c.v[q] = e.coeff[q];
+    r1p_term_value(val, sh, e, aw, v, p);
+    sc_to_mont28(vm, val);
+    sc28_montmul(prod, c, vm);
+    if (e.chal != R1_NO_CHAL) {   // ch_j^e (1 <= e < 256), left-to-right from the top bit
+        const uint32_t j = e.chal & 0xffffu, pw = e.chal >> 16;
+        sc28 ch, cp;
+        r1_load28(ch, fields, sh.c, sh.c.f_ch + j, p);
+        cp = ch;
+        for (int bit = 30 - __builtin_clz(pw); bit >= 0; bit--) {
+            sc28_montsq(cp, cp);
+            if ((pw >> bit) & 1u) sc28_montmul(cp, cp, ch);
+        }
+        sc28_montmul(prod, prod, cp);
+    }
+    sc_from_mont28(s, prod);
+}
 // sum of coeff * ch_j^e * value over the row (Prover::eval)
 BP_HD void r1p_eval_row(sc &acc, const r1p_shape &sh, const uint32_t *row_ptr, const r1p_term *terms, uint32_t r, const uint32_t *aw, const uint8_t *v,
                         const uint32_t *fields, uint32_t p) {
     sc_0(acc);
     for (uint32_t t = row_ptr[r]; t < row_ptr[r + 1]; t++) {
-        const r1p_term &e = terms[t];
-        sc val, s;
-        sc28 c, vm, prod;
-#pragma unroll
-        for (int q = 0; q < 10; q++) c.v[q] = e.coeff[q];
-        r1p_term_value(val, sh, e, aw, v, p);
-        sc_to_mont28(vm, val);
-        sc28_montmul(prod, c, vm);
-        if (e.chal != R1_NO_CHAL) {   // ch_j^e (1 <= e < 256), left-to-right from the top bit
-            const uint32_t j = e.chal & 0xffffu, pw = e.chal >> 16;
-            sc28 ch, cp;
-            r1_load28(ch, fields, sh.c, sh.c.f_ch + j, p);
-            cp = ch;
-            for (int bit = 30 - __builtin_clz(pw); bit >= 0; bit--) {
-                sc28_montsq(cp, cp);
-                if ((pw >> bit) & 1u) sc28_montmul(cp, cp, ch);
-            }
-            sc28_montmul(prod, prod, cp);
-        }
-        sc_from_mont28(s, prod);
+        sc s;
+        r1p_term_product(s, sh, terms[t], aw, v, fields, p);
         sc_add(acc, acc, s);
     }
 }

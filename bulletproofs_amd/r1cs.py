@@ -25,8 +25,16 @@ is then made on the GPU (bpgpu_r1cs_prove_batch):
     proof, V = cs.prove(ctx)                   # R1CSProof, the m commitments (32 bytes each)
 
 Deviation from the reference: ``Prover.commit`` returns the ``Variable`` only; the commitments come back from proving.
+
+Checking a witness (bellman's ``is_satisfied`` / ``which_is_unsatisfied``): ``Prover.check(ctx)`` raises ``Unsatisfied`` naming the
+first constraint the assignment leaves unsatisfied, ``Prover.which_is_unsatisfied(ctx)`` returns its index or None, ``check_batch``
+does the same for many provers of one gadget (bpgpu_r1cs_witness_check: no generators, no transcript, no blindings).
+``prove(ctx, check=True)`` / ``prove_batch(..., check=True)`` run the same check inside the prover, on the proof's own challenges
+(bpgpu_r1cs_prove_batch_checked).  ``Prover(transcript, locate=True)`` remembers where each constraint was added.
 """
 import ctypes as C
+import secrets
+import sys
 
 from . import _lib
 
@@ -42,6 +50,9 @@ VERDICT_VERIFICATION_ERROR = 1
 VERDICT_FORMAT_ERROR = 2
 VERDICT_INVALID_GENERATORS_LENGTH = 4
 
+SATISFIED = 0xffffffff         # BPGPU_R1CS_SATISFIED
+STATUS_UNSATISFIED = 3         # BPGPU_R1CS_UNSATISFIED
+
 
 class R1CSError(Exception):
     pass
@@ -49,6 +60,20 @@ class R1CSError(Exception):
 
 class FormatError(R1CSError):
     pass
+
+
+class Unsatisfied(R1CSError):
+    """The witness leaves a constraint unsatisfied.  ``constraint``: the lowest failing index, in the order the gadget added them;
+    ``where``: "file:line" of the call that added it (a ``Prover`` made with ``locate=True``), else None."""
+
+    def __init__(self, constraint, where=None, position=None):
+        self.constraint, self.where, self.position = constraint, where, position
+        msg = "constraint %d is not satisfied" % constraint
+        if where:
+            msg += " (added at %s)" % where
+        if position is not None:
+            msg += " [proof %d of the batch]" % position
+        super().__init__(msg)
 
 
 # ---- variables and linear combinations (src/r1cs/linear_combination.rs) ------------------------------------------------
@@ -266,11 +291,26 @@ class Prover(Verifier):
     witness program.  Assignments: an int becomes the next free input of the proof; a symbolic expression of challenges (inside
     a randomized callback) becomes an LC row evaluated on the device, as do multiply's inputs (Prover::eval, prover.rs:340-356)."""
 
-    def __init__(self, transcript):
+    def __init__(self, transcript, locate=False):
         super().__init__(transcript)
         self.v, self.v_blinding, self.free = [], [], []
         self.src_left, self.src_right, self.rows = [], [], []
         self._witness = None
+        self.locations = [] if locate else None   # per constraint: (file, line) of the gadget's constrain / multiply call
+
+    def constrain(self, lc):
+        if self.locations is not None:           # the nearest frame outside this module: the gadget's own line
+            f = sys._getframe(1)
+            while f is not None and f.f_code.co_filename == __file__:
+                f = f.f_back
+            self.locations.append((f.f_code.co_filename, f.f_lineno) if f is not None else None)
+        super().constrain(lc)
+
+    def where(self, constraint):
+        """"file:line" of the call that added constraint `constraint`, or None (locate=False)"""
+        if self.locations is None or not 0 <= constraint < len(self.locations) or self.locations[constraint] is None:
+            return None
+        return "%s:%d" % self.locations[constraint]
 
     def commit(self, v, v_blinding):
         """prover.rs:296-306; returns the Variable only (V_j is computed on the device and returned by prove)"""
@@ -343,25 +383,81 @@ class Prover(Verifier):
         enc = lambda xs: b"".join(x.to_bytes(32, "little") for x in xs)
         return enc(self.v), enc(self.v_blinding), enc(self.free)
 
-    def prove(self, ctx, rng32=None):
-        """Prover::prove with the generators of `ctx` (a Context): (R1CSProof, [V_j])"""
-        return prove_batch(ctx, [self], rng32)[0]
+    def prove(self, ctx, rng32=None, check=False):
+        """Prover::prove with the generators of `ctx` (a Context): (R1CSProof, [V_j]).  check=True: ``Unsatisfied`` instead of a
+        proof the verifier would reject (the check runs on the proof's own challenges)."""
+        return prove_batch(ctx, [self], rng32, check=check)[0]
+
+    def which_is_unsatisfied(self, ctx, challenges=None):
+        """the lowest index of a constraint this prover's assignment leaves unsatisfied, or None (see ``check_batch``)"""
+        return check_batch(ctx, [self], challenges)[0]
+
+    def check(self, ctx, challenges=None):
+        """raises ``Unsatisfied`` when the assignment leaves a constraint unsatisfied (see ``check_batch``)"""
+        q = self.which_is_unsatisfied(ctx, challenges)
+        if q is not None:
+            raise Unsatisfied(q, self.where(q))
 
 
-def prove_batch(ctx, provers, rng32=None):
-    """one proof per recorded Prover, all of the same gadget (R1CSError otherwise): [(R1CSProof, [V_j])] in order.
-    rng32: len(provers) x 32 bytes (what finalize takes from thread_rng) or None (the OS generator)."""
-    if not provers:
-        return []
+def _same_gadget(provers):
     st = provers[0].structure()
     if any(p.structure() != st for p in provers[1:]):
         raise R1CSError("the provers of one batch must record the same gadget")
-    w = provers[0].witness()
+
+
+def _challenge_bytes(challenges, nch, nbatch):
+    """None, bytes (nbatch x nch x 32), nch ints (the same values for every proof) or nbatch lists of nch ints"""
+    if challenges is None or isinstance(challenges, (bytes, bytearray)):
+        return challenges
+    rows = list(challenges)
+    if not rows or isinstance(rows[0], int):
+        rows = [rows] * nbatch
+    if len(rows) != nbatch or any(len(r) != nch for r in rows):
+        raise ValueError("challenges: %d values per proof" % nch)
+    return b"".join((c % L_ORDER).to_bytes(32, "little") for r in rows for c in r)
+
+
+def check_batch(ctx, provers, challenges=None, want_count=False, want_map=False):
+    """Which constraint does each prover's assignment leave unsatisfied?  The provers must record the same gadget (R1CSError
+    otherwise).  Returns a list with None (every constraint holds) or the lowest failing index per prover [, the failure counts]
+    [, the failing sets as bytes: bit q % 8 of byte q / 8].  Needs a Context only: no generators, no transcript, no blindings.
+    challenges: the phase-2 challenge values (bytes, ints for all proofs, or a list of ints per proof); None on a gadget that has
+    challenges draws uniform scalars.  A witness that is right satisfies every constraint under any challenges.  One that is wrong
+    fails under almost all of them."""
+    if not provers:
+        return ([],) * (1 + want_count + want_map) if (want_count or want_map) else []
+    _same_gadget(provers)
+    circuit = provers[0].circuit()
     ins = [p.inputs() for p in provers]
-    proofs, coms, status = w.prove_batch(ctx, provers[0].circuit(), len(provers), b"".join(i[0] for i in ins), b"".join(i[1] for i in ins),
-                                         b"".join(i[2] for i in ins), b"".join(p.transcript for p in provers), rng32)
+    nb = len(provers)
+    res = provers[0].witness().check_batch(ctx, circuit, nb, b"".join(i[0] for i in ins), b"".join(i[2] for i in ins),
+                                           _challenge_bytes(challenges, circuit.n_challenges, nb), want_count=want_count, want_map=want_map)
+    first, status = res[0], res[1]
     if any(status):
         raise R1CSError("non-canonical input scalar (status %s)" % list(status))
+    out = [None if q == SATISFIED else q for q in first]
+    return (out,) + tuple(res[2:]) if (want_count or want_map) else out
+
+
+def prove_batch(ctx, provers, rng32=None, check=False):
+    """one proof per recorded Prover, all of the same gadget (R1CSError otherwise): [(R1CSProof, [V_j])] in order.
+    rng32: len(provers) x 32 bytes (what finalize takes from thread_rng) or None (the OS generator).
+    check=True: the witness check runs inside the prover on each proof's own challenges; ``Unsatisfied`` for the first proof whose
+    witness fails (its position in the batch is in the message and in ``.position``)."""
+    if not provers:
+        return []
+    _same_gadget(provers)
+    w = provers[0].witness()
+    ins = [p.inputs() for p in provers]
+    res = w.prove_batch(ctx, provers[0].circuit(), len(provers), b"".join(i[0] for i in ins), b"".join(i[1] for i in ins),
+                        b"".join(i[2] for i in ins), b"".join(p.transcript for p in provers), rng32, check=check)
+    proofs, coms, status = res[:3]
+    if any(st not in (0, STATUS_UNSATISFIED) for st in status):
+        raise R1CSError("non-canonical input scalar (status %s)" % list(status))
+    if check:
+        for b, q in enumerate(res[3]):
+            if q != SATISFIED:
+                raise Unsatisfied(q, provers[b].where(q), position=b)
     m = provers[0].circuit().m
     return [(R1CSProof.from_bytes(pb), [coms[32 * (b * m + j):32 * (b * m + j + 1)] for j in range(m)]) for b, pb in enumerate(proofs)]
 
@@ -401,9 +497,36 @@ class Witness:
         except Exception:
             pass
 
-    def prove_batch(self, ctx, circuit, nbatch, v, v_blinding, free_inputs, transcripts, rng32=None, want_transcripts=False):
+    def check_batch(self, ctx, circuit, nbatch, v, free_inputs, challenges=None, want_count=False, want_map=False):
+        """raw arrays through bpgpu_r1cs_witness_check: v nbatch x m x 32 bytes; free_inputs nbatch x n_free x 32; challenges
+        nbatch x n_challenges x 32 bytes (canonical scalars, proof by proof in draw order) or None: uniform scalars are drawn.
+        A witness that is right satisfies every constraint under any challenges.  One that is wrong fails under almost all of them.
+        Returns (first failing index per proof or SATISFIED, status bytes[, counts][, maps as nbatch byte strings])."""
+        nch, Q = circuit.n_challenges, circuit.n_constraints
+        assert len(v) == 32 * circuit.m * nbatch and len(free_inputs) == 32 * self.n_free * nbatch
+        if challenges is None and nch:
+            challenges = b"".join(secrets.randbelow(L_ORDER).to_bytes(32, "little") for _ in range(nch * nbatch))
+        assert challenges is None or len(challenges) == 32 * nch * nbatch
+        nb = max(nbatch, 1)
+        stride = max((Q + 7) // 8, 1)
+        first, count = (C.c_uint32 * nb)(), (C.c_uint32 * nb)() if want_count else None
+        maps = C.create_string_buffer(stride * nb) if want_map else None
+        status = C.create_string_buffer(nb)
+        rc = lib().bpgpu_r1cs_witness_check(ctx.h, circuit._h, self._h, nbatch, bytes(v), bytes(free_inputs), bytes(challenges) if nch else None,
+                                            first, count, maps, stride if want_map else 0, status)
+        ctx._chk(rc)
+        res = (list(first[:nbatch]), status.raw[:nbatch])
+        if want_count:
+            res += (list(count[:nbatch]),)
+        if want_map:
+            res += ([maps.raw[b * stride:b * stride + (Q + 7) // 8] for b in range(nbatch)],)
+        return res
+
+    def prove_batch(self, ctx, circuit, nbatch, v, v_blinding, free_inputs, transcripts, rng32=None, want_transcripts=False, check=False):
         """raw arrays: v, v_blinding nbatch x m x 32 bytes; free_inputs nbatch x n_free x 32; transcripts one 208-byte state or
-        nbatch of them.  Returns (proofs as bytes, commitments, status bytes[, transcripts])."""
+        nbatch of them.  Returns (proofs as bytes, commitments, status bytes[, transcripts]).  check=True
+        (bpgpu_r1cs_prove_batch_checked): one more element, the first failing constraint per proof (SATISFIED: none); a proof
+        whose witness fails has status STATUS_UNSATISFIED and no bytes."""
         TS = _lib.TRANSCRIPT_BYTES
         assert len(v) == len(v_blinding) == 32 * circuit.m * nbatch and len(free_inputs) == 32 * self.n_free * nbatch
         assert len(transcripts) in (TS, TS * nbatch) and (rng32 is None or len(rng32) == 32 * nbatch)
@@ -415,12 +538,19 @@ class Witness:
         coms = C.create_string_buffer(32 * circuit.m * nb + 1)
         status = C.create_string_buffer(nb)
         tso = C.create_string_buffer(TS * nb) if want_transcripts else None
-        rc = lib().bpgpu_r1cs_prove_batch(ctx.h, circuit._h, self._h, nbatch, v, v_blinding, free_inputs, transcripts, ts_stride, rng32,
-                                          out, stride, lens, coms, status, tso)
+        if check:
+            first = (C.c_uint32 * nb)()
+            rc = lib().bpgpu_r1cs_prove_batch_checked(ctx.h, circuit._h, self._h, nbatch, v, v_blinding, free_inputs, transcripts, ts_stride, rng32,
+                                                      out, stride, lens, coms, status, tso, first)
+        else:
+            rc = lib().bpgpu_r1cs_prove_batch(ctx.h, circuit._h, self._h, nbatch, v, v_blinding, free_inputs, transcripts, ts_stride, rng32,
+                                              out, stride, lens, coms, status, tso)
         ctx._chk(rc)
         proofs = [out.raw[b * stride:b * stride + lens[b]] for b in range(nbatch)]
         res = (proofs, coms.raw[:32 * circuit.m * nbatch], status.raw[:nbatch])
-        return res + (tso.raw[:TS * nbatch],) if want_transcripts else res
+        if want_transcripts:
+            res += (tso.raw[:TS * nbatch],)
+        return res + (list(first[:nbatch]),) if check else res
 
 
 def flattened_constraints(descriptor, z, challenges):
@@ -444,6 +574,7 @@ class Circuit:
     def __init__(self, m, n1, n2, two_phase, labels, constraints):
         L = lib()
         self.m, self.n1, self.n2, self.two_phase = m, n1, n2, bool(two_phase)
+        self.n_challenges, self.n_constraints = len(labels), len(constraints)
         row = [0]
         kind, index, chal, power, coeff = [], [], [], [], []
         for terms in constraints:
@@ -615,5 +746,7 @@ def lib():
         L.bpgpu_r1cs_witness_destroy.argtypes = [vp]
         L.bpgpu_r1cs_witness_destroy.restype = None
         L.bpgpu_r1cs_prove_batch.argtypes = [vp, vp, vp, sz, u8p, u8p, u8p, u8p, sz, u8p, u8p, sz, u32p, u8p, u8p, u8p]
+        L.bpgpu_r1cs_prove_batch_checked.argtypes = L.bpgpu_r1cs_prove_batch.argtypes + [u32p]
+        L.bpgpu_r1cs_witness_check.argtypes = [vp, vp, vp, sz, u8p, u8p, u8p, u32p, u32p, u8p, sz, u8p]
         L._r1cs_bound = True
     return L

@@ -716,6 +716,45 @@ int bpgpu_r1cs_prove_batch(bpgpu_ctx *ctx, const bpgpu_r1cs_circuit *circuit, co
                            size_t transcript_stride, const uint8_t *rng32, uint8_t *proofs_out, size_t proof_stride,
                            uint32_t *proof_lens_out, uint8_t *commitments_out, uint8_t *status_out, uint8_t *transcripts_out);
 
+/* ---- R1CS witness check: which constraint does a witness leave unsatisfied? (bellman's is_satisfied / which_is_unsatisfied) ----
+ * Constraint q of proof p holds iff Prover::eval(lc_q) == 0 (prover.rs:340-356): the sum over its terms of
+ * coeff * challenge^power * value, mod l, over the witness the witness program computes.  ADDITIONAL entry points: no other call
+ * changes.  BPGPU_R1CS_UNSATISFIED is the next status byte after the BPGPU_MSM_* ones the provers' status_out carries. */
+#define BPGPU_R1CS_SATISFIED 0xffffffffu
+#define BPGPU_R1CS_UNSATISFIED 3
+/* The stand-alone check of nbatch witnesses of one recorded gadget.  No generators, no transcript, no blindings: it works on a
+ * context that never loaded generators.
+ *   v           : nbatch x m x 32 bytes; free_inputs: nbatch x n_free x 32 bytes (canonical scalars)
+ *   challenges  : nbatch x n_challenges x 32 bytes, canonical scalars: proof p's phase-2 challenge values in draw order; NULL
+ *                 when the circuit has no challenges (ignored then).  A witness that is right satisfies every constraint under
+ *                 any challenges; one that is wrong fails under almost all of them.
+ *   first_out   : nbatch words, the lowest unsatisfied constraint index (in the order the gadget added them), or
+ *                 BPGPU_R1CS_SATISFIED
+ *   count_out   : optional nbatch words, how many constraints failed
+ *   map_out     : optional nbatch x map_stride bytes, map_stride >= ceil(Q / 8): bit q % 8 of byte q / 8 is set iff constraint q
+ *                 failed; every other bit is zero
+ *   status_out  : nbatch bytes, BPGPU_MSM_BAD_SCALAR for a non-canonical v, free input or challenge -- that proof is not
+ *                 checked (first = BPGPU_R1CS_SATISFIED, count 0, map zero) -- else 0
+ * nbatch = 0 is BPGPU_OK.  BPGPU_ERR_INVALID_ARG: a witness program of another circuit, challenges == NULL for a circuit that
+ * has some, map_stride too small.  v and the free inputs are secrets: staging and working set are cleared on every exit, as the
+ * provers clear theirs.  The circuit's row form is built and uploaded at the first check (here or in the checked prover) and
+ * freed by bpgpu_r1cs_circuit_destroy. */
+int bpgpu_r1cs_witness_check(bpgpu_ctx *ctx, const bpgpu_r1cs_circuit *circuit, const bpgpu_r1cs_witness *witness, size_t nbatch,
+                             const uint8_t *v, const uint8_t *free_inputs, const uint8_t *challenges, uint32_t *first_out,
+                             uint32_t *count_out, uint8_t *map_out, size_t map_stride, uint8_t *status_out);
+/* bpgpu_r1cs_prove_batch with the check run on each proof's OWN phase-2 challenges, after the last witness launch and before
+ * the polynomials (bpgpu_r1cs_prove_batch is this function with the check off).  A proof whose witness satisfies every
+ * constraint: every output equals bpgpu_r1cs_prove_batch's on the same inputs byte for byte, unsat_first_out[p] =
+ * BPGPU_R1CS_SATISFIED.  Otherwise proof p is void: status_out[p] = BPGPU_R1CS_UNSATISFIED, unsat_first_out[p] the first failing
+ * constraint, its proof bytes zero, proof_lens_out[p] = 0, transcripts_out[p] the input state unchanged; commitments_out still
+ * holds its V_j (valid commitments).  A non-canonical input keeps BPGPU_MSM_BAD_SCALAR (and BPGPU_R1CS_SATISFIED): it takes
+ * precedence.  The chain runs at full width; void proofs are blanked at the end. */
+int bpgpu_r1cs_prove_batch_checked(bpgpu_ctx *ctx, const bpgpu_r1cs_circuit *circuit, const bpgpu_r1cs_witness *witness, size_t nbatch,
+                                   const uint8_t *v, const uint8_t *v_blinding, const uint8_t *free_inputs, const uint8_t *transcripts,
+                                   size_t transcript_stride, const uint8_t *rng32, uint8_t *proofs_out, size_t proof_stride,
+                                   uint32_t *proof_lens_out, uint8_t *commitments_out, uint8_t *status_out, uint8_t *transcripts_out,
+                                   uint32_t *unsat_first_out);
+
 /* nbatch independent calls of
  *   LinearProof::create(&mut transcript, &mut rng, &C, r, a_vec, b_vec, G_vec, &F, &B).to_bytes()
  * (src/linear_proof.rs:40-173), all of one size n (a power of two) over the same G, F, B.  Per round the reference forms
