@@ -27,6 +27,7 @@ EXPORTS = [
     "bpgpu_pool_rangeproof_verify_rlc_mixed_ts",
     "bpgpu_profile_enable", "bpgpu_profile_reset", "bpgpu_profile_report",
     "bpgpu_transcript_new", "bpgpu_transcript_append_message", "bpgpu_transcript_challenge_bytes",
+    "bpgpu_transcript_batch", "bpgpu_transcript_batch_dev",
     "bpgpu_rangeproof_verify_batch_ts", "bpgpu_rangeproof_verify_batch_ts_dev", "bpgpu_ipp_verify_batch_dev",
     "bpgpu_ipp_create_batch", "bpgpu_rangeproof_prove_batch", "bpgpu_rangeproof_verify_batch_submit", "bpgpu_ctx_collect",
     "bpgpu_rangeproof_prove_batch_ts", "bpgpu_rangeproof_prove_batch_ts_dev",
@@ -49,6 +50,14 @@ EXPORTS = [
 ]
 
 TRANSCRIPT_BYTES = 208
+TS_APPEND, TS_APPEND_U64, TS_CHALLENGE, TS_CHALLENGE_SCALAR = 1, 2, 3, 4       # bpgpu_ts_op.kind
+TS_MAX_OPS, TS_MAX_LABEL, TS_MAX_LEN, TS_MAX_CHALLENGE = 32, 255, 65536, 4096
+
+
+class TsOp(C.Structure):
+    """bpgpu_ts_op"""
+    _fields_ = [("kind", C.c_uint32), ("label", C.c_void_p), ("label_len", C.c_size_t), ("data", C.c_void_p), ("stride", C.c_size_t),
+                ("len", C.c_size_t), ("lens", C.c_void_p)]
 
 
 class BpgpuError(RuntimeError):
@@ -106,6 +115,8 @@ def lib():
     L.bpgpu_transcript_new.argtypes = [u8p, sz, u8p]
     L.bpgpu_transcript_append_message.argtypes = [u8p, u8p, sz, u8p, sz]
     L.bpgpu_transcript_challenge_bytes.argtypes = [u8p, u8p, sz, u8p, sz]
+    L.bpgpu_transcript_batch.argtypes = [vp, sz, u8p, sz, u8p, sz, C.POINTER(TsOp), sz, u8p]
+    L.bpgpu_transcript_batch_dev.argtypes = [vp, sz, u8p, sz, vp, sz, C.POINTER(TsOp), sz, vp, vp]
     L.bpgpu_rangeproof_verify_batch_ts.argtypes = [vp, sz, sz, sz, u8p, sz, u8p, u8p, sz, u8p, u8p, u8p, u8p]
     L.bpgpu_rangeproof_verify_batch_ts_dev.argtypes = [vp, sz, sz, sz, vp, sz, vp, u8p, vp, vp, vp, vp, vp, vp]
     L.bpgpu_ipp_verify_batch_dev.argtypes = [vp, sz, sz, vp, sz, u8p, sz, u8p, vp, vp, vp, vp, vp, vp, i, vp, vp, vp]
@@ -679,6 +690,71 @@ class Context:
         """bpgpu_rangeproof_prove_batch_ts_dev: every buffer a device address (int), asynchronous on `stream`."""
         self._chk(self._L.bpgpu_rangeproof_prove_batch_ts_dev(self.h, n, m, nbatch, d_values, d_blindings, d_transcripts, transcript_stride, d_rng32, d_proofs,
                                                               d_commitments, d_transcripts_out, stream))
+
+    # ---- batches of transcripts (bpgpu_transcript_batch) ----
+    @staticmethod
+    def _ts_ops(raw):
+        """[(kind, label, data address or None, stride, len, lens address or None)] -> (bpgpu_ts_op array, what must stay alive)"""
+        arr = (TsOp * max(len(raw), 1))()
+        keep = []
+        for o, (kind, label, data, stride, length, lens) in zip(arr, raw):
+            lb = C.create_string_buffer(bytes(label), max(len(label), 1))
+            keep.append(lb)
+            o.kind, o.label, o.label_len, o.data, o.stride, o.len, o.lens = kind, C.addressof(lb), len(label), data, stride, length, lens
+        return arr, keep
+
+    def transcript_batch(self, nbatch, ops, label=None, states=None):
+        """One script over nbatch transcripts, host buffers (bpgpu_transcript_batch).  Start: label (Transcript::new(label) for every row)
+        or states (one 208-byte state for all rows, or one per row).  ops, in order:
+            ("append", label, messages)      messages: one bytes object for every row, or a list of nbatch bytes objects of any lengths
+            ("append_u64", label, xs)        xs: one int, or a list of nbatch
+            ("challenge", label, n)          n challenge bytes per row
+            ("challenge_scalar", label)      the crate's challenge_scalar, 32 canonical bytes per row
+        Returns (states: nbatch x 208 bytes, [per challenge op, in order: list of nbatch bytes objects])."""
+        assert (label is None) != (states is None)
+        assert states is None or len(states) in (TRANSCRIPT_BYTES, TRANSCRIPT_BYTES * nbatch)
+        stride_in = TRANSCRIPT_BYTES if (states is not None and nbatch != 1 and len(states) == TRANSCRIPT_BYTES * nbatch) else 0
+        raw, keep, outs = [], [], []
+        for op in ops:
+            kind, lbl = op[0], bytes(op[1])
+            if kind == "append" and isinstance(op[2], (bytes, bytearray, memoryview)):
+                buf = C.create_string_buffer(bytes(op[2]), max(len(op[2]), 1))
+                keep.append(buf)
+                raw.append((TS_APPEND, lbl, C.addressof(buf), 0, len(op[2]), None))
+            elif kind == "append":
+                msgs = [bytes(m) for m in op[2]]
+                assert len(msgs) == nbatch
+                ln = max([len(m) for m in msgs] or [0])
+                ragged = any(len(m) != ln for m in msgs)
+                buf = C.create_string_buffer(b"".join(m + bytes(ln - len(m)) for m in msgs), max(ln * nbatch, 1))
+                lens = (C.c_uint32 * max(nbatch, 1))(*[len(m) for m in msgs]) if ragged else None
+                keep += [buf, lens]
+                raw.append((TS_APPEND, lbl, C.addressof(buf), ln, ln, C.addressof(lens) if ragged else None))
+            elif kind == "append_u64":
+                xs = [op[2]] if isinstance(op[2], int) else list(op[2])
+                assert isinstance(op[2], int) or len(xs) == nbatch
+                buf = (C.c_uint64 * len(xs))(*xs)
+                keep.append(buf)
+                raw.append((TS_APPEND_U64, lbl, C.addressof(buf), 8 if not isinstance(op[2], int) else 0, 8, None))
+            elif kind in ("challenge", "challenge_scalar"):
+                n = op[2] if kind == "challenge" else 32
+                buf = C.create_string_buffer(max(n * nbatch, 1))
+                keep.append(buf)
+                outs.append((buf, n))
+                raw.append((TS_CHALLENGE if kind == "challenge" else TS_CHALLENGE_SCALAR, lbl, C.addressof(buf), max(n, 1), n, None))
+            else:
+                raise ValueError("unknown transcript operation %r" % (kind,))
+        arr, keep2 = self._ts_ops(raw)
+        out = C.create_string_buffer(TRANSCRIPT_BYTES * max(nbatch, 1))
+        self._chk(self._L.bpgpu_transcript_batch(self.h, nbatch, label, len(label) if label is not None else 0, states, stride_in, arr, len(raw), out))
+        return out.raw[:TRANSCRIPT_BYTES * nbatch], [[b.raw[r * max(n, 1):r * max(n, 1) + n] for r in range(nbatch)] for b, n in outs]
+
+    def transcript_batch_dev(self, nbatch, raw_ops, d_states_out, label=None, d_states_in=None, stride_in=0, stream=None):
+        """bpgpu_transcript_batch_dev: raw_ops = [(kind, label bytes, device address of data, stride, len, device address of lens or None)];
+        the states are device addresses (int); asynchronous on `stream`."""
+        arr, keep = self._ts_ops(raw_ops)
+        self._chk(self._L.bpgpu_transcript_batch_dev(self.h, nbatch, label, len(label) if label is not None else 0, d_states_in, stride_in, arr, len(raw_ops),
+                                                     d_states_out, stream))
 
     # ---- the multi-party aggregation protocol (bpgpu_mpc_*; the typestate classes of range_proof_mpc.py are batches of one) ----
     def mpc_state_bytes(self, n):

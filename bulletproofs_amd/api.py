@@ -156,6 +156,117 @@ class Transcript:
         return out
 
 
+class TranscriptBatch:
+    """n transcripts built and bound on the GPU (bpgpu_transcript_batch): the rows share their labels, the messages are per row.
+    Appends are recorded and sent as ONE script -- by the next challenge, by states(), or when the batch is consumed: wherever a list
+    of Transcript is accepted (RangeProof.verify_batch / verify_batch_combined / prove_batch, LinearProof.create_batch / verify_batch /
+    verify_batch_combined) a TranscriptBatch is, and is left advanced where the list would be.  batch[i] is row i as a Transcript (for
+    the items of RangeProof.verify_mixed_combined, say)."""
+
+    def __init__(self, ctx, label, n, _shared=None, _states=None):
+        self.ctx = getattr(ctx, "ctx", ctx)
+        self.n = int(n)
+        self._label = bytes(label) if (_shared is None and _states is None) else None    # the start is Transcript::new(label) ...
+        self._shared, self._states = _shared, _states                                    # ... or one state for all rows, or one per row
+        self._pending = []
+
+    @staticmethod
+    def from_transcript(ctx, transcript, n):
+        """n rows that all start from one bound Transcript (which is not advanced)"""
+        return TranscriptBatch(ctx, None, n, _shared=bytes(transcript.state))
+
+    @staticmethod
+    def from_states(ctx, states):
+        """rows from per-row states: a list of Transcript / 208-byte states, or their concatenation"""
+        if not isinstance(states, (bytes, bytearray)):
+            states = b"".join(bytes(getattr(t, "state", t)) for t in states)
+        if len(states) % 208:
+            raise ValueError("from_states: 208 bytes per row")
+        return TranscriptBatch(ctx, None, len(states) // 208, _states=bytes(states))
+
+    def __len__(self):
+        return self.n
+
+    def clone(self):
+        t = TranscriptBatch(self.ctx, self._label, self.n, self._shared, self._states)
+        t._pending = list(self._pending)
+        return t
+
+    def _rows(self, what, values, scalar_types):
+        if isinstance(values, scalar_types):
+            return values
+        values = list(values)
+        if len(values) != self.n:
+            raise ValueError("%s: one value per row (%d), or a single one for all rows" % (what, self.n))
+        return values
+
+    def append_message(self, label, messages):
+        """messages: a list of n bytes objects of any lengths, or one bytes object for all rows"""
+        msgs = self._rows("append_message", messages, (bytes, bytearray, memoryview))
+        self._pending.append(("append", bytes(label), bytes(msgs) if isinstance(msgs, (bytes, bytearray, memoryview)) else [bytes(m) for m in msgs]))
+
+    def append_u64(self, label, xs):
+        xs = self._rows("append_u64", xs, int)
+        self._pending.append(("append_u64", bytes(label), xs if isinstance(xs, int) else [int(x) for x in xs]))
+
+    def _flush(self, last=None):
+        """the recorded appends (and one challenge behind them) as scripts of at most TS_MAX_OPS operations"""
+        from ._lib import TS_MAX_OPS
+        script = self._pending + ([last] if last else [])
+        outs = []
+        for lo in range(0, max(len(script), 1), TS_MAX_OPS):
+            chunk = script[lo:lo + TS_MAX_OPS]
+            if self._label is not None:
+                st, o = self.ctx.transcript_batch(self.n, chunk, label=self._label)
+            else:
+                st, o = self.ctx.transcript_batch(self.n, chunk, states=self._shared if self._states is None else self._states)
+            self._label, self._shared, self._states = None, None, st
+            self._pending = self._pending[len(chunk):]      # (a call that raises keeps its appends recorded)
+            outs += o
+        return outs
+
+    def challenge_bytes(self, label, n):
+        """n challenge bytes per row -> list of bytes objects"""
+        return self._flush(("challenge", bytes(label), int(n)))[0]
+
+    def challenge_scalars(self, label):
+        """the crate's challenge_scalar per row -> list of 32-byte canonical scalars"""
+        return self._flush(("challenge_scalar", bytes(label)))[0]
+
+    def states(self):
+        """the rows' states, n x 208 bytes (what the `_ts` entry points take as `transcripts`)"""
+        if self._pending or self._states is None:
+            self._flush()
+        return self._states
+
+    def __getitem__(self, i):
+        if not -self.n <= i < self.n:
+            raise IndexError(i)
+        i %= self.n
+        return Transcript(None, self.states()[208 * i:208 * i + 208])
+
+    def _advance(self, ts):
+        self._label, self._shared, self._states, self._pending = None, None, bytes(ts[:208 * self.n]), []
+
+
+def _per_proof(transcript):
+    return isinstance(transcript, (list, tuple, TranscriptBatch))
+
+
+def _states_of(transcripts):
+    return transcripts.states() if isinstance(transcripts, TranscriptBatch) else b"".join(t.state for t in transcripts)
+
+
+def _advance_all(transcripts, ts):
+    """the callers' transcripts, one per proof, left as the call left them"""
+    if isinstance(transcripts, TranscriptBatch):
+        transcripts._advance(ts)
+        return
+    for i, t in enumerate(transcripts):
+        t.state = ts[208 * i:208 * i + 208]
+        t.fresh_label = None
+
+
 class RangeProof:
     def __init__(self, raw):
         self._raw = raw
@@ -215,16 +326,14 @@ class RangeProof:
         nb, m = len(values), len(values[0])
         if any(len(v) != m for v in values) or len(blindings) != nb or any(len(b) != m for b in blindings):
             raise ValueError("prove_batch: m values and m blindings per proof")
-        per_proof = isinstance(transcript, (list, tuple))
+        per_proof = _per_proof(transcript)
         if per_proof and len(transcript) != nb:
             raise ValueError("prove_batch: one transcript per proof")
-        states = b"".join(t.state for t in transcript) if per_proof else transcript.state
+        states = _states_of(transcript) if per_proof else transcript.state
         proofs, coms, ts = bp_gens.ctx.rangeproof_prove_batch_ts(n, m, [x for v in values for x in v], b"".join(x for b in blindings for x in b), states,
                                                                rng32, want_transcripts=True)
         if per_proof:
-            for i, t in enumerate(transcript):
-                t.state = ts[208 * i:208 * i + 208]
-                t.fresh_label = None
+            _advance_all(transcript, ts)
         pl = len(proofs) // nb
         return [(RangeProof(proofs[pl * i:pl * i + pl]), [coms[32 * (m * i + j):32 * (m * i + j) + 32] for j in range(m)]) for i in range(nb)]
 
@@ -262,14 +371,18 @@ class RangeProof:
     @staticmethod
     def verify_batch(bp_gens, pc_gens, transcript, proofs, commitments, n, rng64=None):
         """proofs[i].verify_multiple(bp_gens, pc_gens, &mut transcript.clone(), &commitments[i], n) for all i in one GPU pass
-        -> list of None / ProofError.  `transcript` itself is not advanced."""
+        -> list of None / ProofError.  `transcript` itself is not advanced.  A list of transcripts or a TranscriptBatch, one per
+        proof: proof i starts from its own; they are not advanced either."""
         if not proofs:
             return []
         bp_gens._check_pedersen(pc_gens)
         raw = [p.to_bytes() if isinstance(p, RangeProof) else bytes(p) for p in proofs]
         m, ln = len(commitments[0]), len(raw[0])
         assert all(len(r) == ln for r in raw) and all(len(c) == m for c in commitments)
-        v = bp_gens.ctx.rangeproof_verify_batch_ts(n, m, b"".join(raw), ln, b"".join(b"".join(c) for c in commitments), transcript.state, rng64)
+        if _per_proof(transcript) and len(transcript) != len(raw):
+            raise ValueError("verify_batch: one transcript per proof")
+        states = _states_of(transcript) if _per_proof(transcript) else transcript.state
+        v = bp_gens.ctx.rangeproof_verify_batch_ts(n, m, b"".join(raw), ln, b"".join(b"".join(c) for c in commitments), states, rng64)
         if len(raw) == 1:
             v = bytes(v)
         return [None if x == 0 else _BY_CODE[x]() for x in v]
@@ -288,10 +401,10 @@ class RangeProof:
         m, ln = len(commitments[0]), len(raw[0])
         assert all(len(r) == ln for r in raw) and all(len(c) == m for c in commitments)
         flat, coms = b"".join(raw), b"".join(b"".join(c) for c in commitments)
-        if isinstance(transcript, (list, tuple)):
+        if _per_proof(transcript):
             if len(transcript) != len(raw):
                 raise ValueError("verify_batch_combined: one transcript per proof")
-            v, _, _ = bp_gens.ctx.rangeproof_verify_rlc_ts(n, m, flat, ln, coms, b"".join(t.state for t in transcript), rng64, weights64)
+            v, _, _ = bp_gens.ctx.rangeproof_verify_rlc_ts(n, m, flat, ln, coms, _states_of(transcript), rng64, weights64)
         elif transcript.fresh_label is None:
             v, _, _ = bp_gens.ctx.rangeproof_verify_rlc_ts(n, m, flat, ln, coms, transcript.state, rng64, weights64)
         else:
@@ -422,23 +535,21 @@ class LinearProof:
         if not Cs:
             return []
         nb, n = len(Cs), len(G)
-        per_proof = isinstance(transcripts, (list, tuple))
+        per_proof = _per_proof(transcripts)
         if per_proof and len(transcripts) != nb:
             raise ValueError("create_batch: one transcript per proof")
         if len(rs) != nb or len(a_vecs) != nb or any(len(a) != n for a in a_vecs) or n == 0 or n & (n - 1):
             raise ValueError("InvalidInputLength")
         shared = len(b_vecs) == n and isinstance(b_vecs[0], (bytes, bytearray))
         b = b"".join(bytes(x) for x in b_vecs) if shared else b"".join(b"".join(bytes(x) for x in v) for v in b_vecs)
-        states = b"".join(t.state for t in transcripts) if per_proof else transcripts.state
+        states = _states_of(transcripts) if per_proof else transcripts.state
         proofs, status, ts = c.linear_create_batch_ts(n, states, b"".join(bytes(x) for x in Cs), b"".join(bytes(x) for x in rs),
                                                       b"".join(b"".join(bytes(x) for x in a) for a in a_vecs), b, b"".join(bytes(g) for g in G), bytes(F),
                                                       bytes(B), rng32=rng_seed32, want_transcripts=True)
         if any(status):
             raise ValueError("an input point does not decode or a scalar is not canonical (proof %d)" % next(i for i, x in enumerate(status) if x))
         if per_proof:
-            for i, t in enumerate(transcripts):
-                t.state = ts[208 * i:208 * i + 208]
-                t.fresh_label = None
+            _advance_all(transcripts, ts)
         pl = len(proofs) // nb
         return [LinearProof(proofs[pl * i:pl * i + pl]) for i in range(nb)]
 
@@ -452,12 +563,6 @@ class LinearProof:
         return n, b"".join(raw), ln, b"".join(bytes(x) for x in Cs), b"".join(bytes(g) for g in G), b
 
     @staticmethod
-    def _advance(transcripts, ts):
-        for i, t in enumerate(transcripts):
-            t.state = ts[208 * i:208 * i + 208]
-            t.fresh_label = None
-
-    @staticmethod
     def verify_batch(ctx, transcript, proofs, Cs, G, F, B, b_vecs):
         """proofs[i].verify(&mut transcript.clone(), &Cs[i], G, F, B, b_vecs[i]) for all i in one GPU pass -> list of None /
         ProofError.  b_vecs: one vector per proof, or a single vector (list of scalars) shared by all.  `transcript`: one Transcript, the
@@ -467,11 +572,11 @@ class LinearProof:
         if not proofs:
             return []
         n, raw, ln, cs, g, b = LinearProof._batch_args(proofs, Cs, G, b_vecs)
-        if isinstance(transcript, (list, tuple)):
+        if _per_proof(transcript):
             if len(transcript) != len(proofs):
                 raise ValueError("verify_batch: one transcript per proof")
-            v, ts = c.linear_verify_batch_ts(n, raw, ln, b"".join(t.state for t in transcript), cs, g, bytes(F), bytes(B), b, want_transcripts=True)
-            LinearProof._advance(transcript, ts)
+            v, ts = c.linear_verify_batch_ts(n, raw, ln, _states_of(transcript), cs, g, bytes(F), bytes(B), b, want_transcripts=True)
+            _advance_all(transcript, ts)
         else:
             v = c.linear_verify_batch(n, raw, ln, cs, g, bytes(F), bytes(B), b, transcript=transcript.state)
         return [None if x == 0 else _BY_CODE[x]() for x in v]
@@ -486,12 +591,12 @@ class LinearProof:
         if not proofs:
             return []
         n, raw, ln, cs, g, b = LinearProof._batch_args(proofs, Cs, G, b_vecs)
-        if isinstance(transcript, (list, tuple)):
+        if _per_proof(transcript):
             if len(transcript) != len(proofs):
                 raise ValueError("verify_batch_combined: one transcript per proof")
-            v, _, _, ts = c.linear_verify_rlc_ts(n, raw, ln, b"".join(t.state for t in transcript), cs, g, bytes(F), bytes(B), b, weights64=weights64,
+            v, _, _, ts = c.linear_verify_rlc_ts(n, raw, ln, _states_of(transcript), cs, g, bytes(F), bytes(B), b, weights64=weights64,
                                                  want_transcripts=True)
-            LinearProof._advance(transcript, ts)
+            _advance_all(transcript, ts)
         else:
             v, _, _ = c.linear_verify_rlc(n, raw, ln, cs, g, bytes(F), bytes(B), b, transcript=transcript.state, weights64=weights64)
         return [None if x == 0 else _BY_CODE[x]() for x in v]

@@ -5985,6 +5985,206 @@ extern "C" int bpgpu_r1cs_witness_check(bpgpu_ctx *c, const bpgpu_r1cs_circuit *
     return BPGPU_OK;
 }
 
+// ---- batches of transcripts (ts_batch.h, k_ts_batch.hip) -------------------------------------------------------------------
+// What the kernel reads besides the rows' data: the ops (tsb_op, device pointers inside), then the label bytes, then -- where the
+// start is Transcript::new(label) -- that one state, computed here once and shared by the rows.
+struct tsb_plan {
+    size_t nops = 0, off_labels = 0, off_st0 = 0, bytes = 0;
+    uint32_t out_len[BPGPU_TS_MAX_OPS];   // bytes a row of op o writes (0: an append)
+};
+
+// the checks both forms share (lens is device memory in one of them: the host form checks it as it stages the rows)
+static int tsb_check(bpgpu_ctx *c, size_t nbatch, const uint8_t *new_label, size_t new_label_len, const void *states_in, size_t stride_in,
+                     const bpgpu_ts_op *ops, size_t nops, const void *states_out, tsb_plan &pl) {
+    if ((new_label != nullptr) == (states_in != nullptr)) return fail(c, BPGPU_ERR_INVALID_ARG, "exactly one of new_label and states_in is needed");
+    if (new_label && new_label_len > BPGPU_TS_MAX_LABEL) return fail(c, BPGPU_ERR_INVALID_ARG, "new_label_len %zu > %d", new_label_len, BPGPU_TS_MAX_LABEL);
+    if (states_in && stride_in != 0 && stride_in != BPGPU_TRANSCRIPT_BYTES)
+        return fail(c, BPGPU_ERR_INVALID_ARG, "stride_in neither 0 nor BPGPU_TRANSCRIPT_BYTES");
+    if (nops > BPGPU_TS_MAX_OPS || (nops && !ops)) return fail(c, BPGPU_ERR_INVALID_ARG, "nops %zu > %d, or ops missing", nops, BPGPU_TS_MAX_OPS);
+    if (nbatch > 0x7fffffffu / 64) return fail(c, BPGPU_ERR_INVALID_ARG, "batch too large");
+    size_t labels = 0;
+    for (size_t o = 0; o < nops; o++) {
+        const bpgpu_ts_op &op = ops[o];
+        if (op.label_len > BPGPU_TS_MAX_LABEL || (op.label_len && !op.label))
+            return fail(c, BPGPU_ERR_INVALID_ARG, "op %zu: label_len %zu > %d, or label missing", o, op.label_len, BPGPU_TS_MAX_LABEL);
+        labels += op.label_len;
+        pl.out_len[o] = 0;
+        size_t need = 0;   // bytes of `data` a row takes
+        switch (op.kind) {
+        case BPGPU_TS_APPEND:
+            if (op.len > BPGPU_TS_MAX_LEN) return fail(c, BPGPU_ERR_INVALID_ARG, "op %zu: len %zu > %d", o, op.len, BPGPU_TS_MAX_LEN);
+            need = op.len;
+            break;
+        case BPGPU_TS_APPEND_U64:
+            if (op.stride != 0 && op.stride != 8) return fail(c, BPGPU_ERR_INVALID_ARG, "op %zu: the stride of uint64 values is 8, or 0 for one value", o);
+            need = 8;
+            break;
+        case BPGPU_TS_CHALLENGE:
+            if (op.len > BPGPU_TS_MAX_CHALLENGE) return fail(c, BPGPU_ERR_INVALID_ARG, "op %zu: challenge of %zu > %d bytes", o, op.len, BPGPU_TS_MAX_CHALLENGE);
+            need = op.len;
+            pl.out_len[o] = (uint32_t)op.len;
+            break;
+        case BPGPU_TS_CHALLENGE_SCALAR:
+            need = 32;
+            pl.out_len[o] = 32;
+            break;
+        default:
+            return fail(c, BPGPU_ERR_INVALID_ARG, "op %zu: unknown kind %u", o, op.kind);
+        }
+        const bool output = op.kind == BPGPU_TS_CHALLENGE || op.kind == BPGPU_TS_CHALLENGE_SCALAR;
+        if (output && (op.stride == 0 || op.stride < need)) return fail(c, BPGPU_ERR_INVALID_ARG, "op %zu: an output needs a stride of at least %zu bytes per row", o, need);
+        if (op.lens && op.kind != BPGPU_TS_APPEND) return fail(c, BPGPU_ERR_INVALID_ARG, "op %zu: lens goes with BPGPU_TS_APPEND only", o);
+        if (nbatch && need && !op.data) return fail(c, BPGPU_ERR_INVALID_ARG, "op %zu: data missing", o);
+    }
+    if (nbatch && !states_out) return fail(c, BPGPU_ERR_INVALID_ARG, "states_out missing");
+    pl.nops = nops;
+    pl.off_labels = nops * sizeof(tsb_op);
+    pl.off_st0 = (pl.off_labels + labels + 7) & ~(size_t)7;
+    pl.bytes = pl.off_st0 + (new_label ? BPGPU_TRANSCRIPT_BYTES : 0);
+    return BPGPU_OK;
+}
+
+// the ops and labels into `blob` (host memory that is then copied to the device); data_of(o) / lens_of(o): where op o's rows are on the device
+template <class D, class Ln>
+static void tsb_fill(char *blob, const tsb_plan &pl, const bpgpu_ts_op *ops, const uint8_t *new_label, size_t new_label_len, D data_of, Ln lens_of) {
+    tsb_op *dst = (tsb_op *)blob;
+    uint32_t loff = 0;
+    for (size_t o = 0; o < pl.nops; o++) {
+        const bpgpu_ts_op &op = ops[o];
+        tsb_op &d = dst[o];
+        d.kind = op.kind == BPGPU_TS_CHALLENGE ? TSB_CHALLENGE : op.kind == BPGPU_TS_CHALLENGE_SCALAR ? TSB_CHALLENGE_SCALAR : TSB_APPEND;
+        d.label_off = loff;
+        d.label_len = (uint32_t)op.label_len;
+        d.len = op.kind == BPGPU_TS_APPEND_U64 ? 8u : op.kind == BPGPU_TS_CHALLENGE_SCALAR ? 64u : (uint32_t)op.len;
+        d.data = (uint8_t *)data_of(o, &d.stride);
+        d.lens = (const uint32_t *)lens_of(o);
+        if (op.label_len) memcpy(blob + pl.off_labels + loff, op.label, op.label_len);
+        loff += (uint32_t)op.label_len;
+    }
+    if (new_label) bpgpu_transcript_new(new_label, new_label_len, (uint8_t *)blob + pl.off_st0);
+}
+
+static void tsb_launch(bpgpu_ctx *c, hipStream_t s, size_t nbatch, const tsb_plan &pl, const char *d_blob, const void *d_states_in, size_t stride_in,
+                       void *d_states_out) {
+    const uint32_t nb32 = (uint32_t)nbatch;
+    LAUNCH(c, s, "ts_batch", k_ts_batch, (nb32 + TSB_BLOCK - 1) / TSB_BLOCK, TSB_BLOCK, nb32, (const uint32_t *)d_states_in, (uint32_t)(stride_in / 4),
+           (uint32_t *)d_states_out, (const tsb_op *)d_blob, (uint32_t)pl.nops, (const uint8_t *)d_blob + pl.off_labels);
+}
+
+extern "C" int bpgpu_transcript_batch(bpgpu_ctx *c, size_t nbatch, const uint8_t *new_label, size_t new_label_len, const uint8_t *states_in, size_t stride_in,
+                                      const bpgpu_ts_op *ops, size_t nops, uint8_t *states_out) {
+    if (!c) return BPGPU_ERR_INVALID_ARG;
+    tsb_plan pl;
+    int rc = tsb_check(c, nbatch, new_label, new_label_len, states_in, stride_in, ops, nops, states_out, pl);
+    if (rc) return rc;
+    if (nbatch == 0) return BPGPU_OK;
+    const size_t TS = BPGPU_TRANSCRIPT_BYTES, nstates = !states_in ? 0 : stride_in ? nbatch : 1;
+    for (size_t r = 0; r < nstates; r++)
+        if (!ts_state_ok(states_in + r * TS)) return fail(c, BPGPU_ERR_INVALID_ARG, "malformed transcript state %zu", r);
+    // one input region: the script, the start states, then op after op its rows (packed at the stride len) and its lens;
+    // one output region: the states, then op after op its challenges (packed at their own length)
+    size_t off_in[BPGPU_TS_MAX_OPS], off_lens[BPGPU_TS_MAX_OPS], off_out[BPGPU_TS_MAX_OPS];
+    const size_t off_states = (pl.bytes + 7) & ~(size_t)7;
+    size_t in_bytes = off_states + nstates * TS, out_bytes = nbatch * TS;
+    for (size_t o = 0; o < nops; o++) {
+        const bpgpu_ts_op &op = ops[o];
+        off_in[o] = off_lens[o] = off_out[o] = 0;
+        if (pl.out_len[o]) {
+            off_out[o] = out_bytes;
+            out_bytes += (nbatch * pl.out_len[o] + 7) & ~(size_t)7;
+            continue;
+        }
+        const size_t len = op.kind == BPGPU_TS_APPEND_U64 ? 8 : op.len;
+        off_in[o] = in_bytes;
+        in_bytes += ((op.stride ? nbatch : 1) * len + 7) & ~(size_t)7;
+        if (op.lens) {
+            off_lens[o] = in_bytes;
+            in_bytes += (nbatch * 4 + 7) & ~(size_t)7;
+        }
+        if (in_bytes > ((size_t)1 << 31)) return fail(c, BPGPU_ERR_INVALID_ARG, "batch too large: more than 2 GiB of messages");
+    }
+    if (out_bytes > ((size_t)1 << 31)) return fail(c, BPGPU_ERR_INVALID_ARG, "batch too large: more than 2 GiB of challenges");
+    std::lock_guard<std::mutex> lk(c->mu);
+    HIPCHK(c, hipSetDevice(c->device));
+    hipStream_t s = c->stream;
+    host_call<bpgpu_ctx> io(c, s);
+    const int r_in = io.in(in_bytes), r_out = io.out(out_bytes);
+    io.secrets(io.in_bytes());   // the messages may be secret, and nothing tells the script from them
+    rc = io.open();
+    if (rc) return io.finish(rc);
+    char *h = io.h(r_in), *d = io.d(r_in);
+    tsb_fill(h, pl, ops, new_label, new_label_len,
+             [&](size_t o, uint64_t *stride) -> char * {
+                 if (pl.out_len[o]) {
+                     *stride = pl.out_len[o];
+                     return io.d(r_out) + off_out[o];
+                 }
+                 *stride = !ops[o].stride ? 0 : ops[o].kind == BPGPU_TS_APPEND_U64 ? 8 : ops[o].len;
+                 return d + off_in[o];
+             },
+             [&](size_t o) -> char * { return ops[o].lens ? d + off_lens[o] : nullptr; });
+    if (nstates) memcpy(h + off_states, states_in, nstates * TS);
+    for (size_t o = 0; o < nops; o++) {
+        const bpgpu_ts_op &op = ops[o];
+        if (pl.out_len[o]) continue;
+        const size_t len = op.kind == BPGPU_TS_APPEND_U64 ? 8 : op.len;
+        // a row is read up to its own length; ONE message for all rows (stride 0) is staged whole, whatever the rows take of it
+        for (size_t r = 0; r < nbatch && op.lens && !rc; r++)
+            if (op.lens[r] > op.len) rc = fail(c, BPGPU_ERR_INVALID_ARG, "op %zu: lens[%zu] = %u > len = %zu", o, r, op.lens[r], op.len);
+        if (rc) return io.finish(rc);   // (rows of earlier ops are staged already: the exit clears them)
+        for (size_t r = 0; r < (op.stride ? nbatch : 1) && len; r++)
+            memcpy(h + off_in[o] + r * len, (const char *)op.data + r * op.stride, op.lens && op.stride ? op.lens[r] : len);
+        if (op.lens) memcpy(h + off_lens[o], op.lens, nbatch * 4);
+    }
+    rc = io.upload();
+    if (rc) return io.finish(rc);
+    tsb_launch(c, s, nbatch, pl, d, new_label ? d + pl.off_st0 : d + off_states, new_label ? 0 : stride_in, io.d(r_out));
+    if (hipGetLastError() != hipSuccess) rc = fail(c, BPGPU_ERR_HIP, "launch failed");
+    rc = io.finish(io.download(rc));
+    if (rc) return rc;
+    const char *ho = io.h(r_out);
+    memcpy(states_out, ho, nbatch * TS);
+    for (size_t o = 0; o < nops; o++)
+        for (size_t r = 0; r < nbatch && pl.out_len[o]; r++) memcpy((char *)ops[o].data + r * ops[o].stride, ho + off_out[o] + r * pl.out_len[o], pl.out_len[o]);
+    return BPGPU_OK;
+}
+
+extern "C" int bpgpu_transcript_batch_dev(bpgpu_ctx *c, size_t nbatch, const uint8_t *new_label, size_t new_label_len, const void *d_states_in, size_t stride_in,
+                                          const bpgpu_ts_op *ops, size_t nops, void *d_states_out, void *stream) {
+    if (!c) return BPGPU_ERR_INVALID_ARG;
+    tsb_plan pl;
+    int rc = tsb_check(c, nbatch, new_label, new_label_len, d_states_in, stride_in, ops, nops, d_states_out, pl);
+    if (rc) return rc;
+    if (nbatch == 0) return BPGPU_OK;
+    uintptr_t al = (uintptr_t)d_states_in | (uintptr_t)d_states_out;
+    for (size_t o = 0; o < nops; o++) al |= (uintptr_t)ops[o].lens;
+    if (al & 3) return fail(c, BPGPU_ERR_INVALID_ARG, "device states and lens must be 4-byte aligned");
+    if (d_states_in == d_states_out && stride_in == 0 && nbatch > 1)
+        return fail(c, BPGPU_ERR_INVALID_ARG, "states_out may be states_in only with one state per row");
+    std::lock_guard<std::mutex> lk(c->mu);
+    HIPCHK(c, hipSetDevice(c->device));
+    hipStream_t s = stream ? (hipStream_t)stream : c->stream;
+    rc = ctx_enter(c, s);
+    if (rc) return rc;
+    do {
+        if ((rc = ipp_reserve(c, align_up(pl.bytes)))) break;
+        char *h = nullptr, *d = c->ipp_buf;
+        if ((rc = c->io.pin_alloc(pl.bytes, &h))) break;
+        tsb_fill(h, pl, ops, new_label, new_label_len,
+                 [&](size_t o, uint64_t *stride) -> char * {
+                     *stride = ops[o].stride;
+                     return (char *)ops[o].data;
+                 },
+                 [&](size_t o) -> char * { return (char *)ops[o].lens; });
+        if (pl.bytes && (rc = HIPRC(c, hipMemcpyAsync(d, h, pl.bytes, hipMemcpyHostToDevice, s)))) break;
+        if ((rc = c->io.pin_mark(s))) break;
+        tsb_launch(c, s, nbatch, pl, d, new_label ? d + pl.off_st0 : d_states_in, new_label ? 0 : stride_in, d_states_out);
+        if (hipGetLastError() != hipSuccess) rc = fail(c, BPGPU_ERR_HIP, "launch failed");
+    } while (0);
+    const int rc2 = ctx_leave(c, s);
+    return rc ? rc : rc2;
+}
+
 // the pool form: the whole call on the next device's context (pool.hip)
 extern "C" int bpgpu_internal_pool_run_on_context(bpgpu_pool *p, size_t nbatch, uint8_t *verdict, int (*run)(bpgpu_ctx *, void *), void *arg);
 namespace {

@@ -26,6 +26,7 @@
 #include "ipp_rlc.h"
 #include "mpc_party.h"
 #include "mpc_dealer.h"
+#include "ts_batch.h"
 
 #define BP_BLOCK 64   // one wavefront per workgroup: under contention a CU rarely has room for four waves of one group at once (256: -8% at 48 streams)
 #define FB_BLOCK 64
@@ -189,5 +190,8 @@ __global__ void k_mpc_accum(fb_params prm, uint32_t nrows, uint32_t nslots, uint
 __global__ void k_mpc_accum_ct(fb_params prm, uint32_t nrows, uint32_t nslots, uint32_t nsplit, uint32_t npairs, const uint32_t *ids_tab, uint32_t ids_stride, const uint32_t *blk_pos, const uint32_t *slot_pos, const fb_digit *digits, const fb_entry *table, ge_ext *partial);
 __global__ void k_mpc_ptsum(uint32_t nthreads, uint32_t m, uint32_t ncol, uint32_t rec, uint32_t off, const uint8_t *in, uint32_t *out, uint32_t *status);
 __global__ void k_mpc_vectors(uint32_t nthreads, uint32_t n, uint32_t m, const uint8_t *shares, const uint32_t *yinv, const uint8_t *skip, uint32_t *a_vec, uint32_t *b_vec, uint32_t *Gf, uint32_t *Hf);
+
+// k_ts_batch.hip
+__global__ void k_ts_batch(uint32_t nbatch, const uint32_t *ts_in, uint32_t ts_in_stride, uint32_t *ts_out, const tsb_op *ops, uint32_t nops, const uint8_t *labels);
 
 #endif

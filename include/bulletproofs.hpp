@@ -17,6 +17,7 @@
 // and everything else is one call into the GPU library.  There is no CPU fallback.
 #ifndef BULLETPROOFS_HPP
 #define BULLETPROOFS_HPP
+#include <algorithm>
 #include <array>
 #include <cstdint>
 #include <cstring>
@@ -171,6 +172,138 @@ class Transcript {
     bool fresh_;
 };
 
+// n transcripts built and bound on the GPU (bpgpu_transcript_batch): the rows share their labels, the messages are per row.  Appends are
+// recorded and sent as ONE script -- by the next challenge, by states(), or when the batch is consumed: the std::vector<Transcript>&
+// overloads of RangeProof::prove_batch / verify_batch_combined and LinearProof::create_batch / verify_batch / verify_batch_combined have a
+// TranscriptBatch& twin that leaves the batch advanced where the vector would be.
+class TranscriptBatch {
+  public:
+    TranscriptBatch(bpgpu_ctx *ctx, const std::string &label, size_t n) : ctx_(ctx), n_(n), label_(label.begin(), label.end()), fresh_(true) {}
+    // n rows that all start from one bound transcript (which is not advanced)
+    static TranscriptBatch from_transcript(bpgpu_ctx *ctx, const Transcript &t, size_t n) {
+        TranscriptBatch b(ctx, "", n);
+        b.fresh_ = false;
+        b.states_.assign(t.state().begin(), t.state().end());
+        b.shared_ = true;
+        return b;
+    }
+    // rows from per-row states
+    static TranscriptBatch from_states(bpgpu_ctx *ctx, const std::vector<Transcript> &ts) {
+        TranscriptBatch b(ctx, "", ts.size());
+        b.assign(ts);
+        return b;
+    }
+    size_t size() const { return n_; }
+    TranscriptBatch clone() const { return *this; }
+
+    // one message per row, of any lengths
+    void append_message(const std::string &label, const std::vector<std::vector<uint8_t>> &messages) {
+        if (messages.size() != n_) throw std::invalid_argument("append_message: one message per row");
+        op o{BPGPU_TS_APPEND, label, {}, 0, 0, {}};
+        for (const auto &m : messages) o.len = std::max(o.len, m.size());
+        o.stride = o.len;
+        o.data.resize(n_ * o.len);
+        bool ragged = false;
+        for (size_t r = 0; r < n_; r++) {
+            if (!messages[r].empty()) std::memcpy(&o.data[r * o.len], messages[r].data(), messages[r].size());
+            o.lens.push_back(static_cast<uint32_t>(messages[r].size()));
+            ragged = ragged || messages[r].size() != o.len;
+        }
+        if (!ragged) o.lens.clear();
+        pending_.push_back(std::move(o));
+    }
+    // one message for all rows
+    void append_message(const std::string &label, const uint8_t *msg, size_t n) {
+        pending_.push_back(op{BPGPU_TS_APPEND, label, std::vector<uint8_t>(msg, msg + n), 0, n, {}});
+    }
+    void append_u64(const std::string &label, const std::vector<uint64_t> &xs) {
+        if (xs.size() != n_) throw std::invalid_argument("append_u64: one value per row");
+        op o{BPGPU_TS_APPEND_U64, label, std::vector<uint8_t>(8 * n_), 8, 8, {}};
+        if (n_) std::memcpy(o.data.data(), xs.data(), 8 * n_);
+        pending_.push_back(std::move(o));
+    }
+    void append_u64(const std::string &label, uint64_t x) {
+        op o{BPGPU_TS_APPEND_U64, label, std::vector<uint8_t>(8), 0, 8, {}};
+        std::memcpy(o.data.data(), &x, 8);
+        pending_.push_back(std::move(o));
+    }
+    // n challenge bytes per row
+    std::vector<std::vector<uint8_t>> challenge_bytes(const std::string &label, size_t n) {
+        pending_.push_back(op{BPGPU_TS_CHALLENGE, label, std::vector<uint8_t>(n_ * n + 1), n ? n : 1, n, {}});
+        const std::vector<uint8_t> flat = flush();
+        std::vector<std::vector<uint8_t>> out(n_);
+        for (size_t r = 0; r < n_; r++) out[r].assign(flat.begin() + r * n, flat.begin() + (r + 1) * n);
+        return out;
+    }
+    // the crate's challenge_scalar per row (transcript.rs:89-95)
+    std::vector<ScalarBytes> challenge_scalars(const std::string &label) {
+        pending_.push_back(op{BPGPU_TS_CHALLENGE_SCALAR, label, std::vector<uint8_t>(n_ * 32 + 1), 32, 0, {}});
+        const std::vector<uint8_t> flat = flush();
+        std::vector<ScalarBytes> out(n_);
+        for (size_t r = 0; r < n_; r++) std::memcpy(out[r].data(), &flat[r * 32], 32);
+        return out;
+    }
+    // the rows' states, n x BPGPU_TRANSCRIPT_BYTES (what the `_ts` entry points take as `transcripts`)
+    const std::vector<uint8_t> &states() {
+        if (!pending_.empty() || fresh_ || shared_) flush();
+        return states_;
+    }
+    Transcript operator[](size_t i) {
+        Transcript t("");
+        std::memcpy(t.state_mut().data(), &states().at(i * BPGPU_TRANSCRIPT_BYTES), BPGPU_TRANSCRIPT_BYTES);
+        return t;
+    }
+    std::vector<Transcript> to_transcripts() {
+        std::vector<Transcript> out;
+        for (size_t i = 0; i < n_; i++) out.push_back((*this)[i]);
+        return out;
+    }
+    // the rows as some call left them
+    void assign(const std::vector<Transcript> &ts) {
+        n_ = ts.size();
+        states_.resize(n_ * BPGPU_TRANSCRIPT_BYTES);
+        for (size_t i = 0; i < n_; i++) std::memcpy(&states_[i * BPGPU_TRANSCRIPT_BYTES], ts[i].state().data(), BPGPU_TRANSCRIPT_BYTES);
+        fresh_ = shared_ = false;
+        pending_.clear();
+    }
+
+  private:
+    struct op {
+        uint32_t kind;
+        std::string label;
+        std::vector<uint8_t> data;
+        size_t stride, len;
+        std::vector<uint32_t> lens;
+    };
+    // the recorded operations as scripts of at most BPGPU_TS_MAX_OPS; returns the last operation's output rows
+    std::vector<uint8_t> flush() {
+        std::vector<op> script;
+        script.swap(pending_);
+        size_t lo = 0;
+        do {
+            const size_t hi = std::min(script.size(), lo + BPGPU_TS_MAX_OPS);
+            std::vector<bpgpu_ts_op> ops;
+            for (size_t o = lo; o < hi; o++)
+                ops.push_back(bpgpu_ts_op{script[o].kind, reinterpret_cast<const uint8_t *>(script[o].label.data()), script[o].label.size(), script[o].data.data(),
+                                          script[o].stride, script[o].len, script[o].lens.empty() ? nullptr : script[o].lens.data()});
+            std::vector<uint8_t> out(n_ * BPGPU_TRANSCRIPT_BYTES + 1);
+            const int rc = bpgpu_transcript_batch(ctx_, n_, !fresh_ ? nullptr : label_.empty() ? reinterpret_cast<const uint8_t *>("") : label_.data(), fresh_ ? label_.size() : 0, fresh_ ? nullptr : states_.data(),
+                                                  fresh_ || shared_ ? 0 : BPGPU_TRANSCRIPT_BYTES, ops.data(), ops.size(), out.data());
+            if (rc != BPGPU_OK) throw GpuError(bpgpu_last_error(ctx_));
+            out.resize(n_ * BPGPU_TRANSCRIPT_BYTES);
+            states_.swap(out);
+            fresh_ = shared_ = false;
+            lo = hi;
+        } while (lo < script.size());
+        return script.empty() ? std::vector<uint8_t>() : std::move(script.back().data);
+    }
+    bpgpu_ctx *ctx_;
+    size_t n_;
+    std::vector<uint8_t> label_, states_;
+    bool fresh_, shared_ = false;
+    std::vector<op> pending_;
+};
+
 namespace detail {
 inline bool scalar_is_canonical(const uint8_t *s) {   // Scalar::from_canonical_bytes
     static const uint8_t L[32] = {0xed, 0xd3, 0xf5, 0x5c, 0x1a, 0x63, 0x12, 0x58, 0xd6, 0x9c, 0xf7, 0xa2, 0xde, 0xf9, 0xde, 0x14,
@@ -277,6 +410,18 @@ class RangeProof {
             for (size_t j = 0; j < m; j++) std::memcpy(out[i].second[j].data(), &vc[32 * (i * m + j)], 32);
             if (transcripts.size() == nb) std::memcpy(transcripts[i].state_mut().data(), &tso[i * TS], TS);
         }
+        return out;
+    }
+    // ... on a TranscriptBatch, one row per proof, left advanced as the vector would be
+    static std::vector<std::pair<RangeProof, std::vector<CompressedRistretto>>> prove_batch(const BulletproofGens &bp_gens, const PedersenGens &pc_gens,
+                                                                                            TranscriptBatch &transcripts,
+                                                                                            const std::vector<std::vector<uint64_t>> &values,
+                                                                                            const std::vector<std::vector<ScalarBytes>> &blindings, size_t n,
+                                                                                            const uint8_t *rng32 = nullptr) {
+        if (transcripts.size() != values.size()) throw std::invalid_argument("prove_batch: one row per proof");
+        std::vector<Transcript> ts = transcripts.to_transcripts();
+        auto out = prove_batch(bp_gens, pc_gens, ts, values, blindings, n, rng32);
+        transcripts.assign(ts);
         return out;
     }
     const std::vector<uint8_t> &to_bytes() const { return bytes_; }
@@ -395,6 +540,12 @@ class RangeProof {
         if (rc != BPGPU_OK) throw GpuError(bpgpu_last_error(bp_gens.ctx()));
         for (size_t i = 0; i < nb; i++) out.push_back(verdict[i] == 0 ? Status::Ok() : Status::Err(static_cast<ProofError>(verdict[i])));
         return out;
+    }
+    static std::vector<Status> verify_batch_combined(const BulletproofGens &bp_gens, const PedersenGens &pc_gens, TranscriptBatch &transcripts,
+                                                     const std::vector<std::vector<uint8_t>> &proofs,
+                                                     const std::vector<std::vector<CompressedRistretto>> &commitments, size_t n,
+                                                     const uint8_t *rng64 = nullptr, const uint8_t *weights64 = nullptr) {
+        return verify_batch_combined(bp_gens, pc_gens, transcripts.to_transcripts(), proofs, commitments, n, rng64, weights64);
     }
 
   private:
@@ -566,6 +717,34 @@ class LinearProof {
             p.bytes_.assign(pb.begin() + i * pl, pb.begin() + (i + 1) * pl);
             out.push_back(std::move(p));
         }
+        return out;
+    }
+    // ... and the same three on a TranscriptBatch, left advanced as the vector would be
+    static std::vector<Status> verify_batch(bpgpu_ctx *ctx, TranscriptBatch &transcripts, const std::vector<LinearProof> &proofs,
+                                            const std::vector<CompressedRistretto> &Cs, const std::vector<CompressedRistretto> &G,
+                                            const CompressedRistretto &F, const CompressedRistretto &B,
+                                            const std::vector<std::vector<ScalarBytes>> &b_vecs) {
+        std::vector<Transcript> ts = transcripts.to_transcripts();
+        std::vector<Status> out = verify_ts(ctx, ts, proofs, Cs, G, F, B, b_vecs, false, nullptr);
+        transcripts.assign(ts);
+        return out;
+    }
+    static std::vector<Status> verify_batch_combined(bpgpu_ctx *ctx, TranscriptBatch &transcripts, const std::vector<LinearProof> &proofs,
+                                                     const std::vector<CompressedRistretto> &Cs, const std::vector<CompressedRistretto> &G,
+                                                     const CompressedRistretto &F, const CompressedRistretto &B,
+                                                     const std::vector<std::vector<ScalarBytes>> &b_vecs, const uint8_t *weights64 = nullptr) {
+        std::vector<Transcript> ts = transcripts.to_transcripts();
+        std::vector<Status> out = verify_ts(ctx, ts, proofs, Cs, G, F, B, b_vecs, true, weights64);
+        transcripts.assign(ts);
+        return out;
+    }
+    static std::vector<LinearProof> create_batch(bpgpu_ctx *ctx, TranscriptBatch &transcripts, const std::vector<CompressedRistretto> &Cs,
+                                                 const std::vector<ScalarBytes> &rs, const std::vector<std::vector<ScalarBytes>> &a_vecs,
+                                                 const std::vector<std::vector<ScalarBytes>> &b_vecs, const std::vector<CompressedRistretto> &G,
+                                                 const CompressedRistretto &F, const CompressedRistretto &B, const uint8_t *rng_seed32 = nullptr) {
+        std::vector<Transcript> ts = transcripts.to_transcripts();
+        std::vector<LinearProof> out = create_batch(ctx, ts, Cs, rs, a_vecs, b_vecs, G, F, B, rng_seed32);
+        transcripts.assign(ts);
         return out;
     }
 

@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """include/bpgpu.h -> the Rust `extern "C"` declarations of INTEGRATION.md section 1.
-    python tools/gen_rust_extern.py            every prototype of the header as a Rust declaration
+    python tools/gen_rust_extern.py            every prototype of the header as a Rust declaration, and every struct the header
+                                               defines with its fields (bpgpu_ts_op) as a #[repr(C)] struct
     python tools/gen_rust_extern.py --missing  only the ones INTEGRATION.md does not carry yet
 (tests/test_abi_and_host.py checks that none is missing.)"""
 import os
@@ -10,7 +11,7 @@ import sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 TYPES = {"int": "c_int", "size_t": "usize", "uint8_t": "u8", "uint32_t": "u32", "uint64_t": "u64", "int64_t": "i64", "char": "c_char", "void": "c_void",
          "bpgpu_ctx": "bpgpu_ctx", "bpgpu_pool": "bpgpu_pool", "bpgpu_ticket": "bpgpu_ticket",
-         "bpgpu_r1cs_circuit": "bpgpu_r1cs_circuit", "bpgpu_r1cs_witness": "bpgpu_r1cs_witness"}
+         "bpgpu_r1cs_circuit": "bpgpu_r1cs_circuit", "bpgpu_r1cs_witness": "bpgpu_r1cs_witness", "bpgpu_ts_op": "bpgpu_ts_op"}
 
 
 def prototypes(text):
@@ -18,6 +19,23 @@ def prototypes(text):
     text = re.sub(r"//[^\n]*", "", text)
     for m in re.finditer(r"^\s*((?:const\s+)?[a-z_0-9]+\s*\**)\s*(bpgpu_[a-z0-9_]+)\s*\(([^;{]*?)\)\s*;", text, flags=re.M | re.S):
         yield m.group(2), m.group(1).strip(), " ".join(m.group(3).split())
+
+
+def structs(text):
+    """typedef struct NAME { fields } NAME; -> (NAME, [(field, C type)])"""
+    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
+    for m in re.finditer(r"typedef\s+struct\s+(bpgpu_[a-z0-9_]+)\s*\{(.*?)\}\s*\1\s*;", text, flags=re.S):
+        fields = []
+        for decl in m.group(2).split(";"):
+            decl = " ".join(decl.split())
+            if decl:
+                f = re.match(r"(.*?)([A-Za-z_][A-Za-z_0-9]*)$", decl)
+                fields.append((f.group(2), f.group(1)))
+        yield m.group(1), fields
+
+
+def rust_struct(name, fields):
+    return "#[repr(C)] pub struct %s { %s }" % (name, ", ".join("pub %s: %s" % (f, rust_type(t)) for f, t in fields))
 
 
 def rust_type(ctype):
@@ -54,7 +72,13 @@ def rust_decl(name, ret, args):
 
 def main():
     hdr = open(os.path.join(ROOT, "include", "bpgpu.h")).read()
-    have = set(re.findall(r"fn (bpgpu_[a-z0-9_]+)", open(os.path.join(ROOT, "INTEGRATION.md")).read()))
+    doc = open(os.path.join(ROOT, "INTEGRATION.md")).read()
+    have = set(re.findall(r"fn (bpgpu_[a-z0-9_]+)", doc))
+    for name, fields in structs(hdr):
+        decl = rust_struct(name, fields)
+        if "--missing" in sys.argv and decl in doc:
+            continue
+        print(decl)
     for name, ret, args in prototypes(hdr):
         if "--missing" in sys.argv and name in have:
             continue
