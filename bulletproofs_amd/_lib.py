@@ -47,6 +47,7 @@ EXPORTS = [
     "bpgpu_pool_msm_batch_shared_submit_dev",
     "bpgpu_mpc_state1_bytes", "bpgpu_mpc_state2_bytes", "bpgpu_mpc_party_bit_commit", "bpgpu_mpc_party_poly_commit", "bpgpu_mpc_party_proof_share",
     "bpgpu_mpc_dealer_bit_challenge", "bpgpu_mpc_dealer_poly_challenge", "bpgpu_mpc_dealer_assemble",
+    "bpgpu_mpc_party_bit_commit_seeded", "bpgpu_mpc_party_poly_commit_seeded",
 ]
 
 TRANSCRIPT_BYTES = 208
@@ -152,6 +153,8 @@ def lib():
     L.bpgpu_mpc_party_bit_commit.argtypes = [vp, sz, sz, C.POINTER(C.c_uint32), C.POINTER(C.c_uint64), u8p, u8p, u8p, u8p]
     L.bpgpu_mpc_party_poly_commit.argtypes = [vp, sz, sz, u8p, u8p, i, u8p, u8p, u8p, u8p]
     L.bpgpu_mpc_party_proof_share.argtypes = [vp, sz, sz, u8p, u8p, i, u8p, u8p]
+    L.bpgpu_mpc_party_bit_commit_seeded.argtypes = [vp, sz, sz, C.POINTER(C.c_uint32), C.POINTER(C.c_uint64), u8p, u8p, C.POINTER(C.c_uint64), u8p, u8p]
+    L.bpgpu_mpc_party_poly_commit_seeded.argtypes = [vp, sz, sz, u8p, u8p, i, u8p, C.POINTER(C.c_uint64), u8p, u8p, u8p]
     L.bpgpu_mpc_dealer_bit_challenge.argtypes = [vp, sz, sz, sz, u8p, u8p, sz, u8p, sz, u8p, u8p, u8p, u8p]
     L.bpgpu_mpc_dealer_poly_challenge.argtypes = [vp, sz, sz, u8p, u8p, u8p, u8p, u8p]
     L.bpgpu_mpc_dealer_assemble.argtypes = [vp, sz, sz, sz, u8p, u8p, u8p, u8p, u8p, u8p, sz, u8p, sz, u8p, i, u8p, u8p, u8p]
@@ -760,10 +763,28 @@ class Context:
     def mpc_state_bytes(self, n):
         return self._L.bpgpu_mpc_state1_bytes(n), self._L.bpgpu_mpc_state2_bytes(n)
 
-    def mpc_party_bit_commit(self, n, party_index, values, blindings, rng=None):
+    @staticmethod
+    def _mpc_seeded(npar, rng, rng_seed32, first_draw):
+        """the seeded form's arguments: None when neither keyword is given, else (rng32 bytes or None, uint64 array or None);
+        first_draw alone: the seeded call with rng32 = NULL (the library draws the seeds)."""
+        if rng_seed32 is None and first_draw is None:
+            return None
+        if rng is not None:
+            raise ValueError("rng bytes and rng_seed32 / first_draw exclude each other")
+        seeds = None if rng_seed32 is None else bytes(rng_seed32)
+        if seeds is not None and len(seeds) != 32 * npar:
+            raise ValueError("rng_seed32: 32 bytes per party")
+        if first_draw is not None and len(first_draw) != npar:
+            raise ValueError("first_draw: one block index per party")
+        return seeds, (None if first_draw is None else (C.c_uint64 * max(npar, 1))(*first_draw))
+
+    def mpc_party_bit_commit(self, n, party_index, values, blindings, rng=None, rng_seed32=None, first_draw=None):
         """Party::new + assign_position_with_rng for len(party_index) parties: returns (bit_commitments 96 bytes each, state1 blobs as one
-        bytearray -- secrets: zero it when done)."""
+        bytearray -- secrets: zero it when done).  rng_seed32 (32 bytes per party; None: seeds drawn by the library) and/or first_draw
+        (one block index per party) instead of rng: bpgpu_mpc_party_bit_commit_seeded, party p's rng being
+        ChaChaRng::from_seed(rng_seed32[32 p:32 p + 32]) advanced by first_draw[p] draws."""
         npar = len(party_index)
+        seeded = self._mpc_seeded(npar, rng, rng_seed32, first_draw)
         assert len(values) == npar and len(blindings) == 32 * npar
         assert rng is None or len(rng) == 64 * (2 * n + 2) * npar
         pi = (C.c_uint32 * max(npar, 1))(*party_index)
@@ -772,22 +793,35 @@ class Context:
         bc = C.create_string_buffer(96 * max(npar, 1))
         st = bytearray(s1 * max(npar, 1))
         stb = (C.c_char * len(st)).from_buffer(st)
-        self._chk(self._L.bpgpu_mpc_party_bit_commit(self.h, n, npar, pi, va, blindings, rng, bc, C.cast(stb, C.c_char_p)))
-        del stb
+        try:
+            if seeded:
+                self._chk(self._L.bpgpu_mpc_party_bit_commit_seeded(self.h, n, npar, pi, va, blindings, seeded[0], seeded[1], bc, C.cast(stb, C.c_char_p)))
+            else:
+                self._chk(self._L.bpgpu_mpc_party_bit_commit(self.h, n, npar, pi, va, blindings, rng, bc, C.cast(stb, C.c_char_p)))
+        finally:
+            del stb
         return bc.raw[:96 * npar], (st if npar else bytearray())
 
-    def mpc_party_poly_commit(self, n, state1, bit_challenges, rng=None):
-        """apply_challenge_with_rng: state1 blobs, (y, z) per party (64 bytes each) or one shared pair -> (poly_commitments, state2 bytearray, status)."""
+    def mpc_party_poly_commit(self, n, state1, bit_challenges, rng=None, rng_seed32=None, first_draw=None):
+        """apply_challenge_with_rng: state1 blobs, (y, z) per party (64 bytes each) or one shared pair -> (poly_commitments, state2 bytearray, status).
+        rng_seed32 / first_draw as in mpc_party_bit_commit (bpgpu_mpc_party_poly_commit_seeded; first_draw None: 2n + 2 for every party)."""
         s1, s2 = self.mpc_state_bytes(n)
         npar = len(state1) // s1
+        seeded = self._mpc_seeded(npar, rng, rng_seed32, first_draw)
         assert len(state1) == npar * s1 and len(bit_challenges) in (64, 64 * npar)
         assert rng is None or len(rng) == 128 * npar
         shared = 1 if (len(bit_challenges) == 64 and npar != 1) else 0
         pc, status = C.create_string_buffer(64 * max(npar, 1)), C.create_string_buffer(max(npar, 1))
         st = bytearray(s2 * max(npar, 1))
         stb = (C.c_char * len(st)).from_buffer(st)
-        self._chk(self._L.bpgpu_mpc_party_poly_commit(self.h, n, npar, bytes(state1), bytes(bit_challenges), shared, rng, pc, C.cast(stb, C.c_char_p), status))
-        del stb
+        try:
+            if seeded:
+                self._chk(self._L.bpgpu_mpc_party_poly_commit_seeded(self.h, n, npar, bytes(state1), bytes(bit_challenges), shared, seeded[0], seeded[1], pc,
+                                                                     C.cast(stb, C.c_char_p), status))
+            else:
+                self._chk(self._L.bpgpu_mpc_party_poly_commit(self.h, n, npar, bytes(state1), bytes(bit_challenges), shared, rng, pc, C.cast(stb, C.c_char_p), status))
+        finally:
+            del stb
         return pc.raw[:64 * npar], (st if npar else bytearray()), status.raw[:npar]
 
     def mpc_party_proof_share(self, n, state2, poly_challenges):

@@ -4061,12 +4061,18 @@ static void mpc_clear_staged_state(host_call<bpgpu_ctx> &io, int r) {
 }
 
 // ---- step 1: Party::new + assign_position_with_rng -------------------------------------------------------------------------
-extern "C" int bpgpu_mpc_party_bit_commit(bpgpu_ctx *c, size_t n, size_t nparties, const uint32_t *party_index, const uint64_t *values, const uint8_t *blindings,
-                                          const uint8_t *rng, uint8_t *bit_commitments, uint8_t *state1) {
+// seeded (bpgpu_mpc_party_bit_commit_seeded): the draws are keystream blocks first_draw[r] ... of ChaChaRng::from_seed(rng32[r]), computed by
+// the lanes that consume them; the rng region of the staging block then holds 32 + 8 bytes per slot in place of 64 (2n + 2)
+static int mpc_bit_commit(bpgpu_ctx *c, size_t n, size_t nparties, const uint32_t *party_index, const uint64_t *values, const uint8_t *blindings, bool seeded,
+                          const uint8_t *rng, const uint64_t *first_draw, uint8_t *bit_commitments, uint8_t *state1) {
     if (!c) return BPGPU_ERR_INVALID_ARG;
     if (nparties == 0) return BPGPU_OK;
     if (!party_index || !values || !blindings || !bit_commitments || !state1) return BPGPU_ERR_INVALID_ARG;
     if (!mpc_bitsize_ok(n)) return fail(c, BPGPU_ERR_INVALID_ARG, "InvalidBitsize: n must be 8, 16, 32 or 64 (party.rs:41-43)");
+    if (seeded && first_draw)
+        for (size_t r = 0; r < nparties; r++)
+            if (first_draw[r] > (uint64_t)0 - (uint64_t)(2 * n + 2))
+                return fail(c, BPGPU_ERR_INVALID_ARG, "first_draw of party %zu: its 2n + 2 draws would run the block counter past 2^64 - 1", r);
     std::lock_guard<std::mutex> lk(c->mu);
     HIPCHK(c, hipSetDevice(c->device));
     if (!c->d_table) return fail(c, BPGPU_ERR_NO_GENS, "generators not loaded");
@@ -4077,7 +4083,7 @@ extern "C" int bpgpu_mpc_party_bit_commit(bpgpu_ctx *c, size_t n, size_t npartie
     if ((uint64_t)mpc_plan_cap(nparties, c->party_capacity) * 2 * (2 * n + 2) > 0x7fffffffull / 64) return fail(c, BPGPU_ERR_INVALID_ARG, "batch too large for this shape");
     mpc_plan pl;
     mpc_make_plan(pl, nparties, party_index, c->party_capacity);
-    const size_t ns = pl.nslots, per_rng = 64 * (2 * n + 2), st_bytes = bpgpu_mpc_state1_bytes(n);
+    const size_t ns = pl.nslots, per_rng = seeded ? 32 + 8 : 64 * (2 * n + 2), st_bytes = bpgpu_mpc_state1_bytes(n);
     hipStream_t s = c->stream;
     host_call<bpgpu_ctx> io(c, s);
     const int r_sp = io.in(ns * 4), r_bp = io.in(ns / MPC_WAVE * 4), r_val = io.in(ns * 8), r_bl = io.in(ns * 32), r_rng = io.in(ns * per_rng);
@@ -4088,16 +4094,21 @@ extern "C" int bpgpu_mpc_party_bit_commit(bpgpu_ctx *c, size_t n, size_t npartie
     memset(io.h(r_sp), 0, io.in_bytes());
     io.put(r_sp, pl.slot_pos.data(), ns * 4);
     io.put(r_bp, pl.blk_pos.data(), ns / MPC_WAVE * 4);
-    char *h_val = io.h(r_val), *h_bl = io.h(r_bl), *h_rng = io.h(r_rng);
-    if (!rng) {   // Scalar::random(&mut thread_rng()): OS CSPRNG (padding slots draw too; they are never read)
-        rc = os_random(c, h_rng, ns * per_rng);
+    char *h_val = io.h(r_val), *h_bl = io.h(r_bl), *h_rng = io.h(r_rng), *h_base = h_rng + ns * 32;   // seeded: seeds [ns][32], then bases [ns]
+    if (!rng) {   // Scalar::random(&mut thread_rng()): OS CSPRNG (padding slots draw too; they are never read); seeded: the seeds alone
+        rc = os_random(c, h_rng, seeded ? ns * 32 : ns * per_rng);
         if (rc) return io.finish(rc);
     }
     for (size_t r = 0; r < nparties; r++) {
         const size_t sl = pl.row_slot[r];
         memcpy(h_val + sl * 8, values + r, 8);
         memcpy(h_bl + sl * 32, blindings + r * 32, 32);
-        if (rng) memcpy(h_rng + sl * per_rng, rng + r * per_rng, per_rng);
+        if (seeded) {   // seed and base go through the same row-to-slot map as the value (first_draw == NULL: 0, the region is pre-zeroed)
+            if (rng) memcpy(h_rng + sl * 32, rng + r * 32, 32);
+            if (first_draw) memcpy(h_base + sl * 8, first_draw + r, 8);
+        } else if (rng) {
+            memcpy(h_rng + sl * per_rng, rng + r * per_rng, per_rng);
+        }
     }
     const uint32_t *d_sp = (const uint32_t *)io.d(r_sp), *d_bp = (const uint32_t *)io.d(r_bp);
     const uint64_t *d_val = (const uint64_t *)io.d(r_val);
@@ -4114,7 +4125,11 @@ extern "C" int bpgpu_mpc_party_bit_commit(bpgpu_ctx *c, size_t n, size_t npartie
             break;
         }
         const uint32_t ns32 = (uint32_t)ns, nbits = (uint32_t)(ns * n), n_b = (ns32 + BP_BLOCK - 1) / BP_BLOCK;
-        LAUNCH(c, s, "mpc_commit1", k_mpc_commit1, n_b + (nbits + BP_BLOCK - 1) / BP_BLOCK, BP_BLOCK, n_b, nbits, (uint32_t)n, ns32, d_sp, d_val, d_bl, d_rng, gsV, gsAS, d_st);
+        if (seeded)
+            LAUNCH(c, s, "mpc_commit1_seeded", k_mpc_commit1_seeded, n_b + (nbits + BP_BLOCK - 1) / BP_BLOCK, BP_BLOCK, n_b, nbits, (uint32_t)n, ns32, d_sp, d_val, d_bl, d_rng,
+                   (const uint64_t *)(d_rng + ns * 32), gsV, gsAS, d_st);
+        else
+            LAUNCH(c, s, "mpc_commit1", k_mpc_commit1, n_b + (nbits + BP_BLOCK - 1) / BP_BLOCK, BP_BLOCK, n_b, nbits, (uint32_t)n, ns32, d_sp, d_val, d_bl, d_rng, gsV, gsAS, d_st);
         rc = mpc_walk(c, s, n, 1, ns32, 2, gsV, d_bp, d_sp, d_v);                       // V_j = v B + v_blinding B~ (party.rs:55)
         if (rc) break;
         rc = mpc_walk(c, s, n, 2, ns32, (uint32_t)row_len, gsAS, d_bp, d_sp, d_as);     // A_j, S_j over B~, G_j(n), H_j(n) (party.rs:99-124)
@@ -4131,6 +4146,15 @@ extern "C" int bpgpu_mpc_party_bit_commit(bpgpu_ctx *c, size_t n, size_t npartie
     mpc_clear_staged_state(io, r_st);
     return rc;
 }
+extern "C" int bpgpu_mpc_party_bit_commit(bpgpu_ctx *c, size_t n, size_t nparties, const uint32_t *party_index, const uint64_t *values, const uint8_t *blindings,
+                                          const uint8_t *rng, uint8_t *bit_commitments, uint8_t *state1) {
+    return mpc_bit_commit(c, n, nparties, party_index, values, blindings, false, rng, nullptr, bit_commitments, state1);
+}
+extern "C" int bpgpu_mpc_party_bit_commit_seeded(bpgpu_ctx *c, size_t n, size_t nparties, const uint32_t *party_index, const uint64_t *values,
+                                                 const uint8_t *blindings, const uint8_t *rng32, const uint64_t *first_draw, uint8_t *bit_commitments,
+                                                 uint8_t *state1) {
+    return mpc_bit_commit(c, n, nparties, party_index, values, blindings, true, rng32, first_draw, bit_commitments, state1);
+}
 
 // validates the headers of caller-held state blobs; pos (optional): the rows' positions
 static int mpc_check_states(bpgpu_ctx *c, size_t n, size_t nrows, const uint8_t *state, size_t st_bytes, uint32_t magic, uint32_t *pos) {
@@ -4145,12 +4169,17 @@ static int mpc_check_states(bpgpu_ctx *c, size_t n, size_t nrows, const uint8_t 
 }
 
 // ---- step 2: PartyAwaitingBitChallenge::apply_challenge_with_rng ------------------------------------------------------------
-extern "C" int bpgpu_mpc_party_poly_commit(bpgpu_ctx *c, size_t n, size_t nparties, const uint8_t *state1, const uint8_t *bit_challenges, int challenges_shared,
-                                           const uint8_t *rng, uint8_t *poly_commitments, uint8_t *state2, uint8_t *status) {
+// seeded (bpgpu_mpc_party_poly_commit_seeded): as mpc_bit_commit; first_draw == NULL: 2n + 2, one ChaChaRng carried through both steps
+static int mpc_poly_commit(bpgpu_ctx *c, size_t n, size_t nparties, const uint8_t *state1, const uint8_t *bit_challenges, int challenges_shared, bool seeded,
+                           const uint8_t *rng, const uint64_t *first_draw, uint8_t *poly_commitments, uint8_t *state2, uint8_t *status) {
     if (!c) return BPGPU_ERR_INVALID_ARG;
     if (nparties == 0) return BPGPU_OK;
     if (!state1 || !bit_challenges || !poly_commitments || !state2 || !status) return BPGPU_ERR_INVALID_ARG;
     if (!mpc_bitsize_ok(n)) return fail(c, BPGPU_ERR_INVALID_ARG, "InvalidBitsize: n must be 8, 16, 32 or 64 (party.rs:41-43)");
+    if (seeded && first_draw)
+        for (size_t r = 0; r < nparties; r++)
+            if (first_draw[r] > (uint64_t)0 - 2)
+                return fail(c, BPGPU_ERR_INVALID_ARG, "first_draw of party %zu: its 2 draws would run the block counter past 2^64 - 1", r);
     std::lock_guard<std::mutex> lk(c->mu);
     HIPCHK(c, hipSetDevice(c->device));
     if (!c->d_table) return fail(c, BPGPU_ERR_NO_GENS, "generators not loaded");
@@ -4162,10 +4191,10 @@ extern "C" int bpgpu_mpc_party_poly_commit(bpgpu_ctx *c, size_t n, size_t nparti
     if ((uint64_t)mpc_plan_cap(nparties, c->party_capacity) * st2_bytes > 0x7fffffffull) return fail(c, BPGPU_ERR_INVALID_ARG, "batch too large for this shape");
     mpc_plan pl;
     mpc_make_plan(pl, nparties, pos.data(), c->party_capacity);
-    const size_t ns = pl.nslots, nch = challenges_shared ? 1 : ns;
+    const size_t ns = pl.nslots, nch = challenges_shared ? 1 : ns, per_rng = seeded ? 32 + 8 : 128;
     hipStream_t s = c->stream;
     host_call<bpgpu_ctx> io(c, s);
-    const int r_sp = io.in(ns * 4), r_bp = io.in(ns / MPC_WAVE * 4), r_s1 = io.in(ns * st1_bytes), r_ch = io.in(nch * 64), r_rng = io.in(ns * 128);
+    const int r_sp = io.in(ns * 4), r_bp = io.in(ns / MPC_WAVE * 4), r_s1 = io.in(ns * st1_bytes), r_ch = io.in(nch * 64), r_rng = io.in(ns * per_rng);
     const int r_s2 = io.out(ns * st2_bytes), r_t = io.out(2 * ns * 32), r_stat = io.out(ns * 4);
     io.secrets(io.in_bytes());
     rc = io.open();
@@ -4173,17 +4202,23 @@ extern "C" int bpgpu_mpc_party_poly_commit(bpgpu_ctx *c, size_t n, size_t nparti
     memset(io.h(r_sp), 0, io.in_bytes());
     io.put(r_sp, pl.slot_pos.data(), ns * 4);
     io.put(r_bp, pl.blk_pos.data(), ns / MPC_WAVE * 4);
-    char *h_s1 = io.h(r_s1), *h_ch = io.h(r_ch), *h_rng = io.h(r_rng);
+    char *h_s1 = io.h(r_s1), *h_ch = io.h(r_ch), *h_rng = io.h(r_rng), *h_base = h_rng + ns * 32;   // seeded: seeds [ns][32], then bases [ns]
     if (!rng) {
-        rc = os_random(c, h_rng, ns * 128);
+        rc = os_random(c, h_rng, seeded ? ns * 32 : ns * per_rng);
         if (rc) return io.finish(rc);
     }
     if (challenges_shared) memcpy(h_ch, bit_challenges, 64);
+    const uint64_t carried = 2 * n + 2;
     for (size_t r = 0; r < nparties; r++) {
         const size_t sl = pl.row_slot[r];
         memcpy(h_s1 + sl * st1_bytes, state1 + r * st1_bytes, st1_bytes);
         if (!challenges_shared) memcpy(h_ch + sl * 64, bit_challenges + r * 64, 64);
-        if (rng) memcpy(h_rng + sl * 128, rng + r * 128, 128);
+        if (seeded) {
+            if (rng) memcpy(h_rng + sl * 32, rng + r * 32, 32);
+            memcpy(h_base + sl * 8, first_draw ? first_draw + r : &carried, 8);
+        } else if (rng) {
+            memcpy(h_rng + sl * per_rng, rng + r * per_rng, per_rng);
+        }
     }
     const uint32_t *d_sp = (const uint32_t *)io.d(r_sp), *d_bp = (const uint32_t *)io.d(r_bp), *d_s1 = (const uint32_t *)io.d(r_s1);
     const uint8_t *d_ch = (const uint8_t *)io.d(r_ch), *d_rng = (const uint8_t *)io.d(r_rng);
@@ -4199,8 +4234,12 @@ extern "C" int bpgpu_mpc_party_poly_commit(bpgpu_ctx *c, size_t n, size_t nparti
             break;
         }
         const uint32_t ns32 = (uint32_t)ns;
-        LAUNCH(c, s, "mpc_poly", k_mpc_poly, (ns32 + BP_BLOCK - 1) / BP_BLOCK, BP_BLOCK, (uint32_t)n, ns32, d_sp, d_s1, d_ch, challenges_shared ? 1u : 0u, d_rng, d_s2, gsT,
-               d_stat);
+        if (seeded)
+            LAUNCH(c, s, "mpc_poly_seeded", k_mpc_poly_seeded, (ns32 + BP_BLOCK - 1) / BP_BLOCK, BP_BLOCK, (uint32_t)n, ns32, d_sp, d_s1, d_ch, challenges_shared ? 1u : 0u,
+                   d_rng, (const uint64_t *)(d_rng + ns * 32), d_s2, gsT, d_stat);
+        else
+            LAUNCH(c, s, "mpc_poly", k_mpc_poly, (ns32 + BP_BLOCK - 1) / BP_BLOCK, BP_BLOCK, (uint32_t)n, ns32, d_sp, d_s1, d_ch, challenges_shared ? 1u : 0u, d_rng, d_s2, gsT,
+                   d_stat);
         rc = mpc_walk(c, s, n, 2, ns32, 2, gsT, d_bp, d_sp, d_t);   // T_i_j = t_i B + t_i_blinding B~ (party.rs:224-227)
     } while (0);
     rc = io.finish(io.download(rc));
@@ -4220,6 +4259,15 @@ extern "C" int bpgpu_mpc_party_poly_commit(bpgpu_ctx *c, size_t n, size_t nparti
         }
     mpc_clear_staged_state(io, r_s2);
     return rc;
+}
+extern "C" int bpgpu_mpc_party_poly_commit(bpgpu_ctx *c, size_t n, size_t nparties, const uint8_t *state1, const uint8_t *bit_challenges, int challenges_shared,
+                                           const uint8_t *rng, uint8_t *poly_commitments, uint8_t *state2, uint8_t *status) {
+    return mpc_poly_commit(c, n, nparties, state1, bit_challenges, challenges_shared, false, rng, nullptr, poly_commitments, state2, status);
+}
+extern "C" int bpgpu_mpc_party_poly_commit_seeded(bpgpu_ctx *c, size_t n, size_t nparties, const uint8_t *state1, const uint8_t *bit_challenges,
+                                                  int challenges_shared, const uint8_t *rng32, const uint64_t *first_draw, uint8_t *poly_commitments,
+                                                  uint8_t *state2, uint8_t *status) {
+    return mpc_poly_commit(c, n, nparties, state1, bit_challenges, challenges_shared, true, rng32, first_draw, poly_commitments, state2, status);
 }
 
 // ---- step 3: PartyAwaitingPolyChallenge::apply_challenge -------------------------------------------------------------------

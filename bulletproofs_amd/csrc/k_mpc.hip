@@ -17,10 +17,32 @@ __global__ void __launch_bounds__(BP_BLOCK) k_mpc_commit1(uint32_t n_b, uint32_t
     }
 }
 
+// the seeded twin (bpgpu_mpc_party_bit_commit_seeded): seeds [nslots][32], base [nslots] -- lane (slot, i) computes the keystream
+// blocks of s_L[i] and s_R[i] itself, the slot lane those of a_blinding and s_blinding; padding slots return before any draw
+__global__ void __launch_bounds__(BP_BLOCK) k_mpc_commit1_seeded(uint32_t n_b, uint32_t nthreads, uint32_t n, uint32_t nslots, const uint32_t *slot_pos,
+                                                                  const uint64_t *values, const uint8_t *blindings, const uint8_t *seeds, const uint64_t *base,
+                                                                  uint32_t *gsV, uint32_t *gsAS, uint32_t *st1) {
+    const mpc_from_seed src{seeds, base};
+    if (blockIdx.x < n_b) {
+        const uint32_t s = blockIdx.x * BP_BLOCK + threadIdx.x;
+        if (s < nslots) mpc_blind_lane(s, n, nslots, slot_pos, values, blindings, src, gsV, gsAS, st1);
+    } else {
+        const uint32_t tid = (blockIdx.x - n_b) * BP_BLOCK + threadIdx.x;
+        if (tid < nthreads) mpc_bits_lane(tid, n, nslots, slot_pos, values, src, gsAS, st1);
+    }
+}
+
 __global__ void __launch_bounds__(BP_BLOCK) k_mpc_poly(uint32_t n, uint32_t nslots, const uint32_t *slot_pos, const uint32_t *st1, const uint8_t *chal,
                                                         uint32_t chal_shared, const uint8_t *rng, uint32_t *st2, uint32_t *gsT, uint32_t *status) {
     const uint32_t s = blockIdx.x * blockDim.x + threadIdx.x;
     if (s < nslots) mpc_poly_thread(s, n, nslots, slot_pos, st1, chal, chal_shared, rng, st2, gsT, status);
+}
+// the seeded twin (bpgpu_mpc_party_poly_commit_seeded): t_1_blinding, t_2_blinding are blocks base[s], base[s] + 1 of seeds[s]
+__global__ void __launch_bounds__(BP_BLOCK) k_mpc_poly_seeded(uint32_t n, uint32_t nslots, const uint32_t *slot_pos, const uint32_t *st1, const uint8_t *chal,
+                                                               uint32_t chal_shared, const uint8_t *seeds, const uint64_t *base, uint32_t *st2, uint32_t *gsT,
+                                                               uint32_t *status) {
+    const uint32_t s = blockIdx.x * blockDim.x + threadIdx.x;
+    if (s < nslots) mpc_poly_lane(s, n, nslots, slot_pos, st1, chal, chal_shared, mpc_from_seed{seeds, base}, st2, gsT, status);
 }
 
 __global__ void __launch_bounds__(BP_BLOCK) k_mpc_share(uint32_t nrows, uint32_t n, const uint32_t *st2, const uint8_t *xs, uint32_t x_shared, uint32_t *shares,

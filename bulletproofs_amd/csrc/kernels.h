@@ -184,7 +184,9 @@ __global__ void k_linc_final(linc_shape sh, const uint32_t *msm_out, const uint8
 
 // k_mpc.hip
 __global__ void k_mpc_commit1(uint32_t n_b, uint32_t nthreads, uint32_t n, uint32_t nslots, const uint32_t *slot_pos, const uint64_t *values, const uint8_t *blindings, const uint8_t *rng, uint32_t *gsV, uint32_t *gsAS, uint32_t *st1);
+__global__ void k_mpc_commit1_seeded(uint32_t n_b, uint32_t nthreads, uint32_t n, uint32_t nslots, const uint32_t *slot_pos, const uint64_t *values, const uint8_t *blindings, const uint8_t *seeds, const uint64_t *base, uint32_t *gsV, uint32_t *gsAS, uint32_t *st1);
 __global__ void k_mpc_poly(uint32_t n, uint32_t nslots, const uint32_t *slot_pos, const uint32_t *st1, const uint8_t *chal, uint32_t chal_shared, const uint8_t *rng, uint32_t *st2, uint32_t *gsT, uint32_t *status);
+__global__ void k_mpc_poly_seeded(uint32_t n, uint32_t nslots, const uint32_t *slot_pos, const uint32_t *st1, const uint8_t *chal, uint32_t chal_shared, const uint8_t *seeds, const uint64_t *base, uint32_t *st2, uint32_t *gsT, uint32_t *status);
 __global__ void k_mpc_share(uint32_t nrows, uint32_t n, const uint32_t *st2, const uint8_t *xs, uint32_t x_shared, uint32_t *shares, uint8_t *status);
 __global__ void k_mpc_accum(fb_params prm, uint32_t nrows, uint32_t nslots, uint32_t nsplit, uint32_t npairs, const uint32_t *ids_tab, uint32_t ids_stride, const uint32_t *blk_pos, const uint32_t *slot_pos, const fb_digit *digits, const fb_entry *table, ge_ext *partial);
 __global__ void k_mpc_accum_ct(fb_params prm, uint32_t nrows, uint32_t nslots, uint32_t nsplit, uint32_t npairs, const uint32_t *ids_tab, uint32_t ids_stride, const uint32_t *blk_pos, const uint32_t *slot_pos, const fb_digit *digits, const fb_entry *table, ge_ext *partial);

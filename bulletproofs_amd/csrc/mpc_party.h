@@ -71,11 +71,28 @@ inline void mpc_fill_ids(uint32_t *ids, uint32_t n, uint32_t j, uint32_t gens_ca
     }
 }
 
+// ---- where a party's draws come from ----------------------------------------------------------------------------------------
+// draw(r, s, d) = the d-th random scalar of the step for the party in slot s (the reference's order: step 1 a_blinding, s_blinding,
+// s_L[0..n), s_R[0..n) (party.rs:87-118); step 2 t_1_blinding, t_2_blinding (party.rs:224-227)).  Either pre-expanded bytes, `ndraws`
+// draws of 64 bytes per slot (bpgpu_mpc_party_*), or the party's ChaChaRng: a 32-byte seed and the block index of the step's first draw
+// per slot (bpgpu_mpc_party_*_seeded) -- the lane that consumes a draw computes its keystream block (rpp_draw), no buffer of draws exists.
+struct mpc_from_bytes {
+    const uint8_t *rng;      // [slot][ndraws][64]
+    uint32_t ndraws;
+    BP_HD void draw(sc &r, uint32_t s, uint64_t d) const { rpp_wide(r, rng + (uint64_t)s * 64 * ndraws + 64 * d); }
+};
+struct mpc_from_seed {
+    const uint8_t *seeds;    // [slot][32]
+    const uint64_t *base;    // [slot]: the 64-bit block counter of draw 0 (the host has checked that base + draws does not wrap)
+    BP_HD void draw(sc &r, uint32_t s, uint64_t d) const { rpp_draw(r, seeds + 32 * (uint64_t)s, base[s] + d); }
+};
+
 // ---- step 1 ------------------------------------------------------------------------------------------------------------------
 // Scalar rows: gsV [nslots][2] (B~, B); gsAS [2 nslots][2n + 2]: row s = A, row nslots + s = S.  All pre-zeroed.
 // lane = slot: header, blindings, the V row, the blinding terms of A and S
-BP_HD void mpc_blind_thread(uint32_t s, uint32_t n, uint32_t nslots, const uint32_t *slot_pos, const uint64_t *values, const uint8_t *blindings,
-                            const uint8_t *rng, uint32_t *gsV, uint32_t *gsAS, uint32_t *st1) {
+template <class Src>
+BP_HD void mpc_blind_lane(uint32_t s, uint32_t n, uint32_t nslots, const uint32_t *slot_pos, const uint64_t *values, const uint8_t *blindings, const Src &src,
+                          uint32_t *gsV, uint32_t *gsAS, uint32_t *st1) {
     const uint32_t j = slot_pos[s];
     if (j == MPC_NO_ROW) return;
     uint32_t *st = st1 + (uint64_t)s * MPC_ST1_WORDS(n);
@@ -88,7 +105,6 @@ BP_HD void mpc_blind_thread(uint32_t s, uint32_t n, uint32_t nslots, const uint3
     st[5] = (uint32_t)(v >> 32);
     st[6] = 0;
     st[7] = 0;
-    const uint8_t *r = rng + (uint64_t)s * 64 * (2 * n + 2);
     const uint32_t row_len = 2 * n + 2;
     sc x;
     uint32_t w[16];
@@ -102,16 +118,21 @@ BP_HD void mpc_blind_thread(uint32_t s, uint32_t n, uint32_t nslots, const uint3
     vs.v[0] = (uint32_t)v;
     vs.v[1] = (uint32_t)(v >> 32);
     ippc_st(gsV + (uint64_t)s * 16 + 8, vs);                      // v on B
-    rpp_wide(x, r);
+    src.draw(x, s, 0);
     ippc_st(st + 8 * MPC1_ABL, x);
     ippc_st(gsAS + (uint64_t)s * row_len * 8, x);
-    rpp_wide(x, r + 64);
+    src.draw(x, s, 1);
     ippc_st(st + 8 * MPC1_SBL, x);
     ippc_st(gsAS + (uint64_t)(nslots + s) * row_len * 8, x);
 }
+BP_HD void mpc_blind_thread(uint32_t s, uint32_t n, uint32_t nslots, const uint32_t *slot_pos, const uint64_t *values, const uint8_t *blindings,
+                            const uint8_t *rng, uint32_t *gsV, uint32_t *gsAS, uint32_t *st1) {
+    mpc_blind_lane(s, n, nslots, slot_pos, values, blindings, mpc_from_bytes{rng, 2 * n + 2}, gsV, gsAS, st1);
+}
 // lane = (slot, bit i): a_L on G_{j,i}, a_R = a_L - 1 on H_{j,i}; s_L, s_R (party.rs:99-124)
-BP_HD void mpc_bits_thread(uint32_t tid, uint32_t n, uint32_t nslots, const uint32_t *slot_pos, const uint64_t *values, const uint8_t *rng,
-                           uint32_t *gsAS, uint32_t *st1) {
+template <class Src>
+BP_HD void mpc_bits_lane(uint32_t tid, uint32_t n, uint32_t nslots, const uint32_t *slot_pos, const uint64_t *values, const Src &src, uint32_t *gsAS,
+                         uint32_t *st1) {
     const uint32_t s = tid / n, i = tid - s * n;
     if (slot_pos[s] == MPC_NO_ROW) return;
     const bool bit = (values[s] >> i) & 1;
@@ -124,21 +145,25 @@ BP_HD void mpc_bits_thread(uint32_t tid, uint32_t n, uint32_t nslots, const uint
     sc_neg(m1, one);
     ippc_st(rowA + 8 * (2 + i), bit ? one : zero);
     ippc_st(rowA + 8 * (2 + n + i), bit ? zero : m1);
-    const uint8_t *r = rng + (uint64_t)s * 64 * (2 * n + 2) + 128;
-    rpp_wide(x, r + 64 * (uint64_t)i);
+    src.draw(x, s, 2 + (uint64_t)i);
     ippc_st(rowS + 8 * (2 + i), x);
     ippc_st(st + 8 * (MPC1_SL + i), x);
-    rpp_wide(x, r + 64 * (uint64_t)(n + i));
+    src.draw(x, s, 2 + (uint64_t)(n + i));
     ippc_st(rowS + 8 * (2 + n + i), x);
     ippc_st(st + 8 * (MPC1_SL + n + i), x);
+}
+BP_HD void mpc_bits_thread(uint32_t tid, uint32_t n, uint32_t nslots, const uint32_t *slot_pos, const uint64_t *values, const uint8_t *rng,
+                           uint32_t *gsAS, uint32_t *st1) {
+    mpc_bits_lane(tid, n, nslots, slot_pos, values, mpc_from_bytes{rng, 2 * n + 2}, gsAS, st1);
 }
 
 // ---- step 2 ------------------------------------------------------------------------------------------------------------------
 // lane = slot: l(X) = l0 + l1 X, r(X) = r0 + r1 X, t(X) = <l, r> with the offsets y^(jn), z^2 z^j of the row's position
 // (party.rs:189-222, the body of rpp_poly_thread), t_1_blinding, t_2_blinding; the T rows gsT [2 nslots][2]: row s = T_1, nslots + s = T_2.
 // chal: y, z per slot (64 bytes) or one pair.  st2, gsT, status pre-zeroed: a rejected row leaves zeros.
-BP_HD void mpc_poly_thread(uint32_t s, uint32_t n, uint32_t nslots, const uint32_t *slot_pos, const uint32_t *st1, const uint8_t *chal, uint32_t chal_shared,
-                           const uint8_t *rng, uint32_t *st2, uint32_t *gsT, uint32_t *status) {
+template <class Src>
+BP_HD void mpc_poly_lane(uint32_t s, uint32_t n, uint32_t nslots, const uint32_t *slot_pos, const uint32_t *st1, const uint8_t *chal, uint32_t chal_shared,
+                         const Src &src, uint32_t *st2, uint32_t *gsT, uint32_t *status) {
     if (slot_pos[s] == MPC_NO_ROW) return;
     const uint32_t *a = st1 + (uint64_t)s * MPC_ST1_WORDS(n);
     uint32_t *o = st2 + (uint64_t)s * MPC_ST2_WORDS(n);
@@ -212,15 +237,18 @@ BP_HD void mpc_poly_thread(uint32_t s, uint32_t n, uint32_t nslots, const uint32
     ippc_st(o + 8 * MPC2_T0, t0);
     ippc_st(o + 8 * MPC2_T1, t1);
     ippc_st(o + 8 * MPC2_T2, t2);
-    const uint8_t *r = rng + (uint64_t)s * 128;
-    rpp_wide(x, r);
+    src.draw(x, s, 0);
     ippc_st(o + 8 * MPC2_T1B, x);
     ippc_st(gsT + (uint64_t)s * 16, x);                           // T_1 = t_1 B + t_1_blinding B~ (party.rs:224-227)
     ippc_st(gsT + (uint64_t)s * 16 + 8, t1);
-    rpp_wide(x, r + 64);
+    src.draw(x, s, 1);
     ippc_st(o + 8 * MPC2_T2B, x);
     ippc_st(gsT + (uint64_t)(nslots + s) * 16, x);
     ippc_st(gsT + (uint64_t)(nslots + s) * 16 + 8, t2);
+}
+BP_HD void mpc_poly_thread(uint32_t s, uint32_t n, uint32_t nslots, const uint32_t *slot_pos, const uint32_t *st1, const uint8_t *chal, uint32_t chal_shared,
+                           const uint8_t *rng, uint32_t *st2, uint32_t *gsT, uint32_t *status) {
+    mpc_poly_lane(s, n, nslots, slot_pos, st1, chal, chal_shared, mpc_from_bytes{rng, 2}, st2, gsT, status);
 }
 
 // ---- step 3 ------------------------------------------------------------------------------------------------------------------

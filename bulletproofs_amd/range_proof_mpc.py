@@ -131,6 +131,15 @@ def _check_shape(bp_gens, n, m=None):
         raise MPCError.InvalidGeneratorsLength()
 
 
+def _seeded_kw(rng_bytes, rng_seed32, first_draw):
+    """keywords of the seeded party calls (Context.mpc_party_*_commit) for a batch of one; {} when the step is not seeded"""
+    if rng_seed32 is None and first_draw is None:
+        return {}
+    if rng_bytes is not None or (rng_seed32 is not None and len(rng_seed32) != 32):
+        raise ValueError("rng_seed32: 32 bytes, and not together with rng_bytes")
+    return {"rng_seed32": None if rng_seed32 is None else bytes(rng_seed32), "first_draw": None if first_draw is None else [int(first_draw)]}
+
+
 class _State:
     _blob = None   # party states: the secret blob (bytearray)
 
@@ -167,14 +176,17 @@ class PartyAwaitingPosition(_State):
         self.bp_gens, self.n, self._v = bp_gens, n, v
         self._blob = bytearray(v_blinding)
 
-    def assign_position_with_rng(self, j, rng_bytes=None):
+    def assign_position_with_rng(self, j, rng_bytes=None, *, rng_seed32=None, first_draw=None):
         """party.rs:73-144.  rng_bytes: the 64 (2n + 2) bytes the rng would hand Scalar::random (a_blinding, s_blinding, s_L, s_R), or
-        None for the OS CSPRNG.  Returns (PartyAwaitingBitChallenge, BitCommitment)."""
+        None for the OS CSPRNG.  rng_seed32 instead: the rng is ChaChaRng::from_seed(rng_seed32), its scalars drawn on the device
+        (bpgpu_mpc_party_bit_commit_seeded), first_draw (default 0) the number of scalars it has handed out before this step -- j (2n + 2)
+        for party j of a prove_multiple_with_rng.  Returns (PartyAwaitingBitChallenge, BitCommitment)."""
+        kw = _seeded_kw(rng_bytes, rng_seed32, first_draw)
         self._consume()
         try:
             if self.bp_gens.party_capacity <= j:
                 raise MPCError.InvalidGeneratorsLength()
-            bc, st = self.bp_gens.ctx.mpc_party_bit_commit(self.n, [j], [self._v], bytes(self._blob), rng_bytes)
+            bc, st = self.bp_gens.ctx.mpc_party_bit_commit(self.n, [j], [self._v], bytes(self._blob), rng_bytes, **kw)
         finally:
             self.zeroize()
             self._v = 0
@@ -188,11 +200,14 @@ class PartyAwaitingBitChallenge(_State):
     def __init__(self, bp_gens, n, j, blob):
         self.bp_gens, self.n, self.j, self._blob = bp_gens, n, j, blob
 
-    def apply_challenge_with_rng(self, vc, rng_bytes=None):
-        """party.rs:182-237.  rng_bytes: 128 bytes (t_1_blinding, t_2_blinding) or None.  Returns (PartyAwaitingPolyChallenge, PolyCommitment)."""
+    def apply_challenge_with_rng(self, vc, rng_bytes=None, *, rng_seed32=None, first_draw=None):
+        """party.rs:182-237.  rng_bytes: 128 bytes (t_1_blinding, t_2_blinding) or None.  rng_seed32 / first_draw as in assign_position_with_rng
+        (bpgpu_mpc_party_poly_commit_seeded); first_draw defaults to 2n + 2, the rng carried on from assign_position_with_rng -- m (2n + 2) + 2j
+        for party j of a prove_multiple_with_rng.  Returns (PartyAwaitingPolyChallenge, PolyCommitment)."""
+        kw = _seeded_kw(rng_bytes, rng_seed32, first_draw)
         self._consume()
         try:
-            pc, st, status = self.bp_gens.ctx.mpc_party_poly_commit(self.n, self._blob, vc.to_bytes(), rng_bytes)
+            pc, st, status = self.bp_gens.ctx.mpc_party_poly_commit(self.n, self._blob, vc.to_bytes(), rng_bytes, **kw)
         finally:
             self.zeroize()
         if status[0] != MPC_OK:

@@ -1014,6 +1014,30 @@ int bpgpu_mpc_party_bit_commit(bpgpu_ctx *ctx, size_t n, size_t nparties, const 
 int bpgpu_mpc_party_poly_commit(bpgpu_ctx *ctx, size_t n, size_t nparties, const uint8_t *state1, const uint8_t *bit_challenges,
                                 int challenges_shared, const uint8_t *rng, uint8_t *poly_commitments, uint8_t *state2,
                                 uint8_t *status);
+/* The SEEDED forms of the two steps that draw: "this party's rng is ChaChaRng::from_seed(s)", as bpgpu_rangeproof_prove_batch_ts
+ * speaks of a proof's.  Every random scalar is a ChaCha20 block computed by the lane that consumes it: 32 + 8 bytes per party
+ * cross the staging block in place of 64 (2n + 2) (or 128), and no buffer of draws exists on the host or the device.
+ *   rng32       : nparties x 32 bytes; row p's rng is rand_chacha's ChaChaRng::from_seed(rng32[p]) -- ChaCha20 with a 64-bit
+ *                 block counter and stream id 0 (see bpgpu_rangeproof_prove_batch_ts); draw d is
+ *                 Scalar::from_bytes_mod_order_wide(keystream block d).  NULL: 32 bytes per row from the OS-seeded CSPRNG
+ *   first_draw  : nparties x uint64, the block index of the row's first draw in this step: how far the client's rng has
+ *                 advanced.  Bit commit consumes first_draw + 0: a_blinding, + 1: s_blinding, + 2 + i: s_L[i],
+ *                 + 2 + n + i: s_R[i] (party.rs:87-118); poly commit first_draw + 0: t_1_blinding, + 1: t_2_blinding
+ *                 (party.rs:224-227).  NULL: 0 for every row in bit commit, 2n + 2 in poly commit (one ChaChaRng carried
+ *                 through both steps).  A party at position j of an m-party prove_multiple_with_rng sits at j (2n + 2) in
+ *                 bit commit and at m (2n + 2) + 2j in poly commit.  A first_draw whose draws would run the counter past
+ *                 2^64 - 1 (first_draw > 2^64 - (2n + 2) in bit commit, > 2^64 - 2 in poly commit): BPGPU_ERR_INVALID_ARG
+ * CONTRACT: every output of every row equals what the unseeded call writes when its rng holds keystream blocks first_draw ...
+ * of rng32[p]; state blobs keep their layout and size, so seeded and unseeded steps interoperate.  Parameter errors, per-row
+ * status, "prover_constant_time" (byte-identical outputs) and the clearing of what was staged -- the seeds are in the secret
+ * part of the staging block -- are those of the unseeded calls. */
+int bpgpu_mpc_party_bit_commit_seeded(bpgpu_ctx *ctx, size_t n, size_t nparties, const uint32_t *party_index,
+                                      const uint64_t *values, const uint8_t *blindings, const uint8_t *rng32,
+                                      const uint64_t *first_draw, uint8_t *bit_commitments, uint8_t *state1);
+int bpgpu_mpc_party_poly_commit_seeded(bpgpu_ctx *ctx, size_t n, size_t nparties, const uint8_t *state1,
+                                       const uint8_t *bit_challenges, int challenges_shared, const uint8_t *rng32,
+                                       const uint64_t *first_draw, uint8_t *poly_commitments, uint8_t *state2,
+                                       uint8_t *status);
 /* PartyAwaitingPolyChallenge::apply_challenge (party.rs:279-311).
  *   poly_challenges : nparties x 32 bytes (x per row), or 32 bytes when challenges_shared != 0 (PolyChallenge)
  *   shares      : nparties x 32 (3 + 2n) bytes: t_x, t_x_blinding, e_blinding, l_vec[n], r_vec[n] (ProofShare)

@@ -6,7 +6,10 @@ at (n, m) = (64, 1), (64, 16), (32, 4), beside bpgpu_rangeproof_prove_batch on t
   position  : the bit commitments of P parties all at position 0 against all at position 3 of a (64, 4) table set, interleaved --
               the same 2n + 2 terms and table sizes, so the two should agree within the run-to-run spread
 The parties draw their randomness from the OS CSPRNG; every session's proof is verified by the dealer step itself (status 0).
-    python tools/mpc_rate.py [--iters N] [--only position|rates]"""
+  --seeded  : the two party steps that draw, both ways on the same rows, interleaved -- unseeded with the caller's pre-expanded bytes
+              (64 (2n + 2) and 128 per party) and with rng = NULL (the host expands them), seeded with 32 + 8 bytes per party and with
+              rng32 = NULL -- at n = 64 and n = 8; the seeded outputs are checked against the unseeded ones on the same keystream first
+    python tools/mpc_rate.py [--iters N] [--only position|rates] [--seeded]"""
 import hashlib
 import json
 import os
@@ -80,8 +83,60 @@ def position(iters, npar=1024):
     ctx.close()
 
 
+def seeded(n, npar, iters):
+    sys.path.insert(0, os.path.join(ROOT, "oracle", "py"))
+    from chacha_rng import chacha20_block
+    ctx = bp.Context(0)
+    ctx.gens_create(64, 4)
+    vals = [int.from_bytes(hashlib.shake_256(b"v%d" % i).digest(8), "little") % (1 << n) for i in range(npar)]
+    bl = b"".join(hashlib.shake_256(b"b%d" % i).digest(31) + b"\x00" for i in range(npar))
+    idx = [(r * 7 + r // 5) % 4 for r in range(npar)]
+    seeds = hashlib.shake_256(b"seeds%d" % n).digest(32 * npar)
+    chal = b"".join(hashlib.shake_256(b"c%d/%d" % (i, q)).digest(31) + b"\x00" for i in range(npar) for q in range(2))
+    nd = 2 * n + 2
+    # parity on the head of the batch (the keystream in Python is slow), then the timing on bytes of the same size
+    k = 8
+    ks1 = b"".join(chacha20_block(seeds[32 * r:32 * r + 32], d) for r in range(k) for d in range(nd))
+    ks2 = b"".join(chacha20_block(seeds[32 * r:32 * r + 32], nd + d) for r in range(k) for d in range(2))
+    bc_u, st_u = ctx.mpc_party_bit_commit(n, idx[:k], vals[:k], bl[:32 * k], ks1)
+    bc_s, st_s = ctx.mpc_party_bit_commit(n, idx[:k], vals[:k], bl[:32 * k], rng_seed32=seeds[:32 * k])
+    pc_u, st2_u, _ = ctx.mpc_party_poly_commit(n, st_u, chal[:64 * k], ks2)
+    pc_s, st2_s, _ = ctx.mpc_party_poly_commit(n, st_s, chal[:64 * k], rng_seed32=seeds[:32 * k])
+    assert (bc_u, st_u, pc_u, st2_u) == (bc_s, st_s, pc_s, st2_s), "seeded and unseeded outputs differ"
+    rng1, rng2 = hashlib.shake_256(b"r1").digest(64 * nd * npar), hashlib.shake_256(b"r2").digest(128 * npar)
+    _, st1 = ctx.mpc_party_bit_commit(n, idx, vals, bl, rng1)
+    forms = {"bit_unseeded_bytes": lambda: ctx.mpc_party_bit_commit(n, idx, vals, bl, rng1),
+             "bit_unseeded_null": lambda: ctx.mpc_party_bit_commit(n, idx, vals, bl),
+             "bit_seeded": lambda: ctx.mpc_party_bit_commit(n, idx, vals, bl, rng_seed32=seeds),
+             "bit_seeded_null": lambda: ctx.mpc_party_bit_commit(n, idx, vals, bl, first_draw=[0] * npar),
+             "poly_unseeded_bytes": lambda: ctx.mpc_party_poly_commit(n, st1, chal, rng2),
+             "poly_unseeded_null": lambda: ctx.mpc_party_poly_commit(n, st1, chal),
+             "poly_seeded": lambda: ctx.mpc_party_poly_commit(n, st1, chal, rng_seed32=seeds),
+             "poly_seeded_null": lambda: ctx.mpc_party_poly_commit(n, st1, chal, first_draw=[nd] * npar)}
+    t = {k_: [] for k_ in forms}
+    for it in range(iters + 2):
+        for k_, f in forms.items():          # interleaved: drift hits every form alike
+            d, _ = timed(f)
+            if it >= 2:
+                t[k_].append(d)
+    med = {k_: statistics.median(v) for k_, v in t.items()}
+    out = {"seeded": True, "n": n, "table_set": [64, 4], "parties": npar, "iters": iters, "rng_bytes_per_party_unseeded": [64 * nd, 128],
+           "rng_bytes_per_party_seeded": [40, 40]}
+    out.update({k_ + "_ms": round(v * 1e3, 3) for k_, v in med.items()})
+    out.update({k_ + "_spread": round((max(v) - min(v)) / med[k_], 4) for k_, v in t.items()})
+    for step in ("bit", "poly"):
+        out[step + "_seeded_over_unseeded_bytes"] = round(med[step + "_seeded"] / med[step + "_unseeded_bytes"], 4)
+        out[step + "_seeded_null_over_unseeded_null"] = round(med[step + "_seeded_null"] / med[step + "_unseeded_null"], 4)
+    print(json.dumps(out), flush=True)
+    ctx.close()
+
+
 def main():
     iters = int(sys.argv[sys.argv.index("--iters") + 1]) if "--iters" in sys.argv else 5
+    if "--seeded" in sys.argv:
+        for n, npar in ((64, 1024), (8, 1024)):
+            seeded(n, npar, max(iters, 9))
+        return
     only = sys.argv[sys.argv.index("--only") + 1] if "--only" in sys.argv else None
     if only in (None, "position"):
         position(max(iters, 7))
