@@ -48,6 +48,7 @@ EXPORTS = [
     "bpgpu_mpc_state1_bytes", "bpgpu_mpc_state2_bytes", "bpgpu_mpc_party_bit_commit", "bpgpu_mpc_party_poly_commit", "bpgpu_mpc_party_proof_share",
     "bpgpu_mpc_dealer_bit_challenge", "bpgpu_mpc_dealer_poly_challenge", "bpgpu_mpc_dealer_assemble",
     "bpgpu_mpc_party_bit_commit_seeded", "bpgpu_mpc_party_poly_commit_seeded",
+    "bpgpu_pedersen_commit_batch", "bpgpu_pedersen_open_batch", "bpgpu_pedersen_commit_batch_dev", "bpgpu_pedersen_open_batch_dev",
 ]
 
 TRANSCRIPT_BYTES = 208
@@ -158,6 +159,10 @@ def lib():
     L.bpgpu_mpc_dealer_bit_challenge.argtypes = [vp, sz, sz, sz, u8p, u8p, sz, u8p, sz, u8p, u8p, u8p, u8p]
     L.bpgpu_mpc_dealer_poly_challenge.argtypes = [vp, sz, sz, u8p, u8p, u8p, u8p, u8p]
     L.bpgpu_mpc_dealer_assemble.argtypes = [vp, sz, sz, sz, u8p, u8p, u8p, u8p, u8p, u8p, sz, u8p, sz, u8p, i, u8p, u8p, u8p]
+    L.bpgpu_pedersen_commit_batch.argtypes = [vp, sz, u8p, sz, u8p, u8p, C.c_uint64, u8p, u8p, u8p]
+    L.bpgpu_pedersen_open_batch.argtypes = [vp, sz, u8p, u8p, sz, u8p, u8p]
+    L.bpgpu_pedersen_commit_batch_dev.argtypes = [vp, sz, vp, sz, vp, vp, C.c_uint64, vp, vp, vp, vp]
+    L.bpgpu_pedersen_open_batch_dev.argtypes = [vp, sz, vp, vp, sz, vp, vp, vp]
     L.bpgpu_pool_create.argtypes = [C.POINTER(C.c_int), i, i, C.POINTER(vp)]
     L.bpgpu_pool_destroy.argtypes = [vp]
     L.bpgpu_pool_destroy.restype = None
@@ -693,6 +698,43 @@ class Context:
         """bpgpu_rangeproof_prove_batch_ts_dev: every buffer a device address (int), asynchronous on `stream`."""
         self._chk(self._L.bpgpu_rangeproof_prove_batch_ts_dev(self.h, n, m, nbatch, d_values, d_blindings, d_transcripts, transcript_stride, d_rng32, d_proofs,
                                                               d_commitments, d_transcripts_out, stream))
+
+    # ---- batches of Pedersen commitments and openings (bpgpu_pedersen_commit_batch / _open_batch) ----
+    def pedersen_commit_batch(self, values, value_bytes, blindings=None, rng_seed32=None, first_draw=0, want_blindings=False):
+        """len(values) / value_bytes commitments value B + blinding B_blinding in one launch.  values: packed little-endian u64
+        (value_bytes = 8) or 32-byte scalars (32).  blindings: 32 bytes per row, or None: row i takes draw first_draw + i of
+        ChaChaRng::from_seed(rng_seed32) (rng_seed32 None: the library draws the seed, and the blindings are always returned).
+        Returns (commitments bytes, status bytes[, blindings bytes])."""
+        assert value_bytes in (8, 32) and len(values) % value_bytes == 0
+        nb = len(values) // value_bytes
+        assert blindings is None or len(blindings) == 32 * nb
+        assert rng_seed32 is None or len(rng_seed32) == 32
+        want_blindings = want_blindings or (blindings is None and rng_seed32 is None)
+        out, st = C.create_string_buffer(32 * max(nb, 1)), C.create_string_buffer(max(nb, 1))
+        blo = C.create_string_buffer(32 * max(nb, 1)) if want_blindings else None
+        self._chk(self._L.bpgpu_pedersen_commit_batch(self.h, nb, bytes(values), value_bytes, blindings, rng_seed32, first_draw, out, blo, st))
+        res = (out.raw[:32 * nb], st.raw[:nb])
+        return res + (blo.raw[:32 * nb],) if want_blindings else res
+
+    def pedersen_open_batch(self, commitments, values, value_bytes, blindings):
+        """does (values[i], blindings[i]) open commitments[i]?  Returns the verdict bytes: 0 yes, 1 no (VerificationError: also a
+        commitment that is no valid encoding), 2 a non-canonical scalar (FormatError)."""
+        assert value_bytes in (8, 32) and len(values) % value_bytes == 0
+        nb = len(values) // value_bytes
+        assert len(commitments) == len(blindings) == 32 * nb
+        vd = C.create_string_buffer(max(nb, 1))
+        self._chk(self._L.bpgpu_pedersen_open_batch(self.h, nb, bytes(commitments), bytes(values), value_bytes, bytes(blindings), vd))
+        return vd.raw[:nb]
+
+    def pedersen_commit_batch_dev(self, nbatch, d_values, value_bytes, d_blindings, d_rng_seed32, first_draw, d_commitments, d_blindings_out, d_status,
+                                  stream=None):
+        """bpgpu_pedersen_commit_batch_dev: every buffer a device address (int, or None), asynchronous on `stream`."""
+        self._chk(self._L.bpgpu_pedersen_commit_batch_dev(self.h, nbatch, d_values, value_bytes, d_blindings, d_rng_seed32, first_draw, d_commitments,
+                                                          d_blindings_out, d_status, stream))
+
+    def pedersen_open_batch_dev(self, nbatch, d_commitments, d_values, value_bytes, d_blindings, d_verdict, stream=None):
+        """bpgpu_pedersen_open_batch_dev: every buffer a device address (int), asynchronous on `stream`."""
+        self._chk(self._L.bpgpu_pedersen_open_batch_dev(self.h, nbatch, d_commitments, d_values, value_bytes, d_blindings, d_verdict, stream))
 
     # ---- batches of transcripts (bpgpu_transcript_batch) ----
     @staticmethod

@@ -101,6 +101,58 @@ class BulletproofGens:
             raise ValueError("scalars must be canonical")
         return out
 
+    def commit_batch(self, values, blindings=None, rng_seed32=None, first_draw=0):
+        """len(values) calls of PedersenGens::commit in ONE GPU launch (bpgpu_pedersen_commit_batch; no counterpart in the crate).
+        values: ints below 2^64, or 32-byte scalars -- one kind per call.  blindings: 32-byte scalars, or None: blinding i is the
+        (first_draw + i)-th Scalar::random of ChaChaRng::from_seed(rng_seed32), drawn on the device (rng_seed32 None: the library
+        draws the seed).  Returns ([32-byte commitments], [32-byte blindings]).  Variable time unless the context option
+        prover_constant_time is set; row i equals commit(values[i], blindings[i])."""
+        values = list(values)
+        ints = [isinstance(v, int) for v in values]
+        if any(ints) and not all(ints):
+            raise TypeError("commit_batch takes ints or 32-byte scalars, not both in one call")
+        if values and all(ints):
+            if any(v < 0 or v >> 64 for v in values):
+                raise ValueError("integer values must be below 2^64 (pass larger ones as 32-byte scalars)")
+            packed, vb = b"".join(v.to_bytes(8, "little") for v in values), 8
+        else:
+            packed, vb = b"".join(bytes(v) for v in values), 32
+            if len(packed) != 32 * len(values):
+                raise ValueError("scalar values must be 32 bytes each")
+        if blindings is not None:
+            blindings = [bytes(b) for b in blindings]
+            if len(blindings) != len(values) or any(len(b) != 32 for b in blindings):
+                raise ValueError("one 32-byte blinding per value")
+            if rng_seed32 is not None or first_draw:
+                raise ValueError("blindings given: rng_seed32 and first_draw do not apply")
+        if not values:
+            return [], []
+        out, st, blo = self.ctx.pedersen_commit_batch(packed, vb, None if blindings is None else b"".join(blindings),
+                                                      None if rng_seed32 is None else bytes(rng_seed32), first_draw, want_blindings=True)
+        if st != bytes(len(values)):
+            raise ValueError("scalars must be canonical (row %d)" % next(i for i, x in enumerate(st) if x))
+        return [out[32 * i:32 * i + 32] for i in range(len(values))], [blo[32 * i:32 * i + 32] for i in range(len(values))]
+
+    def verify_openings(self, commitments, values, blindings):
+        """does (values[i], blindings[i]) open commitments[i]? (bpgpu_pedersen_open_batch) -> a list of None / ProofError:
+        VerificationError when it does not (also for a commitment that is no valid encoding), FormatError for a non-canonical scalar."""
+        values, commitments, blindings = list(values), [bytes(c) for c in commitments], [bytes(b) for b in blindings]
+        if not (len(values) == len(commitments) == len(blindings)):
+            raise ValueError("one commitment and one blinding per value")
+        ints = [isinstance(v, int) for v in values]
+        if any(ints) and not all(ints):
+            raise TypeError("verify_openings takes ints or 32-byte scalars, not both in one call")
+        if not values:
+            return []
+        if all(ints) and all(0 <= v < 2 ** 64 for v in values):
+            packed, vb = b"".join(v.to_bytes(8, "little") for v in values), 8
+        elif all(ints):
+            raise ValueError("integer values must be below 2^64 (pass larger ones as 32-byte scalars)")
+        else:
+            packed, vb = b"".join(bytes(v) for v in values), 32
+        vd = self.ctx.pedersen_open_batch(b"".join(commitments), packed, vb, b"".join(blindings))
+        return [None if x == 0 else _BY_CODE[x]() for x in vd]
+
     def _check_pedersen(self, pc_gens):
         """The verifier multiplies by pc_gens.B / B_blinding (mod.rs:439-440); the device tables hold the bases this
         BulletproofGens was created with.  A different PedersenGens must be loaded with Context.gens_load."""

@@ -3969,6 +3969,178 @@ extern "C" int bpgpu_rangeproof_prove_batch_ts_dev(bpgpu_ctx *c, size_t n, size_
 }
 
 // ============================================================================
+// batches of Pedersen commitments and openings (pedersen.h): one launch, lane = row
+// ============================================================================
+#define PED_MAX_BATCH ((size_t)1 << 28)
+// the argument rules the four entry points share; commit = false: the open forms (blindings required, no seed)
+static int ped_check_args(bpgpu_ctx *c, size_t nbatch, size_t value_bytes, const void *values, const void *blindings, const void *seed, uint64_t first_draw,
+                          const void *blindings_out, bool commit) {
+    if (value_bytes != 8 && value_bytes != 32) return fail(c, BPGPU_ERR_INVALID_ARG, "value_bytes must be 8 (u64) or 32 (scalars)");
+    if (nbatch > PED_MAX_BATCH) return fail(c, BPGPU_ERR_INVALID_ARG, "batch too large: at most 2^28 rows per call");
+    if (!values) return fail(c, BPGPU_ERR_INVALID_ARG, "values missing");
+    if (!commit) return blindings ? BPGPU_OK : fail(c, BPGPU_ERR_INVALID_ARG, "blindings missing");
+    if (blindings && (seed || first_draw)) return fail(c, BPGPU_ERR_INVALID_ARG, "blindings given: rng_seed32 must be NULL and first_draw 0");
+    if (!blindings && !seed && !blindings_out)
+        return fail(c, BPGPU_ERR_INVALID_ARG, "the library draws the seed: blindings_out is required (nothing else tells the caller the openings)");
+    return BPGPU_OK;
+}
+// enqueue the one launch on s.  d_commitments_in != nullptr: the open form (verdicts to d_verdict); else the commit form, constant-time
+// under the context option "prover_constant_time" (its own small-window table, built on first use)
+static int ped_launch_locked(bpgpu_ctx *c, hipStream_t s, size_t nbatch, const void *d_values, size_t value_bytes, const void *d_blindings, const void *d_seed,
+                             uint64_t first_draw, const void *d_commitments_in, void *d_out, void *d_blindings_out, void *d_status) {
+    uint32_t *d_ids = nullptr;
+    int rc = gen_ids_for(c, 1, 1, &d_ids);   // the shared path's list: [0] = B_blinding, [1] = B
+    if (rc) return rc;
+    const bool ct = !d_commitments_in && c->prover_ct;
+    if (ct && (rc = build_ct_table(c))) return rc;
+    ped_in in;
+    in.values = (const uint32_t *)d_values;
+    in.value_words = (uint32_t)(value_bytes / 4);
+    in.blindings = (const uint32_t *)d_blindings;
+    in.seed32 = (const uint8_t *)d_seed;
+    in.first_draw = first_draw;
+    const uint32_t nb = (uint32_t)nbatch, grid = (nb + BP_BLOCK - 1) / BP_BLOCK;
+    if (d_commitments_in)
+        LAUNCH(c, s, "ped_open", k_ped_open, grid, BP_BLOCK, nb, in, (const uint32_t *)d_commitments_in, c->prm, (const uint32_t *)d_ids, (const fb_entry *)c->d_table,
+               (uint8_t *)d_out);
+    else if (ct)
+        LAUNCH(c, s, "ped_commit_ct", k_ped_commit<true>, grid, BP_BLOCK, nb, in, c->prm_ct, (const uint32_t *)d_ids, (const fb_entry *)c->d_table_ct, (uint32_t *)d_out,
+               (uint32_t *)d_blindings_out, (uint8_t *)d_status);
+    else
+        LAUNCH(c, s, "ped_commit", k_ped_commit<false>, grid, BP_BLOCK, nb, in, c->prm, (const uint32_t *)d_ids, (const fb_entry *)c->d_table, (uint32_t *)d_out,
+               (uint32_t *)d_blindings_out, (uint8_t *)d_status);
+    if (hipGetLastError() != hipSuccess) return fail(c, BPGPU_ERR_HIP, "launch failed");
+    return BPGPU_OK;
+}
+
+extern "C" int bpgpu_pedersen_commit_batch(bpgpu_ctx *c, size_t nbatch, const void *values, size_t value_bytes, const uint8_t *blindings, const uint8_t *rng_seed32,
+                                           uint64_t first_draw, uint8_t *commitments_out, uint8_t *blindings_out, uint8_t *status_out) {
+    if (!c) return BPGPU_ERR_INVALID_ARG;
+    if (nbatch == 0) return BPGPU_OK;
+    int rc = ped_check_args(c, nbatch, value_bytes, values, blindings, rng_seed32, first_draw, blindings_out, true);
+    if (rc) return rc;
+    if (!commitments_out || !status_out) return fail(c, BPGPU_ERR_INVALID_ARG, "commitments_out and status_out are required");
+    std::lock_guard<std::mutex> lk(c->mu);
+    HIPCHK(c, hipSetDevice(c->device));
+    if (!c->d_table) return fail(c, BPGPU_ERR_NO_GENS, "generators not loaded");
+    hipStream_t s = c->stream;
+    // values, blindings and the seed through the provers' staging: the secret span is every input
+    host_call<bpgpu_ctx> io(c, s);
+    const int r_val = io.in(nbatch * value_bytes), r_bl = io.in(blindings ? nbatch * 32 : 0), r_seed = io.in(32);
+    const int r_blo = io.out(blindings_out ? nbatch * 32 : 0), r_cm = io.out(nbatch * 32), r_st = io.out(nbatch);
+    io.secrets(io.in_bytes());
+    rc = io.open();
+    if (rc) return io.finish(rc);
+    io.put(r_val, values, nbatch * value_bytes);
+    if (blindings) io.put(r_bl, blindings, nbatch * 32);
+    else if (rng_seed32) io.put(r_seed, rng_seed32, 32);
+    else if ((rc = os_random(c, io.h(r_seed), 32)) != 0) return io.finish(rc);
+    if ((rc = io.upload())) return io.finish(rc);
+    rc = ped_launch_locked(c, s, nbatch, io.d(r_val), value_bytes, blindings ? io.d(r_bl) : nullptr, blindings ? nullptr : io.d(r_seed), first_draw, nullptr, io.d(r_cm),
+                           blindings_out ? io.d(r_blo) : nullptr, io.d(r_st));
+    rc = io.finish(io.download(rc));
+    if (blindings_out) {   // the staged copy of the blindings is a secret too: handed over, then cleared
+        if (!rc) memcpy(blindings_out, io.h(r_blo), nbatch * 32);
+        memset(io.h(r_blo), 0, nbatch * 32);
+        if (io.hb == c->io.pin) c->io.last_secret_bytes = io.off[r_blo + 1];   // (the first output region: the secret span grows by it)
+    }
+    if (rc) return rc;
+    memcpy(commitments_out, io.h(r_cm), nbatch * 32);
+    memcpy(status_out, io.h(r_st), nbatch);
+    return BPGPU_OK;
+}
+
+extern "C" int bpgpu_pedersen_open_batch(bpgpu_ctx *c, size_t nbatch, const uint8_t *commitments, const void *values, size_t value_bytes, const uint8_t *blindings,
+                                         uint8_t *verdict_out) {
+    if (!c) return BPGPU_ERR_INVALID_ARG;
+    if (nbatch == 0) return BPGPU_OK;
+    int rc = ped_check_args(c, nbatch, value_bytes, values, blindings, nullptr, 0, nullptr, false);
+    if (rc) return rc;
+    if (!commitments || !verdict_out) return fail(c, BPGPU_ERR_INVALID_ARG, "commitments and verdict_out are required");
+    std::lock_guard<std::mutex> lk(c->mu);
+    HIPCHK(c, hipSetDevice(c->device));
+    if (!c->d_table) return fail(c, BPGPU_ERR_NO_GENS, "generators not loaded");
+    hipStream_t s = c->stream;
+    host_call<bpgpu_ctx> io(c, s);
+    const int r_val = io.in(nbatch * value_bytes), r_bl = io.in(nbatch * 32), r_cm = io.in(nbatch * 32);
+    const int r_vd = io.out(nbatch);
+    io.secrets(io.off[r_cm]);   // an opening is a secret of whoever made it, public only to this verifier
+    rc = io.open();
+    if (rc) return io.finish(rc);
+    io.put(r_val, values, nbatch * value_bytes);
+    io.put(r_bl, blindings, nbatch * 32);
+    io.put(r_cm, commitments, nbatch * 32);
+    if ((rc = io.upload())) return io.finish(rc);
+    rc = ped_launch_locked(c, s, nbatch, io.d(r_val), value_bytes, io.d(r_bl), nullptr, 0, io.d(r_cm), io.d(r_vd), nullptr, nullptr);
+    rc = io.finish(io.download(rc));
+    if (rc) return rc;
+    memcpy(verdict_out, io.h(r_vd), nbatch);
+    return BPGPU_OK;
+}
+
+extern "C" int bpgpu_pedersen_commit_batch_dev(bpgpu_ctx *c, size_t nbatch, const void *d_values, size_t value_bytes, const void *d_blindings, const void *d_rng_seed32,
+                                               uint64_t first_draw, void *d_commitments_out, void *d_blindings_out, void *d_status_out, void *stream) {
+    if (!c) return BPGPU_ERR_INVALID_ARG;
+    if (nbatch == 0) return BPGPU_OK;
+    int rc = ped_check_args(c, nbatch, value_bytes, d_values, d_blindings, d_rng_seed32, first_draw, d_blindings_out, true);
+    if (rc) return rc;
+    if (!d_commitments_out || !d_status_out) return fail(c, BPGPU_ERR_INVALID_ARG, "commitments_out and status_out are required");
+    if (((uintptr_t)d_values | (uintptr_t)d_blindings | (uintptr_t)d_rng_seed32 | (uintptr_t)d_commitments_out | (uintptr_t)d_blindings_out) & 3)
+        return fail(c, BPGPU_ERR_INVALID_ARG, "device buffers must be 4-byte aligned");
+    std::lock_guard<std::mutex> lk(c->mu);
+    HIPCHK(c, hipSetDevice(c->device));
+    if (!c->d_table) return fail(c, BPGPU_ERR_NO_GENS, "generators not loaded");
+    hipStream_t s = stream ? (hipStream_t)stream : c->stream;
+    if ((rc = ctx_enter(c, s))) return rc;
+    char *h_seed = nullptr;
+    const void *d_seed = d_rng_seed32;
+    size_t slot_bytes = 256;
+    do {
+        if (!d_blindings && !d_rng_seed32) {   // the library's own seed: pinned staging -> a slot of the arena, cleared behind the kernel
+            const bool fresh = c->arena_cap < 256;   // (an arena allocated here is cleared whole: the allocator hands out what its last owner left)
+            if ((rc = arena_reserve(c, 256)) || (rc = c->io.pin_alloc(32, &h_seed)) || (rc = os_random(c, h_seed, 32))) break;
+            if (fresh) slot_bytes = c->arena_cap;
+            // ... and wait for that one copy, so that the staged seed can be cleared before this returns (the one wait of this form)
+            if (hipMemcpyAsync(c->arena, h_seed, 32, hipMemcpyHostToDevice, s) != hipSuccess || c->io.pin_mark(s) || hipEventSynchronize(c->io.pin_ev) != hipSuccess) {
+                rc = fail(c, BPGPU_ERR_HIP, "staging the seed failed");
+                break;
+            }
+            c->io.pin_pending = false;
+            d_seed = c->arena;
+        }
+        rc = ped_launch_locked(c, s, nbatch, d_values, value_bytes, d_blindings, d_blindings ? nullptr : d_seed, first_draw, nullptr, d_commitments_out, d_blindings_out,
+                               d_status_out);
+    } while (0);
+    bool ok = true;
+    if (h_seed) {
+        if (c->arena) ok = hipMemsetAsync(c->arena, 0, slot_bytes, s) == hipSuccess;
+        memset(h_seed, 0, 32);
+        c->io.last_secret_bytes = (h_seed == c->io.pin) ? 32 : 0;
+    }
+    const int rc2 = ctx_leave(c, s);
+    if (!rc && !ok) rc = fail(c, BPGPU_ERR_HIP, "clearing the seed slot failed");
+    return rc ? rc : rc2;
+}
+
+extern "C" int bpgpu_pedersen_open_batch_dev(bpgpu_ctx *c, size_t nbatch, const void *d_commitments, const void *d_values, size_t value_bytes, const void *d_blindings,
+                                             void *d_verdict_out, void *stream) {
+    if (!c) return BPGPU_ERR_INVALID_ARG;
+    if (nbatch == 0) return BPGPU_OK;
+    int rc = ped_check_args(c, nbatch, value_bytes, d_values, d_blindings, nullptr, 0, nullptr, false);
+    if (rc) return rc;
+    if (!d_commitments || !d_verdict_out) return fail(c, BPGPU_ERR_INVALID_ARG, "commitments and verdict_out are required");
+    if (((uintptr_t)d_values | (uintptr_t)d_blindings | (uintptr_t)d_commitments) & 3) return fail(c, BPGPU_ERR_INVALID_ARG, "device buffers must be 4-byte aligned");
+    std::lock_guard<std::mutex> lk(c->mu);
+    HIPCHK(c, hipSetDevice(c->device));
+    if (!c->d_table) return fail(c, BPGPU_ERR_NO_GENS, "generators not loaded");
+    hipStream_t s = stream ? (hipStream_t)stream : c->stream;
+    if ((rc = ctx_enter(c, s))) return rc;
+    rc = ped_launch_locked(c, s, nbatch, d_values, value_bytes, d_blindings, nullptr, 0, d_commitments, d_verdict_out, nullptr, nullptr);
+    const int rc2 = ctx_leave(c, s);
+    return rc ? rc : rc2;
+}
+
+// ============================================================================
 // the multi-party aggregation protocol: parties (mpc_party.h) and dealer (mpc_dealer.h)
 // ============================================================================
 static bool mpc_bitsize_ok(size_t n) { return n == 8 || n == 16 || n == 32 || n == 64; }

@@ -27,6 +27,7 @@
 #include "mpc_party.h"
 #include "mpc_dealer.h"
 #include "ts_batch.h"
+#include "pedersen.h"
 
 #define BP_BLOCK 64   // one wavefront per workgroup: under contention a CU rarely has room for four waves of one group at once (256: -8% at 48 streams)
 #define FB_BLOCK 64
@@ -195,5 +196,10 @@ __global__ void k_mpc_vectors(uint32_t nthreads, uint32_t n, uint32_t m, const u
 
 // k_ts_batch.hip
 __global__ void k_ts_batch(uint32_t nbatch, const uint32_t *ts_in, uint32_t ts_in_stride, uint32_t *ts_out, const tsb_op *ops, uint32_t nops, const uint8_t *labels);
+
+// k_pedersen.hip
+template <bool CT>
+__global__ void k_ped_commit(uint32_t nbatch, ped_in in, fb_params prm, const uint32_t *gen_ids, const fb_entry *table, uint32_t *out_words, uint32_t *blindings_out, uint8_t *status);
+__global__ void k_ped_open(uint32_t nbatch, ped_in in, const uint32_t *commitments, fb_params prm, const uint32_t *gen_ids, const fb_entry *table, uint8_t *verdict);
 
 #endif

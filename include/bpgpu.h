@@ -967,6 +967,50 @@ int bpgpu_rangeproof_prove_batch_ts_dev(bpgpu_ctx *ctx, size_t n, size_t m, size
                                         const void *d_rng32, void *d_proofs_out, void *d_commitments_out,
                                         void *d_transcripts_out, void *stream);
 
+/* ---- batches of Pedersen commitments and openings -----------------------------------------------
+ * nbatch calls of PedersenGens::commit(value, blinding) = value B + blinding B_blinding (src/generators.rs:38-42) with the bases
+ * the context holds, in ONE launch: a lane walks the window tables of the two bases that already sit in device memory (no point is
+ * decoded, nothing is doubled), compresses its point and stores the 32 bytes (commit) or compares them with a given commitment
+ * (open).  csrc/pedersen.h.
+ *   values       : value_bytes = 8: nbatch u64; value_bytes = 32: nbatch x 32-byte scalars.  Anything else: BPGPU_ERR_INVALID_ARG.
+ *   blindings    : nbatch x 32 bytes, with rng_seed32 == NULL and first_draw == 0 (else BPGPU_ERR_INVALID_ARG); or NULL, the
+ *                  SEEDED mode: blinding i is draw first_draw + i of rand_chacha's ChaChaRng::from_seed(rng_seed32) -- ONE rng for
+ *                  the batch, one Scalar::random per commitment: Scalar::from_bytes_mod_order_wide of keystream block
+ *                  first_draw + i (64-bit block counter, stream id 0), exactly as documented for bpgpu_rangeproof_prove_batch_ts,
+ *                  computed by the lane that consumes it.  rng_seed32 == NULL then means 32 bytes from the library's OS-seeded
+ *                  generator, and blindings_out is required (BPGPU_ERR_INVALID_ARG if it is NULL).
+ *   commitments_out : nbatch x 32 bytes
+ *   blindings_out   : nbatch x 32 bytes: the blindings used (given or drawn); optional when the caller gave the seed or the blindings
+ *   status_out      : nbatch bytes: BPGPU_MSM_OK, or BPGPU_MSM_BAD_SCALAR for a non-canonical value or blinding -- that row's
+ *                     commitment is then 32 zero bytes (the status tells it from the commitment to (0, 0), which is 32 zero bytes
+ *                     with BPGPU_MSM_OK); the other rows are unaffected.
+ * CONTRACT: row i of the commit call equals bpgpu_msm_batch with the two terms (value_i, B), (blinding_i, B_blinding) -- what
+ * BulletproofGens.commit of the Python package returns -- whatever "fixed_window_bits" and "prover_constant_time" are.
+ * bpgpu_pedersen_open_batch: verdict_out, nbatch bytes of BPGPU_VERDICT_*: 0 = (value_i, blinding_i) opens commitments[i];
+ * VerificationError = it does not, which includes a commitment that is no valid encoding (the encodings are compared, and the
+ * encoder's output is canonical); FormatError = a non-canonical scalar.
+ * nbatch = 0 is BPGPU_OK; a context without generators returns BPGPU_ERR_NO_GENS; one call takes at most 2^28 rows.
+ * Timing: VARIABLE TIME in the scalars by default.  With the context option "prover_constant_time" = 1 the commit forms walk the
+ * small-window table of the provers' constant-time path: every (generator, window) pair reads all 8 entries, selects by masks and
+ * always adds, and the number of B windows follows from the value's type (u64 or scalar), never from its bits; the bytes are the
+ * same.  The open forms are always variable time: their inputs are public to the verifier.
+ * Secrets: values, blindings and seeds are staged through the provers' secret staging; staging, the device IO buffer and the working
+ * sets are cleared on every exit, as bpgpu_rangeproof_prove_batch documents.  The _dev forms take device pointers (4-byte aligned)
+ * and enqueue on `stream` (NULL: the context's own) with the conventions of the other _dev entry points; nothing is read back.
+ * They clear what the library itself allocated (the slot of a library-drawn seed) on the stream behind the kernel; with
+ * d_rng_seed32 = NULL and d_blindings = NULL the library draws the seed, uploads it through its own staging and clears that once
+ * the copy has completed (the one wait of the _dev form). */
+int bpgpu_pedersen_commit_batch(bpgpu_ctx *ctx, size_t nbatch, const void *values, size_t value_bytes,
+                                const uint8_t *blindings, const uint8_t *rng_seed32, uint64_t first_draw,
+                                uint8_t *commitments_out, uint8_t *blindings_out, uint8_t *status_out);
+int bpgpu_pedersen_open_batch(bpgpu_ctx *ctx, size_t nbatch, const uint8_t *commitments, const void *values, size_t value_bytes,
+                              const uint8_t *blindings, uint8_t *verdict_out);
+int bpgpu_pedersen_commit_batch_dev(bpgpu_ctx *ctx, size_t nbatch, const void *d_values, size_t value_bytes,
+                                    const void *d_blindings, const void *d_rng_seed32, uint64_t first_draw,
+                                    void *d_commitments_out, void *d_blindings_out, void *d_status_out, void *stream);
+int bpgpu_pedersen_open_batch_dev(bpgpu_ctx *ctx, size_t nbatch, const void *d_commitments, const void *d_values, size_t value_bytes,
+                                  const void *d_blindings, void *d_verdict_out, void *stream);
+
 /* ---- the multi-party aggregation protocol: parties and dealer ------------------------------------
  * range_proof_mpc of the reference (src/range_proof/party.rs, dealer.rs, messages.rs; docs/aggregation-api.md) as six
  * batched, STATELESS calls: host pointers in and out, nothing retained after return.  bpgpu_rangeproof_prove_batch above

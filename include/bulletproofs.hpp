@@ -99,6 +99,27 @@ class BulletproofGens {
         if (status != 0) throw std::invalid_argument("commit: scalars must be canonical");
         return out;
     }
+    // values.size() calls of commit in ONE GPU launch (bpgpu_pedersen_commit_batch; no counterpart in the crate) -> (commitments, blindings).
+    // blindings == nullptr: blinding i is the (first_draw + i)-th Scalar::random of ChaChaRng::from_seed(rng_seed32), drawn on the
+    // device (rng_seed32 == nullptr: the library draws the seed).  Row i equals commit(values[i], blindings[i]).
+    std::pair<std::vector<CompressedRistretto>, std::vector<ScalarBytes>> commit_batch(const std::vector<uint64_t> &values, const std::vector<ScalarBytes> *blindings,
+                                                                                      const uint8_t *rng_seed32 = nullptr, uint64_t first_draw = 0) const {
+        return commit_rows(values.data(), 8, values.size(), blindings, rng_seed32, first_draw);
+    }
+    std::pair<std::vector<CompressedRistretto>, std::vector<ScalarBytes>> commit_batch(const std::vector<ScalarBytes> &values, const std::vector<ScalarBytes> *blindings,
+                                                                                      const uint8_t *rng_seed32 = nullptr, uint64_t first_draw = 0) const {
+        return commit_rows(values.data(), 32, values.size(), blindings, rng_seed32, first_draw);
+    }
+    // does (values[i], blindings[i]) open commitments[i]? (bpgpu_pedersen_open_batch)  VerificationError: it does not, or the
+    // commitment is no valid encoding; FormatError: a non-canonical scalar
+    std::vector<Status> verify_openings(const std::vector<CompressedRistretto> &commitments, const std::vector<uint64_t> &values,
+                                        const std::vector<ScalarBytes> &blindings) const {
+        return open_rows(commitments, values.data(), 8, values.size(), blindings);
+    }
+    std::vector<Status> verify_openings(const std::vector<CompressedRistretto> &commitments, const std::vector<ScalarBytes> &values,
+                                        const std::vector<ScalarBytes> &blindings) const {
+        return open_rows(commitments, values.data(), 32, values.size(), blindings);
+    }
     // BulletproofGens::increase_capacity (generators.rs:177-204): no-op unless larger; the device tables are rebuilt
     void increase_capacity(size_t new_capacity) {
         if (gens_capacity >= new_capacity) return;
@@ -119,6 +140,33 @@ class BulletproofGens {
     }
 
   private:
+    std::pair<std::vector<CompressedRistretto>, std::vector<ScalarBytes>> commit_rows(const void *values, size_t value_bytes, size_t nb,
+                                                                                     const std::vector<ScalarBytes> *blindings, const uint8_t *rng_seed32,
+                                                                                     uint64_t first_draw) const {
+        if (blindings && blindings->size() != nb) throw std::invalid_argument("commit_batch: one blinding per value");
+        std::vector<CompressedRistretto> out(nb);
+        std::vector<ScalarBytes> bl(nb);
+        std::vector<uint8_t> st(nb);
+        const uint8_t *bl_in = blindings && nb ? (*blindings)[0].data() : nullptr;
+        if (blindings && (rng_seed32 || first_draw)) throw std::invalid_argument("commit_batch: blindings given, rng_seed32 and first_draw do not apply");
+        if (nb == 0) return {out, bl};
+        if (bpgpu_pedersen_commit_batch(ctx_.get(), nb, values, value_bytes, bl_in, rng_seed32, first_draw, out[0].data(), bl[0].data(), st.data()) != BPGPU_OK)
+            throw GpuError(bpgpu_last_error(ctx_.get()));
+        for (size_t i = 0; i < nb; i++)
+            if (st[i] != BPGPU_MSM_OK) throw std::invalid_argument("commit_batch: scalars must be canonical");
+        return {out, bl};
+    }
+    std::vector<Status> open_rows(const std::vector<CompressedRistretto> &commitments, const void *values, size_t value_bytes, size_t nb,
+                                  const std::vector<ScalarBytes> &blindings) const {
+        if (commitments.size() != nb || blindings.size() != nb) throw std::invalid_argument("verify_openings: one commitment and one blinding per value");
+        std::vector<uint8_t> vd(nb);
+        std::vector<Status> res;
+        if (nb == 0) return res;
+        if (bpgpu_pedersen_open_batch(ctx_.get(), nb, commitments[0].data(), values, value_bytes, blindings[0].data(), vd.data()) != BPGPU_OK)
+            throw GpuError(bpgpu_last_error(ctx_.get()));
+        for (size_t i = 0; i < nb; i++) res.push_back(vd[i] == 0 ? Status::Ok() : Status::Err((ProofError)vd[i]));
+        return res;
+    }
     std::vector<CompressedRistretto> slice(bool g, size_t n, size_t m, size_t first_party) const {
         if (n > gens_capacity || first_party + m > party_capacity) throw std::out_of_range("generators: n or party index beyond capacity");
         const size_t tot = gens_capacity * party_capacity;
