@@ -49,6 +49,7 @@ EXPORTS = [
     "bpgpu_mpc_dealer_bit_challenge", "bpgpu_mpc_dealer_poly_challenge", "bpgpu_mpc_dealer_assemble",
     "bpgpu_mpc_party_bit_commit_seeded", "bpgpu_mpc_party_poly_commit_seeded",
     "bpgpu_pedersen_commit_batch", "bpgpu_pedersen_open_batch", "bpgpu_pedersen_commit_batch_dev", "bpgpu_pedersen_open_batch_dev",
+    "bpgpu_pedersen_sum_batch", "bpgpu_pedersen_balance_batch", "bpgpu_pedersen_sum_batch_dev", "bpgpu_pedersen_balance_batch_dev",
 ]
 
 TRANSCRIPT_BYTES = 208
@@ -163,6 +164,11 @@ def lib():
     L.bpgpu_pedersen_open_batch.argtypes = [vp, sz, u8p, u8p, sz, u8p, u8p]
     L.bpgpu_pedersen_commit_batch_dev.argtypes = [vp, sz, vp, sz, vp, vp, C.c_uint64, vp, vp, vp, vp]
     L.bpgpu_pedersen_open_batch_dev.argtypes = [vp, sz, vp, vp, sz, vp, vp, vp]
+    u32p = C.POINTER(C.c_uint32)
+    L.bpgpu_pedersen_sum_batch.argtypes = [vp, sz, u32p, u8p, u8p, u8p, sz, u8p, u8p, u8p]
+    L.bpgpu_pedersen_balance_batch.argtypes = [vp, sz, u32p, u8p, u8p, u8p, sz, u8p, u8p]
+    L.bpgpu_pedersen_sum_batch_dev.argtypes = [vp, sz, u32p, vp, vp, vp, sz, vp, vp, vp, vp]
+    L.bpgpu_pedersen_balance_batch_dev.argtypes = [vp, sz, u32p, vp, vp, vp, sz, vp, vp, vp]
     L.bpgpu_pool_create.argtypes = [C.POINTER(C.c_int), i, i, C.POINTER(vp)]
     L.bpgpu_pool_destroy.argtypes = [vp]
     L.bpgpu_pool_destroy.restype = None
@@ -735,6 +741,48 @@ class Context:
     def pedersen_open_batch_dev(self, nbatch, d_commitments, d_values, value_bytes, d_blindings, d_verdict, stream=None):
         """bpgpu_pedersen_open_batch_dev: every buffer a device address (int), asynchronous on `stream`."""
         self._chk(self._L.bpgpu_pedersen_open_batch_dev(self.h, nbatch, d_commitments, d_values, value_bytes, d_blindings, d_verdict, stream))
+
+    # ---- signed sums of commitments and the balance check (bpgpu_pedersen_sum_batch / _balance_batch) ----
+    @staticmethod
+    def _psum_args(row_offsets, points, signs, values, value_bytes, blindings):
+        row_offsets = [int(x) for x in row_offsets]
+        nb = len(row_offsets) - 1
+        assert nb >= 0 and (points is None or len(points) == 32 * row_offsets[-1]) and (signs is None or len(signs) == row_offsets[-1])
+        assert values is None or len(values) == value_bytes * nb
+        assert blindings is None or len(blindings) == 32 * nb
+        b = lambda x: None if x is None else bytes(x)
+        return nb, (C.c_uint32 * (nb + 1))(*row_offsets), b(points), b(signs), b(values), b(blindings)
+
+    def pedersen_sum_batch(self, row_offsets, points, signs=None, values=None, value_bytes=8, blindings=None):
+        """Row r: compress(sum of +-points[row_offsets[r] : row_offsets[r + 1]] + values[r] B + blindings[r] B_blinding).  points: 32
+        bytes per term; signs: one byte per term (0 add, 1 subtract) or None; values: packed u64 (value_bytes = 8) or 32-byte scalars
+        (32), or None; blindings: 32 bytes per row, or None.  Returns (32 bytes per row, BPGPU_MSM_* status bytes)."""
+        nb, off, points, signs, values, blindings = self._psum_args(row_offsets, points, signs, values, value_bytes, blindings)
+        out, st = C.create_string_buffer(32 * max(nb, 1)), C.create_string_buffer(max(nb, 1))
+        self._chk(self._L.bpgpu_pedersen_sum_batch(self.h, nb, off, points, signs, values, value_bytes, blindings, out, st))
+        return out.raw[:32 * nb], st.raw[:nb]
+
+    def pedersen_balance_batch(self, row_offsets, points, signs=None, values=None, value_bytes=8, blindings=None):
+        """Does the signed sum of row r's points open to (values[r], blindings[r])?  Returns the verdict bytes: 0 yes, 1 no
+        (VerificationError: also a term that does not decode), 2 a non-canonical scalar (FormatError)."""
+        nb, off, points, signs, values, blindings = self._psum_args(row_offsets, points, signs, values, value_bytes, blindings)
+        vd = C.create_string_buffer(max(nb, 1))
+        self._chk(self._L.bpgpu_pedersen_balance_batch(self.h, nb, off, points, signs, values, value_bytes, blindings, vd))
+        return vd.raw[:nb]
+
+    def pedersen_sum_batch_dev(self, row_offsets, d_points, d_signs, d_values, value_bytes, d_blindings, d_out, d_status, stream=None):
+        """bpgpu_pedersen_sum_batch_dev: row_offsets a host sequence, every buffer a device address (int, or None), asynchronous on `stream`."""
+        row_offsets = [int(x) for x in row_offsets]
+        nb = len(row_offsets) - 1
+        self._chk(self._L.bpgpu_pedersen_sum_batch_dev(self.h, nb, (C.c_uint32 * (nb + 1))(*row_offsets), d_points, d_signs, d_values, value_bytes, d_blindings,
+                                                       d_out, d_status, stream))
+
+    def pedersen_balance_batch_dev(self, row_offsets, d_points, d_signs, d_values, value_bytes, d_blindings, d_verdict, stream=None):
+        """bpgpu_pedersen_balance_batch_dev: row_offsets a host sequence, every buffer a device address (int, or None), asynchronous on `stream`."""
+        row_offsets = [int(x) for x in row_offsets]
+        nb = len(row_offsets) - 1
+        self._chk(self._L.bpgpu_pedersen_balance_batch_dev(self.h, nb, (C.c_uint32 * (nb + 1))(*row_offsets), d_points, d_signs, d_values, value_bytes, d_blindings,
+                                                           d_verdict, stream))
 
     # ---- batches of transcripts (bpgpu_transcript_batch) ----
     @staticmethod

@@ -153,6 +153,67 @@ class BulletproofGens:
         vd = self.ctx.pedersen_open_batch(b"".join(commitments), packed, vb, b"".join(blindings))
         return [None if x == 0 else _BY_CODE[x]() for x in vd]
 
+    @staticmethod
+    def _signed_rows(plus, minus, values, blindings, who):
+        """(row_offsets, points, signs, packed values or None, value_bytes, packed blindings or None) of bpgpu_pedersen_sum_batch"""
+        plus = [[bytes(c) for c in row] for row in plus]
+        minus = [[] for _ in plus] if minus is None else [[bytes(c) for c in row] for row in minus]
+        if len(minus) != len(plus):
+            raise ValueError("one list of subtracted commitments per row")
+        off, pts, sg = [0], [], bytearray()
+        for a, s in zip(plus, minus):
+            if any(len(c) != 32 for c in a + s):
+                raise ValueError("commitments are 32 bytes each")
+            pts += a + s
+            sg += bytes(len(a)) + bytes([1]) * len(s)
+            off.append(len(pts))
+        packed, vb = None, 8
+        if values is not None:
+            values = list(values)
+            if len(values) != len(plus):
+                raise ValueError("one value per row")
+            ints = [isinstance(v, int) for v in values]
+            if any(ints) and not all(ints):
+                raise TypeError("%s takes ints or 32-byte scalars, not both in one call" % who)
+            if values and all(ints):
+                if any(v < 0 or v >> 64 for v in values):
+                    raise ValueError("integer values must be below 2^64 (pass larger ones as 32-byte scalars)")
+                packed = b"".join(v.to_bytes(8, "little") for v in values)
+            else:
+                packed, vb = b"".join(bytes(v) for v in values), 32
+                if len(packed) != 32 * len(values):
+                    raise ValueError("scalar values must be 32 bytes each")
+        if blindings is not None:
+            blindings = [bytes(b) for b in blindings]
+            if len(blindings) != len(plus) or any(len(b) != 32 for b in blindings):
+                raise ValueError("one 32-byte blinding per row")
+            blindings = b"".join(blindings)
+        return off, b"".join(pts), bytes(sg), packed, vb, blindings
+
+    def sum_commitments(self, plus, minus=None, values=None, blindings=None):
+        """Row r: sum(plus[r]) - sum(minus[r]) + values[r] B + blindings[r] B_blinding, compressed, for every row in a few GPU launches
+        (bpgpu_pedersen_sum_batch; no counterpart in the crate).  plus, minus: lists of lists of 32-byte commitments, one inner list
+        per row; values: ints below 2^64 or 32-byte scalars, one kind per call, or None; blindings: 32-byte scalars or None.  Returns a
+        list of 32-byte encodings; an entry is None where a term of the row did not decode.  ValueError for a non-canonical scalar."""
+        off, pts, sg, packed, vb, bl = self._signed_rows(plus, minus, values, blindings, "sum_commitments")
+        nb = len(off) - 1
+        if nb == 0:
+            return []
+        out, st = self.ctx.pedersen_sum_batch(off, pts, sg, packed, vb, bl)
+        if 2 in st:
+            raise ValueError("scalars must be canonical (row %d)" % st.index(2))
+        return [None if st[i] else out[32 * i:32 * i + 32] for i in range(nb)]
+
+    def verify_balance(self, inputs, outputs, values=None, blindings=None):
+        """does sum(inputs[r]) - sum(outputs[r]) open to (values[r], blindings[r])? (bpgpu_pedersen_balance_batch) -> a list of None /
+        ProofError, as verify_openings: VerificationError when the row does not balance (also for a commitment that is no valid
+        encoding), FormatError for a non-canonical scalar.  A missing value or blinding is zero."""
+        off, pts, sg, packed, vb, bl = self._signed_rows(inputs, outputs, values, blindings, "verify_balance")
+        if len(off) == 1:
+            return []
+        vd = self.ctx.pedersen_balance_batch(off, pts, sg, packed, vb, bl)
+        return [None if x == 0 else _BY_CODE[x]() for x in vd]
+
     def _check_pedersen(self, pc_gens):
         """The verifier multiplies by pc_gens.B / B_blinding (mod.rs:439-440); the device tables hold the bases this
         BulletproofGens was created with.  A different PedersenGens must be loaded with Context.gens_load."""

@@ -13,6 +13,7 @@
 #include <map>
 #include <mutex>
 #include <string>
+#include <new>
 #include <vector>
 
 #include "../../include/bpgpu.h"
@@ -4138,6 +4139,180 @@ extern "C" int bpgpu_pedersen_open_batch_dev(bpgpu_ctx *c, size_t nbatch, const 
     rc = ped_launch_locked(c, s, nbatch, d_values, value_bytes, d_blindings, nullptr, 0, d_commitments, d_verdict_out, nullptr, nullptr);
     const int rc2 = ctx_leave(c, s);
     return rc ? rc : rc2;
+}
+
+// ============================================================================
+// signed sums of Pedersen commitments and the balance check (pedersen_sum.h): term launch, reduce passes, finish launch
+// ============================================================================
+// the argument rules the four entry points share; fills the plan (host: row_offsets never leaves it but as the plan table)
+static int psum_check_args(bpgpu_ctx *c, size_t nbatch, const uint32_t *row_offsets, const void *points, const void *values, size_t value_bytes, psum_plan &pl) {
+    if (nbatch > PED_MAX_BATCH) return fail(c, BPGPU_ERR_INVALID_ARG, "batch too large: at most 2^28 rows per call");
+    if (!row_offsets) return fail(c, BPGPU_ERR_INVALID_ARG, "row_offsets missing");
+    if (values && value_bytes != 8 && value_bytes != 32) return fail(c, BPGPU_ERR_INVALID_ARG, "value_bytes must be 8 (u64) or 32 (scalars)");
+    if (row_offsets[0] != 0) return fail(c, BPGPU_ERR_INVALID_ARG, "row_offsets must start at 0");
+    for (size_t r = 0; r < nbatch; r++)
+        if (row_offsets[r + 1] < row_offsets[r]) return fail(c, BPGPU_ERR_INVALID_ARG, "row_offsets must not decrease");
+    if (row_offsets[nbatch] > PED_MAX_BATCH) return fail(c, BPGPU_ERR_INVALID_ARG, "too many terms: at most 2^28 per call");
+    if (row_offsets[nbatch] && !points) return fail(c, BPGPU_ERR_INVALID_ARG, "points missing");
+    try {   // (the table has (passes + 1)(nbatch + 1) words: gigabytes at the documented limit)
+        psum_make_plan(pl, (uint32_t)nbatch, row_offsets);
+    } catch (const std::bad_alloc &) {
+        return fail(c, BPGPU_ERR_INVALID_ARG, "out of host memory for the plan table of %zu rows", nbatch);
+    }
+    return BPGPU_OK;
+}
+// the call's working set in the arena: [plan table (the _dev forms; the host forms stage it with their inputs)][row flags][partials]
+struct psum_arena {
+    size_t off_tab, off_bad, off_part, total;
+    psum_arena(const psum_plan &pl, bool with_table) {
+        arena_plan ap;
+        off_tab = ap.add(with_table ? pl.table.size() * 4 : 0);
+        off_bad = ap.add(pl.nbatch);
+        off_part = ap.add((size_t)pl.partials() * sizeof(ge_ext));
+        total = ap.total;
+    }
+};
+// enqueue the launches on s.  d_tab: the plan table on the device.  balance: verdicts to d_status; else sums to d_out and BPGPU_MSM_*
+// bytes to d_status, the walk constant-time under the context option "prover_constant_time" (its own small-window table, built on
+// first use).  Without a scalar no generator is touched.
+static int psum_launch_locked(bpgpu_ctx *c, hipStream_t s, const psum_plan &pl, const psum_arena &ar, const uint32_t *d_tab, const void *d_points, const void *d_signs,
+                              const void *d_values, size_t value_bytes, const void *d_blindings, bool balance, void *d_out, void *d_status) {
+    const bool scalars = d_values || d_blindings;
+    uint32_t *d_ids = nullptr;
+    int rc;
+    if (scalars && (rc = gen_ids_for(c, 1, 1, &d_ids))) return rc;   // the shared path's list: [0] = B_blinding, [1] = B
+    const bool ct = scalars && !balance && c->prover_ct;
+    if (ct && (rc = build_ct_table(c))) return rc;
+    ped_in in;
+    in.values = (const uint32_t *)d_values;
+    in.value_words = (uint32_t)(value_bytes / 4);
+    in.blindings = (const uint32_t *)d_blindings;
+    in.seed32 = nullptr;
+    in.first_draw = 0;
+    const uint32_t nb = pl.nbatch, stride = nb + 1;
+    uint8_t *d_bad = (uint8_t *)(c->arena + ar.off_bad);
+    ge_ext *src = (ge_ext *)(c->arena + ar.off_part), *dst = src;
+    HIPCHK(c, hipMemsetAsync(d_bad, 0, nb, s));
+    for (uint32_t k = 0; k < pl.npasses && pl.items(0); k++) {
+        const psum_pass ps = {pl.items(k), nb, d_tab + (size_t)k * stride, d_tab + (size_t)(k + 1) * stride};
+        const uint32_t grid = (ps.total + PSUM_BLOCK - 1) / PSUM_BLOCK;
+        if (k == 0) LAUNCH(c, s, "psum_terms", k_psum_terms, grid, PSUM_BLOCK, ps, (const uint32_t *)d_points, (const uint8_t *)d_signs, d_bad, dst);
+        else LAUNCH(c, s, "psum_reduce", k_psum_reduce, grid, PSUM_BLOCK, ps, (const ge_ext *)src, dst);
+        src = dst;
+        dst += pl.items(k + 1);
+    }
+    const uint32_t *d_slot = d_tab + (size_t)pl.npasses * stride;
+    const fb_params prm = scalars ? (ct ? c->prm_ct : c->prm) : fb_params();
+    const fb_entry *table = scalars ? (const fb_entry *)(ct ? c->d_table_ct : c->d_table) : nullptr;
+    const uint32_t grid = (nb + BP_BLOCK - 1) / BP_BLOCK;
+    if (balance)
+        LAUNCH(c, s, "psum_balance", k_psum_balance, grid, BP_BLOCK, nb, in, prm, (const uint32_t *)d_ids, table, d_slot, (const ge_ext *)src, (const uint8_t *)d_bad,
+               (uint8_t *)d_status);
+    else if (ct)
+        LAUNCH(c, s, "psum_finish_ct", k_psum_finish<true>, grid, BP_BLOCK, nb, in, prm, (const uint32_t *)d_ids, table, d_slot, (const ge_ext *)src, (const uint8_t *)d_bad,
+               (uint32_t *)d_out, (uint8_t *)d_status);
+    else
+        LAUNCH(c, s, "psum_finish", k_psum_finish<false>, grid, BP_BLOCK, nb, in, prm, (const uint32_t *)d_ids, table, d_slot, (const ge_ext *)src, (const uint8_t *)d_bad,
+               (uint32_t *)d_out, (uint8_t *)d_status);
+    if (hipGetLastError() != hipSuccess) return fail(c, BPGPU_ERR_HIP, "launch failed");
+    return BPGPU_OK;
+}
+
+// the host forms: values and blindings lead the staged inputs -- the secret span of the sum form; out == nullptr: the balance form
+static int psum_host(bpgpu_ctx *c, size_t nbatch, const uint32_t *row_offsets, const uint8_t *points, const uint8_t *signs, const void *values, size_t value_bytes,
+                     const uint8_t *blindings, uint8_t *out, uint8_t *status) {
+    if (!c) return BPGPU_ERR_INVALID_ARG;
+    if (nbatch == 0) return BPGPU_OK;
+    const bool balance = !out;
+    psum_plan pl;
+    int rc = psum_check_args(c, nbatch, row_offsets, points, values, value_bytes, pl);
+    if (rc) return rc;
+    if (!status) return fail(c, BPGPU_ERR_INVALID_ARG, balance ? "verdict_out is required" : "out and status_out are required");
+    const size_t total = row_offsets[nbatch];
+    for (size_t t = 0; signs && t < total; t++)
+        if (signs[t] > 1) return fail(c, BPGPU_ERR_INVALID_ARG, "a sign byte is 0 (add) or 1 (subtract)");
+    std::lock_guard<std::mutex> lk(c->mu);
+    HIPCHK(c, hipSetDevice(c->device));
+    if ((values || blindings) && !c->d_table) return fail(c, BPGPU_ERR_NO_GENS, "generators not loaded");
+    hipStream_t s = c->stream;
+    host_call<bpgpu_ctx> io(c, s);
+    const int r_val = io.in(values ? nbatch * value_bytes : 0), r_bl = io.in(blindings ? nbatch * 32 : 0), r_tab = io.in(pl.table.size() * 4);
+    const int r_pts = io.in(total * 32), r_sg = io.in(signs ? total : 0);
+    const int r_out = io.out(balance ? 0 : nbatch * 32), r_st = io.out(nbatch);
+    if (values || blindings) io.secrets(io.off[r_tab]);   // a wallet's (value, blinding), or an opening shown to this verifier alone (as bpgpu_pedersen_open_batch); the commitments are public
+    rc = io.open();
+    if (rc) return io.finish(rc);
+    const psum_arena ar(pl, false);
+    if ((rc = arena_reserve(c, ar.total))) return io.finish(rc);
+    if (values) io.put(r_val, values, nbatch * value_bytes);
+    if (blindings) io.put(r_bl, blindings, nbatch * 32);
+    io.put(r_tab, pl.table.data(), pl.table.size() * 4);
+    if (total) io.put(r_pts, points, total * 32);
+    if (signs && total) io.put(r_sg, signs, total);
+    if ((rc = io.upload())) return io.finish(rc);
+    rc = psum_launch_locked(c, s, pl, ar, (const uint32_t *)io.d(r_tab), io.d(r_pts), signs ? io.d(r_sg) : nullptr, values ? io.d(r_val) : nullptr, value_bytes,
+                            blindings ? io.d(r_bl) : nullptr, balance, balance ? nullptr : io.d(r_out), io.d(r_st));
+    rc = io.finish(io.download(rc));
+    if (rc) return rc;
+    if (!balance) memcpy(out, io.h(r_out), nbatch * 32);
+    memcpy(status, io.h(r_st), nbatch);
+    return BPGPU_OK;
+}
+extern "C" int bpgpu_pedersen_sum_batch(bpgpu_ctx *c, size_t nbatch, const uint32_t *row_offsets, const uint8_t *points, const uint8_t *signs, const void *values,
+                                        size_t value_bytes, const uint8_t *blindings, uint8_t *out, uint8_t *status_out) {
+    if (c && nbatch && !out) return fail(c, BPGPU_ERR_INVALID_ARG, "out and status_out are required");
+    return psum_host(c, nbatch, row_offsets, points, signs, values, value_bytes, blindings, out, status_out);
+}
+extern "C" int bpgpu_pedersen_balance_batch(bpgpu_ctx *c, size_t nbatch, const uint32_t *row_offsets, const uint8_t *points, const uint8_t *signs, const void *values,
+                                            size_t value_bytes, const uint8_t *blindings, uint8_t *verdict_out) {
+    return psum_host(c, nbatch, row_offsets, points, signs, values, value_bytes, blindings, nullptr, verdict_out);
+}
+
+// the _dev forms: row_offsets stays a host array (the launch geometry follows from it); the plan table is the only host -> device traffic
+static int psum_dev(bpgpu_ctx *c, size_t nbatch, const uint32_t *row_offsets, const void *d_points, const void *d_signs, const void *d_values, size_t value_bytes,
+                    const void *d_blindings, void *d_out, void *d_status, void *stream) {
+    if (!c) return BPGPU_ERR_INVALID_ARG;
+    if (nbatch == 0) return BPGPU_OK;
+    const bool balance = !d_out;
+    psum_plan pl;
+    int rc = psum_check_args(c, nbatch, row_offsets, d_points, d_values, value_bytes, pl);
+    if (rc) return rc;
+    if (!d_status) return fail(c, BPGPU_ERR_INVALID_ARG, balance ? "verdict_out is required" : "out and status_out are required");
+    if (((uintptr_t)d_points | (uintptr_t)d_values | (uintptr_t)d_blindings | (uintptr_t)d_out) & 3) return fail(c, BPGPU_ERR_INVALID_ARG, "device buffers must be 4-byte aligned");
+    std::lock_guard<std::mutex> lk(c->mu);
+    HIPCHK(c, hipSetDevice(c->device));
+    if ((d_values || d_blindings) && !c->d_table) return fail(c, BPGPU_ERR_NO_GENS, "generators not loaded");
+    hipStream_t s = stream ? (hipStream_t)stream : c->stream;
+    if ((rc = ctx_enter(c, s))) return rc;
+    const psum_arena ar(pl, true);
+    char *h_tab = nullptr;
+    const size_t tab_bytes = pl.table.size() * 4;
+    do {
+        if ((rc = arena_reserve(c, ar.total)) || (rc = c->io.pin_alloc(tab_bytes, &h_tab))) break;
+        memcpy(h_tab, pl.table.data(), tab_bytes);
+        c->io.last_secret_bytes = 0;   // (the block's leading bytes now hold this call's plan table: public)
+        if (hipMemcpyAsync(c->arena + ar.off_tab, h_tab, tab_bytes, hipMemcpyHostToDevice, s) != hipSuccess || c->io.pin_mark(s)) {
+            rc = fail(c, BPGPU_ERR_HIP, "staging the plan table failed");
+            break;
+        }
+        rc = psum_launch_locked(c, s, pl, ar, (const uint32_t *)(c->arena + ar.off_tab), d_points, d_signs, d_values, value_bytes, d_blindings, balance, d_out, d_status);
+    } while (0);
+    // what the library itself allocated for the call -- plan table, row flags, partials -- is cleared on the stream behind the finish, as the
+    // other _dev forms of this family clear theirs: nothing of a call stays in the context's working set
+    bool ok = true;
+    if (c->arena && c->arena_cap >= ar.total) ok = hipMemsetAsync(c->arena, 0, ar.total, s) == hipSuccess;
+    const int rc2 = ctx_leave(c, s);
+    if (!rc && !ok) rc = fail(c, BPGPU_ERR_HIP, "clearing the working set failed");
+    return rc ? rc : rc2;
+}
+extern "C" int bpgpu_pedersen_sum_batch_dev(bpgpu_ctx *c, size_t nbatch, const uint32_t *row_offsets, const void *d_points, const void *d_signs, const void *d_values,
+                                            size_t value_bytes, const void *d_blindings, void *d_out, void *d_status_out, void *stream) {
+    if (c && nbatch && !d_out) return fail(c, BPGPU_ERR_INVALID_ARG, "out and status_out are required");
+    return psum_dev(c, nbatch, row_offsets, d_points, d_signs, d_values, value_bytes, d_blindings, d_out, d_status_out, stream);
+}
+extern "C" int bpgpu_pedersen_balance_batch_dev(bpgpu_ctx *c, size_t nbatch, const uint32_t *row_offsets, const void *d_points, const void *d_signs, const void *d_values,
+                                                size_t value_bytes, const void *d_blindings, void *d_verdict_out, void *stream) {
+    return psum_dev(c, nbatch, row_offsets, d_points, d_signs, d_values, value_bytes, d_blindings, nullptr, d_verdict_out, stream);
 }
 
 // ============================================================================

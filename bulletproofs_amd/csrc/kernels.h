@@ -28,6 +28,7 @@
 #include "mpc_dealer.h"
 #include "ts_batch.h"
 #include "pedersen.h"
+#include "pedersen_sum.h"
 
 #define BP_BLOCK 64   // one wavefront per workgroup: under contention a CU rarely has room for four waves of one group at once (256: -8% at 48 streams)
 #define FB_BLOCK 64
@@ -201,5 +202,12 @@ __global__ void k_ts_batch(uint32_t nbatch, const uint32_t *ts_in, uint32_t ts_i
 template <bool CT>
 __global__ void k_ped_commit(uint32_t nbatch, ped_in in, fb_params prm, const uint32_t *gen_ids, const fb_entry *table, uint32_t *out_words, uint32_t *blindings_out, uint8_t *status);
 __global__ void k_ped_open(uint32_t nbatch, ped_in in, const uint32_t *commitments, fb_params prm, const uint32_t *gen_ids, const fb_entry *table, uint8_t *verdict);
+
+// k_pedersen_sum.hip
+__global__ void k_psum_terms(psum_pass ps, const uint32_t *points, const uint8_t *signs, uint8_t *bad, ge_ext *partial);
+__global__ void k_psum_reduce(psum_pass ps, const ge_ext *src, ge_ext *partial);
+template <bool CT>
+__global__ void k_psum_finish(uint32_t nbatch, ped_in in, fb_params prm, const uint32_t *gen_ids, const fb_entry *table, const uint32_t *slot, const ge_ext *partial, const uint8_t *bad, uint32_t *out_words, uint8_t *status);
+__global__ void k_psum_balance(uint32_t nbatch, ped_in in, fb_params prm, const uint32_t *gen_ids, const fb_entry *table, const uint32_t *slot, const ge_ext *partial, const uint8_t *bad, uint8_t *verdict);
 
 #endif

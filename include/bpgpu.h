@@ -1011,6 +1011,53 @@ int bpgpu_pedersen_commit_batch_dev(bpgpu_ctx *ctx, size_t nbatch, const void *d
 int bpgpu_pedersen_open_batch_dev(bpgpu_ctx *ctx, size_t nbatch, const void *d_commitments, const void *d_values, size_t value_bytes,
                                   const void *d_blindings, void *d_verdict_out, void *stream);
 
+/* ---- signed sums of Pedersen commitments, and the balance check over them ------------------------
+ * What the commitments are for: a validator of confidential transactions checks, beside the range proofs, that inputs minus outputs
+ * open to (fee, excess); a wallet or ledger updates a committed balance, C' = C + v B + r B_blinding.  csrc/pedersen_sum.h.
+ * A call has nbatch rows.  Row r owns the terms [row_offsets[r], row_offsets[r + 1]) of ONE flat array of 32-byte Ristretto encodings.
+ *   row_offsets : HOST array of nbatch + 1 uint32_t, non-decreasing, row_offsets[0] = 0 (also in the _dev forms: the launch geometry
+ *                 follows from it, as from n_terms in bpgpu_msm_batch_dev).  A row may have no terms.  At most 2^28 rows and 2^28
+ *                 terms per call.
+ *   points      : row_offsets[nbatch] x 32 bytes
+ *   signs       : one byte per term, 0 = add, 1 = subtract; NULL = every term is added
+ *   values      : optional.  value_bytes = 8: nbatch u64; value_bytes = 32: nbatch x 32-byte scalars.  NULL = 0.
+ *   blindings   : optional, nbatch x 32 bytes.  NULL = 0.
+ * With S_r = sum_{sign 0} C_i - sum_{sign 1} C_i and O_r = values[r] B + blindings[r] B_blinding (the context's bases):
+ * bpgpu_pedersen_sum_batch:     out[r] = compress(S_r + O_r), 32 bytes.  status_out[r] = BPGPU_MSM_OK, BPGPU_MSM_BAD_POINT when a term
+ *   of the row does not decode, BPGPU_MSM_BAD_SCALAR when the value or the blinding is not canonical.  A rejected row's output is 32
+ *   zero bytes; the other rows are unaffected.
+ * bpgpu_pedersen_balance_batch: verdict_out[r] = BPGPU_VERDICT_OK iff S_r == O_r as Ristretto elements -- the signed sum opens to
+ *   (value, blinding).  The test is the coset identity test (X == 0 or Y == 0) on S_r - O_r: nothing is compressed, no inversion is
+ *   taken.  BPGPU_VERDICT_VERIFICATION_ERROR when the row does not balance or a term does not decode (a None of
+ *   optional_multiscalar_mul in the verifiers); BPGPU_VERDICT_FORMAT_ERROR for a scalar that is not canonical.
+ * In both a scalar that is not canonical takes precedence over a point that does not decode in the same row (as in
+ * bpgpu_pedersen_open_batch).  nbatch = 0 is BPGPU_OK.  With values == NULL and blindings == NULL no generator is needed and the call
+ * works on a context that never loaded any (as bpgpu_r1cs_witness_check does); otherwise such a context returns BPGPU_ERR_NO_GENS.
+ * BPGPU_ERR_INVALID_ARG: a value_bytes other than 8 or 32 when values is given; offsets that decrease or do not start at 0; too many
+ * rows or terms; in the host forms a sign byte above 1 (the _dev forms use bit 0 of the byte and read nothing back).
+ * CONTRACTS: (a) row r of the sum call equals bpgpu_msm_batch on the terms (+-1, C_i) ..., (value, B), (blinding, B_blinding);
+ * (b) a row without terms equals row r of bpgpu_pedersen_commit_batch; (c) a balance row with exactly one added term has the verdict
+ * of bpgpu_pedersen_open_batch on the same (commitment, value, blinding) -- whatever "fixed_window_bits" and "prover_constant_time"
+ * are.
+ * Timing and secrets: the balance forms are VARIABLE TIME; their inputs are public to a verifier.  In the sum forms the commitments are
+ * public, but (value, blinding) may be a wallet's secrets: the walk over B and B_blinding honours "prover_constant_time" exactly as
+ * bpgpu_pedersen_commit_batch does (the bytes are the same either way), and a host form that is given a value or a blinding -- sum or
+ * balance: an opening is shown to this verifier alone, as in bpgpu_pedersen_open_batch -- stages them through the provers' secret
+ * staging: staging, the device IO buffer and the working sets are cleared on every exit, as bpgpu_rangeproof_prove_batch documents.
+ * The _dev forms take device pointers for points, signs, values, blindings and outputs (4-byte aligned; signs at any alignment) and
+ * enqueue on `stream` (NULL: the context's own) with the conventions of the other _dev entry points.  The only host -> device traffic
+ * is the library's own plan table (a few words per row), through its staging; what the library allocated for the call (plan table,
+ * row flags, partial sums) is cleared on the stream behind the last kernel. */
+int bpgpu_pedersen_sum_batch(bpgpu_ctx *ctx, size_t nbatch, const uint32_t *row_offsets, const uint8_t *points, const uint8_t *signs,
+                             const void *values, size_t value_bytes, const uint8_t *blindings, uint8_t *out, uint8_t *status_out);
+int bpgpu_pedersen_balance_batch(bpgpu_ctx *ctx, size_t nbatch, const uint32_t *row_offsets, const uint8_t *points, const uint8_t *signs,
+                                 const void *values, size_t value_bytes, const uint8_t *blindings, uint8_t *verdict_out);
+int bpgpu_pedersen_sum_batch_dev(bpgpu_ctx *ctx, size_t nbatch, const uint32_t *row_offsets, const void *d_points, const void *d_signs,
+                                 const void *d_values, size_t value_bytes, const void *d_blindings, void *d_out, void *d_status_out,
+                                 void *stream);
+int bpgpu_pedersen_balance_batch_dev(bpgpu_ctx *ctx, size_t nbatch, const uint32_t *row_offsets, const void *d_points, const void *d_signs,
+                                     const void *d_values, size_t value_bytes, const void *d_blindings, void *d_verdict_out, void *stream);
+
 /* ---- the multi-party aggregation protocol: parties and dealer ------------------------------------
  * range_proof_mpc of the reference (src/range_proof/party.rs, dealer.rs, messages.rs; docs/aggregation-api.md) as six
  * batched, STATELESS calls: host pointers in and out, nothing retained after return.  bpgpu_rangeproof_prove_batch above

@@ -22,6 +22,7 @@
 #include <cstdint>
 #include <cstring>
 #include <memory>
+#include <optional>
 #include <stdexcept>
 #include <string>
 #include <utility>
@@ -120,6 +121,28 @@ class BulletproofGens {
                                         const std::vector<ScalarBytes> &blindings) const {
         return open_rows(commitments, values.data(), 32, values.size(), blindings);
     }
+    // Row r: sum(plus[r]) - sum(minus[r]) + values[r] B + blindings[r] B_blinding, compressed (bpgpu_pedersen_sum_batch; no counterpart
+    // in the crate).  minus, values, blindings may be nullptr (no subtracted terms / zero).  An entry is empty where a term of the row
+    // did not decode; a non-canonical scalar throws std::invalid_argument.
+    using Rows = std::vector<std::vector<CompressedRistretto>>;
+    std::vector<std::optional<CompressedRistretto>> sum_commitments(const Rows &plus, const Rows *minus = nullptr, const std::vector<uint64_t> *values = nullptr,
+                                                                    const std::vector<ScalarBytes> *blindings = nullptr) const {
+        return sum_rows(plus, minus, values ? values->data() : nullptr, 8, values ? values->size() : plus.size(), blindings);
+    }
+    std::vector<std::optional<CompressedRistretto>> sum_commitments(const Rows &plus, const Rows *minus, const std::vector<ScalarBytes> &values,
+                                                                    const std::vector<ScalarBytes> *blindings = nullptr) const {
+        return sum_rows(plus, minus, values.data(), 32, values.size(), blindings);
+    }
+    // does sum(inputs[r]) - sum(outputs[r]) open to (values[r], blindings[r])? (bpgpu_pedersen_balance_batch)  VerificationError: it
+    // does not, or a commitment is no valid encoding; FormatError: a non-canonical scalar.  A missing value or blinding is zero.
+    std::vector<Status> verify_balance(const Rows &inputs, const Rows &outputs, const std::vector<uint64_t> *values = nullptr,
+                                       const std::vector<ScalarBytes> *blindings = nullptr) const {
+        return balance_rows(inputs, outputs, values ? values->data() : nullptr, 8, values ? values->size() : inputs.size(), blindings);
+    }
+    std::vector<Status> verify_balance(const Rows &inputs, const Rows &outputs, const std::vector<ScalarBytes> &values,
+                                       const std::vector<ScalarBytes> *blindings = nullptr) const {
+        return balance_rows(inputs, outputs, values.data(), 32, values.size(), blindings);
+    }
     // BulletproofGens::increase_capacity (generators.rs:177-204): no-op unless larger; the device tables are rebuilt
     void increase_capacity(size_t new_capacity) {
         if (gens_capacity >= new_capacity) return;
@@ -163,6 +186,58 @@ class BulletproofGens {
         std::vector<Status> res;
         if (nb == 0) return res;
         if (bpgpu_pedersen_open_batch(ctx_.get(), nb, commitments[0].data(), values, value_bytes, blindings[0].data(), vd.data()) != BPGPU_OK)
+            throw GpuError(bpgpu_last_error(ctx_.get()));
+        for (size_t i = 0; i < nb; i++) res.push_back(vd[i] == 0 ? Status::Ok() : Status::Err((ProofError)vd[i]));
+        return res;
+    }
+    // the flat form of bpgpu_pedersen_sum_batch: offsets, the rows' added terms followed by their subtracted ones, one sign byte per term
+    struct SignedRows {
+        std::vector<uint32_t> off;
+        std::vector<uint8_t> pts, signs;
+    };
+    static SignedRows flatten(const Rows &plus, const Rows *minus, size_t n_scalars, const std::vector<ScalarBytes> *blindings, const char *who) {
+        if ((minus && minus->size() != plus.size()) || n_scalars != plus.size() || (blindings && blindings->size() != plus.size()))
+            throw std::invalid_argument(std::string(who) + ": one list of subtracted commitments, one value and one blinding per row");
+        SignedRows f;
+        f.off.push_back(0);
+        for (size_t r = 0; r < plus.size(); r++) {
+            for (int side = 0; side < 2; side++) {
+                if (side && !minus) break;
+                for (const CompressedRistretto &c : side ? (*minus)[r] : plus[r]) {
+                    f.pts.insert(f.pts.end(), c.begin(), c.end());
+                    f.signs.push_back(static_cast<uint8_t>(side));
+                }
+            }
+            f.off.push_back(static_cast<uint32_t>(f.signs.size()));
+        }
+        return f;
+    }
+    std::vector<std::optional<CompressedRistretto>> sum_rows(const Rows &plus, const Rows *minus, const void *values, size_t value_bytes, size_t n_values,
+                                                             const std::vector<ScalarBytes> *blindings) const {
+        const SignedRows f = flatten(plus, minus, n_values, blindings, "sum_commitments");
+        const size_t nb = plus.size();
+        std::vector<std::optional<CompressedRistretto>> res(nb);
+        if (nb == 0) return res;
+        std::vector<CompressedRistretto> out(nb);
+        std::vector<uint8_t> st(nb);
+        if (bpgpu_pedersen_sum_batch(ctx_.get(), nb, f.off.data(), f.pts.data(), f.signs.data(), values, value_bytes, blindings ? (*blindings)[0].data() : nullptr,
+                                     out[0].data(), st.data()) != BPGPU_OK)
+            throw GpuError(bpgpu_last_error(ctx_.get()));
+        for (size_t i = 0; i < nb; i++) {
+            if (st[i] == BPGPU_MSM_BAD_SCALAR) throw std::invalid_argument("sum_commitments: scalars must be canonical");
+            if (st[i] == BPGPU_MSM_OK) res[i] = out[i];
+        }
+        return res;
+    }
+    std::vector<Status> balance_rows(const Rows &inputs, const Rows &outputs, const void *values, size_t value_bytes, size_t n_values,
+                                     const std::vector<ScalarBytes> *blindings) const {
+        const SignedRows f = flatten(inputs, &outputs, n_values, blindings, "verify_balance");
+        const size_t nb = inputs.size();
+        std::vector<uint8_t> vd(nb);
+        std::vector<Status> res;
+        if (nb == 0) return res;
+        if (bpgpu_pedersen_balance_batch(ctx_.get(), nb, f.off.data(), f.pts.data(), f.signs.data(), values, value_bytes, blindings ? (*blindings)[0].data() : nullptr,
+                                         vd.data()) != BPGPU_OK)
             throw GpuError(bpgpu_last_error(ctx_.get()));
         for (size_t i = 0; i < nb; i++) res.push_back(vd[i] == 0 ? Status::Ok() : Status::Err((ProofError)vd[i]));
         return res;
