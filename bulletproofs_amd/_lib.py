@@ -50,7 +50,11 @@ EXPORTS = [
     "bpgpu_mpc_party_bit_commit_seeded", "bpgpu_mpc_party_poly_commit_seeded",
     "bpgpu_pedersen_commit_batch", "bpgpu_pedersen_open_batch", "bpgpu_pedersen_commit_batch_dev", "bpgpu_pedersen_open_batch_dev",
     "bpgpu_pedersen_sum_batch", "bpgpu_pedersen_balance_batch", "bpgpu_pedersen_sum_batch_dev", "bpgpu_pedersen_balance_batch_dev",
+    "bpgpu_opening_create_batch_ts", "bpgpu_opening_verify_batch_ts", "bpgpu_opening_verify_batch_ts_dev", "bpgpu_opening_verify_rlc_ts",
+    "bpgpu_opening_verify_rlc_ts_dev",
 ]
+
+OPENING_FULL, OPENING_BLINDING = 0, 1   # bpgpu_opening_*: v and r secret (96-byte proofs) / v public, r secret (64-byte proofs)
 
 TRANSCRIPT_BYTES = 208
 TS_APPEND, TS_APPEND_U64, TS_CHALLENGE, TS_CHALLENGE_SCALAR = 1, 2, 3, 4       # bpgpu_ts_op.kind
@@ -169,6 +173,11 @@ def lib():
     L.bpgpu_pedersen_balance_batch.argtypes = [vp, sz, u32p, u8p, u8p, u8p, sz, u8p, u8p]
     L.bpgpu_pedersen_sum_batch_dev.argtypes = [vp, sz, u32p, vp, vp, vp, sz, vp, vp, vp, vp]
     L.bpgpu_pedersen_balance_batch_dev.argtypes = [vp, sz, u32p, vp, vp, vp, sz, vp, vp, vp]
+    L.bpgpu_opening_create_batch_ts.argtypes = [vp, i, sz, u8p, sz, u8p, u8p, u8p, sz, u8p, u8p, u8p, u8p]
+    L.bpgpu_opening_verify_batch_ts.argtypes = [vp, i, sz, u8p, sz, u8p, sz, u8p, u8p, sz, u8p, u8p, u8p]
+    L.bpgpu_opening_verify_batch_ts_dev.argtypes = [vp, i, sz, vp, sz, u8p, vp, vp, vp, sz, vp, vp, vp, vp]
+    L.bpgpu_opening_verify_rlc_ts.argtypes = [vp, i, sz, u8p, sz, u8p, sz, u8p, u8p, sz, u8p, u8p, u8p, u8p]
+    L.bpgpu_opening_verify_rlc_ts_dev.argtypes = [vp, i, sz, vp, sz, u8p, vp, vp, vp, sz, vp, vp, vp, vp, vp]
     L.bpgpu_pool_create.argtypes = [C.POINTER(C.c_int), i, i, C.POINTER(vp)]
     L.bpgpu_pool_destroy.argtypes = [vp]
     L.bpgpu_pool_destroy.restype = None
@@ -783,6 +792,70 @@ class Context:
         nb = len(row_offsets) - 1
         self._chk(self._L.bpgpu_pedersen_balance_batch_dev(self.h, nb, (C.c_uint32 * (nb + 1))(*row_offsets), d_points, d_signs, d_values, value_bytes, d_blindings,
                                                            d_verdict, stream))
+
+    # ---- proofs of knowledge of commitment openings (bpgpu_opening_*) ----
+    @staticmethod
+    def _opening_args(form, nb, values, value_bytes):
+        assert form in (OPENING_FULL, OPENING_BLINDING) and value_bytes in (8, 32)
+        assert values is None or len(values) == value_bytes * nb
+        return None if values is None else bytes(values)
+
+    def opening_create_batch_ts(self, form, transcripts, commitments, values, value_bytes, blindings, rng32=None, want_transcripts=False):
+        """Proofs that the caller knows the openings (values[i], blindings[i]) of commitments[i], each on its caller's own transcript
+        (bpgpu_opening_create_batch_ts).  form OPENING_FULL: value and blinding secret, 96-byte proofs; OPENING_BLINDING: the value is
+        public (values None: every value 0), 64-byte proofs.  rng32: 32 bytes per proof, the seed of its ChaChaRng (None: the library
+        draws them); never one seed for two statements or transcripts.  Returns (proofs bytes, status bytes[, transcripts])."""
+        nb = len(commitments) // 32
+        values = self._opening_args(form, nb, values, value_bytes)
+        assert len(commitments) == len(blindings) == 32 * nb and (rng32 is None or len(rng32) == 32 * nb)
+        pl = 96 if form == OPENING_FULL else 64
+        out, st = C.create_string_buffer(pl * max(nb, 1)), C.create_string_buffer(max(nb, 1))
+        tso = C.create_string_buffer(TRANSCRIPT_BYTES * max(nb, 1)) if want_transcripts else None
+        self._chk(self._L.bpgpu_opening_create_batch_ts(self.h, form, nb, transcripts, self._ts_stride(transcripts, nb), rng32, bytes(commitments), values,
+                                                        value_bytes, bytes(blindings), out, st, tso))
+        res = (out.raw[:pl * nb], st.raw[:nb])
+        return res + (tso.raw[:TRANSCRIPT_BYTES * nb],) if want_transcripts else res
+
+    def opening_verify_batch_ts(self, form, proofs, proof_len, transcripts, commitments, values=None, value_bytes=8, want_msm=False, want_transcripts=False):
+        """Verify len(commitments) / 32 opening proofs one by one (bpgpu_opening_verify_batch_ts).  values: the public values of form
+        OPENING_BLINDING (None: every value 0); None in form OPENING_FULL.  Returns the verdict bytes[, msm_out][, transcripts]."""
+        nb = len(commitments) // 32
+        values = self._opening_args(form, nb, values, value_bytes)
+        assert len(proofs) == nb * proof_len
+        verdict = C.create_string_buffer(max(nb, 1))
+        msm = C.create_string_buffer(32 * max(nb, 1)) if want_msm else None
+        tso = C.create_string_buffer(TRANSCRIPT_BYTES * max(nb, 1)) if want_transcripts else None
+        self._chk(self._L.bpgpu_opening_verify_batch_ts(self.h, form, nb, bytes(proofs), proof_len, transcripts, self._ts_stride(transcripts, nb),
+                                                        bytes(commitments), values, value_bytes, verdict, msm, tso))
+        out = (verdict.raw[:nb],) + ((msm.raw[:32 * nb],) if want_msm else ()) + ((tso.raw[:TRANSCRIPT_BYTES * nb],) if want_transcripts else ())
+        return out if len(out) > 1 else out[0]
+
+    def opening_verify_rlc_ts(self, form, proofs, proof_len, transcripts, commitments, values=None, value_bytes=8, weights64=None, want_transcripts=False):
+        """The same verdicts through ONE combined check (bpgpu_opening_verify_rlc_ts; per-proof fallback where it does not decide).
+        Returns (verdict bytes, batch_ok, 32-byte encoding of the combined point[, transcripts])."""
+        nb = len(commitments) // 32
+        values = self._opening_args(form, nb, values, value_bytes)
+        assert len(proofs) == nb * proof_len and (weights64 is None or len(weights64) == 64 * nb)
+        verdict = C.create_string_buffer(max(nb, 1))
+        bo = C.create_string_buffer(33)
+        tso = C.create_string_buffer(TRANSCRIPT_BYTES * max(nb, 1)) if want_transcripts else None
+        self._chk(self._L.bpgpu_opening_verify_rlc_ts(self.h, form, nb, bytes(proofs), proof_len, transcripts, self._ts_stride(transcripts, nb),
+                                                      bytes(commitments), values, value_bytes, weights64, verdict, bo, tso))
+        out = (verdict.raw[:nb], bo.raw[0] == 0, bo.raw[1:33])
+        return out + (tso.raw[:TRANSCRIPT_BYTES * nb],) if want_transcripts else out
+
+    def opening_verify_batch_ts_dev(self, form, nbatch, d_proofs, proof_len, shared_transcript, d_transcripts, d_commitments, d_values, value_bytes,
+                                    d_verdict, d_msm_out=None, d_transcripts_out=None, stream=None):
+        """bpgpu_opening_verify_batch_ts_dev: shared_transcript a 208-byte host state or None, every buffer a device address (int, or
+        None), asynchronous on `stream`."""
+        self._chk(self._L.bpgpu_opening_verify_batch_ts_dev(self.h, form, nbatch, d_proofs, proof_len, shared_transcript, d_transcripts, d_commitments,
+                                                            d_values, value_bytes, d_verdict, d_msm_out, d_transcripts_out, stream))
+
+    def opening_verify_rlc_ts_dev(self, form, nbatch, d_proofs, proof_len, shared_transcript, d_transcripts, d_commitments, d_values, value_bytes,
+                                  d_weights64, d_verdict, d_batch_out=None, d_transcripts_out=None, stream=None):
+        """bpgpu_opening_verify_rlc_ts_dev: as above; undecided verdicts read BPGPU_VERDICT_UNDECIDED (5)."""
+        self._chk(self._L.bpgpu_opening_verify_rlc_ts_dev(self.h, form, nbatch, d_proofs, proof_len, shared_transcript, d_transcripts, d_commitments,
+                                                          d_values, value_bytes, d_weights64, d_verdict, d_batch_out, d_transcripts_out, stream))
 
     # ---- batches of transcripts (bpgpu_transcript_batch) ----
     @staticmethod

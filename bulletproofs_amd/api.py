@@ -49,7 +49,7 @@ class BulletproofGens:
     """BulletproofGens::new(gens_capacity, party_capacity) (src/generators.rs:157-166), derived on the GPU."""
 
     def __init__(self, gens_capacity, party_capacity, device=0, **ctx_options):
-        self.gens_capacity, self.party_capacity = gens_capacity, party_capacity
+        self.gens_capacity, self.party_capacity, self.device = gens_capacity, party_capacity, device
         self.ctx = Context(device, **ctx_options)
         self.ctx.gens_create(gens_capacity, party_capacity)
 
@@ -214,6 +214,63 @@ class BulletproofGens:
         vd = self.ctx.pedersen_balance_batch(off, pts, sg, packed, vb, bl)
         return [None if x == 0 else _BY_CODE[x]() for x in vd]
 
+    def prove_balance(self, fees, excess_blindings, transcripts, inputs, outputs, rng_seed32=None):
+        """The excess proofs of a block of confidential transactions: row r proves knowledge of the blinding of
+        E_r = sum(inputs[r]) - sum(outputs[r]) - fees[r] B, which is excess_blindings[r] B_blinding when the row balances -- a Schnorr
+        signature under the key E_r (OpeningProof with the public value 0).  fees: ints below 2^64.  `transcripts` as in
+        OpeningProof.create_batch.  Returns [OpeningProof]; raises ValueError for a commitment that does not decode or a scalar that
+        is not canonical.  The prover needs no fee-free row: E_r is computed here, on the GPU (bpgpu_pedersen_sum_batch)."""
+        fees = [int(f) for f in fees]
+        if any(f < 0 or f >> 64 for f in fees):
+            raise ValueError("fees must be below 2^64")
+        E = self.sum_commitments(inputs, outputs, values=[((_L - f) % _L).to_bytes(32, "little") for f in fees])
+        if any(e is None for e in E):
+            raise ValueError("a commitment does not decode (row %d)" % next(i for i, e in enumerate(E) if e is None))
+        return OpeningProof.create_batch(self, transcripts, [0] * len(fees), excess_blindings, commitments=E, public_values=True, rng_seed32=rng_seed32)
+
+    def verify_balance_proved(self, inputs, outputs, fees, proofs, transcripts):
+        """The validator's side of prove_balance, without any secret: E_r = sum(inputs[r]) - sum(outputs[r]) - fees[r] B on the GPU
+        (bpgpu_pedersen_sum_batch_dev with the value l - fee) goes as a device buffer straight into the combined check of the excess
+        proofs (bpgpu_opening_verify_rlc_ts_dev, form OPENING_BLINDING, value 0); the excess never visits the host.  Returns a list of
+        None / ProofError.  A list of transcripts or a TranscriptBatch is left advanced as OpeningProof.verify_batch leaves it."""
+        import torch
+        fees = [int(f) for f in fees]
+        if any(f < 0 or f >> 64 for f in fees):
+            raise ValueError("fees must be below 2^64")
+        off, pts, sg, packed, vb, _ = self._signed_rows(inputs, outputs, [((_L - f) % _L).to_bytes(32, "little") for f in fees], None, "verify_balance_proved")
+        nb = len(off) - 1
+        raw, pl = OpeningProof._raw(proofs, 64)
+        if len(proofs) != nb:
+            raise ValueError("verify_balance_proved: one proof per row")
+        if nb == 0:
+            return []
+        per_proof = _per_proof(transcripts)
+        if per_proof and len(transcripts) != nb:
+            raise ValueError("verify_balance_proved: one transcript per row")
+        c = self.ctx
+        dev = torch.device("cuda:%d" % self.device)
+        up = lambda b: torch.frombuffer(bytearray(b), dtype=torch.uint8).to(dev)
+        new = lambda n: torch.zeros(n, dtype=torch.uint8, device=dev)
+        d_pts, d_sg, d_val, d_pr = up(pts) if pts else new(4), up(sg) if sg else new(4), up(packed), up(raw)
+        d_ts = up(_states_of(transcripts)) if per_proof else None
+        d_E, d_st, d_vd, d_to = new(32 * nb), new(nb), new(nb), new(208 * nb)
+        torch.cuda.synchronize(dev)
+        ptr = lambda t: None if t is None else t.data_ptr()
+        c.pedersen_sum_batch_dev(off, ptr(d_pts), ptr(d_sg), ptr(d_val), vb, None, ptr(d_E), ptr(d_st))
+        shared = None if per_proof else transcripts.state
+        c.opening_verify_rlc_ts_dev(1, nb, ptr(d_pr), pl, shared, ptr(d_ts), ptr(d_E), None, 8, None, ptr(d_vd), None, ptr(d_to))
+        c.synchronize()
+        vd = bytes(d_vd.cpu().numpy())
+        if 5 in vd:   # the combination did not decide: proof by proof, still on the device
+            c.opening_verify_batch_ts_dev(1, nb, ptr(d_pr), pl, shared, ptr(d_ts), ptr(d_E), None, 8, ptr(d_vd))
+            c.synchronize()
+            vd = bytes(d_vd.cpu().numpy())
+        st = bytes(d_st.cpu().numpy())
+        if per_proof:
+            _advance_all(transcripts, bytes(d_to.cpu().numpy()))
+        # a row whose sum did not decode has no key: never verified, whatever its proof says about the placeholder
+        return [VerificationError() if st[i] else (None if vd[i] == 0 else _BY_CODE[vd[i]]()) for i in range(nb)]
+
     def _check_pedersen(self, pc_gens):
         """The verifier multiplies by pc_gens.B / B_blinding (mod.rs:439-440); the device tables hold the bases this
         BulletproofGens was created with.  A different PedersenGens must be loaded with Context.gens_load."""
@@ -273,7 +330,7 @@ class TranscriptBatch:
     """n transcripts built and bound on the GPU (bpgpu_transcript_batch): the rows share their labels, the messages are per row.
     Appends are recorded and sent as ONE script -- by the next challenge, by states(), or when the batch is consumed: wherever a list
     of Transcript is accepted (RangeProof.verify_batch / verify_batch_combined / prove_batch, LinearProof.create_batch / verify_batch /
-    verify_batch_combined) a TranscriptBatch is, and is left advanced where the list would be.  batch[i] is row i as a Transcript (for
+    verify_batch_combined, OpeningProof.create_batch / verify_batch / verify_batch_combined, verify_balance_proved) a TranscriptBatch is, and is left advanced where the list would be.  batch[i] is row i as a Transcript (for
     the items of RangeProof.verify_mixed_combined, say)."""
 
     def __init__(self, ctx, label, n, _shared=None, _states=None):
@@ -713,3 +770,140 @@ class LinearProof:
         else:
             v, _, _ = c.linear_verify_rlc(n, raw, ln, cs, g, bytes(F), bytes(B), b, transcript=transcript.state, weights64=weights64)
         return [None if x == 0 else _BY_CODE[x]() for x in v]
+
+
+class OpeningProof:
+    """A proof of knowledge of the opening of a Pedersen commitment C = v B + r B_blinding under the context's bases (no counterpart in the
+    crate; the protocol is fixed in include/bpgpu.h, bpgpu_opening_*).  Two forms: both v and r secret (96 bytes: R | s_v | s_r), or
+    `public_values` -- v is known to the verifier, only r is secret (64 bytes: R | s_r); with v = 0 that is a Schnorr signature under
+    the key C, the excess proof of a confidential transaction.  `transcripts` everywhere: one bound Transcript, the start state of
+    every proof (not advanced), or a list of transcripts / a TranscriptBatch, one per proof, each left advanced."""
+
+    def __init__(self, raw):
+        self._raw = raw
+
+    @staticmethod
+    def from_bytes(b):
+        """raises FormatError for a length other than 64 or 96 or a scalar that is not canonical"""
+        b = bytes(b)
+        if len(b) not in (64, 96):
+            raise FormatError()
+        for off in range(32, len(b), 32):
+            if int.from_bytes(b[off:off + 32], "little") >= _L:
+                raise FormatError()
+        return OpeningProof(b)
+
+    def to_bytes(self):
+        return self._raw
+
+    def serialized_size(self):
+        return len(self._raw)
+
+    @staticmethod
+    def _raw(proofs, proof_len=None):
+        raw = [p.to_bytes() if isinstance(p, OpeningProof) else bytes(p) for p in proofs]
+        ln = proof_len if proof_len is not None else (len(raw[0]) if raw else 96)
+        if any(len(r) != ln for r in raw):
+            raise ValueError("every proof of a call has one form: %d bytes" % ln)
+        return b"".join(raw), ln
+
+    @staticmethod
+    def _values(values, who):
+        """ints below 2^64 or 32-byte scalars, one kind per call -> (packed, value_bytes)"""
+        values = list(values)
+        ints = [isinstance(v, int) for v in values]
+        if any(ints) and not all(ints):
+            raise TypeError("%s takes ints or 32-byte scalars, not both in one call" % who)
+        if all(ints):
+            if any(v < 0 or v >> 64 for v in values):
+                raise ValueError("integer values must be below 2^64 (pass larger ones as 32-byte scalars)")
+            return b"".join(v.to_bytes(8, "little") for v in values), 8
+        packed = b"".join(bytes(v) for v in values)
+        if len(packed) != 32 * len(values):
+            raise ValueError("scalar values must be 32 bytes each")
+        return packed, 32
+
+    @staticmethod
+    def create_batch(bp_gens, transcripts, values, blindings, commitments=None, public_values=False, rng_seed32=None):
+        """len(values) proofs in ONE GPU launch (bpgpu_opening_create_batch_ts).  commitments: the 32-byte commitments the proofs are
+        about, or None: they are made here with bp_gens.commit_batch(values, blindings).  rng_seed32: 32 bytes per proof, the seed of
+        its ChaChaRng (None: the library draws them) -- never one seed for two statements or transcripts.  Returns [OpeningProof]
+        (with commitments=None: ([OpeningProof], [commitments])); raises ValueError for a scalar that is not canonical."""
+        c = getattr(bp_gens, "ctx", bp_gens)
+        values, blindings = list(values), [bytes(b) for b in blindings]
+        nb = len(values)
+        if len(blindings) != nb or any(len(b) != 32 for b in blindings):
+            raise ValueError("one 32-byte blinding per value")
+        made = commitments is None
+        if nb == 0:
+            return ([], []) if made else []
+        if made:
+            commitments, _ = bp_gens.commit_batch(values, blindings)
+        commitments = [bytes(x) for x in commitments]
+        if len(commitments) != nb or any(len(x) != 32 for x in commitments):
+            raise ValueError("one 32-byte commitment per value")
+        per_proof = _per_proof(transcripts)
+        if per_proof and len(transcripts) != nb:
+            raise ValueError("create_batch: one transcript per proof")
+        packed, vb = OpeningProof._values(values, "create_batch")
+        states = _states_of(transcripts) if per_proof else transcripts.state
+        form = 1 if public_values else 0
+        proofs, status, ts = c.opening_create_batch_ts(form, states, b"".join(commitments), packed, vb, b"".join(blindings),
+                                                       rng32=None if rng_seed32 is None else bytes(rng_seed32), want_transcripts=True)
+        if any(status):
+            raise ValueError("scalars must be canonical (proof %d)" % next(i for i, x in enumerate(status) if x))
+        if per_proof:
+            _advance_all(transcripts, ts)
+        pl = len(proofs) // nb
+        out = [OpeningProof(proofs[pl * i:pl * i + pl]) for i in range(nb)]
+        return (out, commitments) if made else out
+
+    @staticmethod
+    def _verify(bp_gens, transcripts, proofs, commitments, public_values, combined, weights64):
+        c = getattr(bp_gens, "ctx", bp_gens)
+        if not proofs:
+            return []
+        form = 0 if public_values is None else 1
+        raw, pl = OpeningProof._raw(proofs, 96 if form == 0 else 64)
+        commitments = b"".join(bytes(x) for x in commitments)
+        if len(commitments) != 32 * len(proofs):
+            raise ValueError("one 32-byte commitment per proof")
+        packed, vb = (None, 8) if public_values is None else OpeningProof._values(public_values, "verify_batch")
+        if packed is not None and len(packed) != vb * len(proofs):
+            raise ValueError("one public value per proof")
+        per_proof = _per_proof(transcripts)
+        if per_proof and len(transcripts) != len(proofs):
+            raise ValueError("verify_batch: one transcript per proof")
+        states = _states_of(transcripts) if per_proof else transcripts.state
+        if combined:
+            v, _, _, ts = c.opening_verify_rlc_ts(form, raw, pl, states, commitments, packed, vb, weights64=weights64, want_transcripts=True)
+        else:
+            v, ts = c.opening_verify_batch_ts(form, raw, pl, states, commitments, packed, vb, want_transcripts=True)
+        if per_proof:
+            _advance_all(transcripts, ts)
+        return [None if x == 0 else _BY_CODE[x]() for x in v]
+
+    @staticmethod
+    def verify_batch(bp_gens, transcripts, proofs, commitments, public_values=None):
+        """Every proof on its own (bpgpu_opening_verify_batch_ts) -> list of None / ProofError.  public_values: None for proofs with
+        a secret value (96 bytes), else the public values (ints below 2^64 or 32-byte scalars) of 64-byte proofs."""
+        return OpeningProof._verify(bp_gens, transcripts, proofs, commitments, public_values, False, None)
+
+    @staticmethod
+    def verify_batch_combined(bp_gens, transcripts, proofs, commitments, public_values=None, weights64=None):
+        """verify_batch's arguments and verdicts through ONE combined check (bpgpu_opening_verify_rlc_ts): one multiscalar
+        multiplication over two points per proof when every proof verifies, per-proof re-verification inside the call when not.
+        weights64: 64 bytes per proof, unpredictable to the provers, or None (drawn by the library)."""
+        return OpeningProof._verify(bp_gens, transcripts, proofs, commitments, public_values, True, weights64)
+
+    @staticmethod
+    def create(bp_gens, transcript, value, blinding, commitment, public_value=False, rng_seed32=None):
+        """one proof; the transcript is left advanced.  Raises ValueError for a scalar that is not canonical."""
+        return OpeningProof.create_batch(bp_gens, [transcript], [value], [blinding], commitments=[commitment], public_values=public_value,
+                                         rng_seed32=rng_seed32)[0]
+
+    def verify(self, bp_gens, transcript, commitment, public_value=None):
+        """Ok(()) -> None, Err(e) -> raises e (a ProofError).  The transcript is left advanced as the contract of bpgpu_opening_* says."""
+        e = OpeningProof.verify_batch(bp_gens, [transcript], [self], [commitment], None if public_value is None else [public_value])[0]
+        if e is not None:
+            raise e

@@ -7036,3 +7036,270 @@ extern "C" int bpgpu_pool_rangeproof_verify_rlc_mixed_ts(bpgpu_pool *pool, size_
                   transcripts_out};
     return bpgpu_internal_pool_run_on_context(pool, total, verdict, rp_mix_call_run, &a);
 }
+
+// ============================================================================
+// proofs of knowledge of commitment openings (opening.h)
+// ============================================================================
+// the argument rules every entry point of the family shares; `proof_len` is 0 for the creation
+static int opn_check_args(bpgpu_ctx *c, int form, size_t nbatch, size_t proof_len, bool create, const void *values, size_t value_bytes) {
+    if (form != BPGPU_OPENING_FULL && form != BPGPU_OPENING_BLINDING) return fail(c, BPGPU_ERR_INVALID_ARG, "form must be BPGPU_OPENING_FULL or BPGPU_OPENING_BLINDING");
+    if (!create && proof_len != (form == BPGPU_OPENING_FULL ? 96u : 64u)) return fail(c, BPGPU_ERR_INVALID_ARG, "proof_len must be 96 (form 0) or 64 (form 1)");
+    if (values && value_bytes != 8 && value_bytes != 32) return fail(c, BPGPU_ERR_INVALID_ARG, "value_bytes must be 8 (u64) or 32 (scalars)");
+    if (create && form == BPGPU_OPENING_FULL && !values) return fail(c, BPGPU_ERR_INVALID_ARG, "values missing");
+    if (!create && form == BPGPU_OPENING_FULL && values) return fail(c, BPGPU_ERR_INVALID_ARG, "form 0 has no public value: values must be NULL");
+    if (nbatch > OPN_RLC_MAX_PROOFS) return fail(c, BPGPU_ERR_INVALID_ARG, "batch too large: at most 2^23 proofs per call");
+    return BPGPU_OK;
+}
+static opn_shape opn_make_shape(int form, size_t nbatch, const void *values, size_t value_bytes, const ipp_ts &ts) {
+    opn_shape sh;
+    sh.form = (uint32_t)form;
+    sh.nproofs = (uint32_t)nbatch;
+    sh.value_words = values ? (uint32_t)(value_bytes / 4) : 0u;
+    sh.ts_in_stride = ts.stride;
+    return sh;
+}
+
+// what the front end leaves on the device (c->ipp_buf) for the multiscalar multiplication(s)
+struct opn_staged {
+    char *d_sc = nullptr, *d_pt = nullptr, *d_gen = nullptr, *d_stat = nullptr, *d_mst = nullptr, *d_out = nullptr;
+    size_t sz_b = 0, sz_o = 0;
+};
+// the staging and the k_opn_front launch (lane = proof) of nbatch proofs
+static int opn_front_dev_locked(bpgpu_ctx *c, int form, size_t nbatch, const void *d_proofs, const ipp_ts &ts, const void *d_C, const void *d_values,
+                                size_t value_bytes, void *d_ts_out, hipStream_t s, opn_staged &stg) {
+    if (!c->d_table) return fail(c, BPGPU_ERR_NO_GENS, "generators not loaded");
+    const size_t sz_terms = align_up(nbatch * 2 * 32 + 64), sz_gen = align_up(nbatch * OPN_GEN_ROW * 32 + 64), sz_st = align_up(nbatch * 4),
+                 sz_b = align_up(nbatch + 64), sz_o = align_up(nbatch * 32 + 64);
+    int rc = ipp_reserve(c, 2 * sz_terms + sz_gen + sz_st + sz_b + sz_o);
+    if (rc) return rc;
+    stg.d_sc = c->ipp_buf, stg.d_pt = stg.d_sc + sz_terms, stg.d_gen = stg.d_pt + sz_terms, stg.d_stat = stg.d_gen + sz_gen, stg.d_mst = stg.d_stat + sz_st,
+    stg.d_out = stg.d_mst + sz_b;
+    stg.sz_b = sz_b, stg.sz_o = sz_o;
+    HIPCHK(c, hipMemsetAsync(stg.d_sc, 0, 2 * sz_terms + sz_gen + sz_st, s));   // scalars, points, generator rows, status
+    rp_strobe_init init;
+    ipp_ts_init(init, ts);
+    const opn_shape sh = opn_make_shape(form, nbatch, d_values, value_bytes, ts);
+    LAUNCH(c, s, "opn_front", k_opn_front, (sh.nproofs + RP_BLOCK - 1) / RP_BLOCK, RP_BLOCK, sh, init, (const uint32_t *)d_proofs, (const uint32_t *)d_C,
+           (const uint32_t *)d_values, (const uint32_t *)ts.d_in, (uint32_t *)stg.d_sc, (uint32_t *)stg.d_pt, (uint32_t *)stg.d_gen, (uint32_t *)stg.d_stat,
+           (uint32_t *)d_ts_out);
+    return BPGPU_OK;
+}
+
+// per proof: the front end, then the shared-generator chain with 2 unique terms per row -- s_r and s_v go through the window tables of
+// B_blinding and B (a row of three generator-table scalars: G_0 takes 0), C and R decode in the chain -- then the verdicts
+static int opn_verify_dev_locked(bpgpu_ctx *c, int form, size_t nbatch, const void *d_proofs, const ipp_ts &ts, const void *d_C, const void *d_values,
+                                 size_t value_bytes, void *d_verdict, void *d_msm_out, void *d_ts_out, hipStream_t s) {
+    opn_staged stg;
+    int rc = opn_front_dev_locked(c, form, nbatch, d_proofs, ts, d_C, d_values, value_bytes, d_ts_out, s, stg);
+    if (rc) return rc;
+    rc = msm_shared_dev_locked(c, 1, 1, nbatch, 2, stg.d_gen, stg.d_sc, stg.d_pt, stg.d_out, stg.d_mst, nullptr, s, true);
+    if (rc) return rc;
+    const uint32_t nb32 = (uint32_t)nbatch;
+    LAUNCH(c, s, "opn_verdict", k_ipp_verdict, (nb32 + 63) / 64, 64, nb32, (const uint32_t *)stg.d_stat, (const uint8_t *)stg.d_mst, (const uint32_t *)stg.d_out,
+           (uint8_t *)d_verdict);
+    if (d_msm_out) HIPCHK(c, hipMemcpyAsync(d_msm_out, stg.d_out, nbatch * 32, hipMemcpyDeviceToDevice, s));
+    HIPCHK(c, hipGetLastError());
+    return BPGPU_OK;
+}
+
+// combined: R = sum_p rho_p Check_p = (sum rho_p s_r) B_blinding + (sum rho_p s_v) B + sum_p (-rho_p c_p) C_p + (-rho_p) R_p: the front end,
+// the weights, the weigh launch (U = 2, two shared rows), the reduction into the generator-table row and ONE multiscalar multiplication
+// over 2 nbatch points, then the verdicts (undecided where R is not the identity).  Nothing is staged per (proof, generator).
+static int opn_rlc_dev_locked(bpgpu_ctx *c, int form, size_t nbatch, const void *d_proofs, const ipp_ts &ts, const void *d_C, const void *d_values,
+                              size_t value_bytes, const void *d_weights64, uint8_t *d_verdict, uint8_t *d_batch, void *d_ts_out, hipStream_t s) {
+    opn_staged stg;
+    int rc = opn_front_dev_locked(c, form, nbatch, d_proofs, ts, d_C, d_values, value_bytes, d_ts_out, s, stg);
+    if (rc) return rc;
+    const size_t nterms = 2 * nbatch;
+    arena_plan ap;
+    const size_t off_csc = ap.add(nterms * 32 + 64), off_cpt = ap.add(nterms * 32 + 64), off_acc = ap.add(OPN_GEN_ROW * 80), off_row = ap.add(OPN_GEN_ROW * 32 + 64),
+                 off_rho = ap.add(nbatch * 32), off_bo = ap.add(64);
+    rc = comb_reserve(c, ap.total);
+    if (rc) return rc;
+    char *b = c->comb_buf, *d_csc = b + off_csc, *d_cpt = b + off_cpt, *d_acc = b + off_acc, *d_row = b + off_row, *d_rho = b + off_rho, *d_bo = b + off_bo;
+    if (!d_batch) d_batch = (uint8_t *)d_bo;
+    const uint32_t nb32 = (uint32_t)nbatch, nstride = (uint32_t)((nbatch + 63) / 64 * 64);
+    rc = comb_rho_locked(c, s, "opn_rlc_rho", nb32, d_weights64, OPN_RLC_WEIGHT_DOMAIN, d_rho);
+    if (rc) return rc;
+    HIPCHK(c, hipMemsetAsync(d_acc, 0, OPN_GEN_ROW * 80, s));   // (the row of G_0 stays 0)
+    LAUNCH(c, s, "opn_rlc_weigh", k_opn_rlc_weigh, 4 * nstride / 64, 64, nb32, nstride, (const uint32_t *)stg.d_stat, (const uint32_t *)d_rho,
+           (const uint32_t *)stg.d_gen, (const uint32_t *)stg.d_sc, (const uint32_t *)stg.d_pt, (uint32_t *)d_csc, (uint32_t *)d_cpt, (unsigned long long *)d_acc);
+    LAUNCH(c, s, "opn_rlc_reduce", k_rlc_comb_reduce, 1, 64, OPN_GEN_ROW, (const unsigned long long *)d_acc, (uint32_t *)d_row);
+    rc = msm_shared_dev_locked(c, 1, 1, 1, nterms, d_row, d_csc, d_cpt, stg.d_out, stg.d_mst, nullptr, s, true);
+    if (rc) return rc;
+    LAUNCH(c, s, "opn_rlc_verdict", k_rlc_comb_verdict, (nb32 + 63) / 64, 64, nb32, (const uint32_t *)stg.d_stat, (const uint32_t *)stg.d_out,
+           (const uint8_t *)stg.d_mst, d_verdict, d_batch);
+    HIPCHK(c, hipGetLastError());
+    return BPGPU_OK;
+}
+
+// host pointers, both verifiers: rlc = the combined check with its per-proof fallback
+static int opn_verify_host_call(bpgpu_ctx *c, int form, size_t nbatch, const uint8_t *proofs, size_t proof_len, const uint8_t *transcripts, size_t transcript_stride,
+                                const uint8_t *commitments, const void *values, size_t value_bytes, bool rlc, const uint8_t *weights64, uint8_t *verdict,
+                                uint8_t *msm_out, uint8_t *batch_out, uint8_t *transcripts_out) {
+    if (!c) return BPGPU_ERR_INVALID_ARG;
+    int rc = opn_check_args(c, form, nbatch, proof_len, false, values, value_bytes);
+    if (rc) return rc;
+    if ((rc = ipp_ts_host_args(c, transcripts, transcript_stride, nbatch))) return rc;
+    if (nbatch == 0) {
+        if (rlc && batch_out) memset(batch_out, 0, 33);
+        return BPGPU_OK;
+    }
+    if (!proofs || !commitments || !verdict) return BPGPU_ERR_INVALID_ARG;
+    std::lock_guard<std::mutex> lk(c->mu);
+    HIPCHK(c, hipSetDevice(c->device));
+    hipStream_t s = c->stream;
+    const size_t TS = BPGPU_TRANSCRIPT_BYTES, nstates = transcript_stride ? nbatch : 1;
+    host_call<bpgpu_ctx> io(c, s);
+    const int r_pr = io.in(nbatch * proof_len + 64), r_c = io.in(nbatch * 32 + 64), r_val = io.in(values ? nbatch * value_bytes + 64 : 0), r_ti = io.in(nstates * TS),
+              r_w = io.in(weights64 ? nbatch * 64 : 0);
+    const int r_v = io.out(nbatch), r_o = io.out(rlc ? 64 : nbatch * 32), r_t = io.out(transcripts_out ? nbatch * TS : 0);
+    rc = io.open();
+    if (rc) return rc;
+    io.put(r_pr, proofs, nbatch * proof_len);
+    io.put(r_c, commitments, nbatch * 32);
+    if (values) io.put(r_val, values, nbatch * value_bytes);
+    io.put(r_ti, transcripts, nstates * TS);
+    if (weights64) io.put(r_w, weights64, nbatch * 64);
+    ipp_ts ts;
+    ts.d_in = io.d(r_ti);
+    ts.stride = transcript_stride ? BP_TS_WORDS : 0;
+    const void *a_val = values ? io.d(r_val) : nullptr;
+    void *a_to = transcripts_out ? io.d(r_t) : nullptr;
+    rc = io.upload();
+    if (!rc) {
+        if (rlc)
+            rc = opn_rlc_dev_locked(c, form, nbatch, io.d(r_pr), ts, io.d(r_c), a_val, value_bytes, weights64 ? io.d(r_w) : nullptr, (uint8_t *)io.d(r_v),
+                                    (uint8_t *)io.d(r_o), a_to, s);
+        else rc = opn_verify_dev_locked(c, form, nbatch, io.d(r_pr), ts, io.d(r_c), a_val, value_bytes, io.d(r_v), io.d(r_o), a_to, s);
+    }
+    rc = io.finish(io.download(rc));
+    if (rc) return rc;
+    if (transcripts_out) memcpy(transcripts_out, io.h(r_t), nbatch * TS);
+    if (rlc) {
+        if (batch_out) memcpy(batch_out, io.h(r_o), 33);   // (R as computed before any fallback)
+        if ((uint8_t)io.h(r_o)[0] != 0) {
+            // R is not the identity, or a point of the combined MSM did not decode: the batch again through the per-proof path (inputs are
+            // still on the device; the transcripts it leaves are the ones already copied out)
+            rc = io.rerun_per_proof(r_v, r_o, [&] {
+                return opn_verify_dev_locked(c, form, nbatch, io.d(r_pr), ts, io.d(r_c), a_val, value_bytes, io.d(r_v), nullptr, nullptr, s);
+            });
+            if (rc) return rc;
+        }
+    } else if (msm_out) {
+        memcpy(msm_out, io.h(r_o), nbatch * 32);
+    }
+    memcpy(verdict, io.h(r_v), nbatch);
+    return BPGPU_OK;
+}
+
+extern "C" int bpgpu_opening_verify_batch_ts(bpgpu_ctx *c, int form, size_t nbatch, const uint8_t *proofs, size_t proof_len, const uint8_t *transcripts,
+                                             size_t transcript_stride, const uint8_t *commitments, const void *values, size_t value_bytes, uint8_t *verdict,
+                                             uint8_t *msm_out, uint8_t *transcripts_out) {
+    return opn_verify_host_call(c, form, nbatch, proofs, proof_len, transcripts, transcript_stride, commitments, values, value_bytes, false, nullptr, verdict, msm_out,
+                                nullptr, transcripts_out);
+}
+extern "C" int bpgpu_opening_verify_rlc_ts(bpgpu_ctx *c, int form, size_t nbatch, const uint8_t *proofs, size_t proof_len, const uint8_t *transcripts,
+                                           size_t transcript_stride, const uint8_t *commitments, const void *values, size_t value_bytes, const uint8_t *weights64,
+                                           uint8_t *verdict, uint8_t *batch_out, uint8_t *transcripts_out) {
+    return opn_verify_host_call(c, form, nbatch, proofs, proof_len, transcripts, transcript_stride, commitments, values, value_bytes, true, weights64, verdict, nullptr,
+                                batch_out, transcripts_out);
+}
+
+// device pointers, both verifiers
+static int opn_verify_dev_call(bpgpu_ctx *c, int form, size_t nbatch, const void *d_proofs, size_t proof_len, const uint8_t *shared_transcript,
+                               const void *d_transcripts, const void *d_commitments, const void *d_values, size_t value_bytes, bool rlc, const void *d_weights64,
+                               void *d_verdict, void *d_out, void *d_transcripts_out, void *stream) {
+    if (!c) return BPGPU_ERR_INVALID_ARG;
+    int rc = opn_check_args(c, form, nbatch, proof_len, false, d_values, value_bytes);
+    if (rc) return rc;
+    ipp_ts ts;
+    if ((rc = ipp_ts_dev_args(c, shared_transcript, d_transcripts, d_transcripts_out, ts))) return rc;
+    if (nbatch == 0) return BPGPU_OK;
+    if (!d_proofs || !d_commitments || !d_verdict) return BPGPU_ERR_INVALID_ARG;
+    if (((uintptr_t)d_proofs | (uintptr_t)d_commitments | (uintptr_t)d_values) & 3) return fail(c, BPGPU_ERR_INVALID_ARG, "device buffers must be 4-byte aligned");
+    std::lock_guard<std::mutex> lk(c->mu);
+    HIPCHK(c, hipSetDevice(c->device));
+    hipStream_t s = stream ? (hipStream_t)stream : c->stream;
+    if ((rc = ctx_enter(c, s))) return rc;
+    if (rlc)
+        rc = opn_rlc_dev_locked(c, form, nbatch, d_proofs, ts, d_commitments, d_values, value_bytes, d_weights64, (uint8_t *)d_verdict, (uint8_t *)d_out,
+                                d_transcripts_out, s);
+    else rc = opn_verify_dev_locked(c, form, nbatch, d_proofs, ts, d_commitments, d_values, value_bytes, d_verdict, d_out, d_transcripts_out, s);
+    const int rc2 = ctx_leave(c, s);
+    return rc ? rc : rc2;
+}
+extern "C" int bpgpu_opening_verify_batch_ts_dev(bpgpu_ctx *c, int form, size_t nbatch, const void *d_proofs, size_t proof_len, const uint8_t *shared_transcript,
+                                                 const void *d_transcripts, const void *d_commitments, const void *d_values, size_t value_bytes, void *d_verdict,
+                                                 void *d_msm_out, void *d_transcripts_out, void *stream) {
+    return opn_verify_dev_call(c, form, nbatch, d_proofs, proof_len, shared_transcript, d_transcripts, d_commitments, d_values, value_bytes, false, nullptr, d_verdict,
+                               d_msm_out, d_transcripts_out, stream);
+}
+extern "C" int bpgpu_opening_verify_rlc_ts_dev(bpgpu_ctx *c, int form, size_t nbatch, const void *d_proofs, size_t proof_len, const uint8_t *shared_transcript,
+                                               const void *d_transcripts, const void *d_commitments, const void *d_values, size_t value_bytes,
+                                               const void *d_weights64, void *d_verdict, void *d_batch_out, void *d_transcripts_out, void *stream) {
+    return opn_verify_dev_call(c, form, nbatch, d_proofs, proof_len, shared_transcript, d_transcripts, d_commitments, d_values, value_bytes, true, d_weights64,
+                               d_verdict, d_batch_out, d_transcripts_out, stream);
+}
+
+// creation: ONE launch.  v (form 0), r and the seeds come first in the staging: the secret span, cleared on every exit
+extern "C" int bpgpu_opening_create_batch_ts(bpgpu_ctx *c, int form, size_t nbatch, const uint8_t *transcripts, size_t transcript_stride, const uint8_t *rng32,
+                                             const uint8_t *commitments, const void *values, size_t value_bytes, const uint8_t *blindings, uint8_t *proofs_out,
+                                             uint8_t *status, uint8_t *transcripts_out) {
+    if (!c) return BPGPU_ERR_INVALID_ARG;
+    int rc = opn_check_args(c, form, nbatch, 0, true, values, value_bytes);
+    if (rc) return rc;
+    if ((rc = ipp_ts_host_args(c, transcripts, transcript_stride, nbatch))) return rc;
+    if (nbatch == 0) return BPGPU_OK;
+    if (!commitments || !blindings || !proofs_out || !status) return BPGPU_ERR_INVALID_ARG;
+    std::lock_guard<std::mutex> lk(c->mu);
+    HIPCHK(c, hipSetDevice(c->device));
+    if (!c->d_table) return fail(c, BPGPU_ERR_NO_GENS, "generators not loaded");
+    hipStream_t s = c->stream;
+    const size_t TS = BPGPU_TRANSCRIPT_BYTES, nstates = transcript_stride ? nbatch : 1, proof_len = form == BPGPU_OPENING_FULL ? 96 : 64;
+    host_call<bpgpu_ctx> io(c, s);
+    const int r_bl = io.in(nbatch * 32), r_seed = io.in(nbatch * 32), r_val = io.in(values ? nbatch * value_bytes : 0), r_c = io.in(nbatch * 32),
+              r_ti = io.in(nstates * TS);
+    const int r_pr = io.out(nbatch * proof_len), r_st = io.out(nbatch), r_t = io.out(transcripts_out ? nbatch * TS : 0);
+    io.secrets(io.off[form == BPGPU_OPENING_FULL ? r_c : r_val]);   // blindings, seeds and, where they are secret, the values
+    rc = io.open();
+    if (rc) return io.finish(rc);
+    io.put(r_bl, blindings, nbatch * 32);
+    if (rng32) io.put(r_seed, rng32, nbatch * 32);
+    else if ((rc = os_random(c, io.h(r_seed), nbatch * 32)) != 0) return io.finish(rc);
+    if (values) io.put(r_val, values, nbatch * value_bytes);
+    io.put(r_c, commitments, nbatch * 32);
+    io.put(r_ti, transcripts, nstates * TS);
+    if ((rc = io.upload())) return io.finish(rc);
+    do {
+        uint32_t *d_ids = nullptr;
+        if ((rc = gen_ids_for(c, 1, 1, &d_ids))) break;   // the shared path's list: [0] = B_blinding, [1] = B
+        const bool ct = c->prover_ct;
+        if (ct && (rc = build_ct_table(c))) break;
+        ipp_ts ts;
+        ts.d_in = io.d(r_ti);
+        ts.stride = transcript_stride ? BP_TS_WORDS : 0;
+        const opn_shape sh = opn_make_shape(form, nbatch, values, value_bytes, ts);
+        opn_create_in in;
+        in.values = values ? (const uint32_t *)io.d(r_val) : nullptr;
+        in.blindings = (const uint32_t *)io.d(r_bl);
+        in.seeds = (const uint8_t *)io.d(r_seed);
+        in.commitments = (const uint32_t *)io.d(r_c);
+        in.ts_in = (const uint32_t *)io.d(r_ti);
+        const uint32_t grid = (sh.nproofs + BP_BLOCK - 1) / BP_BLOCK;
+        uint32_t *d_to = transcripts_out ? (uint32_t *)io.d(r_t) : nullptr;
+        if (ct)
+            LAUNCH(c, s, "opn_create_ct", k_opn_create<true>, grid, BP_BLOCK, sh, in, c->prm_ct, (const uint32_t *)d_ids, (const fb_entry *)c->d_table_ct,
+                   (uint32_t *)io.d(r_pr), (uint8_t *)io.d(r_st), d_to);
+        else
+            LAUNCH(c, s, "opn_create", k_opn_create<false>, grid, BP_BLOCK, sh, in, c->prm, (const uint32_t *)d_ids, (const fb_entry *)c->d_table,
+                   (uint32_t *)io.d(r_pr), (uint8_t *)io.d(r_st), d_to);
+        if (hipGetLastError() != hipSuccess) rc = fail(c, BPGPU_ERR_HIP, "launch failed");
+    } while (0);
+    rc = io.finish(io.download(rc));
+    if (rc) return rc;
+    memcpy(proofs_out, io.h(r_pr), nbatch * proof_len);
+    memcpy(status, io.h(r_st), nbatch);
+    if (transcripts_out) memcpy(transcripts_out, io.h(r_t), nbatch * TS);
+    return BPGPU_OK;
+}

@@ -29,6 +29,7 @@
 #include "ts_batch.h"
 #include "pedersen.h"
 #include "pedersen_sum.h"
+#include "opening.h"
 
 #define BP_BLOCK 64   // one wavefront per workgroup: under contention a CU rarely has room for four waves of one group at once (256: -8% at 48 streams)
 #define FB_BLOCK 64
@@ -209,5 +210,11 @@ __global__ void k_psum_reduce(psum_pass ps, const ge_ext *src, ge_ext *partial);
 template <bool CT>
 __global__ void k_psum_finish(uint32_t nbatch, ped_in in, fb_params prm, const uint32_t *gen_ids, const fb_entry *table, const uint32_t *slot, const ge_ext *partial, const uint8_t *bad, uint32_t *out_words, uint8_t *status);
 __global__ void k_psum_balance(uint32_t nbatch, ped_in in, fb_params prm, const uint32_t *gen_ids, const fb_entry *table, const uint32_t *slot, const ge_ext *partial, const uint8_t *bad, uint8_t *verdict);
+
+// k_opening.hip
+template <bool CT>
+__global__ void k_opn_create(opn_shape sh, opn_create_in in, fb_params prm, const uint32_t *gen_ids, const fb_entry *table, uint32_t *proofs_out, uint8_t *status, uint32_t *ts_out);
+__global__ void k_opn_front(opn_shape sh, rp_strobe_init init, const uint32_t *proofs, const uint32_t *commitments, const uint32_t *values, const uint32_t *ts_in, uint32_t *uniq_sc, uint32_t *uniq_pt, uint32_t *gen_sc, uint32_t *status, uint32_t *ts_out);
+__global__ void k_opn_rlc_weigh(uint32_t nproofs, uint32_t nstride, const uint32_t *status, const uint32_t *rho, const uint32_t *gen_sc, const uint32_t *uniq_sc, const uint32_t *uniq_pt, uint32_t *comb_sc, uint32_t *comb_pt, unsigned long long *acc);
 
 #endif

@@ -1058,6 +1058,80 @@ int bpgpu_pedersen_sum_batch_dev(bpgpu_ctx *ctx, size_t nbatch, const uint32_t *
 int bpgpu_pedersen_balance_batch_dev(bpgpu_ctx *ctx, size_t nbatch, const uint32_t *row_offsets, const void *d_points, const void *d_signs,
                                      const void *d_values, size_t value_bytes, const void *d_blindings, void *d_verdict_out, void *stream);
 
+/* ---- proofs of knowledge of commitment openings -------------------------------------------------
+ * A validator of someone else's transactions never sees a blinding; it is handed a PROOF that the sender knows the opening of
+ * C = v B + r B_blinding (the context's bases): the excess signature of a Mimblewimble kernel, the proof that goes with a committed
+ * balance.  A sigma protocol, csrc/opening.h; nothing in the reference defines it.  A call has ONE form:
+ *   BPGPU_OPENING_FULL     : v and r are secret.        proof = R | s_v | s_r, 96 bytes.
+ *   BPGPU_OPENING_BLINDING : v is public, r is secret.  proof = R | s_r, 64 bytes.  With v = 0 a Schnorr signature under the key C on
+ *                            the base B_blinding: the excess proof.
+ * Transcript, in the style of src/transcript.rs, applied to the caller's own state at any STROBE position:
+ *     append_message(b"dom-sep", b"openingproof v1"); append_u64(b"form", form); append_point(b"C", C);
+ *     form 1 only: append_scalar(b"v", v)  -- a u64 value zero-extended to 32 bytes;
+ *     validate_and_append_point(b"R", R)   -- 32 zero bytes: VerificationError, nothing of R absorbed;
+ *     c = challenge_scalar(b"c").
+ * Prover: nonces k_v (form 0 only) and k_r; R = k_v B + k_r B_blinding; s_v = k_v + c v; s_r = k_r + c r.
+ * Verifier: s_v from the proof (form 0) or s_v = c v (form 1); s_v B + s_r B_blinding - c C - R must be the identity.
+ * Arguments (the transcript arguments, the shared_transcript / d_transcripts pair of the _dev forms, malformed states, nbatch = 0 and
+ * BPGPU_VERDICT_UNDECIDED are those of bpgpu_linear_verify_rlc_ts[_dev] above):
+ *   form         : BPGPU_OPENING_FULL or BPGPU_OPENING_BLINDING; anything else is BPGPU_ERR_INVALID_ARG.
+ *   proof_len    : 96 (form 0) or 64 (form 1); anything else is BPGPU_ERR_INVALID_ARG.
+ *   commitments  : nbatch x 32 bytes.
+ *   values       : value_bytes = 8: nbatch u64; 32: nbatch x 32-byte scalars; any other value_bytes with values given is BPGPU_ERR_INVALID_ARG.  Creation:
+ *                  required in form 0; NULL in form 1 when every value is 0.  Verification: NULL in form 0 (the value is not public);
+ *                  in form 1 the public values, NULL when every value is 0.
+ *   blindings    : creation, nbatch x 32 bytes.
+ *   rng32        : creation, ONE 32-byte seed per proof: ChaChaRng::from_seed(rng32[p]), as in bpgpu_linear_create_batch_ts.  Form 0:
+ *                  k_v = draw 0, k_r = draw 1; form 1: k_r = draw 0.  NULL: the seeds come from the OS CSPRNG.  A SEED MUST NEVER BE
+ *                  USED FOR TWO DIFFERENT STATEMENTS OR TRANSCRIPTS: two proofs with one nonce and different challenges give away r
+ *                  (and v).  Fixed seeds are for tests and for derandomised signing under a seed derived from (secret, statement,
+ *                  transcript).
+ *   status       : creation, nbatch bytes: BPGPU_MSM_OK, or BPGPU_MSM_BAD_SCALAR for a value or blinding that is not canonical -- that
+ *                  row's proof bytes are zero and its transcripts_out row is its input state; the other rows are unaffected.
+ *   msm_out      : optional nbatch x 32 bytes, compress of the row's check (32 zero bytes for a row that verifies or that stopped
+ *                  before the multiplication).
+ *   weights64, batch_out, verdict of the combined forms: as bpgpu_linear_verify_rlc_ts.
+ * Verdicts and transcripts_out of the verifiers:
+ *   a scalar of the proof that is not canonical : FORMAT_ERROR,        the input state
+ *   a public value that is not canonical        : FORMAT_ERROR,        the input state
+ *   R of 32 zero bytes                          : VERIFICATION_ERROR,  the state as of that message (separator, form, C, v absorbed)
+ *   C or R that does not decode, a failing check: VERIFICATION_ERROR,  the state after c
+ *   a proof that verifies                       : OK,                  the state after c
+ * CONTRACTS (tests/test_gpu_opening.py):
+ *   (a) a row's msm_out equals bpgpu_msm_batch on (s_v, B), (s_r, B_blinding), (l - c, C), (l - 1, R), with c taken from
+ *       bpgpu_transcript_batch running the script above;
+ *   (b) verdict and transcripts_out of an _rlc_ts call ALWAYS equal those of the _verify_batch_ts call on the same inputs; the host
+ *       form falls back to the per-proof path where the combination does not decide, the _dev form marks BPGPU_VERDICT_UNDECIDED;
+ *   (c) a proof from bpgpu_opening_create_batch_ts verifies, and the transcripts_out of the two sides are equal.
+ * Timing and secrets: creation is ONE launch, lane = proof; its walk over the window tables is variable time unless the context option
+ * "prover_constant_time" is set (the W = 4 mask-select table of bpgpu_pedersen_commit_batch; the same bytes); a rejected row walks like
+ * any other.  v (form 0), r and the seeds are staged in the secret span: staging, the device IO buffer and the working sets are cleared
+ * on every exit, as bpgpu_rangeproof_prove_batch documents.  The verifiers are variable time.  The context needs generators
+ * (bpgpu_gens_create / _load with n >= 1), else BPGPU_ERR_NO_GENS.
+ * Measured on one MI355X (profiles/opening_rate.json; host pointers, one state per proof, medians): 4 096 proofs -- creation
+ * 0.33 / 0.38 ms (form 1 / 0), _verify_batch_ts 0.81 ms, _verify_rlc_ts 0.93 ms, against 0.97 ms for bpgpu_transcript_batch + bpgpu_msm_batch
+ * on the four terms per row; 65 536 proofs -- _verify_rlc_ts 3.1 ms, _verify_batch_ts 8.3 ms, the old route 11.1 ms. */
+#define BPGPU_OPENING_FULL 0
+#define BPGPU_OPENING_BLINDING 1
+int bpgpu_opening_create_batch_ts(bpgpu_ctx *ctx, int form, size_t nbatch, const uint8_t *transcripts, size_t transcript_stride,
+                                  const uint8_t *rng32, const uint8_t *commitments, const void *values, size_t value_bytes,
+                                  const uint8_t *blindings, uint8_t *proofs_out, uint8_t *status, uint8_t *transcripts_out);
+int bpgpu_opening_verify_batch_ts(bpgpu_ctx *ctx, int form, size_t nbatch, const uint8_t *proofs, size_t proof_len,
+                                  const uint8_t *transcripts, size_t transcript_stride, const uint8_t *commitments,
+                                  const void *values, size_t value_bytes, uint8_t *verdict, uint8_t *msm_out, uint8_t *transcripts_out);
+int bpgpu_opening_verify_batch_ts_dev(bpgpu_ctx *ctx, int form, size_t nbatch, const void *d_proofs, size_t proof_len,
+                                      const uint8_t *shared_transcript, const void *d_transcripts, const void *d_commitments,
+                                      const void *d_values, size_t value_bytes, void *d_verdict, void *d_msm_out,
+                                      void *d_transcripts_out, void *stream);
+int bpgpu_opening_verify_rlc_ts(bpgpu_ctx *ctx, int form, size_t nbatch, const uint8_t *proofs, size_t proof_len,
+                                const uint8_t *transcripts, size_t transcript_stride, const uint8_t *commitments,
+                                const void *values, size_t value_bytes, const uint8_t *weights64, uint8_t *verdict, uint8_t *batch_out,
+                                uint8_t *transcripts_out);
+int bpgpu_opening_verify_rlc_ts_dev(bpgpu_ctx *ctx, int form, size_t nbatch, const void *d_proofs, size_t proof_len,
+                                    const uint8_t *shared_transcript, const void *d_transcripts, const void *d_commitments,
+                                    const void *d_values, size_t value_bytes, const void *d_weights64, void *d_verdict,
+                                    void *d_batch_out, void *d_transcripts_out, void *stream);
+
 /* ---- the multi-party aggregation protocol: parties and dealer ------------------------------------
  * range_proof_mpc of the reference (src/range_proof/party.rs, dealer.rs, messages.rs; docs/aggregation-api.md) as six
  * batched, STATELESS calls: host pointers in and out, nothing retained after return.  bpgpu_rangeproof_prove_batch above

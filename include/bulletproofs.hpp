@@ -68,6 +68,9 @@ class PedersenGens {
     bool operator==(const PedersenGens &o) const { return B == o.B && B_blinding == o.B_blinding; }
 };
 
+class Transcript;
+class OpeningProof;
+
 class BulletproofGens {
   public:
     size_t gens_capacity, party_capacity;
@@ -143,6 +146,15 @@ class BulletproofGens {
                                        const std::vector<ScalarBytes> *blindings = nullptr) const {
         return balance_rows(inputs, outputs, values.data(), 32, values.size(), blindings);
     }
+    // The excess proofs of a block of confidential transactions (defined behind OpeningProof below): row r proves knowledge of the
+    // blinding of E_r = sum(inputs[r]) - sum(outputs[r]) - fees[r] B -- an OpeningProof with the public value 0 under the key E_r -- and
+    // verify_balance_proved checks rows of them without any secret: E_r through sum_commitments (value l - fee), then ONE combined
+    // check.  (The Python twin keeps E_r on the device between the two calls; this header has no device allocator and uses the host forms.)
+    inline std::vector<OpeningProof> prove_balance(const std::vector<uint64_t> &fees, const std::vector<ScalarBytes> &excess_blindings,
+                                                   std::vector<Transcript> &transcripts, const Rows &inputs, const Rows &outputs,
+                                                   const uint8_t *rng_seed32 = nullptr) const;
+    inline std::vector<Status> verify_balance_proved(const Rows &inputs, const Rows &outputs, const std::vector<uint64_t> &fees,
+                                                     const std::vector<OpeningProof> &proofs, std::vector<Transcript> &transcripts) const;
     // BulletproofGens::increase_capacity (generators.rs:177-204): no-op unless larger; the device tables are rebuilt
     void increase_capacity(size_t new_capacity) {
         if (gens_capacity >= new_capacity) return;
@@ -904,6 +916,206 @@ class LinearProof {
     }
     std::vector<uint8_t> bytes_;
 };
+
+// A proof of knowledge of the opening of a Pedersen commitment C = v B + r B_blinding under the context's bases (no counterpart in the
+// crate; the protocol is fixed in bpgpu.h, bpgpu_opening_*).  Two forms: v and r both secret (96 bytes: R | s_v | s_r), or `public_values`
+// -- v is known to the verifier, only r is secret (64 bytes: R | s_r); with v = 0 that is a Schnorr signature under the key C, the excess
+// proof of a confidential transaction.  Transcripts are one per proof and are left advanced; the TranscriptBatch twins leave the batch so.
+class OpeningProof {
+  public:
+    // raises FormatError for a length other than 64 or 96 or a scalar that is not canonical
+    static std::optional<OpeningProof> from_bytes(const uint8_t *b, size_t n, ProofError *err = nullptr) {
+        bool ok = n == 64 || n == 96;
+        for (size_t off = 32; ok && off < n; off += 32) ok = detail::scalar_is_canonical(b + off);
+        if (!ok) {
+            if (err) *err = ProofError::FormatError;
+            return std::nullopt;
+        }
+        OpeningProof p;
+        p.bytes_.assign(b, b + n);
+        return p;
+    }
+    const std::vector<uint8_t> &to_bytes() const { return bytes_; }
+    size_t serialized_size() const { return bytes_.size(); }
+
+    // values.size() proofs in ONE GPU launch (bpgpu_opening_create_batch_ts).  rng_seed32: 32 bytes per proof, proof i's rng being
+    // ChaChaRng::from_seed(rng_seed32 + 32 i) (nullptr: the library draws the seeds) -- never one seed for two statements or transcripts.
+    // Throws std::invalid_argument for a scalar that is not canonical.
+    static std::vector<OpeningProof> create_batch(const BulletproofGens &bp_gens, std::vector<Transcript> &transcripts, const std::vector<uint64_t> &values,
+                                                  const std::vector<ScalarBytes> &blindings, const std::vector<CompressedRistretto> &commitments,
+                                                  bool public_values = false, const uint8_t *rng_seed32 = nullptr) {
+        return create_rows(bp_gens, transcripts, values.data(), 8, values.size(), blindings, commitments, public_values, rng_seed32);
+    }
+    static std::vector<OpeningProof> create_batch(const BulletproofGens &bp_gens, std::vector<Transcript> &transcripts, const std::vector<ScalarBytes> &values,
+                                                  const std::vector<ScalarBytes> &blindings, const std::vector<CompressedRistretto> &commitments,
+                                                  bool public_values = false, const uint8_t *rng_seed32 = nullptr) {
+        return create_rows(bp_gens, transcripts, values.data(), 32, values.size(), blindings, commitments, public_values, rng_seed32);
+    }
+    // ... with the commitments made here by bp_gens.commit_batch(values, blindings) -> (proofs, commitments)
+    static std::pair<std::vector<OpeningProof>, std::vector<CompressedRistretto>> create_batch(const BulletproofGens &bp_gens, std::vector<Transcript> &transcripts,
+                                                                                             const std::vector<uint64_t> &values,
+                                                                                             const std::vector<ScalarBytes> &blindings, bool public_values = false,
+                                                                                             const uint8_t *rng_seed32 = nullptr) {
+        std::vector<CompressedRistretto> coms = bp_gens.commit_batch(values, &blindings).first;
+        return {create_batch(bp_gens, transcripts, values, blindings, coms, public_values, rng_seed32), coms};
+    }
+    // every proof on its own (bpgpu_opening_verify_batch_ts).  public_values == nullptr: proofs with a secret value (96 bytes); else the
+    // public values of 64-byte proofs
+    static std::vector<Status> verify_batch(const BulletproofGens &bp_gens, std::vector<Transcript> &transcripts, const std::vector<OpeningProof> &proofs,
+                                            const std::vector<CompressedRistretto> &commitments, const std::vector<uint64_t> *public_values = nullptr) {
+        return verify_rows(bp_gens, transcripts, proofs, commitments, public_values, false, nullptr);
+    }
+    // the same verdicts through ONE combined check (bpgpu_opening_verify_rlc_ts): one multiscalar multiplication over two points per proof
+    // when every proof verifies, per-proof re-verification inside the call when not.  weights64: 64 bytes per proof, unpredictable to the
+    // provers, or nullptr (drawn by the library)
+    static std::vector<Status> verify_batch_combined(const BulletproofGens &bp_gens, std::vector<Transcript> &transcripts, const std::vector<OpeningProof> &proofs,
+                                                     const std::vector<CompressedRistretto> &commitments, const std::vector<uint64_t> *public_values = nullptr,
+                                                     const uint8_t *weights64 = nullptr) {
+        return verify_rows(bp_gens, transcripts, proofs, commitments, public_values, true, weights64);
+    }
+    // ... and on a TranscriptBatch, left advanced as the vector would be
+    static std::vector<OpeningProof> create_batch(const BulletproofGens &bp_gens, TranscriptBatch &transcripts, const std::vector<uint64_t> &values,
+                                                  const std::vector<ScalarBytes> &blindings, const std::vector<CompressedRistretto> &commitments,
+                                                  bool public_values = false, const uint8_t *rng_seed32 = nullptr) {
+        std::vector<Transcript> ts = transcripts.to_transcripts();
+        std::vector<OpeningProof> out = create_batch(bp_gens, ts, values, blindings, commitments, public_values, rng_seed32);
+        transcripts.assign(ts);
+        return out;
+    }
+    static std::vector<Status> verify_batch(const BulletproofGens &bp_gens, TranscriptBatch &transcripts, const std::vector<OpeningProof> &proofs,
+                                            const std::vector<CompressedRistretto> &commitments, const std::vector<uint64_t> *public_values = nullptr) {
+        std::vector<Transcript> ts = transcripts.to_transcripts();
+        std::vector<Status> out = verify_rows(bp_gens, ts, proofs, commitments, public_values, false, nullptr);
+        transcripts.assign(ts);
+        return out;
+    }
+    static std::vector<Status> verify_batch_combined(const BulletproofGens &bp_gens, TranscriptBatch &transcripts, const std::vector<OpeningProof> &proofs,
+                                                     const std::vector<CompressedRistretto> &commitments, const std::vector<uint64_t> *public_values = nullptr,
+                                                     const uint8_t *weights64 = nullptr) {
+        std::vector<Transcript> ts = transcripts.to_transcripts();
+        std::vector<Status> out = verify_rows(bp_gens, ts, proofs, commitments, public_values, true, weights64);
+        transcripts.assign(ts);
+        return out;
+    }
+    // one proof; the transcript is left advanced
+    static OpeningProof create(const BulletproofGens &bp_gens, Transcript &transcript, uint64_t value, const ScalarBytes &blinding,
+                               const CompressedRistretto &commitment, bool public_value = false, const uint8_t *rng_seed32 = nullptr) {
+        std::vector<Transcript> ts{transcript};
+        OpeningProof p = create_batch(bp_gens, ts, std::vector<uint64_t>{value}, {blinding}, {commitment}, public_value, rng_seed32)[0];
+        transcript = ts[0];
+        return p;
+    }
+    Status verify(const BulletproofGens &bp_gens, Transcript &transcript, const CompressedRistretto &commitment, const uint64_t *public_value = nullptr) const {
+        std::vector<Transcript> ts{transcript};
+        const std::vector<uint64_t> pv{public_value ? *public_value : 0};
+        const Status st = verify_rows(bp_gens, ts, {*this}, {commitment}, public_value ? &pv : nullptr, false, nullptr)[0];
+        transcript = ts[0];
+        return st;
+    }
+
+  private:
+    static std::vector<uint8_t> states_of(const std::vector<Transcript> &transcripts) {
+        std::vector<uint8_t> ts;
+        for (const Transcript &t : transcripts) ts.insert(ts.end(), t.state().begin(), t.state().end());
+        return ts;
+    }
+    static std::vector<OpeningProof> create_rows(const BulletproofGens &bp_gens, std::vector<Transcript> &transcripts, const void *values, size_t value_bytes,
+                                                 size_t nb, const std::vector<ScalarBytes> &blindings, const std::vector<CompressedRistretto> &commitments,
+                                                 bool public_values, const uint8_t *rng_seed32) {
+        std::vector<OpeningProof> out;
+        if (transcripts.size() != nb || blindings.size() != nb || commitments.size() != nb)
+            throw std::invalid_argument("create_batch: one transcript, one blinding and one commitment per value");
+        if (nb == 0) return out;
+        const size_t pl = public_values ? 64 : 96;
+        const std::vector<uint8_t> ts = states_of(transcripts);
+        std::vector<uint8_t> pb(nb * pl), status(nb), tso(nb * BPGPU_TRANSCRIPT_BYTES);
+        const int rc = bpgpu_opening_create_batch_ts(bp_gens.ctx(), public_values ? BPGPU_OPENING_BLINDING : BPGPU_OPENING_FULL, nb, ts.data(), BPGPU_TRANSCRIPT_BYTES,
+                                                     rng_seed32, commitments[0].data(), values, value_bytes, blindings[0].data(), pb.data(), status.data(), tso.data());
+        if (rc != BPGPU_OK) throw GpuError(bpgpu_last_error(bp_gens.ctx()));
+        for (uint8_t s : status)
+            if (s != 0) throw std::invalid_argument("create_batch: scalars must be canonical");
+        for (size_t i = 0; i < nb; i++) {
+            std::memcpy(transcripts[i].state_mut().data(), &tso[i * BPGPU_TRANSCRIPT_BYTES], BPGPU_TRANSCRIPT_BYTES);
+            OpeningProof p;
+            p.bytes_.assign(pb.begin() + i * pl, pb.begin() + (i + 1) * pl);
+            out.push_back(std::move(p));
+        }
+        return out;
+    }
+    static std::vector<Status> verify_rows(const BulletproofGens &bp_gens, std::vector<Transcript> &transcripts, const std::vector<OpeningProof> &proofs,
+                                           const std::vector<CompressedRistretto> &commitments, const std::vector<uint64_t> *public_values, bool combined,
+                                           const uint8_t *weights64) {
+        const size_t nb = proofs.size(), pl = public_values ? 64 : 96;
+        std::vector<Status> out;
+        if (transcripts.size() != nb || commitments.size() != nb || (public_values && public_values->size() != nb))
+            throw std::invalid_argument("one transcript, one commitment and one public value per proof");
+        if (nb == 0) return out;
+        const std::vector<uint8_t> ts = states_of(transcripts);
+        std::vector<uint8_t> pb, verdict(nb), tso(nb * BPGPU_TRANSCRIPT_BYTES);
+        for (const OpeningProof &p : proofs) {
+            if (p.bytes_.size() != pl) throw std::invalid_argument("every proof of a call has one form");
+            pb.insert(pb.end(), p.bytes_.begin(), p.bytes_.end());
+        }
+        const int form = public_values ? BPGPU_OPENING_BLINDING : BPGPU_OPENING_FULL;
+        const void *pv = public_values ? public_values->data() : nullptr;
+        bpgpu_ctx *ctx = bp_gens.ctx();
+        const int rc = combined ? bpgpu_opening_verify_rlc_ts(ctx, form, nb, pb.data(), pl, ts.data(), BPGPU_TRANSCRIPT_BYTES, commitments[0].data(), pv, 8, weights64,
+                                                              verdict.data(), nullptr, tso.data())
+                                : bpgpu_opening_verify_batch_ts(ctx, form, nb, pb.data(), pl, ts.data(), BPGPU_TRANSCRIPT_BYTES, commitments[0].data(), pv, 8,
+                                                                verdict.data(), nullptr, tso.data());
+        if (rc != BPGPU_OK) throw GpuError(bpgpu_last_error(ctx));
+        for (size_t i = 0; i < nb; i++) {
+            std::memcpy(transcripts[i].state_mut().data(), &tso[i * BPGPU_TRANSCRIPT_BYTES], BPGPU_TRANSCRIPT_BYTES);
+            out.push_back(verdict[i] == 0 ? Status::Ok() : Status::Err(static_cast<ProofError>(verdict[i])));
+        }
+        return out;
+    }
+    std::vector<uint8_t> bytes_;
+};
+
+namespace detail {
+// l - fee as a canonical 32-byte scalar
+inline ScalarBytes neg_fee(uint64_t fee) {
+    static const uint8_t L[32] = {0xed, 0xd3, 0xf5, 0x5c, 0x1a, 0x63, 0x12, 0x58, 0xd6, 0x9c, 0xf7, 0xa2, 0xde, 0xf9, 0xde, 0x14,
+                                  0,    0,    0,    0,    0,    0,    0,    0,    0,    0,    0,    0,    0,    0,    0,    0x10};
+    ScalarBytes out{};
+    if (fee == 0) return out;
+    int borrow = 0;
+    for (int i = 0; i < 32; i++) {
+        const int f = i < 8 ? static_cast<int>((fee >> (8 * i)) & 0xff) : 0, d = L[i] - f - borrow;
+        out[i] = static_cast<uint8_t>(d & 0xff);
+        borrow = d < 0;
+    }
+    return out;
+}
+}  // namespace detail
+
+inline std::vector<OpeningProof> BulletproofGens::prove_balance(const std::vector<uint64_t> &fees, const std::vector<ScalarBytes> &excess_blindings,
+                                                                std::vector<Transcript> &transcripts, const Rows &inputs, const Rows &outputs,
+                                                                const uint8_t *rng_seed32) const {
+    std::vector<ScalarBytes> neg;
+    for (uint64_t f : fees) neg.push_back(detail::neg_fee(f));
+    std::vector<CompressedRistretto> E;
+    for (const auto &e : sum_commitments(inputs, &outputs, neg)) {
+        if (!e) throw std::invalid_argument("prove_balance: a commitment does not decode");
+        E.push_back(*e);
+    }
+    return OpeningProof::create_batch(*this, transcripts, std::vector<uint64_t>(fees.size(), 0), excess_blindings, E, true, rng_seed32);
+}
+inline std::vector<Status> BulletproofGens::verify_balance_proved(const Rows &inputs, const Rows &outputs, const std::vector<uint64_t> &fees,
+                                                                  const std::vector<OpeningProof> &proofs, std::vector<Transcript> &transcripts) const {
+    std::vector<ScalarBytes> neg;
+    for (uint64_t f : fees) neg.push_back(detail::neg_fee(f));
+    const auto sums = sum_commitments(inputs, &outputs, neg);
+    std::vector<CompressedRistretto> E;
+    for (const auto &e : sums) E.push_back(e ? *e : CompressedRistretto{});
+    const std::vector<uint64_t> zeros(fees.size(), 0);
+    std::vector<Status> out = OpeningProof::verify_batch_combined(*this, transcripts, proofs, E, &zeros);
+    // a row whose sum did not decode has no key: never verified, whatever its proof says about the placeholder
+    for (size_t i = 0; i < out.size(); i++)
+        if (!sums[i]) out[i] = Status::Err(ProofError::VerificationError);
+    return out;
+}
 
 }  // namespace bulletproofs
 #endif

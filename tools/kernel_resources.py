@@ -44,7 +44,7 @@ def _demangle(names):
 
 
 def kernels_of(path):
-    """[{name, vgpr, agpr, sgpr, scratch, spill_vgpr, spill_sgpr, code_bytes}] for one object file"""
+    """[{name, vgpr, agpr, sgpr, scratch, spill_vgpr, spill_sgpr, lds, code_bytes}] for one object file (lds: static LDS bytes per workgroup)"""
     with tempfile.TemporaryDirectory() as tmp:
         co = _code_object(path, tmp)
         if co is None:
@@ -59,14 +59,14 @@ def kernels_of(path):
     ks, cur = [], None
     for ln in notes.splitlines():
         ln = ln.strip()
-        if ln.startswith("- .") or ln.startswith("- "):
+        if ln.startswith("- ."):   # (a list of plain values, such as .language_version, does not begin a record)
             if cur and "name" in cur:
                 ks.append(cur)
             cur = {}
             ln = ln[2:]
         if cur is None:
             continue
-        m = re.match(r"\.(agpr_count|vgpr_count|sgpr_count|private_segment_fixed_size|vgpr_spill_count|sgpr_spill_count|name):\s+(\S+)", ln)
+        m = re.match(r"\.(agpr_count|vgpr_count|sgpr_count|private_segment_fixed_size|group_segment_fixed_size|vgpr_spill_count|sgpr_spill_count|name):\s+(\S+)", ln)
         if m:
             cur[m.group(1)] = m.group(2) if m.group(1) == "name" else int(m.group(2))
     if cur and "name" in cur:
@@ -74,7 +74,7 @@ def kernels_of(path):
     ks = [k for k in ks if "vgpr_count" in k]
     dm = _demangle([k["name"] for k in ks])
     return [dict(name=dm.get(k["name"], k["name"]), vgpr=k.get("vgpr_count", 0), agpr=k.get("agpr_count", 0), sgpr=k.get("sgpr_count", 0),
-                 scratch=k.get("private_segment_fixed_size", 0), spill_vgpr=k.get("vgpr_spill_count", 0), spill_sgpr=k.get("sgpr_spill_count", 0),
+                 scratch=k.get("private_segment_fixed_size", 0), spill_vgpr=k.get("vgpr_spill_count", 0), spill_sgpr=k.get("sgpr_spill_count", 0), lds=k.get("group_segment_fixed_size", 0),
                  code_bytes=size.get(k["name"], 0)) for k in ks]
 
 
@@ -83,9 +83,10 @@ def report(paths):
     for p in paths:
         for k in kernels_of(p):
             rows.append((os.path.basename(p), k))
-    print("%-14s %-46s %5s %5s %5s %8s %6s %9s" % ("object", "kernel", "vgpr", "agpr", "sgpr", "scratch", "spills", "code"))
+    print("%-14s %-46s %5s %5s %5s %8s %6s %7s %9s" % ("object", "kernel", "vgpr", "agpr", "sgpr", "scratch", "spills", "lds", "code"))
     for obj, k in rows:
-        print("%-14s %-46s %5d %5d %5d %8d %6d %9d" % (obj, k["name"][:46], k["vgpr"], k["agpr"], k["sgpr"], k["scratch"], k["spill_vgpr"], k["code_bytes"]))
+        print("%-14s %-46s %5d %5d %5d %8d %6d %7d %9d" % (obj, k["name"][:46], k["vgpr"], k["agpr"], k["sgpr"], k["scratch"], k["spill_vgpr"], k["lds"],
+                                                             k["code_bytes"]))
     return rows
 
 
