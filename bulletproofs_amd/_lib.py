@@ -52,8 +52,10 @@ EXPORTS = [
     "bpgpu_pedersen_sum_batch", "bpgpu_pedersen_balance_batch", "bpgpu_pedersen_sum_batch_dev", "bpgpu_pedersen_balance_batch_dev",
     "bpgpu_opening_create_batch_ts", "bpgpu_opening_verify_batch_ts", "bpgpu_opening_verify_batch_ts_dev", "bpgpu_opening_verify_rlc_ts",
     "bpgpu_opening_verify_rlc_ts_dev",
+    "bpgpu_rangeproof_prove_batch_rw", "bpgpu_rangeproof_prove_batch_rw_dev", "bpgpu_rangeproof_rewind_batch", "bpgpu_rangeproof_rewind_batch_dev",
 ]
 
+REWIND_OK, REWIND_NOT_FOUND, REWIND_FORMAT = 0, 1, 2   # bpgpu_rangeproof_rewind_batch: the status byte of a row
 OPENING_FULL, OPENING_BLINDING = 0, 1   # bpgpu_opening_*: v and r secret (96-byte proofs) / v public, r secret (64-byte proofs)
 
 TRANSCRIPT_BYTES = 208
@@ -178,6 +180,10 @@ def lib():
     L.bpgpu_opening_verify_batch_ts_dev.argtypes = [vp, i, sz, vp, sz, u8p, vp, vp, vp, sz, vp, vp, vp, vp]
     L.bpgpu_opening_verify_rlc_ts.argtypes = [vp, i, sz, u8p, sz, u8p, sz, u8p, u8p, sz, u8p, u8p, u8p, u8p]
     L.bpgpu_opening_verify_rlc_ts_dev.argtypes = [vp, i, sz, vp, sz, u8p, vp, vp, vp, sz, vp, vp, vp, vp, vp]
+    L.bpgpu_rangeproof_prove_batch_rw.argtypes = [vp, sz, sz, sz, C.POINTER(C.c_uint64), u8p, u8p, sz, u8p, u8p, u8p, u8p, u8p]
+    L.bpgpu_rangeproof_prove_batch_rw_dev.argtypes = [vp, sz, sz, sz, vp, vp, vp, sz, vp, vp, vp, vp, vp, vp]
+    L.bpgpu_rangeproof_rewind_batch.argtypes = [vp, sz, sz, u8p, sz, u8p, u8p, sz, u8p, u8p, C.POINTER(C.c_uint64), u8p, u8p]
+    L.bpgpu_rangeproof_rewind_batch_dev.argtypes = [vp, sz, sz, vp, sz, vp, vp, sz, vp, vp, vp, vp, vp, vp]
     L.bpgpu_pool_create.argtypes = [C.POINTER(C.c_int), i, i, C.POINTER(vp)]
     L.bpgpu_pool_destroy.argtypes = [vp]
     L.bpgpu_pool_destroy.restype = None
@@ -713,6 +719,50 @@ class Context:
         """bpgpu_rangeproof_prove_batch_ts_dev: every buffer a device address (int), asynchronous on `stream`."""
         self._chk(self._L.bpgpu_rangeproof_prove_batch_ts_dev(self.h, n, m, nbatch, d_values, d_blindings, d_transcripts, transcript_stride, d_rng32, d_proofs,
                                                               d_commitments, d_transcripts_out, stream))
+
+    # ---- rewindable range proofs (bpgpu_rangeproof_prove_batch_rw / _rewind_batch) ----
+    def rangeproof_prove_batch_rw(self, n, m, values, blindings, transcripts, rng32, messages=None, want_transcripts=False):
+        """rangeproof_prove_batch_ts with a_blinding = draw 0 - (value + 2^64 message): whoever holds rng32[p] gets value, message and
+        blinding back with rangeproof_rewind_batch (bpgpu_rangeproof_prove_batch_rw).  m must be 1 and rng32 is required; messages: 16
+        bytes per proof, or None (every message 0).  Returns (proofs bytes, commitments bytes[, final states])."""
+        nb = len(values) // max(m, 1)
+        assert len(values) == nb * m and len(blindings) == 32 * nb * m
+        assert transcripts is None or len(transcripts) in (TRANSCRIPT_BYTES, TRANSCRIPT_BYTES * nb)
+        assert (rng32 is None or len(rng32) == 32 * nb) and (messages is None or len(messages) == 16 * nb)
+        stride = TRANSCRIPT_BYTES if (transcripts is not None and nb != 1 and len(transcripts) == TRANSCRIPT_BYTES * nb) else 0
+        pl = 32 * (9 + 2 * ((n * m).bit_length() - 1))
+        va = (C.c_uint64 * max(len(values), 1))(*values)
+        proofs, coms = C.create_string_buffer(pl * max(nb, 1)), C.create_string_buffer(32 * m * max(nb, 1))
+        tso = C.create_string_buffer(TRANSCRIPT_BYTES * max(nb, 1)) if want_transcripts else None
+        self._chk(self._L.bpgpu_rangeproof_prove_batch_rw(self.h, n, m, nb, va, blindings, transcripts, stride, rng32,
+                                                          None if messages is None else bytes(messages), proofs, coms, tso))
+        out = (proofs.raw[:pl * nb], coms.raw[:32 * m * nb])
+        return out + (tso.raw[:TRANSCRIPT_BYTES * nb],) if want_transcripts else out
+
+    def rangeproof_prove_batch_rw_dev(self, n, m, nbatch, d_values, d_blindings, d_transcripts, transcript_stride, d_rng32, d_messages, d_proofs,
+                                      d_commitments, d_transcripts_out=None, stream=None):
+        """bpgpu_rangeproof_prove_batch_rw_dev: every buffer a device address (int; d_messages may be None), asynchronous on `stream`."""
+        self._chk(self._L.bpgpu_rangeproof_prove_batch_rw_dev(self.h, n, m, nbatch, d_values, d_blindings, d_transcripts, transcript_stride, d_rng32, d_messages,
+                                                              d_proofs, d_commitments, d_transcripts_out, stream))
+
+    def rangeproof_rewind_batch(self, n, proofs, proof_len, commitments, transcripts, rng32):
+        """Rewind len(commitments) / 32 (proof, commitment) rows under the seeds rng32 (bpgpu_rangeproof_rewind_batch): one launch, lane =
+        row.  transcripts: one 208-byte state (before rangeproof_domain_sep) shared by every row, or one per row.  Returns (status
+        bytes, [values], messages bytes (16 per row), blindings bytes (32 per row)); a row's data is zero unless its status is
+        REWIND_OK.  This does not verify the proofs."""
+        nb = len(commitments) // 32
+        assert len(commitments) == 32 * nb and len(proofs) == nb * proof_len and len(rng32) == 32 * nb
+        st, va = C.create_string_buffer(max(nb, 1)), (C.c_uint64 * max(nb, 1))()
+        msg, bl = C.create_string_buffer(16 * max(nb, 1)), C.create_string_buffer(32 * max(nb, 1))
+        self._chk(self._L.bpgpu_rangeproof_rewind_batch(self.h, n, nb, bytes(proofs), proof_len, bytes(commitments), transcripts,
+                                                        self._ts_stride(transcripts, nb), bytes(rng32), st, va, msg, bl))
+        return st.raw[:nb], list(va)[:nb], msg.raw[:16 * nb], bl.raw[:32 * nb]
+
+    def rangeproof_rewind_batch_dev(self, n, nbatch, d_proofs, proof_len, d_commitments, d_transcripts, transcript_stride, d_rng32, d_status, d_values,
+                                    d_messages, d_blindings, stream=None):
+        """bpgpu_rangeproof_rewind_batch_dev: every buffer a device address (int), asynchronous on `stream`."""
+        self._chk(self._L.bpgpu_rangeproof_rewind_batch_dev(self.h, n, nbatch, d_proofs, proof_len, d_commitments, d_transcripts, transcript_stride, d_rng32,
+                                                            d_status, d_values, d_messages, d_blindings, stream))
 
     # ---- batches of Pedersen commitments and openings (bpgpu_pedersen_commit_batch / _open_batch) ----
     def pedersen_commit_batch(self, values, value_bytes, blindings=None, rng_seed32=None, first_draw=0, want_blindings=False):

@@ -329,7 +329,7 @@ class Transcript:
 class TranscriptBatch:
     """n transcripts built and bound on the GPU (bpgpu_transcript_batch): the rows share their labels, the messages are per row.
     Appends are recorded and sent as ONE script -- by the next challenge, by states(), or when the batch is consumed: wherever a list
-    of Transcript is accepted (RangeProof.verify_batch / verify_batch_combined / prove_batch, LinearProof.create_batch / verify_batch /
+    of Transcript is accepted (RangeProof.verify_batch / verify_batch_combined / prove_batch / rewind_batch, LinearProof.create_batch / verify_batch /
     verify_batch_combined, OpeningProof.create_batch / verify_batch / verify_batch_combined, verify_balance_proved) a TranscriptBatch is, and is left advanced where the list would be.  batch[i] is row i as a Transcript (for
     the items of RangeProof.verify_mixed_combined, say)."""
 
@@ -484,12 +484,15 @@ class RangeProof:
         return proof, coms[0]
 
     @staticmethod
-    def prove_batch(bp_gens, pc_gens, transcript, values, blindings, n, rng32=None):
+    def prove_batch(bp_gens, pc_gens, transcript, values, blindings, n, rng32=None, rewind=False, messages=None):
         """len(values) proofs in ONE GPU pass (bpgpu_rangeproof_prove_batch_ts; no counterpart in the crate): values[i] / blindings[i]
         are the m values / 32-byte blindings of proof i.  `transcript`: one bound Transcript, the start state of every proof (not
         advanced, as in verify_batch), or a list of transcripts, one per proof, each left advanced as prove_multiple_with_rng
         leaves it.  rng32: 32 bytes per proof, proof i's rng being ChaChaRng::from_seed(rng32[32 i:32 i + 32]) (None: the library
-        draws the seeds).  Returns [(RangeProof, [commitment bytes])]."""
+        draws the seeds).  Returns [(RangeProof, [commitment bytes])].
+        rewind=True: rewindable proofs (bpgpu_rangeproof_prove_batch_rw; m = 1, rng32 required): whoever holds proof i's seed gets
+        (value, blinding, message) back with rewind_batch.  messages: one 16-byte message per proof (None entries and messages=None:
+        zero).  A seed must never serve two (commitment, transcript) pairs: see rewind_seeds."""
         if not values:
             return []
         bp_gens._check_pedersen(pc_gens)
@@ -500,12 +503,71 @@ class RangeProof:
         if per_proof and len(transcript) != nb:
             raise ValueError("prove_batch: one transcript per proof")
         states = _states_of(transcript) if per_proof else transcript.state
-        proofs, coms, ts = bp_gens.ctx.rangeproof_prove_batch_ts(n, m, [x for v in values for x in v], b"".join(x for b in blindings for x in b), states,
-                                                               rng32, want_transcripts=True)
+        if rewind:
+            if m != 1 or rng32 is None:
+                raise ValueError("prove_batch(rewind=True): one value per proof, and the seeds rng32")
+            if messages is not None:
+                if len(messages) != nb or any(x is not None and len(x) != 16 for x in messages):
+                    raise ValueError("prove_batch(rewind=True): one 16-byte message (or None) per proof")
+                messages = b"".join(bytes(16) if x is None else bytes(x) for x in messages)
+            proofs, coms, ts = bp_gens.ctx.rangeproof_prove_batch_rw(n, m, [x for v in values for x in v], b"".join(x for b in blindings for x in b), states,
+                                                                   rng32, messages, want_transcripts=True)
+        else:
+            if messages is not None:
+                raise ValueError("prove_batch: messages go with rewind=True")
+            proofs, coms, ts = bp_gens.ctx.rangeproof_prove_batch_ts(n, m, [x for v in values for x in v], b"".join(x for b in blindings for x in b), states,
+                                                                   rng32, want_transcripts=True)
         if per_proof:
             _advance_all(transcript, ts)
         pl = len(proofs) // nb
         return [(RangeProof(proofs[pl * i:pl * i + pl]), [coms[32 * (m * i + j):32 * (m * i + j) + 32] for j in range(m)]) for i in range(nb)]
+
+    @staticmethod
+    def rewind_seeds(ctx, key32, commitments):
+        """One seed per commitment from a 32-byte wallet key, derived on the GPU with TranscriptBatch (the derivation fixed in
+        include/bpgpu.h): Transcript::new(b"bpgpu rewind seed v1"), append_message(b"key", key32), append_message(b"C", commitment_i),
+        challenge_bytes(b"seed", 32).  Returns the seeds concatenated, 32 bytes per commitment: the rng32 of prove_batch(rewind=True)
+        and the seeds of rewind_batch."""
+        if len(key32) != 32 or any(len(c) != 32 for c in commitments):
+            raise ValueError("rewind_seeds: a 32-byte key and 32-byte commitments")
+        if not commitments:
+            return b""
+        t = TranscriptBatch(ctx, b"bpgpu rewind seed v1", len(commitments))
+        t.append_message(b"key", bytes(key32))
+        t.append_message(b"C", [bytes(c) for c in commitments])
+        return b"".join(t.challenge_bytes(b"seed", 32))
+
+    @staticmethod
+    def rewind_batch(bp_gens, pc_gens, transcripts, proofs, commitments, n, seeds):
+        """Rewind every (proofs[i], commitments[i]) under seeds[32 i:32 i + 32] in ONE GPU launch (bpgpu_rangeproof_rewind_batch; no
+        counterpart in the crate).  `transcripts`: one bound Transcript, the start state of every row, or a list of transcripts or a
+        TranscriptBatch, one per row; none is advanced.  Returns, per row, (value, 32-byte blinding, 16-byte message) when the row is
+        the seed holder's own, else None.  Raises FormatError where a proof is one that from_bytes rejects.  This does NOT verify the
+        proofs: a recovered message is only as good as the proof's verification."""
+        if not proofs:
+            return []
+        bp_gens._check_pedersen(pc_gens)
+        raw = [p.to_bytes() if isinstance(p, RangeProof) else bytes(p) for p in proofs]
+        nb, ln = len(raw), len(raw[0])
+        if any(len(r) != ln for r in raw) or len(commitments) != nb or any(len(c) != 32 for c in commitments) or len(seeds) != 32 * nb:
+            raise ValueError("rewind_batch: proofs of one length, one 32-byte commitment and one 32-byte seed per proof")
+        if ln != 32 * (9 + 2 * (int(n).bit_length() - 1)):
+            raise FormatError()
+        if _per_proof(transcripts) and len(transcripts) != nb:
+            raise ValueError("rewind_batch: one transcript per proof")
+        states = _states_of(transcripts) if _per_proof(transcripts) else transcripts.state
+        from ._lib import REWIND_FORMAT, REWIND_OK
+        st, vals, msgs, bls = bp_gens.ctx.rangeproof_rewind_batch(n, b"".join(raw), ln, b"".join(bytes(c) for c in commitments), states, bytes(seeds))
+        if nb == 1:
+            st = bytes(st)
+        if any(x == REWIND_FORMAT for x in st):
+            raise FormatError()
+        return [(vals[i], bls[32 * i:32 * i + 32], msgs[16 * i:16 * i + 16]) if st[i] == REWIND_OK else None for i in range(nb)]
+
+    def rewind_single(self, bp_gens, pc_gens, transcript, V, n, seed32):
+        """(value, blinding, message) of the commitment V if this proof was made rewindable under seed32 on `transcript` (which is not
+        advanced), else None.  Raises FormatError as from_bytes would."""
+        return RangeProof.rewind_batch(bp_gens, pc_gens, transcript, [self], [V], n, seed32)[0]
 
     @staticmethod
     def prove_multiple(bp_gens, pc_gens, transcript, values, blindings, n):

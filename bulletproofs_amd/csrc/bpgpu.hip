@@ -3711,6 +3711,8 @@ struct rpp_source {
     const uint8_t *seeds = nullptr;     // 32 bytes per proof
     const uint32_t *ts_in = nullptr;    // the callers' states before rangeproof_domain_sep (nullptr: d_ts holds separated states)
     uint32_t ts_in_stride = 0;          // words between them: 0 (one for all) or BP_TS_WORDS
+    bool rw = false;                    // the rewindable form (m = 1): draw 0 of the seed minus (value + 2^64 message)
+    const uint32_t *messages = nullptr; // 16 bytes per proof, or nullptr (every message 0)
 };
 static int rpp_chain(bpgpu_ctx *c, hipStream_t s, const rpp_shape &sh, const uint64_t *d_values, const uint8_t *d_bl, rpp_source src, uint32_t *d_ts,
                      uint8_t *d_proofs, uint8_t *d_coms, const char *stage_seeds);
@@ -3826,7 +3828,10 @@ static int rpp_chain(bpgpu_ctx *c, hipStream_t s, const rpp_shape &sh, const uin
             break;
         }
         // (1) V_j, A, S
-        if (seeded)
+        if (src.rw)
+            LAUNCH(c, s, "rpp_commit1_rw", k_rpp_commit1_rw, n_b + (nbits + BP_BLOCK - 1) / BP_BLOCK, BP_BLOCK, n_b, nbits, sh, d_values, d_bl, src.seeds, src.messages, gsc,
+                   party, sL, sR);
+        else if (seeded)
             LAUNCH(c, s, "rpp_commit1_seed", k_rpp_commit1_seed, n_b + (nbits + BP_BLOCK - 1) / BP_BLOCK, BP_BLOCK, n_b, nbits, sh, d_values, d_bl, src.seeds, gsc, party,
                    sL, sR);
         else
@@ -3880,15 +3885,24 @@ static int rpp_ts_args(bpgpu_ctx *c, size_t n, size_t m, size_t transcript_strid
     return BPGPU_OK;
 }
 
-extern "C" int bpgpu_rangeproof_prove_batch_ts(bpgpu_ctx *c, size_t n, size_t m, size_t nbatch, const uint64_t *values, const uint8_t *blindings,
-                                               const uint8_t *transcripts, size_t transcript_stride, const uint8_t *rng32, uint8_t *proofs_out,
-                                               uint8_t *commitments_out, uint8_t *transcripts_out) {
+// the argument rule of the rewindable forms beyond the seeded ones': one party, and a seed that somebody holds
+static int rpp_rw_args(bpgpu_ctx *c, size_t m, const void *rng32) {
+    if (m != 1) return fail(c, BPGPU_ERR_INVALID_ARG, "rewindable proofs have m = 1: the parties of an aggregated proof cannot be separated");
+    if (!rng32) return fail(c, BPGPU_ERR_INVALID_ARG, "rng32 missing: a rewindable proof is rewound with its seed");
+    return BPGPU_OK;
+}
+
+// host pointers, the seeded form and (rw) the rewindable one: messages may be null
+static int rpp_ts_host_call(bpgpu_ctx *c, size_t n, size_t m, size_t nbatch, const uint64_t *values, const uint8_t *blindings, const uint8_t *transcripts,
+                            size_t transcript_stride, const uint8_t *rng32, bool rw, const uint8_t *messages, uint8_t *proofs_out, uint8_t *commitments_out,
+                            uint8_t *transcripts_out) {
     if (!c) return BPGPU_ERR_INVALID_ARG;
     if (nbatch == 0) return BPGPU_OK;
     if (!values || !blindings || !proofs_out || !commitments_out) return BPGPU_ERR_INVALID_ARG;
     if (!transcripts) return fail(c, BPGPU_ERR_INVALID_ARG, "transcripts missing");
     int rc = rpp_ts_args(c, n, m, transcript_stride);
     if (rc) return rc;
+    if (rw && (rc = rpp_rw_args(c, m, rng32))) return rc;
     const size_t TS = BPGPU_TRANSCRIPT_BYTES, nstates = transcript_stride ? nbatch : 1;
     for (size_t p = 0; p < nstates; p++)
         if (!ts_state_ok(transcripts + p * TS)) return fail(c, BPGPU_ERR_INVALID_ARG, "malformed transcript state %zu", p);
@@ -3900,18 +3914,22 @@ extern "C" int bpgpu_rangeproof_prove_batch_ts(bpgpu_ctx *c, size_t n, size_t m,
     hipStream_t s = c->stream;
     // ---- inputs through pinned staging into the persistent IO buffer: 32 bytes of randomness per proof, no draw buffer
     host_call<bpgpu_ctx> io(c, s);
-    const int r_val = io.in(nbatch * m * 8), r_bl = io.in(nbatch * m * 32), r_seed = io.in(nbatch * 32), r_ts = io.in(nstates * TS);
+    const int r_val = io.in(nbatch * m * 8), r_bl = io.in(nbatch * m * 32), r_seed = io.in(nbatch * 32), r_msg = io.in(messages ? nbatch * 16 : 0),
+              r_ts = io.in(nstates * TS);
     const int r_pr = io.out(nbatch * proof_len), r_cm = io.out(nbatch * m * 32), r_to = io.out(nbatch * TS);
-    io.secrets(io.off[r_ts]);   // values, blindings, the seeds
+    io.secrets(io.off[r_ts]);   // values, blindings, the seeds, the messages
     rc = io.open();
     if (rc) return io.finish(rc);
     io.put(r_val, values, nbatch * m * 8);
     io.put(r_bl, blindings, nbatch * m * 32);
     if (rng32) io.put(r_seed, rng32, nbatch * 32);
     else if ((rc = os_random(c, io.h(r_seed), nbatch * 32)) != 0) return io.finish(rc);
+    if (messages) io.put(r_msg, messages, nbatch * 16);
     io.put(r_ts, transcripts, nstates * TS);
     if ((rc = io.upload())) return io.finish(rc);
     rpp_source src;
+    src.rw = rw;
+    src.messages = messages ? (const uint32_t *)io.d(r_msg) : nullptr;
     src.seeds = (const uint8_t *)io.d(r_seed);
     src.ts_in = (const uint32_t *)io.d(r_ts);
     src.ts_in_stride = transcript_stride ? BP_TS_WORDS : 0;
@@ -3924,18 +3942,29 @@ extern "C" int bpgpu_rangeproof_prove_batch_ts(bpgpu_ctx *c, size_t n, size_t m,
     if (transcripts_out) memcpy(transcripts_out, io.h(r_to), nbatch * TS);
     return BPGPU_OK;
 }
+extern "C" int bpgpu_rangeproof_prove_batch_ts(bpgpu_ctx *c, size_t n, size_t m, size_t nbatch, const uint64_t *values, const uint8_t *blindings,
+                                               const uint8_t *transcripts, size_t transcript_stride, const uint8_t *rng32, uint8_t *proofs_out,
+                                               uint8_t *commitments_out, uint8_t *transcripts_out) {
+    return rpp_ts_host_call(c, n, m, nbatch, values, blindings, transcripts, transcript_stride, rng32, false, nullptr, proofs_out, commitments_out, transcripts_out);
+}
+extern "C" int bpgpu_rangeproof_prove_batch_rw(bpgpu_ctx *c, size_t n, size_t m, size_t nbatch, const uint64_t *values, const uint8_t *blindings,
+                                               const uint8_t *transcripts, size_t transcript_stride, const uint8_t *rng32, const uint8_t *messages,
+                                               uint8_t *proofs_out, uint8_t *commitments_out, uint8_t *transcripts_out) {
+    return rpp_ts_host_call(c, n, m, nbatch, values, blindings, transcripts, transcript_stride, rng32, true, messages, proofs_out, commitments_out, transcripts_out);
+}
 
-extern "C" int bpgpu_rangeproof_prove_batch_ts_dev(bpgpu_ctx *c, size_t n, size_t m, size_t nbatch, const void *d_values, const void *d_blindings,
-                                                   const void *d_transcripts, size_t transcript_stride, const void *d_rng32, void *d_proofs_out,
-                                                   void *d_commitments_out, void *d_transcripts_out, void *stream) {
+static int rpp_ts_dev_call(bpgpu_ctx *c, size_t n, size_t m, size_t nbatch, const void *d_values, const void *d_blindings, const void *d_transcripts,
+                           size_t transcript_stride, const void *d_rng32, bool rw, const void *d_messages, void *d_proofs_out, void *d_commitments_out,
+                           void *d_transcripts_out, void *stream) {
     if (!c) return BPGPU_ERR_INVALID_ARG;
     if (nbatch == 0) return BPGPU_OK;
     if (!d_values || !d_blindings || !d_proofs_out || !d_commitments_out) return BPGPU_ERR_INVALID_ARG;
     if (!d_transcripts) return fail(c, BPGPU_ERR_INVALID_ARG, "transcripts missing");
     int rc = rpp_ts_args(c, n, m, transcript_stride);
     if (rc) return rc;
+    if (rw && (rc = rpp_rw_args(c, m, d_rng32))) return rc;
     if (((uintptr_t)d_values & 7) || (((uintptr_t)d_blindings | (uintptr_t)d_transcripts | (uintptr_t)d_rng32 | (uintptr_t)d_proofs_out | (uintptr_t)d_commitments_out |
-                                       (uintptr_t)d_transcripts_out) & 3))
+                                       (uintptr_t)d_transcripts_out | (uintptr_t)d_messages) & 3))
         return fail(c, BPGPU_ERR_INVALID_ARG, "device buffers must be 4-byte aligned (values: 8-byte)");
     std::lock_guard<std::mutex> lk(c->mu);
     HIPCHK(c, hipSetDevice(c->device));
@@ -3949,6 +3978,8 @@ extern "C" int bpgpu_rangeproof_prove_batch_ts_dev(bpgpu_ctx *c, size_t n, size_
         if (!rc) rc = os_random(c, h_seeds, nbatch * 32);
     }
     rpp_source src;
+    src.rw = rw;
+    src.messages = (const uint32_t *)d_messages;
     src.seeds = (const uint8_t *)d_rng32;
     src.ts_in = (const uint32_t *)d_transcripts;
     src.ts_in_stride = transcript_stride ? BP_TS_WORDS : 0;
@@ -3967,6 +3998,18 @@ extern "C" int bpgpu_rangeproof_prove_batch_ts_dev(bpgpu_ctx *c, size_t n, size_
     }
     if (!rc && !ok) rc = fail(c, BPGPU_ERR_HIP, "clearing the prover's working set failed");
     return rc ? rc : rc2;
+}
+extern "C" int bpgpu_rangeproof_prove_batch_ts_dev(bpgpu_ctx *c, size_t n, size_t m, size_t nbatch, const void *d_values, const void *d_blindings,
+                                                   const void *d_transcripts, size_t transcript_stride, const void *d_rng32, void *d_proofs_out,
+                                                   void *d_commitments_out, void *d_transcripts_out, void *stream) {
+    return rpp_ts_dev_call(c, n, m, nbatch, d_values, d_blindings, d_transcripts, transcript_stride, d_rng32, false, nullptr, d_proofs_out, d_commitments_out,
+                           d_transcripts_out, stream);
+}
+extern "C" int bpgpu_rangeproof_prove_batch_rw_dev(bpgpu_ctx *c, size_t n, size_t m, size_t nbatch, const void *d_values, const void *d_blindings,
+                                                   const void *d_transcripts, size_t transcript_stride, const void *d_rng32, const void *d_messages,
+                                                   void *d_proofs_out, void *d_commitments_out, void *d_transcripts_out, void *stream) {
+    return rpp_ts_dev_call(c, n, m, nbatch, d_values, d_blindings, d_transcripts, transcript_stride, d_rng32, true, d_messages, d_proofs_out, d_commitments_out,
+                           d_transcripts_out, stream);
 }
 
 // ============================================================================
@@ -7302,4 +7345,112 @@ extern "C" int bpgpu_opening_create_batch_ts(bpgpu_ctx *c, int form, size_t nbat
     memcpy(status, io.h(r_st), nbatch);
     if (transcripts_out) memcpy(transcripts_out, io.h(r_t), nbatch * TS);
     return BPGPU_OK;
+}
+
+// ============================================================================
+// rewinding range proofs (rewind.h): one launch, lane = row
+// ============================================================================
+// the argument rules the two entry points share: n, and the one length a proof of (n, 1) has
+static int rwd_check_args(bpgpu_ctx *c, size_t n, size_t nbatch, size_t proof_len, rwd_shape &sh) {
+    int rc = rpp_check_nm(c, n, 1);
+    if (rc) return rc;
+    size_t k = 0;
+    while (((size_t)1 << k) < n) k++;
+    if (proof_len != 32 * (9 + 2 * k)) return fail(c, BPGPU_ERR_INVALID_ARG, "proof_len must be 32 * (9 + 2 lg n) = %zu", 32 * (9 + 2 * k));
+    if (nbatch > RWD_MAX_BATCH) return fail(c, BPGPU_ERR_INVALID_ARG, "batch too large: at most 2^26 rows per call");
+    sh.n = (uint32_t)n;
+    sh.k = (uint32_t)k;
+    sh.nproofs = (uint32_t)nbatch;
+    sh.proof_words = (uint32_t)(proof_len / 4);
+    sh.ts_in_stride = 0;
+    return BPGPU_OK;
+}
+// enqueue the launch on s; constant-time under the context option "prover_constant_time" (its own small-window table, built on first use)
+static int rwd_launch_locked(bpgpu_ctx *c, hipStream_t s, const rwd_shape &sh, const rwd_in &in, const rwd_out &out) {
+    uint32_t *d_ids = nullptr;
+    int rc = gen_ids_for(c, 1, 1, &d_ids);   // the shared path's list: [0] = B_blinding, [1] = B
+    if (rc) return rc;
+    const bool ct = c->prover_ct;
+    if (ct && (rc = build_ct_table(c))) return rc;
+    const uint32_t grid = (sh.nproofs + BP_BLOCK - 1) / BP_BLOCK;
+    if (ct) LAUNCH(c, s, "rewind_ct", k_rewind<true>, grid, BP_BLOCK, sh, in, out, c->prm_ct, (const uint32_t *)d_ids, (const fb_entry *)c->d_table_ct);
+    else LAUNCH(c, s, "rewind", k_rewind<false>, grid, BP_BLOCK, sh, in, out, c->prm, (const uint32_t *)d_ids, (const fb_entry *)c->d_table);
+    if (hipGetLastError() != hipSuccess) return fail(c, BPGPU_ERR_HIP, "launch failed");
+    return BPGPU_OK;
+}
+
+// the seeds lead the staged inputs and value, message and blinding lead the outputs: the secret spans, cleared on every exit
+extern "C" int bpgpu_rangeproof_rewind_batch(bpgpu_ctx *c, size_t n, size_t nbatch, const uint8_t *proofs, size_t proof_len, const uint8_t *commitments,
+                                             const uint8_t *transcripts, size_t transcript_stride, const uint8_t *rng32, uint8_t *status_out,
+                                             uint64_t *values_out, uint8_t *messages_out, uint8_t *blindings_out) {
+    if (!c) return BPGPU_ERR_INVALID_ARG;
+    rwd_shape sh;
+    int rc = rwd_check_args(c, n, nbatch, proof_len, sh);
+    if (rc) return rc;
+    if ((rc = ipp_ts_host_args(c, transcripts, transcript_stride, nbatch))) return rc;
+    if (nbatch == 0) return BPGPU_OK;
+    if (!proofs || !commitments || !rng32 || !status_out || !values_out || !messages_out || !blindings_out) return BPGPU_ERR_INVALID_ARG;
+    std::lock_guard<std::mutex> lk(c->mu);
+    HIPCHK(c, hipSetDevice(c->device));
+    if (!c->d_table) return fail(c, BPGPU_ERR_NO_GENS, "generators not loaded");
+    hipStream_t s = c->stream;
+    const size_t TS = BPGPU_TRANSCRIPT_BYTES, nstates = transcript_stride ? nbatch : 1;
+    host_call<bpgpu_ctx> io(c, s);
+    const int r_seed = io.in(nbatch * 32), r_pr = io.in(nbatch * proof_len), r_c = io.in(nbatch * 32), r_ti = io.in(nstates * TS);
+    const int r_v = io.out(nbatch * 8), r_m = io.out(nbatch * 16), r_g = io.out(nbatch * 32), r_st = io.out(nbatch);
+    io.secrets(io.off[r_pr]);   // the seeds
+    rc = io.open();
+    if (rc) return io.finish(rc);
+    io.put(r_seed, rng32, nbatch * 32);
+    io.put(r_pr, proofs, nbatch * proof_len);
+    io.put(r_c, commitments, nbatch * 32);
+    io.put(r_ti, transcripts, nstates * TS);
+    if (!(rc = io.upload())) {
+        sh.ts_in_stride = transcript_stride ? BP_TS_WORDS : 0;
+        const rwd_in in = {(const uint32_t *)io.d(r_pr), (const uint32_t *)io.d(r_c), (const uint8_t *)io.d(r_seed), (const uint32_t *)io.d(r_ti)};
+        const rwd_out out = {(uint8_t *)io.d(r_st), (uint32_t *)io.d(r_v), (uint32_t *)io.d(r_m), (uint32_t *)io.d(r_g)};
+        rc = rwd_launch_locked(c, s, sh, in, out);
+    }
+    rc = io.finish(io.download(rc));
+    // the staged copies of value, message and blinding are secrets too: handed over, then cleared (the output span up to the status)
+    if (!rc) {
+        memcpy(values_out, io.h(r_v), nbatch * 8);
+        memcpy(messages_out, io.h(r_m), nbatch * 16);
+        memcpy(blindings_out, io.h(r_g), nbatch * 32);
+        memcpy(status_out, io.h(r_st), nbatch);
+    }
+    if (io.hb) {
+        memset(io.h(r_v), 0, io.off[r_st] - io.off[r_v]);
+        if (io.hb == c->io.pin) c->io.last_secret_bytes = io.off[r_st];
+    }
+    return rc;
+}
+
+// device pointers: nothing is staged, nothing is read back; the caller's buffers are the caller's
+extern "C" int bpgpu_rangeproof_rewind_batch_dev(bpgpu_ctx *c, size_t n, size_t nbatch, const void *d_proofs, size_t proof_len, const void *d_commitments,
+                                                 const void *d_transcripts, size_t transcript_stride, const void *d_rng32, void *d_status_out,
+                                                 void *d_values_out, void *d_messages_out, void *d_blindings_out, void *stream) {
+    if (!c) return BPGPU_ERR_INVALID_ARG;
+    rwd_shape sh;
+    int rc = rwd_check_args(c, n, nbatch, proof_len, sh);
+    if (rc) return rc;
+    if (transcript_stride != 0 && transcript_stride != BPGPU_TRANSCRIPT_BYTES)
+        return fail(c, BPGPU_ERR_INVALID_ARG, "transcript_stride must be 0 or %d", BPGPU_TRANSCRIPT_BYTES);
+    if (nbatch == 0) return BPGPU_OK;
+    if (!d_proofs || !d_commitments || !d_rng32 || !d_status_out || !d_values_out || !d_messages_out || !d_blindings_out) return BPGPU_ERR_INVALID_ARG;
+    if (!d_transcripts) return fail(c, BPGPU_ERR_INVALID_ARG, "transcripts missing");
+    if (((uintptr_t)d_values_out & 7) ||
+        (((uintptr_t)d_proofs | (uintptr_t)d_commitments | (uintptr_t)d_transcripts | (uintptr_t)d_rng32 | (uintptr_t)d_messages_out | (uintptr_t)d_blindings_out) & 3))
+        return fail(c, BPGPU_ERR_INVALID_ARG, "device buffers must be 4-byte aligned (values: 8-byte)");
+    std::lock_guard<std::mutex> lk(c->mu);
+    HIPCHK(c, hipSetDevice(c->device));
+    if (!c->d_table) return fail(c, BPGPU_ERR_NO_GENS, "generators not loaded");
+    hipStream_t s = stream ? (hipStream_t)stream : c->stream;
+    if ((rc = ctx_enter(c, s))) return rc;
+    sh.ts_in_stride = transcript_stride ? BP_TS_WORDS : 0;
+    const rwd_in in = {(const uint32_t *)d_proofs, (const uint32_t *)d_commitments, (const uint8_t *)d_rng32, (const uint32_t *)d_transcripts};
+    const rwd_out out = {(uint8_t *)d_status_out, (uint32_t *)d_values_out, (uint32_t *)d_messages_out, (uint32_t *)d_blindings_out};
+    rc = rwd_launch_locked(c, s, sh, in, out);
+    const int rc2 = ctx_leave(c, s);
+    return rc ? rc : rc2;
 }

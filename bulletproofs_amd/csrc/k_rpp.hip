@@ -41,6 +41,21 @@ __global__ void __launch_bounds__(BP_BLOCK) k_rpp_commit1_seed(uint32_t n_b, uin
     }
 }
 
+// the rewindable form (rpp_from_seed_rw): draw 0 carries the value and the message; every other draw, and so k_rpp_tcommit_seed, is the
+// seeded form's
+__global__ void __launch_bounds__(BP_BLOCK) k_rpp_commit1_rw(uint32_t n_b, uint32_t nthreads, rpp_shape sh, const uint64_t *values, const uint8_t *blindings,
+                                                              const uint8_t *seeds, const uint32_t *messages, uint32_t *gen_scalars, uint32_t *party, uint32_t *sL,
+                                                              uint32_t *sR) {
+    const rpp_from_seed_rw src{seeds, values, messages};
+    if (blockIdx.x < n_b) {
+        const uint32_t p = blockIdx.x * BP_BLOCK + threadIdx.x;
+        if (p < sh.nproofs) rpp_blind_lane(p, sh, values, blindings, src, gen_scalars, party);
+    } else {
+        const uint32_t tid = (blockIdx.x - n_b) * BP_BLOCK + threadIdx.x;
+        if (tid < nthreads) rpp_bits_lane(tid, sh, values, src, gen_scalars, sL, sR);
+    }
+}
+
 __global__ void __launch_bounds__(BP_BLOCK) k_rpp_tcommit_seed(rpp_shape sh, const uint8_t *seeds, uint32_t *gen_scalars, uint32_t *party) {
     const uint32_t p = blockIdx.x * blockDim.x + threadIdx.x;
     if (p < sh.nproofs) rpp_tcommit_lane(p, sh, rpp_from_seed{seeds}, gen_scalars, party);

@@ -30,6 +30,7 @@
 #include "pedersen.h"
 #include "pedersen_sum.h"
 #include "opening.h"
+#include "rewind.h"
 
 #define BP_BLOCK 64   // one wavefront per workgroup: under contention a CU rarely has room for four waves of one group at once (256: -8% at 48 streams)
 #define FB_BLOCK 64
@@ -142,6 +143,7 @@ __global__ void k_rpp_chal2(rpp_shape sh, const uint32_t *msm_out, uint32_t *ts,
 __global__ void k_rpp_vectors(uint32_t nthreads, rpp_shape sh, const uint32_t *fields, const uint32_t *l0, const uint32_t *l1, const uint32_t *r0, const uint32_t *r1, uint32_t *a_vec, uint32_t *b_vec, uint32_t *Gf, uint32_t *Hf);
 __global__ void k_rpp_commit1_seed(uint32_t n_b, uint32_t nthreads, rpp_shape sh, const uint64_t *values, const uint8_t *blindings, const uint8_t *seeds, uint32_t *gen_scalars, uint32_t *party, uint32_t *sL, uint32_t *sR);
 __global__ void k_rpp_tcommit_seed(rpp_shape sh, const uint8_t *seeds, uint32_t *gen_scalars, uint32_t *party);
+__global__ void k_rpp_commit1_rw(uint32_t n_b, uint32_t nthreads, rpp_shape sh, const uint64_t *values, const uint8_t *blindings, const uint8_t *seeds, const uint32_t *messages, uint32_t *gen_scalars, uint32_t *party, uint32_t *sL, uint32_t *sR);
 __global__ void k_rpp_chal1_sep(rpp_shape sh, const uint32_t *msm_out, const uint32_t *ts_in, uint32_t ts_in_stride, uint32_t *ts, uint32_t *fields, uint8_t *proofs, uint8_t *commitments);
 __global__ void k_gather32(uint32_t count, const uint32_t *ids, const uint32_t *src, uint32_t *dst);
 // k_ippc.hip
@@ -216,5 +218,9 @@ template <bool CT>
 __global__ void k_opn_create(opn_shape sh, opn_create_in in, fb_params prm, const uint32_t *gen_ids, const fb_entry *table, uint32_t *proofs_out, uint8_t *status, uint32_t *ts_out);
 __global__ void k_opn_front(opn_shape sh, rp_strobe_init init, const uint32_t *proofs, const uint32_t *commitments, const uint32_t *values, const uint32_t *ts_in, uint32_t *uniq_sc, uint32_t *uniq_pt, uint32_t *gen_sc, uint32_t *status, uint32_t *ts_out);
 __global__ void k_opn_rlc_weigh(uint32_t nproofs, uint32_t nstride, const uint32_t *status, const uint32_t *rho, const uint32_t *gen_sc, const uint32_t *uniq_sc, const uint32_t *uniq_pt, uint32_t *comb_sc, uint32_t *comb_pt, unsigned long long *acc);
+
+// k_rewind.hip
+template <bool CT>
+__global__ void k_rewind(rwd_shape sh, rwd_in in, rwd_out out, fb_params prm, const uint32_t *gen_ids, const fb_entry *table);
 
 #endif

@@ -56,7 +56,8 @@ BP_HD void rpp_draw(sc &r, const uint8_t *seed32, uint64_t d) {
 }
 // Where a draw comes from: draw(r, sh, p, d) = the d-th random scalar of proof p, d counting in the order above -- party j's
 // a_blinding is j (2n + 2), its s_blinding the next, s_L[i] at + 2 + i, s_R[i] at + 2 + n + i; t_1_blinding_j is m (2n + 2) + 2j,
-// t_2_blinding_j the next.  Either the caller's bytes (bpgpu_rangeproof_prove_batch) or a 32-byte seed per proof (..._prove_batch_ts).
+// t_2_blinding_j the next.  Either the caller's bytes (bpgpu_rangeproof_prove_batch), a 32-byte seed per proof (..._prove_batch_ts), or
+// that seed with the value and a message taken off draw 0 (..._prove_batch_rw).
 struct rpp_from_bytes {
     const uint8_t *rng;     // [proof][rng_per_proof]
     BP_HD void draw(sc &r, const rpp_shape &sh, uint32_t p, uint32_t d) const { rpp_wide(r, rng + (uint64_t)p * sh.rng_per_proof + 64 * (uint64_t)d); }
@@ -64,6 +65,27 @@ struct rpp_from_bytes {
 struct rpp_from_seed {
     const uint8_t *seeds;   // [proof][32]
     BP_HD void draw(sc &r, const rpp_shape &, uint32_t p, uint32_t d) const { rpp_draw(r, seeds + 32 * (uint64_t)p, d); }
+};
+// The rewindable form (bpgpu_rangeproof_prove_batch_rw, m = 1): the seed's draws, with e = v + 2^64 msg taken off draw 0 (a_blinding),
+// so that whoever holds the seed gets e back out of e_blinding = a_blinding + s_blinding x (rewind.h).  d is public; the subtraction
+// is sc_sub's fixed instruction stream.
+struct rpp_from_seed_rw {
+    const uint8_t *seeds;       // [proof][32]
+    const uint64_t *values;     // [proof] (m = 1)
+    const uint32_t *messages;   // [proof][4]: the 16-byte message as a little-endian integer, or nullptr (0)
+    BP_HD void draw(sc &r, const rpp_shape &, uint32_t p, uint32_t d) const {
+        rpp_draw(r, seeds + 32 * (uint64_t)p, d);
+        if (d != 0) return;
+        sc e;
+        sc_0(e);
+        e.v[0] = (uint32_t)values[p];
+        e.v[1] = (uint32_t)(values[p] >> 32);
+        if (messages) {
+#pragma unroll
+            for (int q = 0; q < 4; q++) e.v[2 + q] = messages[4 * (uint64_t)p + q];
+        }
+        sc_sub(r, r, e);
+    }
 };
 
 // lane = (proof p, party j, bit i): the bit's terms of A (MSM row 2p) and S (row 2p + 1); s_L, s_R kept for the polynomials

@@ -967,6 +967,82 @@ int bpgpu_rangeproof_prove_batch_ts_dev(bpgpu_ctx *ctx, size_t n, size_t m, size
                                         const void *d_rng32, void *d_proofs_out, void *d_commitments_out,
                                         void *d_transcripts_out, void *stream);
 
+/* ---- rewindable range proofs: value, message and blinding back out of (proof, commitment, seed) ---------------
+ * The wallet side of a confidential ledger: a wallet that restores from its key, or follows the chain, finds its own outputs by
+ * rewinding every (proof, commitment) row under the seed it would have used, and gets value and blinding back from what the chain
+ * stores.  Nothing in the reference defines this; the protocol is fixed here.  m = 1 ONLY (any other m: BPGPU_ERR_INVALID_ARG): in an
+ * aggregated proof the blindings and values of the parties cannot be separated.  csrc/rewind.h.
+ * Write d_k for draw k of the proof's seed exactly as bpgpu_rangeproof_prove_batch_ts defines draws; for m = 1: d_0 is a_blinding,
+ * d_1 s_blinding, d_{2n+2} t_1_blinding, d_{2n+3} t_2_blinding.
+ * REWINDABLE PROVING (bpgpu_rangeproof_prove_batch_rw[_dev]): let e = v + 2^64 msg, msg the caller's optional 16-byte message read as
+ * a little-endian integer (0 where none is given), so e < 2^192.  The proof is the seeded prover's proof with
+ * a_blinding = d_0 - e (mod l); every other draw is unchanged.  a_blinding stays uniform; the proof is an ordinary proof of the
+ * reference's format and verifies under every existing verifier.
+ *   arguments : those of bpgpu_rangeproof_prove_batch_ts[_dev], plus messages: nbatch x 16 bytes, or NULL (every message 0).
+ *               rng32 is REQUIRED (NULL: BPGPU_ERR_INVALID_ARG): a proof made from a seed nobody holds cannot be rewound.
+ *   CONTRACT  : for every p the outputs equal bpgpu_rangeproof_prove_batch(nbatch = 1, shared_transcript = transcripts[p], rng = ...)
+ *               where rng is keystream blocks 0 .. 2n+3 of rng32[p] with block 0 replaced by the 32 canonical bytes of (d_0 - e) mod l,
+ *               zero-extended to 64.
+ *   "prover_constant_time" applies as before.  The messages are secrets like values, blindings and seeds: staged in the secret span
+ *   and cleared with it on every exit.
+ * REWINDING row p (bpgpu_rangeproof_rewind_batch[_dev]): inputs are the proof bytes, the commitment V, the caller's state BEFORE
+ * rangeproof_domain_sep (any STROBE position; one shared state with transcript_stride = 0, or one per row with 208) and the seed.
+ *   1. Parse: proof_len must be 32 * (9 + 2 lg n) (else BPGPU_ERR_INVALID_ARG for the call); a proof that RangeProof::from_bytes
+ *      rejects -- one of t_x, t_x_blinding, e_blinding, a, b not canonical -- gets status BPGPU_REWIND_FORMAT.
+ *   2. Replay the transcript to x: rangeproof_domain_sep(n, 1); append V; validate-and-append A and S; challenges y, z;
+ *      validate-and-append T_1 and T_2; challenge x.  A, S, T_1 or T_2 of 32 zero bytes: BPGPU_REWIND_NOT_FOUND.
+ *   3. e = d_0 + d_1 x - e_blinding (mod l).  e >= 2^192: BPGPU_REWIND_NOT_FOUND.
+ *   4. gamma = (t_x_blinding - x (d_{2n+2} + x d_{2n+3})) z^-2;  v = e mod 2^64;  msg = e >> 64.
+ *   5. compress(v B + gamma B_blinding) != V: BPGPU_REWIND_NOT_FOUND; otherwise BPGPU_REWIND_OK.
+ *   status_out : nbatch bytes;  values_out : nbatch u64;  messages_out : nbatch x 16 bytes;  blindings_out : nbatch x 32 bytes.
+ *   The three data outputs of a row are all zero unless its status is BPGPU_REWIND_OK.  rng32: nbatch x 32 bytes, required.
+ * WHAT REWINDING IS NOT:
+ *   - It does NOT verify the proof.  A changed e_blinding can change the recovered message and still pass step 5 (the message takes
+ *     no part in the commitment), so a recovered message is only as good as the proof's verification: verify first.
+ *   - Whoever holds a seed opens the output: value, message and blinding.
+ *   - A SEED MUST NEVER SERVE TWO (COMMITMENT, TRANSCRIPT) PAIRS: the existing rule for seeds (two proofs from one set of nonces give
+ *     away the secrets).  Derive it from (key, commitment), as below.
+ *   - z is public: its inversion is the variable-time one, also under "prover_constant_time".
+ *   - With value 0 and no message e = 0: bpgpu_rangeproof_prove_batch_ts's proof of the value 0 IS the rewindable proof and rewinds
+ *     under its seed.  Every other proof of the seeded prover gives BPGPU_REWIND_NOT_FOUND under its own seed (e = l - v >= 2^192).
+ * SEED DERIVATION (RangeProof.rewind_seeds of the bindings; fixed here so that C and Rust callers reproduce it): seed_i is
+ *     t = Transcript::new(b"bpgpu rewind seed v1"); t.append_message(b"key", key32); t.append_message(b"C", commitment_i);
+ *     t.challenge_bytes(b"seed", 32 bytes)
+ * -- one bpgpu_transcript_batch call for a batch of commitments.
+ * Timing and secrets: ONE launch, lane = row.  By default variable time: a row rejected by step 1, 2 or 3 computes no gamma and
+ * skips the walk over the window tables (a scan is almost all such rows).  With "prover_constant_time" = 1 every row computes gamma
+ * and walks the W = 4 mask-select table of bpgpu_pedersen_commit_batch; nothing branches on e (a row that the parse or the replay
+ * rejected -- public -- walks zeros).  The seeds and the three data outputs are secrets: the host form stages them in the secret
+ * span and clears staging, the device IO buffer and the working sets on every exit, as bpgpu_rangeproof_prove_batch documents.
+ * nbatch = 0 is BPGPU_OK; states and lengths are checked before anything is staged; at most 2^26 rows per call; a context without
+ * generators returns BPGPU_ERR_NO_GENS.  The _dev forms take device pointers (4-byte aligned, values 8-byte) and enqueue on `stream`
+ * (NULL: the context's own) with the conventions of the other _dev entry points; nothing is read back, and a state whose position
+ * bytes are out of range is started at position 0.
+ * Measured on one MI355X (profiles/rewind_rate.json; n = 64, one state per row, medians): 4 096 rows through host pointers --
+ * 0.60 ms when every row is the caller's, 0.41 ms when none is, 0.74 ms constant-time, against 1.44 ms for bpgpu_rangeproof_verify_batch_ts
+ * on the same proofs; the launch alone (_dev, buffers on the device) 0.26 / 0.09 / 0.56 ms at 4 096 rows and 0.29 / 0.11 / 0.70 ms at
+ * 65 536, where the host-pointer call (4.3 - 4.6 ms) is its staging of 944 bytes per row.  The two provers do not differ beyond their
+ * spreads (11.3 ms for 4 096 proofs either way). */
+#define BPGPU_REWIND_OK 0
+#define BPGPU_REWIND_NOT_FOUND 1
+#define BPGPU_REWIND_FORMAT 2
+int bpgpu_rangeproof_prove_batch_rw(bpgpu_ctx *ctx, size_t n, size_t m, size_t nbatch, const uint64_t *values,
+                                    const uint8_t *blindings, const uint8_t *transcripts, size_t transcript_stride,
+                                    const uint8_t *rng32, const uint8_t *messages, uint8_t *proofs_out, uint8_t *commitments_out,
+                                    uint8_t *transcripts_out);
+int bpgpu_rangeproof_prove_batch_rw_dev(bpgpu_ctx *ctx, size_t n, size_t m, size_t nbatch, const void *d_values,
+                                        const void *d_blindings, const void *d_transcripts, size_t transcript_stride,
+                                        const void *d_rng32, const void *d_messages, void *d_proofs_out, void *d_commitments_out,
+                                        void *d_transcripts_out, void *stream);
+int bpgpu_rangeproof_rewind_batch(bpgpu_ctx *ctx, size_t n, size_t nbatch, const uint8_t *proofs, size_t proof_len,
+                                  const uint8_t *commitments, const uint8_t *transcripts, size_t transcript_stride,
+                                  const uint8_t *rng32, uint8_t *status_out, uint64_t *values_out, uint8_t *messages_out,
+                                  uint8_t *blindings_out);
+int bpgpu_rangeproof_rewind_batch_dev(bpgpu_ctx *ctx, size_t n, size_t nbatch, const void *d_proofs, size_t proof_len,
+                                      const void *d_commitments, const void *d_transcripts, size_t transcript_stride,
+                                      const void *d_rng32, void *d_status_out, void *d_values_out, void *d_messages_out,
+                                      void *d_blindings_out, void *stream);
+
 /* ---- batches of Pedersen commitments and openings -----------------------------------------------
  * nbatch calls of PedersenGens::commit(value, blinding) = value B + blinding B_blinding (src/generators.rs:38-42) with the bases
  * the context holds, in ONE launch: a lane walks the window tables of the two bases that already sit in device memory (no point is

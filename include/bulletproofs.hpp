@@ -559,6 +559,110 @@ class RangeProof {
         transcripts.assign(ts);
         return out;
     }
+
+    // ---- rewindable proofs (bpgpu_rangeproof_prove_batch_rw / bpgpu_rangeproof_rewind_batch; no counterpart in the crate; m = 1) ----
+    // What a rewound row gives back: the value, its blinding and the 16-byte message the prover put in.
+    struct Rewound {
+        uint64_t value;
+        ScalarBytes blinding;
+        std::array<uint8_t, 16> message;
+    };
+    // values.size() rewindable proofs in ONE GPU pass: prove_batch with one value per proof and a_blinding = draw 0 - (value + 2^64
+    // message), so that whoever holds proof i's seed (rng32 + 32 i, REQUIRED) gets (value, blinding, message) back with rewind_batch.
+    // messages: empty (every message zero) or one per proof.  transcripts: as prove_batch.  A seed must never serve two
+    // (commitment, transcript) pairs: derive it with rewind_seeds.
+    static std::vector<std::pair<RangeProof, CompressedRistretto>> prove_batch_rewindable(const BulletproofGens &bp_gens, const PedersenGens &pc_gens,
+                                                                                          std::vector<Transcript> &transcripts, const std::vector<uint64_t> &values,
+                                                                                          const std::vector<ScalarBytes> &blindings, size_t n, const uint8_t *rng32,
+                                                                                          const std::vector<std::array<uint8_t, 16>> &messages = {}) {
+        bp_gens.check_pedersen(pc_gens);
+        const size_t nb = values.size();
+        std::vector<std::pair<RangeProof, CompressedRistretto>> out(nb);
+        if (!nb) return out;
+        if (blindings.size() != nb || (transcripts.size() != nb && transcripts.size() != 1) || (!messages.empty() && messages.size() != nb))
+            throw std::invalid_argument("prove_batch_rewindable: one row per proof");
+        if (!rng32) throw std::invalid_argument("prove_batch_rewindable: the seeds are required");
+        const bool per_proof = transcripts.size() == nb && nb != 1;
+        size_t k = 0;
+        while ((size_t(1) << k) < n) k++;
+        const size_t pl = 32 * (9 + 2 * k), TS = BPGPU_TRANSCRIPT_BYTES;
+        std::vector<uint8_t> bl(32 * nb), ts(per_proof ? nb * TS : TS), tso(nb * TS), pr(nb * pl), vc(32 * nb), msg(messages.empty() ? 0 : 16 * nb);
+        for (size_t i = 0; i < nb; i++) {
+            std::memcpy(&bl[32 * i], blindings[i].data(), 32);
+            if (!messages.empty()) std::memcpy(&msg[16 * i], messages[i].data(), 16);
+            if (per_proof || i == 0) std::memcpy(&ts[i * TS], transcripts[i].state().data(), TS);
+        }
+        const int rc = bpgpu_rangeproof_prove_batch_rw(bp_gens.ctx(), n, 1, nb, values.data(), bl.data(), ts.data(), per_proof ? TS : 0, rng32,
+                                                       messages.empty() ? nullptr : msg.data(), pr.data(), vc.data(), tso.data());
+        if (rc != BPGPU_OK) throw GpuError(bpgpu_last_error(bp_gens.ctx()));
+        for (size_t i = 0; i < nb; i++) {
+            out[i].first.bytes_.assign(pr.begin() + i * pl, pr.begin() + (i + 1) * pl);
+            std::memcpy(out[i].second.data(), &vc[32 * i], 32);
+            if (transcripts.size() == nb) std::memcpy(transcripts[i].state_mut().data(), &tso[i * TS], TS);
+        }
+        return out;
+    }
+    // Rewind every (proofs[i], commitments[i]) under seeds + 32 i in ONE GPU launch.  transcripts: ONE bound transcript, the start state
+    // of every row, or one per row; none is advanced.  A row that is the seed holder's own gives its Rewound, any other std::nullopt;
+    // a proof that from_bytes rejects (or a length that is not that of an (n, 1) proof) makes the call return FormatError.
+    // This does NOT verify the proofs: a recovered message is only as good as the proof's verification.
+    static std::variant<std::vector<std::optional<Rewound>>, ProofError> rewind_batch(const BulletproofGens &bp_gens, const PedersenGens &pc_gens,
+                                                                                      const std::vector<Transcript> &transcripts,
+                                                                                      const std::vector<std::vector<uint8_t>> &proofs,
+                                                                                      const std::vector<CompressedRistretto> &commitments, size_t n,
+                                                                                      const uint8_t *seeds) {
+        bp_gens.check_pedersen(pc_gens);
+        const size_t nb = proofs.size();
+        std::vector<std::optional<Rewound>> out(nb);
+        if (!nb) return out;
+        if (commitments.size() != nb || (transcripts.size() != nb && transcripts.size() != 1) || !seeds) throw std::invalid_argument("rewind_batch: one row per proof");
+        const bool per_proof = transcripts.size() == nb && nb != 1;
+        size_t k = 0;
+        while ((size_t(1) << k) < n) k++;
+        const size_t pl = 32 * (9 + 2 * k), TS = BPGPU_TRANSCRIPT_BYTES;
+        std::vector<uint8_t> pr(nb * pl), vc(32 * nb), ts(per_proof ? nb * TS : TS), st(nb), msg(16 * nb), bl(32 * nb);
+        std::vector<uint64_t> va(nb);
+        for (size_t i = 0; i < nb; i++) {
+            if (proofs[i].size() != pl) return ProofError::FormatError;
+            std::memcpy(&pr[i * pl], proofs[i].data(), pl);
+            std::memcpy(&vc[32 * i], commitments[i].data(), 32);
+            if (per_proof || i == 0) std::memcpy(&ts[i * TS], transcripts[i].state().data(), TS);
+        }
+        const int rc = bpgpu_rangeproof_rewind_batch(bp_gens.ctx(), n, nb, pr.data(), pl, vc.data(), ts.data(), per_proof ? TS : 0, seeds, st.data(), va.data(),
+                                                     msg.data(), bl.data());
+        if (rc != BPGPU_OK) throw GpuError(bpgpu_last_error(bp_gens.ctx()));
+        for (size_t i = 0; i < nb; i++) {
+            if (st[i] == BPGPU_REWIND_FORMAT) return ProofError::FormatError;
+            if (st[i] != BPGPU_REWIND_OK) continue;
+            Rewound r;
+            r.value = va[i];
+            std::memcpy(r.blinding.data(), &bl[32 * i], 32);
+            std::memcpy(r.message.data(), &msg[16 * i], 16);
+            out[i] = r;
+        }
+        return out;
+    }
+    // one proof: the Rewound of V if this proof was made rewindable under seed32 on `transcript` (not advanced), std::nullopt if not
+    std::variant<std::optional<Rewound>, ProofError> rewind_single(const BulletproofGens &bp_gens, const PedersenGens &pc_gens, const Transcript &transcript,
+                                                                   const CompressedRistretto &V, size_t n, const uint8_t *seed32) const {
+        auto r = rewind_batch(bp_gens, pc_gens, std::vector<Transcript>{transcript}, {bytes_}, {V}, n, seed32);
+        if (std::holds_alternative<ProofError>(r)) return std::get<ProofError>(r);
+        return std::get<0>(r)[0];
+    }
+    // One seed per commitment from a 32-byte wallet key, derived on the GPU (the derivation fixed in bpgpu.h): Transcript::new(b"bpgpu
+    // rewind seed v1"), append_message(b"key", key32), append_message(b"C", commitment_i), challenge_bytes(b"seed", 32).  Returns the
+    // seeds concatenated: the rng32 of prove_batch_rewindable and the seeds of rewind_batch.
+    static std::vector<uint8_t> rewind_seeds(bpgpu_ctx *ctx, const uint8_t *key32, const std::vector<CompressedRistretto> &commitments) {
+        std::vector<uint8_t> out;
+        if (commitments.empty()) return out;
+        TranscriptBatch t(ctx, "bpgpu rewind seed v1", commitments.size());
+        t.append_message("key", key32, 32);
+        std::vector<std::vector<uint8_t>> cs;
+        for (const auto &c : commitments) cs.emplace_back(c.begin(), c.end());
+        t.append_message("C", cs);
+        for (const auto &s : t.challenge_bytes("seed", 32)) out.insert(out.end(), s.begin(), s.end());
+        return out;
+    }
     const std::vector<uint8_t> &to_bytes() const { return bytes_; }
 
     // verify_multiple_with_rng: rng64 = the 64 bytes the rng would hand Scalar::random (mod.rs:396)
