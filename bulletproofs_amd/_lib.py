@@ -53,6 +53,7 @@ EXPORTS = [
     "bpgpu_opening_create_batch_ts", "bpgpu_opening_verify_batch_ts", "bpgpu_opening_verify_batch_ts_dev", "bpgpu_opening_verify_rlc_ts",
     "bpgpu_opening_verify_rlc_ts_dev",
     "bpgpu_rangeproof_prove_batch_rw", "bpgpu_rangeproof_prove_batch_rw_dev", "bpgpu_rangeproof_rewind_batch", "bpgpu_rangeproof_rewind_batch_dev",
+    "bpgpu_rangeproof_scan_batch", "bpgpu_rangeproof_scan_batch_dev",
 ]
 
 REWIND_OK, REWIND_NOT_FOUND, REWIND_FORMAT = 0, 1, 2   # bpgpu_rangeproof_rewind_batch: the status byte of a row
@@ -184,6 +185,8 @@ def lib():
     L.bpgpu_rangeproof_prove_batch_rw_dev.argtypes = [vp, sz, sz, sz, vp, vp, vp, sz, vp, vp, vp, vp, vp, vp]
     L.bpgpu_rangeproof_rewind_batch.argtypes = [vp, sz, sz, u8p, sz, u8p, u8p, sz, u8p, u8p, C.POINTER(C.c_uint64), u8p, u8p]
     L.bpgpu_rangeproof_rewind_batch_dev.argtypes = [vp, sz, sz, vp, sz, vp, vp, sz, vp, vp, vp, vp, vp, vp]
+    L.bpgpu_rangeproof_scan_batch.argtypes = [vp, sz, sz, u8p, sz, u8p, u8p, sz, u8p, sz, u8p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint64), u8p, u8p]
+    L.bpgpu_rangeproof_scan_batch_dev.argtypes = [vp, sz, sz, vp, sz, vp, vp, sz, vp, sz, vp, vp, vp, vp, vp, vp]
     L.bpgpu_pool_create.argtypes = [C.POINTER(C.c_int), i, i, C.POINTER(vp)]
     L.bpgpu_pool_destroy.argtypes = [vp]
     L.bpgpu_pool_destroy.restype = None
@@ -763,6 +766,26 @@ class Context:
         """bpgpu_rangeproof_rewind_batch_dev: every buffer a device address (int), asynchronous on `stream`."""
         self._chk(self._L.bpgpu_rangeproof_rewind_batch_dev(self.h, n, nbatch, d_proofs, proof_len, d_commitments, d_transcripts, transcript_stride, d_rng32,
                                                             d_status, d_values, d_messages, d_blindings, stream))
+
+    # ---- scanning under many keys (bpgpu_rangeproof_scan_batch) ----
+    def rangeproof_scan_batch(self, n, proofs, proof_len, commitments, transcripts, keys32):
+        """Scan len(commitments) / 32 (proof, commitment) rows under the len(keys32) / 32 wallet keys, replaying each row's transcript
+        once (bpgpu_rangeproof_scan_batch).  transcripts as in rangeproof_rewind_batch.  Returns (status bytes, [key indices], [values],
+        messages bytes, blindings bytes): a row's key index is 0xFFFFFFFF and its data zero unless its status is REWIND_OK.  This does
+        not verify the proofs."""
+        nb, nk = len(commitments) // 32, len(keys32) // 32
+        assert len(commitments) == 32 * nb and len(proofs) == nb * proof_len and len(keys32) == 32 * nk
+        st, va, ki = C.create_string_buffer(max(nb, 1)), (C.c_uint64 * max(nb, 1))(), (C.c_uint32 * max(nb, 1))()
+        msg, bl = C.create_string_buffer(16 * max(nb, 1)), C.create_string_buffer(32 * max(nb, 1))
+        self._chk(self._L.bpgpu_rangeproof_scan_batch(self.h, n, nb, bytes(proofs), proof_len, bytes(commitments), transcripts,
+                                                      self._ts_stride(transcripts, nb), bytes(keys32), nk, st, ki, va, msg, bl))
+        return st.raw[:nb], list(ki)[:nb], list(va)[:nb], msg.raw[:16 * nb], bl.raw[:32 * nb]
+
+    def rangeproof_scan_batch_dev(self, n, nbatch, d_proofs, proof_len, d_commitments, d_transcripts, transcript_stride, d_keys32, nkeys, d_status, d_key_index,
+                                  d_values, d_messages, d_blindings, stream=None):
+        """bpgpu_rangeproof_scan_batch_dev: every buffer a device address (int), asynchronous on `stream`."""
+        self._chk(self._L.bpgpu_rangeproof_scan_batch_dev(self.h, n, nbatch, d_proofs, proof_len, d_commitments, d_transcripts, transcript_stride, d_keys32, nkeys,
+                                                          d_status, d_key_index, d_values, d_messages, d_blindings, stream))
 
     # ---- batches of Pedersen commitments and openings (bpgpu_pedersen_commit_batch / _open_batch) ----
     def pedersen_commit_batch(self, values, value_bytes, blindings=None, rng_seed32=None, first_draw=0, want_blindings=False):

@@ -329,7 +329,7 @@ class Transcript:
 class TranscriptBatch:
     """n transcripts built and bound on the GPU (bpgpu_transcript_batch): the rows share their labels, the messages are per row.
     Appends are recorded and sent as ONE script -- by the next challenge, by states(), or when the batch is consumed: wherever a list
-    of Transcript is accepted (RangeProof.verify_batch / verify_batch_combined / prove_batch / rewind_batch, LinearProof.create_batch / verify_batch /
+    of Transcript is accepted (RangeProof.verify_batch / verify_batch_combined / prove_batch / rewind_batch / scan_batch, LinearProof.create_batch / verify_batch /
     verify_batch_combined, OpeningProof.create_batch / verify_batch / verify_batch_combined, verify_balance_proved) a TranscriptBatch is, and is left advanced where the list would be.  batch[i] is row i as a Transcript (for
     the items of RangeProof.verify_mixed_combined, say)."""
 
@@ -563,6 +563,38 @@ class RangeProof:
         if any(x == REWIND_FORMAT for x in st):
             raise FormatError()
         return [(vals[i], bls[32 * i:32 * i + 32], msgs[16 * i:16 * i + 16]) if st[i] == REWIND_OK else None for i in range(nb)]
+
+    @staticmethod
+    def scan_batch(bp_gens, pc_gens, transcripts, proofs, commitments, n, keys):
+        """Scan every (proofs[i], commitments[i]) under the wallet keys `keys` (a list of 32-byte keys, or their concatenation; at most
+        1024) with ONE transcript replay per row (bpgpu_rangeproof_scan_batch; no counterpart in the crate): the seed of (key j,
+        commitment i) is rewind_seeds' derivation, and the lowest key that passes the 2^192 test decides a row.  `transcripts` as in
+        rewind_batch (a bound Transcript, a list, or a TranscriptBatch); none is advanced.  Returns (status, key_index, values, messages,
+        blindings): per row the status byte (REWIND_OK / REWIND_NOT_FOUND), the index of the key that opens it (None unless OK), the
+        value, the 16-byte message and the 32-byte blinding (0 / zero bytes unless OK).  Raises FormatError where a proof is one that
+        from_bytes rejects.  This does NOT verify the proofs."""
+        keys32 = bytes(keys) if isinstance(keys, (bytes, bytearray)) else b"".join(bytes(k) for k in keys)
+        if not keys32 or len(keys32) % 32 or (not isinstance(keys, (bytes, bytearray)) and any(len(k) != 32 for k in keys)):
+            raise ValueError("scan_batch: 32-byte keys, at least one")
+        if not proofs:
+            return b"", [], [], [], []
+        bp_gens._check_pedersen(pc_gens)
+        raw = [p.to_bytes() if isinstance(p, RangeProof) else bytes(p) for p in proofs]
+        nb, ln = len(raw), len(raw[0])
+        if any(len(r) != ln for r in raw) or len(commitments) != nb or any(len(c) != 32 for c in commitments):
+            raise ValueError("scan_batch: proofs of one length and one 32-byte commitment per proof")
+        if ln != 32 * (9 + 2 * (int(n).bit_length() - 1)):
+            raise FormatError()
+        if _per_proof(transcripts) and len(transcripts) != nb:
+            raise ValueError("scan_batch: one transcript per proof")
+        states = _states_of(transcripts) if _per_proof(transcripts) else transcripts.state
+        from ._lib import REWIND_FORMAT, REWIND_OK
+        st, ki, vals, msgs, bls = bp_gens.ctx.rangeproof_scan_batch(n, b"".join(raw), ln, b"".join(bytes(c) for c in commitments), states, keys32)
+        st = bytes(st)
+        if any(x == REWIND_FORMAT for x in st):
+            raise FormatError()
+        return (st, [ki[i] if st[i] == REWIND_OK else None for i in range(nb)], vals, [msgs[16 * i:16 * i + 16] for i in range(nb)],
+                [bls[32 * i:32 * i + 32] for i in range(nb)])
 
     def rewind_single(self, bp_gens, pc_gens, transcript, V, n, seed32):
         """(value, blinding, message) of the commitment V if this proof was made rewindable under seed32 on `transcript` (which is not

@@ -7454,3 +7454,129 @@ extern "C" int bpgpu_rangeproof_rewind_batch_dev(bpgpu_ctx *c, size_t n, size_t 
     const int rc2 = ctx_leave(c, s);
     return rc ? rc : rc2;
 }
+
+// ============================================================================
+// scanning range proofs under many keys (scan.h): prefixes, one replay per row, candidates per (row, key), open
+// ============================================================================
+static int scn_check_args(bpgpu_ctx *c, size_t n, size_t nbatch, size_t proof_len, size_t nkeys, rwd_shape &sh) {
+    int rc = rwd_check_args(c, n, nbatch, proof_len, sh);
+    if (rc) return rc;
+    if (nkeys < 1 || nkeys > SCN_MAX_KEYS) return fail(c, BPGPU_ERR_INVALID_ARG, "nkeys must be 1 .. 1024");
+    if (nbatch * nkeys > SCN_MAX_CANDIDATES) return fail(c, BPGPU_ERR_INVALID_ARG, "scan too large: at most 2^28 (row, key) candidates per call");
+    return BPGPU_OK;
+}
+// Enqueue the four launches on s.  The working set (key prefixes, x and z, the survivors, the derived seeds: secrets) lies in the arena,
+// which the caller clears on the stream behind the last launch.
+static int scn_launch_locked(bpgpu_ctx *c, hipStream_t s, const rwd_shape &sh, const rwd_in &in, const uint32_t *d_keys, uint32_t nkeys, const rwd_out &out,
+                             uint32_t *d_key_index, size_t *ws_bytes = nullptr) {
+    uint32_t *d_ids = nullptr;
+    int rc = gen_ids_for(c, 1, 1, &d_ids);   // [0] = B_blinding, [1] = B
+    if (rc) return rc;
+    const bool ct = c->prover_ct;
+    if (ct && (rc = build_ct_table(c))) return rc;
+    const size_t nb = sh.nproofs;
+    arena_plan ap;
+    const size_t off_pre = ap.add((size_t)nkeys * BP_TS_WORDS * 4), off_base = ap.add(BP_TS_WORDS * 4), off_st = ap.add(nb * 4), off_xz = ap.add(nb * 64),
+                 off_j = ap.add(nb * 4), off_seed = ap.add(nb * 32);
+    if ((rc = arena_reserve(c, ap.total))) return rc;
+    if (ws_bytes) *ws_bytes = ap.total;
+    char *b = c->arena;
+    const scn_ws ws = {(uint32_t *)(b + off_pre), (uint32_t *)(b + off_base), (uint32_t *)(b + off_st), (uint32_t *)(b + off_xz), (uint32_t *)(b + off_j),
+                       (uint32_t *)(b + off_seed)};
+    const scn_keys keys = {d_keys, nkeys};
+    const uint32_t grid = (sh.nproofs + BP_BLOCK - 1) / BP_BLOCK;
+    LAUNCH(c, s, "scan_prefix", k_scan_prefix, (nkeys + BP_BLOCK - 1) / BP_BLOCK, BP_BLOCK, keys, ws);
+    LAUNCH(c, s, "scan_replay", k_scan_replay, grid, BP_BLOCK, sh, in, ws);
+    if (ct) {
+        LAUNCH(c, s, "scan_cand_ct", k_scan_cand<true>, dim3(grid, nkeys), BP_BLOCK, sh, in, ws);
+        LAUNCH(c, s, "scan_open_ct", k_scan_open<true>, grid, BP_BLOCK, sh, in, keys, ws, out, d_key_index, c->prm_ct, (const uint32_t *)d_ids,
+               (const fb_entry *)c->d_table_ct);
+    } else {
+        LAUNCH(c, s, "scan_cand", k_scan_cand<false>, dim3(grid, nkeys), BP_BLOCK, sh, in, ws);
+        LAUNCH(c, s, "scan_open", k_scan_open<false>, grid, BP_BLOCK, sh, in, keys, ws, out, d_key_index, c->prm, (const uint32_t *)d_ids, (const fb_entry *)c->d_table);
+    }
+    if (hipGetLastError() != hipSuccess) return fail(c, BPGPU_ERR_HIP, "launch failed");
+    return BPGPU_OK;
+}
+
+// the keys lead the staged inputs and value, message, blinding and key index lead the outputs: the secret spans, cleared on every exit
+extern "C" int bpgpu_rangeproof_scan_batch(bpgpu_ctx *c, size_t n, size_t nbatch, const uint8_t *proofs, size_t proof_len, const uint8_t *commitments,
+                                           const uint8_t *transcripts, size_t transcript_stride, const uint8_t *keys32, size_t nkeys, uint8_t *status_out,
+                                           uint32_t *key_index_out, uint64_t *values_out, uint8_t *messages_out, uint8_t *blindings_out) {
+    if (!c) return BPGPU_ERR_INVALID_ARG;
+    rwd_shape sh;
+    int rc = scn_check_args(c, n, nbatch, proof_len, nkeys, sh);
+    if (rc) return rc;
+    if ((rc = ipp_ts_host_args(c, transcripts, transcript_stride, nbatch))) return rc;
+    if (nbatch == 0) return BPGPU_OK;
+    if (!keys32) return fail(c, BPGPU_ERR_INVALID_ARG, "keys32 missing");
+    if (!proofs || !commitments || !status_out || !key_index_out || !values_out || !messages_out || !blindings_out) return BPGPU_ERR_INVALID_ARG;
+    std::lock_guard<std::mutex> lk(c->mu);
+    HIPCHK(c, hipSetDevice(c->device));
+    if (!c->d_table) return fail(c, BPGPU_ERR_NO_GENS, "generators not loaded");
+    hipStream_t s = c->stream;
+    const size_t TS = BPGPU_TRANSCRIPT_BYTES, nstates = transcript_stride ? nbatch : 1;
+    host_call<bpgpu_ctx> io(c, s);
+    const int r_key = io.in(nkeys * 32), r_pr = io.in(nbatch * proof_len), r_c = io.in(nbatch * 32), r_ti = io.in(nstates * TS);
+    const int r_v = io.out(nbatch * 8), r_m = io.out(nbatch * 16), r_g = io.out(nbatch * 32), r_k = io.out(nbatch * 4), r_st = io.out(nbatch);
+    io.secrets(io.off[r_pr]);   // the keys
+    rc = io.open();
+    if (rc) return io.finish(rc);
+    io.put(r_key, keys32, nkeys * 32);
+    io.put(r_pr, proofs, nbatch * proof_len);
+    io.put(r_c, commitments, nbatch * 32);
+    io.put(r_ti, transcripts, nstates * TS);
+    if (!(rc = io.upload())) {
+        sh.ts_in_stride = transcript_stride ? BP_TS_WORDS : 0;
+        const rwd_in in = {(const uint32_t *)io.d(r_pr), (const uint32_t *)io.d(r_c), nullptr, (const uint32_t *)io.d(r_ti)};
+        const rwd_out out = {(uint8_t *)io.d(r_st), (uint32_t *)io.d(r_v), (uint32_t *)io.d(r_m), (uint32_t *)io.d(r_g)};
+        rc = scn_launch_locked(c, s, sh, in, (const uint32_t *)io.d(r_key), (uint32_t)nkeys, out, (uint32_t *)io.d(r_k));
+    }
+    rc = io.finish(io.download(rc));
+    // the staged copies of value, message, blinding and key index are secrets too: handed over, then cleared (the output span up to the status)
+    if (!rc) {
+        memcpy(values_out, io.h(r_v), nbatch * 8);
+        memcpy(messages_out, io.h(r_m), nbatch * 16);
+        memcpy(blindings_out, io.h(r_g), nbatch * 32);
+        memcpy(key_index_out, io.h(r_k), nbatch * 4);
+        memcpy(status_out, io.h(r_st), nbatch);
+    }
+    if (io.hb) {
+        memset(io.h(r_v), 0, io.off[r_st] - io.off[r_v]);
+        if (io.hb == c->io.pin) c->io.last_secret_bytes = io.off[r_st];
+    }
+    return rc;
+}
+
+// device pointers: nothing is staged, nothing is read back; the working set is cleared on the stream behind the open
+extern "C" int bpgpu_rangeproof_scan_batch_dev(bpgpu_ctx *c, size_t n, size_t nbatch, const void *d_proofs, size_t proof_len, const void *d_commitments,
+                                               const void *d_transcripts, size_t transcript_stride, const void *d_keys32, size_t nkeys, void *d_status_out,
+                                               void *d_key_index_out, void *d_values_out, void *d_messages_out, void *d_blindings_out, void *stream) {
+    if (!c) return BPGPU_ERR_INVALID_ARG;
+    rwd_shape sh;
+    int rc = scn_check_args(c, n, nbatch, proof_len, nkeys, sh);
+    if (rc) return rc;
+    if (transcript_stride != 0 && transcript_stride != BPGPU_TRANSCRIPT_BYTES)
+        return fail(c, BPGPU_ERR_INVALID_ARG, "transcript_stride must be 0 or %d", BPGPU_TRANSCRIPT_BYTES);
+    if (nbatch == 0) return BPGPU_OK;
+    if (!d_keys32) return fail(c, BPGPU_ERR_INVALID_ARG, "keys32 missing");
+    if (!d_proofs || !d_commitments || !d_status_out || !d_key_index_out || !d_values_out || !d_messages_out || !d_blindings_out) return BPGPU_ERR_INVALID_ARG;
+    if (!d_transcripts) return fail(c, BPGPU_ERR_INVALID_ARG, "transcripts missing");
+    if (((uintptr_t)d_values_out & 7) || (((uintptr_t)d_proofs | (uintptr_t)d_commitments | (uintptr_t)d_transcripts | (uintptr_t)d_keys32 | (uintptr_t)d_key_index_out |
+                                           (uintptr_t)d_messages_out | (uintptr_t)d_blindings_out) & 3))
+        return fail(c, BPGPU_ERR_INVALID_ARG, "device buffers must be 4-byte aligned (values: 8-byte)");
+    std::lock_guard<std::mutex> lk(c->mu);
+    HIPCHK(c, hipSetDevice(c->device));
+    if (!c->d_table) return fail(c, BPGPU_ERR_NO_GENS, "generators not loaded");
+    hipStream_t s = stream ? (hipStream_t)stream : c->stream;
+    if ((rc = ctx_enter(c, s))) return rc;
+    sh.ts_in_stride = transcript_stride ? BP_TS_WORDS : 0;
+    const rwd_in in = {(const uint32_t *)d_proofs, (const uint32_t *)d_commitments, nullptr, (const uint32_t *)d_transcripts};
+    const rwd_out out = {(uint8_t *)d_status_out, (uint32_t *)d_values_out, (uint32_t *)d_messages_out, (uint32_t *)d_blindings_out};
+    size_t ws_bytes = 0;   // (what this call laid out in the arena: all that it wrote there)
+    rc = scn_launch_locked(c, s, sh, in, (const uint32_t *)d_keys32, (uint32_t)nkeys, out, (uint32_t *)d_key_index_out, &ws_bytes);
+    const bool ok = !ws_bytes || hipMemsetAsync(c->arena, 0, ws_bytes, s) == hipSuccess;
+    const int rc2 = ctx_leave(c, s);
+    if (!rc && !ok) rc = fail(c, BPGPU_ERR_HIP, "clearing the scan's working set failed");
+    return rc ? rc : rc2;
+}

@@ -31,6 +31,7 @@
 #include "pedersen_sum.h"
 #include "opening.h"
 #include "rewind.h"
+#include "scan.h"
 
 #define BP_BLOCK 64   // one wavefront per workgroup: under contention a CU rarely has room for four waves of one group at once (256: -8% at 48 streams)
 #define FB_BLOCK 64
@@ -222,5 +223,13 @@ __global__ void k_opn_rlc_weigh(uint32_t nproofs, uint32_t nstride, const uint32
 // k_rewind.hip
 template <bool CT>
 __global__ void k_rewind(rwd_shape sh, rwd_in in, rwd_out out, fb_params prm, const uint32_t *gen_ids, const fb_entry *table);
+
+// k_scan.hip
+__global__ void k_scan_prefix(scn_keys k, scn_ws ws);
+__global__ void k_scan_replay(rwd_shape sh, rwd_in in, scn_ws ws);
+template <bool CT>
+__global__ void k_scan_cand(rwd_shape sh, rwd_in in, scn_ws ws);
+template <bool CT>
+__global__ void k_scan_open(rwd_shape sh, rwd_in in, scn_keys k, scn_ws ws, rwd_out out, uint32_t *key_index, fb_params prm, const uint32_t *gen_ids, const fb_entry *table);
 
 #endif

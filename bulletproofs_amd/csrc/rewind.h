@@ -148,9 +148,10 @@ BP_HD uint32_t rwd_scalars(uint32_t p, bool live, const rwd_shape &sh, const rwd
 
 // Phase 3, live lanes only: compress(v B + gamma B_blinding) against V.  pk lies over the sponge of phase 1: every lane of the workgroup has left that
 // phase.  gen_ids: [0] = B_blinding, [1] = B.  CT: table and prm are the W = 4 set.  The scalars are read back from the output words,
-// each when its walk begins; the row's output words are rewritten under the final status (all zero unless it is RWD_OK).
+// each when its walk begins; the row's output words are rewritten under the final status (all zero unless it is RWD_OK), which is
+// returned (scan.h derives the row's key index from it).
 template <bool CT>
-BP_HD void rwd_check(uint32_t p, const rwd_in &in, const rwd_out &out, uint32_t stat, const ped_park &pk, fb_params prm, const uint32_t *gen_ids,
+BP_HD uint32_t rwd_check(uint32_t p, const rwd_in &in, const rwd_out &out, uint32_t stat, const ped_park &pk, fb_params prm, const uint32_t *gen_ids,
                      const fb_entry *table) {
     if (CT || stat == RWD_OK) {
         ge_ext acc;
@@ -187,6 +188,7 @@ BP_HD void rwd_check(uint32_t p, const rwd_in &in, const rwd_out &out, uint32_t 
         for (int q = 0; q < 8; q++) out.blindings[8 * (uint64_t)p + q] &= keep;
     }
     out.status[p] = (uint8_t)stat;
+    return stat;
 }
 
 }  // namespace bp

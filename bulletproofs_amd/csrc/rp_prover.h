@@ -48,11 +48,15 @@ BP_HD uint32_t *rpp_row(uint32_t *gen_scalars, const rpp_shape &sh, uint32_t msm
 
 // Scalar::from_bytes_mod_order_wide of keystream block d of ChaCha20 under `seed32` (64-bit block counter d, stream id 0): what
 // rand_chacha's ChaChaRng::from_seed(seed32) hands to the d-th Scalar::random.  State and block live in registers (chacha20.h).
-BP_HD void rpp_draw(sc &r, const uint8_t *seed32, uint64_t d) {
-    uint32_t key[8], w[16];
-    load_words8(key, seed32);
+BP_HD void rpp_draw_key(sc &r, const uint32_t key[8], uint64_t d) {   // (the seed as the cipher's key words: scan.h holds it in registers)
+    uint32_t w[16];
     chacha20_block(key, d, 0, 0, w);
     sc_from_wide(r, w);
+}
+BP_HD void rpp_draw(sc &r, const uint8_t *seed32, uint64_t d) {
+    uint32_t key[8];
+    load_words8(key, seed32);
+    rpp_draw_key(r, key, d);
 }
 // Where a draw comes from: draw(r, sh, p, d) = the d-th random scalar of proof p, d counting in the order above -- party j's
 // a_blinding is j (2n + 2), its s_blinding the next, s_L[i] at + 2 + i, s_R[i] at + 2 + n + i; t_1_blinding_j is m (2n + 2) + 2j,

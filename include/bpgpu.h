@@ -1003,6 +1003,9 @@ int bpgpu_rangeproof_prove_batch_ts_dev(bpgpu_ctx *ctx, size_t n, size_t m, size
  *   - A SEED MUST NEVER SERVE TWO (COMMITMENT, TRANSCRIPT) PAIRS: the existing rule for seeds (two proofs from one set of nonces give
  *     away the secrets).  Derive it from (key, commitment), as below.
  *   - z is public: its inversion is the variable-time one, also under "prover_constant_time".
+ *   - Scanning under many keys (bpgpu_rangeproof_scan_batch, below) decides a row by the LOWEST key whose candidate passes step 3, not
+ *     by the first key that opens it: a key that passes step 3 and fails step 5 makes the row BPGPU_REWIND_NOT_FOUND even if a higher
+ *     key would open it.  It verifies no more than rewinding does.
  *   - With value 0 and no message e = 0: bpgpu_rangeproof_prove_batch_ts's proof of the value 0 IS the rewindable proof and rewinds
  *     under its seed.  Every other proof of the seeded prover gives BPGPU_REWIND_NOT_FOUND under its own seed (e = l - v >= 2^192).
  * SEED DERIVATION (RangeProof.rewind_seeds of the bindings; fixed here so that C and Rust callers reproduce it): seed_i is
@@ -1042,6 +1045,58 @@ int bpgpu_rangeproof_rewind_batch_dev(bpgpu_ctx *ctx, size_t n, size_t nbatch, c
                                       const void *d_commitments, const void *d_transcripts, size_t transcript_stride,
                                       const void *d_rng32, void *d_status_out, void *d_values_out, void *d_messages_out,
                                       void *d_blindings_out, void *stream);
+
+/* ---- scanning range proofs under many wallet keys: one transcript replay per row ----------------------------------
+ * A wallet service, an exchange with sub-accounts or a wallet with rotated view keys holds nkeys keys and follows one chain.  With
+ * bpgpu_rangeproof_rewind_batch it makes nkeys passes, each deriving its seeds and replaying every row's transcript again; the replay
+ * does not depend on the key.  bpgpu_rangeproof_scan_batch[_dev] replays once per row and tests every key's candidate.  csrc/scan.h.
+ *   keys32 : nkeys x 32 bytes, shared by every row.  For row p:
+ *   1. Parse and replay to x: steps 1 and 2 of REWINDING above, unchanged (BPGPU_REWIND_FORMAT and the zero-point
+ *      BPGPU_REWIND_NOT_FOUND keep their meaning).  m = 1 only.
+ *   2. For j = 0 .. nkeys-1: seed_{p,j} = the SEED DERIVATION above of (keys32[j], commitment_p), and e_j = d_0 + d_1 x - e_blinding
+ *      with the draws of seed_{p,j}.  j* is the LOWEST j with e_j < 2^192.  None: BPGPU_REWIND_NOT_FOUND.
+ *   3. Steps 4 and 5 of REWINDING with seed_{p,j*}: the status is BPGPU_REWIND_OK iff compress(v B + gamma B_blinding) == V.
+ *   status_out : nbatch bytes;  key_index_out : nbatch x u32, j* when the status is OK, else 0xFFFFFFFF;  values_out, messages_out,
+ *   blindings_out as in rewinding: all zero unless the status is OK.
+ * CONSEQUENCES:
+ *   - If at most one key of a row passes step 2, row p equals the first BPGPU_REWIND_OK among the seed derivation +
+ *     bpgpu_rangeproof_rewind_batch run once per key, with key_index that key.  Every honest input is such a row, up to probability
+ *     about nkeys * 2^-61 (a wrong seed's e is uniform mod l ~ 2^252.6 and passes the 2^192 test with probability 2^-60.6).
+ *   - A key listed twice reports the lower index.
+ *   - A key that passes step 2 and fails step 3 makes the row BPGPU_REWIND_NOT_FOUND, EVEN IF A HIGHER KEY WOULD OPEN IT: e_blinding is
+ *     absorbed after x, so whoever writes the proof bytes can make any one key pass step 2.  Like everything under WHAT REWINDING IS
+ *     NOT: scanning does NOT verify, and a recovered message is only as good as the proof's verification.  Verify first; a row that
+ *     verifies and was made by bpgpu_rangeproof_prove_batch_rw is an honest input.
+ * Limits, checked before anything is staged: 1 <= nkeys <= 1024, nbatch <= 2^26, nbatch * nkeys <= 2^28, the proof_len,
+ * transcript_stride and state checks of rewinding (BPGPU_ERR_INVALID_ARG); nbatch = 0 is BPGPU_OK; a context without generators
+ * returns BPGPU_ERR_NO_GENS.
+ * Timing and secrets: FOUR launches -- the keys' STROBE prefixes (lane = key), the replay (lane = row), the candidate test
+ * (lane = (row, key)) and the open (lane = row).  A candidate's state stands at STROBE position 91 after the key; C and the challenge
+ * take it to 144 < 166, so a candidate costs ONE Keccak-f, two ChaCha blocks and one scalar multiply-add.  Rows whose replay failed
+ * spend nothing per key.  With "prover_constant_time" = 1 nothing branches on e or j* and no address depends on them: every
+ * (row, key) lane of a replayed row does the same work, j*'s key is picked by mask-select over a loop across all keys, and every
+ * replayed row derives one seed, computes one gamma and walks the W = 4 table (a row without a survivor walks a discarded candidate;
+ * a row that the parse or the replay rejected -- public -- walks zeros); z's inversion stays the variable-time one.  Keys, derived
+ * seeds, x-dependent candidates and the outputs (the key index included) are secrets: the host form stages keys and outputs in the
+ * secret span and clears staging, the device IO buffer and every working set on every exit; the _dev form stages nothing, reads
+ * nothing back and clears its working set on `stream` behind the last launch.  _dev: device pointers 4-byte aligned (values 8-byte),
+ * enqueued on `stream` (NULL: the context's own) with the conventions of the other _dev entry points.
+ * Measured on one MI355X (profiles/scan_rate.json; n = 64, one state per row, medians, _dev forms on device-resident buffers)
+ * against the path it replaces, nkeys x (the seed derivation through bpgpu_transcript_batch_dev + bpgpu_rangeproof_rewind_batch_dev):
+ * 4 096 rows x 16 keys 0.12 ms against 2.11 ms when no row is the caller's and 0.32 against 2.28 ms when every row belongs to the last
+ * key; 4 096 x 256: 0.39 / 0.58 against 33.7 / 34.0 ms; 65 536 x 16: 0.44 / 0.76 against 2.58 / 2.76 ms; 65 536 x 256: 4.62 / 4.87 against
+ * 41.5 / 41.6 ms (3.6 G candidates/s).  AT ONE KEY THE SCAN IS NOT FASTER: 0.32 against 0.30 ms at 4 096 rows that are all the caller's
+ * (0.93 of the passes' speed) and 1.24 - 1.26 times bpgpu_rangeproof_rewind_batch_dev with ready seeds (0.26 ms): four launches and a
+ * second derivation of the seed.  With one key, derive the seeds and rewind.  The kernel split (rocprofv3 --kernel-trace --stats,
+ * 65 536 x 16): candidates 299 us, open 4 (none mine) to 360 us (all mine), replay 124 us, prefixes 11 us. */
+int bpgpu_rangeproof_scan_batch(bpgpu_ctx *ctx, size_t n, size_t nbatch, const uint8_t *proofs, size_t proof_len,
+                                const uint8_t *commitments, const uint8_t *transcripts, size_t transcript_stride,
+                                const uint8_t *keys32, size_t nkeys, uint8_t *status_out, uint32_t *key_index_out,
+                                uint64_t *values_out, uint8_t *messages_out, uint8_t *blindings_out);
+int bpgpu_rangeproof_scan_batch_dev(bpgpu_ctx *ctx, size_t n, size_t nbatch, const void *d_proofs, size_t proof_len,
+                                    const void *d_commitments, const void *d_transcripts, size_t transcript_stride,
+                                    const void *d_keys32, size_t nkeys, void *d_status_out, void *d_key_index_out,
+                                    void *d_values_out, void *d_messages_out, void *d_blindings_out, void *stream);
 
 /* ---- batches of Pedersen commitments and openings -----------------------------------------------
  * nbatch calls of PedersenGens::commit(value, blinding) = value B + blinding B_blinding (src/generators.rs:38-42) with the bases

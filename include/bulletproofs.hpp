@@ -642,6 +642,47 @@ class RangeProof {
         }
         return out;
     }
+    // Scan every (proofs[i], commitments[i]) under nkeys wallet keys (keys32: nkeys x 32 bytes, shared by every row) with ONE transcript
+    // replay per row (bpgpu_rangeproof_scan_batch): the seed of (key j, commitment i) is rewind_seeds' derivation.  A row that one of
+    // the keys opens gives (index of that key, its Rewound), any other std::nullopt; FormatError as rewind_batch.  The lowest key that
+    // passes the 2^192 test decides a row (bpgpu.h).  This does NOT verify the proofs.
+    static std::variant<std::vector<std::optional<std::pair<uint32_t, Rewound>>>, ProofError> scan_batch(const BulletproofGens &bp_gens, const PedersenGens &pc_gens,
+                                                                                                        const std::vector<Transcript> &transcripts,
+                                                                                                        const std::vector<std::vector<uint8_t>> &proofs,
+                                                                                                        const std::vector<CompressedRistretto> &commitments,
+                                                                                                        size_t n, const uint8_t *keys32, size_t nkeys) {
+        bp_gens.check_pedersen(pc_gens);
+        const size_t nb = proofs.size();
+        std::vector<std::optional<std::pair<uint32_t, Rewound>>> out(nb);
+        if (!nb) return out;
+        if (commitments.size() != nb || (transcripts.size() != nb && transcripts.size() != 1) || !keys32) throw std::invalid_argument("scan_batch: one row per proof, and the keys");
+        const bool per_proof = transcripts.size() == nb && nb != 1;
+        size_t k = 0;
+        while ((size_t(1) << k) < n) k++;
+        const size_t pl = 32 * (9 + 2 * k), TS = BPGPU_TRANSCRIPT_BYTES;
+        std::vector<uint8_t> pr(nb * pl), vc(32 * nb), ts(per_proof ? nb * TS : TS), st(nb), msg(16 * nb), bl(32 * nb);
+        std::vector<uint64_t> va(nb);
+        std::vector<uint32_t> ki(nb);
+        for (size_t i = 0; i < nb; i++) {
+            if (proofs[i].size() != pl) return ProofError::FormatError;
+            std::memcpy(&pr[i * pl], proofs[i].data(), pl);
+            std::memcpy(&vc[32 * i], commitments[i].data(), 32);
+            if (per_proof || i == 0) std::memcpy(&ts[i * TS], transcripts[i].state().data(), TS);
+        }
+        const int rc = bpgpu_rangeproof_scan_batch(bp_gens.ctx(), n, nb, pr.data(), pl, vc.data(), ts.data(), per_proof ? TS : 0, keys32, nkeys, st.data(), ki.data(),
+                                                   va.data(), msg.data(), bl.data());
+        if (rc != BPGPU_OK) throw GpuError(bpgpu_last_error(bp_gens.ctx()));
+        for (size_t i = 0; i < nb; i++) {
+            if (st[i] == BPGPU_REWIND_FORMAT) return ProofError::FormatError;
+            if (st[i] != BPGPU_REWIND_OK) continue;
+            Rewound r;
+            r.value = va[i];
+            std::memcpy(r.blinding.data(), &bl[32 * i], 32);
+            std::memcpy(r.message.data(), &msg[16 * i], 16);
+            out[i] = std::make_pair(ki[i], r);
+        }
+        return out;
+    }
     // one proof: the Rewound of V if this proof was made rewindable under seed32 on `transcript` (not advanced), std::nullopt if not
     std::variant<std::optional<Rewound>, ProofError> rewind_single(const BulletproofGens &bp_gens, const PedersenGens &pc_gens, const Transcript &transcript,
                                                                    const CompressedRistretto &V, size_t n, const uint8_t *seed32) const {
