@@ -13,6 +13,6 @@ import os as _os
 _os.environ.setdefault("GPU_MAX_HW_QUEUES", "16")
 
 from ._lib import BpgpuError, Context, Pool, lib, LIB_PATH  # noqa: F401
-from .api import (BulletproofGens, BulletproofGensShare, PedersenGens, RangeProof, LinearProof, OpeningProof, Transcript, TranscriptBatch, ProofError, VerificationError,  # noqa: F401,E402
+from .api import (BulletproofGens, BulletproofGensShare, PedersenGens, RangeProof, LinearProof, OpeningProof, SigmaStatement, SigmaRelation, Transcript, TranscriptBatch, ProofError, VerificationError,  # noqa: F401,E402
                   FormatError, InvalidBitsize, InvalidGeneratorsLength)
 from . import range_proof_mpc  # noqa: F401,E402

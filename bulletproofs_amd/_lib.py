@@ -52,6 +52,9 @@ EXPORTS = [
     "bpgpu_pedersen_sum_batch", "bpgpu_pedersen_balance_batch", "bpgpu_pedersen_sum_batch_dev", "bpgpu_pedersen_balance_batch_dev",
     "bpgpu_opening_create_batch_ts", "bpgpu_opening_verify_batch_ts", "bpgpu_opening_verify_batch_ts_dev", "bpgpu_opening_verify_rlc_ts",
     "bpgpu_opening_verify_rlc_ts_dev",
+    "bpgpu_sigma_descriptor_check", "bpgpu_sigma_relation_create", "bpgpu_sigma_relation_destroy", "bpgpu_sigma_relation_shape",
+    "bpgpu_sigma_create_batch_ts", "bpgpu_sigma_verify_batch_ts", "bpgpu_sigma_verify_batch_ts_dev", "bpgpu_sigma_verify_rlc_ts",
+    "bpgpu_sigma_verify_rlc_ts_dev",
     "bpgpu_rangeproof_prove_batch_rw", "bpgpu_rangeproof_prove_batch_rw_dev", "bpgpu_rangeproof_rewind_batch", "bpgpu_rangeproof_rewind_batch_dev",
     "bpgpu_rangeproof_scan_batch", "bpgpu_rangeproof_scan_batch_dev",
 ]
@@ -181,6 +184,16 @@ def lib():
     L.bpgpu_opening_verify_batch_ts_dev.argtypes = [vp, i, sz, vp, sz, u8p, vp, vp, vp, sz, vp, vp, vp, vp]
     L.bpgpu_opening_verify_rlc_ts.argtypes = [vp, i, sz, u8p, sz, u8p, sz, u8p, u8p, sz, u8p, u8p, u8p, u8p]
     L.bpgpu_opening_verify_rlc_ts_dev.argtypes = [vp, i, sz, vp, sz, u8p, vp, vp, vp, sz, vp, vp, vp, vp, vp]
+    L.bpgpu_sigma_descriptor_check.argtypes = [u8p, sz, sz, u8p]
+    L.bpgpu_sigma_relation_create.argtypes = [vp, u8p, sz, C.POINTER(vp)]
+    L.bpgpu_sigma_relation_destroy.argtypes = [vp]
+    L.bpgpu_sigma_relation_destroy.restype = None
+    L.bpgpu_sigma_relation_shape.argtypes = [vp, C.POINTER(sz), C.POINTER(sz), C.POINTER(sz), u8p]
+    L.bpgpu_sigma_create_batch_ts.argtypes = [vp, vp, sz, u8p, sz, u8p, u8p, u8p, u8p, u8p, u8p]
+    L.bpgpu_sigma_verify_batch_ts.argtypes = [vp, vp, sz, u8p, sz, u8p, sz, u8p, u8p, u8p, u8p]
+    L.bpgpu_sigma_verify_batch_ts_dev.argtypes = [vp, vp, sz, vp, sz, u8p, vp, vp, vp, vp, vp, vp]
+    L.bpgpu_sigma_verify_rlc_ts.argtypes = [vp, vp, sz, u8p, sz, u8p, sz, u8p, u8p, u8p, u8p, u8p]
+    L.bpgpu_sigma_verify_rlc_ts_dev.argtypes = [vp, vp, sz, vp, sz, u8p, vp, vp, vp, vp, vp, vp, vp]
     L.bpgpu_rangeproof_prove_batch_rw.argtypes = [vp, sz, sz, sz, C.POINTER(C.c_uint64), u8p, u8p, sz, u8p, u8p, u8p, u8p, u8p]
     L.bpgpu_rangeproof_prove_batch_rw_dev.argtypes = [vp, sz, sz, sz, vp, vp, vp, sz, vp, vp, vp, vp, vp, vp]
     L.bpgpu_rangeproof_rewind_batch.argtypes = [vp, sz, sz, u8p, sz, u8p, u8p, sz, u8p, u8p, C.POINTER(C.c_uint64), u8p, u8p]
@@ -929,6 +942,72 @@ class Context:
         """bpgpu_opening_verify_rlc_ts_dev: as above; undecided verdicts read BPGPU_VERDICT_UNDECIDED (5)."""
         self._chk(self._L.bpgpu_opening_verify_rlc_ts_dev(self.h, form, nbatch, d_proofs, proof_len, shared_transcript, d_transcripts, d_commitments,
                                                           d_values, value_bytes, d_weights64, d_verdict, d_batch_out, d_transcripts_out, stream))
+
+    # ---- proofs of recorded linear relations between points (bpgpu_sigma_*) ----
+    def sigma_relation_create(self, desc):
+        """Record a relation from its canonical descriptor bytes (include/bpgpu.h) -> (handle, S, P, E, digest).  The handle belongs to
+        this context; release it with sigma_relation_destroy."""
+        h = C.c_void_p()
+        self._chk(self._L.bpgpu_sigma_relation_create(self.h, bytes(desc), len(desc), C.byref(h)))
+        S, P, E, dg = C.c_size_t(), C.c_size_t(), C.c_size_t(), C.create_string_buffer(32)
+        self._chk(self._L.bpgpu_sigma_relation_shape(h, C.byref(S), C.byref(P), C.byref(E), dg))
+        return h, S.value, P.value, E.value, dg.raw
+
+    def sigma_relation_destroy(self, rel):
+        self._L.bpgpu_sigma_relation_destroy(rel)
+
+    def sigma_create_batch_ts(self, rel, shape, transcripts, points, secrets, rng32=None, want_transcripts=False):
+        """Proofs of the relation `rel` (shape = (S, P, E)) for len(points) / (32 P) rows, each on its caller's own transcript
+        (bpgpu_sigma_create_batch_ts).  rng32: 32 bytes per row, the seed of its ChaChaRng (None: the library draws them); never one seed
+        for two statements or transcripts.  Returns (proofs bytes, status bytes[, transcripts])."""
+        S, P, E = shape
+        nb = len(points) // (32 * P)
+        assert len(points) == 32 * P * nb and len(secrets) == 32 * S * nb and (rng32 is None or len(rng32) == 32 * nb)
+        pl = 32 * (E + S)
+        out, st = C.create_string_buffer(pl * max(nb, 1)), C.create_string_buffer(max(nb, 1))
+        tso = C.create_string_buffer(TRANSCRIPT_BYTES * max(nb, 1)) if want_transcripts else None
+        self._chk(self._L.bpgpu_sigma_create_batch_ts(self.h, rel, nb, transcripts, self._ts_stride(transcripts, nb), rng32, bytes(points), bytes(secrets), out, st, tso))
+        res = (out.raw[:pl * nb], st.raw[:nb])
+        return res + (tso.raw[:TRANSCRIPT_BYTES * nb],) if want_transcripts else res
+
+    def sigma_verify_batch_ts(self, rel, shape, proofs, transcripts, points, want_msm=False, want_transcripts=False):
+        """Verify the rows one by one (bpgpu_sigma_verify_batch_ts).  Returns the verdict bytes[, msm_out (E x 32 bytes per row)][, transcripts]."""
+        S, P, E = shape
+        nb, pl = len(points) // (32 * P), 32 * (E + S)
+        assert len(points) == 32 * P * nb and len(proofs) == nb * pl
+        verdict = C.create_string_buffer(max(nb, 1))
+        msm = C.create_string_buffer(32 * E * max(nb, 1)) if want_msm else None
+        tso = C.create_string_buffer(TRANSCRIPT_BYTES * max(nb, 1)) if want_transcripts else None
+        self._chk(self._L.bpgpu_sigma_verify_batch_ts(self.h, rel, nb, bytes(proofs), pl, transcripts, self._ts_stride(transcripts, nb), bytes(points), verdict, msm, tso))
+        out = (verdict.raw[:nb],) + ((msm.raw[:32 * E * nb],) if want_msm else ()) + ((tso.raw[:TRANSCRIPT_BYTES * nb],) if want_transcripts else ())
+        return out if len(out) > 1 else out[0]
+
+    def sigma_verify_rlc_ts(self, rel, shape, proofs, transcripts, points, weights64=None, want_transcripts=False):
+        """The same verdicts through ONE combined check (bpgpu_sigma_verify_rlc_ts; per-proof fallback where it does not decide).
+        weights64: 64 bytes per (row, equation).  Returns (verdict bytes, batch_ok, 32-byte encoding of the combined point[, transcripts])."""
+        S, P, E = shape
+        nb, pl = len(points) // (32 * P), 32 * (E + S)
+        assert len(points) == 32 * P * nb and len(proofs) == nb * pl and (weights64 is None or len(weights64) == 64 * E * nb)
+        verdict = C.create_string_buffer(max(nb, 1))
+        bo = C.create_string_buffer(33)
+        tso = C.create_string_buffer(TRANSCRIPT_BYTES * max(nb, 1)) if want_transcripts else None
+        self._chk(self._L.bpgpu_sigma_verify_rlc_ts(self.h, rel, nb, bytes(proofs), pl, transcripts, self._ts_stride(transcripts, nb), bytes(points), weights64,
+                                                    verdict, bo, tso))
+        out = (verdict.raw[:nb], bo.raw[0] == 0, bo.raw[1:33])
+        return out + (tso.raw[:TRANSCRIPT_BYTES * nb],) if want_transcripts else out
+
+    def sigma_verify_batch_ts_dev(self, rel, nbatch, d_proofs, proof_len, shared_transcript, d_transcripts, d_points, d_verdict, d_msm_out=None,
+                                  d_transcripts_out=None, stream=None):
+        """bpgpu_sigma_verify_batch_ts_dev: shared_transcript a 208-byte host state or None, every buffer a device address (int, or
+        None), asynchronous on `stream`."""
+        self._chk(self._L.bpgpu_sigma_verify_batch_ts_dev(self.h, rel, nbatch, d_proofs, proof_len, shared_transcript, d_transcripts, d_points, d_verdict,
+                                                          d_msm_out, d_transcripts_out, stream))
+
+    def sigma_verify_rlc_ts_dev(self, rel, nbatch, d_proofs, proof_len, shared_transcript, d_transcripts, d_points, d_weights64, d_verdict,
+                                d_batch_out=None, d_transcripts_out=None, stream=None):
+        """bpgpu_sigma_verify_rlc_ts_dev: as above; undecided verdicts read BPGPU_VERDICT_UNDECIDED (5)."""
+        self._chk(self._L.bpgpu_sigma_verify_rlc_ts_dev(self.h, rel, nbatch, d_proofs, proof_len, shared_transcript, d_transcripts, d_points, d_weights64,
+                                                        d_verdict, d_batch_out, d_transcripts_out, stream))
 
     # ---- batches of transcripts (bpgpu_transcript_batch) ----
     @staticmethod

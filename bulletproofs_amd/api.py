@@ -3,7 +3,7 @@ argument meaning and error behaviour as src/lib.rs:34-45 exports for this path (
 BulletproofGens, PedersenGens, ProofError, Transcript).  The C++ twin is include/bulletproofs.hpp.
 No arithmetic happens here: parsing checks lengths / scalar canonicity, everything else is one call
 into libbpgpu.so.  There is no CPU fallback."""
-from ._lib import Context, transcript_new, transcript_append_message, transcript_challenge_bytes
+from ._lib import BpgpuError, Context, ERR_NAMES, transcript_new, transcript_append_message, transcript_challenge_bytes
 
 _L = 2**252 + 27742317777372353535851937790883648493
 
@@ -999,5 +999,164 @@ class OpeningProof:
     def verify(self, bp_gens, transcript, commitment, public_value=None):
         """Ok(()) -> None, Err(e) -> raises e (a ProofError).  The transcript is left advanced as the contract of bpgpu_opening_* says."""
         e = OpeningProof.verify_batch(bp_gens, [transcript], [self], [commitment], None if public_value is None else [public_value])[0]
+        if e is not None:
+            raise e
+
+
+class _SigmaSecret(int):
+    """a secret scalar of a SigmaStatement, by index"""
+
+
+class _SigmaBase(int):
+    """a base of a SigmaStatement, by its id (0 B_blinding, 1 B, 2 + i G_i, 16 + p instance slot p)"""
+
+
+class SigmaStatement:
+    """A linear relation between points, written once (no counterpart in the crate; the `zkp` crate's pattern next to it): secrets, instance
+    points and equations  point = sum secret * base , where a base is B, B_blinding or G(i) of bp_gens or another instance point.
+    compile() records it on the GPU context (bpgpu_sigma_relation_create) and returns the SigmaRelation that proves and verifies batches.
+        st = SigmaStatement(bp_gens); x = st.secret(); A, H, Bp = st.point(), st.point(), st.point()
+        st.equation(A, [(x, st.B)]); st.equation(H, [(x, Bp)]); dleq = st.compile()
+    At most 8 secrets, 8 points, 8 equations of 8 terms, 32 terms in all.  Public scalar coefficients are not part of a relation: fold them
+    into an instance point first (sum_commitments)."""
+
+    def __init__(self, bp_gens):
+        self._gens = bp_gens
+        self._S = self._P = 0
+        self._eqs = []
+        self.B_blinding, self.B = _SigmaBase(0), _SigmaBase(1)
+
+    def secret(self):
+        self._S += 1
+        return _SigmaSecret(self._S - 1)
+
+    def point(self):
+        self._P += 1
+        return _SigmaBase(16 + self._P - 1)
+
+    def G(self, i):
+        if not 0 <= i < 8:
+            raise ValueError("G(i): i in 0 .. 7")
+        return _SigmaBase(2 + i)
+
+    def equation(self, lhs, terms):
+        terms = list(terms)
+        if not isinstance(lhs, _SigmaBase) or lhs < 16:
+            raise TypeError("the left-hand side is an instance point (from .point())")
+        if any(not isinstance(s, _SigmaSecret) or not isinstance(b, _SigmaBase) for s, b in terms):
+            raise TypeError("terms are (secret, base) pairs")
+        self._eqs.append((int(lhs), [(int(s), int(b)) for s, b in terms]))
+
+    def descriptor(self):
+        """the canonical bytes of include/bpgpu.h"""
+        if max(self._S, self._P, len(self._eqs)) > 255 or any(len(t) > 255 for _, t in self._eqs):
+            raise ValueError("a relation has at most 8 secrets, 8 points and 8 equations of 8 terms")
+        out = bytearray([self._S, self._P, len(self._eqs)])
+        for lhs, terms in self._eqs:
+            out += bytes([lhs, len(terms)]) + b"".join(bytes(t) for t in terms)
+        return bytes(out)
+
+    def compile(self):
+        """raises ValueError for what bpgpu_sigma_relation_create refuses (a count out of range, an unused secret or point, a G(i) beyond
+        the generators)"""
+        return SigmaRelation(self._gens, self.descriptor())
+
+
+class SigmaRelation:
+    """A recorded relation (SigmaStatement.compile, or canonical descriptor bytes).  A proof is T_1 | .. | T_E | s_1 | .. | s_S, 32 (E + S)
+    bytes.  `transcripts` everywhere: one bound Transcript, the start state of every proof (not advanced), or a list of transcripts / a
+    TranscriptBatch, one per proof, each left advanced.  secrets: per row S scalars (ints below the group order or 32-byte strings);
+    points: per row P 32-byte encodings, slot order."""
+
+    def __init__(self, bp_gens, descriptor):
+        self._ctx = getattr(bp_gens, "ctx", bp_gens)
+        self.descriptor = bytes(descriptor)
+        try:
+            self._h, self.S, self.P, self.E, self.digest = self._ctx.sigma_relation_create(self.descriptor)
+        except BpgpuError as e:
+            if str(e).startswith(ERR_NAMES[-1]):
+                raise ValueError(str(e)) from None
+            raise
+        self.proof_len = 32 * (self.E + self.S)
+
+    def close(self):
+        if self._h is not None:
+            self._ctx.sigma_relation_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _shape(self):
+        return (self.S, self.P, self.E)
+
+    def _points(self, points, nb=None):
+        rows = [[bytes(x) for x in row] for row in points]
+        if any(len(row) != self.P or any(len(x) != 32 for x in row) for row in rows) or (nb is not None and len(rows) != nb):
+            raise ValueError("%d 32-byte points per row" % self.P)
+        return b"".join(b"".join(row) for row in rows), len(rows)
+
+    def create_batch(self, transcripts, secrets, points, rng_seed32=None):
+        """len(points) proofs (bpgpu_sigma_create_batch_ts) -> [bytes].  rng_seed32: 32 bytes per row, the seed of its ChaChaRng (None: the
+        library draws them) -- never one seed for two statements or transcripts.  Raises ValueError for a secret that is not canonical
+        or an instance base that does not decode."""
+        pts, nb = self._points(points)
+        rows = [[int(x).to_bytes(32, "little") if isinstance(x, int) else bytes(x) for x in row] for row in secrets]
+        if len(rows) != nb or any(len(row) != self.S or any(len(x) != 32 for x in row) for row in rows):
+            raise ValueError("%d 32-byte secrets per row" % self.S)
+        if nb == 0:
+            return []
+        per_proof = _per_proof(transcripts)
+        if per_proof and len(transcripts) != nb:
+            raise ValueError("create_batch: one transcript per proof")
+        states = _states_of(transcripts) if per_proof else transcripts.state
+        proofs, status, ts = self._ctx.sigma_create_batch_ts(self._h, self._shape(), states, pts, b"".join(b"".join(row) for row in rows),
+                                                             rng32=None if rng_seed32 is None else bytes(rng_seed32), want_transcripts=True)
+        if any(status):
+            i = next(i for i, x in enumerate(status) if x)
+            raise ValueError(("secrets must be canonical (row %d)" if status[i] == 2 else "an instance base does not decode (row %d)") % i)
+        if per_proof:
+            _advance_all(transcripts, ts)
+        return [proofs[self.proof_len * i:self.proof_len * (i + 1)] for i in range(nb)]
+
+    def _verify(self, transcripts, proofs, points, combined, weights64):
+        proofs = [bytes(p) for p in proofs]
+        if not proofs:
+            return []
+        if any(len(p) != self.proof_len for p in proofs):
+            raise ValueError("a proof of this relation has %d bytes" % self.proof_len)
+        pts, _ = self._points(points, len(proofs))
+        per_proof = _per_proof(transcripts)
+        if per_proof and len(transcripts) != len(proofs):
+            raise ValueError("verify_batch: one transcript per proof")
+        states = _states_of(transcripts) if per_proof else transcripts.state
+        if combined:
+            v, _, _, ts = self._ctx.sigma_verify_rlc_ts(self._h, self._shape(), b"".join(proofs), states, pts, weights64=weights64, want_transcripts=True)
+        else:
+            v, ts = self._ctx.sigma_verify_batch_ts(self._h, self._shape(), b"".join(proofs), states, pts, want_transcripts=True)
+        if per_proof:
+            _advance_all(transcripts, ts)
+        return [None if x == 0 else _BY_CODE[x]() for x in v]
+
+    def verify_batch(self, transcripts, proofs, points):
+        """Every proof on its own (bpgpu_sigma_verify_batch_ts) -> list of None / ProofError."""
+        return self._verify(transcripts, proofs, points, False, None)
+
+    def verify_batch_combined(self, transcripts, proofs, points, weights64=None):
+        """verify_batch's arguments and verdicts through ONE combined check (bpgpu_sigma_verify_rlc_ts): one multiscalar multiplication
+        over P + E points per proof when every proof verifies, per-proof re-verification inside the call when not.  weights64: 64 bytes
+        per (proof, equation), unpredictable to the provers, or None (drawn by the library)."""
+        return self._verify(transcripts, proofs, points, True, weights64)
+
+    def create(self, transcript, secrets, points, rng_seed32=None):
+        """one proof; the transcript is left advanced"""
+        return self.create_batch([transcript], [secrets], [points], rng_seed32=rng_seed32)[0]
+
+    def verify(self, transcript, proof, points):
+        """Ok(()) -> None, Err(e) -> raises e (a ProofError).  The transcript is left advanced."""
+        e = self.verify_batch([transcript], [proof], [points])[0]
         if e is not None:
             raise e

@@ -7,6 +7,7 @@
 #include <sys/random.h>
 
 #include <algorithm>
+#include <atomic>
 #include <cstdarg>
 #include <cstdio>
 #include <cstring>
@@ -45,7 +46,9 @@ static std::mutex g_tab_build_mu[64];       // one table under construction per 
                                             // one waits and finds it); tables of different devices are built at the same time (pool over N devices)
 static std::vector<shared_table *> g_tables;
 
+static std::atomic<uint64_t> g_ctx_serial{1};
 struct bpgpu_ctx {
+    const uint64_t serial = g_ctx_serial.fetch_add(1);   // never reused, unlike the address: what a recorded relation remembers of its context
     int device = 0;
     hipStream_t stream = nullptr;
     std::mutex mu;
@@ -7579,4 +7582,336 @@ extern "C" int bpgpu_rangeproof_scan_batch_dev(bpgpu_ctx *c, size_t n, size_t nb
     const int rc2 = ctx_leave(c, s);
     if (!rc && !ok) rc = fail(c, BPGPU_ERR_HIP, "clearing the scan's working set failed");
     return rc ? rc : rc2;
+}
+
+// ============================================================================
+// proofs of recorded linear relations between points (sigma.h)
+// ============================================================================
+struct bpgpu_sigma_relation {
+    bpgpu_ctx *ctx = nullptr;   // (compared, never followed, by destroy: the context may be gone by then)
+    uint64_t ctx_serial = 0;    // a later context at the same address is another context
+    int device = 0;
+    sig_rel h{};
+    sig_rel *d = nullptr;       // the record on the context's device
+};
+
+static int sig_parse(bpgpu_ctx *c, const uint8_t *desc, size_t desc_len, size_t gens_capacity, sig_rel &r) {
+    const char *why = sig_rel_parse(desc, desc_len, gens_capacity, r);
+    return why ? fail(c, BPGPU_ERR_INVALID_ARG, "%s", why) : BPGPU_OK;
+}
+extern "C" int bpgpu_sigma_descriptor_check(const uint8_t *desc, size_t desc_len, size_t gens_capacity, uint8_t digest[32]) {
+    sig_rel r;
+    const int rc = sig_parse(nullptr, desc, desc_len, gens_capacity, r);
+    if (!rc && digest) memcpy(digest, r.digest, 32);
+    return rc;
+}
+extern "C" int bpgpu_sigma_relation_create(bpgpu_ctx *c, const uint8_t *desc, size_t desc_len, bpgpu_sigma_relation **out) {
+    if (!c || !out) return BPGPU_ERR_INVALID_ARG;
+    *out = nullptr;
+    std::lock_guard<std::mutex> lk(c->mu);
+    sig_rel r;
+    const int rcp = sig_parse(c, desc, desc_len, c->gens_capacity, r);
+    if (rcp) return rcp;
+    HIPCHK(c, hipSetDevice(c->device));
+    sig_rel *d = nullptr;
+    if (hipMalloc((void **)&d, sizeof r) != hipSuccess) return fail(c, BPGPU_ERR_HIP, "out of device memory");
+    if (hipMemcpy(d, &r, sizeof r, hipMemcpyHostToDevice) != hipSuccess) {
+        (void)hipFree(d);
+        return fail(c, BPGPU_ERR_HIP, "copying the relation failed");
+    }
+    bpgpu_sigma_relation *rel = new bpgpu_sigma_relation;
+    rel->ctx = c;
+    rel->ctx_serial = c->serial;
+    rel->device = c->device;
+    rel->h = r;
+    rel->d = d;
+    *out = rel;
+    return BPGPU_OK;
+}
+extern "C" void bpgpu_sigma_relation_destroy(bpgpu_sigma_relation *rel) {
+    if (!rel) return;
+    if (rel->d) {
+        (void)hipSetDevice(rel->device);
+        (void)hipDeviceSynchronize();   // a _dev call may still be reading the record on a caller's stream
+        (void)hipFree(rel->d);
+    }
+    delete rel;
+}
+extern "C" int bpgpu_sigma_relation_shape(const bpgpu_sigma_relation *rel, size_t *S, size_t *P, size_t *E, uint8_t digest[32]) {
+    if (!rel) return BPGPU_ERR_INVALID_ARG;
+    if (S) *S = rel->h.S;
+    if (P) *P = rel->h.P;
+    if (E) *E = rel->h.E;
+    if (digest) memcpy(digest, rel->h.digest, 32);
+    return BPGPU_OK;
+}
+
+// the argument rules every entry point of the family shares; `proof_len` is 0 for the creation
+static int sig_check_args(bpgpu_ctx *c, const bpgpu_sigma_relation *rel, size_t nbatch, size_t proof_len, bool create) {
+    if (!rel || rel->ctx != c || rel->ctx_serial != c->serial) return fail(c, BPGPU_ERR_INVALID_ARG, "the relation is missing or was recorded on another context");
+    const size_t want = 32 * (size_t)(rel->h.E + rel->h.S);
+    if (!create && proof_len != want) return fail(c, BPGPU_ERR_INVALID_ARG, "proof_len must be 32 (E + S) = %zu", want);
+    if (nbatch * (rel->h.P + rel->h.E) > SIG_RLC_MAX_TERMS) return fail(c, BPGPU_ERR_INVALID_ARG, "batch too large: at most 2^24 / (P + E) proofs per call");
+    return BPGPU_OK;
+}
+// (under the lock) the generators may have been replaced since the relation was recorded
+static int sig_check_gens_locked(bpgpu_ctx *c, const bpgpu_sigma_relation *rel) {
+    if (!c->d_table) return fail(c, BPGPU_ERR_NO_GENS, "generators not loaded");
+    if (rel->h.G > c->gens_capacity) return fail(c, BPGPU_ERR_NO_GENS, "the relation uses G_%u: beyond the loaded generators", rel->h.G - 1);
+    return BPGPU_OK;
+}
+
+// what the front end leaves on the device (c->ipp_buf) for the multiscalar multiplication(s)
+struct sig_staged {
+    char *d_sc = nullptr, *d_pt = nullptr, *d_gen = nullptr, *d_stat = nullptr, *d_mst = nullptr, *d_out = nullptr;
+};
+// the staging and the k_sig_front launch (lane = proof) of nbatch proofs: nbatch E rows of P + 1 unique terms and 2 + G generator columns
+static int sig_front_dev_locked(bpgpu_ctx *c, const bpgpu_sigma_relation *rel, size_t nbatch, const void *d_proofs, const ipp_ts &ts, const void *d_points,
+                                void *d_ts_out, hipStream_t s, sig_staged &stg) {
+    int rc = sig_check_gens_locked(c, rel);
+    if (rc) return rc;
+    const size_t rows = nbatch * rel->h.E, U = sig_uniq(rel->h), GR = sig_gen_row(rel->h);
+    const size_t sz_terms = align_up(rows * U * 32 + 64), sz_gen = align_up(rows * GR * 32 + 64), sz_st = align_up(nbatch * 4), sz_b = align_up(rows + 64),
+                 sz_o = align_up(rows * 32 + 64);
+    rc = ipp_reserve(c, 2 * sz_terms + sz_gen + sz_st + sz_b + sz_o);
+    if (rc) return rc;
+    stg.d_sc = c->ipp_buf, stg.d_pt = stg.d_sc + sz_terms, stg.d_gen = stg.d_pt + sz_terms, stg.d_stat = stg.d_gen + sz_gen, stg.d_mst = stg.d_stat + sz_st,
+    stg.d_out = stg.d_mst + sz_b;
+    HIPCHK(c, hipMemsetAsync(stg.d_sc, 0, 2 * sz_terms + sz_gen + sz_st, s));   // scalars, points, generator rows, status
+    rp_strobe_init init;
+    ipp_ts_init(init, ts);
+    const uint32_t nb32 = (uint32_t)nbatch;
+    LAUNCH(c, s, "sig_front", k_sig_front, (nb32 + RP_BLOCK - 1) / RP_BLOCK, RP_BLOCK, (const sig_rel *)rel->d, nb32, init, (const uint32_t *)d_proofs,
+           (const uint32_t *)d_points, (const uint32_t *)ts.d_in, ts.stride, (uint32_t *)stg.d_sc, (uint32_t *)stg.d_pt, (uint32_t *)stg.d_gen,
+           (uint32_t *)stg.d_stat, (uint32_t *)d_ts_out);
+    return BPGPU_OK;
+}
+
+// per proof: the front end, then the shared-generator chain with one row per (proof, equation), then the verdicts
+static int sig_verify_dev_locked(bpgpu_ctx *c, const bpgpu_sigma_relation *rel, size_t nbatch, const void *d_proofs, const ipp_ts &ts, const void *d_points,
+                                 void *d_verdict, void *d_msm_out, void *d_ts_out, hipStream_t s) {
+    sig_staged stg;
+    int rc = sig_front_dev_locked(c, rel, nbatch, d_proofs, ts, d_points, d_ts_out, s, stg);
+    if (rc) return rc;
+    const size_t rows = nbatch * rel->h.E;
+    rc = msm_shared_dev_locked(c, rel->h.G, 1, rows, sig_uniq(rel->h), stg.d_gen, stg.d_sc, stg.d_pt, stg.d_out, stg.d_mst, nullptr, s, true);
+    if (rc) return rc;
+    const uint32_t nb32 = (uint32_t)nbatch;
+    LAUNCH(c, s, "sig_verdict", k_sig_verdict, (nb32 + 63) / 64, 64, nb32, rel->h.E, (const uint32_t *)stg.d_stat, (const uint8_t *)stg.d_mst,
+           (const uint32_t *)stg.d_out, (uint8_t *)d_verdict);
+    if (d_msm_out) HIPCHK(c, hipMemcpyAsync(d_msm_out, stg.d_out, rows * 32, hipMemcpyDeviceToDevice, s));
+    HIPCHK(c, hipGetLastError());
+    return BPGPU_OK;
+}
+
+// combined: R = sum_{p,k} rho_{p,k} Check_{p,k}: the front end, one weight per (proof, equation), the weigh launch (P + E unique terms per
+// proof, 2 + G shared rows), the reduction into the generator-table row and ONE multiscalar multiplication over nbatch (P + E) points,
+// then the verdicts (undecided where R is not the identity)
+static int sig_rlc_dev_locked(bpgpu_ctx *c, const bpgpu_sigma_relation *rel, size_t nbatch, const void *d_proofs, const ipp_ts &ts, const void *d_points,
+                              const void *d_weights64, uint8_t *d_verdict, uint8_t *d_batch, void *d_ts_out, hipStream_t s) {
+    sig_staged stg;
+    int rc = sig_front_dev_locked(c, rel, nbatch, d_proofs, ts, d_points, d_ts_out, s, stg);
+    if (rc) return rc;
+    const size_t NU = rel->h.P + rel->h.E, GR = sig_gen_row(rel->h), nterms = NU * nbatch, nrho = nbatch * rel->h.E;
+    arena_plan ap;
+    const size_t off_csc = ap.add(nterms * 32 + 64), off_cpt = ap.add(nterms * 32 + 64), off_acc = ap.add(GR * 80), off_row = ap.add(GR * 32 + 64),
+                 off_rho = ap.add(nrho * 32), off_bo = ap.add(64);
+    rc = comb_reserve(c, ap.total);
+    if (rc) return rc;
+    char *b = c->comb_buf, *d_csc = b + off_csc, *d_cpt = b + off_cpt, *d_acc = b + off_acc, *d_row = b + off_row, *d_rho = b + off_rho, *d_bo = b + off_bo;
+    if (!d_batch) d_batch = (uint8_t *)d_bo;
+    const uint32_t nb32 = (uint32_t)nbatch, nstride = (uint32_t)((nbatch + 63) / 64 * 64);
+    rc = comb_rho_locked(c, s, "sig_rlc_rho", (uint32_t)nrho, d_weights64, SIG_RLC_WEIGHT_DOMAIN, d_rho);
+    if (rc) return rc;
+    HIPCHK(c, hipMemsetAsync(d_acc, 0, GR * 80, s));
+    LAUNCH(c, s, "sig_rlc_weigh", k_sig_rlc_weigh, (uint32_t)((NU + GR) * nstride / 64), 64, (const sig_rel *)rel->d, nb32, nstride, (const uint32_t *)stg.d_stat,
+           (const uint32_t *)d_rho, (const uint32_t *)stg.d_gen, (const uint32_t *)stg.d_sc, (const uint32_t *)stg.d_pt, (const uint32_t *)d_points,
+           (uint32_t *)d_csc, (uint32_t *)d_cpt, (unsigned long long *)d_acc);
+    LAUNCH(c, s, "sig_rlc_reduce", k_rlc_comb_reduce, 1, 64, (uint32_t)GR, (const unsigned long long *)d_acc, (uint32_t *)d_row);
+    rc = msm_shared_dev_locked(c, rel->h.G, 1, 1, nterms, d_row, d_csc, d_cpt, stg.d_out, stg.d_mst, nullptr, s, true);
+    if (rc) return rc;
+    LAUNCH(c, s, "sig_rlc_verdict", k_rlc_comb_verdict, (nb32 + 63) / 64, 64, nb32, (const uint32_t *)stg.d_stat, (const uint32_t *)stg.d_out,
+           (const uint8_t *)stg.d_mst, d_verdict, d_batch);
+    HIPCHK(c, hipGetLastError());
+    return BPGPU_OK;
+}
+
+// host pointers, both verifiers: rlc = the combined check with its per-proof fallback
+static int sig_verify_host_call(bpgpu_ctx *c, const bpgpu_sigma_relation *rel, size_t nbatch, const uint8_t *proofs, size_t proof_len, const uint8_t *transcripts,
+                                size_t transcript_stride, const uint8_t *points, bool rlc, const uint8_t *weights64, uint8_t *verdict, uint8_t *msm_out,
+                                uint8_t *batch_out, uint8_t *transcripts_out) {
+    if (!c) return BPGPU_ERR_INVALID_ARG;
+    int rc = sig_check_args(c, rel, nbatch, proof_len, false);
+    if (rc) return rc;
+    if ((rc = ipp_ts_host_args(c, transcripts, transcript_stride, nbatch))) return rc;
+    if (nbatch == 0) {
+        if (rlc && batch_out) memset(batch_out, 0, 33);
+        return BPGPU_OK;
+    }
+    if (!proofs || !points || !verdict) return BPGPU_ERR_INVALID_ARG;
+    std::lock_guard<std::mutex> lk(c->mu);
+    HIPCHK(c, hipSetDevice(c->device));
+    hipStream_t s = c->stream;
+    const size_t TS = BPGPU_TRANSCRIPT_BYTES, nstates = transcript_stride ? nbatch : 1, P = rel->h.P, E = rel->h.E;
+    host_call<bpgpu_ctx> io(c, s);
+    const int r_pr = io.in(nbatch * proof_len + 64), r_p = io.in(nbatch * P * 32 + 64), r_ti = io.in(nstates * TS), r_w = io.in(weights64 ? nbatch * E * 64 : 0);
+    const int r_v = io.out(nbatch), r_o = io.out(rlc ? 64 : nbatch * E * 32), r_t = io.out(transcripts_out ? nbatch * TS : 0);
+    rc = io.open();
+    if (rc) return rc;
+    io.put(r_pr, proofs, nbatch * proof_len);
+    io.put(r_p, points, nbatch * P * 32);
+    io.put(r_ti, transcripts, nstates * TS);
+    if (weights64) io.put(r_w, weights64, nbatch * E * 64);
+    ipp_ts ts;
+    ts.d_in = io.d(r_ti);
+    ts.stride = transcript_stride ? BP_TS_WORDS : 0;
+    void *a_to = transcripts_out ? io.d(r_t) : nullptr;
+    rc = io.upload();
+    if (!rc) {
+        if (rlc)
+            rc = sig_rlc_dev_locked(c, rel, nbatch, io.d(r_pr), ts, io.d(r_p), weights64 ? io.d(r_w) : nullptr, (uint8_t *)io.d(r_v), (uint8_t *)io.d(r_o), a_to, s);
+        else rc = sig_verify_dev_locked(c, rel, nbatch, io.d(r_pr), ts, io.d(r_p), io.d(r_v), io.d(r_o), a_to, s);
+    }
+    rc = io.finish(io.download(rc));
+    if (rc) return rc;
+    if (transcripts_out) memcpy(transcripts_out, io.h(r_t), nbatch * TS);
+    if (rlc) {
+        if (batch_out) memcpy(batch_out, io.h(r_o), 33);   // (R as computed before any fallback)
+        if ((uint8_t)io.h(r_o)[0] != 0) {
+            // R is not the identity, or a point of the combined MSM did not decode: the batch again through the per-proof path (inputs are
+            // still on the device; the transcripts it leaves are the ones already copied out)
+            rc = io.rerun_per_proof(r_v, r_o, [&] { return sig_verify_dev_locked(c, rel, nbatch, io.d(r_pr), ts, io.d(r_p), io.d(r_v), nullptr, nullptr, s); });
+            if (rc) return rc;
+        }
+    } else if (msm_out) {
+        memcpy(msm_out, io.h(r_o), nbatch * E * 32);
+    }
+    memcpy(verdict, io.h(r_v), nbatch);
+    return BPGPU_OK;
+}
+
+extern "C" int bpgpu_sigma_verify_batch_ts(bpgpu_ctx *c, const bpgpu_sigma_relation *rel, size_t nbatch, const uint8_t *proofs, size_t proof_len,
+                                           const uint8_t *transcripts, size_t transcript_stride, const uint8_t *points, uint8_t *verdict, uint8_t *msm_out,
+                                           uint8_t *transcripts_out) {
+    return sig_verify_host_call(c, rel, nbatch, proofs, proof_len, transcripts, transcript_stride, points, false, nullptr, verdict, msm_out, nullptr, transcripts_out);
+}
+extern "C" int bpgpu_sigma_verify_rlc_ts(bpgpu_ctx *c, const bpgpu_sigma_relation *rel, size_t nbatch, const uint8_t *proofs, size_t proof_len,
+                                         const uint8_t *transcripts, size_t transcript_stride, const uint8_t *points, const uint8_t *weights64, uint8_t *verdict,
+                                         uint8_t *batch_out, uint8_t *transcripts_out) {
+    return sig_verify_host_call(c, rel, nbatch, proofs, proof_len, transcripts, transcript_stride, points, true, weights64, verdict, nullptr, batch_out, transcripts_out);
+}
+
+// device pointers, both verifiers
+static int sig_verify_dev_call(bpgpu_ctx *c, const bpgpu_sigma_relation *rel, size_t nbatch, const void *d_proofs, size_t proof_len, const uint8_t *shared_transcript,
+                               const void *d_transcripts, const void *d_points, bool rlc, const void *d_weights64, void *d_verdict, void *d_out,
+                               void *d_transcripts_out, void *stream) {
+    if (!c) return BPGPU_ERR_INVALID_ARG;
+    int rc = sig_check_args(c, rel, nbatch, proof_len, false);
+    if (rc) return rc;
+    ipp_ts ts;
+    if ((rc = ipp_ts_dev_args(c, shared_transcript, d_transcripts, d_transcripts_out, ts))) return rc;
+    if (nbatch == 0) return BPGPU_OK;
+    if (!d_proofs || !d_points || !d_verdict) return BPGPU_ERR_INVALID_ARG;
+    if (((uintptr_t)d_proofs | (uintptr_t)d_points) & 3) return fail(c, BPGPU_ERR_INVALID_ARG, "device buffers must be 4-byte aligned");
+    std::lock_guard<std::mutex> lk(c->mu);
+    HIPCHK(c, hipSetDevice(c->device));
+    hipStream_t s = stream ? (hipStream_t)stream : c->stream;
+    if ((rc = ctx_enter(c, s))) return rc;
+    if (rlc) rc = sig_rlc_dev_locked(c, rel, nbatch, d_proofs, ts, d_points, d_weights64, (uint8_t *)d_verdict, (uint8_t *)d_out, d_transcripts_out, s);
+    else rc = sig_verify_dev_locked(c, rel, nbatch, d_proofs, ts, d_points, d_verdict, d_out, d_transcripts_out, s);
+    const int rc2 = ctx_leave(c, s);
+    return rc ? rc : rc2;
+}
+extern "C" int bpgpu_sigma_verify_batch_ts_dev(bpgpu_ctx *c, const bpgpu_sigma_relation *rel, size_t nbatch, const void *d_proofs, size_t proof_len,
+                                               const uint8_t *shared_transcript, const void *d_transcripts, const void *d_points, void *d_verdict,
+                                               void *d_msm_out, void *d_transcripts_out, void *stream) {
+    return sig_verify_dev_call(c, rel, nbatch, d_proofs, proof_len, shared_transcript, d_transcripts, d_points, false, nullptr, d_verdict, d_msm_out,
+                               d_transcripts_out, stream);
+}
+extern "C" int bpgpu_sigma_verify_rlc_ts_dev(bpgpu_ctx *c, const bpgpu_sigma_relation *rel, size_t nbatch, const void *d_proofs, size_t proof_len,
+                                             const uint8_t *shared_transcript, const void *d_transcripts, const void *d_points, const void *d_weights64,
+                                             void *d_verdict, void *d_batch_out, void *d_transcripts_out, void *stream) {
+    return sig_verify_dev_call(c, rel, nbatch, d_proofs, proof_len, shared_transcript, d_transcripts, d_points, true, d_weights64, d_verdict, d_batch_out,
+                               d_transcripts_out, stream);
+}
+
+// creation: per slice of rows the product launch (lane = (instance-base term, row)) and the walk (lane = (equation, row)), then ONE finish
+// launch over the batch.  A slice is as many rows as keep the product launch at SIG_CREATE_LANES lanes: their tables of multiples live
+// in the workspace (c->ipp_buf: the products are partial sums of the T_k, part of the prover's working set).  The secrets and the seeds
+// come first in the staging: the secret span, cleared on every exit
+#define SIG_CREATE_LANES 65536u
+extern "C" int bpgpu_sigma_create_batch_ts(bpgpu_ctx *c, const bpgpu_sigma_relation *rel, size_t nbatch, const uint8_t *transcripts, size_t transcript_stride,
+                                           const uint8_t *rng32, const uint8_t *points, const uint8_t *secrets, uint8_t *proofs_out, uint8_t *status,
+                                           uint8_t *transcripts_out) {
+    if (!c) return BPGPU_ERR_INVALID_ARG;
+    int rc = sig_check_args(c, rel, nbatch, 0, true);
+    if (rc) return rc;
+    if ((rc = ipp_ts_host_args(c, transcripts, transcript_stride, nbatch))) return rc;
+    if (nbatch == 0) return BPGPU_OK;
+    if (!points || !secrets || !proofs_out || !status) return BPGPU_ERR_INVALID_ARG;
+    std::lock_guard<std::mutex> lk(c->mu);
+    HIPCHK(c, hipSetDevice(c->device));
+    if ((rc = sig_check_gens_locked(c, rel))) return rc;
+    hipStream_t s = c->stream;
+    const size_t TS = BPGPU_TRANSCRIPT_BYTES, nstates = transcript_stride ? nbatch : 1, S = rel->h.S, P = rel->h.P, proof_len = 32 * (size_t)(rel->h.E + S);
+    host_call<bpgpu_ctx> io(c, s);
+    const int r_x = io.in(nbatch * S * 32), r_seed = io.in(nbatch * 32), r_p = io.in(nbatch * P * 32 + 64), r_ti = io.in(nstates * TS);
+    const int r_pr = io.out(nbatch * proof_len), r_st = io.out(nbatch), r_t = io.out(transcripts_out ? nbatch * TS : 0);
+    io.secrets(io.off[r_p]);   // secrets and seeds
+    rc = io.open();
+    if (rc) return io.finish(rc);
+    io.put(r_x, secrets, nbatch * S * 32);
+    if (rng32) io.put(r_seed, rng32, nbatch * 32);
+    else if ((rc = os_random(c, io.h(r_seed), nbatch * 32)) != 0) return io.finish(rc);
+    io.put(r_p, points, nbatch * P * 32);
+    io.put(r_ti, transcripts, nstates * TS);
+    if ((rc = io.upload())) return io.finish(rc);
+    do {
+        const bool ct = c->prover_ct;
+        if (ct && (rc = build_ct_table(c))) break;
+        const uint32_t nb32 = (uint32_t)nbatch, nvb = rel->h.nvb, E = rel->h.E;
+        uint32_t slice = SIG_CREATE_LANES / (nvb ? nvb : 1) / 64 * 64;   // (nvb <= 32: at least 2 048 rows)
+        if (slice > nb32) slice = (nb32 + 63) / 64 * 64;
+        const size_t sz_tab = align_up((size_t)nvb * slice * SIG_VB_WORDS * 4 + 64), sz_prod = align_up((size_t)nvb * slice * 160 + 64), sz_bad = align_up(nbatch * 4);
+        if ((rc = ipp_reserve(c, sz_tab + sz_prod + sz_bad))) break;
+        sig_ws ws;
+        ws.tab = (uint32_t *)c->ipp_buf;
+        ws.prod = (uint32_t *)(c->ipp_buf + sz_tab);
+        ws.bad = (uint32_t *)(c->ipp_buf + sz_tab + sz_prod);
+        ws.nstride = slice;
+        if (hipMemsetAsync(ws.bad, 0, sz_bad, s) != hipSuccess) {
+            rc = fail(c, BPGPU_ERR_HIP, "memset failed");
+            break;
+        }
+        sig_create_in in;
+        in.secrets = (const uint32_t *)io.d(r_x);
+        in.seeds = (const uint8_t *)io.d(r_seed);
+        in.points = (const uint32_t *)io.d(r_p);
+        in.ts_in = (const uint32_t *)io.d(r_ti);
+        in.ts_in_stride = transcript_stride ? BP_TS_WORDS : 0;
+        in.nrows = nb32;
+        for (uint32_t row0 = 0; row0 < nb32; row0 += slice) {   // (slices run one after another on the stream: they share the workspace)
+            ws.row0 = row0;
+            const uint32_t nslice = std::min<uint32_t>(slice, nb32 - row0);
+            if (nvb) {
+                if (ct) LAUNCH(c, s, "sig_vb_ct", k_sig_vb<true>, nvb * slice / BP_BLOCK, BP_BLOCK, (const sig_rel *)rel->d, in, ws);
+                else LAUNCH(c, s, "sig_vb", k_sig_vb<false>, nvb * slice / BP_BLOCK, BP_BLOCK, (const sig_rel *)rel->d, in, ws);
+            }
+            if (ct)
+                LAUNCH(c, s, "sig_walk_ct", k_sig_walk<true>, E * slice / BP_BLOCK, BP_BLOCK, rel->h, in, ws, nslice, c->prm_ct, (const fb_entry *)c->d_table_ct,
+                       (uint32_t *)io.d(r_pr));
+            else
+                LAUNCH(c, s, "sig_walk", k_sig_walk<false>, E * slice / BP_BLOCK, BP_BLOCK, rel->h, in, ws, nslice, c->prm, (const fb_entry *)c->d_table,
+                       (uint32_t *)io.d(r_pr));
+        }
+        LAUNCH(c, s, "sig_finish", k_sig_finish, (nb32 + RP_BLOCK - 1) / RP_BLOCK, RP_BLOCK, (const sig_rel *)rel->d, in, (const uint32_t *)ws.bad,
+               (uint32_t *)io.d(r_pr), (uint8_t *)io.d(r_st), transcripts_out ? (uint32_t *)io.d(r_t) : nullptr);
+        if (hipGetLastError() != hipSuccess) rc = fail(c, BPGPU_ERR_HIP, "launch failed");
+    } while (0);
+    rc = io.finish(io.download(rc));
+    if (rc) return rc;
+    memcpy(proofs_out, io.h(r_pr), nbatch * proof_len);
+    memcpy(status, io.h(r_st), nbatch);
+    if (transcripts_out) memcpy(transcripts_out, io.h(r_t), nbatch * TS);
+    return BPGPU_OK;
 }

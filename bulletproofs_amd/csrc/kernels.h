@@ -32,6 +32,7 @@
 #include "opening.h"
 #include "rewind.h"
 #include "scan.h"
+#include "sigma.h"
 
 #define BP_BLOCK 64   // one wavefront per workgroup: under contention a CU rarely has room for four waves of one group at once (256: -8% at 48 streams)
 #define FB_BLOCK 64
@@ -231,5 +232,15 @@ template <bool CT>
 __global__ void k_scan_cand(rwd_shape sh, rwd_in in, scn_ws ws);
 template <bool CT>
 __global__ void k_scan_open(rwd_shape sh, rwd_in in, scn_keys k, scn_ws ws, rwd_out out, uint32_t *key_index, fb_params prm, const uint32_t *gen_ids, const fb_entry *table);
+
+// k_sigma.hip
+template <bool CT>
+__global__ void k_sig_vb(const sig_rel *rel, sig_create_in in, sig_ws ws);
+template <bool CT>
+__global__ void k_sig_walk(sig_rel rel, sig_create_in in, sig_ws ws, uint32_t nslice, fb_params prm, const fb_entry *table, uint32_t *proofs_out);
+__global__ void k_sig_finish(const sig_rel *rel, sig_create_in in, const uint32_t *bad, uint32_t *proofs_out, uint8_t *status, uint32_t *ts_out);
+__global__ void k_sig_front(const sig_rel *rel, uint32_t nproofs, rp_strobe_init init, const uint32_t *proofs, const uint32_t *points, const uint32_t *ts_in, uint32_t ts_in_stride, uint32_t *eq_sc, uint32_t *eq_pt, uint32_t *gen_sc, uint32_t *status, uint32_t *ts_out);
+__global__ void k_sig_verdict(uint32_t n, uint32_t E, const uint32_t *status, const uint8_t *msm_status, const uint32_t *msm_out, uint8_t *verdict);
+__global__ void k_sig_rlc_weigh(const sig_rel *rel, uint32_t nproofs, uint32_t nstride, const uint32_t *status, const uint32_t *rho, const uint32_t *gen_sc, const uint32_t *eq_sc, const uint32_t *eq_pt, const uint32_t *points, uint32_t *comb_sc, uint32_t *comb_pt, unsigned long long *acc);
 
 #endif

@@ -1263,6 +1263,85 @@ int bpgpu_opening_verify_rlc_ts_dev(bpgpu_ctx *ctx, int form, size_t nbatch, con
                                     const void *d_values, size_t value_bytes, const void *d_weights64, void *d_verdict,
                                     void *d_batch_out, void *d_transcripts_out, void *stream);
 
+/* ---- proofs of recorded linear relations between points -------------------------------------------
+ * The sigma protocol of the opening proofs over ANY set of linear equations between points (csrc/sigma.h; nothing in the reference
+ * defines it): "two commitments under different value bases hold the same amount", "a key and a tag share a discrete log" (DLEQ), "an
+ * ElGamal pair encrypts what a commitment commits to", "I can open this vector commitment".  A relation is recorded once per context,
+ * as a gadget is for R1CS (bpgpu_r1cs_circuit_create), and batches are proved and verified against the record.
+ * THE RELATION: S secret scalars x_0 .. x_{S-1}, P instance-point slots per row, E equations, each of 1 .. 8; equation k reads
+ *     slot[lhs_k] = sum_t x[sec_{k,t}] Base[base_{k,t}]     with 1 .. 8 terms, at most 32 terms in all.
+ * A base id is 0 = B_blinding or 1 = B of the context's generators, 2 + i = G_i of party 0 (i < 8 and i < gens_capacity; custom shared
+ * bases come in through bpgpu_gens_load), or 16 + p = instance slot p of the row.  An lhs is always 16 + p.  Public scalar coefficients
+ * are out of scope: a caller folds them into an instance point (bpgpu_pedersen_sum_batch) before the call.
+ * Canonical descriptor bytes:  u8 S, u8 P, u8 E,  then per equation  u8 lhs, u8 nterms,  then nterms x (u8 secret, u8 base).
+ * bpgpu_sigma_relation_create returns BPGPU_ERR_INVALID_ARG when a count is out of range, an lhs is not an instance slot, a secret or a
+ * slot index is out of range, a secret is used in no term, an instance slot is used nowhere, a G_i lies beyond the loaded generators,
+ * or the bytes end early or late.  It stores digest = Transcript(b"sigma statement"), append_message(b"desc", bytes),
+ * challenge_bytes(b"digest", 32).  The relation belongs to the context it was recorded on and may only be used there (another context, also a later one at the same
+ * address, is BPGPU_ERR_INVALID_ARG).  bpgpu_sigma_relation_destroy waits for the device to drain before it frees the record, so it may
+ * follow an asynchronous _dev call directly; it must not run concurrently with a call that uses the relation.  Destroying it after the
+ * context is allowed.
+ * Transcript, applied to the caller's own state at any STROBE position:
+ *     append_message(b"dom-sep", b"sigmaproof v1"); append_message(b"stmt", digest);
+ *     append_point(b"P", P_i) for the P instance points in slot order -- as given; the identity is allowed (a zero balance as an lhs);
+ *     validate_and_append_point(b"T", T_k), k = 1 .. E -- 32 zero bytes: VerificationError, nothing of that T_k absorbed;
+ *     c = challenge_scalar(b"c").
+ * Prover: nonce k_j = draw j of ChaChaRng::from_seed(rng32[row]); T_k = sum_t k[sec] Base; s_j = k_j + c x_j.
+ * proof = T_1 | .. | T_E | s_1 | .. | s_S, 32 (E + S) bytes.
+ * Verifier, equation k: sum_t s[sec] Base - c slot[lhs_k] - T_k must be the identity.
+ * Arguments (the transcript arguments, the shared_transcript / d_transcripts pair of the _dev forms, malformed states, nbatch = 0 and
+ * BPGPU_VERDICT_UNDECIDED are those of bpgpu_opening_verify_*):
+ *   proof_len    : 32 (E + S); anything else is BPGPU_ERR_INVALID_ARG.
+ *   points       : nbatch x P x 32 bytes, slot order.      secrets : creation, nbatch x S x 32 bytes.
+ *   rng32        : creation, ONE 32-byte seed per row; NULL: the seeds come from the OS CSPRNG.  A SEED MUST NEVER SERVE TWO DIFFERENT
+ *                  STATEMENTS OR TRANSCRIPTS: two proofs with one nonce and different challenges give away the secrets.
+ *   status       : creation, nbatch bytes: BPGPU_MSM_OK; BPGPU_MSM_BAD_SCALAR for a secret that is not canonical; BPGPU_MSM_BAD_POINT
+ *                  for an instance BASE that does not decode.  Such a row walks like any other, its proof bytes are zero and its
+ *                  transcripts_out row is its input state; the other rows are unaffected.
+ *   msm_out      : optional nbatch x E x 32 bytes, compress of each equation's check (32 zero bytes where it holds or the row stopped).
+ *   weights64    : the combined forms, nbatch x E x 64 bytes (one weight per proof and equation) or NULL: drawn by the library.
+ *   nbatch (P + E) may not exceed 2^24 (the combined list): more is BPGPU_ERR_INVALID_ARG in every call of the family.
+ * Verdicts and transcripts_out of the verifiers:
+ *   an s_j that is not canonical                : FORMAT_ERROR,        the input state
+ *   a T_k of 32 zero bytes                      : VERIFICATION_ERROR,  the state as of that message
+ *   a point that does not decode, a failing check: VERIFICATION_ERROR, the state after c
+ *   a proof that verifies                       : OK,                  the state after c
+ * CONTRACTS (tests/test_gpu_sigma.py): (a) msm_out of (row, equation) equals bpgpu_msm_batch on that equation's terms with c from
+ * bpgpu_transcript_batch running the script; (b) verdict and transcripts_out of an _rlc_ts call ALWAYS equal those of the
+ * _verify_batch_ts call on the same inputs (the host form falls back to the per-proof path where the combination does not decide, the
+ * _dev form marks BPGPU_VERDICT_UNDECIDED); (c) a created proof verifies and both sides' transcripts_out are equal.
+ * Timing and secrets: creation is three launches (the per-lane variable-base products k P, the table walks with the encodings, the
+ * transcripts).  Its walks are variable time unless the context option "prover_constant_time" is set; then the shared bases take the
+ * W = 4 mask-select table and the product k P reads all 8 multiples of its point per window, selects by masks and applies the sign by
+ * mask -- the nonce is as secret as the witness; the same bytes.  Secrets and seeds are staged in the secret span: staging, the device
+ * IO buffer and the working sets are cleared on every exit.  The verifiers are variable time.  The context needs generators.
+ * Measured on one MI355X (profiles/sigma_rate.json; host pointers, one state per row, medians; DLEQ / one amount under two
+ * value bases): 65 536 rows -- _verify_rlc_ts 4.7 / 5.3 ms, _verify_batch_ts 15.4 / 16.2 ms, creation 5.1 / 6.0 ms, against 19.4 / 21.2 ms
+ * (verification) and 16.8 / 18.2 ms (creation) for bpgpu_transcript_batch + bpgpu_msm_batch on the same terms.  4 096 rows -- creation
+ * 1.43 / 2.15 ms is 7 % SLOWER than that route (1.34 / 2.01 ms), and at 64 rows 1.8 - 2.6 times slower: small batches are made faster the
+ * old way. */
+typedef struct bpgpu_sigma_relation bpgpu_sigma_relation;
+/* the validation of bpgpu_sigma_relation_create alone, on the host, against gens_capacity generators; digest (optional): the 32 bytes */
+int bpgpu_sigma_descriptor_check(const uint8_t *desc, size_t desc_len, size_t gens_capacity, uint8_t digest[32]);
+int bpgpu_sigma_relation_create(bpgpu_ctx *ctx, const uint8_t *desc, size_t desc_len, bpgpu_sigma_relation **out);
+void bpgpu_sigma_relation_destroy(bpgpu_sigma_relation *rel);
+int bpgpu_sigma_relation_shape(const bpgpu_sigma_relation *rel, size_t *S, size_t *P, size_t *E, uint8_t digest[32]);
+int bpgpu_sigma_create_batch_ts(bpgpu_ctx *ctx, const bpgpu_sigma_relation *rel, size_t nbatch, const uint8_t *transcripts,
+                                size_t transcript_stride, const uint8_t *rng32, const uint8_t *points, const uint8_t *secrets,
+                                uint8_t *proofs_out, uint8_t *status, uint8_t *transcripts_out);
+int bpgpu_sigma_verify_batch_ts(bpgpu_ctx *ctx, const bpgpu_sigma_relation *rel, size_t nbatch, const uint8_t *proofs, size_t proof_len,
+                                const uint8_t *transcripts, size_t transcript_stride, const uint8_t *points, uint8_t *verdict,
+                                uint8_t *msm_out, uint8_t *transcripts_out);
+int bpgpu_sigma_verify_batch_ts_dev(bpgpu_ctx *ctx, const bpgpu_sigma_relation *rel, size_t nbatch, const void *d_proofs,
+                                    size_t proof_len, const uint8_t *shared_transcript, const void *d_transcripts, const void *d_points,
+                                    void *d_verdict, void *d_msm_out, void *d_transcripts_out, void *stream);
+int bpgpu_sigma_verify_rlc_ts(bpgpu_ctx *ctx, const bpgpu_sigma_relation *rel, size_t nbatch, const uint8_t *proofs, size_t proof_len,
+                              const uint8_t *transcripts, size_t transcript_stride, const uint8_t *points, const uint8_t *weights64,
+                              uint8_t *verdict, uint8_t *batch_out, uint8_t *transcripts_out);
+int bpgpu_sigma_verify_rlc_ts_dev(bpgpu_ctx *ctx, const bpgpu_sigma_relation *rel, size_t nbatch, const void *d_proofs, size_t proof_len,
+                                  const uint8_t *shared_transcript, const void *d_transcripts, const void *d_points,
+                                  const void *d_weights64, void *d_verdict, void *d_batch_out, void *d_transcripts_out, void *stream);
+
 /* ---- the multi-party aggregation protocol: parties and dealer ------------------------------------
  * range_proof_mpc of the reference (src/range_proof/party.rs, dealer.rs, messages.rs; docs/aggregation-api.md) as six
  * batched, STATELESS calls: host pointers in and out, nothing retained after return.  bpgpu_rangeproof_prove_batch above

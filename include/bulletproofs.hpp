@@ -1262,5 +1262,199 @@ inline std::vector<Status> BulletproofGens::verify_balance_proved(const Rows &in
     return out;
 }
 
+// A linear relation between points, written once (no counterpart in the crate; the `zkp` crate's pattern next to it; the protocol is fixed
+// in include/bpgpu.h, bpgpu_sigma_*): secrets, instance points and equations  point = sum secret * base , where a base is B, B_blinding or
+// G(i) of bp_gens or another instance point.  compile() records it on the GPU context and returns the SigmaRelation that proves and
+// verifies batches.
+//     SigmaStatement st(gens); auto x = st.secret(); auto A = st.point(), H = st.point(), Bp = st.point();
+//     st.equation(A, {{x, st.B}}); st.equation(H, {{x, Bp}}); SigmaRelation dleq = st.compile();
+// At most 8 secrets, 8 points, 8 equations of 8 terms, 32 terms in all.  Public scalar coefficients are not part of a relation: fold them
+// into an instance point first (BulletproofGens::sum_commitments).
+// Canonical descriptor bytes: u8 S, u8 P, u8 E, then per equation u8 lhs, u8 nterms, then nterms x (u8 secret, u8 base); base ids
+// 0 = B_blinding, 1 = B, 2 + i = G_i, 16 + p = instance point p.
+// Transcript, on the caller's own state: append_message(b"dom-sep", b"sigmaproof v1"); append_message(b"stmt", digest);
+// append_point(b"P", P_i) in slot order; validate_and_append_point(b"T", T_k), k = 1 .. E; c = challenge_scalar(b"c").
+// A proof is T_1 | .. | T_E | s_1 | .. | s_S, 32 (E + S) bytes, s_j = k_j + c x_j.
+class SigmaRelation;
+class SigmaStatement {
+  public:
+    struct Secret {
+        uint8_t index;
+    };
+    struct Base {
+        uint8_t id;
+    };
+    const Base B_blinding{0}, B{1};
+    explicit SigmaStatement(const BulletproofGens &bp_gens) : gens_(bp_gens) {}
+    Secret secret() { return Secret{static_cast<uint8_t>(S_++)}; }
+    Base point() { return Base{static_cast<uint8_t>(16 + P_++)}; }
+    Base G(size_t i) const {
+        if (i >= 8) throw std::invalid_argument("G(i): i in 0 .. 7");
+        return Base{static_cast<uint8_t>(2 + i)};
+    }
+    void equation(Base lhs, const std::vector<std::pair<Secret, Base>> &terms) {
+        if (lhs.id < 16) throw std::invalid_argument("the left-hand side is an instance point (from point())");
+        eqs_.push_back({lhs.id, terms});
+    }
+    // the canonical bytes of include/bpgpu.h
+    std::vector<uint8_t> descriptor() const {
+        if (S_ > 255 || P_ > 239 || eqs_.size() > 255) throw std::invalid_argument("a relation has at most 8 secrets, 8 points and 8 equations of 8 terms");
+        std::vector<uint8_t> d{static_cast<uint8_t>(S_), static_cast<uint8_t>(P_), static_cast<uint8_t>(eqs_.size())};
+        for (const auto &e : eqs_) {
+            if (e.second.size() > 255) throw std::invalid_argument("a relation has at most 8 terms per equation");
+            d.push_back(e.first);
+            d.push_back(static_cast<uint8_t>(e.second.size()));
+            for (const auto &t : e.second) {
+                d.push_back(t.first.index);
+                d.push_back(t.second.id);
+            }
+        }
+        return d;
+    }
+    // throws std::invalid_argument for what bpgpu_sigma_relation_create refuses (a count out of range, an unused secret or point, a G(i)
+    // beyond the generators)
+    inline SigmaRelation compile() const;
+
+  private:
+    BulletproofGens gens_;
+    size_t S_ = 0, P_ = 0;
+    std::vector<std::pair<uint8_t, std::vector<std::pair<Secret, Base>>>> eqs_;
+};
+
+// A recorded relation (SigmaStatement::compile, or canonical descriptor bytes).  secrets: per row S scalars; points: per row P encodings,
+// slot order.  Transcripts: one per proof, each left advanced; a TranscriptBatch is left advanced as the vector would be.
+class SigmaRelation {
+  public:
+    using Proof = std::vector<uint8_t>;
+    using SecretRows = std::vector<std::vector<ScalarBytes>>;
+    using PointRows = std::vector<std::vector<CompressedRistretto>>;
+    SigmaRelation(const BulletproofGens &bp_gens, const std::vector<uint8_t> &descriptor) : gens_(bp_gens), descriptor_(descriptor) {
+        bpgpu_sigma_relation *r = nullptr;
+        const int rc = bpgpu_sigma_relation_create(gens_.ctx(), descriptor_.data(), descriptor_.size(), &r);
+        if (rc == BPGPU_ERR_INVALID_ARG) throw std::invalid_argument(bpgpu_last_error(gens_.ctx()));
+        if (rc != BPGPU_OK) throw GpuError(bpgpu_last_error(gens_.ctx()));
+        rel_.reset(r, bpgpu_sigma_relation_destroy);
+        bpgpu_sigma_relation_shape(r, &S_, &P_, &E_, digest_.data());
+    }
+    size_t secrets() const { return S_; }
+    size_t points() const { return P_; }
+    size_t equations() const { return E_; }
+    size_t proof_len() const { return 32 * (E_ + S_); }
+    const std::array<uint8_t, 32> &digest() const { return digest_; }
+    const std::vector<uint8_t> &descriptor() const { return descriptor_; }
+
+    // points.size() proofs (bpgpu_sigma_create_batch_ts).  rng_seed32: 32 bytes per row, row i's rng being ChaChaRng::from_seed(rng_seed32 + 32 i)
+    // (nullptr: the library draws the seeds) -- never one seed for two statements or transcripts.  Throws std::invalid_argument for a
+    // secret that is not canonical or an instance base that does not decode.
+    std::vector<Proof> create_batch(std::vector<Transcript> &transcripts, const SecretRows &secrets, const PointRows &points, const uint8_t *rng_seed32 = nullptr) const {
+        const size_t nb = points.size();
+        if (transcripts.size() != nb || secrets.size() != nb) throw std::invalid_argument("create_batch: one transcript and one row of secrets per row of points");
+        std::vector<Proof> out;
+        if (nb == 0) return out;
+        const std::vector<uint8_t> ts = states_of(transcripts), pts = pack(points, P_, "points"), xs = pack(secrets, S_, "secrets");
+        const size_t pl = proof_len();
+        std::vector<uint8_t> pb(nb * pl), status(nb), tso(nb * BPGPU_TRANSCRIPT_BYTES);
+        const int rc = bpgpu_sigma_create_batch_ts(gens_.ctx(), rel_.get(), nb, ts.data(), BPGPU_TRANSCRIPT_BYTES, rng_seed32, pts.data(), xs.data(), pb.data(),
+                                                   status.data(), tso.data());
+        if (rc != BPGPU_OK) throw GpuError(bpgpu_last_error(gens_.ctx()));
+        for (uint8_t s : status)
+            if (s != 0) throw std::invalid_argument(s == 2 ? "create_batch: secrets must be canonical" : "create_batch: an instance base does not decode");
+        for (size_t i = 0; i < nb; i++) {
+            std::memcpy(transcripts[i].state_mut().data(), &tso[i * BPGPU_TRANSCRIPT_BYTES], BPGPU_TRANSCRIPT_BYTES);
+            out.emplace_back(pb.begin() + i * pl, pb.begin() + (i + 1) * pl);
+        }
+        return out;
+    }
+    // every proof on its own (bpgpu_sigma_verify_batch_ts)
+    std::vector<Status> verify_batch(std::vector<Transcript> &transcripts, const std::vector<Proof> &proofs, const PointRows &points) const {
+        return verify_rows(transcripts, proofs, points, false, nullptr);
+    }
+    // the same verdicts through ONE combined check (bpgpu_sigma_verify_rlc_ts): one multiscalar multiplication over P + E points per proof
+    // when every proof verifies, per-proof re-verification inside the call when not.  weights64: 64 bytes per (proof, equation),
+    // unpredictable to the provers, or nullptr (drawn by the library)
+    std::vector<Status> verify_batch_combined(std::vector<Transcript> &transcripts, const std::vector<Proof> &proofs, const PointRows &points,
+                                              const uint8_t *weights64 = nullptr) const {
+        return verify_rows(transcripts, proofs, points, true, weights64);
+    }
+    std::vector<Proof> create_batch(TranscriptBatch &transcripts, const SecretRows &secrets, const PointRows &points, const uint8_t *rng_seed32 = nullptr) const {
+        std::vector<Transcript> ts = transcripts.to_transcripts();
+        std::vector<Proof> out = create_batch(ts, secrets, points, rng_seed32);
+        transcripts.assign(ts);
+        return out;
+    }
+    std::vector<Status> verify_batch(TranscriptBatch &transcripts, const std::vector<Proof> &proofs, const PointRows &points) const {
+        std::vector<Transcript> ts = transcripts.to_transcripts();
+        std::vector<Status> out = verify_rows(ts, proofs, points, false, nullptr);
+        transcripts.assign(ts);
+        return out;
+    }
+    std::vector<Status> verify_batch_combined(TranscriptBatch &transcripts, const std::vector<Proof> &proofs, const PointRows &points,
+                                              const uint8_t *weights64 = nullptr) const {
+        std::vector<Transcript> ts = transcripts.to_transcripts();
+        std::vector<Status> out = verify_rows(ts, proofs, points, true, weights64);
+        transcripts.assign(ts);
+        return out;
+    }
+    // one proof; the transcript is left advanced
+    Proof create(Transcript &transcript, const std::vector<ScalarBytes> &secrets, const std::vector<CompressedRistretto> &points, const uint8_t *rng_seed32 = nullptr) const {
+        std::vector<Transcript> ts{transcript};
+        Proof p = create_batch(ts, SecretRows{secrets}, PointRows{points}, rng_seed32)[0];
+        transcript = ts[0];
+        return p;
+    }
+    Status verify(Transcript &transcript, const Proof &proof, const std::vector<CompressedRistretto> &points) const {
+        std::vector<Transcript> ts{transcript};
+        const Status st = verify_rows(ts, {proof}, PointRows{points}, false, nullptr)[0];
+        transcript = ts[0];
+        return st;
+    }
+
+  private:
+    static std::vector<uint8_t> states_of(const std::vector<Transcript> &transcripts) {
+        std::vector<uint8_t> ts;
+        for (const Transcript &t : transcripts) ts.insert(ts.end(), t.state().begin(), t.state().end());
+        return ts;
+    }
+    template <class T>
+    static std::vector<uint8_t> pack(const std::vector<std::vector<T>> &rows, size_t per_row, const char *what) {
+        std::vector<uint8_t> out;
+        for (const auto &row : rows) {
+            if (row.size() != per_row) throw std::invalid_argument(std::string("wrong number of ") + what + " in a row");
+            for (const T &x : row) out.insert(out.end(), x.begin(), x.end());
+        }
+        return out;
+    }
+    std::vector<Status> verify_rows(std::vector<Transcript> &transcripts, const std::vector<Proof> &proofs, const PointRows &points, bool combined,
+                                    const uint8_t *weights64) const {
+        const size_t nb = proofs.size(), pl = proof_len();
+        std::vector<Status> out;
+        if (transcripts.size() != nb || points.size() != nb) throw std::invalid_argument("one transcript and one row of points per proof");
+        if (nb == 0) return out;
+        const std::vector<uint8_t> ts = states_of(transcripts), pts = pack(points, P_, "points");
+        std::vector<uint8_t> pb, verdict(nb), tso(nb * BPGPU_TRANSCRIPT_BYTES);
+        for (const Proof &p : proofs) {
+            if (p.size() != pl) throw std::invalid_argument("a proof of this relation has 32 (E + S) bytes");
+            pb.insert(pb.end(), p.begin(), p.end());
+        }
+        bpgpu_ctx *ctx = gens_.ctx();
+        const int rc = combined ? bpgpu_sigma_verify_rlc_ts(ctx, rel_.get(), nb, pb.data(), pl, ts.data(), BPGPU_TRANSCRIPT_BYTES, pts.data(), weights64, verdict.data(),
+                                                            nullptr, tso.data())
+                                : bpgpu_sigma_verify_batch_ts(ctx, rel_.get(), nb, pb.data(), pl, ts.data(), BPGPU_TRANSCRIPT_BYTES, pts.data(), verdict.data(), nullptr,
+                                                              tso.data());
+        if (rc != BPGPU_OK) throw GpuError(bpgpu_last_error(ctx));
+        for (size_t i = 0; i < nb; i++) {
+            std::memcpy(transcripts[i].state_mut().data(), &tso[i * BPGPU_TRANSCRIPT_BYTES], BPGPU_TRANSCRIPT_BYTES);
+            out.push_back(verdict[i] == 0 ? Status::Ok() : Status::Err(static_cast<ProofError>(verdict[i])));
+        }
+        return out;
+    }
+    BulletproofGens gens_;   // (a copy: it shares the context and keeps it alive as long as the relation)
+    std::vector<uint8_t> descriptor_;
+    std::shared_ptr<bpgpu_sigma_relation> rel_;
+    size_t S_ = 0, P_ = 0, E_ = 0;
+    std::array<uint8_t, 32> digest_{};
+};
+inline SigmaRelation SigmaStatement::compile() const { return SigmaRelation(gens_, descriptor()); }
+
 }  // namespace bulletproofs
 #endif

@@ -11,7 +11,8 @@ import sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 TYPES = {"int": "c_int", "size_t": "usize", "uint8_t": "u8", "uint32_t": "u32", "uint64_t": "u64", "int64_t": "i64", "char": "c_char", "void": "c_void",
          "bpgpu_ctx": "bpgpu_ctx", "bpgpu_pool": "bpgpu_pool", "bpgpu_ticket": "bpgpu_ticket",
-         "bpgpu_r1cs_circuit": "bpgpu_r1cs_circuit", "bpgpu_r1cs_witness": "bpgpu_r1cs_witness", "bpgpu_ts_op": "bpgpu_ts_op"}
+         "bpgpu_r1cs_circuit": "bpgpu_r1cs_circuit", "bpgpu_r1cs_witness": "bpgpu_r1cs_witness", "bpgpu_ts_op": "bpgpu_ts_op",
+         "bpgpu_sigma_relation": "bpgpu_sigma_relation"}
 
 
 def prototypes(text):
