@@ -264,6 +264,13 @@ static hipEvent_t get_event(bpgpu_ctx *c) {
         }                                                                                                   \
     } while (0)
 
+// a kernel template with a constant-time form: kern<true> under the name `name "_ct"`, kern<false> under `name`, the same arguments
+#define LAUNCH_CT(c, s, ct, name, kern, grid, block, ...)                          \
+    do {                                                                           \
+        if (ct) LAUNCH(c, s, name "_ct", kern<true>, grid, block, __VA_ARGS__);    \
+        else LAUNCH(c, s, name, kern<false>, grid, block, __VA_ARGS__);            \
+    } while (0)
+
 static void drain_profile(bpgpu_ctx *c) {
     for (auto &t : c->pending) {
         hipEventSynchronize(std::get<2>(t));
@@ -855,6 +862,20 @@ static int build_ct_table(bpgpu_ctx *c) {
     c->prm_ct = prm;
     return BPGPU_OK;
 }
+// the window tables a launch walks and their parameters: the context's, or -- ct -- the constant-time path's, built on first use
+struct fb_walk {
+    fb_params prm;
+    const fb_entry *table;
+};
+static int fb_walk_for(bpgpu_ctx *c, bool ct, fb_walk &w) {
+    if (ct) {
+        const int rc = build_ct_table(c);
+        if (rc) return rc;
+    }
+    w.prm = ct ? c->prm_ct : c->prm;
+    w.table = ct ? c->d_table_ct : c->d_table;
+    return BPGPU_OK;
+}
 
 static int load_gens_locked(bpgpu_ctx *c, size_t gens_capacity, size_t party_capacity, const uint8_t *G, const uint8_t *H,
                             const uint8_t *B, const uint8_t *Bb) {
@@ -1376,17 +1397,15 @@ static int msm_batch_dev_locked(bpgpu_ctx *c, size_t nbatch, const uint32_t *n_t
 extern "C" int bpgpu_msm_batch_dev(bpgpu_ctx *c, size_t nbatch, const uint32_t *n_terms, const void *d_scalars, const void *d_points,
                                    void *d_out, void *d_status, void *stream) {
     if (!c || (nbatch && (!n_terms || !d_out || !d_status))) return BPGPU_ERR_INVALID_ARG;
-    std::lock_guard<std::mutex> lk(c->mu);
-    HIPCHK(c, hipSetDevice(c->device));
-    uint64_t total = 0;
-    for (size_t b = 0; b < nbatch; b++) total += n_terms[b];
-    if (nbatch > 0x7fffffffu / 64 || total > 0x7fffffffu / 64) return fail(c, BPGPU_ERR_INVALID_ARG, "batch too large");
-    hipStream_t s = stream ? (hipStream_t)stream : c->stream;
-    int rc = ctx_enter(c, s);
-    if (rc) return rc;
-    rc = msm_batch_dev_locked(c, nbatch, n_terms, d_scalars, d_points, d_out, d_status, s);
-    const int rc2 = ctx_leave(c, s);
-    return rc ? rc : rc2;
+    return dev_call(
+        c, stream,
+        [&] {
+            uint64_t total = 0;
+            for (size_t b = 0; b < nbatch; b++) total += n_terms[b];
+            if (nbatch > 0x7fffffffu / 64 || total > 0x7fffffffu / 64) return fail(c, BPGPU_ERR_INVALID_ARG, "batch too large");
+            return BPGPU_OK;
+        },
+        [&](hipStream_t s) { return msm_batch_dev_locked(c, nbatch, n_terms, d_scalars, d_points, d_out, d_status, s); });
 }
 
 extern "C" int bpgpu_msm_batch(bpgpu_ctx *c, size_t nbatch, const uint32_t *n_terms, const uint8_t *scalars, const uint8_t *points,
@@ -1635,14 +1654,9 @@ extern "C" int bpgpu_msm_batch_shared_dev(bpgpu_ctx *c, size_t n, size_t m, size
                                           void *stream) {
     if (!c || (nbatch && (!d_gen_scalars || !d_out || !d_status))) return BPGPU_ERR_INVALID_ARG;
     if (n_unique && (!d_uniq_scalars || !d_uniq_points)) return BPGPU_ERR_INVALID_ARG;
-    std::lock_guard<std::mutex> lk(c->mu);
-    HIPCHK(c, hipSetDevice(c->device));
-    hipStream_t s = stream ? (hipStream_t)stream : c->stream;
-    int rc = ctx_enter(c, s);
-    if (rc) return rc;
-    rc = msm_shared_dev_locked(c, n, m, nbatch, n_unique, d_gen_scalars, d_uniq_scalars, d_uniq_points, d_out, d_status, nullptr, s);
-    const int rc2 = ctx_leave(c, s);
-    return rc ? rc : rc2;
+    return dev_call(c, stream, [&](hipStream_t s) {
+        return msm_shared_dev_locked(c, n, m, nbatch, n_unique, d_gen_scalars, d_uniq_scalars, d_uniq_points, d_out, d_status, nullptr, s);
+    });
 }
 
 extern "C" int bpgpu_msm_batch_shared(bpgpu_ctx *c, size_t n, size_t m, size_t nbatch, size_t n_unique, const uint8_t *gen_scalars,
@@ -2431,15 +2445,10 @@ static int rp_dev_call(bpgpu_ctx *c, size_t n, size_t m, size_t nbatch, const vo
     if (!c || (nbatch && (!d_proofs || !d_verdict || (m && !d_commitments))) || (tr.label_len && !tr.label)) return BPGPU_ERR_INVALID_ARG;
     if (((uintptr_t)d_proofs | (uintptr_t)d_commitments | (uintptr_t)d_rng64 | (uintptr_t)d_weights64 | (uintptr_t)tr.d_ts_in | (uintptr_t)tr.d_ts_out) & 3)
         return fail(c, BPGPU_ERR_INVALID_ARG, "device buffers must be 4-byte aligned");
-    std::lock_guard<std::mutex> lk(c->mu);
-    HIPCHK(c, hipSetDevice(c->device));
-    hipStream_t s = stream ? (hipStream_t)stream : c->stream;
-    int rc = ctx_enter(c, s);
-    if (rc) return rc;
-    rc = rp_verify_dev_locked(c, n, m, nbatch, d_proofs, proof_len, d_commitments, tr, d_rng64, d_verdict, d_msm_out, s, rlc, d_weights64, d_batch_out,
-                              nullptr, 0, true);
-    const int rc2 = ctx_leave(c, s);
-    return rc ? rc : rc2;
+    return dev_call(c, stream, [&](hipStream_t s) {
+        return rp_verify_dev_locked(c, n, m, nbatch, d_proofs, proof_len, d_commitments, tr, d_rng64, d_verdict, d_msm_out, s, rlc, d_weights64, d_batch_out,
+                                  nullptr, 0, true);
+    });
 }
 
 // ---- hooks of the pool (pool.hip; not part of the C ABI) -----------------------------------------------------
@@ -2476,24 +2485,20 @@ int bpgpu_internal_rp_verify_segs(bpgpu_ctx *c, size_t n, size_t m, size_t proof
     const size_t total = (size_t)segs[nseg - 1].first + segs[nseg - 1].count;
     bool any_rng_missing = false;
     for (uint32_t i = 0; i < nseg; i++) any_rng_missing = any_rng_missing || !segs[i].rng64;
-    std::lock_guard<std::mutex> lk(c->mu);
-    HIPCHK(c, hipSetDevice(c->device));
-    hipStream_t s = c->stream;
-    int rc = ctx_enter(c, s);
-    if (rc) return rc;
-    rp_transcripts tr;
-    tr.label = label;
-    tr.label_len = label_len;
-    tr.seg_labels = labels;
-    c->splits_hint = splits_hint;
-    c->busy_hint = busy;
-    // d_rng64: a non-null dummy keeps the library from drawing randomness nobody reads (every item brought its own)
-    rc = rp_verify_dev_locked(c, n, m, total, nullptr, proof_len, nullptr, tr, any_rng_missing ? nullptr : (const void *)segs[0].rng64, nullptr,
-                              (any_msm && !rlc) ? (void *)segs : nullptr, s, rlc, nullptr, (any_msm && rlc) ? (void *)segs : nullptr, segs, nseg, true);
-    c->splits_hint = 0;
-    c->busy_hint = -1;
-    const int rc2 = ctx_leave(c, s);
-    return rc ? rc : rc2;
+    return dev_call(c, nullptr, [&](hipStream_t s) {   // (no stream: the context's own)
+        rp_transcripts tr;
+        tr.label = label;
+        tr.label_len = label_len;
+        tr.seg_labels = labels;
+        c->splits_hint = splits_hint;
+        c->busy_hint = busy;
+        // d_rng64: a non-null dummy keeps the library from drawing randomness nobody reads (every item brought its own)
+        const int rc = rp_verify_dev_locked(c, n, m, total, nullptr, proof_len, nullptr, tr, any_rng_missing ? nullptr : (const void *)segs[0].rng64, nullptr,
+                                            (any_msm && !rlc) ? (void *)segs : nullptr, s, rlc, nullptr, (any_msm && rlc) ? (void *)segs : nullptr, segs, nseg, true);
+        c->splits_hint = 0;
+        c->busy_hint = -1;
+        return rc;
+    });
 }
 // buffers of the context sized for chains of up to `nbatch_max` proofs of this shape (see rp_verify_dev_locked, reserve_only)
 int bpgpu_internal_rp_reserve(bpgpu_ctx *c, size_t n, size_t m, size_t proof_len, size_t nbatch_max) {
@@ -2516,26 +2521,22 @@ int bpgpu_internal_rp_verify_chain(bpgpu_ctx *c, size_t n, size_t m, size_t nbat
                                    const uint8_t *shared_ts, const void *d_ts_in, void *d_ts_out, int ts_uniform, uint32_t pos, uint32_t pos_begin,
                                    uint32_t flags, const void *d_rng64, void *d_verdict, void *d_msm_out, uint32_t splits_hint, int busy) {
     if (!c || !d_proofs || !d_verdict || !d_rng64 || (shared_ts == nullptr) == (d_ts_in == nullptr)) return BPGPU_ERR_INVALID_ARG;
-    std::lock_guard<std::mutex> lk(c->mu);
-    HIPCHK(c, hipSetDevice(c->device));
-    hipStream_t s = c->stream;
-    int rc = ctx_enter(c, s);
-    if (rc) return rc;
-    rp_transcripts tr;
-    tr.shared_ts = shared_ts;
-    tr.d_ts_in = d_ts_in;
-    tr.d_ts_out = d_ts_out;
-    tr.ts_uniform = d_ts_in && ts_uniform;
-    tr.u_pos = pos;
-    tr.u_pos_begin = pos_begin;
-    tr.u_flags = flags;
-    c->splits_hint = splits_hint;
-    c->busy_hint = busy;
-    rc = rp_verify_dev_locked(c, n, m, nbatch, d_proofs, proof_len, d_commitments, tr, d_rng64, d_verdict, d_msm_out, s, false, nullptr, nullptr, nullptr, 0, true);
-    c->splits_hint = 0;
-    c->busy_hint = -1;
-    const int rc2 = ctx_leave(c, s);
-    return rc ? rc : rc2;
+    return dev_call(c, nullptr, [&](hipStream_t s) {   // (no stream: the context's own)
+        rp_transcripts tr;
+        tr.shared_ts = shared_ts;
+        tr.d_ts_in = d_ts_in;
+        tr.d_ts_out = d_ts_out;
+        tr.ts_uniform = d_ts_in && ts_uniform;
+        tr.u_pos = pos;
+        tr.u_pos_begin = pos_begin;
+        tr.u_flags = flags;
+        c->splits_hint = splits_hint;
+        c->busy_hint = busy;
+        const int rc = rp_verify_dev_locked(c, n, m, nbatch, d_proofs, proof_len, d_commitments, tr, d_rng64, d_verdict, d_msm_out, s, false, nullptr, nullptr, nullptr, 0, true);
+        c->splits_hint = 0;
+        c->busy_hint = -1;
+        return rc;
+    });
 }
 
 extern "C" int bpgpu_rangeproof_verify_batch_dev(bpgpu_ctx *c, size_t n, size_t m, size_t nbatch, const void *d_proofs, size_t proof_len,
@@ -2619,15 +2620,16 @@ static int rp_host_call(bpgpu_ctx *c, size_t n, size_t m, size_t nbatch, const u
     }
     rc = io.finish(rc);
     if (rc) return rc;
-    if (rlc && (uint8_t)io.h(r_b)[0] != 0) {
-        // the combination is not the identity: some proof fails -- find out which, proof by proof (inputs are still on the device)
-        rc = io.rerun_per_proof(r_v, r_b, [&] { return rp_verify_dev_locked(c, n, m, nbatch, io.d(r_p), proof_len, io.d(r_c), tr, d_rng, io.d(r_v), nullptr, s); });
+    if (rlc) {
+        // where the combination is not the identity some proof fails: find out which, proof by proof (inputs are still on the device)
+        rc = io.deliver_combined(r_v, verdict, nbatch, r_b, batch_out, r_to, ts_out_host, nbatch * TS,
+                                 [&] { return rp_verify_dev_locked(c, n, m, nbatch, io.d(r_p), proof_len, io.d(r_c), tr, d_rng, io.d(r_v), nullptr, s); });
         if (rc) return rc;
+    } else {
+        memcpy(verdict, io.h(r_v), nbatch);
+        if (ts_out_host) memcpy(ts_out_host, io.h(r_to), nbatch * TS);
     }
-    memcpy(verdict, io.h(r_v), nbatch);
     if (msm_out) memcpy(msm_out, io.h(r_o), nbatch * 32);
-    if (rlc && batch_out) memcpy(batch_out, io.h(r_b), 33);
-    if (ts_out_host) memcpy(ts_out_host, io.h(r_to), nbatch * TS);
     return BPGPU_OK;
 }
 
@@ -2699,6 +2701,23 @@ static int ipp_reserve(bpgpu_ctx *c, size_t need) {
     c->ipp_cap = need + need / 4;
     return BPGPU_OK;
 }
+// what a front end leaves there for the multiscalar multiplication(s): the unique terms' scalars and points, the generator-table rows, its
+// own status words, then the status bytes and the results of the multiplication(s)
+struct front_staged {
+    char *d_sc = nullptr, *d_pt = nullptr, *d_gen = nullptr, *d_stat = nullptr, *d_mst = nullptr, *d_out = nullptr;
+    size_t sz_b = 0, sz_o = 0;   // the widths of d_mst and d_out
+};
+// ... carved in that order (the term lists `terms` bytes each), everything the front end writes zeroed: scalars, points, generator rows, status
+static int front_stage_locked(bpgpu_ctx *c, hipStream_t s, size_t terms, size_t gen, size_t stat, size_t mst, size_t out, front_staged &stg) {
+    const size_t sz_terms = align_up(terms), sz_gen = align_up(gen), sz_st = align_up(stat);
+    stg.sz_b = align_up(mst), stg.sz_o = align_up(out);
+    const int rc = ipp_reserve(c, 2 * sz_terms + sz_gen + sz_st + stg.sz_b + stg.sz_o);
+    if (rc) return rc;
+    stg.d_sc = c->ipp_buf, stg.d_pt = stg.d_sc + sz_terms, stg.d_gen = stg.d_pt + sz_terms, stg.d_stat = stg.d_gen + sz_gen, stg.d_mst = stg.d_stat + sz_st,
+    stg.d_out = stg.d_mst + stg.sz_b;
+    HIPCHK(c, hipMemsetAsync(stg.d_sc, 0, 2 * sz_terms + sz_gen + sz_st, s));
+    return BPGPU_OK;
+}
 
 // Transcript::new(label) [or the caller's 208-byte state] followed by innerproduct_domain_sep(n) (transcript.rs:50-53): the
 // batch-invariant prefix of the stand-alone inner-product and linear proofs, replayed once on the host
@@ -2741,6 +2760,13 @@ static int ipp_ts_host_args(bpgpu_ctx *c, const uint8_t *transcripts, size_t tra
     for (size_t b = 0; b < (transcript_stride ? nbatch : 1); b++)
         if (!ts_state_ok(transcripts + b * BPGPU_TRANSCRIPT_BYTES)) return fail(c, BPGPU_ERR_INVALID_ARG, "malformed transcript state %zu", b);
     return BPGPU_OK;
+}
+// ... and the staged copy as the kernels take it
+static ipp_ts ipp_ts_staged(const void *d_in, size_t transcript_stride) {
+    ipp_ts ts;
+    ts.d_in = d_in;
+    ts.stride = transcript_stride ? BP_TS_WORDS : 0;
+    return ts;
 }
 // ... and of the _dev forms: one checked host state or nbatch device states (which the lanes guard themselves)
 static int ipp_ts_dev_args(bpgpu_ctx *c, const uint8_t *shared_transcript, const void *d_transcripts, const void *d_transcripts_out, ipp_ts &ts) {
@@ -2835,15 +2861,10 @@ extern "C" int bpgpu_ipp_verify_batch_dev(bpgpu_ctx *c, size_t n, size_t nbatch,
     if (!d_proofs || !d_verdict || !d_P || !d_Q || (n && (!d_G_factors || !d_H_factors || !d_G || !d_H))) return BPGPU_ERR_INVALID_ARG;
     if (((uintptr_t)d_proofs | (uintptr_t)d_G_factors | (uintptr_t)d_H_factors | (uintptr_t)d_P | (uintptr_t)d_Q | (uintptr_t)d_G | (uintptr_t)d_H) & 3)
         return fail(c, BPGPU_ERR_INVALID_ARG, "device buffers must be 4-byte aligned");
-    std::lock_guard<std::mutex> lk(c->mu);
-    HIPCHK(c, hipSetDevice(c->device));
-    hipStream_t s = stream ? (hipStream_t)stream : c->stream;
-    int rc = ctx_enter(c, s);
-    if (rc) return rc;
-    rc = ipp_verify_dev_locked(c, n, nbatch, d_proofs, proof_len, label, label_len, shared_transcript, d_G_factors, d_H_factors, d_P, d_Q, d_G, d_H,
-                               bases_shared, d_verdict, d_msm_out, s);
-    const int rc2 = ctx_leave(c, s);
-    return rc ? rc : rc2;
+    return dev_call(c, stream, [&](hipStream_t s) {
+        return ipp_verify_dev_locked(c, n, nbatch, d_proofs, proof_len, label, label_len, shared_transcript, d_G_factors, d_H_factors, d_P, d_Q, d_G, d_H,
+                                   bases_shared, d_verdict, d_msm_out, s);
+    });
 }
 
 // InnerProductProof::from_bytes + verification_scalars (ipp.rs:198-253, 373-407) for nbatch proofs, host pointers
@@ -3022,25 +3043,19 @@ extern "C" int bpgpu_ipp_verify_batch_ts_dev(bpgpu_ctx *c, size_t n, size_t nbat
     if (!d_proofs || !d_verdict || !d_P || !d_Q || (n && (!d_G_factors || !d_H_factors || !d_G || !d_H))) return BPGPU_ERR_INVALID_ARG;
     if (((uintptr_t)d_proofs | (uintptr_t)d_G_factors | (uintptr_t)d_H_factors | (uintptr_t)d_P | (uintptr_t)d_Q | (uintptr_t)d_G | (uintptr_t)d_H) & 3)
         return fail(c, BPGPU_ERR_INVALID_ARG, "device buffers must be 4-byte aligned");
-    std::lock_guard<std::mutex> lk(c->mu);
-    HIPCHK(c, hipSetDevice(c->device));
-    hipStream_t s = stream ? (hipStream_t)stream : c->stream;
-    int rc = ctx_enter(c, s);
-    if (rc) return rc;
-    rc = ipp_verify_dev_locked(c, n, nbatch, d_proofs, proof_len, nullptr, 0, nullptr, d_G_factors, d_H_factors, d_P, d_Q, d_G, d_H, bases_shared, d_verdict,
-                               d_msm_out, s, &ts);
-    const int rc2 = ctx_leave(c, s);
-    return rc ? rc : rc2;
+    return dev_call(c, stream, [&](hipStream_t s) {
+        return ipp_verify_dev_locked(c, n, nbatch, d_proofs, proof_len, nullptr, 0, nullptr, d_G_factors, d_H_factors, d_P, d_Q, d_G, d_H, bases_shared, d_verdict,
+                                   d_msm_out, s, &ts);
+    });
 }
 
-// what the front end of a LinearProof batch leaves on the device (c->ipp_buf) for its multiscalar multiplication(s)
-struct lin_staged {
+// what the front end of a LinearProof batch leaves on the device (c->ipp_buf) for its multiscalar multiplication(s): its own order
+// (the generator rows last, and only in generator-table mode)
+struct lin_staged : front_staged {
     lin_shape sh;
     bool fmt = false;     // proof_len is not a LinearProof length: nothing was launched, every proof is a FormatError
     bool fixed = false;   // generator-table mode
-    char *d_sc = nullptr, *d_pt = nullptr, *d_stat = nullptr, *d_mst = nullptr, *d_out = nullptr, *d_gen = nullptr;
     const void *d_G = nullptr, *d_F = nullptr, *d_B = nullptr;   // the bases in use (the context's generators in generator-table mode)
-    size_t sz_b = 0, sz_o = 0;
 };
 
 // LinearProof::from_bytes' length part, the staging and the k_lin_prepare launch (lane = proof) of nbatch proofs
@@ -3168,15 +3183,10 @@ extern "C" int bpgpu_linear_verify_batch_dev(bpgpu_ctx *c, size_t n, size_t nbat
     if (!d_proofs || !d_verdict || !d_C || (n && !d_b) || (!from_gens && (!d_F || !d_B || (n && !d_G)))) return BPGPU_ERR_INVALID_ARG;
     if (((uintptr_t)d_proofs | (uintptr_t)d_C | (uintptr_t)d_G | (uintptr_t)d_F | (uintptr_t)d_B | (uintptr_t)d_b | (uintptr_t)d_transcripts_out) & 3)
         return fail(c, BPGPU_ERR_INVALID_ARG, "device buffers must be 4-byte aligned");
-    std::lock_guard<std::mutex> lk(c->mu);
-    HIPCHK(c, hipSetDevice(c->device));
-    hipStream_t s = stream ? (hipStream_t)stream : c->stream;
-    int rc = ctx_enter(c, s);
-    if (rc) return rc;
-    rc = lin_verify_dev_locked(c, n, nbatch, d_proofs, proof_len, label, label_len, shared_transcript, d_C, d_G, d_F, d_B, d_b, b_shared, d_verdict,
-                               d_msm_out, d_transcripts_out, s);
-    const int rc2 = ctx_leave(c, s);
-    return rc ? rc : rc2;
+    return dev_call(c, stream, [&](hipStream_t s) {
+        return lin_verify_dev_locked(c, n, nbatch, d_proofs, proof_len, label, label_len, shared_transcript, d_C, d_G, d_F, d_B, d_b, b_shared, d_verdict,
+                                   d_msm_out, d_transcripts_out, s);
+    });
 }
 
 // host pointers.  ts_host (with ts_stride 0 or BPGPU_TRANSCRIPT_BYTES): the callers' own transcripts, checked by the caller, in place of label /
@@ -3261,15 +3271,10 @@ extern "C" int bpgpu_linear_verify_batch_ts_dev(bpgpu_ctx *c, size_t n, size_t n
     if (!d_proofs || !d_verdict || !d_C || (n && !d_b) || (!from_gens && (!d_F || !d_B || (n && !d_G)))) return BPGPU_ERR_INVALID_ARG;
     if (((uintptr_t)d_proofs | (uintptr_t)d_C | (uintptr_t)d_G | (uintptr_t)d_F | (uintptr_t)d_B | (uintptr_t)d_b) & 3)
         return fail(c, BPGPU_ERR_INVALID_ARG, "device buffers must be 4-byte aligned");
-    std::lock_guard<std::mutex> lk(c->mu);
-    HIPCHK(c, hipSetDevice(c->device));
-    hipStream_t s = stream ? (hipStream_t)stream : c->stream;
-    int rc = ctx_enter(c, s);
-    if (rc) return rc;
-    rc = lin_verify_dev_locked(c, n, nbatch, d_proofs, proof_len, nullptr, 0, nullptr, d_C, d_G, d_F, d_B, d_b, b_shared, d_verdict, d_msm_out, d_transcripts_out,
-                               s, &ts);
-    const int rc2 = ctx_leave(c, s);
-    return rc ? rc : rc2;
+    return dev_call(c, stream, [&](hipStream_t s) {
+        return lin_verify_dev_locked(c, n, nbatch, d_proofs, proof_len, nullptr, 0, nullptr, d_C, d_G, d_F, d_B, d_b, b_shared, d_verdict, d_msm_out, d_transcripts_out,
+                                   s, &ts);
+    });
 }
 
 // ProofShare::audit_share for nshares shares of bitsize n (audit.h): front end (lane = share) -> the ragged (2n + 3, 5) pairs of
@@ -3969,12 +3974,12 @@ static int rpp_ts_dev_call(bpgpu_ctx *c, size_t n, size_t m, size_t nbatch, cons
     if (((uintptr_t)d_values & 7) || (((uintptr_t)d_blindings | (uintptr_t)d_transcripts | (uintptr_t)d_rng32 | (uintptr_t)d_proofs_out | (uintptr_t)d_commitments_out |
                                        (uintptr_t)d_transcripts_out | (uintptr_t)d_messages) & 3))
         return fail(c, BPGPU_ERR_INVALID_ARG, "device buffers must be 4-byte aligned (values: 8-byte)");
-    std::lock_guard<std::mutex> lk(c->mu);
-    HIPCHK(c, hipSetDevice(c->device));
+    dev_scope<bpgpu_ctx> sc(c);
+    if (sc.rc) return sc.rc;
     rpp_shape sh;
     if ((rc = rpp_shape_locked(c, n, m, nbatch, nullptr, sh))) return rc;
-    hipStream_t s = stream ? (hipStream_t)stream : c->stream;
-    if ((rc = ctx_enter(c, s))) return rc;
+    if ((rc = sc.enter(stream))) return rc;
+    hipStream_t s = sc.s;
     char *h_seeds = nullptr;
     if (!d_rng32) {   // the library's own seeds: drawn into pinned staging, copied by the chain into its working set
         rc = c->io.pin_alloc(nbatch * 32, &h_seeds);
@@ -3994,7 +3999,7 @@ static int rpp_ts_dev_call(bpgpu_ctx *c, size_t n, size_t m, size_t nbatch, cons
     bool ok = true;
     for (const dev_span &x : b)
         if (x.p) ok = hipMemsetAsync(x.p, 0, x.bytes, s) == hipSuccess && ok;
-    const int rc2 = ctx_leave(c, s);
+    const int rc2 = sc.leave();
     if (h_seeds) {   // (the chain has waited until the seeds had left the staging block: the one wait of this form)
         memset(h_seeds, 0, nbatch * 32);
         c->io.last_secret_bytes = (h_seeds == c->io.pin) ? nbatch * 32 : 0;
@@ -4039,7 +4044,8 @@ static int ped_launch_locked(bpgpu_ctx *c, hipStream_t s, size_t nbatch, const v
     int rc = gen_ids_for(c, 1, 1, &d_ids);   // the shared path's list: [0] = B_blinding, [1] = B
     if (rc) return rc;
     const bool ct = !d_commitments_in && c->prover_ct;
-    if (ct && (rc = build_ct_table(c))) return rc;
+    fb_walk w;
+    if ((rc = fb_walk_for(c, ct, w))) return rc;
     ped_in in;
     in.values = (const uint32_t *)d_values;
     in.value_words = (uint32_t)(value_bytes / 4);
@@ -4050,12 +4056,9 @@ static int ped_launch_locked(bpgpu_ctx *c, hipStream_t s, size_t nbatch, const v
     if (d_commitments_in)
         LAUNCH(c, s, "ped_open", k_ped_open, grid, BP_BLOCK, nb, in, (const uint32_t *)d_commitments_in, c->prm, (const uint32_t *)d_ids, (const fb_entry *)c->d_table,
                (uint8_t *)d_out);
-    else if (ct)
-        LAUNCH(c, s, "ped_commit_ct", k_ped_commit<true>, grid, BP_BLOCK, nb, in, c->prm_ct, (const uint32_t *)d_ids, (const fb_entry *)c->d_table_ct, (uint32_t *)d_out,
-               (uint32_t *)d_blindings_out, (uint8_t *)d_status);
     else
-        LAUNCH(c, s, "ped_commit", k_ped_commit<false>, grid, BP_BLOCK, nb, in, c->prm, (const uint32_t *)d_ids, (const fb_entry *)c->d_table, (uint32_t *)d_out,
-               (uint32_t *)d_blindings_out, (uint8_t *)d_status);
+        LAUNCH_CT(c, s, ct, "ped_commit", k_ped_commit, grid, BP_BLOCK, nb, in, w.prm, (const uint32_t *)d_ids, w.table, (uint32_t *)d_out, (uint32_t *)d_blindings_out,
+                  (uint8_t *)d_status);
     if (hipGetLastError() != hipSuccess) return fail(c, BPGPU_ERR_HIP, "launch failed");
     return BPGPU_OK;
 }
@@ -4134,11 +4137,11 @@ extern "C" int bpgpu_pedersen_commit_batch_dev(bpgpu_ctx *c, size_t nbatch, cons
     if (!d_commitments_out || !d_status_out) return fail(c, BPGPU_ERR_INVALID_ARG, "commitments_out and status_out are required");
     if (((uintptr_t)d_values | (uintptr_t)d_blindings | (uintptr_t)d_rng_seed32 | (uintptr_t)d_commitments_out | (uintptr_t)d_blindings_out) & 3)
         return fail(c, BPGPU_ERR_INVALID_ARG, "device buffers must be 4-byte aligned");
-    std::lock_guard<std::mutex> lk(c->mu);
-    HIPCHK(c, hipSetDevice(c->device));
+    dev_scope<bpgpu_ctx> sc(c);
+    if (sc.rc) return sc.rc;
     if (!c->d_table) return fail(c, BPGPU_ERR_NO_GENS, "generators not loaded");
-    hipStream_t s = stream ? (hipStream_t)stream : c->stream;
-    if ((rc = ctx_enter(c, s))) return rc;
+    if ((rc = sc.enter(stream))) return rc;
+    hipStream_t s = sc.s;
     char *h_seed = nullptr;
     const void *d_seed = d_rng_seed32;
     size_t slot_bytes = 256;
@@ -4164,7 +4167,7 @@ extern "C" int bpgpu_pedersen_commit_batch_dev(bpgpu_ctx *c, size_t nbatch, cons
         memset(h_seed, 0, 32);
         c->io.last_secret_bytes = (h_seed == c->io.pin) ? 32 : 0;
     }
-    const int rc2 = ctx_leave(c, s);
+    const int rc2 = sc.leave();
     if (!rc && !ok) rc = fail(c, BPGPU_ERR_HIP, "clearing the seed slot failed");
     return rc ? rc : rc2;
 }
@@ -4177,14 +4180,9 @@ extern "C" int bpgpu_pedersen_open_batch_dev(bpgpu_ctx *c, size_t nbatch, const 
     if (rc) return rc;
     if (!d_commitments || !d_verdict_out) return fail(c, BPGPU_ERR_INVALID_ARG, "commitments and verdict_out are required");
     if (((uintptr_t)d_values | (uintptr_t)d_blindings | (uintptr_t)d_commitments) & 3) return fail(c, BPGPU_ERR_INVALID_ARG, "device buffers must be 4-byte aligned");
-    std::lock_guard<std::mutex> lk(c->mu);
-    HIPCHK(c, hipSetDevice(c->device));
-    if (!c->d_table) return fail(c, BPGPU_ERR_NO_GENS, "generators not loaded");
-    hipStream_t s = stream ? (hipStream_t)stream : c->stream;
-    if ((rc = ctx_enter(c, s))) return rc;
-    rc = ped_launch_locked(c, s, nbatch, d_values, value_bytes, d_blindings, nullptr, 0, d_commitments, d_verdict_out, nullptr, nullptr);
-    const int rc2 = ctx_leave(c, s);
-    return rc ? rc : rc2;
+    return dev_call(
+        c, stream, [&] { return c->d_table ? BPGPU_OK : fail(c, BPGPU_ERR_NO_GENS, "generators not loaded"); },
+        [&](hipStream_t s) { return ped_launch_locked(c, s, nbatch, d_values, value_bytes, d_blindings, nullptr, 0, d_commitments, d_verdict_out, nullptr, nullptr); });
 }
 
 // ============================================================================
@@ -4254,12 +4252,9 @@ static int psum_launch_locked(bpgpu_ctx *c, hipStream_t s, const psum_plan &pl, 
     if (balance)
         LAUNCH(c, s, "psum_balance", k_psum_balance, grid, BP_BLOCK, nb, in, prm, (const uint32_t *)d_ids, table, d_slot, (const ge_ext *)src, (const uint8_t *)d_bad,
                (uint8_t *)d_status);
-    else if (ct)
-        LAUNCH(c, s, "psum_finish_ct", k_psum_finish<true>, grid, BP_BLOCK, nb, in, prm, (const uint32_t *)d_ids, table, d_slot, (const ge_ext *)src, (const uint8_t *)d_bad,
-               (uint32_t *)d_out, (uint8_t *)d_status);
     else
-        LAUNCH(c, s, "psum_finish", k_psum_finish<false>, grid, BP_BLOCK, nb, in, prm, (const uint32_t *)d_ids, table, d_slot, (const ge_ext *)src, (const uint8_t *)d_bad,
-               (uint32_t *)d_out, (uint8_t *)d_status);
+        LAUNCH_CT(c, s, ct, "psum_finish", k_psum_finish, grid, BP_BLOCK, nb, in, prm, (const uint32_t *)d_ids, table, d_slot, (const ge_ext *)src, (const uint8_t *)d_bad,
+                  (uint32_t *)d_out, (uint8_t *)d_status);
     if (hipGetLastError() != hipSuccess) return fail(c, BPGPU_ERR_HIP, "launch failed");
     return BPGPU_OK;
 }
@@ -4325,11 +4320,11 @@ static int psum_dev(bpgpu_ctx *c, size_t nbatch, const uint32_t *row_offsets, co
     if (rc) return rc;
     if (!d_status) return fail(c, BPGPU_ERR_INVALID_ARG, balance ? "verdict_out is required" : "out and status_out are required");
     if (((uintptr_t)d_points | (uintptr_t)d_values | (uintptr_t)d_blindings | (uintptr_t)d_out) & 3) return fail(c, BPGPU_ERR_INVALID_ARG, "device buffers must be 4-byte aligned");
-    std::lock_guard<std::mutex> lk(c->mu);
-    HIPCHK(c, hipSetDevice(c->device));
+    dev_scope<bpgpu_ctx> sc(c);
+    if (sc.rc) return sc.rc;
     if ((d_values || d_blindings) && !c->d_table) return fail(c, BPGPU_ERR_NO_GENS, "generators not loaded");
-    hipStream_t s = stream ? (hipStream_t)stream : c->stream;
-    if ((rc = ctx_enter(c, s))) return rc;
+    if ((rc = sc.enter(stream))) return rc;
+    hipStream_t s = sc.s;
     const psum_arena ar(pl, true);
     char *h_tab = nullptr;
     const size_t tab_bytes = pl.table.size() * 4;
@@ -4347,7 +4342,7 @@ static int psum_dev(bpgpu_ctx *c, size_t nbatch, const uint32_t *row_offsets, co
     // other _dev forms of this family clear theirs: nothing of a call stays in the context's working set
     bool ok = true;
     if (c->arena && c->arena_cap >= ar.total) ok = hipMemsetAsync(c->arena, 0, ar.total, s) == hipSuccess;
-    const int rc2 = ctx_leave(c, s);
+    const int rc2 = sc.leave();
     if (!rc && !ok) rc = fail(c, BPGPU_ERR_HIP, "clearing the working set failed");
     return rc ? rc : rc2;
 }
@@ -5278,15 +5273,10 @@ extern "C" int bpgpu_r1cs_verify_batch_ts_dev(bpgpu_ctx *c, const bpgpu_r1cs_cir
     if (!d_proofs || !d_proof_lens || !d_verdict || (circuit->m && !d_commitments) || (!shared_transcript == !d_transcripts)) return BPGPU_ERR_INVALID_ARG;
     if (((uintptr_t)d_proof_lens | (uintptr_t)d_transcripts | (uintptr_t)d_transcripts_out) & 3)
         return fail(c, BPGPU_ERR_INVALID_ARG, "device buffers must be 4-byte aligned");
-    std::lock_guard<std::mutex> lk(c->mu);
-    HIPCHK(c, hipSetDevice(c->device));
-    hipStream_t s = stream ? (hipStream_t)stream : c->stream;
-    int rc = ctx_enter(c, s);
-    if (rc) return rc;
-    rc = r1cs_verify_dev_locked(c, circuit, nbatch, d_proofs, proof_stride, d_proof_lens, d_commitments, shared_transcript, d_transcripts, d_rng32,
-                                d_verdict, d_msm_out, d_transcripts_out, s);
-    const int rc2 = ctx_leave(c, s);
-    return rc ? rc : rc2;
+    return dev_call(c, stream, [&](hipStream_t s) {
+        return r1cs_verify_dev_locked(c, circuit, nbatch, d_proofs, proof_stride, d_proof_lens, d_commitments, shared_transcript, d_transcripts, d_rng32,
+                                    d_verdict, d_msm_out, d_transcripts_out, s);
+    });
 }
 
 extern "C" int bpgpu_r1cs_verify_batch_ts(bpgpu_ctx *c, const bpgpu_r1cs_circuit *circuit, size_t nbatch, const uint8_t *proofs, size_t proof_stride,
@@ -5350,6 +5340,53 @@ static int comb_rho_locked(bpgpu_ctx *c, hipStream_t s, const char *label, uint3
     return BPGPU_OK;
 }
 
+// How every combined check lays out the shared buffer: the combined scalars and points (`list` bytes each), the limb sums, the reduced row, the
+// weights, 64 bytes of result (compress(R), its status byte at + 32).  A multi-group check add()s its own regions behind these before reserve().
+struct comb_layout {
+    arena_plan ap;
+    size_t off[6];
+    char *base = nullptr, *d_csc = nullptr, *d_cpt = nullptr, *d_acc = nullptr, *d_row = nullptr, *d_rho = nullptr, *d_res = nullptr;
+    comb_layout(size_t list, size_t acc, size_t row, size_t rho) {
+        const size_t bytes[6] = {list, list, acc, row, rho, 64};
+        for (int i = 0; i < 6; i++) off[i] = ap.add(bytes[i]);
+    }
+    size_t add(size_t bytes) { return ap.add(bytes); }
+    // d_batch (the one-list checks): a caller that wants no batch result has it written to the result slot
+    int reserve(bpgpu_ctx *c, uint8_t **d_batch = nullptr) {
+        const int rc = comb_reserve(c, ap.total);
+        if (rc) return rc;
+        base = c->comb_buf;
+        d_csc = base + off[0], d_cpt = base + off[1], d_acc = base + off[2], d_row = base + off[3], d_rho = base + off[4], d_res = base + off[5];
+        if (d_batch && !*d_batch) *d_batch = (uint8_t *)d_res;
+        return BPGPU_OK;
+    }
+};
+
+// The tail of a one-list combined check behind its front end: comb_begin_locked, the family's weigh launch(es), then comb_finish_locked
+// (generator tables) or the family's own reduce into the head of the list, msm_batch_dev_locked over it and comb_verdict_locked.
+
+// the verdicts (undecided where R is not the identity) from the front end's status words and the multiplication's result
+static int comb_verdict_locked(bpgpu_ctx *c, hipStream_t s, const char *label, uint32_t nproofs, const front_staged &stg, uint8_t *d_verdict, uint8_t *d_batch) {
+    LAUNCH(c, s, label, k_rlc_comb_verdict, (nproofs + 63) / 64, 64, nproofs, (const uint32_t *)stg.d_stat, (const uint32_t *)stg.d_out,
+           (const uint8_t *)stg.d_mst, d_verdict, d_batch);
+    HIPCHK(c, hipGetLastError());
+    return BPGPU_OK;
+}
+// the weights (nrho of them) and the limb sums of `rows` rows zeroed
+static int comb_begin_locked(bpgpu_ctx *c, hipStream_t s, const char *label, const comb_layout &lay, uint32_t nrho, const void *d_weights64, uint32_t dom, size_t rows) {
+    const int rc = comb_rho_locked(c, s, label, nrho, d_weights64, dom, lay.d_rho);
+    if (rc) return rc;
+    HIPCHK(c, hipMemsetAsync(lay.d_acc, 0, rows * 80, s));
+    return BPGPU_OK;
+}
+// the limb sums reduced into the generator-table row, ONE multiplication over the tables of (gn, gm) and the list's nterms terms, the verdicts
+static int comb_finish_locked(bpgpu_ctx *c, hipStream_t s, const char *reduce, const char *verdict, const comb_layout &lay, const front_staged &stg, size_t rows,
+                              size_t gn, size_t gm, bool g_only, size_t nterms, uint32_t nproofs, uint8_t *d_verdict, uint8_t *d_batch) {
+    LAUNCH(c, s, reduce, k_rlc_comb_reduce, (uint32_t)((rows + 63) / 64), 64, (uint32_t)rows, (const unsigned long long *)lay.d_acc, (uint32_t *)lay.d_row);
+    const int rc = msm_shared_dev_locked(c, gn, gm, 1, nterms, lay.d_row, lay.d_csc, lay.d_cpt, stg.d_out, stg.d_mst, nullptr, s, g_only);
+    return rc ? rc : comb_verdict_locked(c, s, verdict, nproofs, stg, d_verdict, d_batch);
+}
+
 // one group's inputs on the device; its proof i is proof gp0 + i of the call
 struct r1cs_rlc_group {
     const bpgpu_r1cs_circuit *ci;
@@ -5388,14 +5425,12 @@ static int r1cs_rlc_dev_locked(bpgpu_ctx *c, const std::vector<r1cs_rlc_group> &
     size_t list_max = 1;
     for (size_t t : comb_terms) list_max = std::max(list_max, t);
     const size_t ncomb = comb_terms.size(), nrows = 2 * (size_t)PN + 2;
-    arena_plan ap;
-    const size_t off_csc = ap.add(list_max * 32), off_cpt = ap.add(list_max * 32), off_acc = ap.add(nrows * 80), off_gen = ap.add(nrows * 32),
-                 off_rho = ap.add(total * 32), off_gst = ap.add(total * 4), off_parts = ap.add(ncomb * 32), off_pst = ap.add(ncomb + 64),
-                 off_res = ap.add(64);   // (compress(R), then its status byte at + 32)
-    int rc = comb_reserve(c, ap.total);
+    comb_layout lay(list_max * 32, nrows * 80, nrows * 32, total * 32);
+    const size_t off_gst = lay.add(total * 4), off_parts = lay.add(ncomb * 32), off_pst = lay.add(ncomb + 64);
+    int rc = lay.reserve(c);
     if (rc) return rc;
-    char *b = c->comb_buf, *d_csc = b + off_csc, *d_cpt = b + off_cpt, *d_acc = b + off_acc, *d_gen = b + off_gen, *d_rho = b + off_rho, *d_gst = b + off_gst,
-         *d_parts = b + off_parts, *d_pst = b + off_pst, *d_res = b + off_res;
+    char *d_csc = lay.d_csc, *d_cpt = lay.d_cpt, *d_acc = lay.d_acc, *d_gen = lay.d_row, *d_rho = lay.d_rho, *d_res = lay.d_res, *d_gst = lay.base + off_gst,
+         *d_parts = lay.base + off_parts, *d_pst = lay.base + off_pst;
     const uint32_t n32 = (uint32_t)total;
     rc = comb_rho_locked(c, s, "r1cs_rlc_rho", n32, d_weights64, R1_RLC_WEIGHT_DOMAIN, d_rho);
     if (rc) return rc;
@@ -5508,26 +5543,19 @@ extern "C" int bpgpu_r1cs_verify_rlc(bpgpu_ctx *c, size_t ngroups, const bpgpu_r
         rc = r1cs_rlc_dev_locked(c, gr, total, d_r, weights64 ? io.d(r_w) : nullptr, (uint8_t *)d_v, (uint8_t *)io.d(r_b), transcripts_out ? io.d(r_to) : nullptr, s);
     rc = io.finish(io.download(rc));
     if (rc) return rc;
-    if ((uint8_t)io.h(r_b)[0] != 0) {
-        // R is not the identity, or a point did not decode: every group again through the per-proof chain, with the same rng bytes
-        // (inputs are still on the device; the transcripts it leaves are the ones already copied out)
-        rc = io.rerun_per_proof(r_v, r_b, [&] {
-            int rcg = BPGPU_OK;
-            for (const auto &g : gr)   // (in slices of R1_RLC_SLICE proofs, as above: the staging stays bounded)
-                for (size_t f = 0; f < g.nbatch && !rcg; f += R1_RLC_SLICE) {
-                    const size_t cnt = std::min<size_t>(R1_RLC_SLICE, g.nbatch - f);
-                    rcg = r1cs_verify_dev_locked(c, g.ci, cnt, g.d_proofs + f * g.proof_stride, g.proof_stride, g.d_lens + f * 4,
-                                                 g.d_coms ? g.d_coms + f * g.ci->m * 32 : nullptr, g.shared_ts, g.d_ts ? g.d_ts + f * TS : nullptr,
-                                                 d_r + 32 * (g.gp0 + f), d_v + g.gp0 + f, nullptr, nullptr, s);
-                }
-            return rcg;
-        });
-        if (rc) return rc;
-    }
-    memcpy(verdict, io.h(r_v), total);
-    if (batch_out) memcpy(batch_out, io.h(r_b), 33);
-    if (transcripts_out) memcpy(transcripts_out, io.h(r_to), total * TS);
-    return BPGPU_OK;
+    // where R is not the identity, or a point did not decode: every group again through the per-proof chain, with the same rng bytes
+    // (inputs are still on the device; the transcripts it leaves are the ones already copied out)
+    return io.deliver_combined(r_v, verdict, total, r_b, batch_out, r_to, transcripts_out, total * TS, [&] {
+        int rcg = BPGPU_OK;
+        for (const auto &g : gr)   // (in slices of R1_RLC_SLICE proofs, as above: the staging stays bounded)
+            for (size_t f = 0; f < g.nbatch && !rcg; f += R1_RLC_SLICE) {
+                const size_t cnt = std::min<size_t>(R1_RLC_SLICE, g.nbatch - f);
+                rcg = r1cs_verify_dev_locked(c, g.ci, cnt, g.d_proofs + f * g.proof_stride, g.proof_stride, g.d_lens + f * 4,
+                                             g.d_coms ? g.d_coms + f * g.ci->m * 32 : nullptr, g.shared_ts, g.d_ts ? g.d_ts + f * TS : nullptr,
+                                             d_r + 32 * (g.gp0 + f), d_v + g.gp0 + f, nullptr, nullptr, s);
+            }
+        return rcg;
+    });
 }
 
 // ---- batch-combined LinearProof verification (linear_rlc.h; an ADDITIONAL entry point, as bpgpu_r1cs_verify_rlc) ------------
@@ -5551,43 +5579,31 @@ static int lin_rlc_dev_locked(bpgpu_ctx *c, size_t n, size_t nbatch, const void 
     const lin_shape &sh = stg.sh;
     const size_t U = 2 * (size_t)sh.k + 2, nrows = (size_t)sh.n + 2, head = stg.fixed ? 0 : nrows, nterms = head + nbatch * U;
     if (nbatch * U > LIN_RLC_MAX_TERMS) return fail(c, BPGPU_ERR_INVALID_ARG, "batch too large: more than 2^24 proof-specific terms in one combination");
-    arena_plan ap;
-    const size_t off_csc = ap.add(nterms * 32 + 64), off_cpt = ap.add(nterms * 32 + 64), off_acc = ap.add(nrows * 80), off_row = ap.add(nrows * 32 + 64),
-                 off_rho = ap.add(nbatch * 32), off_bo = ap.add(64);
-    rc = comb_reserve(c, ap.total);
+    comb_layout lay(nterms * 32 + 64, nrows * 80, nrows * 32 + 64, nbatch * 32);
+    rc = lay.reserve(c, &d_batch);
     if (rc) return rc;
-    char *b = c->comb_buf, *d_csc = b + off_csc, *d_cpt = b + off_cpt, *d_acc = b + off_acc, *d_row = b + off_row, *d_rho = b + off_rho, *d_bo = b + off_bo;
-    if (!d_batch) d_batch = (uint8_t *)d_bo;
     const uint32_t nb32 = (uint32_t)nbatch;
     if (sh.shape_verdict) {   // n != 2^k: every proof already carries its code and nothing enters R
         HIPCHK(c, hipMemsetAsync(stg.d_mst, 0, stg.sz_b + stg.sz_o, s));
-    } else {
-        rc = comb_rho_locked(c, s, "lin_rlc_rho", nb32, d_weights64, LIN_RLC_WEIGHT_DOMAIN, d_rho);
-        if (rc) return rc;
-        lin_rlc_shape ws;
-        ws.nproofs = nb32, ws.nstride = (uint32_t)((nbatch + 63) / 64 * 64), ws.n = sh.n, ws.k = sh.k, ws.U = (uint32_t)U, ws.fixed = stg.fixed ? 1u : 0u,
-        ws.u0 = (uint32_t)head;
-        const uint64_t nt = (uint64_t)ws.nstride * (U + nrows);   // (a multiple of 64: whole wavefronts)
-        if (nt > 0x7fffffffull) return fail(c, BPGPU_ERR_INVALID_ARG, "batch too large for this shape");
-        HIPCHK(c, hipMemsetAsync(d_acc, 0, nrows * 80, s));
-        LAUNCH(c, s, "lin_rlc_weigh", k_lin_rlc_weigh, (uint32_t)(nt / 64), 64, ws, (const uint32_t *)stg.d_stat, (const uint32_t *)d_rho, (const uint32_t *)stg.d_gen,
-               (const uint32_t *)stg.d_sc, (const uint32_t *)stg.d_pt, (uint32_t *)d_csc, (uint32_t *)d_cpt, (unsigned long long *)d_acc);
-        // the combined coefficients of (B, F, G_0..): the generator-table row, or the head of the list with the caller's encodings
-        if (stg.fixed) {
-            LAUNCH(c, s, "lin_rlc_reduce", k_rlc_comb_reduce, (uint32_t)((nrows + 63) / 64), 64, (uint32_t)nrows, (const unsigned long long *)d_acc, (uint32_t *)d_row);
-            rc = msm_shared_dev_locked(c, sh.n, 1, 1, nbatch * U, d_row, d_csc, d_cpt, stg.d_out, stg.d_mst, nullptr, s, true);
-        } else {
-            LAUNCH(c, s, "lin_rlc_reduce", k_lin_rlc_reduce, (uint32_t)((nrows + 63) / 64), 64, (uint32_t)nrows, (const unsigned long long *)d_acc,
-                   (const uint8_t *)stg.d_B, (const uint8_t *)stg.d_F, (const uint8_t *)stg.d_G, (uint32_t *)d_csc, (uint32_t *)d_cpt);
-            const uint32_t nt1 = (uint32_t)nterms;
-            rc = msm_batch_dev_locked(c, 1, &nt1, d_csc, d_cpt, stg.d_out, stg.d_mst, s);
-        }
-        if (rc) return rc;
+        return comb_verdict_locked(c, s, "lin_rlc_verdict", nb32, stg, d_verdict, d_batch);
     }
-    LAUNCH(c, s, "lin_rlc_verdict", k_rlc_comb_verdict, (nb32 + 63) / 64, 64, nb32, (const uint32_t *)stg.d_stat, (const uint32_t *)stg.d_out,
-           (const uint8_t *)stg.d_mst, d_verdict, d_batch);
-    HIPCHK(c, hipGetLastError());
-    return BPGPU_OK;
+    rc = comb_rho_locked(c, s, "lin_rlc_rho", nb32, d_weights64, LIN_RLC_WEIGHT_DOMAIN, lay.d_rho);
+    if (rc) return rc;
+    lin_rlc_shape ws;
+    ws.nproofs = nb32, ws.nstride = (uint32_t)((nbatch + 63) / 64 * 64), ws.n = sh.n, ws.k = sh.k, ws.U = (uint32_t)U, ws.fixed = stg.fixed ? 1u : 0u,
+    ws.u0 = (uint32_t)head;
+    const uint64_t nt = (uint64_t)ws.nstride * (U + nrows);   // (a multiple of 64: whole wavefronts)
+    if (nt > 0x7fffffffull) return fail(c, BPGPU_ERR_INVALID_ARG, "batch too large for this shape");
+    HIPCHK(c, hipMemsetAsync(lay.d_acc, 0, nrows * 80, s));
+    LAUNCH(c, s, "lin_rlc_weigh", k_lin_rlc_weigh, (uint32_t)(nt / 64), 64, ws, (const uint32_t *)stg.d_stat, (const uint32_t *)lay.d_rho, (const uint32_t *)stg.d_gen,
+           (const uint32_t *)stg.d_sc, (const uint32_t *)stg.d_pt, (uint32_t *)lay.d_csc, (uint32_t *)lay.d_cpt, (unsigned long long *)lay.d_acc);
+    // the combined coefficients of (B, F, G_0..): the generator-table row, or the head of the list with the caller's encodings
+    if (stg.fixed) return comb_finish_locked(c, s, "lin_rlc_reduce", "lin_rlc_verdict", lay, stg, nrows, sh.n, 1, true, nbatch * U, nb32, d_verdict, d_batch);
+    LAUNCH(c, s, "lin_rlc_reduce", k_lin_rlc_reduce, (uint32_t)((nrows + 63) / 64), 64, (uint32_t)nrows, (const unsigned long long *)lay.d_acc,
+           (const uint8_t *)stg.d_B, (const uint8_t *)stg.d_F, (const uint8_t *)stg.d_G, (uint32_t *)lay.d_csc, (uint32_t *)lay.d_cpt);
+    const uint32_t nt1 = (uint32_t)nterms;
+    rc = msm_batch_dev_locked(c, 1, &nt1, lay.d_csc, lay.d_cpt, stg.d_out, stg.d_mst, s);
+    return rc ? rc : comb_verdict_locked(c, s, "lin_rlc_verdict", nb32, stg, d_verdict, d_batch);
 }
 
 extern "C" int bpgpu_linear_verify_rlc_dev(bpgpu_ctx *c, size_t n, size_t nbatch, const void *d_proofs, size_t proof_len, const uint8_t *label,
@@ -5600,15 +5616,10 @@ extern "C" int bpgpu_linear_verify_rlc_dev(bpgpu_ctx *c, size_t n, size_t nbatch
     if (!d_proofs || !d_verdict || !d_C || (n && !d_b) || (!from_gens && (!d_F || !d_B || (n && !d_G)))) return BPGPU_ERR_INVALID_ARG;
     if (((uintptr_t)d_proofs | (uintptr_t)d_C | (uintptr_t)d_G | (uintptr_t)d_F | (uintptr_t)d_B | (uintptr_t)d_b | (uintptr_t)d_transcripts_out) & 3)
         return fail(c, BPGPU_ERR_INVALID_ARG, "device buffers must be 4-byte aligned");
-    std::lock_guard<std::mutex> lk(c->mu);
-    HIPCHK(c, hipSetDevice(c->device));
-    hipStream_t s = stream ? (hipStream_t)stream : c->stream;
-    int rc = ctx_enter(c, s);
-    if (rc) return rc;
-    rc = lin_rlc_dev_locked(c, n, nbatch, d_proofs, proof_len, label, label_len, shared_transcript, d_C, d_G, d_F, d_B, d_b, b_shared, d_weights64,
-                            (uint8_t *)d_verdict, (uint8_t *)d_batch_out, d_transcripts_out, s);
-    const int rc2 = ctx_leave(c, s);
-    return rc ? rc : rc2;
+    return dev_call(c, stream, [&](hipStream_t s) {
+        return lin_rlc_dev_locked(c, n, nbatch, d_proofs, proof_len, label, label_len, shared_transcript, d_C, d_G, d_F, d_B, d_b, b_shared, d_weights64,
+                                (uint8_t *)d_verdict, (uint8_t *)d_batch_out, d_transcripts_out, s);
+    });
 }
 
 // host pointers.  ts_host (with ts_stride 0 or BPGPU_TRANSCRIPT_BYTES): the callers' own transcripts, checked by the caller, in place of label /
@@ -5659,19 +5670,12 @@ static int lin_rlc_host_call(bpgpu_ctx *c, size_t n, size_t nbatch, const uint8_
                                 weights64 ? io.d(r_w) : nullptr, (uint8_t *)io.d(r_v), (uint8_t *)io.d(r_bo), transcripts_out ? io.d(r_t) : nullptr, s, a_ts);
     rc = io.finish(io.download(rc));
     if (rc) return rc;
-    if (batch_out) memcpy(batch_out, io.h(r_bo), 33);   // (R as computed before any fallback)
-    if (transcripts_out) memcpy(transcripts_out, io.h(r_t), nbatch * BPGPU_TRANSCRIPT_BYTES);
-    if ((uint8_t)io.h(r_bo)[0] != 0) {
-        // R is not the identity, or a point of the combined MSM did not decode: the batch again through the per-proof path (inputs are
-        // still on the device; the transcripts it leaves are the ones already copied out)
-        rc = io.rerun_per_proof(r_v, r_bo, [&] {
-            return lin_verify_dev_locked(c, n, nbatch, io.d(r_pr), proof_len, label, label_len, shared_transcript, io.d(r_c), a_g, a_f, a_b, io.d(r_bv), b_shared,
-                                         io.d(r_v), nullptr, nullptr, s, a_ts);
-        });
-        if (rc) return rc;
-    }
-    memcpy(verdict, io.h(r_v), nbatch);
-    return BPGPU_OK;
+    // where R is not the identity, or a point of the combined MSM did not decode: the batch again through the per-proof path (inputs are
+    // still on the device; the transcripts it leaves are the ones already copied out)
+    return io.deliver_combined(r_v, verdict, nbatch, r_bo, batch_out, r_t, transcripts_out, nbatch * BPGPU_TRANSCRIPT_BYTES, [&] {
+        return lin_verify_dev_locked(c, n, nbatch, io.d(r_pr), proof_len, label, label_len, shared_transcript, io.d(r_c), a_g, a_f, a_b, io.d(r_bv), b_shared,
+                                     io.d(r_v), nullptr, nullptr, s, a_ts);
+    });
 }
 
 extern "C" int bpgpu_linear_verify_rlc(bpgpu_ctx *c, size_t n, size_t nbatch, const uint8_t *proofs, size_t proof_len, const uint8_t *label,
@@ -5708,15 +5712,10 @@ extern "C" int bpgpu_linear_verify_rlc_ts_dev(bpgpu_ctx *c, size_t n, size_t nba
     if (!d_proofs || !d_verdict || !d_C || (n && !d_b) || (!from_gens && (!d_F || !d_B || (n && !d_G)))) return BPGPU_ERR_INVALID_ARG;
     if (((uintptr_t)d_proofs | (uintptr_t)d_C | (uintptr_t)d_G | (uintptr_t)d_F | (uintptr_t)d_B | (uintptr_t)d_b) & 3)
         return fail(c, BPGPU_ERR_INVALID_ARG, "device buffers must be 4-byte aligned");
-    std::lock_guard<std::mutex> lk(c->mu);
-    HIPCHK(c, hipSetDevice(c->device));
-    hipStream_t s = stream ? (hipStream_t)stream : c->stream;
-    int rc = ctx_enter(c, s);
-    if (rc) return rc;
-    rc = lin_rlc_dev_locked(c, n, nbatch, d_proofs, proof_len, nullptr, 0, nullptr, d_C, d_G, d_F, d_B, d_b, b_shared, d_weights64, (uint8_t *)d_verdict,
-                            (uint8_t *)d_batch_out, d_transcripts_out, s, &ts);
-    const int rc2 = ctx_leave(c, s);
-    return rc ? rc : rc2;
+    return dev_call(c, stream, [&](hipStream_t s) {
+        return lin_rlc_dev_locked(c, n, nbatch, d_proofs, proof_len, nullptr, 0, nullptr, d_C, d_G, d_F, d_B, d_b, b_shared, d_weights64, (uint8_t *)d_verdict,
+                                (uint8_t *)d_batch_out, d_transcripts_out, s, &ts);
+    });
 }
 
 // ---- batch-combined InnerProductProof verification (ipp_rlc.h; an ADDITIONAL entry point, as bpgpu_linear_verify_rlc) ---------
@@ -5790,13 +5789,11 @@ static int ipp_rlc_dev_locked(bpgpu_ctx *c, size_t n, size_t nbatch, const void 
     if (rc) return rc;
     char *d_stat = c->ipp_buf, *d_us = d_stat + sz_st, *d_ui = d_us + sz_u, *d_tab = d_ui + sz_u, *d_ab = d_tab + sz_tab, *d_mst = d_ab + sz_ab,
          *d_out = d_mst + sz_b;
-    arena_plan ap;
-    const size_t off_csc = ap.add(nterms * 32 + 64), off_cpt = ap.add(nterms * 32 + 64), off_acc = ap.add(nrows * 80), off_row = ap.add(nrows * 32 + 64),
-                 off_rho = ap.add(nbatch * 32), off_bo = ap.add(64);
-    rc = comb_reserve(c, ap.total);
+    front_staged stg;   // (what the tail reads of it)
+    stg.d_stat = d_stat, stg.d_mst = d_mst, stg.d_out = d_out;
+    comb_layout lay(nterms * 32 + 64, nrows * 80, nrows * 32 + 64, nbatch * 32);
+    rc = lay.reserve(c, &d_batch);
     if (rc) return rc;
-    char *b = c->comb_buf, *d_csc = b + off_csc, *d_cpt = b + off_cpt, *d_acc = b + off_acc, *d_row = b + off_row, *d_rho = b + off_rho, *d_bo = b + off_bo;
-    if (!d_batch) d_batch = (uint8_t *)d_bo;
     HIPCHK(c, hipMemsetAsync(d_stat, 0, sz_st + 2 * sz_u, s));
     if (ts) {
         LAUNCH(c, s, "ipp_rlc_front_ts", k_ipp_vs_front_ts, (nb32 + RP_BLOCK - 1) / RP_BLOCK, RP_BLOCK, sh, init, (const uint8_t *)d_proofs, (const uint32_t *)ts->d_in,
@@ -5809,34 +5806,25 @@ static int ipp_rlc_dev_locked(bpgpu_ctx *c, size_t n, size_t nbatch, const void 
     }
     if (shape_bad) {   // n != 2^k: every proof already carries its code and nothing enters R
         HIPCHK(c, hipMemsetAsync(d_mst, 0, sz_b + sz_o, s));
-    } else {
-        rc = comb_rho_locked(c, s, "ipp_rlc_rho", nb32, d_weights64, IPP_RLC_WEIGHT_DOMAIN, d_rho);
-        if (rc) return rc;
-        ipp_rlc_shape ws;
-        ws.nproofs = nb32, ws.nstride = nstride, ws.n = (uint32_t)n, ws.k = (uint32_t)k, ws.U = (uint32_t)U, ws.proof_len = (uint32_t)proof_len,
-        ws.row0 = fixed ? 2u : 0u, ws.u0 = (uint32_t)head, ws.B = (uint32_t)wB;
-        HIPCHK(c, hipMemsetAsync(d_acc, 0, nrows * 80, s));
-        LAUNCH(c, s, "ipp_rlc_uniq", k_ipp_rlc_uniq, (nb32 + 63) / 64, 64, ws, (const uint32_t *)d_stat, (const uint32_t *)d_rho, (const uint8_t *)d_proofs,
-               (const uint8_t *)d_P, (const uint8_t *)d_Q, (const uint32_t *)d_us, (const uint32_t *)d_ui, (uint32_t *)d_ab, (uint32_t *)d_csc, (uint32_t *)d_cpt);
-        LAUNCH(c, s, "ipp_rlc_weigh", k_ipp_rlc_weigh, (uint32_t)(nt / 64), 64, ws, (const uint32_t *)d_stat, (const uint32_t *)d_ab, (const uint32_t *)d_tab,
-               (const uint8_t *)d_Gf, (const uint8_t *)d_Hf, (unsigned long long *)d_acc);
-        // the combined coefficients of (G_0.., H_0..): the generator-table row behind B_blinding = B = 0, or the head of the list with the
-        // caller's encodings
-        if (fixed) {
-            LAUNCH(c, s, "ipp_rlc_reduce", k_rlc_comb_reduce, (uint32_t)((nrows + 63) / 64), 64, (uint32_t)nrows, (const unsigned long long *)d_acc, (uint32_t *)d_row);
-            rc = msm_shared_dev_locked(c, n / gens_m, gens_m, 1, nbatch * U, d_row, d_csc, d_cpt, d_out, d_mst, nullptr, s);
-        } else {
-            LAUNCH(c, s, "ipp_rlc_reduce", k_ipp_rlc_reduce, (uint32_t)((nrows + 63) / 64), 64, (uint32_t)nrows, (uint32_t)n, (const unsigned long long *)d_acc,
-                   (const uint8_t *)d_G, (const uint8_t *)d_H, (uint32_t *)d_csc, (uint32_t *)d_cpt);
-            const uint32_t nt1 = (uint32_t)nterms;
-            rc = msm_batch_dev_locked(c, 1, &nt1, d_csc, d_cpt, d_out, d_mst, s);
-        }
-        if (rc) return rc;
+        return comb_verdict_locked(c, s, "ipp_rlc_verdict", nb32, stg, d_verdict, d_batch);
     }
-    LAUNCH(c, s, "ipp_rlc_verdict", k_rlc_comb_verdict, (nb32 + 63) / 64, 64, nb32, (const uint32_t *)d_stat, (const uint32_t *)d_out, (const uint8_t *)d_mst,
-           d_verdict, d_batch);
-    HIPCHK(c, hipGetLastError());
-    return BPGPU_OK;
+    ipp_rlc_shape ws;
+    ws.nproofs = nb32, ws.nstride = nstride, ws.n = (uint32_t)n, ws.k = (uint32_t)k, ws.U = (uint32_t)U, ws.proof_len = (uint32_t)proof_len,
+    ws.row0 = fixed ? 2u : 0u, ws.u0 = (uint32_t)head, ws.B = (uint32_t)wB;
+    rc = comb_begin_locked(c, s, "ipp_rlc_rho", lay, nb32, d_weights64, IPP_RLC_WEIGHT_DOMAIN, nrows);
+    if (rc) return rc;
+    LAUNCH(c, s, "ipp_rlc_uniq", k_ipp_rlc_uniq, (nb32 + 63) / 64, 64, ws, (const uint32_t *)d_stat, (const uint32_t *)lay.d_rho, (const uint8_t *)d_proofs,
+           (const uint8_t *)d_P, (const uint8_t *)d_Q, (const uint32_t *)d_us, (const uint32_t *)d_ui, (uint32_t *)d_ab, (uint32_t *)lay.d_csc, (uint32_t *)lay.d_cpt);
+    LAUNCH(c, s, "ipp_rlc_weigh", k_ipp_rlc_weigh, (uint32_t)(nt / 64), 64, ws, (const uint32_t *)d_stat, (const uint32_t *)d_ab, (const uint32_t *)d_tab,
+           (const uint8_t *)d_Gf, (const uint8_t *)d_Hf, (unsigned long long *)lay.d_acc);
+    // the combined coefficients of (G_0.., H_0..): the generator-table row behind B_blinding = B = 0, or the head of the list with the
+    // caller's encodings
+    if (fixed) return comb_finish_locked(c, s, "ipp_rlc_reduce", "ipp_rlc_verdict", lay, stg, nrows, n / gens_m, gens_m, false, nbatch * U, nb32, d_verdict, d_batch);
+    LAUNCH(c, s, "ipp_rlc_reduce", k_ipp_rlc_reduce, (uint32_t)((nrows + 63) / 64), 64, (uint32_t)nrows, (uint32_t)n, (const unsigned long long *)lay.d_acc,
+           (const uint8_t *)d_G, (const uint8_t *)d_H, (uint32_t *)lay.d_csc, (uint32_t *)lay.d_cpt);
+    const uint32_t nt1 = (uint32_t)nterms;
+    rc = msm_batch_dev_locked(c, 1, &nt1, lay.d_csc, lay.d_cpt, d_out, d_mst, s);
+    return rc ? rc : comb_verdict_locked(c, s, "ipp_rlc_verdict", nb32, stg, d_verdict, d_batch);
 }
 
 extern "C" int bpgpu_ipp_verify_rlc_dev(bpgpu_ctx *c, size_t n, size_t nbatch, const void *d_proofs, size_t proof_len, const uint8_t *label,
@@ -5848,15 +5836,10 @@ extern "C" int bpgpu_ipp_verify_rlc_dev(bpgpu_ctx *c, size_t n, size_t nbatch, c
     if (!d_proofs || !d_verdict || !d_P || !d_Q || (n && (!d_G_factors || !d_H_factors)) || (d_G == nullptr) != (d_H == nullptr)) return BPGPU_ERR_INVALID_ARG;
     if (((uintptr_t)d_proofs | (uintptr_t)d_G_factors | (uintptr_t)d_H_factors | (uintptr_t)d_P | (uintptr_t)d_Q | (uintptr_t)d_G | (uintptr_t)d_H) & 3)
         return fail(c, BPGPU_ERR_INVALID_ARG, "device buffers must be 4-byte aligned");
-    std::lock_guard<std::mutex> lk(c->mu);
-    HIPCHK(c, hipSetDevice(c->device));
-    hipStream_t s = stream ? (hipStream_t)stream : c->stream;
-    int rc = ctx_enter(c, s);
-    if (rc) return rc;
-    rc = ipp_rlc_dev_locked(c, n, nbatch, d_proofs, proof_len, label, label_len, shared_transcript, d_G_factors, d_H_factors, d_P, d_Q, d_G, d_H, gens_m,
-                            d_weights64, (uint8_t *)d_verdict, (uint8_t *)d_batch_out, s);
-    const int rc2 = ctx_leave(c, s);
-    return rc ? rc : rc2;
+    return dev_call(c, stream, [&](hipStream_t s) {
+        return ipp_rlc_dev_locked(c, n, nbatch, d_proofs, proof_len, label, label_len, shared_transcript, d_G_factors, d_H_factors, d_P, d_Q, d_G, d_H, gens_m,
+                                d_weights64, (uint8_t *)d_verdict, (uint8_t *)d_batch_out, s);
+    });
 }
 
 // host pointers.  ts_host (with ts_stride 0 or BPGPU_TRANSCRIPT_BYTES): the callers' own transcripts, checked by the caller, in place of label /
@@ -5914,31 +5897,24 @@ static int ipp_rlc_host_call(bpgpu_ctx *c, size_t n, size_t nbatch, const uint8_
                                 gens_m, weights64 ? io.d(r_w) : nullptr, (uint8_t *)io.d(r_v), (uint8_t *)io.d(r_bo), s, ts_host ? &ts : nullptr);
     rc = io.finish(io.download(rc));
     if (rc) return rc;
-    if (batch_out) memcpy(batch_out, io.h(r_bo), 33);   // (R as computed before any fallback)
-    if (ts_out_host) memcpy(ts_out_host, io.h(r_to), nbatch * BPGPU_TRANSCRIPT_BYTES);
-    ts.d_out = nullptr;   // (the fallback's transcripts are the ones already copied out)
-    if ((uint8_t)io.h(r_bo)[0] != 0) {
-        // R is not the identity, or a point of the combined MSM did not decode: the batch again through the per-proof path with the
-        // bases given once (inputs are still on the device; in generator-table mode G(n / gens_m, gens_m), H(..) are gathered first)
-        rc = io.rerun_per_proof(r_v, r_bo, [&]() -> int {
-            const void *f_g = a_g, *f_h = a_h;
-            if (from_gens && n) {
-                uint32_t *d_ids = nullptr;
-                const int rci = gen_ids_for(c, n / gens_m, gens_m, &d_ids);
-                if (rci) return rci;
-                LAUNCH(c, s, "gather32", k_gather32, ((uint32_t)(2 * n) + BP_BLOCK - 1) / BP_BLOCK, BP_BLOCK, (uint32_t)(2 * n), (const uint32_t *)(d_ids + 2),
-                       (const uint32_t *)c->d_gens, (uint32_t *)io.d(r_gen));
-                f_g = io.d(r_gen), f_h = io.d(r_gen) + n * 32;
-            } else if (from_gens) {
-                f_g = f_h = io.d(r_gen);
-            }
-            return ipp_verify_dev_locked(c, n, nbatch, io.d(r_pr), proof_len, label, label_len, shared_transcript, io.d(r_gf), io.d(r_hf), io.d(r_p), io.d(r_q),
-                                         f_g, f_h, 1, io.d(r_v), nullptr, s, ts_host ? &ts : nullptr);
-        });
-        if (rc) return rc;
-    }
-    memcpy(verdict, io.h(r_v), nbatch);
-    return BPGPU_OK;
+    // where R is not the identity, or a point of the combined MSM did not decode: the batch again through the per-proof path with the
+    // bases given once (inputs are still on the device; in generator-table mode G(n / gens_m, gens_m), H(..) are gathered first)
+    return io.deliver_combined(r_v, verdict, nbatch, r_bo, batch_out, r_to, ts_out_host, nbatch * BPGPU_TRANSCRIPT_BYTES, [&]() -> int {
+        ts.d_out = nullptr;   // (the fallback's transcripts are the ones already copied out)
+        const void *f_g = a_g, *f_h = a_h;
+        if (from_gens && n) {
+            uint32_t *d_ids = nullptr;
+            const int rci = gen_ids_for(c, n / gens_m, gens_m, &d_ids);
+            if (rci) return rci;
+            LAUNCH(c, s, "gather32", k_gather32, ((uint32_t)(2 * n) + BP_BLOCK - 1) / BP_BLOCK, BP_BLOCK, (uint32_t)(2 * n), (const uint32_t *)(d_ids + 2),
+                   (const uint32_t *)c->d_gens, (uint32_t *)io.d(r_gen));
+            f_g = io.d(r_gen), f_h = io.d(r_gen) + n * 32;
+        } else if (from_gens) {
+            f_g = f_h = io.d(r_gen);
+        }
+        return ipp_verify_dev_locked(c, n, nbatch, io.d(r_pr), proof_len, label, label_len, shared_transcript, io.d(r_gf), io.d(r_hf), io.d(r_p), io.d(r_q),
+                                     f_g, f_h, 1, io.d(r_v), nullptr, s, ts_host ? &ts : nullptr);
+    });
 }
 
 extern "C" int bpgpu_ipp_verify_rlc(bpgpu_ctx *c, size_t n, size_t nbatch, const uint8_t *proofs, size_t proof_len, const uint8_t *label,
@@ -5975,15 +5951,10 @@ extern "C" int bpgpu_ipp_verify_rlc_ts_dev(bpgpu_ctx *c, size_t n, size_t nbatch
     if (!d_proofs || !d_verdict || !d_P || !d_Q || (n && (!d_G_factors || !d_H_factors)) || (d_G == nullptr) != (d_H == nullptr)) return BPGPU_ERR_INVALID_ARG;
     if (((uintptr_t)d_proofs | (uintptr_t)d_G_factors | (uintptr_t)d_H_factors | (uintptr_t)d_P | (uintptr_t)d_Q | (uintptr_t)d_G | (uintptr_t)d_H) & 3)
         return fail(c, BPGPU_ERR_INVALID_ARG, "device buffers must be 4-byte aligned");
-    std::lock_guard<std::mutex> lk(c->mu);
-    HIPCHK(c, hipSetDevice(c->device));
-    hipStream_t s = stream ? (hipStream_t)stream : c->stream;
-    int rc = ctx_enter(c, s);
-    if (rc) return rc;
-    rc = ipp_rlc_dev_locked(c, n, nbatch, d_proofs, proof_len, nullptr, 0, nullptr, d_G_factors, d_H_factors, d_P, d_Q, d_G, d_H, gens_m, d_weights64,
-                            (uint8_t *)d_verdict, (uint8_t *)d_batch_out, s, &ts);
-    const int rc2 = ctx_leave(c, s);
-    return rc ? rc : rc2;
+    return dev_call(c, stream, [&](hipStream_t s) {
+        return ipp_rlc_dev_locked(c, n, nbatch, d_proofs, proof_len, nullptr, 0, nullptr, d_G_factors, d_H_factors, d_P, d_Q, d_G, d_H, gens_m, d_weights64,
+                                (uint8_t *)d_verdict, (uint8_t *)d_batch_out, s, &ts);
+    });
 }
 
 // ============================================================================
@@ -6602,28 +6573,23 @@ extern "C" int bpgpu_transcript_batch_dev(bpgpu_ctx *c, size_t nbatch, const uin
     if (al & 3) return fail(c, BPGPU_ERR_INVALID_ARG, "device states and lens must be 4-byte aligned");
     if (d_states_in == d_states_out && stride_in == 0 && nbatch > 1)
         return fail(c, BPGPU_ERR_INVALID_ARG, "states_out may be states_in only with one state per row");
-    std::lock_guard<std::mutex> lk(c->mu);
-    HIPCHK(c, hipSetDevice(c->device));
-    hipStream_t s = stream ? (hipStream_t)stream : c->stream;
-    rc = ctx_enter(c, s);
-    if (rc) return rc;
-    do {
-        if ((rc = ipp_reserve(c, align_up(pl.bytes)))) break;
+    return dev_call(c, stream, [&](hipStream_t s) {
+        int rcb = ipp_reserve(c, align_up(pl.bytes));
+        if (rcb) return rcb;
         char *h = nullptr, *d = c->ipp_buf;
-        if ((rc = c->io.pin_alloc(pl.bytes, &h))) break;
+        if ((rcb = c->io.pin_alloc(pl.bytes, &h))) return rcb;
         tsb_fill(h, pl, ops, new_label, new_label_len,
                  [&](size_t o, uint64_t *stride) -> char * {
                      *stride = ops[o].stride;
                      return (char *)ops[o].data;
                  },
                  [&](size_t o) -> char * { return (char *)ops[o].lens; });
-        if (pl.bytes && (rc = HIPRC(c, hipMemcpyAsync(d, h, pl.bytes, hipMemcpyHostToDevice, s)))) break;
-        if ((rc = c->io.pin_mark(s))) break;
+        if (pl.bytes && (rcb = HIPRC(c, hipMemcpyAsync(d, h, pl.bytes, hipMemcpyHostToDevice, s)))) return rcb;
+        if ((rcb = c->io.pin_mark(s))) return rcb;
         tsb_launch(c, s, nbatch, pl, d, new_label ? d + pl.off_st0 : d_states_in, new_label ? 0 : stride_in, d_states_out);
-        if (hipGetLastError() != hipSuccess) rc = fail(c, BPGPU_ERR_HIP, "launch failed");
-    } while (0);
-    const int rc2 = ctx_leave(c, s);
-    return rc ? rc : rc2;
+        if (hipGetLastError() != hipSuccess) return fail(c, BPGPU_ERR_HIP, "launch failed");
+        return BPGPU_OK;
+    });
 }
 
 // the pool form: the whole call on the next device's context (pool.hip)
@@ -6759,14 +6725,12 @@ static int rp_mix_dev_locked(bpgpu_ctx *c, std::vector<rp_mix_group> &gr, size_t
     }
     if (u_total > RM_MAX_TERMS) return fail(c, BPGPU_ERR_INVALID_ARG, "more than 2^24 proof-specific terms in one call");
     const size_t nrows = N ? 2 * N * M + 2 : 0;
-    arena_plan cp;   // (the combined checks share their buffer)
-    const size_t list = std::max<size_t>(u_total, 1) * 32;
-    const size_t off_csc = cp.add(list), off_cpt = cp.add(list), off_acc = cp.add(nrows * 80 + 16), off_gen = cp.add(nrows * 32 + 16), off_gst = cp.add(total * 4),
-                 off_res = cp.add(64), off_rdraw = cp.add(d_rng64 ? 0 : total * 64), off_wdraw = cp.add(d_weights64 ? 0 : total * 64);
-    int rc = comb_reserve(c, cp.total);
+    comb_layout lay(std::max<size_t>(u_total, 1) * 32, nrows * 80 + 16, nrows * 32 + 16, 0);   // (no weights of its own: they arrive as 64 bytes per proof)
+    const size_t off_gst = lay.add(total * 4), off_rdraw = lay.add(d_rng64 ? 0 : total * 64), off_wdraw = lay.add(d_weights64 ? 0 : total * 64);
+    int rc = lay.reserve(c);
     if (rc) return rc;
-    char *b = c->comb_buf, *d_csc = b + off_csc, *d_cpt = b + off_cpt, *d_acc = b + off_acc, *d_gen = b + off_gen, *d_gst = b + off_gst, *d_res = b + off_res,
-         *d_rdraw = b + off_rdraw, *d_wdraw = b + off_wdraw;
+    char *d_csc = lay.d_csc, *d_cpt = lay.d_cpt, *d_acc = lay.d_acc, *d_gen = lay.d_row, *d_res = lay.d_res, *d_gst = lay.base + off_gst,
+         *d_rdraw = lay.base + off_rdraw, *d_wdraw = lay.base + off_wdraw;
     const uint32_t n32 = (uint32_t)total;
     if (!d_rng64) {   // as the per-proof path's seeded mode (the tests' chain seed pins it), but per call and under this entry point's domain
         rlc_key key;
@@ -6949,25 +6913,18 @@ static int rp_mix_host_call(bpgpu_ctx *c, size_t ngroups, const size_t *n, const
     if (!rc) rc = rp_mix_dev_locked(c, gr, total, rng64 ? io.d(r_r) : nullptr, weights64 ? io.d(r_w) : nullptr, (uint8_t *)d_v, (uint8_t *)io.d(r_b), s, &d_rng_used);
     rc = io.finish(io.download(rc));
     if (rc) return rc;
-    if ((uint8_t)io.h(r_b)[0] != 0) {
-        // R is not the identity, or did not decode: every group the combination took again through the per-proof chain of its shape, with
-        // the same rng bytes (inputs, and rng bytes drawn above, are still on the device)
-        // (the per-proof path writes the same advanced states again: byte for byte those of bpgpu_rangeproof_verify_batch_ts either way)
-        rc = io.rerun_per_proof(r_v, r_b, [&] {
-            for (const auto &g : gr) {
-                if (g.whole) continue;
-                const int rcg = rp_verify_dev_locked(c, g.n, g.m, g.nbatch, g.d_proofs, g.proof_len, g.d_coms, rp_mix_transcripts(g), d_rng_used + 64 * g.gp0, d_v + g.gp0,
-                                                     nullptr, s);
-                if (rcg) return rcg;
-            }
-            return (int)BPGPU_OK;
-        });
-        if (rc) return rc;
-    }
-    memcpy(verdict, io.h(r_v), total);
-    if (batch_out) memcpy(batch_out, io.h(r_b), 33);
-    if (transcripts_out) memcpy(transcripts_out, io.h(r_to), total * TS);
-    return BPGPU_OK;
+    // where R is not the identity, or did not decode: every group the combination took again through the per-proof chain of its shape, with
+    // the same rng bytes (inputs, and rng bytes drawn above, are still on the device)
+    // (the per-proof path writes the same advanced states again: byte for byte those of bpgpu_rangeproof_verify_batch_ts either way)
+    return io.deliver_combined(r_v, verdict, total, r_b, batch_out, r_to, transcripts_out, total * TS, [&] {
+        for (const auto &g : gr) {
+            if (g.whole) continue;
+            const int rcg = rp_verify_dev_locked(c, g.n, g.m, g.nbatch, g.d_proofs, g.proof_len, g.d_coms, rp_mix_transcripts(g), d_rng_used + 64 * g.gp0, d_v + g.gp0,
+                                                 nullptr, s);
+            if (rcg) return rcg;
+        }
+        return (int)BPGPU_OK;
+    });
 }
 
 extern "C" int bpgpu_rangeproof_verify_rlc_mixed(bpgpu_ctx *c, size_t ngroups, const size_t *n, const size_t *m, const size_t *nbatch, const size_t *proof_len,
@@ -7105,23 +7062,12 @@ static opn_shape opn_make_shape(int form, size_t nbatch, const void *values, siz
     return sh;
 }
 
-// what the front end leaves on the device (c->ipp_buf) for the multiscalar multiplication(s)
-struct opn_staged {
-    char *d_sc = nullptr, *d_pt = nullptr, *d_gen = nullptr, *d_stat = nullptr, *d_mst = nullptr, *d_out = nullptr;
-    size_t sz_b = 0, sz_o = 0;
-};
 // the staging and the k_opn_front launch (lane = proof) of nbatch proofs
 static int opn_front_dev_locked(bpgpu_ctx *c, int form, size_t nbatch, const void *d_proofs, const ipp_ts &ts, const void *d_C, const void *d_values,
-                                size_t value_bytes, void *d_ts_out, hipStream_t s, opn_staged &stg) {
+                                size_t value_bytes, void *d_ts_out, hipStream_t s, front_staged &stg) {
     if (!c->d_table) return fail(c, BPGPU_ERR_NO_GENS, "generators not loaded");
-    const size_t sz_terms = align_up(nbatch * 2 * 32 + 64), sz_gen = align_up(nbatch * OPN_GEN_ROW * 32 + 64), sz_st = align_up(nbatch * 4),
-                 sz_b = align_up(nbatch + 64), sz_o = align_up(nbatch * 32 + 64);
-    int rc = ipp_reserve(c, 2 * sz_terms + sz_gen + sz_st + sz_b + sz_o);
+    const int rc = front_stage_locked(c, s, nbatch * 2 * 32 + 64, nbatch * OPN_GEN_ROW * 32 + 64, nbatch * 4, nbatch + 64, nbatch * 32 + 64, stg);
     if (rc) return rc;
-    stg.d_sc = c->ipp_buf, stg.d_pt = stg.d_sc + sz_terms, stg.d_gen = stg.d_pt + sz_terms, stg.d_stat = stg.d_gen + sz_gen, stg.d_mst = stg.d_stat + sz_st,
-    stg.d_out = stg.d_mst + sz_b;
-    stg.sz_b = sz_b, stg.sz_o = sz_o;
-    HIPCHK(c, hipMemsetAsync(stg.d_sc, 0, 2 * sz_terms + sz_gen + sz_st, s));   // scalars, points, generator rows, status
     rp_strobe_init init;
     ipp_ts_init(init, ts);
     const opn_shape sh = opn_make_shape(form, nbatch, d_values, value_bytes, ts);
@@ -7135,7 +7081,7 @@ static int opn_front_dev_locked(bpgpu_ctx *c, int form, size_t nbatch, const voi
 // B_blinding and B (a row of three generator-table scalars: G_0 takes 0), C and R decode in the chain -- then the verdicts
 static int opn_verify_dev_locked(bpgpu_ctx *c, int form, size_t nbatch, const void *d_proofs, const ipp_ts &ts, const void *d_C, const void *d_values,
                                  size_t value_bytes, void *d_verdict, void *d_msm_out, void *d_ts_out, hipStream_t s) {
-    opn_staged stg;
+    front_staged stg;
     int rc = opn_front_dev_locked(c, form, nbatch, d_proofs, ts, d_C, d_values, value_bytes, d_ts_out, s, stg);
     if (rc) return rc;
     rc = msm_shared_dev_locked(c, 1, 1, nbatch, 2, stg.d_gen, stg.d_sc, stg.d_pt, stg.d_out, stg.d_mst, nullptr, s, true);
@@ -7153,30 +7099,20 @@ static int opn_verify_dev_locked(bpgpu_ctx *c, int form, size_t nbatch, const vo
 // over 2 nbatch points, then the verdicts (undecided where R is not the identity).  Nothing is staged per (proof, generator).
 static int opn_rlc_dev_locked(bpgpu_ctx *c, int form, size_t nbatch, const void *d_proofs, const ipp_ts &ts, const void *d_C, const void *d_values,
                               size_t value_bytes, const void *d_weights64, uint8_t *d_verdict, uint8_t *d_batch, void *d_ts_out, hipStream_t s) {
-    opn_staged stg;
+    front_staged stg;
     int rc = opn_front_dev_locked(c, form, nbatch, d_proofs, ts, d_C, d_values, value_bytes, d_ts_out, s, stg);
     if (rc) return rc;
     const size_t nterms = 2 * nbatch;
-    arena_plan ap;
-    const size_t off_csc = ap.add(nterms * 32 + 64), off_cpt = ap.add(nterms * 32 + 64), off_acc = ap.add(OPN_GEN_ROW * 80), off_row = ap.add(OPN_GEN_ROW * 32 + 64),
-                 off_rho = ap.add(nbatch * 32), off_bo = ap.add(64);
-    rc = comb_reserve(c, ap.total);
+    comb_layout lay(nterms * 32 + 64, OPN_GEN_ROW * 80, OPN_GEN_ROW * 32 + 64, nbatch * 32);
+    rc = lay.reserve(c, &d_batch);
     if (rc) return rc;
-    char *b = c->comb_buf, *d_csc = b + off_csc, *d_cpt = b + off_cpt, *d_acc = b + off_acc, *d_row = b + off_row, *d_rho = b + off_rho, *d_bo = b + off_bo;
-    if (!d_batch) d_batch = (uint8_t *)d_bo;
     const uint32_t nb32 = (uint32_t)nbatch, nstride = (uint32_t)((nbatch + 63) / 64 * 64);
-    rc = comb_rho_locked(c, s, "opn_rlc_rho", nb32, d_weights64, OPN_RLC_WEIGHT_DOMAIN, d_rho);
+    rc = comb_begin_locked(c, s, "opn_rlc_rho", lay, nb32, d_weights64, OPN_RLC_WEIGHT_DOMAIN, OPN_GEN_ROW);   // (the row of G_0 stays 0)
     if (rc) return rc;
-    HIPCHK(c, hipMemsetAsync(d_acc, 0, OPN_GEN_ROW * 80, s));   // (the row of G_0 stays 0)
-    LAUNCH(c, s, "opn_rlc_weigh", k_opn_rlc_weigh, 4 * nstride / 64, 64, nb32, nstride, (const uint32_t *)stg.d_stat, (const uint32_t *)d_rho,
-           (const uint32_t *)stg.d_gen, (const uint32_t *)stg.d_sc, (const uint32_t *)stg.d_pt, (uint32_t *)d_csc, (uint32_t *)d_cpt, (unsigned long long *)d_acc);
-    LAUNCH(c, s, "opn_rlc_reduce", k_rlc_comb_reduce, 1, 64, OPN_GEN_ROW, (const unsigned long long *)d_acc, (uint32_t *)d_row);
-    rc = msm_shared_dev_locked(c, 1, 1, 1, nterms, d_row, d_csc, d_cpt, stg.d_out, stg.d_mst, nullptr, s, true);
-    if (rc) return rc;
-    LAUNCH(c, s, "opn_rlc_verdict", k_rlc_comb_verdict, (nb32 + 63) / 64, 64, nb32, (const uint32_t *)stg.d_stat, (const uint32_t *)stg.d_out,
-           (const uint8_t *)stg.d_mst, d_verdict, d_batch);
-    HIPCHK(c, hipGetLastError());
-    return BPGPU_OK;
+    LAUNCH(c, s, "opn_rlc_weigh", k_opn_rlc_weigh, 4 * nstride / 64, 64, nb32, nstride, (const uint32_t *)stg.d_stat, (const uint32_t *)lay.d_rho,
+           (const uint32_t *)stg.d_gen, (const uint32_t *)stg.d_sc, (const uint32_t *)stg.d_pt, (uint32_t *)lay.d_csc, (uint32_t *)lay.d_cpt,
+           (unsigned long long *)lay.d_acc);
+    return comb_finish_locked(c, s, "opn_rlc_reduce", "opn_rlc_verdict", lay, stg, OPN_GEN_ROW, 1, 1, true, nterms, nb32, d_verdict, d_batch);
 }
 
 // host pointers, both verifiers: rlc = the combined check with its per-proof fallback
@@ -7207,9 +7143,7 @@ static int opn_verify_host_call(bpgpu_ctx *c, int form, size_t nbatch, const uin
     if (values) io.put(r_val, values, nbatch * value_bytes);
     io.put(r_ti, transcripts, nstates * TS);
     if (weights64) io.put(r_w, weights64, nbatch * 64);
-    ipp_ts ts;
-    ts.d_in = io.d(r_ti);
-    ts.stride = transcript_stride ? BP_TS_WORDS : 0;
+    const ipp_ts ts = ipp_ts_staged(io.d(r_ti), transcript_stride);
     const void *a_val = values ? io.d(r_val) : nullptr;
     void *a_to = transcripts_out ? io.d(r_t) : nullptr;
     rc = io.upload();
@@ -7221,20 +7155,12 @@ static int opn_verify_host_call(bpgpu_ctx *c, int form, size_t nbatch, const uin
     }
     rc = io.finish(io.download(rc));
     if (rc) return rc;
+    if (rlc)   // where R is not the identity, or a point of the combined MSM did not decode: the batch again through the per-proof path
+        return io.deliver_combined(r_v, verdict, nbatch, r_o, batch_out, r_t, transcripts_out, nbatch * TS, [&] {
+            return opn_verify_dev_locked(c, form, nbatch, io.d(r_pr), ts, io.d(r_c), a_val, value_bytes, io.d(r_v), nullptr, nullptr, s);
+        });
     if (transcripts_out) memcpy(transcripts_out, io.h(r_t), nbatch * TS);
-    if (rlc) {
-        if (batch_out) memcpy(batch_out, io.h(r_o), 33);   // (R as computed before any fallback)
-        if ((uint8_t)io.h(r_o)[0] != 0) {
-            // R is not the identity, or a point of the combined MSM did not decode: the batch again through the per-proof path (inputs are
-            // still on the device; the transcripts it leaves are the ones already copied out)
-            rc = io.rerun_per_proof(r_v, r_o, [&] {
-                return opn_verify_dev_locked(c, form, nbatch, io.d(r_pr), ts, io.d(r_c), a_val, value_bytes, io.d(r_v), nullptr, nullptr, s);
-            });
-            if (rc) return rc;
-        }
-    } else if (msm_out) {
-        memcpy(msm_out, io.h(r_o), nbatch * 32);
-    }
+    if (msm_out) memcpy(msm_out, io.h(r_o), nbatch * 32);
     memcpy(verdict, io.h(r_v), nbatch);
     return BPGPU_OK;
 }
@@ -7264,16 +7190,12 @@ static int opn_verify_dev_call(bpgpu_ctx *c, int form, size_t nbatch, const void
     if (nbatch == 0) return BPGPU_OK;
     if (!d_proofs || !d_commitments || !d_verdict) return BPGPU_ERR_INVALID_ARG;
     if (((uintptr_t)d_proofs | (uintptr_t)d_commitments | (uintptr_t)d_values) & 3) return fail(c, BPGPU_ERR_INVALID_ARG, "device buffers must be 4-byte aligned");
-    std::lock_guard<std::mutex> lk(c->mu);
-    HIPCHK(c, hipSetDevice(c->device));
-    hipStream_t s = stream ? (hipStream_t)stream : c->stream;
-    if ((rc = ctx_enter(c, s))) return rc;
-    if (rlc)
-        rc = opn_rlc_dev_locked(c, form, nbatch, d_proofs, ts, d_commitments, d_values, value_bytes, d_weights64, (uint8_t *)d_verdict, (uint8_t *)d_out,
-                                d_transcripts_out, s);
-    else rc = opn_verify_dev_locked(c, form, nbatch, d_proofs, ts, d_commitments, d_values, value_bytes, d_verdict, d_out, d_transcripts_out, s);
-    const int rc2 = ctx_leave(c, s);
-    return rc ? rc : rc2;
+    return dev_call(c, stream, [&](hipStream_t s) {
+        if (rlc)
+            return opn_rlc_dev_locked(c, form, nbatch, d_proofs, ts, d_commitments, d_values, value_bytes, d_weights64, (uint8_t *)d_verdict, (uint8_t *)d_out,
+                                      d_transcripts_out, s);
+        return opn_verify_dev_locked(c, form, nbatch, d_proofs, ts, d_commitments, d_values, value_bytes, d_verdict, d_out, d_transcripts_out, s);
+    });
 }
 extern "C" int bpgpu_opening_verify_batch_ts_dev(bpgpu_ctx *c, int form, size_t nbatch, const void *d_proofs, size_t proof_len, const uint8_t *shared_transcript,
                                                  const void *d_transcripts, const void *d_commitments, const void *d_values, size_t value_bytes, void *d_verdict,
@@ -7321,10 +7243,9 @@ extern "C" int bpgpu_opening_create_batch_ts(bpgpu_ctx *c, int form, size_t nbat
         uint32_t *d_ids = nullptr;
         if ((rc = gen_ids_for(c, 1, 1, &d_ids))) break;   // the shared path's list: [0] = B_blinding, [1] = B
         const bool ct = c->prover_ct;
-        if (ct && (rc = build_ct_table(c))) break;
-        ipp_ts ts;
-        ts.d_in = io.d(r_ti);
-        ts.stride = transcript_stride ? BP_TS_WORDS : 0;
+        fb_walk w;
+        if ((rc = fb_walk_for(c, ct, w))) break;
+        const ipp_ts ts = ipp_ts_staged(io.d(r_ti), transcript_stride);
         const opn_shape sh = opn_make_shape(form, nbatch, values, value_bytes, ts);
         opn_create_in in;
         in.values = values ? (const uint32_t *)io.d(r_val) : nullptr;
@@ -7334,12 +7255,8 @@ extern "C" int bpgpu_opening_create_batch_ts(bpgpu_ctx *c, int form, size_t nbat
         in.ts_in = (const uint32_t *)io.d(r_ti);
         const uint32_t grid = (sh.nproofs + BP_BLOCK - 1) / BP_BLOCK;
         uint32_t *d_to = transcripts_out ? (uint32_t *)io.d(r_t) : nullptr;
-        if (ct)
-            LAUNCH(c, s, "opn_create_ct", k_opn_create<true>, grid, BP_BLOCK, sh, in, c->prm_ct, (const uint32_t *)d_ids, (const fb_entry *)c->d_table_ct,
-                   (uint32_t *)io.d(r_pr), (uint8_t *)io.d(r_st), d_to);
-        else
-            LAUNCH(c, s, "opn_create", k_opn_create<false>, grid, BP_BLOCK, sh, in, c->prm, (const uint32_t *)d_ids, (const fb_entry *)c->d_table,
-                   (uint32_t *)io.d(r_pr), (uint8_t *)io.d(r_st), d_to);
+        LAUNCH_CT(c, s, ct, "opn_create", k_opn_create, grid, BP_BLOCK, sh, in, w.prm, (const uint32_t *)d_ids, w.table, (uint32_t *)io.d(r_pr), (uint8_t *)io.d(r_st),
+                  d_to);
         if (hipGetLastError() != hipSuccess) rc = fail(c, BPGPU_ERR_HIP, "launch failed");
     } while (0);
     rc = io.finish(io.download(rc));
@@ -7374,10 +7291,10 @@ static int rwd_launch_locked(bpgpu_ctx *c, hipStream_t s, const rwd_shape &sh, c
     int rc = gen_ids_for(c, 1, 1, &d_ids);   // the shared path's list: [0] = B_blinding, [1] = B
     if (rc) return rc;
     const bool ct = c->prover_ct;
-    if (ct && (rc = build_ct_table(c))) return rc;
+    fb_walk w;
+    if ((rc = fb_walk_for(c, ct, w))) return rc;
     const uint32_t grid = (sh.nproofs + BP_BLOCK - 1) / BP_BLOCK;
-    if (ct) LAUNCH(c, s, "rewind_ct", k_rewind<true>, grid, BP_BLOCK, sh, in, out, c->prm_ct, (const uint32_t *)d_ids, (const fb_entry *)c->d_table_ct);
-    else LAUNCH(c, s, "rewind", k_rewind<false>, grid, BP_BLOCK, sh, in, out, c->prm, (const uint32_t *)d_ids, (const fb_entry *)c->d_table);
+    LAUNCH_CT(c, s, ct, "rewind", k_rewind, grid, BP_BLOCK, sh, in, out, w.prm, (const uint32_t *)d_ids, w.table);
     if (hipGetLastError() != hipSuccess) return fail(c, BPGPU_ERR_HIP, "launch failed");
     return BPGPU_OK;
 }
@@ -7445,17 +7362,12 @@ extern "C" int bpgpu_rangeproof_rewind_batch_dev(bpgpu_ctx *c, size_t n, size_t 
     if (((uintptr_t)d_values_out & 7) ||
         (((uintptr_t)d_proofs | (uintptr_t)d_commitments | (uintptr_t)d_transcripts | (uintptr_t)d_rng32 | (uintptr_t)d_messages_out | (uintptr_t)d_blindings_out) & 3))
         return fail(c, BPGPU_ERR_INVALID_ARG, "device buffers must be 4-byte aligned (values: 8-byte)");
-    std::lock_guard<std::mutex> lk(c->mu);
-    HIPCHK(c, hipSetDevice(c->device));
-    if (!c->d_table) return fail(c, BPGPU_ERR_NO_GENS, "generators not loaded");
-    hipStream_t s = stream ? (hipStream_t)stream : c->stream;
-    if ((rc = ctx_enter(c, s))) return rc;
     sh.ts_in_stride = transcript_stride ? BP_TS_WORDS : 0;
     const rwd_in in = {(const uint32_t *)d_proofs, (const uint32_t *)d_commitments, (const uint8_t *)d_rng32, (const uint32_t *)d_transcripts};
     const rwd_out out = {(uint8_t *)d_status_out, (uint32_t *)d_values_out, (uint32_t *)d_messages_out, (uint32_t *)d_blindings_out};
-    rc = rwd_launch_locked(c, s, sh, in, out);
-    const int rc2 = ctx_leave(c, s);
-    return rc ? rc : rc2;
+    return dev_call(
+        c, stream, [&] { return c->d_table ? BPGPU_OK : fail(c, BPGPU_ERR_NO_GENS, "generators not loaded"); },
+        [&](hipStream_t s) { return rwd_launch_locked(c, s, sh, in, out); });
 }
 
 // ============================================================================
@@ -7476,7 +7388,8 @@ static int scn_launch_locked(bpgpu_ctx *c, hipStream_t s, const rwd_shape &sh, c
     int rc = gen_ids_for(c, 1, 1, &d_ids);   // [0] = B_blinding, [1] = B
     if (rc) return rc;
     const bool ct = c->prover_ct;
-    if (ct && (rc = build_ct_table(c))) return rc;
+    fb_walk w;
+    if ((rc = fb_walk_for(c, ct, w))) return rc;
     const size_t nb = sh.nproofs;
     arena_plan ap;
     const size_t off_pre = ap.add((size_t)nkeys * BP_TS_WORDS * 4), off_base = ap.add(BP_TS_WORDS * 4), off_st = ap.add(nb * 4), off_xz = ap.add(nb * 64),
@@ -7490,14 +7403,8 @@ static int scn_launch_locked(bpgpu_ctx *c, hipStream_t s, const rwd_shape &sh, c
     const uint32_t grid = (sh.nproofs + BP_BLOCK - 1) / BP_BLOCK;
     LAUNCH(c, s, "scan_prefix", k_scan_prefix, (nkeys + BP_BLOCK - 1) / BP_BLOCK, BP_BLOCK, keys, ws);
     LAUNCH(c, s, "scan_replay", k_scan_replay, grid, BP_BLOCK, sh, in, ws);
-    if (ct) {
-        LAUNCH(c, s, "scan_cand_ct", k_scan_cand<true>, dim3(grid, nkeys), BP_BLOCK, sh, in, ws);
-        LAUNCH(c, s, "scan_open_ct", k_scan_open<true>, grid, BP_BLOCK, sh, in, keys, ws, out, d_key_index, c->prm_ct, (const uint32_t *)d_ids,
-               (const fb_entry *)c->d_table_ct);
-    } else {
-        LAUNCH(c, s, "scan_cand", k_scan_cand<false>, dim3(grid, nkeys), BP_BLOCK, sh, in, ws);
-        LAUNCH(c, s, "scan_open", k_scan_open<false>, grid, BP_BLOCK, sh, in, keys, ws, out, d_key_index, c->prm, (const uint32_t *)d_ids, (const fb_entry *)c->d_table);
-    }
+    LAUNCH_CT(c, s, ct, "scan_cand", k_scan_cand, dim3(grid, nkeys), BP_BLOCK, sh, in, ws);
+    LAUNCH_CT(c, s, ct, "scan_open", k_scan_open, grid, BP_BLOCK, sh, in, keys, ws, out, d_key_index, w.prm, (const uint32_t *)d_ids, w.table);
     if (hipGetLastError() != hipSuccess) return fail(c, BPGPU_ERR_HIP, "launch failed");
     return BPGPU_OK;
 }
@@ -7568,18 +7475,18 @@ extern "C" int bpgpu_rangeproof_scan_batch_dev(bpgpu_ctx *c, size_t n, size_t nb
     if (((uintptr_t)d_values_out & 7) || (((uintptr_t)d_proofs | (uintptr_t)d_commitments | (uintptr_t)d_transcripts | (uintptr_t)d_keys32 | (uintptr_t)d_key_index_out |
                                            (uintptr_t)d_messages_out | (uintptr_t)d_blindings_out) & 3))
         return fail(c, BPGPU_ERR_INVALID_ARG, "device buffers must be 4-byte aligned (values: 8-byte)");
-    std::lock_guard<std::mutex> lk(c->mu);
-    HIPCHK(c, hipSetDevice(c->device));
+    dev_scope<bpgpu_ctx> sc(c);
+    if (sc.rc) return sc.rc;
     if (!c->d_table) return fail(c, BPGPU_ERR_NO_GENS, "generators not loaded");
-    hipStream_t s = stream ? (hipStream_t)stream : c->stream;
-    if ((rc = ctx_enter(c, s))) return rc;
+    if ((rc = sc.enter(stream))) return rc;
+    hipStream_t s = sc.s;
     sh.ts_in_stride = transcript_stride ? BP_TS_WORDS : 0;
     const rwd_in in = {(const uint32_t *)d_proofs, (const uint32_t *)d_commitments, nullptr, (const uint32_t *)d_transcripts};
     const rwd_out out = {(uint8_t *)d_status_out, (uint32_t *)d_values_out, (uint32_t *)d_messages_out, (uint32_t *)d_blindings_out};
     size_t ws_bytes = 0;   // (what this call laid out in the arena: all that it wrote there)
     rc = scn_launch_locked(c, s, sh, in, (const uint32_t *)d_keys32, (uint32_t)nkeys, out, (uint32_t *)d_key_index_out, &ws_bytes);
     const bool ok = !ws_bytes || hipMemsetAsync(c->arena, 0, ws_bytes, s) == hipSuccess;
-    const int rc2 = ctx_leave(c, s);
+    const int rc2 = sc.leave();
     if (!rc && !ok) rc = fail(c, BPGPU_ERR_HIP, "clearing the scan's working set failed");
     return rc ? rc : rc2;
 }
@@ -7661,23 +7568,14 @@ static int sig_check_gens_locked(bpgpu_ctx *c, const bpgpu_sigma_relation *rel) 
     return BPGPU_OK;
 }
 
-// what the front end leaves on the device (c->ipp_buf) for the multiscalar multiplication(s)
-struct sig_staged {
-    char *d_sc = nullptr, *d_pt = nullptr, *d_gen = nullptr, *d_stat = nullptr, *d_mst = nullptr, *d_out = nullptr;
-};
 // the staging and the k_sig_front launch (lane = proof) of nbatch proofs: nbatch E rows of P + 1 unique terms and 2 + G generator columns
 static int sig_front_dev_locked(bpgpu_ctx *c, const bpgpu_sigma_relation *rel, size_t nbatch, const void *d_proofs, const ipp_ts &ts, const void *d_points,
-                                void *d_ts_out, hipStream_t s, sig_staged &stg) {
+                                void *d_ts_out, hipStream_t s, front_staged &stg) {
     int rc = sig_check_gens_locked(c, rel);
     if (rc) return rc;
     const size_t rows = nbatch * rel->h.E, U = sig_uniq(rel->h), GR = sig_gen_row(rel->h);
-    const size_t sz_terms = align_up(rows * U * 32 + 64), sz_gen = align_up(rows * GR * 32 + 64), sz_st = align_up(nbatch * 4), sz_b = align_up(rows + 64),
-                 sz_o = align_up(rows * 32 + 64);
-    rc = ipp_reserve(c, 2 * sz_terms + sz_gen + sz_st + sz_b + sz_o);
+    rc = front_stage_locked(c, s, rows * U * 32 + 64, rows * GR * 32 + 64, nbatch * 4, rows + 64, rows * 32 + 64, stg);
     if (rc) return rc;
-    stg.d_sc = c->ipp_buf, stg.d_pt = stg.d_sc + sz_terms, stg.d_gen = stg.d_pt + sz_terms, stg.d_stat = stg.d_gen + sz_gen, stg.d_mst = stg.d_stat + sz_st,
-    stg.d_out = stg.d_mst + sz_b;
-    HIPCHK(c, hipMemsetAsync(stg.d_sc, 0, 2 * sz_terms + sz_gen + sz_st, s));   // scalars, points, generator rows, status
     rp_strobe_init init;
     ipp_ts_init(init, ts);
     const uint32_t nb32 = (uint32_t)nbatch;
@@ -7690,7 +7588,7 @@ static int sig_front_dev_locked(bpgpu_ctx *c, const bpgpu_sigma_relation *rel, s
 // per proof: the front end, then the shared-generator chain with one row per (proof, equation), then the verdicts
 static int sig_verify_dev_locked(bpgpu_ctx *c, const bpgpu_sigma_relation *rel, size_t nbatch, const void *d_proofs, const ipp_ts &ts, const void *d_points,
                                  void *d_verdict, void *d_msm_out, void *d_ts_out, hipStream_t s) {
-    sig_staged stg;
+    front_staged stg;
     int rc = sig_front_dev_locked(c, rel, nbatch, d_proofs, ts, d_points, d_ts_out, s, stg);
     if (rc) return rc;
     const size_t rows = nbatch * rel->h.E;
@@ -7709,31 +7607,21 @@ static int sig_verify_dev_locked(bpgpu_ctx *c, const bpgpu_sigma_relation *rel, 
 // then the verdicts (undecided where R is not the identity)
 static int sig_rlc_dev_locked(bpgpu_ctx *c, const bpgpu_sigma_relation *rel, size_t nbatch, const void *d_proofs, const ipp_ts &ts, const void *d_points,
                               const void *d_weights64, uint8_t *d_verdict, uint8_t *d_batch, void *d_ts_out, hipStream_t s) {
-    sig_staged stg;
+    front_staged stg;
     int rc = sig_front_dev_locked(c, rel, nbatch, d_proofs, ts, d_points, d_ts_out, s, stg);
     if (rc) return rc;
     const size_t NU = rel->h.P + rel->h.E, GR = sig_gen_row(rel->h), nterms = NU * nbatch, nrho = nbatch * rel->h.E;
-    arena_plan ap;
-    const size_t off_csc = ap.add(nterms * 32 + 64), off_cpt = ap.add(nterms * 32 + 64), off_acc = ap.add(GR * 80), off_row = ap.add(GR * 32 + 64),
-                 off_rho = ap.add(nrho * 32), off_bo = ap.add(64);
-    rc = comb_reserve(c, ap.total);
+    comb_layout lay(nterms * 32 + 64, GR * 80, GR * 32 + 64, nrho * 32);
+    rc = lay.reserve(c, &d_batch);
     if (rc) return rc;
-    char *b = c->comb_buf, *d_csc = b + off_csc, *d_cpt = b + off_cpt, *d_acc = b + off_acc, *d_row = b + off_row, *d_rho = b + off_rho, *d_bo = b + off_bo;
-    if (!d_batch) d_batch = (uint8_t *)d_bo;
     const uint32_t nb32 = (uint32_t)nbatch, nstride = (uint32_t)((nbatch + 63) / 64 * 64);
-    rc = comb_rho_locked(c, s, "sig_rlc_rho", (uint32_t)nrho, d_weights64, SIG_RLC_WEIGHT_DOMAIN, d_rho);
+    rc = comb_begin_locked(c, s, "sig_rlc_rho", lay, (uint32_t)nrho, d_weights64, SIG_RLC_WEIGHT_DOMAIN, GR);
     if (rc) return rc;
-    HIPCHK(c, hipMemsetAsync(d_acc, 0, GR * 80, s));
     LAUNCH(c, s, "sig_rlc_weigh", k_sig_rlc_weigh, (uint32_t)((NU + GR) * nstride / 64), 64, (const sig_rel *)rel->d, nb32, nstride, (const uint32_t *)stg.d_stat,
-           (const uint32_t *)d_rho, (const uint32_t *)stg.d_gen, (const uint32_t *)stg.d_sc, (const uint32_t *)stg.d_pt, (const uint32_t *)d_points,
-           (uint32_t *)d_csc, (uint32_t *)d_cpt, (unsigned long long *)d_acc);
-    LAUNCH(c, s, "sig_rlc_reduce", k_rlc_comb_reduce, 1, 64, (uint32_t)GR, (const unsigned long long *)d_acc, (uint32_t *)d_row);
-    rc = msm_shared_dev_locked(c, rel->h.G, 1, 1, nterms, d_row, d_csc, d_cpt, stg.d_out, stg.d_mst, nullptr, s, true);
-    if (rc) return rc;
-    LAUNCH(c, s, "sig_rlc_verdict", k_rlc_comb_verdict, (nb32 + 63) / 64, 64, nb32, (const uint32_t *)stg.d_stat, (const uint32_t *)stg.d_out,
-           (const uint8_t *)stg.d_mst, d_verdict, d_batch);
-    HIPCHK(c, hipGetLastError());
-    return BPGPU_OK;
+           (const uint32_t *)lay.d_rho, (const uint32_t *)stg.d_gen, (const uint32_t *)stg.d_sc, (const uint32_t *)stg.d_pt, (const uint32_t *)d_points,
+           (uint32_t *)lay.d_csc, (uint32_t *)lay.d_cpt, (unsigned long long *)lay.d_acc);
+    // (GR <= 10: the reduce is one workgroup)
+    return comb_finish_locked(c, s, "sig_rlc_reduce", "sig_rlc_verdict", lay, stg, GR, rel->h.G, 1, true, nterms, nb32, d_verdict, d_batch);
 }
 
 // host pointers, both verifiers: rlc = the combined check with its per-proof fallback
@@ -7762,9 +7650,7 @@ static int sig_verify_host_call(bpgpu_ctx *c, const bpgpu_sigma_relation *rel, s
     io.put(r_p, points, nbatch * P * 32);
     io.put(r_ti, transcripts, nstates * TS);
     if (weights64) io.put(r_w, weights64, nbatch * E * 64);
-    ipp_ts ts;
-    ts.d_in = io.d(r_ti);
-    ts.stride = transcript_stride ? BP_TS_WORDS : 0;
+    const ipp_ts ts = ipp_ts_staged(io.d(r_ti), transcript_stride);
     void *a_to = transcripts_out ? io.d(r_t) : nullptr;
     rc = io.upload();
     if (!rc) {
@@ -7774,18 +7660,11 @@ static int sig_verify_host_call(bpgpu_ctx *c, const bpgpu_sigma_relation *rel, s
     }
     rc = io.finish(io.download(rc));
     if (rc) return rc;
+    if (rlc)   // where R is not the identity, or a point of the combined MSM did not decode: the batch again through the per-proof path
+        return io.deliver_combined(r_v, verdict, nbatch, r_o, batch_out, r_t, transcripts_out, nbatch * TS,
+                                   [&] { return sig_verify_dev_locked(c, rel, nbatch, io.d(r_pr), ts, io.d(r_p), io.d(r_v), nullptr, nullptr, s); });
     if (transcripts_out) memcpy(transcripts_out, io.h(r_t), nbatch * TS);
-    if (rlc) {
-        if (batch_out) memcpy(batch_out, io.h(r_o), 33);   // (R as computed before any fallback)
-        if ((uint8_t)io.h(r_o)[0] != 0) {
-            // R is not the identity, or a point of the combined MSM did not decode: the batch again through the per-proof path (inputs are
-            // still on the device; the transcripts it leaves are the ones already copied out)
-            rc = io.rerun_per_proof(r_v, r_o, [&] { return sig_verify_dev_locked(c, rel, nbatch, io.d(r_pr), ts, io.d(r_p), io.d(r_v), nullptr, nullptr, s); });
-            if (rc) return rc;
-        }
-    } else if (msm_out) {
-        memcpy(msm_out, io.h(r_o), nbatch * E * 32);
-    }
+    if (msm_out) memcpy(msm_out, io.h(r_o), nbatch * E * 32);
     memcpy(verdict, io.h(r_v), nbatch);
     return BPGPU_OK;
 }
@@ -7813,14 +7692,10 @@ static int sig_verify_dev_call(bpgpu_ctx *c, const bpgpu_sigma_relation *rel, si
     if (nbatch == 0) return BPGPU_OK;
     if (!d_proofs || !d_points || !d_verdict) return BPGPU_ERR_INVALID_ARG;
     if (((uintptr_t)d_proofs | (uintptr_t)d_points) & 3) return fail(c, BPGPU_ERR_INVALID_ARG, "device buffers must be 4-byte aligned");
-    std::lock_guard<std::mutex> lk(c->mu);
-    HIPCHK(c, hipSetDevice(c->device));
-    hipStream_t s = stream ? (hipStream_t)stream : c->stream;
-    if ((rc = ctx_enter(c, s))) return rc;
-    if (rlc) rc = sig_rlc_dev_locked(c, rel, nbatch, d_proofs, ts, d_points, d_weights64, (uint8_t *)d_verdict, (uint8_t *)d_out, d_transcripts_out, s);
-    else rc = sig_verify_dev_locked(c, rel, nbatch, d_proofs, ts, d_points, d_verdict, d_out, d_transcripts_out, s);
-    const int rc2 = ctx_leave(c, s);
-    return rc ? rc : rc2;
+    return dev_call(c, stream, [&](hipStream_t s) {
+        if (rlc) return sig_rlc_dev_locked(c, rel, nbatch, d_proofs, ts, d_points, d_weights64, (uint8_t *)d_verdict, (uint8_t *)d_out, d_transcripts_out, s);
+        return sig_verify_dev_locked(c, rel, nbatch, d_proofs, ts, d_points, d_verdict, d_out, d_transcripts_out, s);
+    });
 }
 extern "C" int bpgpu_sigma_verify_batch_ts_dev(bpgpu_ctx *c, const bpgpu_sigma_relation *rel, size_t nbatch, const void *d_proofs, size_t proof_len,
                                                const uint8_t *shared_transcript, const void *d_transcripts, const void *d_points, void *d_verdict,
@@ -7868,7 +7743,8 @@ extern "C" int bpgpu_sigma_create_batch_ts(bpgpu_ctx *c, const bpgpu_sigma_relat
     if ((rc = io.upload())) return io.finish(rc);
     do {
         const bool ct = c->prover_ct;
-        if (ct && (rc = build_ct_table(c))) break;
+        fb_walk w;
+        if ((rc = fb_walk_for(c, ct, w))) break;
         const uint32_t nb32 = (uint32_t)nbatch, nvb = rel->h.nvb, E = rel->h.E;
         uint32_t slice = SIG_CREATE_LANES / (nvb ? nvb : 1) / 64 * 64;   // (nvb <= 32: at least 2 048 rows)
         if (slice > nb32) slice = (nb32 + 63) / 64 * 64;
@@ -7893,16 +7769,8 @@ extern "C" int bpgpu_sigma_create_batch_ts(bpgpu_ctx *c, const bpgpu_sigma_relat
         for (uint32_t row0 = 0; row0 < nb32; row0 += slice) {   // (slices run one after another on the stream: they share the workspace)
             ws.row0 = row0;
             const uint32_t nslice = std::min<uint32_t>(slice, nb32 - row0);
-            if (nvb) {
-                if (ct) LAUNCH(c, s, "sig_vb_ct", k_sig_vb<true>, nvb * slice / BP_BLOCK, BP_BLOCK, (const sig_rel *)rel->d, in, ws);
-                else LAUNCH(c, s, "sig_vb", k_sig_vb<false>, nvb * slice / BP_BLOCK, BP_BLOCK, (const sig_rel *)rel->d, in, ws);
-            }
-            if (ct)
-                LAUNCH(c, s, "sig_walk_ct", k_sig_walk<true>, E * slice / BP_BLOCK, BP_BLOCK, rel->h, in, ws, nslice, c->prm_ct, (const fb_entry *)c->d_table_ct,
-                       (uint32_t *)io.d(r_pr));
-            else
-                LAUNCH(c, s, "sig_walk", k_sig_walk<false>, E * slice / BP_BLOCK, BP_BLOCK, rel->h, in, ws, nslice, c->prm, (const fb_entry *)c->d_table,
-                       (uint32_t *)io.d(r_pr));
+            if (nvb) LAUNCH_CT(c, s, ct, "sig_vb", k_sig_vb, nvb * slice / BP_BLOCK, BP_BLOCK, (const sig_rel *)rel->d, in, ws);
+            LAUNCH_CT(c, s, ct, "sig_walk", k_sig_walk, E * slice / BP_BLOCK, BP_BLOCK, rel->h, in, ws, nslice, w.prm, w.table, (uint32_t *)io.d(r_pr));
         }
         LAUNCH(c, s, "sig_finish", k_sig_finish, (nb32 + RP_BLOCK - 1) / RP_BLOCK, RP_BLOCK, (const sig_rel *)rel->d, in, (const uint32_t *)ws.bad,
                (uint32_t *)io.d(r_pr), (uint8_t *)io.d(r_st), transcripts_out ? (uint32_t *)io.d(r_t) : nullptr);

@@ -2,10 +2,13 @@
 // runtime, tests/cpu_host_io/).
 //   host_staging: the context's pinned block, its guard event and the persistent device IO buffer.
 //   host_call:    ONE call's use of them -- regions declared in order, one H2D copy, one D2H copy, one wait.
+//   dev_scope / dev_call: ONE device-pointer call -- lock, device, stream, ctx_enter ... ctx_leave on every path.
 #pragma once
 #include <hip/hip_runtime_api.h>
 
+#include <cstdint>
 #include <cstring>
+#include <mutex>
 #include <string>
 #include <vector>
 
@@ -237,4 +240,67 @@ struct host_call {
         memcpy(h(r_batch), bo, 33);
         return 0;
     }
+    // What a combined check hands to its caller once finish() has succeeded: batch_out (33 bytes) and the transcripts are the first
+    // pass's; the verdicts are the first pass's where the combination decided (byte 0 of the batch result is 0), the per-proof
+    // rerun's otherwise.  A failed rerun is returned and leaves the caller's verdicts untouched.  batch_out / ts_out may be null.
+    template <class F>
+    int deliver_combined(int r_verdict, uint8_t *verdict, size_t verdict_bytes, int r_batch, uint8_t *batch_out, int r_ts, uint8_t *ts_out, size_t ts_bytes,
+                         F per_proof) {
+        if (batch_out) memcpy(batch_out, h(r_batch), 33);
+        if (ts_out) memcpy(ts_out, h(r_ts), ts_bytes);
+        if ((uint8_t)h(r_batch)[0] != 0) {
+            const int rc = rerun_per_proof(r_verdict, r_batch, per_proof);
+            if (rc) return rc;
+        }
+        memcpy(verdict, h(r_verdict), verdict_bytes);
+        return 0;
+    }
 };
+
+// One device-pointer call.  Ctx has `std::mutex mu`, `int device`, `hipStream_t stream`, `host_staging io` and the free functions
+// ctx_enter / ctx_leave.  The scope holds the lock from its construction and has set the device (rc: why it could not); after a
+// successful enter() the context is left exactly once -- by leave(), or by the destructor on a path that returned without it.
+template <class Ctx>
+struct dev_scope {
+    Ctx *c;
+    std::lock_guard<std::mutex> lk;
+    hipStream_t s = nullptr;
+    bool entered = false;
+    int rc = 0;
+
+    explicit dev_scope(Ctx *c_) : c(c_), lk(c_->mu) {
+        const hipError_t e = hipSetDevice(c->device);
+        if (e != hipSuccess) rc = c->io.hip_failed("hipSetDevice(c->device) failed", e);
+    }
+    ~dev_scope() {
+        if (entered) (void)ctx_leave(c, s);
+    }
+    // the caller's stream, or the context's own where it gives none
+    int enter(void *stream) {
+        s = stream ? (hipStream_t)stream : c->stream;
+        const int rce = ctx_enter(c, s, false);
+        entered = !rce;
+        return rce;
+    }
+    int leave() {
+        entered = false;
+        return ctx_leave(c, s);
+    }
+};
+// ... and the whole of it where nothing happens behind the leave: `pre` (checks of the context's state, under the lock) refuses before the
+// context is entered; then the body's code if non-zero, else ctx_leave's; ctx_enter's, and no body, where that fails
+template <class Ctx, class P, class F>
+static inline int dev_call(Ctx *c, void *stream, P pre, F body) {
+    dev_scope<Ctx> sc(c);
+    if (sc.rc) return sc.rc;
+    int rc = pre();
+    if (!rc) rc = sc.enter(stream);
+    if (rc) return rc;
+    rc = body(sc.s);
+    const int rc2 = sc.leave();
+    return rc ? rc : rc2;
+}
+template <class Ctx, class F>
+static inline int dev_call(Ctx *c, void *stream, F body) {
+    return dev_call(c, stream, [] { return 0; }, body);
+}

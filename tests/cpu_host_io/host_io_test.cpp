@@ -3,7 +3,8 @@
 // malloc'ed -- a pinned block freed while a copy is queued, or read after it was freed, is a use-after-free AddressSanitizer reports.
 // The context below has what bpgpu.hip's has around the staging: ctx_enter / ctx_leave / host_wait, a pending submitted result, three
 // working sets a prover clears.  These are re-implementations: host_io.h must not need bpgpu_ctx, so the production ctx_enter /
-// collect_locked glue of bpgpu.hip itself is covered by the GPU suite only; what runs here is host_staging and host_call.
+// collect_locked glue of bpgpu.hip itself is covered by the GPU suite only; what runs here is host_staging, host_call and dev_scope /
+// dev_call.
 #include <hip/hip_runtime_api.h>
 
 #include <atomic>
@@ -28,8 +29,12 @@ extern "C" void fake_open_gates(void);
 struct test_ctx {
     host_staging io;
     std::string err;
+    std::mutex mu;
+    int device = 0;
     hipStream_t stream = nullptr;
-    int fail_leave = 0, fail_wait = 0;   // injected return codes
+    int fail_enter = 0, fail_leave = 0, fail_wait = 0;   // injected return codes
+    int enters = 0, leaves = 0;                          // calls of ctx_enter that succeeded / of ctx_leave
+    hipStream_t left_on = nullptr;                       // the stream of the last ctx_leave
     char *work[3] = {nullptr, nullptr, nullptr};
     size_t work_cap[3] = {1000, 0, 4096};
     struct {
@@ -71,13 +76,17 @@ static int collect(test_ctx *c) {
     return 0;
 }
 static int ctx_enter(test_ctx *c, hipStream_t, bool keep_staging) {
+    if (c->fail_enter) return c->fail_enter;
     if (c->pend.active) {
         int rc = collect(c);
         if (rc) return rc;
     }
+    c->enters++;
     return c->io.begin(keep_staging);
 }
 static int ctx_leave(test_ctx *c, hipStream_t s) {
+    c->leaves++;
+    c->left_on = s;
     if (c->fail_leave) return c->fail_leave;
     return c->io.left(s);
 }
@@ -316,12 +325,193 @@ static void test_submit_collect() {
     puts("submit/collect ok");
 }
 
+// a device-pointer call: lock, stream, enter, body, ONE leave; the body's code first, then ctx_leave's
+static void test_dev_call() {
+    test_ctx c;
+    hipStream_t mine = nullptr;
+    hipStreamCreateWithFlags(&mine, 0);
+    for (hipStream_t given : {mine, (hipStream_t) nullptr}) {   // the caller's stream, or the context's own where none is given
+        const hipStream_t want = given ? given : c.stream;
+        const int cases[4][3] = {{5, 7, 5}, {0, 7, 7}, {5, 0, 5}, {0, 0, 0}};   // body, ctx_leave, returned
+        for (const auto &k : cases) {
+            const int enters = c.enters, leaves = c.leaves;
+            int ran = 0;
+            c.fail_leave = k[1];
+            const int rc = dev_call(&c, (void *)given, [&](hipStream_t s) {
+                ran++;
+                CHECK(s == want);
+                CHECK(c.leaves == leaves);                   // not left before or during the body
+                std::thread([&] { CHECK(!c.mu.try_lock()); }).join();   // the lock is held (asked from another thread: try_lock by the owner is undefined)
+                return k[0];
+            });
+            c.fail_leave = 0;
+            CHECK(rc == k[2] && ran == 1);
+            CHECK(c.enters == enters + 1 && c.leaves == leaves + 1 && c.left_on == want);
+            CHECK(c.mu.try_lock());                          // ... and free afterwards
+            c.mu.unlock();
+        }
+    }
+    {   // ctx_enter fails: no body, no leave, its code
+        const int leaves = c.leaves;
+        int ran = 0;
+        c.fail_enter = 11;
+        CHECK(dev_call(&c, nullptr, [&](hipStream_t) { return ++ran; }) == 11);
+        c.fail_enter = 0;
+        CHECK(ran == 0 && c.leaves == leaves);
+        CHECK(c.mu.try_lock());
+        c.mu.unlock();
+    }
+    {   // a check under the lock in front of the enter: where it refuses, its code, no enter, no body, no leave; where it passes, as above
+        const int enters = c.enters, leaves = c.leaves;
+        int ran = 0, checked = 0;
+        auto pre = [&](int code) {
+            return [&, code] {
+                checked++;
+                std::thread([&] { CHECK(!c.mu.try_lock()); }).join();
+                CHECK(c.enters == enters);
+                return code;
+            };
+        };
+        CHECK(dev_call(&c, nullptr, pre(17), [&](hipStream_t) { return ++ran; }) == 17);
+        CHECK(checked == 1 && ran == 0 && c.enters == enters && c.leaves == leaves);
+        CHECK(dev_call(&c, (void *)mine, pre(0), [&](hipStream_t s) { return s == mine ? 0 : 1; }) == 0);
+        CHECK(checked == 2 && c.enters == enters + 1 && c.leaves == leaves + 1 && c.left_on == mine);
+        CHECK(c.mu.try_lock());
+        c.mu.unlock();
+    }
+    {   // the scope alone: a path that returns without leave() is left by the destructor, one that called leave() is not left twice
+        const int leaves = c.leaves;
+        {
+            dev_scope<test_ctx> sc(&c);
+            CHECK(sc.rc == 0 && sc.enter((void *)mine) == 0 && sc.s == mine && c.leaves == leaves);
+        }
+        CHECK(c.leaves == leaves + 1 && c.left_on == mine);
+        {
+            dev_scope<test_ctx> sc(&c);
+            CHECK(sc.enter(nullptr) == 0 && sc.s == c.stream);
+            c.fail_leave = 9;
+            CHECK(sc.leave() == 9);
+            c.fail_leave = 0;
+        }
+        CHECK(c.leaves == leaves + 2 && c.left_on == c.stream);
+        {
+            dev_scope<test_ctx> sc(&c);   // never entered: never left
+            c.fail_enter = 3;
+            CHECK(sc.enter(nullptr) == 3);
+            c.fail_enter = 0;
+        }
+        CHECK(c.leaves == leaves + 2);
+        CHECK(c.mu.try_lock());
+        c.mu.unlock();
+    }
+    hipStreamSynchronize(mine);
+    hipStreamDestroy(mine);
+    puts("dev call ok");
+}
+
+// The tail of a combined check: regions at their exact sizes -- inputs 300, outputs verdicts (n), batch result (64), transcripts (n * 208).
+// First pass: "the device" fills verdicts with 0x10, the batch result with `byte0` then 0x20.., transcripts with 0x30; the per-proof pass
+// overwrites ALL outputs on the device with 0x40 / 0x50 / 0x60 (only its verdicts may reach the caller).
+struct comb_case {
+    static const size_t N = 37, TSB = 37 * 208;
+    call io;
+    int r_i, r_v, r_b, r_t;
+    comb_case(test_ctx &c) : io(&c, c.stream) {
+        r_i = io.in(300);
+        r_v = io.out(N), r_b = io.out(64), r_t = io.out(TSB);
+    }
+    void fill(char v, char b0, char b, char t) {
+        hipMemsetAsync(io.d(r_v), v, N, io.s);
+        hipMemsetAsync(io.d(r_b), b, 64, io.s);
+        hipMemsetAsync(io.d(r_b), b0, 1, io.s);
+        hipMemsetAsync(io.d(r_t), t, TSB, io.s);
+    }
+    void first_pass(test_ctx &c, char byte0, bool outgrow) {
+        CHECK(io.open() == 0);
+        memset(io.h(r_i), 0x31, 300);
+        CHECK(io.upload() == 0);
+        if (outgrow) {   // the pinned block is outgrown in mid-call: the outputs come back into a retired block
+            char *nested = nullptr, *first = io.hb;
+            CHECK(c.io.pin_alloc(c.io.pin_cap + 1, &nested) == 0);
+            CHECK(c.io.pin_retired.size() == 1 && c.io.pin_retired[0] == first && io.hb == first);
+            memset(nested, 0x77, 64);
+        }
+        fill(0x10, byte0, 0x20, 0x30);
+        CHECK(io.finish(io.download(0)) == 0);
+    }
+};
+static void test_combined_delivery() {
+    const size_t N = comb_case::N, TSB = comb_case::TSB;
+    for (bool outgrow : {false, true}) {
+        {   // decided (byte 0 == 0): no second pass, everything the first pass's
+            test_ctx c;
+            comb_case k(c);
+            k.first_pass(c, 0, outgrow);
+            uint8_t *v = new uint8_t[N], *b = new uint8_t[33], *t = new uint8_t[TSB];
+            int calls = 0;
+            CHECK(k.io.deliver_combined(k.r_v, v, N, k.r_b, b, k.r_t, t, TSB, [&] { return ++calls; }) == 0);
+            CHECK(calls == 0);
+            CHECK(all_bytes((char *)v, N, 0x10) && b[0] == 0 && all_bytes((char *)b + 1, 32, 0x20) && all_bytes((char *)t, TSB, 0x30));
+            delete[] v, delete[] b, delete[] t;
+        }
+        {   // undecided: ONE second pass, its verdicts; batch_out (all 33 bytes) and transcripts the first pass's
+            test_ctx c;
+            comb_case k(c);
+            k.first_pass(c, 0x21, outgrow);
+            uint8_t *v = new uint8_t[N], *b = new uint8_t[33], *t = new uint8_t[TSB];
+            int calls = 0;
+            const int enters = c.enters, leaves = c.leaves;
+            CHECK(k.io.deliver_combined(k.r_v, v, N, k.r_b, b, k.r_t, t, TSB, [&] {
+                calls++;
+                if (outgrow) CHECK(c.io.pin_retired.size() == 1);   // the reopen kept the retired block
+                k.fill(0x40, 0x51, 0x50, 0x60);
+                return 0;
+            }) == 0);
+            CHECK(calls == 1 && c.enters == enters + 1 && c.leaves == leaves + 1);
+            CHECK(all_bytes((char *)v, N, 0x40));
+            CHECK(b[0] == 0x21 && all_bytes((char *)b + 1, 32, 0x20) && all_bytes((char *)t, TSB, 0x30));
+            CHECK((uint8_t)k.io.h(k.r_b)[0] == 0x21 && all_bytes(k.io.h(k.r_b) + 1, 32, 0x20));   // the staged copy too
+            delete[] v, delete[] b, delete[] t;
+            // optional outputs left out: the verdicts still arrive
+            comb_case k2(c);
+            k2.first_pass(c, 0, false);
+            uint8_t v2[comb_case::N];
+            CHECK(k2.io.deliver_combined(k2.r_v, v2, N, k2.r_b, nullptr, k2.r_t, nullptr, 0, [&] { return 1; }) == 0);
+            CHECK(all_bytes((char *)v2, N, 0x10));
+        }
+        {   // the second pass fails -- in the callable, or in its finish: that code, and the caller's verdicts untouched
+            for (int where : {0, 1}) {
+                test_ctx c;
+                comb_case k(c);
+                k.first_pass(c, 1, outgrow);
+                uint8_t *v = new uint8_t[N], *b = new uint8_t[33], *t = new uint8_t[TSB];
+                memset(v, 0x7f, N);
+                int calls = 0;
+                const int rc = k.io.deliver_combined(k.r_v, v, N, k.r_b, b, k.r_t, t, TSB, [&] {
+                    calls++;
+                    k.fill(0x40, 0x51, 0x50, 0x60);
+                    if (where == 1) c.fail_wait = 13;
+                    return where == 0 ? 12 : 0;
+                });
+                c.fail_wait = 0;
+                CHECK(rc == (where == 0 ? 12 : 13) && calls == 1);
+                CHECK(all_bytes((char *)v, N, 0x7f));
+                CHECK(b[0] == 1 && all_bytes((char *)b + 1, 32, 0x20) && all_bytes((char *)t, TSB, 0x30));   // (handed out before the rerun)
+                delete[] v, delete[] b, delete[] t;
+            }
+        }
+    }
+    puts("combined delivery ok");
+}
+
 int main() {
     test_layout();
     test_growth_inside_a_call();
     test_reuse_guard();
     test_finish();
     test_submit_collect();
+    test_dev_call();
+    test_combined_delivery();
     puts("all ok");
     return 0;
 }

@@ -5,7 +5,11 @@ while a copy is queued or read after its release is a reported use-after-free.  
 aligned sizes, inputs < outputs < device-only, host and device offsets equal, empty regions take no room); a block outgrown inside a
 call (retired, readable after finish, kept by a reopen, freed by the next call); the reuse guard (the next call's first allocation
 waits for a call left in flight, after a mark only up to the mark); finish (return-code priority, exactly the declared secret bytes
-and every device buffer cleared, whatever the call's return code); submit / collect (delivered once, by collect or by the next open)."""
+and every device buffer cleared, whatever the call's return code); submit / collect (delivered once, by collect or by the next open);
+a device-pointer call (the body on the caller's stream or the context's own, under the lock, one ctx_leave behind it whatever it
+returns, none and no body where ctx_enter fails, return-code priority); the delivery of a combined check (no rerun where the batch
+result's byte 0 is 0, one rerun otherwise whose verdicts alone replace the first pass's, also from a retired block, and a failed
+rerun leaves the caller's verdicts untouched)."""
 import os
 import subprocess
 
@@ -13,7 +17,7 @@ import pytest
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 DIR = os.path.join(HERE, "cpu_host_io")
-STAGES = ["layout ok", "growth ok", "reuse guard ok", "finish ok", "submit/collect ok", "all ok"]
+STAGES = ["layout ok", "growth ok", "reuse guard ok", "finish ok", "submit/collect ok", "dev call ok", "combined delivery ok", "all ok"]
 
 
 @pytest.fixture(scope="module")
