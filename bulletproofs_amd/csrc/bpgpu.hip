@@ -270,6 +270,18 @@ static hipEvent_t get_event(bpgpu_ctx *c) {
         if (ct) LAUNCH(c, s, name "_ct", kern<true>, grid, block, __VA_ARGS__);    \
         else LAUNCH(c, s, name, kern<false>, grid, block, __VA_ARGS__);            \
     } while (0)
+// a kernel template with two / three forms under ONE name: kern<true> or kern<false>; kern<v0>, kern<v1> or kern<v2> by sel = 0, 1, 2 -- the same arguments
+#define LAUNCH_TF(c, s, flag, name, kern, grid, block, ...)                        \
+    do {                                                                           \
+        if (flag) LAUNCH(c, s, name, kern<true>, grid, block, __VA_ARGS__);        \
+        else LAUNCH(c, s, name, kern<false>, grid, block, __VA_ARGS__);            \
+    } while (0)
+#define LAUNCH_SEL3(c, s, sel, v0, v1, v2, name, kern, grid, block, ...)           \
+    do {                                                                           \
+        if ((sel) == 0) LAUNCH(c, s, name, kern<v0>, grid, block, __VA_ARGS__);    \
+        else if ((sel) == 1) LAUNCH(c, s, name, kern<v1>, grid, block, __VA_ARGS__); \
+        else LAUNCH(c, s, name, kern<v2>, grid, block, __VA_ARGS__);               \
+    } while (0)
 
 static void drain_profile(bpgpu_ctx *c) {
     for (auto &t : c->pending) {
@@ -1440,10 +1452,11 @@ extern "C" int bpgpu_msm_batch(bpgpu_ctx *c, size_t nbatch, const uint32_t *n_te
 // ============================================================================
 // shared-generator MSM
 // ============================================================================
-static uint32_t pick_splits(bpgpu_ctx *c, size_t nbatch, uint32_t npairs, bool walk_alone_in_launch = false) {
-    if (c->splits) return c->splits;
-    if (c->splits_hint && npairs <= 8192) {   // the pool knows how much else is in flight (pool.hip flush_dev)
-        uint32_t s = c->splits_hint;
+// (fixed: option fixed_splits; hint / busy_hint: what the pool said about this chain -- bpgpu_ctx::splits, splits_hint, busy_hint)
+static uint32_t pick_splits(uint32_t fixed, uint32_t hint, int busy_hint, size_t nbatch, uint32_t npairs, bool walk_alone_in_launch = false) {
+    if (fixed) return fixed;
+    if (hint && npairs <= 8192) {   // the pool knows how much else is in flight (pool.hip flush_dev)
+        uint32_t s = hint;
         while (s > 8 && npairs / s < 8) s -= 8;
         return s;
     }
@@ -1458,7 +1471,7 @@ static uint32_t pick_splits(bpgpu_ctx *c, size_t nbatch, uint32_t npairs, bool w
     // flight (a context on its own, >= 8192 proofs): two full rounds of three wavefronts per SIMD (a lone 16 384-proof chain ran its walk at 0.59 of the mixed-addition rate
     // with 2048 wavefronts, profiles/r03/chain16384_alone_kernel_stats.csv).
     const uint32_t nblk = (uint32_t)((nbatch + FB_BLOCK - 1) / FB_BLOCK);
-    const bool lone = walk_alone_in_launch && c->busy_hint < 0;   // (a pool that said "busy" has other chains to fill the device)
+    const bool lone = walk_alone_in_launch && busy_hint < 0;   // (a pool that said "busy" has other chains to fill the device)
     const uint32_t target = npairs > 8192 ? 4096 : (lone ? 6144 : 1024);
     uint32_t s = (target + nblk - 1) / nblk;
     s = (s + 7) & ~7u;
@@ -1467,6 +1480,7 @@ static uint32_t pick_splits(bpgpu_ctx *c, size_t nbatch, uint32_t npairs, bool w
     if (s < 8) s = 8;
     return s;
 }
+static uint32_t pick_splits(bpgpu_ctx *c, size_t nbatch, uint32_t npairs) { return pick_splits(c->splits, c->splits_hint, c->busy_hint, nbatch, npairs); }
 
 // Tree-reduce the per-split partial points (8-way per level) until at most `until` remain per proof.
 // `buf` must hold nsplit*nbatch + ceil(nsplit/8)*nbatch (+ ...) points: callers reserve 2*nsplit*nbatch.
@@ -1947,166 +1961,323 @@ extern "C" int bpgpu_internal_set_chain_seed(bpgpu_ctx *c, const uint8_t *key32)
     return BPGPU_OK;
 }
 
-static int rp_verify_dev_locked(bpgpu_ctx *c, size_t n, size_t m, size_t nbatch, const void *d_proofs, size_t proof_len,
-                                const void *d_commitments, const rp_transcripts &tr, const void *d_rng64, void *d_verdict,
-                                void *d_msm_out, hipStream_t s, bool rlc = false, const void *d_weights64 = nullptr,
-                                void *d_batch_out = nullptr, const rp_seg *h_segs = nullptr, uint32_t nseg = 0, bool dev_call = false,
-                                bool reserve_only = false) {
-    // reserve_only: size the arena, the status words and the work decomposition for a chain of `nbatch` proofs and return --
-    // a lane of the pool's combining queue sees chains of every width and should not grow its buffers (a device-wide
-    // synchronisation each time) on the way up
-    // h_segs (bpgpu_pool_*, coalesced launch): the nbatch proofs are the concatenation of nseg submitted items, each with its
-    // own input / output buffers (d_proofs, d_commitments, d_verdict, d_msm_out unused; d_msm_out non-null = some item wants encodings)
-    // rlc: batch-combination mode (bpgpu_rangeproof_verify_rlc[_dev]); d_msm_out is unused then, d_batch_out
-    // (33 bytes, optional) receives the batch verdict and the encoding of the combined point
-    if (nbatch == 0) {
-        if (rlc && d_batch_out) HIPCHK(c, hipMemsetAsync(d_batch_out, 0, 33, s));
-        return BPGPU_OK;
+// ---- what a proof length and a shape are, before any arithmetic -------------------------------------------------------------------------
+// The length-only part of RangeProof::from_bytes / InnerProductProof::from_bytes (mod.rs:505-510, ipp.rs:374-388) -- one verdict for the whole
+// batch --, then the parameter checks of verify_multiple_with_rng in the reference's order (mod.rs:358-366: Bitsize, GeneratorsLength; ipp.rs:209:
+// n m == 2^k), reported per proof AFTER its own format check.  The one copy of these rules: the chain driver, the pool's "can these share a
+// chain" and the mixed check's grouping all ask here.
+struct rp_class {
+    uint32_t all_verdict = 0;     // BPGPU_VERDICT_FORMAT_ERROR: every proof of the batch has the same malformed length
+    uint32_t shape_verdict = 0;   // else: the code of every proof that passes its own format check (0: a shape to verify)
+    size_t k = 0;                 // lg(n m) as the length has it (all_verdict == 0)
+    bool unsupported = false;     // a shape to verify with k > BP_RP_MAX_K
+};
+static rp_class rp_classify(size_t n, size_t m, size_t proof_len, size_t gens_capacity, size_t party_capacity) {
+    rp_class r;
+    const size_t ne = proof_len / 32;   // 32-byte elements: A, S, T_1, T_2, t_x, t_x_blinding, e_blinding, k pairs (L, R), a, b
+    if (proof_len % 32 != 0 || ne < 9 || (ne - 9) % 2 != 0 || (ne - 9) / 2 >= 32) {
+        r.all_verdict = BPGPU_VERDICT_FORMAT_ERROR;
+        return r;
     }
-    if (!c->d_table) return fail(c, BPGPU_ERR_NO_GENS, "generators not loaded");
-    if (nbatch > 0x7fffffffu / 64) return fail(c, BPGPU_ERR_INVALID_ARG, "batch too large");
-    // ---- length-only part of RangeProof::from_bytes / InnerProductProof::from_bytes (mod.rs:505-510, ipp.rs:374-388)
-    uint32_t all_verdict = 0;
-    size_t k = 0;
-    if (proof_len % 32 != 0 || proof_len < 7 * 32) all_verdict = BPGPU_VERDICT_FORMAT_ERROR;
-    else {
-        const size_t ne = (proof_len - 7 * 32) / 32;
-        if (ne < 2 || (ne - 2) % 2 != 0) all_verdict = BPGPU_VERDICT_FORMAT_ERROR;
-        else {
-            k = (ne - 2) / 2;
-            if (k >= 32) all_verdict = BPGPU_VERDICT_FORMAT_ERROR;
-        }
-    }
-    if (tr.shared_ts && !ts_state_ok(tr.shared_ts)) return fail(c, BPGPU_ERR_INVALID_ARG, "malformed transcript state");
-    if (h_segs && (all_verdict || tr.d_ts_in || tr.d_ts_out || tr.shared_ts || (rlc && d_weights64)))   // (the pool sends such items through the ordinary entry point)
-        return fail(c, BPGPU_ERR_INVALID_ARG, "coalesced launches take well-formed shapes and a label only (batch-combined ones: library-drawn weights)");
-    if (all_verdict) {   // every proof of the batch has the same malformed length
-        if (tr.d_ts_out) {   // FormatError leaves the caller's transcript untouched
-            if (tr.d_ts_in) HIPCHK(c, hipMemcpyAsync(tr.d_ts_out, tr.d_ts_in, nbatch * BPGPU_TRANSCRIPT_BYTES, hipMemcpyDeviceToDevice, s));
-            else {
-                char *h = nullptr;
-                int rcp = c->io.pin_alloc(nbatch * BPGPU_TRANSCRIPT_BYTES, &h);
-                if (rcp) return rcp;
-                uint8_t st0[BPGPU_TRANSCRIPT_BYTES];
-                if (tr.shared_ts) memcpy(st0, tr.shared_ts, BPGPU_TRANSCRIPT_BYTES);
-                else bpgpu_transcript_new(tr.label, tr.label_len, st0);
-                for (size_t b = 0; b < nbatch; b++) memcpy(h + b * BPGPU_TRANSCRIPT_BYTES, st0, BPGPU_TRANSCRIPT_BYTES);
-                HIPCHK(c, hipMemcpyAsync(tr.d_ts_out, h, nbatch * BPGPU_TRANSCRIPT_BYTES, hipMemcpyHostToDevice, s));
-            }
-        }
-        HIPCHK(c, hipMemsetAsync(d_verdict, (int)all_verdict, nbatch, s));
-        if (d_msm_out) HIPCHK(c, hipMemsetAsync(d_msm_out, 0, nbatch * 32, s));
-        if (rlc && d_batch_out) HIPCHK(c, hipMemsetAsync(d_batch_out, 0, 33, s));   // nothing to combine
-        return BPGPU_OK;
-    }
-    // ---- parameter checks of verify_multiple_with_rng (mod.rs:358-366), reported per proof AFTER its format check
-    uint32_t shape_verdict = 0;
-    if (!(n == 8 || n == 16 || n == 32 || n == 64)) shape_verdict = BPGPU_VERDICT_INVALID_BITSIZE;
-    else if (c->gens_capacity < n || c->party_capacity < m) shape_verdict = BPGPU_VERDICT_INVALID_GENERATORS_LENGTH;
-    else if (m == 0 || n * m != ((size_t)1 << k)) shape_verdict = BPGPU_VERDICT_VERIFICATION_ERROR;   // ipp.rs:209
-    if (!shape_verdict && k > BP_RP_MAX_K) return fail(c, BPGPU_ERR_INVALID_ARG, "n*m > 2^%d not supported", BP_RP_MAX_K);
-    if (h_segs && shape_verdict) return fail(c, BPGPU_ERR_INVALID_ARG, "coalesced launches take well-formed shapes only");
+    r.k = (ne - 9) / 2;
+    if (!(n == 8 || n == 16 || n == 32 || n == 64)) r.shape_verdict = BPGPU_VERDICT_INVALID_BITSIZE;
+    else if (gens_capacity < n || party_capacity < m) r.shape_verdict = BPGPU_VERDICT_INVALID_GENERATORS_LENGTH;
+    else if (m == 0 || n * m != ((size_t)1 << r.k)) r.shape_verdict = BPGPU_VERDICT_VERIFICATION_ERROR;   // ipp.rs:209
+    else r.unsupported = r.k > BP_RP_MAX_K;
+    return r;
+}
 
-    rp_shape sh;
+// ---- the plan of a launch chain ------------------------------------------------------------------------------------------------------------
+// Everything that is decided about a chain before its first launch, each thing once: the forms it takes (rp_chain_forms above is the first step;
+// the narrow-chain forms follow it), the splits of the table walk, the chunk size of the window sums, every grid count, every arena offset and
+// the arena's size.  Plain host logic -- its inputs are a snapshot of the context's options and hints, the shape and its class, the parameters of
+// the window table the generator terms walk, and the facts of the call; it makes no HIP call and sees no context, so it is checked rule by rule
+// on the CPU (bpgpu_internal_chain_plan below, tests/test_abi_and_host.py).
+#define RP_NARROW_MAX 256   // proofs: up to here a chain is NARROW, a latency matter -- 32 lanes per proof in launch 1, one generator index per lane,
+                            // small chunks of window sums under a wavefront per Horner chain, the walk with lane = split
+struct rp_plan_opts {       // what a plan reads of a context (rp_plan_opts_of)
+    uint32_t splits, splits_hint, horner_lanes, vb_radix, bucket_min;
+    int busy_hint, a_outside, split_stage3, narrow_walk, narrow_hi_max, narrow_hi4_max, narrow_chunk, narrow_fused_finish, transcript_coop, coop_split,
+        coop_defer_emit, exp_single, exp_pairs, exp_w3_min_nm, no_script;
+};
+static rp_plan_opts rp_plan_opts_of(const bpgpu_ctx *c) {
+    return {c->splits, c->splits_hint, c->horner_lanes, c->vb_radix, c->bucket_min, c->busy_hint, c->a_outside, c->split_stage3, c->narrow_walk,
+            c->narrow_hi_max, c->narrow_hi4_max, c->narrow_chunk, c->narrow_fused_finish, c->transcript_coop, c->coop_split, c->coop_defer_emit,
+            c->exp_single, c->exp_pairs, c->exp_w3_min_nm, c->no_script ? 1 : 0};
+}
+struct rp_call_facts {
+    size_t nbatch = 0;
+    bool rlc = false;             // the batch-combined check
+    bool ts_per_proof = false;    // one caller transcript per proof ...
+    bool ts_uniform = false;      // ... all of them at one STROBE position
+    bool want_out = false;        // someone wants the mega-check encodings (combined: the 33-byte result)
+    bool second_stream = false;   // the call came on the context's second stream
+    uint32_t nseg = 0;            // coalesced: items ...
+    uint32_t nlabels = 0;         // ... and the distinct labels among them
+};
+enum { RP_EXP_FOUR = 0, RP_EXP_PAIRS = 1, RP_EXP_SINGLE = 2 };   // generator indices per lane of the exponent role: four, eight in mirrored pairs, one
+struct rp_chain_plan {
+    const char *refused = nullptr;   // the chain cannot be enqueued: why
+    rp_shape sh;                     // as the kernels get it (radix5, a_outside, defer_emit, coop_split, narrow_hi decided here; the seed is the driver's)
+    uint32_t lg_m, n_gen_terms, npairs;
+    uint32_t forms;                  // rp_chain_forms
+    bool wide, wave, aside, r5, a_out;
+    bool scripted;                   // the per-shape transcript script replaces the byte-wise replay
+    bool coop;                       // launch 1 with 32 lanes per proof
+    bool narrow_walk;                // launch 4: lane = split, a proof's partial sums folded in the launch
+    bool hi;                         // second (hi_levels = 2) or second to fourth (4) tables per point, a 32- / 16-window Horner chain
+    uint32_t hi_levels;
+    bool narrow_ok;                  // narrow chains of this context and mode take the wavefront-per-chain form, with small chunks
+    uint32_t narrow_q, vb_chunk_sz;  // points per (chunk, window) lane: of those chains, of this one
+    bool rlc_bucket;                 // combined check: ONE bucket MSM over all proofs' weighted terms
+    bk_params bkp;
+    size_t rlc_terms;
+    bool quad, one_lane, one_chunk;  // Horner chains on four lanes / on one inside launch 4; U <= chunk: window sums are column sums
+    uint32_t exp_form;               // RP_EXP_*
+    bool exp_w3;                     // wide: the paired exponent launch at three wavefronts per SIMD
+    bool fused_finish, finish1;      // no finish launch / lane = proof (else eight lanes per proof)
+    uint32_t nsplit, nsplit1, nparts;   // splits of the walk, of the combined check's one-MSM walk; partial sums per proof that launch 4 leaves
+    size_t n_chunks;
+    // grids (workgroups) and the thread counts behind them
+    uint32_t n_tr, n_pt, g_stage1, nexp, n_exp, nwin, n_win, nrows, n_rows, nwsum, g_wsum, g_colsum, n_sc, nblk_p, n_hw, g_stage4, walk_flags, g_finish;
+    // arena
+    size_t off[7], boff[12], off_digits, off_partial, off_fields, off_mv, off_segs, off_inits, off_acc, off_tree, off_dig1, off_part1, off_res1;
+    size_t arena_need;               // this chain's
+    size_t arena_reserve;            // ... and what a lane that will see chains of every width up to this one reserves
+};
+static void rp_plan_chain(rp_chain_plan &p, const rp_plan_opts &o, const rp_class &cl, size_t n, size_t m, size_t proof_len, const fb_params &prm,
+                          const rp_call_facts &f) {
+    const size_t nbatch = f.nbatch;
+    const uint32_t nb32 = (uint32_t)nbatch;
+    const bool rlc = f.rlc, verdict_only = cl.shape_verdict != 0, narrow = nbatch <= RP_NARROW_MAX;
+    rp_shape &sh = p.sh;
     sh.n = (uint32_t)n;
     sh.m = (uint32_t)m;
     sh.nm = (uint32_t)(n * m);
-    sh.k = (uint32_t)k;
-    sh.U = (uint32_t)(4 + 2 * k + m);
+    sh.k = (uint32_t)cl.k;
+    sh.U = (uint32_t)(4 + 2 * cl.k + m);
     sh.proof_len = (uint32_t)proof_len;
-    sh.nproofs = (uint32_t)nbatch;
-    sh.shape_verdict = shape_verdict;
-    uint32_t lg_m = 0;
-    while (((size_t)1 << lg_m) < m) lg_m++;
-    // which window table the generator terms walk: the secondary one when the shape fits it (bpgpu_gens_add_shape), else the primary
-    const bool use_sec = c->sec.d_table && !shape_verdict && n <= c->sec.n && m <= c->sec.m;
-    const fb_params prm = use_sec ? c->sec.prm : c->prm;
-    const fb_entry *const gen_table = use_sec ? c->sec.d_table : c->d_table;
-    const uint32_t n_gen_terms = shape_verdict ? 2 : (uint32_t)(2 * n * m + 2);
-    const uint32_t npairs = n_gen_terms * prm.nwin;
-    const rp_fields fl = rp_field_layout(sh.k, sh.m);
-    uint32_t *d_ids = nullptr;
-    int rc;
-    if (!shape_verdict) {
-        rc = use_sec ? gen_ids_for_secondary(c, n, m, &d_ids) : gen_ids_for(c, n, m, &d_ids);
-        if (rc) return rc;
+    sh.nproofs = nb32;
+    sh.shape_verdict = cl.shape_verdict;
+    p.lg_m = 0;
+    while (((size_t)1 << p.lg_m) < m) p.lg_m++;
+    p.n_gen_terms = verdict_only ? 2 : (uint32_t)(2 * n * m + 2);
+    p.npairs = p.n_gen_terms * prm.nwin;
+    // ---- forms: the table above, then what narrow chains add to it
+    p.forms = rp_chain_forms(o.horner_lanes, o.split_stage3, o.busy_hint, o.vb_radix, o.a_outside, nbatch, rlc || verdict_only, f.second_stream);
+    p.wide = p.forms & RPC_WIDE, p.wave = p.forms & RPC_WAVE, p.aside = p.forms & RPC_ASIDE, p.r5 = p.forms & RPC_RADIX32, p.a_out = p.forms & RPC_A_OUTSIDE;
+    p.scripted = (!f.ts_per_proof || f.ts_uniform) && !verdict_only && !o.no_script;   // every proof starts at one STROBE position
+    p.coop = p.scripted && o.transcript_coop && narrow;
+    sh.coop_split = (p.coop && o.coop_split && !rlc && !p.wide && !verdict_only && sh.k < 32) ? 1u : 0u;   // (launch 3 then carries the basepoint-coefficient role)
+    // the walk with lane = split, a multiple of 64 splits per proof (rp_walk_narrow)
+    p.narrow_walk = p.wave && !p.wide && !rlc && !verdict_only && narrow && o.narrow_walk;
+    // ... and for VERY narrow ones every per-proof point gets a second table, of its 2^128 multiple, built beside the transcript by a wavefront of its own
+    // (k_rp_stage1_coop's third role): the Horner chain has 32 windows, and the walk twice the splits to end with it; the very narrowest: three more
+    // tables per point, a 16-window chain
+    p.hi = p.narrow_walk && sh.coop_split && (int64_t)nbatch <= (int64_t)o.narrow_hi_max;
+    p.hi_levels = !p.hi ? 1u : ((int64_t)nbatch <= (int64_t)o.narrow_hi4_max ? 4u : 2u);
+    sh.narrow_hi = p.hi ? p.hi_levels : 0u;
+    sh.radix5 = p.r5 ? 1u : 0u;
+    sh.a_outside = p.a_out ? 1u : 0u;
+    sh.defer_emit = o.coop_defer_emit ? 1u : 0u;
+    p.nsplit = pick_splits(o.splits, o.splits_hint, o.busy_hint, nbatch, p.npairs, p.aside);
+    if (p.narrow_walk) {
+        if (p.hi && p.nsplit < 2 * FB_BLOCK) p.nsplit = 2 * FB_BLOCK;
+        if (p.hi_levels == 4 && p.nsplit < 4 * FB_BLOCK) p.nsplit = 4 * FB_BLOCK;
+        p.nsplit = (p.nsplit + FB_BLOCK - 1) / FB_BLOCK * FB_BLOCK;
+        while (p.nsplit > FB_BLOCK && p.npairs / p.nsplit < 4) p.nsplit -= FB_BLOCK;
     }
-    // which forms this chain takes (rp_chain_forms above: the decision table, with the measurements behind every line)
-    const uint32_t forms = rp_chain_forms(c->horner_lanes, c->split_stage3, c->busy_hint, c->vb_radix, c->a_outside, nbatch, rlc || shape_verdict != 0,
-                                          s == c->stream2);
-    const bool wide = forms & RPC_WIDE, wave = forms & RPC_WAVE, aside = forms & RPC_ASIDE, r5 = forms & RPC_RADIX32, a_out = forms & RPC_A_OUTSIDE;
-    uint32_t nsplit = pick_splits(c, nbatch, npairs, aside);
-    // narrow chains in the wavefront-per-chain form: the walk with lane = split, a multiple of 64 splits per proof (rp_walk_narrow)
-    const bool narrow_walk = wave && !wide && !rlc && nbatch <= 256 && c->narrow_walk;
-    // ... and for VERY narrow ones every per-proof point gets a second table, of its 2^128 multiple, built beside the transcript by a wavefront
-    // of its own (k_rp_stage1_coop's third role): the Horner chain has 32 windows, and the walk twice the splits to end with it
-    const bool will_script = (!tr.d_ts_in || tr.ts_uniform) && !shape_verdict && !c->no_script;
-    const bool narrow_hi = narrow_walk && will_script && c->transcript_coop && c->coop_split && !shape_verdict && (int64_t)nbatch <= (int64_t)c->narrow_hi_max;
-    const uint32_t hi_levels = !narrow_hi ? 1u : ((int64_t)nbatch <= (int64_t)c->narrow_hi4_max ? 4u : 2u);   // (the very narrowest: three more tables per point, a 16-window chain)
-    if (narrow_walk) {
-        if (narrow_hi && nsplit < 2 * FB_BLOCK) nsplit = 2 * FB_BLOCK;
-        if (hi_levels == 4 && nsplit < 4 * FB_BLOCK) nsplit = 4 * FB_BLOCK;
-        nsplit = (nsplit + FB_BLOCK - 1) / FB_BLOCK * FB_BLOCK;
-        while (nsplit > FB_BLOCK && npairs / nsplit < 4) nsplit -= FB_BLOCK;
-    }
+    p.nsplit1 = rlc ? pick_splits(o.splits, o.splits_hint, o.busy_hint, 1, p.npairs) : 0;   // the combined check ends in a walk for ONE MSM
+    p.nparts = p.narrow_walk ? p.nsplit / FB_BLOCK : p.nsplit;
     // thread / element counts are 32-bit in the kernels: refuse what does not fit
-    if ((uint64_t)n_gen_terms * nbatch > 0x7fffffffull || (uint64_t)nbatch * sh.U > 0x7fffffffull / 64 ||
+    if ((uint64_t)p.n_gen_terms * nbatch > 0x7fffffffull || (uint64_t)nbatch * sh.U > 0x7fffffffull / 64 ||
         (uint64_t)nbatch * ((sh.U + BP_VB_CHUNK - 1) / BP_VB_CHUNK) * 64 > 0x7fffffffull || (uint64_t)(sh.nm / 4 + 1) * nbatch > 0x7fffffffull ||
-        (uint64_t)((nbatch + FB_BLOCK - 1) / FB_BLOCK) * nsplit > 0x7fffffffull)
-        return fail(c, BPGPU_ERR_INVALID_ARG, "batch too large for this shape");
+        (uint64_t)((nbatch + FB_BLOCK - 1) / FB_BLOCK) * p.nsplit > 0x7fffffffull) {
+        p.refused = "batch too large for this shape";
+        return;
+    }
     // batch combination with enough per-proof terms: ONE bucket MSM (bucket.h) over all proofs' weighted terms
-    const size_t rlc_terms = (size_t)nbatch * sh.U;
-    const bk_params bkp = bk_make(pick_bucket_c(rlc_terms));
-    const bool rlc_bucket = rlc && !shape_verdict && rlc_terms >= (c->bucket_min ? c->bucket_min : BK_RLC_MIN_TERMS) && bucket_fits(1, rlc_terms, bkp);
+    p.rlc_terms = (size_t)nbatch * sh.U;
+    p.bkp = bk_make(pick_bucket_c(p.rlc_terms));
+    p.rlc_bucket = rlc && !verdict_only && p.rlc_terms >= (o.bucket_min ? o.bucket_min : BK_RLC_MIN_TERMS) && bucket_fits(1, p.rlc_terms, p.bkp);
     // Narrow chains (one wavefront per Horner chain, which adds the chunks' window sums itself): a (chunk, window) lane adding all U table
     // entries one after the other is ~50 us of a one-proof chain's launch 3.  With chunks of 8 terms a lane adds 8 entries and the Horner
     // wavefront's lane w adds the U / 8 rows of its window.  (Option narrow_chunk.)
-    uint32_t narrow_q = (uint32_t)c->narrow_chunk;
-    if (narrow_q == 0) narrow_q = 8;   // (A/B at U = 17, profiles/r06/narrow_chain_ab.txt: 3 / 5 / 8 / 32 -> one call 0.456 / 0.457 / 0.448 / 0.464 ms; launch 3 is then bound by its basepoint-coefficient role)
-    narrow_q = narrow_q < 2 ? 2u : (narrow_q > BP_VB_CHUNK ? (uint32_t)BP_VB_CHUNK : narrow_q);
-    const bool narrow_ok = !rlc && !shape_verdict && (c->horner_lanes == 0 || c->horner_lanes == 64);   // (narrow chains of this context take the wavefront-per-chain form)
-    const uint32_t vb_chunk_sz = (wave && !wide && narrow_ok && nbatch <= 256) ? narrow_q : (uint32_t)BP_VB_CHUNK;
-    sh.radix5 = r5 ? 1u : 0u;
-    sh.a_outside = a_out ? 1u : 0u;
-    sh.defer_emit = c->coop_defer_emit ? 1u : 0u;
+    p.narrow_q = (uint32_t)o.narrow_chunk;
+    if (p.narrow_q == 0) p.narrow_q = 8;   // (A/B at U = 17, profiles/r06/narrow_chain_ab.txt: 3 / 5 / 8 / 32 -> one call 0.456 / 0.457 / 0.448 / 0.464 ms; launch 3 is then bound by its basepoint-coefficient role)
+    p.narrow_q = p.narrow_q < 2 ? 2u : (p.narrow_q > BP_VB_CHUNK ? (uint32_t)BP_VB_CHUNK : p.narrow_q);
+    p.narrow_ok = !rlc && !verdict_only && (o.horner_lanes == 0 || o.horner_lanes == 64);
+    p.vb_chunk_sz = (p.wave && !p.wide && p.narrow_ok && narrow) ? p.narrow_q : (uint32_t)BP_VB_CHUNK;
+    p.n_chunks = (verdict_only || p.rlc_bucket) ? 0 : nbatch * ((sh.U + p.vb_chunk_sz - 1) / p.vb_chunk_sz);   // (as uniform_plan cuts them)
+    p.one_chunk = p.n_chunks == nbatch;
+    // Horner layout: quads (16 chains per wavefront, least total work) unless the chain takes the wavefront-per-chain form (lowest latency of a small
+    // batch); with horner_lanes = 1 one lane per chain in the quads' place
+    p.quad = !p.wave;
+    p.one_lane = o.horner_lanes == 1;
+    // the generator-exponent role: one index per lane for narrow chains (latency), eight in mirrored pairs otherwise (rp_expand_b8_thread: least work)
+    const bool exp_single = !rlc && !p.wide && o.exp_single && narrow && sh.nm >= 4;
+    const bool pairs = !rlc && !exp_single && o.exp_pairs && sh.nm >= 8;
+    p.exp_form = exp_single ? RP_EXP_SINGLE : (pairs ? RP_EXP_PAIRS : RP_EXP_FOUR);
+    p.exp_w3 = p.wide && pairs && sh.nm >= (uint32_t)o.exp_w3_min_nm;   // (aggregated shapes: three wavefronts per SIMD)
+    // verdicts only (the crate's own call: nobody asks for the mega-check's encoding) and at most four partial sums per proof: the LAST of a proof's
+    // 1 + nsplit / 64 workgroups of launch 4 to arrive adds them to the Horner result and writes the verdict -- no finish launch (option narrow_fused_finish)
+    // (same-box A/B, profiles/r06/fused_finish_ab.txt: 64 threads +5 %, 256 threads +3 %, tickets and 16 threads unchanged, ONE proof per chain -2.5 % -- the
+    // finisher's three additions then follow the Horner wavefront instead of overlapping with the launch of the next kernel: chains of >= 8 proofs only)
+    p.fused_finish = p.narrow_walk && o.narrow_fused_finish && nbatch >= 8 && !f.want_out && p.nparts <= 4;
+    uint32_t nred = p.nparts;   // (what enqueue_fb_reduce leaves: 8 lanes x <= 8 partials each in finish8)
+    while (nred > 64) nred = (nred + FB_REDUCE_GROUP - 1) / FB_REDUCE_GROUP;
+    p.finish1 = nred <= 2 && p.narrow_walk;   // one or two partial sums + the Horner result per proof: lane = proof (more: eight lanes per proof and a three-level fold)
+    // ---- grids
+    p.n_tr = p.coop ? (nb32 + 1) / 2 : (nb32 + RP_BLOCK - 1) / RP_BLOCK;   // 32 lanes per proof: two proofs per workgroup
+    p.n_pt = verdict_only ? 0 : (nb32 * sh.U + RP_BLOCK - 1) / RP_BLOCK;
+    p.g_stage1 = p.n_tr + p.n_pt + ((p.coop && p.hi) ? (p.hi_levels - 1) * nb32 * sh.U : 0u);
+    p.nexp = (exp_single ? sh.nm : sh.nm / (pairs ? 8 : 4)) * nb32;   // four generator indices per lane (eight in pairs)
+    p.nwin = (uint32_t)p.n_chunks * 64;
+    p.n_win = (p.nwin + BP_BLOCK - 1) / BP_BLOCK, p.n_exp = (p.nexp + BP_BLOCK - 1) / BP_BLOCK;
+    p.nrows = sh.coop_split ? nb32 : 0u, p.n_rows = (p.nrows + BP_BLOCK - 1) / BP_BLOCK;
+    p.nwsum = p.r5 ? nb32 * BP_VB5_WINDOWS : (p.a_out ? nb32 * BP_VB_WINDOWS : p.nwin);   // wide: the window sums as their own launch
+    p.g_wsum = (p.nwsum + BP_BLOCK - 1) / BP_BLOCK;
+    p.g_colsum = (nb32 * 64 + BP_BLOCK - 1) / BP_BLOCK;
+    p.n_sc = (p.n_gen_terms + BP_BLOCK - 1) / BP_BLOCK;
+    p.nblk_p = (nb32 + FB_BLOCK - 1) / FB_BLOCK;
+    p.n_hw = p.aside ? 0u : (p.quad ? (p.one_lane ? p.nblk_p : (nb32 + 15) / 16) : nb32);   // launch 4's Horner role: elsewhere, a lane, four lanes, a wavefront per chain
+    p.g_stage4 = p.n_hw + ((p.narrow_walk && !p.quad) ? nb32 * p.nparts : p.nblk_p * p.nsplit);
+    p.walk_flags = (p.narrow_walk && !p.quad) ? ((p.hi ? (p.hi_levels == 4 ? 9u : 3u) : 1u) | (p.fused_finish ? 4u : 0u)) : 0u;
+    p.g_finish = p.finish1 ? (nb32 + 63) / 64 : (nb32 + 7) / 8;
+    // ---- arena
     arena_plan ap;
-    size_t off[7], boff[12];
-    if (rlc_bucket) plan_bucket(ap, 1, rlc_terms, bkp, boff);
-    else plan_vb_uniform(ap, nbatch, shape_verdict ? 0 : sh.U, off, narrow_hi ? 8 * hi_levels : (r5 ? 16 : 8), vb_chunk_sz);
-    const size_t off_digits = ap.add((size_t)npairs * nbatch * sizeof(fb_digit) + 16);
-    const size_t off_partial = ap.add((size_t)2 * nsplit * nbatch * sizeof(ge_ext) + 16);
-    const size_t off_fields = ap.add((size_t)fl.count * nbatch * BP_RP_REC * 4 + 16);
-    const size_t off_mv = ap.add(nbatch);
-    const size_t off_segs = (h_segs && nseg > RP_SEG_INLINE) ? ap.add((size_t)nseg * sizeof(rp_seg)) : 0;
-    // distinct labels among the items of a coalesced launch (usually one)
-    std::vector<uint32_t> seg_label_of;
-    std::vector<const uint8_t *> distinct_labels;
-    if (h_segs && tr.seg_labels) {
-        seg_label_of.resize(nseg);
-        for (uint32_t i = 0; i < nseg; i++) {
-            uint32_t j = 0;
-            while (j < distinct_labels.size() && tr.label_len != 0 && memcmp(distinct_labels[j], tr.seg_labels[i], tr.label_len) != 0) j++;
-            if (j == distinct_labels.size()) distinct_labels.push_back(tr.seg_labels[i]);
-            seg_label_of[i] = j;
+    const rp_fields fl = rp_field_layout(sh.k, sh.m);
+    if (p.rlc_bucket) plan_bucket(ap, 1, p.rlc_terms, p.bkp, p.boff);
+    else plan_vb_uniform(ap, nbatch, verdict_only ? 0 : sh.U, p.off, p.hi ? 8 * p.hi_levels : (p.r5 ? 16 : 8), p.vb_chunk_sz);
+    p.off_digits = ap.add((size_t)p.npairs * nbatch * sizeof(fb_digit) + 16);
+    p.off_partial = ap.add((size_t)2 * p.nsplit * nbatch * sizeof(ge_ext) + 16);
+    p.off_fields = ap.add((size_t)fl.count * nbatch * BP_RP_REC * 4 + 16);
+    p.off_mv = ap.add(nbatch);
+    p.off_segs = f.nseg > RP_SEG_INLINE ? ap.add((size_t)f.nseg * sizeof(rp_seg)) : 0;
+    p.off_inits = f.nlabels > 1 ? ap.add((size_t)f.nlabels * 256) : 0;   // items whose labels differ start from their own states
+    // batch-combination mode: coefficient accumulators, the column-sum reduction tree, and a batch-of-one table walk (digits, partial sums, result)
+    const size_t n_rows0 = verdict_only ? 0 : nbatch * ((sh.U + BP_VB_CHUNK - 1) / BP_VB_CHUNK);
+    p.off_acc = rlc ? ap.add((size_t)p.n_gen_terms * 10 * 8) : 0;
+    p.off_tree = rlc ? ap.add((n_rows0 / 8 + 64) * 64 * sizeof(ge_ext)) : 0;
+    p.off_dig1 = rlc ? ap.add((size_t)p.npairs * sizeof(fb_digit) + 16) : 0;
+    p.off_part1 = rlc ? ap.add((size_t)2 * p.nsplit1 * sizeof(ge_ext) + 16) : 0;
+    p.off_res1 = rlc ? ap.add(sizeof(ge_ext) + 64) : 0;   // Horner result, then 8 result words, verdict byte, chunk bounds
+    p.arena_need = ap.total;
+    // (a lane sized for wide chains also sees narrow ones, whose window sums come in more, smaller chunks)
+    p.arena_reserve = p.arena_need + ((p.narrow_ok && !narrow) ? (size_t)RP_NARROW_MAX * ((sh.U + p.narrow_q - 1) / p.narrow_q) * 64 * sizeof(ge_ext) : 0);
+}
+// (for tests/test_abi_and_host.py: the classifier and the plan are plain host logic.  opt: the fields of rp_plan_opts in their order; fact: nbatch, rlc,
+// ts_per_proof, ts_uniform, want_out, second_stream, nseg, nlabels.  out, when the shape is one to plan: [4 ..) as listed below; returns the count written)
+extern "C" int bpgpu_internal_chain_plan(const int64_t *opt, uint64_t n, uint64_t m, uint64_t proof_len, uint64_t gens_capacity, uint64_t party_capacity,
+                                         uint32_t window_bits, const int64_t *fact, uint64_t *out, uint32_t n_out) {
+    if (!opt || !fact || !out || n_out < 32 || window_bits < 1) return -1;
+    const rp_class cl = rp_classify(n, m, proof_len, gens_capacity, party_capacity);
+    out[0] = cl.all_verdict, out[1] = cl.shape_verdict, out[2] = cl.k, out[3] = cl.unsupported;
+    if (cl.all_verdict || cl.unsupported || fact[0] <= 0) return 4;
+    const rp_plan_opts o = {(uint32_t)opt[0], (uint32_t)opt[1], (uint32_t)opt[2], (uint32_t)opt[3], (uint32_t)opt[4], (int)opt[5], (int)opt[6], (int)opt[7],
+                            (int)opt[8], (int)opt[9], (int)opt[10], (int)opt[11], (int)opt[12], (int)opt[13], (int)opt[14], (int)opt[15], (int)opt[16],
+                            (int)opt[17], (int)opt[18], (int)opt[19]};
+    rp_call_facts f;
+    f.nbatch = (size_t)fact[0], f.rlc = fact[1], f.ts_per_proof = fact[2], f.ts_uniform = fact[3], f.want_out = fact[4], f.second_stream = fact[5];
+    f.nseg = (uint32_t)fact[6], f.nlabels = (uint32_t)fact[7];
+    fb_params prm;
+    prm.W = window_bits, prm.nwin = fb_nwin(window_bits), prm.half = 1u << (window_bits - 1), prm.n_gens = cl.shape_verdict ? 2 : (uint32_t)(2 * n * m + 2);
+    rp_chain_plan p;
+    rp_plan_chain(p, o, cl, n, m, proof_len, prm, f);
+    out[4] = p.refused != nullptr;
+    if (p.refused) return 5;
+    const uint64_t v[] = {p.forms, p.scripted, p.coop, p.sh.coop_split, p.narrow_walk, p.sh.narrow_hi, p.vb_chunk_sz, p.rlc_bucket, p.exp_form, p.exp_w3,
+                          p.fused_finish, p.finish1, p.nsplit, p.nsplit1, p.nparts, p.n_chunks, p.g_stage1, p.n_win + p.n_exp + p.n_rows, p.g_wsum, p.g_stage4,
+                          p.g_finish, p.quad, p.one_lane, p.arena_need, p.arena_reserve, p.off_digits, p.off_res1};
+    for (size_t i = 0; i < sizeof v / sizeof v[0]; i++) out[5 + i] = v[i];
+    return 5 + (int)(sizeof v / sizeof v[0]);
+}
+
+// ---- one verification call (device pointers; the context is locked, the device set) -----------------------------------------------------------
+struct rp_call {
+    // inputs
+    size_t n = 0, m = 0, nbatch = 0, proof_len = 0;
+    const void *d_proofs = nullptr, *d_commitments = nullptr;
+    rp_transcripts tr;
+    const void *d_rng64 = nullptr;       // 64 bytes per proof; null: expanded on the device from the chain's key
+    const void *d_weights64 = nullptr;   // combined check only; null: likewise
+    // outputs
+    void *d_verdict = nullptr;
+    void *d_msm_out = nullptr;           // per-proof check: 32 bytes per proof, optional
+    void *d_batch_out = nullptr;         // combined check: 33 bytes (batch verdict, encoding of the combined point), optional
+    // mode
+    bool rlc = false;                    // the batch-combined check (bpgpu_rangeproof_verify_rlc[_dev])
+    hipStream_t s = nullptr;
+    bool dev_call = false;               // a device-pointer entry point: nothing but this chain's own pieces is staged
+    // coalesced launch (bpgpu_pool_*): the nbatch proofs are the concatenation of nseg submitted items, each with its own input / output buffers
+    // (the pointers above stay null)
+    const rp_seg *segs = nullptr;
+    uint32_t nseg = 0;
+    bool seg_wants_out = false;          // some item wants its encodings (combined: the 33-byte result)
+    bool seg_brought_rng = false;        // every item brought its own rng bytes: the library draws none
+};
+// a chain on its way into the stream: the call, its plan, and the plan's pieces as pointers
+struct rp_chain {
+    bpgpu_ctx *c;
+    hipStream_t s;
+    const rp_call &a;
+    const rp_chain_plan &p;
+    rp_shape sh;                 // the plan's, with the chain's seed
+    fb_params prm;               // the window table the generator terms walk, its entries and the shape's ids in it
+    const fb_entry *gen_table;
+    uint32_t *d_ids;
+    rp_strobe_init init;
+    uint32_t ts_flags;
+    const rp_script_hdr *d_script;
+    rp_seg_tab segtab;
+    vb_dev d;
+    bk_dev bd;
+    ge_cached *tab_hi;           // the points' second to fourth tables (plan.hi), behind the first ones
+    uint32_t *d_status, *d_fields;
+    fb_digit *d_digits;
+    ge_ext *d_partial;
+    const uint8_t *rng_ptr, *wts_ptr;
+    bool want_out;
+};
+
+// every proof of the batch has the same malformed length: FormatError for all, the callers' transcripts untouched, nothing to combine
+static int rp_answer_malformed(bpgpu_ctx *c, const rp_call &a, uint32_t all_verdict) {
+    const rp_transcripts &tr = a.tr;
+    const size_t nbatch = a.nbatch;
+    hipStream_t s = a.s;
+    if (tr.d_ts_out) {
+        if (tr.d_ts_in) HIPCHK(c, hipMemcpyAsync(tr.d_ts_out, tr.d_ts_in, nbatch * BPGPU_TRANSCRIPT_BYTES, hipMemcpyDeviceToDevice, s));
+        else {
+            char *h = nullptr;
+            int rcp = c->io.pin_alloc(nbatch * BPGPU_TRANSCRIPT_BYTES, &h);
+            if (rcp) return rcp;
+            uint8_t st0[BPGPU_TRANSCRIPT_BYTES];
+            if (tr.shared_ts) memcpy(st0, tr.shared_ts, BPGPU_TRANSCRIPT_BYTES);
+            else bpgpu_transcript_new(tr.label, tr.label_len, st0);
+            for (size_t b = 0; b < nbatch; b++) memcpy(h + b * BPGPU_TRANSCRIPT_BYTES, st0, BPGPU_TRANSCRIPT_BYTES);
+            HIPCHK(c, hipMemcpyAsync(tr.d_ts_out, h, nbatch * BPGPU_TRANSCRIPT_BYTES, hipMemcpyHostToDevice, s));
         }
     }
-    const bool own_inits = distinct_labels.size() > 1;
-    const size_t off_inits = own_inits ? ap.add(distinct_labels.size() * 256) : 0;
-    // batch-combination mode: weights, coefficient accumulators, the column-sum reduction tree, and a batch-of-one
-    // table walk (digits, partial sums, result)
-    const uint32_t nsplit1 = rlc ? pick_splits(c, 1, npairs) : 0;
-    const size_t n_rows0 = shape_verdict ? 0 : nbatch * ((sh.U + BP_VB_CHUNK - 1) / BP_VB_CHUNK);
-    const size_t off_acc = rlc ? ap.add((size_t)n_gen_terms * 10 * 8) : 0;
-    const size_t off_tree = rlc ? ap.add((n_rows0 / 8 + 64) * 64 * sizeof(ge_ext)) : 0;
-    const size_t off_dig1 = rlc ? ap.add((size_t)npairs * sizeof(fb_digit) + 16) : 0;
-    const size_t off_part1 = rlc ? ap.add((size_t)2 * nsplit1 * sizeof(ge_ext) + 16) : 0;
-    const size_t off_res1 = rlc ? ap.add(sizeof(ge_ext) + 64) : 0;   // Horner result, then 8 result words, verdict byte, chunk bounds
-    size_t arena_need = ap.total;
-    if (reserve_only && narrow_ok && nbatch > 256)   // (a lane sized for wide chains also sees narrow ones, whose window sums come in more, smaller chunks)
-        arena_need += (size_t)256 * ((sh.U + narrow_q - 1) / narrow_q) * 64 * sizeof(ge_ext);
-    rc = arena_reserve(c, arena_need);
+    HIPCHK(c, hipMemsetAsync(a.d_verdict, (int)all_verdict, nbatch, s));
+    if (a.d_msm_out) HIPCHK(c, hipMemsetAsync(a.d_msm_out, 0, nbatch * 32, s));
+    if (a.rlc && a.d_batch_out) HIPCHK(c, hipMemsetAsync(a.d_batch_out, 0, 33, s));
+    return BPGPU_OK;
+}
+
+// which window table the generator terms walk: the secondary one when the shape fits it (bpgpu_gens_add_shape), else the primary; the shape's ids in it
+static int rp_table_for(bpgpu_ctx *c, const rp_class &cl, size_t n, size_t m, fb_params *prm, const fb_entry **table, uint32_t **d_ids) {
+    const bool use_sec = c->sec.d_table && !cl.shape_verdict && n <= c->sec.n && m <= c->sec.m;
+    *prm = use_sec ? c->sec.prm : c->prm;
+    *table = use_sec ? c->sec.d_table : c->d_table;
+    *d_ids = nullptr;
+    if (cl.shape_verdict) return BPGPU_OK;
+    return use_sec ? gen_ids_for_secondary(c, n, m, d_ids) : gen_ids_for(c, n, m, d_ids);
+}
+
+// the context's buffers as a plan wants them: the arena, the arrival counters of the fused finish, the status words
+static int rp_reserve_buffers(bpgpu_ctx *c, size_t arena_bytes, size_t nbatch) {
+    int rc = arena_reserve(c, arena_bytes);
     if (rc) return rc;
-    char *a = c->arena;
     if (!c->fin_cnt) {
         HIPCHK(c, hipMalloc((void **)&c->fin_cnt, 256 * 4));
         HIPCHK(c, hipMemset(c->fin_cnt, 0, 256 * 4));
@@ -2119,65 +2290,79 @@ static int rp_verify_dev_locked(bpgpu_ctx *c, size_t n, size_t m, size_t nbatch,
         c->rp_status_cap = nbatch;
         c->rp_status_dirty = true;
     }
-    if (reserve_only) {
-        bpgpu_ctx::plan_view pv0;
-        if (shape_verdict) return BPGPU_OK;
-        if (narrow_ok && narrow_q != BP_VB_CHUNK) {
-            rc = uniform_plan(c, nbatch < 256 ? nbatch : 256, sh.U, &pv0, narrow_q);
-            if (rc) return rc;
-        }
-        return (nbatch > 256 || vb_chunk_sz == BP_VB_CHUNK) ? uniform_plan(c, nbatch, sh.U, &pv0) : BPGPU_OK;
+    return BPGPU_OK;
+}
+
+// distinct labels among the items of a coalesced launch (usually one)
+struct rp_seg_labels {
+    std::vector<uint32_t> of;             // item -> index into `distinct`
+    std::vector<const uint8_t *> distinct;
+};
+static void rp_distinct_labels(rp_seg_labels &l, const rp_transcripts &tr, uint32_t nseg) {
+    l.of.resize(nseg);
+    for (uint32_t i = 0; i < nseg; i++) {
+        uint32_t j = 0;
+        while (j < l.distinct.size() && tr.label_len != 0 && memcmp(l.distinct[j], tr.seg_labels[i], tr.label_len) != 0) j++;
+        if (j == l.distinct.size()) l.distinct.push_back(tr.seg_labels[i]);
+        l.of[i] = j;
     }
-    uint32_t *d_status = c->rp_status;
-    fb_digit *d_digits = (fb_digit *)(a + off_digits);
-    ge_ext *d_partial = (ge_ext *)(a + off_partial);
-    uint32_t *d_fields = (uint32_t *)(a + off_fields);
-    uint8_t *d_mv = (uint8_t *)(a + off_mv);
+}
+
+// What a chain needs in place before launch 1: its seed, the start states of its items' labels, the segment table, the transcript start and script
+static int rp_stage_chain(rp_chain &ch, const rp_seg_labels &labels) {
+    bpgpu_ctx *c = ch.c;
+    const rp_call &a = ch.a;
+    const rp_chain_plan &p = ch.p;
+    const rp_transcripts &tr = a.tr;
+    hipStream_t s = ch.s;
+    char *arena = c->arena;
+    int rc;
     // randomness the caller did not bring -- the batching challenge's rng bytes (thread_rng() in verify_multiple, mod.rs:455-470), the
     // combination weights (unpredictable to the prover) -- is expanded inside launch 1 from ONE key per launch chain (rp_shape::seed,
     // rangeproof.h): drawn here from the calling thread's generator (hostrng.h), carried in the kernel's argument block
-    const uint8_t *rng_ptr = (const uint8_t *)d_rng64;
-    const uint8_t *wts_ptr = (const uint8_t *)d_weights64;
-    if (!rng_ptr) sh.seeded |= RP_SEED_RNG;
-    if (rlc && !wts_ptr) sh.seeded |= RP_SEED_WEIGHTS;
+    rp_shape &sh = ch.sh;
+    if (!ch.rng_ptr && !a.seg_brought_rng) sh.seeded |= RP_SEED_RNG;
+    if (a.rlc && !ch.wts_ptr) sh.seeded |= RP_SEED_WEIGHTS;
     if (sh.seeded) {
         if (c->test_seed_set) memcpy(sh.seed, c->test_seed, 32);
         else if (!bp::fast_random((uint8_t *)sh.seed, 32)) return fail(c, BPGPU_ERR_HIP, "getrandom failed");
     }
-    rp_seg_tab segtab;
-    memset(&segtab, 0, sizeof segtab);
+    const size_t nlabels = labels.distinct.size();
+    const bool own_inits = nlabels > 1;
     if (own_inits) {   // Transcript::new(label) + rangeproof_domain_sep(n, m) of every distinct label: 50 sponge words each, staged ahead of the chain
         char *h = nullptr;
-        rc = c->io.pin_alloc(distinct_labels.size() * 256, &h);
+        rc = c->io.pin_alloc(nlabels * 256, &h);
         if (rc) return rc;
-        for (size_t j = 0; j < distinct_labels.size(); j++) {
+        for (size_t j = 0; j < nlabels; j++) {
             rp_strobe_init ij;
-            make_strobe_init(ij, distinct_labels[j], tr.label_len, n, m);
+            make_strobe_init(ij, labels.distinct[j], tr.label_len, a.n, a.m);
             memcpy(h + j * 256, ij.w, 200);
         }
-        HIPCHK(c, hipMemcpyAsync(a + off_inits, h, distinct_labels.size() * 256, hipMemcpyHostToDevice, s));
+        HIPCHK(c, hipMemcpyAsync(arena + p.off_inits, h, nlabels * 256, hipMemcpyHostToDevice, s));
     }
     auto seg_fix = [&](rp_seg *dst) {   // (the pool's table carries no start states: they live in this chain's arena)
-        for (uint32_t i = 0; i < nseg; i++) dst[i].init_w = own_inits ? (const uint32_t *)(a + off_inits + (size_t)seg_label_of[i] * 256) : nullptr;
+        for (uint32_t i = 0; i < a.nseg; i++) dst[i].init_w = own_inits ? (const uint32_t *)(arena + p.off_inits + (size_t)labels.of[i] * 256) : nullptr;
     };
-    if (h_segs && nseg <= RP_SEG_INLINE) {   // travels in the kernels' argument blocks
-        segtab.n = nseg;
-        memcpy(segtab.in, h_segs, (size_t)nseg * sizeof(rp_seg));
+    rp_seg_tab &segtab = ch.segtab;
+    memset(&segtab, 0, sizeof segtab);
+    if (a.segs && a.nseg <= RP_SEG_INLINE) {   // travels in the kernels' argument blocks
+        segtab.n = a.nseg;
+        memcpy(segtab.in, a.segs, (size_t)a.nseg * sizeof(rp_seg));
         seg_fix(segtab.in);
-    } else if (h_segs) {
+    } else if (a.segs) {
         char *h = nullptr;
-        rc = c->io.pin_alloc((size_t)nseg * sizeof(rp_seg), &h);
+        rc = c->io.pin_alloc((size_t)a.nseg * sizeof(rp_seg), &h);
         if (rc) return rc;
-        memcpy(h, h_segs, (size_t)nseg * sizeof(rp_seg));
+        memcpy(h, a.segs, (size_t)a.nseg * sizeof(rp_seg));
         seg_fix((rp_seg *)h);
-        HIPCHK(c, hipMemcpyAsync(a + off_segs, h, (size_t)nseg * sizeof(rp_seg), hipMemcpyHostToDevice, s));
-        segtab.n = nseg;
-        segtab.ext = (const rp_seg *)(a + off_segs);
+        HIPCHK(c, hipMemcpyAsync(arena + p.off_segs, h, (size_t)a.nseg * sizeof(rp_seg), hipMemcpyHostToDevice, s));
+        segtab.n = a.nseg;
+        segtab.ext = (const rp_seg *)(arena + p.off_segs);
     }
-    rp_strobe_init init;
-    uint32_t ts_flags = 0;
+    rp_strobe_init &init = ch.init;
+    ch.ts_flags = 0;
     if (tr.d_ts_in || tr.shared_ts) {
-        ts_flags = BP_TS_DOMSEP;
+        ch.ts_flags = BP_TS_DOMSEP;
         if (tr.shared_ts) strobe_init_from_state(init, tr.shared_ts);
         else {
             memset(&init, 0, sizeof init);
@@ -2191,263 +2376,303 @@ static int rp_verify_dev_locked(bpgpu_ctx *c, size_t n, size_t m, size_t nbatch,
         uint8_t st0[BPGPU_TRANSCRIPT_BYTES];
         bpgpu_transcript_new(tr.label, tr.label_len, st0);
         strobe_init_from_state(init, st0);
-        ts_flags = BP_TS_DOMSEP;
+        ch.ts_flags = BP_TS_DOMSEP;
     } else {
-        make_strobe_init(init, tr.label, tr.label_len, n, m);
+        make_strobe_init(init, tr.label, tr.label_len, a.n, a.m);
     }
-    const rp_script_hdr *d_script = nullptr;
-    if ((!tr.d_ts_in || tr.ts_uniform) && !shape_verdict && !c->no_script) {   // every proof starts at the position of `init`: the per-shape script replaces the byte-wise replay
-        rc = script_for(c, s, sh.n, sh.m, sh.k, init, (ts_flags & BP_TS_DOMSEP) != 0, &d_script);
+    ch.d_script = nullptr;
+    if (p.scripted) {   // every proof starts at the position of `init`: the per-shape script replaces the byte-wise replay
+        rc = script_for(c, s, sh.n, sh.m, sh.k, init, (ch.ts_flags & BP_TS_DOMSEP) != 0, &ch.d_script);
         if (rc) return rc;
     }
-    if (c->io.pin_off > c->io.pin_marked && dev_call) {   // rng / weights / segment table / a new transcript script staged above, nothing else will be
+    if (c->io.pin_off > c->io.pin_marked && a.dev_call) {   // segment table / start states / a new transcript script staged above, nothing else will be
         rc = c->io.pin_mark(s);
         if (rc) return rc;
     }
-    if (c->rp_status_dirty) {   // (a chain whose enqueue failed half way: its status words and arrival counters were not handed back clean)
-        HIPCHK(c, hipMemsetAsync(d_status, 0, c->rp_status_cap * 4, s));
-        HIPCHK(c, hipMemsetAsync(c->fin_cnt, 0, 256 * 4, s));
+    return BPGPU_OK;
+}
+
+// ---- the launches of a chain, one function per branch ----------------------------------------------------------------------------------------
+// launch 1: transcripts and per-proof scalars || the proofs' points decoded into their tables -- 32 lanes per proof (narrow), lane = proof on the
+// script, lane = proof replaying byte-wise
+static int rp_enqueue_launch1(rp_chain &ch) {
+    bpgpu_ctx *c = ch.c;
+    const rp_chain_plan &p = ch.p;
+    const rp_transcripts &tr = ch.a.tr;
+    const bool bk = p.rlc_bucket;
+#define RP_L1_HEAD                                                                                                                                 \
+    ch.sh, ch.init, p.n_tr, (const uint8_t *)ch.a.d_proofs, (const uint8_t *)ch.a.d_commitments, ch.rng_ptr, ch.d_fields, ch.d.tab, ch.d_status, ch.prm, \
+        p.lg_m, bk ? ch.bd.rwords : ch.d.recoded, ch.d_digits, ch.a.rlc ? ch.wts_ptr : (const uint8_t *)nullptr
+#define RP_L1_TAIL                                                                                                                                 \
+    (const uint32_t *)tr.d_ts_in, (uint32_t *)tr.d_ts_out, bk ? ch.bd.pts : (fb_entry *)nullptr, bk ? p.bkp.c : 0u, ch.segtab, ch.d_script
+    if (p.coop) LAUNCH(c, ch.s, "rp_stage1", k_rp_stage1_coop, p.g_stage1, RP_BLOCK, RP_L1_HEAD, RP_L1_TAIL, p.n_pt, ch.tab_hi);
+    else LAUNCH_TF(c, ch.s, ch.d_script != nullptr, "rp_stage1", k_rp_stage1, p.g_stage1, RP_BLOCK, RP_L1_HEAD, ch.ts_flags, RP_L1_TAIL);
+#undef RP_L1_HEAD
+#undef RP_L1_TAIL
+    return BPGPU_OK;
+}
+// a shape the reference refuses: every proof that parsed gets the shape's code
+static int rp_enqueue_shape_verdict(rp_chain &ch) {
+    bpgpu_ctx *c = ch.c;
+    const rp_call &a = ch.a;
+    const uint32_t nb32 = ch.sh.nproofs;
+    uint8_t *d_mv = (uint8_t *)(c->arena + ch.p.off_mv);
+    HIPCHK(c, hipMemsetAsync(d_mv, 1, a.nbatch, ch.s));
+    LAUNCH(c, ch.s, "rp_verdict", k_rp_verdict, (nb32 + 63) / 64, 64, nb32, ch.d_status, d_mv, (uint8_t *)a.d_verdict);
+    if (a.d_msm_out) HIPCHK(c, hipMemsetAsync(a.d_msm_out, 0, a.nbatch * 32, ch.s));
+    if (a.rlc && a.d_batch_out) HIPCHK(c, hipMemsetAsync(a.d_batch_out, 0, 33, ch.s));
+    return BPGPU_OK;
+}
+// the last launch of a combined check: the one MSM's partial sums + its Horner result, the identity test, every proof's verdict
+static void rp_enqueue_rlc_finish(rp_chain &ch, const ge_ext *hq, const ge_ext *part1) {
+    LAUNCH_TF(ch.c, ch.s, ch.want_out, "rlc_finish", k_rlc_finish, 1, 64, ch.p.nsplit1, hq, part1, ch.sh.nproofs, ch.d_status, (uint8_t *)ch.a.d_verdict,
+              (uint8_t *)ch.a.d_batch_out, ch.segtab);
+}
+// ---- batch combination, bucket variant: R = sum_i rho_i MegaCheck_i with the per-proof terms as ONE MSM ----
+static int rp_enqueue_rlc_buckets(rp_chain &ch) {
+    bpgpu_ctx *c = ch.c;
+    hipStream_t s = ch.s;
+    const rp_chain_plan &p = ch.p;
+    const bk_params &bkp = p.bkp;
+    bk_dev &bd = ch.bd;
+    char *a = c->arena;
+    unsigned long long *d_acc = (unsigned long long *)(a + p.off_acc);
+    HIPCHK(c, hipMemsetAsync(d_acc, 0, (size_t)p.n_gen_terms * 10 * 8, s));
+    LAUNCH(c, s, "rlc_stage3", k_rlc_stage3, p.n_exp, BP_BLOCK, 0u, 0u, (const vb_chunk *)nullptr, (const ge_cached *)nullptr, (const uint32_t *)nullptr,
+           (ge_ext *)nullptr, p.nexp, ch.sh, ch.prm, ch.d_fields, ch.d_status, d_acc, (ch.a.nbatch % 64 == 0) ? 1 : 0);
+    const uint32_t tot32 = (uint32_t)p.rlc_terms;
+    int rc = enqueue_bucket_sort(c, s, bkp, 1u, tot32, p.rlc_terms, 1, bd, ch.d_status, ch.sh.U);
+    if (rc) return rc;
+    fb_digit *d_dig1 = (fb_digit *)(a + p.off_dig1);
+    ge_ext *d_part1 = (ge_ext *)(a + p.off_part1);
+    uint32_t *d_ctl = (uint32_t *)(a + p.off_res1 + sizeof(ge_ext));
+    const uint32_t nt = bkp.nwin * bkp.half, n_acc = (nt + BP_BLOCK - 1) / BP_BLOCK;
+    const uint32_t lim = bk_chain_lim(p.rlc_terms, bkp);
+    LAUNCH(c, s, "rlc_accum", k_rlc_accum_scalars, n_acc + p.n_sc, BP_BLOCK, n_acc, nt, bkp, tot32, bd.desc, bd.idx, bd.pts, bd.bsum, p.n_gen_terms,
+           (const unsigned long long *)d_acc, d_dig1, ch.prm, d_ctl, lim);
+    const uint32_t hg = bk_heavy_groups(bkp, 1);
+    LAUNCH(c, s, "bk_heavy", k_bk_heavy, bkp.nwin * hg, 64, bkp, tot32, (const bk_desc *)bd.desc, (const uint32_t *)bd.idx, (const fb_entry *)bd.pts, bd.bsum, lim, hg);
+    enqueue_bucket_reduce(c, s, bkp, bkp.nwin, bd);
+    LAUNCH(c, s, "rlc_stage4", k_rlc_stage4b, 1 + p.nsplit1, FB_BLOCK, bd.colq16, bd.hq, ch.prm, p.nsplit1, p.npairs, ch.d_ids, d_dig1, ch.gen_table, d_part1);
+    rp_enqueue_rlc_finish(ch, bd.hq, d_part1);
+    return BPGPU_OK;
+}
+// ---- batch combination (rlc.h): R = sum_i rho_i MegaCheck_i, the per-proof terms through the window sums and a tree of column sums ----
+static int rp_enqueue_rlc_tree(rp_chain &ch) {
+    bpgpu_ctx *c = ch.c;
+    hipStream_t s = ch.s;
+    const rp_chain_plan &p = ch.p;
+    vb_dev &d = ch.d;
+    char *a = c->arena;
+    unsigned long long *d_acc = (unsigned long long *)(a + p.off_acc);
+    HIPCHK(c, hipMemsetAsync(d_acc, 0, (size_t)p.n_gen_terms * 10 * 8, s));
+    LAUNCH(c, s, "rlc_stage3", k_rlc_stage3, p.n_win + p.n_exp, BP_BLOCK, p.n_win, p.nwin, d.chunks, d.tab, d.recoded, d.part, p.nexp, ch.sh, ch.prm,
+           ch.d_fields, ch.d_status, d_acc, (ch.a.nbatch % 64 == 0) ? 1 : 0);
+    // column sums over ALL chunks of ALL proofs: rows of 64 window sums, tree-added 16- then 8-way until <= 8 rows
+    // remain; the Horner wavefront adds those itself
+    fb_digit *d_dig1 = (fb_digit *)(a + p.off_dig1);
+    ge_ext *d_part1 = (ge_ext *)(a + p.off_part1), *d_hq1 = (ge_ext *)(a + p.off_res1);
+    uint32_t *d_ctl = (uint32_t *)(a + p.off_res1 + sizeof(ge_ext));   // [0] unused, [1] zero, [2..4) chunk bounds {0, rows}
+    ge_ext *cur = d.part, *next = (ge_ext *)(a + p.off_tree);
+    uint32_t rows = (uint32_t)p.n_chunks;
+    // a level leaves ng groups of rows; the coefficient reduction shares the launch of the last level (ng <= 8) -- or, where <= 8 rows need no level
+    // (ng = 0), has that launch to itself
+    for (bool last = false; !last;) {
+        const uint32_t group = rows > 64 ? 16 : 8, ng = rows > 8 ? (rows + group - 1) / group : 0, nt = ng * 64, n_level = (nt + BP_BLOCK - 1) / BP_BLOCK;
+        last = ng <= 8;
+        if (last)
+            LAUNCH(c, s, "rlc_colsum", k_rlc_colsum_scalars, n_level + p.n_sc, BP_BLOCK, n_level, nt, ng ? rows : 0u, ng ? group : 1u, (const ge_ext *)cur, next,
+                   p.n_gen_terms, (const unsigned long long *)d_acc, d_dig1, ch.prm, d_ctl, ng ? ng : rows);
+        else LAUNCH(c, s, "rlc_colsum", k_fb_reduce, n_level, BP_BLOCK, nt, 64u, rows, group, cur, next);
+        if (ng) cur = next, next = next + (size_t)nt, rows = ng;
     }
-    c->rp_status_dirty = true;   // until the kernel that resets the words has been enqueued
-    const uint32_t nb32 = (uint32_t)nbatch;
-    // the proof-specific ("variable-base") terms: decomposition into chunks of 32 is cached per (batch, U)
-    vb_dev d{};
-    bk_dev bd{};
-    if (rlc_bucket) bucket_bind(c, boff, bd);
-    bpgpu_ctx::plan_view pv, *pd = &pv;
-    if (!shape_verdict && !rlc_bucket) {
-        rc = uniform_plan(c, nbatch, sh.U, &pv, vb_chunk_sz);
-        if (rc) return rc;
-        vb_bind(c, off, d);
-        d.chunks = (vb_chunk *)pv.mem;
-        d.chunk_first = (uint32_t *)(pv.mem + pv.o1);
-        d.hq = (ge_ext *)((char *)d.colq16 + (size_t)nbatch * 64 * sizeof(ge_cached));
+    LAUNCH(c, s, "rlc_stage4", k_rp_stage4<64>, 1 + p.nsplit1, FB_BLOCK, 1u, d_ctl + 2, cur, (const ge_cached *)nullptr, d_hq1, ch.prm, 1u, 1u,
+           p.nsplit1, p.npairs, ch.d_ids, d_dig1, ch.gen_table, d_part1, 0u, (uint32_t *)nullptr, (uint32_t *)nullptr, (uint8_t *)nullptr, rp_seg_tab{});
+    rp_enqueue_rlc_finish(ch, d_hq1, d_part1);
+    return BPGPU_OK;
+}
+
+// more than one chunk per proof: the chunks' window sums added into column sums, as cached points (both the quad and the one-lane chain read them)
+static void rp_enqueue_colsum(rp_chain &ch) {
+    LAUNCH(ch.c, ch.s, "vb_colsum", k_vb_colsum, ch.p.g_colsum, BP_BLOCK, ch.sh.nproofs * 64, ch.d.chunk_first, ch.d.part, (uint32_t *)nullptr, (ge_cached *)ch.d.colq16);
+}
+// Launch 3 holds two independent roles -- window sums and generator exponents.  Narrow chains keep them fused (one launch fewer on the
+// latency path); wide chains split them, and may move the Horner chains to the second stream (rp_chain_forms).
+static int rp_enqueue_launch3_wide(rp_chain &ch) {
+    bpgpu_ctx *c = ch.c;
+    hipStream_t s = ch.s;
+    const rp_chain_plan &p = ch.p;
+    const rp_shape &sh = ch.sh;
+    vb_dev &d = ch.d;
+    const uint32_t nb32 = sh.nproofs;
+    ge_cached *d_colc = p.quad ? (ge_cached *)d.colq16 : nullptr;
+    const bool wide_sums = p.r5 || p.a_out;
+    // After launch 1 a chain has two INDEPENDENT branches: the proof's own points (window sums -> Horner chain) and the generator terms
+    // (exponents -> table walk); they meet in the finish.  With the Horner chains aside, the first branch's LAST kernel goes to the
+    // second stream.  (Moving the whole branch there, or the exponents instead, were options until round 6: no gain in their A/B.)
+    // (A burst of two wide chains runs its phases in lockstep -- profiles/r06/headline_burst_kernel_sequence.txt: both window sums, then both
+    // exponent launches, 470 us at two wavefronts per SIMD beside nothing but the Horner chains, then the walks.  Issuing the exponents on the second
+    // stream FIRST, under the window sums, was built and measured on the same box: no difference in any bench form, cfg4 -1.3 %
+    // (profiles/r06/exp_early_ab.txt) -- removed again.)
+    if (wide_sums) LAUNCH_TF(c, s, p.r5, "rp_stage3w", k_vb_window_wide, p.g_wsum, BP_BLOCK, p.nwsum, sh.U, p.a_out ? 1u : 0u, d.tab, d.recoded, d_colc);
+    else LAUNCH(c, s, "rp_stage3w", k_vb_window_colc, p.g_wsum, BP_BLOCK, p.nwsum, d.chunks, d.tab, d.recoded, d.part, (p.quad && p.one_chunk) ? d_colc : (ge_cached *)nullptr);
+    if (p.aside) {
+        if (!p.one_chunk && !wide_sums) rp_enqueue_colsum(ch);
+        HIPCHK(c, hipEventRecord(c->fork_ev, s));
+        HIPCHK(c, hipStreamWaitEvent(c->stream2, c->fork_ev, 0));
+        const ge_cached *extra = p.a_out ? d.tab : (const ge_cached *)nullptr;
+        if (wide_sums) LAUNCH_TF(c, c->stream2, p.r5, "rp_horner1", k_rp_horner_wide, p.nblk_p, FB_BLOCK, nb32, d_colc, extra, (p.r5 ? 16u : 8u) * sh.U, d.hq);
+        else LAUNCH(c, c->stream2, "rp_horner1", k_rp_horner1, p.nblk_p, FB_BLOCK, nb32, d_colc, d.hq);
+        HIPCHK(c, hipEventRecord(c->join_ev, c->stream2));
     }
-    // Horner layout: quads (16 chains per wavefront, least total work) unless the caller asked for the
-    // wavefront-per-chain variant (lowest latency of a single small batch)
-    const bool quad = !wave;                          // column sums as cached points (both the quad and the one-lane chain read them)
-    const bool one_lane = c->horner_lanes == 1;
-    ge_cached *d_colc = quad ? (ge_cached *)d.colq16 : nullptr;
-    const uint32_t n_tr = (nb32 + RP_BLOCK - 1) / RP_BLOCK;
-    const uint32_t n_pt = shape_verdict ? 0 : (nb32 * sh.U + RP_BLOCK - 1) / RP_BLOCK;
-    const bool coop = d_script && c->transcript_coop && nbatch <= 256;
-    sh.coop_split = (coop && c->coop_split && !rlc && !wide && !shape_verdict && sh.k < 32) ? 1u : 0u;   // (launch 3 then carries the basepoint-coefficient role)
-    const bool hi = narrow_hi && coop && sh.coop_split;
-    sh.narrow_hi = hi ? hi_levels : 0u;
-    ge_cached *tab_hi = hi ? d.tab + (size_t)8 * nb32 * sh.U : (ge_cached *)nullptr;
-    if (coop)   // narrow chain: 32 lanes per proof for the permutations (two proofs per workgroup)
-        LAUNCH(c, s, "rp_stage1", k_rp_stage1_coop, (nb32 + 1) / 2 + n_pt + (hi ? (hi_levels - 1) * nb32 * sh.U : 0u), RP_BLOCK, sh, init, (nb32 + 1) / 2, (const uint8_t *)d_proofs,
-           (const uint8_t *)d_commitments, rng_ptr, d_fields, d.tab, d_status, prm, lg_m, rlc_bucket ? bd.rwords : d.recoded, d_digits,
-           rlc ? wts_ptr : (const uint8_t *)nullptr, (const uint32_t *)tr.d_ts_in, (uint32_t *)tr.d_ts_out,
-           rlc_bucket ? bd.pts : (fb_entry *)nullptr, rlc_bucket ? bkp.c : 0u, segtab, d_script, n_pt, tab_hi);
-    else if (d_script)
-        LAUNCH(c, s, "rp_stage1", k_rp_stage1<true>, n_tr + n_pt, RP_BLOCK, sh, init, n_tr, (const uint8_t *)d_proofs,
-           (const uint8_t *)d_commitments, rng_ptr, d_fields, d.tab, d_status, prm, lg_m, rlc_bucket ? bd.rwords : d.recoded, d_digits,
-           rlc ? wts_ptr : (const uint8_t *)nullptr, ts_flags, (const uint32_t *)tr.d_ts_in, (uint32_t *)tr.d_ts_out,
-           rlc_bucket ? bd.pts : (fb_entry *)nullptr, rlc_bucket ? bkp.c : 0u, segtab, d_script);
-    else
-        LAUNCH(c, s, "rp_stage1", k_rp_stage1<false>, n_tr + n_pt, RP_BLOCK, sh, init, n_tr, (const uint8_t *)d_proofs,
-           (const uint8_t *)d_commitments, rng_ptr, d_fields, d.tab, d_status, prm, lg_m, rlc_bucket ? bd.rwords : d.recoded, d_digits,
-           rlc ? wts_ptr : (const uint8_t *)nullptr, ts_flags, (const uint32_t *)tr.d_ts_in, (uint32_t *)tr.d_ts_out,
-           rlc_bucket ? bd.pts : (fb_entry *)nullptr, rlc_bucket ? bkp.c : 0u, segtab, d_script);
-    if (shape_verdict) {
-        HIPCHK(c, hipMemsetAsync(d_mv, 1, nbatch, s));
-        LAUNCH(c, s, "rp_verdict", k_rp_verdict, (nb32 + 63) / 64, 64, nb32, d_status, d_mv, (uint8_t *)d_verdict);
-        if (d_msm_out) HIPCHK(c, hipMemsetAsync(d_msm_out, 0, nbatch * 32, s));
-        if (rlc && d_batch_out) HIPCHK(c, hipMemsetAsync(d_batch_out, 0, 33, s));
-        HIPCHK(c, hipGetLastError());
-        c->rp_status_dirty = false;
-        return BPGPU_OK;
-    }
-    // the generator-exponent role: one index per lane for narrow chains (latency), eight in mirrored pairs otherwise (rp_expand_b8_thread: least work)
-    const bool exp_single = !rlc && !wide && c->exp_single && nbatch <= 256 && sh.nm >= 4;
-    const bool pairs = !rlc && !exp_single && c->exp_pairs && sh.nm >= 8;
-    const uint32_t nexp = (exp_single ? sh.nm : sh.nm / (pairs ? 8 : 4)) * nb32, nwin = rlc_bucket ? 0u : (uint32_t)pd->n_chunks * 64;   // four generator indices per lane (eight in pairs)
-    const uint32_t n_win = (nwin + BP_BLOCK - 1) / BP_BLOCK, n_exp = (nexp + BP_BLOCK - 1) / BP_BLOCK;
-    if (rlc_bucket) {
-        // ---- batch combination, bucket variant: R = sum_i rho_i MegaCheck_i with the per-proof terms as ONE MSM ----
-        unsigned long long *d_acc = (unsigned long long *)(a + off_acc);
-        HIPCHK(c, hipMemsetAsync(d_acc, 0, (size_t)n_gen_terms * 10 * 8, s));
-        LAUNCH(c, s, "rlc_stage3", k_rlc_stage3, n_exp, BP_BLOCK, 0u, 0u, (const vb_chunk *)nullptr, (const ge_cached *)nullptr, (const uint32_t *)nullptr,
-               (ge_ext *)nullptr, nexp, sh, prm, d_fields, d_status, d_acc, (nbatch % 64 == 0) ? 1 : 0);
-        const uint32_t tot32 = (uint32_t)rlc_terms;
-        rc = enqueue_bucket_sort(c, s, bkp, 1u, tot32, rlc_terms, 1, bd, d_status, sh.U);
-        if (rc) return rc;
-        fb_digit *d_dig1 = (fb_digit *)(a + off_dig1);
-        ge_ext *d_part1 = (ge_ext *)(a + off_part1);
-        uint32_t *d_ctl = (uint32_t *)(a + off_res1 + sizeof(ge_ext));
-        const uint32_t nt = bkp.nwin * bkp.half, n_acc = (nt + BP_BLOCK - 1) / BP_BLOCK, n_sc = (n_gen_terms + BP_BLOCK - 1) / BP_BLOCK;
-        const uint32_t lim = bk_chain_lim(rlc_terms, bkp);
-        LAUNCH(c, s, "rlc_accum", k_rlc_accum_scalars, n_acc + n_sc, BP_BLOCK, n_acc, nt, bkp, tot32, bd.desc, bd.idx, bd.pts, bd.bsum, n_gen_terms,
-               (const unsigned long long *)d_acc, d_dig1, prm, d_ctl, lim);
-        const uint32_t hg = bk_heavy_groups(bkp, 1);
-        LAUNCH(c, s, "bk_heavy", k_bk_heavy, bkp.nwin * hg, 64, bkp, tot32, (const bk_desc *)bd.desc, (const uint32_t *)bd.idx, (const fb_entry *)bd.pts, bd.bsum, lim, hg);
-        enqueue_bucket_reduce(c, s, bkp, bkp.nwin, bd);
-        LAUNCH(c, s, "rlc_stage4", k_rlc_stage4b, 1 + nsplit1, FB_BLOCK, bd.colq16, bd.hq, prm, nsplit1, npairs, d_ids, d_dig1, gen_table, d_part1);
-        if (d_batch_out)
-            LAUNCH(c, s, "rlc_finish", k_rlc_finish<true>, 1, 64, nsplit1, bd.hq, d_part1, nb32, d_status, (uint8_t *)d_verdict, (uint8_t *)d_batch_out, segtab);
-        else
-            LAUNCH(c, s, "rlc_finish", k_rlc_finish<false>, 1, 64, nsplit1, bd.hq, d_part1, nb32, d_status, (uint8_t *)d_verdict, (uint8_t *)nullptr, segtab);
-        HIPCHK(c, hipGetLastError());
-        c->rp_status_dirty = false;
-        return BPGPU_OK;
-    }
-    if (rlc) {
-        // ---- batch combination (rlc.h): R = sum_i rho_i MegaCheck_i ---------------------------------------
-        unsigned long long *d_acc = (unsigned long long *)(a + off_acc);
-        HIPCHK(c, hipMemsetAsync(d_acc, 0, (size_t)n_gen_terms * 10 * 8, s));
-        LAUNCH(c, s, "rlc_stage3", k_rlc_stage3, n_win + n_exp, BP_BLOCK, n_win, nwin, d.chunks, d.tab, d.recoded, d.part, nexp, sh, prm,
-               d_fields, d_status, d_acc, (nbatch % 64 == 0) ? 1 : 0);
-        // column sums over ALL chunks of ALL proofs: rows of 64 window sums, tree-added 16- then 8-way until <= 8 rows
-        // remain; the Horner wavefront adds those itself
-        fb_digit *d_dig1 = (fb_digit *)(a + off_dig1);
-        ge_ext *d_part1 = (ge_ext *)(a + off_part1), *d_hq1 = (ge_ext *)(a + off_res1);
-        uint32_t *d_ctl = (uint32_t *)(a + off_res1 + sizeof(ge_ext));   // [0] unused, [1] zero, [2..4) chunk bounds {0, rows}
-        ge_ext *cur = d.part, *next = (ge_ext *)(a + off_tree);
-        uint32_t rows = (uint32_t)pd->n_chunks;
-        bool scalars_done = false;
-        const uint32_t n_sc = (n_gen_terms + BP_BLOCK - 1) / BP_BLOCK;
-        while (rows > 8) {
-            const uint32_t group = rows > 64 ? 16 : 8, ng = (rows + group - 1) / group, nt = ng * 64;
-            if (ng <= 8) {   // last level: shares its launch with the coefficient reduction
-                LAUNCH(c, s, "rlc_colsum", k_rlc_colsum_scalars, (nt + BP_BLOCK - 1) / BP_BLOCK + n_sc, BP_BLOCK, (nt + BP_BLOCK - 1) / BP_BLOCK, nt, rows,
-                       group, (const ge_ext *)cur, next, n_gen_terms, (const unsigned long long *)d_acc, d_dig1, prm, d_ctl, ng);
-                scalars_done = true;
-            } else {
-                LAUNCH(c, s, "rlc_colsum", k_fb_reduce, (nt + BP_BLOCK - 1) / BP_BLOCK, BP_BLOCK, nt, 64u, rows, group, cur, next);
-            }
-            cur = next;
-            next = next + (size_t)ng * 64;
-            rows = ng;
-        }
-        if (!scalars_done)
-            LAUNCH(c, s, "rlc_colsum", k_rlc_colsum_scalars, n_sc, BP_BLOCK, 0u, 0u, 0u, 1u, (const ge_ext *)cur, next, n_gen_terms,
-                   (const unsigned long long *)d_acc, d_dig1, prm, d_ctl, rows);
-        LAUNCH(c, s, "rlc_stage4", k_rp_stage4<64>, 1 + nsplit1, FB_BLOCK, 1u, d_ctl + 2, cur, (const ge_cached *)nullptr, d_hq1, prm, 1u, 1u,
-               nsplit1, npairs, d_ids, d_dig1, gen_table, d_part1, 0u, (uint32_t *)nullptr, (uint32_t *)nullptr, (uint8_t *)nullptr, rp_seg_tab{});
-        if (d_batch_out)
-            LAUNCH(c, s, "rlc_finish", k_rlc_finish<true>, 1, 64, nsplit1, d_hq1, d_part1, nb32, d_status, (uint8_t *)d_verdict, (uint8_t *)d_batch_out, segtab);
-        else
-            LAUNCH(c, s, "rlc_finish", k_rlc_finish<false>, 1, 64, nsplit1, d_hq1, d_part1, nb32, d_status, (uint8_t *)d_verdict, (uint8_t *)nullptr, segtab);
-        HIPCHK(c, hipGetLastError());
-        c->rp_status_dirty = false;
-        return BPGPU_OK;
-    }
-    const bool one_chunk = pd->n_chunks == nbatch;   // U <= 32: a chunk's window sums are the MSM's column sums
-    // Launch 3 holds two independent roles -- window sums and generator exponents.  Narrow chains keep them fused (one launch fewer on the
-    // latency path); wide chains split them, and may move the Horner chains to the second stream (rp_chain_forms).
-    bool horner_aside = false;
-    if (wide) {
-        const bool wide_sums = r5 || a_out;
-        // After launch 1 a chain has two INDEPENDENT branches: the proof's own points (window sums -> Horner chain) and the generator terms
-        // (exponents -> table walk); they meet in the finish.  With the Horner chains aside, the first branch's LAST kernel goes to the
-        // second stream.  (Moving the whole branch there, or the exponents instead, were options until round 6: no gain in their A/B.)
-        hipStream_t sw = s;
-        // (A burst of two wide chains runs its phases in lockstep -- profiles/r06/headline_burst_kernel_sequence.txt: both window sums, then both
-        // exponent launches, 470 us at two wavefronts per SIMD beside nothing but the Horner chains, then the walks.  Issuing the exponents on the second
-        // stream FIRST, under the window sums, was built and measured on the same box: no difference in any bench form, cfg4 -1.3 %
-        // (profiles/r06/exp_early_ab.txt) -- removed again.)
-        if (r5) {
-            const uint32_t nw5 = nb32 * BP_VB5_WINDOWS;
-            LAUNCH(c, sw, "rp_stage3w", k_vb_window_wide<true>, (nw5 + BP_BLOCK - 1) / BP_BLOCK, BP_BLOCK, nw5, sh.U, a_out ? 1u : 0u, d.tab, d.recoded, d_colc);
-        } else if (a_out) {
-            const uint32_t nw4 = nb32 * BP_VB_WINDOWS;
-            LAUNCH(c, sw, "rp_stage3w", k_vb_window_wide<false>, (nw4 + BP_BLOCK - 1) / BP_BLOCK, BP_BLOCK, nw4, sh.U, 1u, d.tab, d.recoded, d_colc);
-        } else {
-            LAUNCH(c, sw, "rp_stage3w", k_vb_window_colc, n_win, BP_BLOCK, nwin, d.chunks, d.tab, d.recoded, d.part, (quad && one_chunk) ? d_colc : (ge_cached *)nullptr);
-        }
-        if (aside) {
-            if (!one_chunk && !wide_sums) {
-                const uint32_t nc = nb32 * 64;
-                LAUNCH(c, sw, "vb_colsum", k_vb_colsum, (nc + BP_BLOCK - 1) / BP_BLOCK, BP_BLOCK, nc, d.chunk_first, d.part, (uint32_t *)nullptr, d_colc);
-            }
-            HIPCHK(c, hipEventRecord(c->fork_ev, s));
-            HIPCHK(c, hipStreamWaitEvent(c->stream2, c->fork_ev, 0));
-            const uint32_t n_hb = (nb32 + FB_BLOCK - 1) / FB_BLOCK;
-            const ge_cached *extra = a_out ? d.tab : (const ge_cached *)nullptr;
-            if (r5) LAUNCH(c, c->stream2, "rp_horner1", k_rp_horner_wide<true>, n_hb, FB_BLOCK, nb32, d_colc, extra, 16u * sh.U, d.hq);
-            else if (a_out) LAUNCH(c, c->stream2, "rp_horner1", k_rp_horner_wide<false>, n_hb, FB_BLOCK, nb32, d_colc, extra, 8u * sh.U, d.hq);
-            else LAUNCH(c, c->stream2, "rp_horner1", k_rp_horner1, n_hb, FB_BLOCK, nb32, d_colc, d.hq);
-            HIPCHK(c, hipEventRecord(c->join_ev, c->stream2));
-            horner_aside = true;
-        }
-        if (pairs && sh.nm >= (uint32_t)c->exp_w3_min_nm) LAUNCH(c, s, "rp_stage3", k_rp_exponents_w3, n_exp, BP_BLOCK, nexp, sh, prm, d_fields, d_digits, d_status);   // (aggregated shapes: three wavefronts per SIMD)
-        else if (pairs) LAUNCH(c, s, "rp_stage3", k_rp_exponents<true>, n_exp, BP_BLOCK, nexp, sh, prm, d_fields, d_digits, d_status);
-        else LAUNCH(c, s, "rp_stage3", k_rp_exponents<false>, n_exp, BP_BLOCK, nexp, sh, prm, d_fields, d_digits, d_status);
-    } else {
-        const uint32_t nrows = sh.coop_split ? nb32 : 0u, n_rows = (nrows + BP_BLOCK - 1) / BP_BLOCK;
-        ge_cached *colc3 = (quad && one_chunk) ? d_colc : (ge_cached *)nullptr;
-        if (exp_single) LAUNCH(c, s, "rp_stage3", k_rp_stage3<2>, n_win + n_exp + n_rows, BP_BLOCK, n_win, nwin, d.chunks, d.tab, d.recoded, d.part, colc3, nexp, sh, prm,
-                               d_fields, d_digits, d_status, n_exp, nrows, lg_m, (const ge_cached *)tab_hi);
-        else if (pairs) LAUNCH(c, s, "rp_stage3", k_rp_stage3<1>, n_win + n_exp + n_rows, BP_BLOCK, n_win, nwin, d.chunks, d.tab, d.recoded, d.part, colc3, nexp, sh, prm,
-                               d_fields, d_digits, d_status, n_exp, nrows, lg_m, (const ge_cached *)tab_hi);
-        else LAUNCH(c, s, "rp_stage3", k_rp_stage3<0>, n_win + n_exp + n_rows, BP_BLOCK, n_win, nwin, d.chunks, d.tab, d.recoded, d.part, colc3, nexp, sh, prm,
-                    d_fields, d_digits, d_status, n_exp, nrows, lg_m, (const ge_cached *)tab_hi);
-    }
-    if (quad && !one_chunk && !horner_aside) {
-        const uint32_t nc = nb32 * 64;
-        LAUNCH(c, s, "vb_colsum", k_vb_colsum, (nc + BP_BLOCK - 1) / BP_BLOCK, BP_BLOCK, nc, d.chunk_first, d.part, (uint32_t *)nullptr, d_colc);
-    }
-    const uint32_t nblk_p = (nb32 + FB_BLOCK - 1) / FB_BLOCK;
-    uint32_t nparts = nsplit;   // partial sums per proof that launch 4 leaves
-    // verdicts only (the crate's own call: nobody asks for the mega-check's encoding) and at most four partial sums per proof: the LAST of a proof's
-    // 1 + nsplit / 64 workgroups of launch 4 to arrive adds them to the Horner result and writes the verdict -- no finish launch (option narrow_fused_finish)
-    // (same-box A/B, profiles/r06/fused_finish_ab.txt: 64 threads +5 %, 256 threads +3 %, tickets and 16 threads unchanged, ONE proof per chain -2.5 % -- the
-    // finisher's three additions then follow the Horner wavefront instead of overlapping with the launch of the next kernel: chains of >= 8 proofs only)
-    const bool fused_finish = narrow_walk && c->narrow_fused_finish && nbatch >= 8 && !d_msm_out && nsplit / FB_BLOCK <= 4 && !(quad || horner_aside);
-    if (horner_aside) {
-        LAUNCH(c, s, "rp_stage4", k_rp_stage4<4>, nblk_p * nsplit, FB_BLOCK, 0u, d.chunk_first, d.part, d_colc, d.hq, prm, nb32, nblk_p,
-               nsplit, npairs, d_ids, d_digits, gen_table, d_partial, 0u, (uint32_t *)nullptr, (uint32_t *)nullptr, (uint8_t *)nullptr, rp_seg_tab{});
-        HIPCHK(c, hipStreamWaitEvent(s, c->join_ev, 0));
-    } else if (quad && one_lane) {
-        const uint32_t n_hw = (nb32 + FB_BLOCK - 1) / FB_BLOCK;
-        LAUNCH(c, s, "rp_stage4", k_rp_stage4<1>, n_hw + nblk_p * nsplit, FB_BLOCK, n_hw, d.chunk_first, d.part, d_colc, d.hq, prm, nb32, nblk_p,
-               nsplit, npairs, d_ids, d_digits, gen_table, d_partial, 0u, (uint32_t *)nullptr, (uint32_t *)nullptr, (uint8_t *)nullptr, rp_seg_tab{});
-    } else if (quad) {
-        const uint32_t n_hw = (nb32 + 15) / 16;
-        LAUNCH(c, s, "rp_stage4", k_rp_stage4<4>, n_hw + nblk_p * nsplit, FB_BLOCK, n_hw, d.chunk_first, d.part, d_colc, d.hq, prm, nb32, nblk_p,
-               nsplit, npairs, d_ids, d_digits, gen_table, d_partial, 0u, (uint32_t *)nullptr, (uint32_t *)nullptr, (uint8_t *)nullptr, rp_seg_tab{});
-    } else if (narrow_walk) {   // lane = split: a proof's partial sums are folded inside launch 4 (k_rp34.hip: rp_walk_narrow)
-        nparts = nsplit / FB_BLOCK;
-        LAUNCH(c, s, "rp_stage4", k_rp_stage4<64>, nb32 + nb32 * nparts, FB_BLOCK, nb32, d.chunk_first, d.part, (const ge_cached *)nullptr, d.hq,
-               prm, nb32, nblk_p, nsplit, npairs, d_ids, d_digits, gen_table, d_partial, (hi ? (hi_levels == 4 ? 9u : 3u) : 1u) | (fused_finish ? 4u : 0u), c->fin_cnt, d_status,
-               (uint8_t *)d_verdict, segtab);
-    } else {
-        LAUNCH(c, s, "rp_stage4", k_rp_stage4<64>, nb32 + nblk_p * nsplit, FB_BLOCK, nb32, d.chunk_first, d.part, (const ge_cached *)nullptr, d.hq,
-               prm, nb32, nblk_p, nsplit, npairs, d_ids, d_digits, gen_table, d_partial, 0u, (uint32_t *)nullptr, (uint32_t *)nullptr, (uint8_t *)nullptr, rp_seg_tab{});
-    }
-    if (fused_finish) {   // (the last workgroup of every proof has written its verdict and zeroed its status word)
-        HIPCHK(c, hipGetLastError());
-        c->rp_status_dirty = false;
-        return BPGPU_OK;
-    }
+    if (p.exp_w3) LAUNCH(c, s, "rp_stage3", k_rp_exponents_w3, p.n_exp, BP_BLOCK, p.nexp, sh, ch.prm, ch.d_fields, ch.d_digits, ch.d_status);
+    else LAUNCH_TF(c, s, p.exp_form == RP_EXP_PAIRS, "rp_stage3", k_rp_exponents, p.n_exp, BP_BLOCK, p.nexp, sh, ch.prm, ch.d_fields, ch.d_digits, ch.d_status);
+    return BPGPU_OK;
+}
+static int rp_enqueue_launch3_fused(rp_chain &ch) {
+    const rp_chain_plan &p = ch.p;
+    vb_dev &d = ch.d;
+    ge_cached *colc3 = (p.quad && p.one_chunk) ? (ge_cached *)d.colq16 : (ge_cached *)nullptr;
+    LAUNCH_SEL3(ch.c, ch.s, p.exp_form, 0, 1, 2, "rp_stage3", k_rp_stage3, p.n_win + p.n_exp + p.n_rows, BP_BLOCK, p.n_win, p.nwin, d.chunks, d.tab, d.recoded, d.part,
+                colc3, p.nexp, ch.sh, ch.prm, ch.d_fields, ch.d_digits, ch.d_status, p.n_exp, p.nrows, p.lg_m, (const ge_cached *)ch.tab_hi);
+    return BPGPU_OK;
+}
+// launch 4: the Horner chains (unless they ran aside) || the walk of the generator table -- one lane, four lanes (also the form without a Horner role)
+// or a wavefront per chain; a narrow walk (lane = split: k_rp34.hip rp_walk_narrow) folds a proof's partial sums itself and may finish the proof
+static int rp_enqueue_launch4(rp_chain &ch) {
+    bpgpu_ctx *c = ch.c;
+    const rp_chain_plan &p = ch.p;
+    vb_dev &d = ch.d;
+    const bool folds = p.walk_flags != 0;
+    const ge_cached *d_colc = p.quad ? (const ge_cached *)d.colq16 : nullptr;
+    LAUNCH_SEL3(c, ch.s, !p.quad ? 2 : ((p.one_lane && !p.aside) ? 0 : 1), 1, 4, 64, "rp_stage4", k_rp_stage4, p.g_stage4, FB_BLOCK, p.n_hw, d.chunk_first, d.part, d_colc,
+                d.hq, ch.prm, ch.sh.nproofs, p.nblk_p, p.nsplit, p.npairs, ch.d_ids, ch.d_digits, ch.gen_table, ch.d_partial, p.walk_flags,
+                folds ? c->fin_cnt : (uint32_t *)nullptr, folds ? ch.d_status : (uint32_t *)nullptr, folds ? (uint8_t *)ch.a.d_verdict : (uint8_t *)nullptr,
+                folds ? ch.segtab : rp_seg_tab{});
+    if (p.aside) HIPCHK(c, hipStreamWaitEvent(ch.s, c->join_ev, 0));
+    return BPGPU_OK;
+}
+// the finish: a proof's partial sums + its Horner result, the identity test, the verdict (and the encoding, where wanted)
+static int rp_enqueue_finish(rp_chain &ch) {
+    bpgpu_ctx *c = ch.c;
+    const rp_chain_plan &p = ch.p;
+    const uint32_t nb32 = ch.sh.nproofs;
     ge_ext *d_red = nullptr;
     uint32_t nred = 0;
-    enqueue_fb_reduce(c, s, nb32, nparts, d_partial, &d_red, &nred, 64);   // 8 lanes x <= 8 partials each in finish8
-    if (nred <= 2 && narrow_walk) {   // one or two partial sums + the Horner result per proof: lane = proof (more: eight lanes per proof and a three-level fold, below)
-        if (d_msm_out)
-            LAUNCH(c, s, "finish1", k_finish1<true>, (nb32 + 63) / 64, 64, nb32, nred, d.hq, d_red, d_status, (uint32_t *)d_msm_out, (uint8_t *)d_verdict, 1, segtab);
-        else
-            LAUNCH(c, s, "finish1", k_finish1<false>, (nb32 + 63) / 64, 64, nb32, nred, d.hq, d_red, d_status, (uint32_t *)nullptr, (uint8_t *)d_verdict, 1, segtab);
-    } else if (d_msm_out)
-        LAUNCH(c, s, "finish8", k_finish8<true>, (nb32 + 7) / 8, 64, nb32, nred, d.hq, d_red, d_status, (uint32_t *)d_msm_out, (uint8_t *)d_verdict, 1, segtab);
-    else
-        LAUNCH(c, s, "finish8", k_finish8<false>, (nb32 + 7) / 8, 64, nb32, nred, d.hq, d_red, d_status, (uint32_t *)nullptr, (uint8_t *)d_verdict, 1, segtab);
+    enqueue_fb_reduce(c, ch.s, nb32, p.nparts, ch.d_partial, &d_red, &nred, 64);   // 8 lanes x <= 8 partials each in finish8
+#define RP_FINISH_ARGS nb32, nred, ch.d.hq, d_red, ch.d_status, (uint32_t *)ch.a.d_msm_out, (uint8_t *)ch.a.d_verdict, 1, ch.segtab
+    if (p.finish1) LAUNCH_TF(c, ch.s, ch.want_out, "finish1", k_finish1, p.g_finish, 64, RP_FINISH_ARGS);
+    else LAUNCH_TF(c, ch.s, ch.want_out, "finish8", k_finish8, p.g_finish, 64, RP_FINISH_ARGS);
+#undef RP_FINISH_ARGS
+    return BPGPU_OK;
+}
+static int rp_enqueue_chain(rp_chain &ch) {
+    const rp_chain_plan &p = ch.p;
+    int rc = rp_enqueue_launch1(ch);
+    if (rc) return rc;
+    if (ch.sh.shape_verdict) return rp_enqueue_shape_verdict(ch);
+    if (p.rlc_bucket) return rp_enqueue_rlc_buckets(ch);
+    if (ch.a.rlc) return rp_enqueue_rlc_tree(ch);
+    rc = p.wide ? rp_enqueue_launch3_wide(ch) : rp_enqueue_launch3_fused(ch);
+    if (rc) return rc;
+    if (p.quad && !p.one_chunk && !p.aside) rp_enqueue_colsum(ch);
+    rc = rp_enqueue_launch4(ch);
+    if (rc || p.fused_finish) return rc;   // (fused: the last workgroup of every proof has written its verdict and zeroed its status word)
+    return rp_enqueue_finish(ch);
+}
+
+// One launch chain over a.nbatch proofs of one shape: classify, plan, reserve, stage, enqueue.
+static int rp_verify_chain(bpgpu_ctx *c, const rp_call &a) {
+    const rp_transcripts &tr = a.tr;
+    hipStream_t s = a.s;
+    if (a.nbatch == 0) {
+        if (a.rlc && a.d_batch_out) HIPCHK(c, hipMemsetAsync(a.d_batch_out, 0, 33, s));
+        return BPGPU_OK;
+    }
+    if (!c->d_table) return fail(c, BPGPU_ERR_NO_GENS, "generators not loaded");
+    if (a.nbatch > 0x7fffffffu / 64) return fail(c, BPGPU_ERR_INVALID_ARG, "batch too large");
+    const rp_class cl = rp_classify(a.n, a.m, a.proof_len, c->gens_capacity, c->party_capacity);
+    if (tr.shared_ts && !ts_state_ok(tr.shared_ts)) return fail(c, BPGPU_ERR_INVALID_ARG, "malformed transcript state");
+    if (a.segs && (cl.all_verdict || tr.d_ts_in || tr.d_ts_out || tr.shared_ts || (a.rlc && a.d_weights64)))   // (the pool sends such items through the ordinary entry point)
+        return fail(c, BPGPU_ERR_INVALID_ARG, "coalesced launches take well-formed shapes and a label only (batch-combined ones: library-drawn weights)");
+    if (cl.all_verdict) return rp_answer_malformed(c, a, cl.all_verdict);
+    if (cl.unsupported) return fail(c, BPGPU_ERR_INVALID_ARG, "n*m > 2^%d not supported", BP_RP_MAX_K);
+    if (a.segs && cl.shape_verdict) return fail(c, BPGPU_ERR_INVALID_ARG, "coalesced launches take well-formed shapes only");
+    rp_seg_labels labels;
+    if (a.segs && tr.seg_labels) rp_distinct_labels(labels, tr, a.nseg);
+    rp_call_facts f;
+    f.nbatch = a.nbatch;
+    f.rlc = a.rlc;
+    f.ts_per_proof = tr.d_ts_in != nullptr;
+    f.ts_uniform = tr.ts_uniform;
+    f.want_out = a.segs ? a.seg_wants_out : (a.rlc ? a.d_batch_out : a.d_msm_out) != nullptr;
+    f.second_stream = s == c->stream2;
+    f.nseg = a.segs ? a.nseg : 0;
+    f.nlabels = (uint32_t)labels.distinct.size();
+    fb_params prm;
+    const fb_entry *gen_table;
+    uint32_t *d_ids;
+    int rc = rp_table_for(c, cl, a.n, a.m, &prm, &gen_table, &d_ids);
+    if (rc) return rc;
+    rp_chain_plan p;
+    rp_plan_chain(p, rp_plan_opts_of(c), cl, a.n, a.m, a.proof_len, prm, f);
+    if (p.refused) return fail(c, BPGPU_ERR_INVALID_ARG, "%s", p.refused);
+    rc = rp_reserve_buffers(c, p.arena_need, a.nbatch);
+    if (rc) return rc;
+    rp_chain ch = {c, s, a, p, p.sh, prm, gen_table, d_ids};
+    char *arena = c->arena;
+    ch.d_status = c->rp_status;
+    ch.d_digits = (fb_digit *)(arena + p.off_digits);
+    ch.d_partial = (ge_ext *)(arena + p.off_partial);
+    ch.d_fields = (uint32_t *)(arena + p.off_fields);
+    ch.rng_ptr = (const uint8_t *)a.d_rng64;
+    ch.wts_ptr = (const uint8_t *)a.d_weights64;
+    ch.want_out = f.want_out;
+    rc = rp_stage_chain(ch, labels);
+    if (rc) return rc;
+    if (c->rp_status_dirty) {   // (a chain whose enqueue failed half way: its status words and arrival counters were not handed back clean)
+        HIPCHK(c, hipMemsetAsync(ch.d_status, 0, c->rp_status_cap * 4, s));
+        HIPCHK(c, hipMemsetAsync(c->fin_cnt, 0, 256 * 4, s));
+    }
+    c->rp_status_dirty = true;   // until the kernel that resets the words has been enqueued: every error return below leaves it set
+    // the proof-specific ("variable-base") terms: decomposition into chunks is cached per (U, chunk size)
+    if (p.rlc_bucket) bucket_bind(c, p.boff, ch.bd);
+    else if (!cl.shape_verdict) {
+        bpgpu_ctx::plan_view pv;
+        rc = uniform_plan(c, a.nbatch, ch.sh.U, &pv, p.vb_chunk_sz);
+        if (rc) return rc;
+        vb_bind(c, p.off, ch.d);
+        ch.d.chunks = (vb_chunk *)pv.mem;
+        ch.d.chunk_first = (uint32_t *)(pv.mem + pv.o1);
+        ch.d.hq = (ge_ext *)((char *)ch.d.colq16 + a.nbatch * 64 * sizeof(ge_cached));
+        ch.tab_hi = p.hi ? ch.d.tab + (size_t)8 * ch.sh.nproofs * ch.sh.U : (ge_cached *)nullptr;
+    }
+    rc = rp_enqueue_chain(ch);
+    if (rc) return rc;
     HIPCHK(c, hipGetLastError());
     c->rp_status_dirty = false;
     return BPGPU_OK;
 }
 
 // ---- entry points: device pointers ----------------------------------------------------------------------
-static int rp_dev_call(bpgpu_ctx *c, size_t n, size_t m, size_t nbatch, const void *d_proofs, size_t proof_len, const void *d_commitments,
-                       const rp_transcripts &tr, const void *d_rng64, void *d_verdict, void *d_msm_out, void *stream, bool rlc,
-                       const void *d_weights64, void *d_batch_out) {
-    if (!c || (nbatch && (!d_proofs || !d_verdict || (m && !d_commitments))) || (tr.label_len && !tr.label)) return BPGPU_ERR_INVALID_ARG;
-    if (((uintptr_t)d_proofs | (uintptr_t)d_commitments | (uintptr_t)d_rng64 | (uintptr_t)d_weights64 | (uintptr_t)tr.d_ts_in | (uintptr_t)tr.d_ts_out) & 3)
+// what every call brings: the shape, the proofs with their commitments and transcripts, the rng bytes, where the verdicts go.  The rest -- encodings,
+// the combined check with its weights and result, segments -- is set by name
+static rp_call rp_call_of(size_t n, size_t m, size_t nbatch, const void *d_proofs, size_t proof_len, const void *d_commitments, const rp_transcripts &tr,
+                          const void *d_rng64, void *d_verdict) {
+    rp_call a;
+    a.n = n, a.m = m, a.nbatch = nbatch, a.proof_len = proof_len;
+    a.d_proofs = d_proofs, a.d_commitments = d_commitments, a.tr = tr, a.d_rng64 = d_rng64, a.d_verdict = d_verdict;
+    return a;
+}
+static int rp_dev_call(bpgpu_ctx *c, rp_call a, void *stream) {
+    const rp_transcripts &tr = a.tr;
+    if (!c || (a.nbatch && (!a.d_proofs || !a.d_verdict || (a.m && !a.d_commitments))) || (tr.label_len && !tr.label)) return BPGPU_ERR_INVALID_ARG;
+    if (((uintptr_t)a.d_proofs | (uintptr_t)a.d_commitments | (uintptr_t)a.d_rng64 | (uintptr_t)a.d_weights64 | (uintptr_t)tr.d_ts_in | (uintptr_t)tr.d_ts_out) & 3)
         return fail(c, BPGPU_ERR_INVALID_ARG, "device buffers must be 4-byte aligned");
+    a.dev_call = true;
     return dev_call(c, stream, [&](hipStream_t s) {
-        return rp_verify_dev_locked(c, n, m, nbatch, d_proofs, proof_len, d_commitments, tr, d_rng64, d_verdict, d_msm_out, s, rlc, d_weights64, d_batch_out,
-                                  nullptr, 0, true);
+        a.s = s;
+        return rp_verify_chain(c, a);
     });
 }
 
@@ -2455,11 +2680,9 @@ static int rp_dev_call(bpgpu_ctx *c, size_t n, size_t m, size_t nbatch, const vo
 // can batches of this shape share a launch chain?  (malformed lengths / parameter errors take the ordinary entry point,
 // which reports them per proof)
 bool bpgpu_internal_rp_coalescible(bpgpu_ctx *c, size_t n, size_t m, size_t proof_len) {
-    if (proof_len % 32 != 0 || proof_len < 9 * 32 || ((proof_len / 32 - 9) & 1)) return false;
-    const size_t k = (proof_len / 32 - 9) / 2;
-    if (k > BP_RP_MAX_K || !(n == 8 || n == 16 || n == 32 || n == 64) || m == 0) return false;
     std::lock_guard<std::mutex> lk(c->mu);
-    return c->d_table && c->gens_capacity >= n && c->party_capacity >= m && n * m == ((size_t)1 << k);
+    const rp_class cl = rp_classify(n, m, proof_len, c->gens_capacity, c->party_capacity);
+    return c->d_table && !cl.all_verdict && !cl.shape_verdict && !cl.unsupported;
 }
 // has everything enqueued on the context's own stream completed?
 bool bpgpu_internal_idle(bpgpu_ctx *c) {
@@ -2492,25 +2715,53 @@ int bpgpu_internal_rp_verify_segs(bpgpu_ctx *c, size_t n, size_t m, size_t proof
         tr.seg_labels = labels;
         c->splits_hint = splits_hint;
         c->busy_hint = busy;
-        // d_rng64: a non-null dummy keeps the library from drawing randomness nobody reads (every item brought its own)
-        const int rc = rp_verify_dev_locked(c, n, m, total, nullptr, proof_len, nullptr, tr, any_rng_missing ? nullptr : (const void *)segs[0].rng64, nullptr,
-                                            (any_msm && !rlc) ? (void *)segs : nullptr, s, rlc, nullptr, (any_msm && rlc) ? (void *)segs : nullptr, segs, nseg, true);
+        rp_call a = rp_call_of(n, m, total, nullptr, proof_len, nullptr, tr, nullptr, nullptr);   // (inputs and outputs: the items' own)
+        a.rlc = rlc;
+        a.s = s;
+        a.dev_call = true;
+        a.segs = segs;
+        a.nseg = nseg;
+        a.seg_wants_out = any_msm;
+        a.seg_brought_rng = !any_rng_missing;   // (the library then draws no randomness: nobody would read it)
+        const int rc = rp_verify_chain(c, a);
         c->splits_hint = 0;
         c->busy_hint = -1;
         return rc;
     });
 }
-// buffers of the context sized for chains of up to `nbatch_max` proofs of this shape (see rp_verify_dev_locked, reserve_only)
+// buffers of the context sized for chains of up to `nbatch_max` proofs of this shape -- the arena, the status words, the cached chunk decompositions:
+// a lane of the pool's combining queue sees chains of every width and should not grow its buffers (a device-wide synchronisation each time) on the way
+// up.  Sized from the plan of the widest per-proof chain on a label, beside other chains (rp_chain_plan::arena_reserve).
 int bpgpu_internal_rp_reserve(bpgpu_ctx *c, size_t n, size_t m, size_t proof_len, size_t nbatch_max) {
     if (!c) return BPGPU_ERR_INVALID_ARG;
     std::lock_guard<std::mutex> lk(c->mu);
     HIPCHK(c, hipSetDevice(c->device));
-    rp_transcripts tr;
-    c->busy_hint = 1;
-    const int rc = rp_verify_dev_locked(c, n, m, nbatch_max, nullptr, proof_len, nullptr, tr, (const void *)c, nullptr, nullptr, c->stream, false, nullptr, nullptr,
-                                        nullptr, 0, true, true);
-    c->busy_hint = -1;
-    return rc;
+    if (nbatch_max == 0) return BPGPU_OK;
+    if (!c->d_table) return fail(c, BPGPU_ERR_NO_GENS, "generators not loaded");
+    if (nbatch_max > 0x7fffffffu / 64) return fail(c, BPGPU_ERR_INVALID_ARG, "batch too large");
+    const rp_class cl = rp_classify(n, m, proof_len, c->gens_capacity, c->party_capacity);
+    if (cl.all_verdict) return BPGPU_OK;   // (a malformed length never reaches a chain)
+    if (cl.unsupported) return fail(c, BPGPU_ERR_INVALID_ARG, "n*m > 2^%d not supported", BP_RP_MAX_K);
+    fb_params prm;
+    const fb_entry *gen_table;
+    uint32_t *d_ids;
+    int rc = rp_table_for(c, cl, n, m, &prm, &gen_table, &d_ids);
+    if (rc) return rc;
+    rp_plan_opts o = rp_plan_opts_of(c);
+    o.busy_hint = 1;
+    rp_call_facts f;
+    f.nbatch = nbatch_max;
+    rp_chain_plan p;
+    rp_plan_chain(p, o, cl, n, m, proof_len, prm, f);
+    if (p.refused) return fail(c, BPGPU_ERR_INVALID_ARG, "%s", p.refused);
+    rc = rp_reserve_buffers(c, p.arena_reserve, nbatch_max);
+    if (rc || cl.shape_verdict) return rc;
+    bpgpu_ctx::plan_view pv0;
+    if (p.narrow_ok && p.narrow_q != BP_VB_CHUNK) {   // the narrow chains the lane will see
+        rc = uniform_plan(c, nbatch_max < RP_NARROW_MAX ? nbatch_max : RP_NARROW_MAX, p.sh.U, &pv0, p.narrow_q);
+        if (rc) return rc;
+    }
+    return (nbatch_max > RP_NARROW_MAX || p.vb_chunk_sz == BP_VB_CHUNK) ? uniform_plan(c, nbatch_max, p.sh.U, &pv0) : BPGPU_OK;
 }
 // the context's own stream (the pool's combining queue enqueues its staging copies around the chain)
 void *bpgpu_internal_stream(bpgpu_ctx *c) { return c ? (void *)c->stream : nullptr; }
@@ -2532,7 +2783,11 @@ int bpgpu_internal_rp_verify_chain(bpgpu_ctx *c, size_t n, size_t m, size_t nbat
         tr.u_flags = flags;
         c->splits_hint = splits_hint;
         c->busy_hint = busy;
-        const int rc = rp_verify_dev_locked(c, n, m, nbatch, d_proofs, proof_len, d_commitments, tr, d_rng64, d_verdict, d_msm_out, s, false, nullptr, nullptr, nullptr, 0, true);
+        rp_call a = rp_call_of(n, m, nbatch, d_proofs, proof_len, d_commitments, tr, d_rng64, d_verdict);
+        a.d_msm_out = d_msm_out;
+        a.s = s;
+        a.dev_call = true;
+        const int rc = rp_verify_chain(c, a);
         c->splits_hint = 0;
         c->busy_hint = -1;
         return rc;
@@ -2545,7 +2800,9 @@ extern "C" int bpgpu_rangeproof_verify_batch_dev(bpgpu_ctx *c, size_t n, size_t 
     rp_transcripts tr;
     tr.label = label;
     tr.label_len = label_len;
-    return rp_dev_call(c, n, m, nbatch, d_proofs, proof_len, d_commitments, tr, d_rng64, d_verdict, d_msm_out, stream, false, nullptr, nullptr);
+    rp_call a = rp_call_of(n, m, nbatch, d_proofs, proof_len, d_commitments, tr, d_rng64, d_verdict);
+    a.d_msm_out = d_msm_out;
+    return rp_dev_call(c, a, stream);
 }
 
 extern "C" int bpgpu_rangeproof_verify_batch_ts_dev(bpgpu_ctx *c, size_t n, size_t m, size_t nbatch, const void *d_proofs, size_t proof_len,
@@ -2559,7 +2816,9 @@ extern "C" int bpgpu_rangeproof_verify_batch_ts_dev(bpgpu_ctx *c, size_t n, size
     tr.shared_ts = shared_transcript;
     tr.d_ts_in = d_transcripts;
     tr.d_ts_out = d_transcripts_out;
-    return rp_dev_call(c, n, m, nbatch, d_proofs, proof_len, d_commitments, tr, d_rng64, d_verdict, d_msm_out, stream, false, nullptr, nullptr);
+    rp_call a = rp_call_of(n, m, nbatch, d_proofs, proof_len, d_commitments, tr, d_rng64, d_verdict);
+    a.d_msm_out = d_msm_out;
+    return rp_dev_call(c, a, stream);
 }
 
 extern "C" int bpgpu_rangeproof_verify_rlc_dev(bpgpu_ctx *c, size_t n, size_t m, size_t nbatch, const void *d_proofs, size_t proof_len,
@@ -2568,7 +2827,11 @@ extern "C" int bpgpu_rangeproof_verify_rlc_dev(bpgpu_ctx *c, size_t n, size_t m,
     rp_transcripts tr;
     tr.label = label;
     tr.label_len = label_len;
-    return rp_dev_call(c, n, m, nbatch, d_proofs, proof_len, d_commitments, tr, d_rng64, d_verdict, nullptr, stream, true, d_weights64, d_batch_out);
+    rp_call a = rp_call_of(n, m, nbatch, d_proofs, proof_len, d_commitments, tr, d_rng64, d_verdict);
+    a.rlc = true;
+    a.d_weights64 = d_weights64;
+    a.d_batch_out = d_batch_out;
+    return rp_dev_call(c, a, stream);
 }
 
 // ---- entry points: host pointers -------------------------------------------------------------------------
@@ -2601,9 +2864,13 @@ static int rp_host_call(bpgpu_ctx *c, size_t n, size_t m, size_t nbatch, const u
     tr.d_ts_out = ts_out_host ? io.d(r_to) : nullptr;
     char *d_rng = rng64 ? io.d(r_r) : nullptr;
     rc = io.upload();
-    if (!rc)
-        rc = rp_verify_dev_locked(c, n, m, nbatch, io.d(r_p), proof_len, io.d(r_c), tr, d_rng, io.d(r_v), msm_out ? io.d(r_o) : nullptr, s, rlc,
-                                  weights64 ? io.d(r_w) : nullptr, rlc ? io.d(r_b) : nullptr);
+    rp_call a = rp_call_of(n, m, nbatch, io.d(r_p), proof_len, io.d(r_c), tr, d_rng, io.d(r_v));
+    a.s = s;
+    a.d_msm_out = msm_out ? io.d(r_o) : nullptr;
+    a.rlc = rlc;
+    a.d_weights64 = weights64 ? io.d(r_w) : nullptr;
+    a.d_batch_out = rlc ? io.d(r_b) : nullptr;
+    if (!rc) rc = rp_verify_chain(c, a);
     rc = io.download(rc);
     if (submit && !rc) {   // asynchronous form: leave the results in flight; bpgpu_ctx_collect (or the next call) delivers them
         const int rcl = io.leave_in_flight();
@@ -2623,7 +2890,11 @@ static int rp_host_call(bpgpu_ctx *c, size_t n, size_t m, size_t nbatch, const u
     if (rlc) {
         // where the combination is not the identity some proof fails: find out which, proof by proof (inputs are still on the device)
         rc = io.deliver_combined(r_v, verdict, nbatch, r_b, batch_out, r_to, ts_out_host, nbatch * TS,
-                                 [&] { return rp_verify_dev_locked(c, n, m, nbatch, io.d(r_p), proof_len, io.d(r_c), tr, d_rng, io.d(r_v), nullptr, s); });
+                                 [&] {   // the per-proof chain on the same inputs
+                                     a.rlc = false;
+                                     a.d_weights64 = a.d_batch_out = nullptr;
+                                     return rp_verify_chain(c, a);
+                                 });
         if (rc) return rc;
     } else {
         memcpy(verdict, io.h(r_v), nbatch);
@@ -6692,20 +6963,13 @@ static rp_transcripts rp_mix_transcripts(const rp_mix_group &g) {
 }
 }  // namespace
 
-// The checks rp_verify_dev_locked makes before its first launch -- the length-only part of from_bytes (mod.rs:505-510, ipp.rs:374-388),
-// then the parameter checks of verify_multiple_with_rng (mod.rs:358-366, ipp.rs:209): 0 = a shape the combination takes (k set),
-// 1 = the per-shape path gives every proof of the group one code
+// A group's class (rp_classify): whole = false -- a shape the combination takes (k set); whole = true -- the per-shape path gives every proof
+// of the group one code
 static int rp_mix_classify(bpgpu_ctx *c, size_t n, size_t m, size_t proof_len, size_t *k_out, bool *whole) {
-    *whole = true;
-    *k_out = 0;
-    if (proof_len % 32 != 0 || proof_len < 9 * 32 || (proof_len - 9 * 32) % 64 != 0) return BPGPU_OK;
-    const size_t k = (proof_len - 9 * 32) / 64;
-    if (k >= 32) return BPGPU_OK;
-    if (!(n == 8 || n == 16 || n == 32 || n == 64) || c->gens_capacity < n || c->party_capacity < m) return BPGPU_OK;
-    if (m == 0 || n * m != ((size_t)1 << k)) return BPGPU_OK;
-    if (k > BP_RP_MAX_K) return fail(c, BPGPU_ERR_INVALID_ARG, "n*m > 2^%d not supported", BP_RP_MAX_K);
-    *k_out = k;
-    *whole = false;
+    const rp_class cl = rp_classify(n, m, proof_len, c->gens_capacity, c->party_capacity);
+    if (cl.unsupported) return fail(c, BPGPU_ERR_INVALID_ARG, "n*m > 2^%d not supported", BP_RP_MAX_K);
+    *whole = cl.all_verdict || cl.shape_verdict;
+    *k_out = *whole ? 0 : cl.k;
     return BPGPU_OK;
 }
 
@@ -6749,8 +7013,9 @@ static int rp_mix_dev_locked(bpgpu_ctx *c, std::vector<rp_mix_group> &gr, size_t
     // groups rejected as a whole: the per-shape path's own codes, written now; the verdict launch leaves them alone
     for (const auto &g : gr) {
         if (!g.whole || g.nbatch == 0) continue;
-        rc = rp_verify_dev_locked(c, g.n, g.m, g.nbatch, g.d_proofs, g.proof_len, g.d_coms, rp_mix_transcripts(g), d_rng64 + 64 * g.gp0, d_verdict + g.gp0,
-                                  nullptr, s);
+        rp_call a = rp_call_of(g.n, g.m, g.nbatch, g.d_proofs, g.proof_len, g.d_coms, rp_mix_transcripts(g), d_rng64 + 64 * g.gp0, d_verdict + g.gp0);
+        a.s = s;
+        rc = rp_verify_chain(c, a);
         if (rc) return rc;
         HIPCHK(c, hipMemsetAsync(d_gst + 4 * g.gp0, 0xff, 4 * g.nbatch, s));   // (every word RLC_GSTATUS_DONE)
     }
@@ -6919,8 +7184,9 @@ static int rp_mix_host_call(bpgpu_ctx *c, size_t ngroups, const size_t *n, const
     return io.deliver_combined(r_v, verdict, total, r_b, batch_out, r_to, transcripts_out, total * TS, [&] {
         for (const auto &g : gr) {
             if (g.whole) continue;
-            const int rcg = rp_verify_dev_locked(c, g.n, g.m, g.nbatch, g.d_proofs, g.proof_len, g.d_coms, rp_mix_transcripts(g), d_rng_used + 64 * g.gp0, d_v + g.gp0,
-                                                 nullptr, s);
+            rp_call a = rp_call_of(g.n, g.m, g.nbatch, g.d_proofs, g.proof_len, g.d_coms, rp_mix_transcripts(g), d_rng_used + 64 * g.gp0, d_v + g.gp0);
+            a.s = s;
+            const int rcg = rp_verify_chain(c, a);
             if (rcg) return rcg;
         }
         return (int)BPGPU_OK;
@@ -6948,7 +7214,7 @@ extern "C" int bpgpu_rangeproof_verify_rlc_mixed_ts(bpgpu_ctx *c, size_t ngroups
                             batch_out, transcripts_out);
 }
 
-// ---- the one-shape combination on the callers' own transcripts (rp_verify_dev_locked with rlc = true and caller states) -----------------
+// ---- the one-shape combination on the callers' own transcripts (rp_verify_chain with rlc = true and caller states) -----------------
 extern "C" int bpgpu_rangeproof_verify_rlc_ts(bpgpu_ctx *c, size_t n, size_t m, size_t nbatch, const uint8_t *proofs, size_t proof_len, const uint8_t *commitments,
                                               const uint8_t *transcripts, size_t transcript_stride, const uint8_t *rng64, const uint8_t *weights64,
                                               uint8_t *verdict, uint8_t *batch_out, uint8_t *transcripts_out) {
@@ -6983,7 +7249,11 @@ extern "C" int bpgpu_rangeproof_verify_rlc_ts_dev(bpgpu_ctx *c, size_t n, size_t
     tr.shared_ts = shared_transcript;
     tr.d_ts_in = d_transcripts;
     tr.d_ts_out = d_transcripts_out;
-    return rp_dev_call(c, n, m, nbatch, d_proofs, proof_len, d_commitments, tr, d_rng64, d_verdict, nullptr, stream, true, d_weights64, d_batch_out);
+    rp_call a = rp_call_of(n, m, nbatch, d_proofs, proof_len, d_commitments, tr, d_rng64, d_verdict);
+    a.rlc = true;
+    a.d_weights64 = d_weights64;
+    a.d_batch_out = d_batch_out;
+    return rp_dev_call(c, a, stream);
 }
 
 namespace {

@@ -35,20 +35,13 @@ __global__ void __attribute__((amdgpu_waves_per_eu(2, 2))) __launch_bounds__(RP_
         st.w = lds + threadIdx.x;
         st.stride = RP_BLOCK;
         if (p < sh.nproofs) {
-            // (BP_EXP_*: timing experiments only -- tools/archive/stage1_breakdown.py builds variants with one role compiled out)
-#ifndef BP_EXP_NOTR
             if (SCRIPTED) rp_transcript_scripted(p, sh, init, st, rp_resolve(p, sh, proofs, commitments, rng64, segs), script, fields, status, ts_out, ts_in);
             else rp_transcript_thread(p, sh, init, st, rp_resolve(p, sh, proofs, commitments, rng64, segs), fields, status, ts_flags, ts_in, ts_out);
-#endif
-#ifndef BP_EXP_NOSC
             if (!sh.shape_verdict) rp_expand_a_thread(p, sh, prm, lg_m, fields, recoded, digits, status, rho64, bk_c);
-#endif
         }
     } else {
         const uint32_t t = (blockIdx.x - n_tr) * RP_BLOCK + threadIdx.x;
-#ifndef BP_EXP_NOPT
         if (t < sh.nproofs * sh.U) rp_points_thread(t, sh, rp_resolve(t / sh.U, sh, proofs, commitments, nullptr, segs), tab, status, bk_pts);
-#endif
     }
 }
 template __global__ void k_rp_stage1<true>(rp_shape, rp_strobe_init, uint32_t, const uint8_t *, const uint8_t *, const uint8_t *, uint32_t *, ge_cached *, uint32_t *, fb_params,
@@ -126,10 +119,8 @@ __global__ void __launch_bounds__(RP_BLOCK) k_rp_stage1_coop(rp_shape sh, rp_str
             if ((lane & 31) == 0) sgo[g] = (valid && (sflag[g] & 2u) && !sh.shape_verdict) ? 1u : 0u;
             __syncthreads();
             if (valid) rp_split_invert_lane(lane & 31, p, sh, fields, recoded, sp, defer ? &df : nullptr);
-#ifndef BP_EXP_NOREST   // timing experiments only
             if (valid && (lane & 31) == 0 && !sh.shape_verdict)
                 rp_expand_a_thread(p, sh, prm, lg_m, fields, recoded, digits, status, nullptr, 0, defer ? &df : nullptr, RP_SKIP_INV | RP_SKIP_ROWS);
-#endif
         } else {
             rp_transcript_scripted_coop(pp, valid, lane, sh, init, st, in, script, fields, status, ts_out, ts_in);
             if (valid && (lane & 31) == 0 && !sh.shape_verdict) rp_expand_a_thread(p, sh, prm, lg_m, fields, recoded, digits, status, rho64, bk_c, defer ? &df : nullptr);

@@ -79,10 +79,6 @@ BP_HD void keccak_f1600_lanes(uint64_t a[25]) {
 }
 
 BP_HD void keccak_f1600(const kstate &s) {
-#ifdef BP_EXP_NOKECCAK   // timing experiments only (tools/archive/stage1_breakdown.py)
-    ks_set32(s, 0, ks_get32(s, 0) + 1);
-    return;
-#endif
     uint64_t a[25];
 #pragma unroll
     for (int i = 0; i < 25; i++) a[i] = (uint64_t)ks_get32(s, 2 * i) | ((uint64_t)ks_get32(s, 2 * i + 1) << 32);
@@ -115,11 +111,7 @@ BP_HD void keccak_f1600_masked(const kstate &s, const uint32_t *mask, uint32_t n
         if ((uint32_t)(2 * i + 1) < nmask) hi ^= mask[2 * i + 1];
         a[i] = (uint64_t)lo | ((uint64_t)hi << 32);
     }
-#ifdef BP_EXP_NOKECCAK
-    a[0] += 1;
-#else
     keccak_f1600_lanes(a);
-#endif
 #pragma unroll
     for (int i = 0; i < 25; i++) {
         ks_set32(s, 2 * i, (uint32_t)a[i]);
@@ -206,16 +198,12 @@ __device__ __forceinline__ void keccak_f1600_masked_coop(const kstate &st, const
     if (2 * j < nmask) lo ^= mask[2 * j];
     if (2 * j + 1 < nmask) hi ^= mask[2 * j + 1];
     uint64_t a = ((uint64_t)hi << 32) | lo;
-#ifdef BP_EXP_NOKECCAK   // timing experiments only
-    a += 1;
-#else
 #pragma unroll 1
     for (uint32_t r = 0; r < 24; r++) {
         const uint64_t c = kc_p1(a, x, y, g);
         const uint64_t b = kc_p23(a, c, src, rho_src, g);
         a = kc_p4(b, x, y, j, r, g);
     }
-#endif
     if (jj < 25) {
         st.w[(2 * j) * st.stride] = (uint32_t)a;
         st.w[(2 * j + 1) * st.stride] = (uint32_t)(a >> 32);

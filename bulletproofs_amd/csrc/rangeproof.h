@@ -1009,13 +1009,7 @@ BP_HD void rp_split_invert_lane(uint32_t i, uint32_t p, const rp_shape &sh, uint
     sc v, vi;
 #pragma unroll
     for (int q = 0; q < 8; q++) v.v[q] = sp.park[8 * i + q];
-#if defined(BP_EXP_NOINV)   // timing experiments only (tools/r06/call32.sh builds variants with one phase compiled out; results are then wrong)
-    vi = v;
-#elif defined(BP_EXP_CTINV)
-    sc_invert_safegcd(vi, v);
-#else
     sc_invert_safegcd_var(vi, v);
-#endif
     sc28 vm, im, sq, isq;
     sc_to_mont28(vm, v);
     sc_to_mont28(im, vi);

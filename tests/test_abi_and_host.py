@@ -164,6 +164,129 @@ def test_chain_form_decision_table():
     assert forms(50000, other=1, busy=1) == 0 and forms(50000, s2=1, busy=1) == WIDE
 
 
+PLAN_OPTS = {"fixed_splits": 0, "splits_hint": 0, "horner_lanes": 0, "per_proof_radix": 0, "bucket_min_terms": 0, "busy_hint": -1, "a_outside": 1,
+             "split_stage3": -1, "narrow_walk": 1, "narrow_hi_max": 32, "narrow_hi4_max": 4, "narrow_chunk": 0, "narrow_fused_finish": 1, "transcript_coop": 1,
+             "coop_split": 1, "coop_defer_emit": 1, "exp_single": 1, "exponent_pairs": 1, "exp_w3_min_nm": 1024, "no_script": 0}   # a context's defaults
+PLAN_FACTS = ("nbatch", "rlc", "ts_per_proof", "ts_uniform", "want_out", "second_stream", "nseg", "nlabels")
+PLAN_OUT = ("all_verdict", "shape_verdict", "k", "unsupported", "refused", "forms", "scripted", "coop", "coop_split", "narrow_walk", "narrow_hi", "vb_chunk",
+            "rlc_bucket", "exp_form", "exp_w3", "fused_finish", "finish1", "nsplit", "nsplit1", "nparts", "n_chunks", "g_stage1", "g_stage3", "g_wsum", "g_stage4",
+            "g_finish", "quad", "one_lane", "arena_need", "arena_reserve", "off_digits", "off_res1")
+
+
+def _chain_plan(nbatch, n=8, m=1, proof_len=None, caps=None, W=4, **kw):
+    """bpgpu_internal_chain_plan (csrc/bpgpu.hip: rp_classify + rp_plan_chain) -> {name: value}; kw: options (PLAN_OPTS) and call facts (PLAN_FACTS)"""
+    import ctypes as C
+    import types
+    import bulletproofs_amd as bp
+    f = bp.lib().bpgpu_internal_chain_plan
+    f.restype = C.c_int
+    f.argtypes = [C.POINTER(C.c_int64)] + [C.c_uint64] * 5 + [C.c_uint32, C.POINTER(C.c_int64), C.POINTER(C.c_uint64), C.c_uint32]
+    assert all(k in PLAN_OPTS or k in PLAN_FACTS for k in kw), kw
+    if proof_len is None:
+        proof_len = 32 * (9 + 2 * (n * m).bit_length() - 2)
+    opts = (C.c_int64 * len(PLAN_OPTS))(*[kw.get(k, d) for k, d in PLAN_OPTS.items()])
+    facts = (C.c_int64 * len(PLAN_FACTS))(*[nbatch if k == "nbatch" else kw.get(k, 0) for k in PLAN_FACTS])
+    out = (C.c_uint64 * 64)()
+    cnt = f(opts, n, m, proof_len, *(caps or (n, m)), W, facts, out, 64)
+    assert cnt in (4, 5, len(PLAN_OUT)), cnt
+    return types.SimpleNamespace(**dict(zip(PLAN_OUT[:cnt], out[:cnt])))
+
+
+def test_chain_plan_rules_at_their_boundaries():
+    """rp_plan_chain (csrc/bpgpu.hip): everything decided about a launch chain before its first launch, as a function of the context options, the
+    shape, the window table and the facts of the call -- plain host logic.  Each rule the code and DESIGN.md sections 3.1 / 3.2 / 3.2a state is
+    checked on both sides of its boundary.  (8, 1) at 4-bit windows: 18 generator terms x 64 windows = 1152 (term, window) pairs, U = 11."""
+    P = _chain_plan
+    WIDE, SINGLE, PAIRS, FOUR = 1, 2, 1, 0
+    # ---- the 256-proof rule: everything narrow flips between 256 and 257 proofs
+    a, b = P(256), P(257)
+    assert (a.coop, a.coop_split, a.narrow_walk, a.vb_chunk, a.exp_form, a.quad) == (1, 1, 1, 8, SINGLE, 0)
+    assert (b.coop, b.coop_split, b.narrow_walk, b.vb_chunk, b.exp_form, b.quad) == (0, 0, 0, 32, PAIRS, 1)
+    assert a.scripted == b.scripted == 1 and P(3, ts_per_proof=1).scripted == 0 and P(3, ts_per_proof=1, ts_uniform=1).scripted == 1 and P(3, no_script=1).scripted == 0
+    assert P(3, ts_per_proof=1).coop == 0 and P(3, transcript_coop=0).coop == 0 and P(3, transcript_coop=0).narrow_hi == 0
+    # ---- table levels: four up to narrow_hi4_max proofs, two up to narrow_hi_max, one above
+    assert [P(nb).narrow_hi for nb in (4, 5, 32, 33)] == [4, 2, 2, 0]
+    assert [P(nb, narrow_hi_max=10, narrow_hi4_max=2).narrow_hi for nb in (2, 3, 10, 11)] == [4, 2, 2, 0]
+    assert P(1, narrow_hi_max=0).narrow_hi == 0 and P(1, coop_split=0).narrow_hi == 0 and P(1, narrow_walk=0).narrow_hi == 0
+    assert P(2).g_stage1 == 1 + 1 + 3 * 2 * 11 and P(5).g_stage1 == 3 + 1 + 5 * 11 and P(33).g_stage1 == 17 + 6   # two proofs per group, 64 points per group, a wavefront per further table
+    # ---- the narrow walk: whole wavefronts of splits, at least four pairs per split, two / four wavefronts with second / fourth tables
+    for splits in (1, 3, 8, 65, 100, 4096):
+        for nb in (1, 5, 33, 256):
+            p = P(nb, fixed_splits=splits)
+            assert p.narrow_walk and p.nsplit % 64 == 0 and p.nsplit >= 64 and p.nparts == p.nsplit // 64 and (p.nsplit == 64 or 1152 // p.nsplit >= 4), (splits, nb)
+        assert P(257, fixed_splits=splits).nsplit == P(257, fixed_splits=splits).nparts == splits
+    assert P(1, fixed_splits=1).nsplit == 256 and P(5, fixed_splits=1).nsplit == 128 and P(33, fixed_splits=1).nsplit == 64
+    # ---- the fused finish: from 8 proofs, without encodings, with at most four partial sums per proof (2304 pairs at 2-bit windows: 256 / 320 splits)
+    assert [P(nb).fused_finish for nb in (7, 8, 256, 257)] == [0, 1, 1, 0] and P(8, want_out=1).fused_finish == 0 and P(8, narrow_fused_finish=0).fused_finish == 0
+    assert [(p.nparts, p.fused_finish) for p in (P(8, W=2, fixed_splits=256), P(8, W=2, fixed_splits=320))] == [(4, 1), (5, 0)]
+    # ---- the finish launch: lane = proof for one or two partial sums of a narrow walk, else eight lanes per proof
+    assert [P(33, fixed_splits=s).finish1 for s in (64, 128, 192)] == [1, 1, 0] and P(257, fixed_splits=1).finish1 == 0
+    assert P(65, fixed_splits=64).g_finish == 2 and P(257).g_finish == 33
+    # ---- chunks of the window sums: narrow_chunk 0 -> 8, below 2 -> 2, capped at the wide chunk size; wide chunks from 257 proofs, and for one-lane / quad contexts
+    assert [P(9, narrow_chunk=q).vb_chunk for q in (0, 1, 2, 5, 32, 40)] == [8, 2, 2, 5, 32, 32]
+    assert P(257, narrow_chunk=5).vb_chunk == 32 and P(9, horner_lanes=4).vb_chunk == 32 and P(9, horner_lanes=64).vb_chunk == 8
+    assert P(9).n_chunks == 9 * 2 and P(257).n_chunks == 257 and P(9, narrow_chunk=2).n_chunks == 9 * 6
+    # ---- the exponent role: one index per lane needs nm >= 4, mirrored pairs nm >= 8 (smaller nm: shapes that only get a verdict), three wavefronts from exp_w3_min_nm
+    assert [P(3, n=n).exp_form for n in (2, 4, 8)] == [FOUR, SINGLE, SINGLE] and [P(3, n=n, exp_single=0).exp_form for n in (4, 8)] == [FOUR, PAIRS]
+    assert P(3, exponent_pairs=0, exp_single=0).exp_form == FOUR and P(300, split_stage3=1).exp_form == PAIRS
+    assert [P(300, n=64, m=m, split_stage3=1).exp_w3 for m in (8, 16)] == [0, 1] and P(300, n=64, m=8, split_stage3=1, exp_w3_min_nm=512).exp_w3 == 1
+    assert P(300, n=64, m=16).exp_w3 == 0 and P(300, n=64, m=16, split_stage3=1, exponent_pairs=0).exp_w3 == 0
+    # ---- the combined check: buckets from bucket_min_terms terms (default 32768) of nbatch x U
+    assert [P(nb, rlc=1, bucket_min_terms=33).rlc_bucket for nb in (2, 3)] == [0, 1] and [P(nb, rlc=1).rlc_bucket for nb in (2978, 2979)] == [0, 1]
+    assert P(3, bucket_min_terms=33).rlc_bucket == 0
+    # ---- combined checks and shape verdicts: never wide, never a narrow walk, never the split scalar role
+    for nb in (1, 300, 5000):
+        for kw in ({"rlc": 1}, {"n": 12}):
+            p = P(nb, split_stage3=1, **kw)
+            assert (p.forms & WIDE, p.narrow_walk, p.coop_split, p.narrow_hi, p.fused_finish) == (0, 0, 0, 0, 0), (nb, kw)
+        assert P(nb, n=12).scripted == 0 and P(nb, rlc=1).nsplit1 >= 8 and P(nb).nsplit1 == 0
+    assert P(300, split_stage3=1).forms & WIDE and P(300, split_stage3=1, second_stream=1).forms == P(300, split_stage3=1, horner_lanes=1, second_stream=1).forms == WIDE
+    # ---- what a lane of the pool reserves beyond the widest chain's own arena: the narrow chains' smaller chunks (256 x ceil(11 / 8) rows of 64 x 160 bytes)
+    assert P(256).arena_reserve == P(256).arena_need and P(257).arena_reserve - P(257).arena_need == 256 * 2 * 64 * 160
+    assert P(257, horner_lanes=4).arena_reserve == P(257, horner_lanes=4).arena_need
+    assert P(3).off_res1 == 0 and P(3, rlc=1).off_res1 > P(3, rlc=1).off_digits and P(3, nseg=17).arena_need > P(3, nseg=16).arena_need == P(3).arena_need
+    assert P(3, nseg=2, nlabels=2).arena_need == P(3).arena_need + 512 and P(3, nseg=2, nlabels=1).arena_need == P(3).arena_need
+    # ---- 32-bit counts: 64 x nbatch x U, generator terms x nbatch, workgroups of the walk
+    lim = (1 << 31) - 1
+    assert [P(nb).refused for nb in (lim // 64 // 11, lim // 64 // 11 + 1)] == [0, 1]                                    # U = 11
+    assert [P(nb, n=64, m=16).refused for nb in (lim // 64 // 40, lim // 64 // 40 + 1)] == [0, 1]                         # U = 40
+    assert lim // 4098 < lim // 64 // 58 and [P(nb, n=64, m=32).refused for nb in (lim // 4098, lim // 4098 + 1)] == [0, 1]   # 2 x 64 x 32 + 2 generator terms
+    assert [P(nb, fixed_splits=1 << 22).refused for nb in (64 * 511, 64 * 511 + 1)] == [0, 1]                            # 512 workgroups of proofs x 2^22 splits
+
+
+def test_proof_length_and_shape_rules_have_one_copy():
+    """rp_classify (csrc/bpgpu.hip): the length-only part of from_bytes, then verify_multiple_with_rng's parameter checks in the reference's order
+    -- Bitsize, GeneratorsLength, n m == 2^k -- and 'unsupported' for a good shape above 2^16.  The rows are the inputs at which the three
+    former copies of these rules computed k differently: (len - 7*32) / 32 - 2 in halves, len / 32 - 9 in halves, (len - 9*32) / 64."""
+    VER, FMT, BITS, GENS = 1, 2, 3, 4
+    rows = [
+        # (n, m, proof_len, capacities) -> (all_verdict, shape_verdict, k, unsupported)
+        ((8, 1, 7 * 32, (8, 1)), (FMT, 0, 0, 0)),
+        ((8, 1, 8 * 32, (8, 1)), (FMT, 0, 0, 0)),
+        ((8, 1, 9 * 32, (8, 1)), (0, VER, 0, 0)),            # k = 0: well-formed, 8 != 2^0
+        ((8, 1, 10 * 32, (8, 1)), (FMT, 0, 0, 0)),           # an odd count of (L, R) elements
+        ((8, 1, 14 * 32, (8, 1)), (FMT, 0, 0, 0)),
+        ((8, 1, 15 * 32 - 1, (8, 1)), (FMT, 0, 0, 0)),
+        ((8, 1, 15 * 32, (8, 1)), (0, 0, 3, 0)),
+        ((8, 1, 0, (8, 1)), (FMT, 0, 0, 0)),
+        ((8, 1, (9 + 62) * 32, (8, 1)), (0, VER, 31, 0)),    # k = 31 parses
+        ((8, 1, (9 + 64) * 32, (8, 1)), (FMT, 0, 0, 0)),     # k = 32 does not
+        ((64, 2048, (9 + 34) * 32, (64, 2048)), (0, 0, 17, 1)),   # k = BP_RP_MAX_K + 1: a shape to verify, not supported
+        ((64, 2048, (9 + 34) * 32, (64, 1)), (0, GENS, 17, 0)),   # ... reported only behind the reference's own checks
+        ((64, 1024, (9 + 32) * 32, (64, 1024)), (0, 0, 16, 0)),
+        ((8, 0, 9 * 32, (8, 1)), (0, VER, 0, 0)),            # m = 0
+        ((8, 0, 15 * 32, (8, 1)), (0, VER, 3, 0)),
+        ((12, 1, 15 * 32, (8, 1)), (0, BITS, 3, 0)),         # Bitsize before GeneratorsLength
+        ((16, 1, 15 * 32, (8, 1)), (0, GENS, 3, 0)),         # GeneratorsLength before the product
+        ((8, 2, 15 * 32, (8, 1)), (0, GENS, 3, 0)),
+        ((16, 1, 15 * 32, (16, 1)), (0, VER, 3, 0)),
+        ((12, 1, 14 * 32, (8, 1)), (FMT, 0, 0, 0)),          # the format verdict before everything
+    ]
+    for (n, m, plen, caps), want in rows:
+        p = _chain_plan(1, n=n, m=m, proof_len=plen, caps=caps)
+        assert (p.all_verdict, p.shape_verdict, p.k if not p.all_verdict else 0, p.unsupported) == want, (n, m, plen, caps)
+
+
 def test_window_pair_policy_for_two_shapes_under_one_budget():
     """bpgpu_gens_add_shape's choice is plain host logic (pick_window_pair, bpgpu.hip): the pair of windows that minimises
     nwin(W1) / nwin(W1 alone) + nwin(W2) / nwin(W2 alone) among those whose two tables fit the budget together."""
